@@ -7,7 +7,8 @@ the int8 heads stay on their rank unless --gather-heads).  Weak scaling: every r
 N=1, configs[2] = 32768 frames at N=8).  The timed loop rotates through 8 distinct input batches (308 MB per rank, more than
 the 256 MB Infinity Cache), so the input bytes really come from HBM.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5            (the headline line only; --dump-outputs DIR also writes the last step's outputs)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     (+ kernel alone, roofline, one-stream rate, oracle checks, CPU baseline, PCIe, side configurations)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...          (no launcher: starts the N ranks itself as a child torch.distributed.run, see self_launch)
 """
@@ -164,6 +165,31 @@ def event_time_ms(stream, fn, iters):
     e1.record(stream)
     torch.cuda.synchronize()
     return float(e0.elapsed_time(e1)) / iters
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, heads, dets, counts, cap):
+    """--dump-outputs: what a caller of the timed path receives from one step, as DIR/<name>.npy --
+      heads.npy       [n, 7, 7, 18] float32, the int8 heads
+      detections.npy  [n, cap, 10] float64, one column per field of a detection record (DET_DTYPE order: frame, anchor, row, col, q_conf, conf,
+                      x1, y1, x2, y2); the slots beyond a frame's count are never written by the kernel and are zero here
+      counts.npy      [n] float64, each frame's true detection count (it may exceed cap)
+    Above DUMP_BUDGET_BYTES in all, a fixed, seeded sample of the frames is kept and frame_index.npy names them."""
+    n = heads.shape[0]
+    dets = dets.copy()
+    dets[np.arange(cap)[None, :] >= np.minimum(counts, cap)[:, None]] = 0
+    rec = np.stack([dets[f].astype(np.float64) for f in dets.dtype.names], axis=-1)
+    out = {"heads": heads.astype(np.float32), "detections": rec, "counts": counts.astype(np.float64)}
+    per_frame = sum(a[0].nbytes for a in out.values()) + 8
+    if per_frame * n > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET_BYTES // per_frame, replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["frame_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def settle(fn, ms):
@@ -355,7 +381,7 @@ def main():
     ap.add_argument("--streams", type=int, default=2, choices=(1, 2),
                     help="launch streams consecutive steps alternate between (default 2: the next step's workgroups start on CUs the previous launch "
                          "has drained, which hides the ~6.6 us of ramp / drain / dispatch gap a launch costs on one stream: tools/probe/batch_rate.py, two_stream.py)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 160x160 and fp16 side configurations")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the 160x160 and fp16 side configurations")
     ap.add_argument("--only-secondary", choices=sorted(SECONDARY), default=None,
                     help="run ONLY this side configuration (after the same clock settle) and print its line: the command the rocprofv3 "
                          "summaries of the secondaries are taken on (tools/profile_secondary.sh), N = 1 only")
@@ -374,6 +400,13 @@ def main():
                          "kernels, the metric's definition (default); ties_up = dense convs as ruy rounds them (the default resolver of tflite_prediction.py:23); "
                          "same kernels, other constants -- every check of this run then compares with the oracle's statement of THAT variant")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the real path) or gloo (rehearsal of the N>1 code path: ranks may share one GPU, collectives go through host copies)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the kernel timed alone and the roofline figures, the one-stream rate, the check steps against "
+                         "the oracle, the all-gather checks at N > 1, the CPU baseline, the host-buffer (PCIe) rates and the side configurations.  Without it "
+                         "a run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0's heads, detection records and counts) as DIR/<name>.npy "
+                         "in float32 / float64; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -496,8 +529,9 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     ev_begin.record(stream)
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     drain()
     for s_other in streams[1:]:
         stream.wait_stream(s_other)         # the closing event covers the launches of every stream
@@ -511,6 +545,37 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     region_ms = float(ev_begin.elapsed_time(ev_end)) / args.steps
+
+    value = n_total * args.steps / elapsed
+    exch = (f" + RCCL all-gather of detection records (cap {cap}{', 12-byte wire form' if args.compact_records else ''}) and counts" + (" and heads" if args.gather_heads else "")
+            + (f", one collective per {args.gather_every} steps" if args.gather_every > 1 else "")) if dist_on else ""
+    line = {
+        "metric": "images/sec int8 YOLO-face 56x56", "value": round(value, 1), "unit": "images/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int8", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: batch=4096 int8 YOLO-face 56x56x3 frames per GPU, fused LDS-resident "
+                               "forward + GPU box decode" + exch,
+                   "frames_per_gpu": n, "global_batch": n_total, "frame_bytes_in": 9408, "frame_bytes_out": 882,
+                   "clock_settle_ms": round(settled_ms, 1), "input_batches_rotated": NB, "input_bytes_resident": NB * n * 9408,
+                   "kernel": net.kernel_name, "kernel_source_hash": kernel_source_hash(), "requant_rounding": args.requant_rounding,
+                   "parallelism": f"batch-shard x{world}, all-gather of detections" if dist_on else "single GPU",
+                   "exchange_bytes_per_rank_per_step": rec_bytes if dist_on else 0, "gather_every": args.gather_every,
+                   "collectives_issued": ex.collectives, "launch_streams": S,
+                   **({"rehearsal": "--rccl-one-rank: the N > 1 code path in a ONE-rank RCCL group (not a multi-GPU measurement)"} if args.rccl_one_rank else {})},
+    }
+    # the last timed step's outputs, before anything below launches into the same buffers
+    if args.dump_outputs and rank == 0:
+        d_dets, d_counts = ex.views(ex.local[last.i], 0, last.k)
+        dump_outputs(args.dump_outputs, ex.heads(last).view(torch.int8).view(n, 7, 7, 18).cpu().numpy(),
+                     d_dets.cpu().numpy().view(yf.DET_DTYPE).reshape(n, cap), d_counts.cpu().numpy(), cap)
+    if not args.full:       # the headline figure is complete; everything else is --full's
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     kernel_ms = region_ms
     if dist_on or S > 1:  # the timed region above also holds the collectives / overlaps consecutive launches: time the kernel ALONE -- one stream, same
         kernel_ms = event_time_ms(stream, settle_launch, 100)      # inputs, back to back; with one stream and one rank the timed region is that already
@@ -594,24 +659,7 @@ def main():
 
     fail = None
     if rank == 0:
-        value = n_total * args.steps / elapsed
-        exch = (f" + RCCL all-gather of detection records (cap {cap}{', 12-byte wire form' if args.compact_records else ''}) and counts" + (" and heads" if args.gather_heads else "")
-                + (f", one collective per {args.gather_every} steps" if args.gather_every > 1 else "")) if dist_on else ""
-        line = {
-            "metric": "images/sec int8 YOLO-face 56x56", "value": round(value, 1), "unit": "images/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int8", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: batch=4096 int8 YOLO-face 56x56x3 frames per GPU, fused LDS-resident "
-                                   "forward + GPU box decode" + exch,
-                       "frames_per_gpu": n, "global_batch": n_total, "frame_bytes_in": 9408, "frame_bytes_out": 882,
-                       "clock_settle_ms": round(settled_ms, 1), "input_batches_rotated": NB, "input_bytes_resident": NB * n * 9408,
-                       "check_steps": n_check_steps,
-                       "kernel": net.kernel_name, "kernel_source_hash": kernel_source_hash(), "requant_rounding": args.requant_rounding,
-                       "parallelism": f"batch-shard x{world}, all-gather of detections" if dist_on else "single GPU",
-                       "exchange_bytes_per_rank_per_step": rec_bytes if dist_on else 0, "gather_every": args.gather_every,
-                       "collectives_issued": ex.collectives, "launch_streams": S,
-                       **({"rehearsal": "--rccl-one-rank: the N > 1 code path in a ONE-rank RCCL group (not a multi-GPU measurement)"} if args.rccl_one_rank else {})},
-        }
+        line["config"].update(check_steps=n_check_steps, collectives_issued=ex.collectives)
         achieved = n * ALGO_BYTES_PER_FRAME / (kernel_ms * 1e-3) / 1e9
         prof, why = profile_counters(net.kernel_name)
         line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",

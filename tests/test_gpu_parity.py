@@ -1248,7 +1248,7 @@ def test_bench_two_ranks_exchange_detections(tmp_path):
     import json
     import sys
     # plain `python bench.py --gpus 2`: bench.py starts its own ranks (child torch.distributed.run) and relays rank 0's line
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -1268,7 +1268,7 @@ def test_bench_two_ranks_gather_heads_and_a_failing_rank():
     import json
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd + ["--gather-heads"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -1299,7 +1299,7 @@ def test_bench_four_ranks_on_one_gpu_preflight_for_the_eight_gpu_run():
     import json
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--input-batches", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--input-batches", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1324,7 +1324,7 @@ def test_the_bench_line_carries_its_own_context():
     and buffer, each compared with the oracle."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-secondary"], cwd=ROOT, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-secondary"], cwd=ROOT, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -1335,6 +1335,36 @@ def test_the_bench_line_carries_its_own_context():
     assert cb["cores"] == min(cb["affinity_cores"], 16) and cb["all_cores_threads"] == cb["affinity_cores"] and cb["all_cores_images_per_s"] > 0
     assert line["config"]["check_steps"] == 2
     assert line["roofline"]["kernel_ms"] > 0 and line["roofline"]["frac"] > 0
+
+
+def test_the_plain_bench_line_and_its_dumped_outputs(oracle, golden, tmp_path):
+    """`bench.py --steps K --warmup W` without --full prints the headline line only, and --dump-outputs DIR writes what the last timed step computed.
+    With one input batch every step runs the seeded batch that holds the golden frames: the dumped heads equal the golden heads and the oracle's, and
+    the dumped counts and records equal the oracle's decode of those heads."""
+    import json
+    import sys
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--input-batches", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == "images/sec int8 YOLO-face 56x56" and line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "int8"
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 4096 / line["ms_per_step"] * 1e3) < 1e-3 * line["value"]
+    assert not {"cpu_baseline", "secondary", "roofline", "pipelining", "parity"} & set(line)          # --full's
+    heads, dets, counts = (np.load(out / f"{name}.npy") for name in ("heads", "detections", "counts"))
+    assert heads.dtype == np.float32 and heads.shape == (4096, 7, 7, 18) and dets.shape == (4096, 4, 10) and counts.shape == (4096,)
+    x = np.random.default_rng([1, 0, 0]).integers(-128, 128, (4096, 56, 56, 3), dtype=np.int8)     # bench.py's batch 0 of rank 0
+    x[:6] = golden["inputs"]
+    assert np.array_equal(heads[:6], golden["heads"])
+    assert np.array_equal(heads[:512], oracle.run(x[:512]))
+    for f in range(64):
+        want = oracle.decode_py(heads[f].astype(np.int8), f, 1.0, 1.0)
+        assert counts[f] == len(want)
+        kept = [tuple(int(v) for v in d[[1, 2, 3, 4, 6, 7, 8, 9]]) for d in dets[f, :min(4, len(want))]]
+        assert kept == [(w[1], w[2], w[3], w[4], w[6], w[7], w[8], w[9]) for w in want][:4]
+        assert not dets[f, min(4, len(want)):].any()
 
 
 def test_the_bench_step_from_a_pure_c_host():
@@ -1445,7 +1475,7 @@ def test_bench_exchange_through_rccl_in_a_one_rank_group():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rccl-one-rank", "--steps", "5", "--warmup", "2", "--clock-settle-ms", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rccl-one-rank", "--steps", "5", "--warmup", "2", "--clock-settle-ms", "5", "--full"]
     for extra, rec in ([], 4096 * (4 * 28 + 4)), (["--gather-every", "2", "--compact-records"], 4096 * (4 * 12 + 4)):
         r = subprocess.run(cmd + extra, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -514,3 +514,31 @@ def test_profile_summary_separates_overlapped_launches_from_back_to_back_ones(tm
     assert res["trace"]["calls"] == 10 and res["trace"]["avg_ns"] == 140_000
     assert res["trace_overlapped"]["calls"] == 6 and res["trace_overlapped"]["runs"] == 1 and res["trace_overlapped"]["avg_duration_ns"] == 260_000
     assert abs(res["trace_overlapped"]["wall_ns_per_launch"] - (5 * 130_000 + 260_000) / 6) < 1
+
+
+def test_bench_dump_outputs_writes_what_a_caller_receives(tmp_path):
+    """bench.py --dump-outputs: heads as float32, detection records as float64 columns with the never-written slots beyond a frame's count zeroed (stale
+    bytes are not output), counts as float64; an output over the 64 MB budget is cut to a seeded sample of frames, the same one every time."""
+    import importlib
+    bench = importlib.import_module("bench")
+    det = importlib.import_module("stm32h7-yolo_amd").DET_DTYPE
+    rng = np.random.default_rng(7)
+    n, cap = 4096, 4
+    heads = rng.integers(-128, 128, (n, 7, 7, 18), dtype=np.int8)
+    dets = np.zeros((n, cap), det)
+    for f in dets.dtype.names:
+        dets[f] = rng.integers(0, 100, (n, cap))
+    counts = rng.integers(0, 7, n).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), heads, dets, counts, cap)
+    h, d, c = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("heads", "detections", "counts"))
+    assert h.dtype == np.float32 and np.array_equal(h, heads) and c.dtype == np.float64 and np.array_equal(c, counts)
+    assert d.dtype == np.float64 and d.shape == (n, cap, len(det.names))
+    kept = np.arange(cap)[None, :] < np.minimum(counts, cap)[:, None]
+    assert np.array_equal(d[kept], np.stack([dets[f][kept] for f in det.names], axis=-1)) and not d[~kept].any()
+    wide = np.tile(dets, (1, 60))
+    for k in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / k), heads, wide, counts, cap * 60)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 64 << 20 and sorted(os.listdir(tmp_path / "b")) == ["counts.npy", "detections.npy", "frame_index.npy", "heads.npy"]
+    idx = np.load(tmp_path / "b" / "frame_index.npy").astype(int)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_index.npy")) and np.array_equal(np.load(tmp_path / "b" / "heads.npy"), heads[idx])

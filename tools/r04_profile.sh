@@ -18,7 +18,7 @@ for P in $PARTS; do
               bash tools/fp16_pmc.sh lib > $R/fp16_pmc.txt 2>&1 ;;
     f16stage) bash tools/fp16_stage_pmc.sh $R/fp16_stage_pmc.txt ;;
     160)      bash tools/profile_160.sh r04 > $R/160_profile.log 2>&1; cp gpurun_out/prof160/r04/summary.json $R/160_summary.json; cp gpurun_out/prof160/r04/kernel_stats.csv $R/160_kernel_stats.csv ;;
-    bench)    python3 bench.py > $R/bench_line.json 2> $R/bench.err; python3 bench.py --steps 20 --warmup 5 > $R/bench_line_driver_flags.json 2>> $R/bench.err ;;
+    bench)    python3 bench.py --full > $R/bench_line.json 2> $R/bench.err; python3 bench.py --full --steps 20 --warmup 5 > $R/bench_line_driver_flags.json 2>> $R/bench.err ;;
   esac
 done
 echo "== done $(date +%T)"; ls -la $R
