@@ -223,6 +223,10 @@ enum { YF_DECODE_PY = 0,      /* yoloface/tflite/tflite_prediction.py:42-63: anc
  *                         shift breaks ties UPWARD); DEPTHWISE_CONV_2D, LEAKY_RELU, ADD, QUANTIZE keep the reference form.
  *   YF_ROUND_TIES_UP_ALL  every op ties upward.
  *   YF_ROUND_SINGLE       dense CONV_2D with ONE rounding, (acc*M + 2^(30-shift)) >> (31-shift) (ruy's portable path); the rest reference.
+ *   YF_ROUND_FP32         CONV_2D and DEPTHWISE_CONV_2D requantise in float32 as the XNNPACK delegate's qs8 kernels do (the default interpreter may
+ *                         apply that delegate): lrintf((float)acc * fs[c]) + zp_out, fs[c] = (float)((float)(s_in * s_w[c]) / s_out), ties to even;
+ *                         LEAKY_RELU, ADD, QUANTIZE reference.  Runs a third kernel set whose convolutions requantise in float32 (no integer
+ *                         epilogue computes this form): or-ing YF_ROUND_GENERIC_KERNELS into it is invalid.  YF_ROUND_COUNT counts the integer forms only.
  * The rounding lives in the per-channel constants {C64, ZR}, the LeakyReLU / QUANTIZE byte tables and the add tables that ai_network_init builds
  * (csrc/yf_host_prep.c); the four-instruction requantisation of the reference rounding's kernels serves every one of them.  The three roundings whose
  * dense convolutions have NO sign term (ties upward, single rounding) by default run a second set of the same kernels whose dense convolutions
@@ -230,11 +234,11 @@ enum { YF_DECODE_PY = 0,      /* yoloface/tflite/tflite_prediction.py:42-63: anc
  * YF_ROUND_GENERIC_KERNELS into the rounding keeps them on the reference rounding's kernels (same results; for A/B).  Call after ai_network_create, before or after
  * ai_network_init (a ready network waits for its launches, rebuilds its tables from the weights it was initialised with -- which the caller
  * still owns, as on the MCU -- and uploads them); ai_network_create resets the choice to $YF_REQUANT_ROUNDING ("ref", "ties_up",
- * "ties_up_all", "single", each optionally followed by "+generic"; unset = ref) so that an unmodified aiInit() can be steered from outside.  Affects the 56x56 and 160x160 int8
+ * "ties_up_all", "single", each optionally followed by "+generic", or "fp32"; unset = ref) so that an unmodified aiInit() can be steered from outside.  Affects the 56x56 and 160x160 int8
  * paths; the fp16 path has no requantisation.  Returns 0, or -1 with an error latched. */
 #ifndef YF_ROUND_ENUM
 #define YF_ROUND_ENUM
-enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, YF_ROUND_SINGLE = 3, YF_ROUND_COUNT, YF_ROUND_GENERIC_KERNELS = 0x100 };
+enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, YF_ROUND_SINGLE = 3, YF_ROUND_COUNT, YF_ROUND_FP32 = 0x10, YF_ROUND_GENERIC_KERNELS = 0x100 };
 #endif
 YF_API int  yf_network_set_requant_rounding(ai_handle network, int rounding);
 YF_API int  yf_network_get_requant_rounding(ai_handle network);      /* the rounding in force, -1 for an invalid handle */

@@ -30,6 +30,7 @@ YF_DECODE_PY, YF_DECODE_FW, YF_DECODE_FW_HOST = 0, 1, 2
 # rounding of the requantisation step (include/yf_network.h, yf_network_set_requant_rounding)
 YF_ROUND_TFLITE_REF, YF_ROUND_TIES_UP, YF_ROUND_TIES_UP_ALL, YF_ROUND_SINGLE = 0, 1, 2, 3
 YF_ROUND_GENERIC_KERNELS = 0x100      # or-ed into a rounding: keep the reference rounding's four-instruction kernels (A/B against the sign-free kernel set)
+YF_ROUND_FP32 = 0x10                  # float32 requantisation of every conv (the XNNPACK delegate's qs8 arithmetic) on a kernel set of its own; never with 0x100
 
 
 class AiError(ctypes.Structure):
@@ -459,7 +460,7 @@ class Network:
     def set_requant_rounding(self, rounding):
         """Which published rounding of TFLite's requantisation the network computes (YF_ROUND_*; default: the builtin reference kernels).
         Other constants for the same kernels, or -- the roundings without a sign term, by default -- for the kernel set with the three-instruction
-        dense epilogue; before or after init()."""
+        dense epilogue, or -- YF_ROUND_FP32 -- for the kernel set whose convolutions requantise in float32; before or after init()."""
         if self.lib.yf_network_set_requant_rounding(self.handle, int(rounding)) != 0:
             self._raise("yf_network_set_requant_rounding")
         return self

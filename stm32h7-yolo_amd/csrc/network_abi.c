@@ -71,9 +71,10 @@ static int rounding_from_env(void) {
   if (!strcmp(word, "ties_up")) return YF_ROUND_TIES_UP | flags;
   if (!strcmp(word, "ties_up_all")) return YF_ROUND_TIES_UP_ALL | flags;
   if (!strcmp(word, "single")) return YF_ROUND_SINGLE | flags;
+  if (!strcmp(word, "fp32")) return YF_ROUND_FP32 | flags;   /* "fp32+generic" is invalid: no integer-epilogue kernel computes it */
   return -1;                               /* unknown word: ai_network_init fails loudly instead of guessing */
 }
-static int rounding_is_valid(int r) { return r >= 0 && (r & ~YF_ROUND_GENERIC_KERNELS) < YF_ROUND_COUNT; }
+static int rounding_is_valid(int r) { return r == YF_ROUND_FP32 || (r >= 0 && (r & ~YF_ROUND_GENERIC_KERNELS) < YF_ROUND_COUNT); }
 
 /* ------------------------------------------------------------------------------------------------ create / destroy */
 ai_error yf_impl_create(ai_handle* network, const ai_buffer* network_config) {
@@ -151,7 +152,7 @@ ai_bool yf_impl_init(ai_handle network, const ai_network_params* params) {
   }
   if (c->engine) { yf_engine_destroy(c->engine); c->engine = NULL; c->state = ST_CREATED; }
   if (!rounding_is_valid(c->rounding)) {
-    latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, "YF_REQUANT_ROUNDING is none of ref, ties_up, ties_up_all, single (optionally followed by +generic)"); return false;
+    latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, "YF_REQUANT_ROUNDING is none of ref, ties_up, ties_up_all, single (optionally followed by +generic), fp32"); return false;
   }
 
   uint8_t* tables = NULL;
@@ -162,7 +163,7 @@ ai_bool yf_impl_init(ai_handle network, const ai_network_params* params) {
     latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_WEIGHTS, t); return false;
   }
   char etext[400] = "";
-  const int erc = yf_engine_create(c->device, tables, &ix, yf_rounding_signless_dense(c->rounding), &c->engine, etext, sizeof etext);
+  const int erc = yf_engine_create(c->device, tables, &ix, yf_rounding_kernel_set(c->rounding), &c->engine, etext, sizeof etext);
   free(tables);
   if (erc != YF_ENG_OK) { c->engine = NULL; latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK, etext); return false; }
   if (c->cfg_frames || c->cfg_waves) {
@@ -365,7 +366,7 @@ YF_API int yf_network_set_requant_rounding(ai_handle network, int rounding) {
     yf_table_index ix;
     const int prc = yf_prepare_tables_rounding((const uint8_t*)c->bound_weights, c->bound_weights_bytes, rounding, &tables, &ix);
     if (prc != YF_PREP_OK) { latch(c, AI_ERROR_INVALID_STATE, AI_ERROR_CODE_NETWORK_WEIGHTS, "table preparation failed"); return -1; }
-    const int erc = yf_engine_set_tables(c->engine, tables, &ix, yf_rounding_signless_dense(rounding));
+    const int erc = yf_engine_set_tables(c->engine, tables, &ix, yf_rounding_kernel_set(rounding));
     free(tables);
     if (erc != YF_ENG_OK) { latch(c, AI_ERROR_INVALID_STATE, AI_ERROR_CODE_NETWORK, yf_engine_error(c->engine)); return -1; }
   }

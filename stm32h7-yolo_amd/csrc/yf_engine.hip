@@ -43,6 +43,23 @@
 #undef YF_H0
 #undef YF_GENERIC
 #undef YF_RQ3_DENSE
+// ... and a third time with the FLOAT32 requantisation on every convolution, dense and depthwise (yf_kernels.hip.h, rqf): YF_ROUND_FP32, the XNNPACK delegate's
+// arithmetic.  The MFMAs start from the channels' bias' and the epilogue is five VALU instructions.  Namespaces yfx (56x56) and yf160x (160x160).
+#undef YF_STAGE_FN
+#define YF_NS yfx
+#define YF_RQ_FP32 1
+#include "yf_kernels.hip.h"
+#undef YF_NS
+#undef YF_STAGE_FN
+#undef YF_H0
+#define YF_NS yf160x
+#define YF_H0 160
+#define YF_GENERIC 1
+#include "yf_kernels.hip.h"
+#undef YF_NS
+#undef YF_H0
+#undef YF_GENERIC
+#undef YF_RQ_FP32
 #ifdef YF_LAB
 // laboratory: the 56x56 kernel once more, as a dump build that keeps the PRODUCTION stage order (yf_fused56.hip.h, YF_PDUMP) -- per-stage parity of what ships
 #undef YF_STAGE_FN
@@ -144,8 +161,9 @@ __global__ void __launch_bounds__(256) prepare_rgb565_kernel(const uint8_t* __re
 }
 
 typedef void (*fused_fn)(const yf::NetParams);
-struct Variant { int f, nw; bool dump; bool cam; fused_fn fn; size_t lds; size_t park; const char* name; bool prod_order; bool signless; };
-// park: scratch bytes per frame slot of a workgroup; prod_order: the laboratory's dump build in the production stage order; signless: namespace yfu (sign-free dense epilogue)
+struct Variant { int f, nw; bool dump; bool cam; fused_fn fn; size_t lds; size_t park; const char* name; bool prod_order; int kset; };
+// park: scratch bytes per frame slot of a workgroup; prod_order: the laboratory's dump build in the production stage order; kset: the kernel set
+// (yf_rounding_kernel_set): 0 namespace yf (reference rounding's epilogue), 1 yfu (sign-free dense epilogue), 2 yfx (float32 requantisation)
 
 #define YF_VARIANT(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yf::yoloface56_fused<F, NW, DUMP>, yf::lds_bytes<F, NW, DUMP>(), yf::scratch_bytes_per_frame_slot<DUMP>(), \
                                   "yoloface56_fused<F=" #F ",NW=" #NW ">" }
@@ -154,20 +172,26 @@ struct Variant { int f, nw; bool dump; bool cam; fused_fn fn; size_t lds; size_t
 // The product: the batched shape <2,8>, the one-frame-per-workgroup shape <1,8> for small batches, the camera-input form of <2,8> and ONE debug
 // (per-stage dump / stop_stage) build for the per-node observer.  A -DYF_LAB build (make lab) adds the other shapes for tools and tests.
 #define YF_VARIANT_U(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yfu::yoloface56_fused<F, NW, DUMP>, yfu::lds_bytes<F, NW, DUMP>(), yfu::scratch_bytes_per_frame_slot<DUMP>(), \
-                                    "yoloface56_fused<F=" #F ",NW=" #NW ",sign-free dense epilogue>", false, true }
+                                    "yoloface56_fused<F=" #F ",NW=" #NW ",sign-free dense epilogue>", false, 1 }
 #define YF_VARIANT_U_CAM(F, NW) { F, NW, false, true, (fused_fn)yfu::yoloface56_fused<F, NW, false, true>, yfu::lds_bytes<F, NW, false>(), \
-                                  yfu::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input,sign-free dense epilogue>", false, true }
+                                  yfu::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input,sign-free dense epilogue>", false, 1 }
+#define YF_VARIANT_X(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yfx::yoloface56_fused<F, NW, DUMP>, yfx::lds_bytes<F, NW, DUMP>(), yfx::scratch_bytes_per_frame_slot<DUMP>(), \
+                                    "yoloface56_fused<F=" #F ",NW=" #NW ",fp32 requantisation>", false, 2 }
+#define YF_VARIANT_X_CAM(F, NW) { F, NW, false, true, (fused_fn)yfx::yoloface56_fused<F, NW, false, true>, yfx::lds_bytes<F, NW, false>(), \
+                                  yfx::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input,fp32 requantisation>", false, 2 }
 const Variant k_variants[] = {
   YF_VARIANT(2, 8, false), YF_VARIANT(1, 8, false), YF_VARIANT(2, 8, true), YF_VARIANT_CAM(2, 8),
   // ... and the same four with the three-instruction epilogue on the dense convolutions, for the roundings without a sign term
   YF_VARIANT_U(2, 8, false), YF_VARIANT_U(1, 8, false), YF_VARIANT_U(2, 8, true), YF_VARIANT_U_CAM(2, 8),
+  // ... and with the float32 requantisation on every convolution (YF_ROUND_FP32)
+  YF_VARIANT_X(2, 8, false), YF_VARIANT_X(1, 8, false), YF_VARIANT_X(2, 8, true), YF_VARIANT_X_CAM(2, 8),
 #ifdef YF_LAB
   YF_VARIANT(1, 4, false), YF_VARIANT(2, 4, false), YF_VARIANT(4, 8, false), YF_VARIANT(2, 4, true),
   // the dump build in the production stage order (same NetParams layout; selected by YF_LAB_DUMP_PROD_ORDER=1 as the engine's dump variant)
   { 2, 8, true, false, (fused_fn)yfpd::yoloface56_fused<2, 8, true>, yfpd::lds_bytes<2, 8, true>(), yfpd::scratch_bytes_per_frame_slot<true>(),
     "yoloface56_fused<F=2,NW=8,dump in production order>", true },
   { 2, 8, true, false, (fused_fn)yfpdu::yoloface56_fused<2, 8, true>, yfpdu::lds_bytes<2, 8, true>(), yfpdu::scratch_bytes_per_frame_slot<true>(),
-    "yoloface56_fused<F=2,NW=8,dump in production order,sign-free dense epilogue>", true, true },
+    "yoloface56_fused<F=2,NW=8,dump in production order,sign-free dense epilogue>", true, 1 },
 #endif
 };
 
@@ -177,8 +201,9 @@ struct yf_engine {
   int device = 0;
   int cus = 0;
   size_t lds_per_cu = 0;                         // hipDeviceProp_t::maxSharedMemoryPerMultiProcessor
-  int band_wgs_per_cu[2][3] = {{1, 1, 1}, {1, 1, 1}};   // resident workgroups per CU of the three banded 160x160 kernels on this device (occupancy query at creation), per kernel set
-  bool signless = false;                         // the tables are built for -- and the launches take -- the kernels with the sign-free dense epilogue (namespaces yfu / yf160u)
+  int band_wgs_per_cu[3][3] = {{1, 1, 1}, {1, 1, 1}, {1, 1, 1}};   // resident workgroups per CU of the three banded 160x160 kernels on this device (occupancy query at creation), per kernel set
+  int kset = 0;                                  // the kernel set the tables are built for and the launches take (Variant::kset): 1 the sign-free dense epilogue (namespaces yfu /
+                                                 // yf160u), 2 the float32 requantisation (yfx / yf160x)
 #ifdef YF_LAB
   int grid_div = 1;                              // laboratory (YF_LAB_GRID_DIV): a launch takes 1 / grid_div of the resident grid (launch-policy what-ifs: several launches side by side)
   int fail_next_launch = 0;                      // laboratory: the next k fused launches get an invalid grid (tests the scratch lease on the failure path)
@@ -264,8 +289,8 @@ struct Downloader {
     (e_)->err = std::string(#call) + ": " + hipGetErrorString(rc_); return YF_ENG_ERR_HIP; } } while (0)
 
 static const Variant* shape_for(const yf_engine* e, long n);
-static const Variant* find_variant(int f, int nw, bool dump, bool cam = false, bool prod_order = false, bool signless = false) {
-  for (const Variant& v : k_variants) if (v.f == f && v.nw == nw && v.dump == dump && v.cam == cam && v.prod_order == prod_order && v.signless == signless) return &v;
+static const Variant* find_variant(int f, int nw, bool dump, bool cam = false, bool prod_order = false, int kset = 0) {
+  for (const Variant& v : k_variants) if (v.f == f && v.nw == nw && v.dump == dump && v.cam == cam && v.prod_order == prod_order && v.kset == kset) return &v;
   return nullptr;
 }
 
@@ -273,15 +298,18 @@ static const Variant* find_variant(int f, int nw, bool dump, bool cam = false, b
 // dump build that keeps the production stage order instead (shape <2,8> only)
 static const Variant* dump_variant_for(const yf_engine* e, int f, int nw) {
 #ifdef YF_LAB
-  if (e->dump_prod_order) { const Variant* v = find_variant(f, nw, true, false, true, e->signless); if (v) return v; }
+  if (e->dump_prod_order) {                      // (none of the float32 set: the dump entry points refuse rather than run the staged-order build in its place)
+    const Variant* v = find_variant(f, nw, true, false, true, e->kset);
+    if (v || e->kset == 2) return v;
+  }
 #endif
-  return find_variant(f, nw, true, false, false, e->signless);
+  return find_variant(f, nw, true, false, false, e->kset);
 }
 // the engine's three kernel shapes for a configuration (f, nw; 0 = the automatic choice), in the kernel set its tables are built for
 static void select_variants(yf_engine* e, int f, int nw, bool automatic) {
-  e->var = find_variant(f, nw, false, false, false, e->signless);
+  e->var = find_variant(f, nw, false, false, false, e->kset);
   e->var_dump = dump_variant_for(e, f, nw);
-  e->var_small = automatic ? find_variant(1, 8, false, false, false, e->signless) : nullptr;
+  e->var_small = automatic ? find_variant(1, 8, false, false, false, e->kset) : nullptr;
 }
 
 #ifdef YF_LAB
@@ -305,19 +333,22 @@ struct BandKernel { const void* fn; const char* name; unsigned threads; size_t l
 #define YF_K1_NW 8
 #endif
 #define YF_K1_NW_ YF_K1_NW
-static const BandKernel k_band_fused[2][3] = {   // round 3: K2 and K3 fused (three tensors cross HBM instead of five); [1]: the set with the sign-free dense epilogue
+static const BandKernel k_band_fused[3][3] = {   // round 3: K2 and K3 fused (three tensors cross HBM instead of five); [1]: the set with the sign-free dense epilogue, [2]: float32 requantisation
   {{(const void*)yf160::band::band_k1<YF_K1_NW_>, "band_k1", YF_K1_NW_ * 64, (size_t)yf160::band::K1_LDS, yf160::band::K1_BANDS},
    {(const void*)yf160::band::band_k23<8>, "band_k23", 512, (size_t)yf160::band::K23_LDS, yf160::band::K23_BANDS},
    {(const void*)yf160::band::band_k4<8>,  "band_k4", 512,  (size_t)yf160::band::K4_LDS, 1}},
   {{(const void*)yf160u::band::band_k1<YF_K1_NW_>, "band_k1 (sign-free dense epilogue)", YF_K1_NW_ * 64, (size_t)yf160u::band::K1_LDS, yf160u::band::K1_BANDS},
    {(const void*)yf160u::band::band_k23<8>, "band_k23 (sign-free dense epilogue)", 512, (size_t)yf160u::band::K23_LDS, yf160u::band::K23_BANDS},
    {(const void*)yf160u::band::band_k4<8>,  "band_k4 (sign-free dense epilogue)", 512,  (size_t)yf160u::band::K4_LDS, 1}},
+  {{(const void*)yf160x::band::band_k1<YF_K1_NW_>, "band_k1 (fp32 requantisation)", YF_K1_NW_ * 64, (size_t)yf160x::band::K1_LDS, yf160x::band::K1_BANDS},
+   {(const void*)yf160x::band::band_k23<8>, "band_k23 (fp32 requantisation)", 512, (size_t)yf160x::band::K23_LDS, yf160x::band::K23_BANDS},
+   {(const void*)yf160x::band::band_k4<8>,  "band_k4 (fp32 requantisation)", 512,  (size_t)yf160x::band::K4_LDS, 1}},
 };
 static int launch160_banded(yf_engine* e, const yf160::band::Params& prm, hipStream_t s) {
   for (int i = 0; i < 3; ++i) {
-    const BandKernel& k = k_band_fused[e->signless][i];
+    const BandKernel& k = k_band_fused[e->kset][i];
     const long jobs = prm.n * k.jobs_per_frame;
-    const long full = (long)e->cus * e->band_wgs_per_cu[e->signless][i];  // persistent grid: every workgroup resident, jobs grid-strided
+    const long full = (long)e->cus * e->band_wgs_per_cu[e->kset][i];  // persistent grid: every workgroup resident, jobs grid-strided
     const unsigned grid = (unsigned)(jobs < full ? jobs : full);
     void* args[] = {(void*)&prm};
     const hipError_t rc = hipLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, k.lds, s);
@@ -338,7 +369,7 @@ static bool layout_is_the_compiled_plan(const yf_table_index* ix) {
 
 extern "C" {
 
-int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index* ix, int signless_dense, yf_engine** out, char* err, size_t errlen) {
+int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index* ix, int kernel_set, yf_engine** out, char* err, size_t errlen) {
   auto fail = [&](const std::string& m, int code) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; };
   if (!table_blob || !ix || !out) return fail("bad arguments", YF_ENG_ERR_ARG);
   int ndev = 0;
@@ -397,7 +428,7 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
     *wgs_per_cu = occ > 0 ? occ : 1;                          // a property of THIS engine's device (round 5 wrote it into the process-wide kernel table)
     return YF_ENG_OK;
   };
-  for (int u = 0; u < 2; ++u)
+  for (int u = 0; u < 3; ++u)
     for (int i = 0; i < 3; ++i) { const int r = prepare_band(k_band_fused[u][i], &e->band_wgs_per_cu[u][i]); if (r != YF_ENG_OK) return r; }
   { const char* ck = getenv("YF_160_CHUNK"); if (ck && atol(ck) > 0) e->chunk160 = atol(ck); }
 #ifdef YF_LAB
@@ -420,22 +451,22 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
   }
   if ((rc = hipHostMalloc(&e->h_small_in, (size_t)ZERO_COPY_N * 9408, hipHostMallocMapped)) != hipSuccess ||
       (rc = hipHostMalloc(&e->h_small_out, (size_t)ZERO_COPY_N * 882, hipHostMallocMapped)) != hipSuccess) return bail(rc, "hipHostMalloc(pinned staging)");
-  e->signless = signless_dense != 0;
+  e->kset = kernel_set;
   select_variants(e, 2, 8, true);
   *out = e;
   return YF_ENG_OK;
 }
 
-int yf_engine_set_tables(yf_engine* e, const uint8_t* table_blob, const yf_table_index* ix, int signless_dense) {
+int yf_engine_set_tables(yf_engine* e, const uint8_t* table_blob, const yf_table_index* ix, int kernel_set) {
   if (!e || !table_blob || !ix) return YF_ENG_ERR_ARG;
-  if (!find_variant(e->var->f, e->var->nw, false, false, false, signless_dense != 0)) { e->err = "the configured kernel shape has no build for this rounding"; return YF_ENG_ERR_VARIANT; }
+  if (!find_variant(e->var->f, e->var->nw, false, false, false, kernel_set)) { e->err = "the configured kernel shape has no build for this rounding"; return YF_ENG_ERR_VARIANT; }
   if (!layout_is_the_compiled_plan(ix)) { e->err = "table blob layout differs from the layout compiled into the kernels"; return YF_ENG_ERR_ARG; }
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipDeviceSynchronize());             // launches in flight read the old constants to their end
   HIPCHK(e, hipMemcpy(e->d_tab, table_blob, ix->total_bytes, hipMemcpyHostToDevice));
   e->ix = *ix;
   const bool automatic = e->var_small != nullptr;
-  e->signless = signless_dense != 0;             // the tables and the kernels that read them change together (the device is idle here)
+  e->kset = kernel_set;                          // the tables and the kernels that read them change together (the device is idle here)
   select_variants(e, e->var->f, e->var->nw, automatic);
   return YF_ENG_OK;
 }
@@ -485,7 +516,7 @@ int yf_engine_configure(yf_engine* e, int frames_per_wg, int waves_per_wg) {
     return YF_ENG_OK;
   }
   const int f = frames_per_wg > 0 ? frames_per_wg : e->var->f, nw = waves_per_wg > 0 ? waves_per_wg : e->var->nw;
-  if (!find_variant(f, nw, false, false, false, e->signless)) { e->err = "no such kernel variant"; return YF_ENG_ERR_VARIANT; }
+  if (!find_variant(f, nw, false, false, false, e->kset)) { e->err = "no such kernel variant"; return YF_ENG_ERR_VARIANT; }
   select_variants(e, f, nw, false);              /* an explicitly configured shape runs every batch size; debug build of the SAME shape, or none: the dump / stage-timing
                                                     entry points refuse instead of running another shape */
   return YF_ENG_OK;
@@ -578,7 +609,7 @@ int yf_engine_run_camera_device(yf_engine* e, const void* d_rgb565, void* d_out,
   if (d_dets && (!d_counts || cap <= 0 || (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST))) return YF_ENG_ERR_ARG;
   if (((uintptr_t)d_rgb565 & 15) != 0) { e->err = "camera frames must be 16-byte aligned"; return YF_ENG_ERR_ARG; }
   HIPCHK(e, hipSetDevice(e->device));
-  const Variant* v = find_variant(e->var->f, e->var->nw, false, true, false, e->signless);
+  const Variant* v = find_variant(e->var->f, e->var->nw, false, true, false, e->kset);
   if (!v) { e->err = "no camera-input build of the configured kernel shape"; return YF_ENG_ERR_VARIANT; }
   const DecodeArgs dec = {d_dets, d_counts, cap, mode, w_scale, h_scale};
   return launch(e, v, d_rgb565, d_out, nullptr, n, (hipStream_t)stream, -1, d_dets ? &dec : nullptr);
@@ -735,6 +766,8 @@ int yf_engine_run_device_160(yf_engine* e, const void* d_in, void* d_out, long n
     int rc;
 #ifdef YF_LAB
     if (e->layerwise160) {
+      // the layer-by-layer kernels (yf160::generic_stage_kernel) requantise with the reference rounding's integer epilogue: float32 tables would give wrong heads
+      if (e->kset == 2) { e->err = "the layer-by-layer 160x160 form has no float32-requantisation build (YF_160_LAYERWISE with YF_ROUND_FP32)"; return YF_ENG_ERR_VARIANT; }
       yf160::GenParams prm;
       prm.in = (const int8_t*)d_in + done * yf160::IN_FRAME_BYTES;
       prm.out = (int8_t*)d_out + done * yf160::OUT_FRAME_BYTES;

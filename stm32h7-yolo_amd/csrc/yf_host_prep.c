@@ -15,7 +15,8 @@
  * the default is TFLite's builtin REFERENCE kernels (RoundingDivideByPOT: ties away from zero) = SURVEY.md 8(c).3's definition
  * of "the tflite int8 reference"; the reference's script builds its interpreter with the default resolver
  * (yoloface/tflite/tflite_prediction.py:23), whose per-channel int8 CONV_2D goes through ruy -- ties upward, or one single
- * rounding on ruy's portable path.  Every form is a different set of CONSTANTS for the same kernels (yf_tables.h, yf_pass).
+ * rounding on ruy's portable path.  Every integer form is a different set of CONSTANTS for the same kernels (yf_tables.h, yf_pass); the float32
+ * requantisation of the XNNPACK delegate (YF_ROUND_FP32) puts fs, bias' and the rounding constant in the same slots for a kernel set of its own.
  */
 #include "yf_host_prep.h"
 #include "gen/yf_model_gen.h"
@@ -74,6 +75,8 @@ int32_t yf_mbqm_form(int32_t x, int32_t mult, int shift, int form) {
 /* the form each op family takes under a rounding mode of the public interface */
 static int form_dense(int rounding) { return rounding == YF_ROUND_TIES_UP || rounding == YF_ROUND_TIES_UP_ALL ? RQ_UP : rounding == YF_ROUND_SINGLE ? RQ_SINGLE : RQ_REF; }
 static int form_other(int rounding) { return rounding == YF_ROUND_TIES_UP_ALL ? RQ_UP : RQ_REF; }
+/* YF_ROUND_FP32: the conv channels' constants are those of the float32 epilogue (yf_tables.h, yf_pass), not of a fixed-point form */
+enum { RQ_FP32 = 3 };
 
 static int8_t sat8(int32_t v) { return (int8_t)(v < -128 ? -128 : v > 127 ? 127 : v); }
 
@@ -124,10 +127,33 @@ static void build_c64(long long off, int32_t m, int rs, int form, int z, uint32_
   out[0] = (uint32_t)c; out[1] = (uint32_t)(c >> 32);
 }
 
+/* The float32 epilogue's constants (yf_tables.h, yf_pass, FP32) of a channel with accumulator bound |acc| <= acc_max:
+ *   fs = fl32(fl32(s_in * s_w) / s_out)   (two float32 operations as XNNPACK's qs8 requantisation states them: no double, no contraction)
+ * The kernel's rounding (p + 1.5 * 2^23) is round-to-nearest-even of p only while |p| < 2^22; the host asks for |acc| * fs < 2^21. */
+static int build_chan_fp32(float s_in, float s_w, float s_out, long long bias2, long long acc_max, int z, yf_pass* p, int j) {
+  const volatile float num = s_in * s_w;
+  const volatile float fs = num / s_out;
+  if (!(fs > 0.0f) || !((double)acc_max * (double)fs < 2097152.0)) return YF_PREP_ERR_SHIFT_RANGE;
+  const float f = fs;
+  memcpy(&p->mult2[j], &f, 4);
+  p->zr[j] = (uint32_t)(int32_t)bias2;
+  p->c64[j][0] = p->c64[j][1] = 0;
+  p->rshift[j] = (int32_t)(0x4B400000u - (uint32_t)z);
+  return 0;
+}
+
 /* Channel j of pass p.  abs_w = sum |w| (bounds the accumulator).  Returns 0 or an error code. */
 static int build_chan(const yf_conv_desc* d, const uint8_t* blob, int ch, int32_t sum_w, int32_t abs_w, yf_pass* p, int j, int form, int fold) {
   const float s_in = t_scale(d->t_in), s_out = t_scale(d->t_out);
   const float s_w = f32_from_bits(d->wscale_bits[ch]);
+  if (form == RQ_FP32) {
+    int32_t bias;
+    memcpy(&bias, blob + d->b_off + 4 * (size_t)ch, 4);
+    const long long bias2 = (long long)bias - (long long)t_zp(d->t_in) * sum_w;
+    const long long acc_max = (bias2 < 0 ? -bias2 : bias2) + 255ll * abs_w;
+    if (acc_max >= (1ll << 29)) return YF_PREP_ERR_SHIFT_RANGE;
+    return build_chan_fp32(s_in, s_w, s_out, bias2, acc_max, t_zp(d->t_out) + 128, p, j);
+  }
   int32_t m; int sh;
   yf_quantize_multiplier((double)s_in * (double)s_w / (double)s_out, &m, &sh);
   if (sh > -1 || sh < -20) return YF_PREP_ERR_SHIFT_RANGE;      /* fused epilogue needs 1 <= rshift <= 20 */
@@ -144,7 +170,11 @@ static int build_chan(const yf_conv_desc* d, const uint8_t* blob, int ch, int32_
   return 0;
 }
 /* padding channel of a pass (cout not a multiple of 4): harmless constants, the byte it produces is never read */
-static void pad_chan(yf_pass* p, int j) {
+static void pad_chan(yf_pass* p, int j, int form) {
+  if (form == RQ_FP32) {                     /* fs = 0, bias' = 0: every output byte 128 */
+    p->mult2[j] = 0; p->zr[j] = 0; p->c64[j][0] = p->c64[j][1] = 0; p->rshift[j] = (int32_t)(0x4B400000u - 128u);
+    return;
+  }
   p->mult2[j] = ((1u << 30) + 1u) << 1; p->rshift[j] = 1;
   build_c64(-(long long)YF_ACC_OFFSET, (1 << 30) + 1, 1, RQ_REF, 128, p->c64[j], &p->zr[j], 0);
 }
@@ -188,6 +218,9 @@ int yf_rounding_signless_dense(int rounding) {
   if (rounding & YF_ROUND_GENERIC_KERNELS) return 0;
   return rounding > YF_ROUND_TFLITE_REF && rounding < YF_ROUND_COUNT && form_dense(rounding) != RQ_REF;
 }
+int yf_rounding_kernel_set(int rounding) {
+  return rounding == YF_ROUND_FP32 ? 2 : yf_rounding_signless_dense(rounding);
+}
 
 int yf_prepare_tables(const uint8_t* weights_blob, size_t blob_bytes, uint8_t** out_blob, yf_table_index* ix) {
   return yf_prepare_tables_rounding(weights_blob, blob_bytes, YF_ROUND_TFLITE_REF, out_blob, ix);
@@ -196,10 +229,12 @@ int yf_prepare_tables(const uint8_t* weights_blob, size_t blob_bytes, uint8_t** 
 int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, int rounding, uint8_t** out_blob, yf_table_index* ix) {
   if (!weights_blob || blob_bytes < YF_WEIGHTS_BLOB_BYTES || !out_blob || !ix) return YF_PREP_ERR_ARGS;
   const int generic = (rounding & YF_ROUND_GENERIC_KERNELS) != 0;      /* constants for the four-instruction kernels (any rounding) instead of the sign-free dense form */
+  const int fp32 = rounding == YF_ROUND_FP32;                          /* float32 epilogue on every conv (no "+generic": no integer kernel computes it) */
   rounding &= ~YF_ROUND_GENERIC_KERNELS;
-  if (rounding < 0 || rounding >= YF_ROUND_COUNT) return YF_PREP_ERR_ARGS;
-  const int fd = form_dense(rounding), fo = form_other(rounding);      /* dense CONV_2D | DEPTHWISE_CONV_2D, LEAKY_RELU, ADD, QUANTIZE */
-  const int fold = fd != RQ_REF && !generic;                           /* == yf_rounding_signless_dense(rounding): the dense stages' ZR rides in C64 */
+  if (!fp32 && (rounding < 0 || rounding >= YF_ROUND_COUNT)) return YF_PREP_ERR_ARGS;
+  const int fd = fp32 ? RQ_FP32 : form_dense(rounding), fo = form_other(rounding);   /* dense CONV_2D | DEPTHWISE_CONV_2D, LEAKY_RELU, ADD, QUANTIZE */
+  const int fw = fp32 ? RQ_FP32 : fo;                                  /* DEPTHWISE_CONV_2D */
+  const int fold = (fd == RQ_UP || fd == RQ_SINGLE) && !generic;       /* == yf_rounding_signless_dense(rounding): the dense stages' ZR rides in C64 */
   memset(ix, 0, sizeof *ix);
   blob_t b = {0, 0, 0};
   int rc = 0;
@@ -222,7 +257,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
     }
     o->w_off = (uint32_t)blob_alloc(&b, (size_t)o->cout_pad4 * o->krow);
     o->c_off = (uint32_t)blob_alloc(&b, (size_t)(o->cout_pad4 / 4) * sizeof(yf_pass));
-    for (int ch = d->cout; ch < o->cout_pad4; ++ch) pad_chan((yf_pass*)(b.p + o->c_off) + ch / 4, ch & 3);
+    for (int ch = d->cout; ch < o->cout_pad4; ++ch) pad_chan((yf_pass*)(b.p + o->c_off) + ch / 4, ch & 3, fd);
     for (int ch = 0; ch < d->cout; ++ch) {
       int8_t* row = (int8_t*)b.p + o->w_off + (size_t)ch * o->krow;
       int32_t sum_w = 0, abs_w = 0;
@@ -259,7 +294,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
         const int ch = g * 4 + j;
         if (ch >= d->cout) {                 /* padding channel: harmless constants */
           for (int t = 0; t < 9; ++t) wd[t * 4 + j] = 0;
-          pad_chan(cc, j);
+          pad_chan(cc, j, fw);
           continue;
         }
         int32_t sum_w = 0, abs_w = 0;
@@ -268,7 +303,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
           sum_w += wv; abs_w += wv < 0 ? -wv : wv;
           wd[t * 4 + j] = ((uint32_t)(uint8_t)wv) << (8 * j);      /* byte j of the tap's dword carries channel j */
         }
-        rc = build_chan(d, weights_blob, ch, sum_w, abs_w, cc, j, fo, 0);
+        rc = build_chan(d, weights_blob, ch, sum_w, abs_w, cc, j, fw, 0);
         if (rc) break;
       }
       if (rc) break;

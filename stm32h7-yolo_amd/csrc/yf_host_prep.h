@@ -18,7 +18,7 @@ enum {
 /* Rounding of the requantisation's right shift (the values of yf_requant_rounding, include/yf_network.h). */
 #ifndef YF_ROUND_ENUM
 #define YF_ROUND_ENUM
-enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, YF_ROUND_SINGLE = 3, YF_ROUND_COUNT, YF_ROUND_GENERIC_KERNELS = 0x100 };
+enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, YF_ROUND_SINGLE = 3, YF_ROUND_COUNT, YF_ROUND_FP32 = 0x10, YF_ROUND_GENERIC_KERNELS = 0x100 };
 #endif
 
 /* Build the device table blob from the caller's weight blob (ST layout, 11304 B).  *out_blob is malloc'd.
@@ -28,6 +28,9 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
 /* `rounding` may carry YF_ROUND_GENERIC_KERNELS.  Without it the dense stages of a rounding that has no sign term get the FOLDED constants of the three-instruction
  * epilogue (ZR inside C64), and the engine must launch the kernels built for them: */
 int yf_rounding_signless_dense(int rounding);
+/* The kernel set the engine launches for the blob of `rounding`: 0 the reference rounding's (four-instruction epilogue), 1 the sign-free dense
+ * epilogue's (== yf_rounding_signless_dense), 2 the float32 requantisation's (YF_ROUND_FP32) */
+int yf_rounding_kernel_set(int rounding);
 int32_t yf_mbqm_form(int32_t x, int32_t mult, int shift, int form);   /* form: 0 reference, 1 ties upward, 2 single rounding */
 
 /* TFLite QuantizeMultiplier / MultiplyByQuantizedMultiplier (exposed for the CPU tests of the host logic). */

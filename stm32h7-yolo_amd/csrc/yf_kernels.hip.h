@@ -227,9 +227,25 @@ __device__ __forceinline__ void rq4(const v4i acc, const v4u m2, const v4u zr, c
         "s"(cy0), "s"(cy1), "s"(cy2), "s"(cy3)
       : "vcc");
 }
+// FP32 (YF_ROUND_FP32, namespaces yfx / yf160x: YF_RQ_FP32): XNNPACK's qs8 requantisation, clamp(lrintf((float)acc * fs) + Z - 128, ...) + 128, where acc
+// is the exact TFLite accumulator -- the MFMA's C operand was bias' (acc_init) -- fs = m2 (its bits), K = rs = 0x4B400000 - Z (yf_tables.h, yf_pass):
+//   p = fl32(acc) * fs               v_cvt_f32_i32, v_mul_f32
+//   r = bits(p + 1.5 * 2^23)         v_add_f32: 0x4B400000 + rne(p) for |p| < 2^22 (the host bounds |acc * fs| below 2^21); never contracted (-ffp-contract=off)
+//   idx = med3(r - K, 0, 255)        v_sub_u32, v_med3_i32
+// Five VALU instructions, plain C++: the compiler pads the MFMA -> VALU hazard itself.
+__device__ __forceinline__ int rqf(int acc, uint32_t fs, int k) {
+  const float p = (float)acc * __uint_as_float(fs);
+  return min(max(__float_as_int(p + 0x1.8p23f) - k, 0), 255);
+}
 // the four requantised channels of a pass as LUT indices / unsigned bytes (q + 128)
-template <bool AFTER_MFMA, bool SIGNLESS = false>
+template <bool AFTER_MFMA, bool SIGNLESS = false, bool FP32 = false>
 __device__ __forceinline__ void requant4(const v4i acc, const v4u m2, const v4u zr, const v4ul c64, const v4i rs, int (&idx)[4]) {
+  if constexpr (FP32) {
+    (void)zr; (void)c64;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) idx[j] = rqf(acc[j], m2[j], rs[j]);
+    return;
+  }
   int t[4];
   rq4<AFTER_MFMA, SIGNLESS>(acc, m2, zr, c64, t);
 #pragma unroll
@@ -237,8 +253,14 @@ __device__ __forceinline__ void requant4(const v4i acc, const v4u m2, const v4u 
 }
 // the same for TWO channels: the last pass of a layer with 4k + 2 output channels (6, 18) carries two padding channels whose
 // requantisation, LUT reads and packing would be thrown away
-template <bool AFTER_MFMA, bool SIGNLESS = false>
+template <bool AFTER_MFMA, bool SIGNLESS = false, bool FP32 = false>
 __device__ __forceinline__ void requant2(const v4i acc, const v4u m2, const v4u zr, const v4ul c64, const v4i rs, int (&idx)[2]) {
+  if constexpr (FP32) {
+    (void)zr; (void)c64;
+    idx[0] = rqf(acc[0], m2[0], rs[0]);
+    idx[1] = rqf(acc[1], m2[1], rs[1]);
+    return;
+  }
   v2u d0, d1;
   if constexpr (SIGNLESS) {
     (void)zr;
@@ -276,6 +298,16 @@ constexpr bool DENSE_SIGNLESS = true;          // this namespace's dense convolu
 #else
 constexpr bool DENSE_SIGNLESS = false;
 #endif
+#ifdef YF_RQ_FP32
+constexpr bool RQ_FP32 = true;                 // this namespace's convolutions (dense and depthwise) requantise in float32 (rqf)
+#else
+constexpr bool RQ_FP32 = false;
+#endif
+// the MFMA C operand of a convolution: O (the inline constant 2.0: no register) for the integer epilogues, the pass's bias' (zr) for the float32 one
+__device__ __forceinline__ v4i acc_init(const v4u zr) {
+  if constexpr (RQ_FP32) return (v4i)zr;
+  else { (void)zr; return v4i{ACC0, ACC0, ACC0, ACC0}; }
+}
 // A register with no particular content and no instruction behind it: the k-slots of an MFMA B operand whose weights are
 // zero may hold anything (integer arithmetic: 0 * x = 0), so they are not cleared.
 __device__ __forceinline__ int any_value() { int u; asm volatile("" : "=v"(u)); return u; }
@@ -834,7 +866,7 @@ YF_STAGE_FN void dense2_stage(char* frames, char* out_all, const uint8_t* __rest
       for (int t = 0; t < TPJ; ++t) {
         const int ps = chunk * TPJ + t;
         if (ps < NP) {                                          // uniform
-          v4i acc = {ACC0, ACC0, ACC0, ACC0};
+          v4i acc = acc_init(pv[t].zr);
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t][ks], b[ks], acc, 0, 0, 0);
           // the layer's last pass holds two padding channels when COUT = 4k + 2: requantise the two real ones only
@@ -843,12 +875,12 @@ YF_STAGE_FN void dense2_stage(char* frames, char* out_all, const uint8_t* __rest
           if (half) {
             if constexpr (HALF_L) {
               int idx2[2];
-              requant2<true, DENSE_SIGNLESS>(acc, pv[t].m2, pv[t].zr, ksr[t].c64, ksr[t].rs, idx2);
+              requant2<true, DENSE_SIGNLESS, RQ_FP32>(acc, pv[t].m2, pv[t].zr, ksr[t].c64, ksr[t].rs, idx2);
               epilogue2_half<EPI, LUT_ID, LA>(dstpix, addpix, t * 4, idx2, ad);
             }
           } else {
             int idx[4];
-            requant4<true, DENSE_SIGNLESS>(acc, pv[t].m2, pv[t].zr, ksr[t].c64, ksr[t].rs, idx);
+            requant4<true, DENSE_SIGNLESS, RQ_FP32>(acc, pv[t].m2, pv[t].zr, ksr[t].c64, ksr[t].rs, idx);
             epilogue2<EPI, LUT_ID, LA, STASH_LUT>(dstpix, addpix, headpix, t * 4, ps * 4, idx, ad, stashpix);
           }
         }
@@ -913,12 +945,12 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
     for (int ps = 0; ps < 2; ++ps) {
       const uint8_t* s = sc + ps * (int)sizeof(yf_pass_s);
       const PassS k = PassS{*(cv4ul_ptr)(uintptr_t)s, *(cv4i_ptr)(uintptr_t)(s + 32)};
-      v4i acc = {ACC0, ACC0, ACC0, ACC0};
+      v4i acc = acc_init(pv[ps].zr);
       acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ps][0], b0, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ps][1], b1, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ps][2], b2, acc, 0, 0, 0);
       int idx[4];
-      requant4<true, DENSE_SIGNLESS>(acc, pv[ps].m2, pv[ps].zr, k.c64, k.rs, idx);
+      requant4<true, DENSE_SIGNLESS, RQ_FP32>(acc, pv[ps].m2, pv[ps].zr, k.c64, k.rs, idx);
       epilogue2<EPI_LUT, YF_L_LEAKY2, 0>(dstpix, nullptr, nullptr, 4 * ps, 0, idx, ad);
     }
   }
@@ -1076,7 +1108,7 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
       dst = lout + e[1];
     };
     auto conv = [&](const v4i& b0, const v4i& b1, const v4i& b2) {
-      v4i acc = {ACC0, ACC0, ACC0, ACC0};
+      v4i acc = acc_init(pv.zr);
       acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, acc, 0, 0, 0);
       return __builtin_amdgcn_mfma_i32_16x16x64_i8(a2, b2, acc, 0, 0, 0);
@@ -1084,11 +1116,11 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
     auto finish = [&](const v4i& acc, char* dst) {
       if (YF_HALF_PASS && C % 4 == 2 && cg == NG - 1) {          // uniform: the last channel group of an 18-channel layer has two real channels
         int idx2[2];
-        requant2<true>(acc, pv.m2, pv.zr, k.c64, k.rs, idx2);
+        requant2<true, false, RQ_FP32>(acc, pv.m2, pv.zr, k.c64, k.rs, idx2);
         *reinterpret_cast<uint32_t*>(dst) = join2(lutb<LUT_ID>(idx2[0]), lutb<LUT_ID>(idx2[1]));
       } else {
         int idx[4];
-        requant4<true>(acc, pv.m2, pv.zr, k.c64, k.rs, idx);
+        requant4<true, false, RQ_FP32>(acc, pv.m2, pv.zr, k.c64, k.rs, idx);
         *reinterpret_cast<uint32_t*>(dst) = join4(lutb<LUT_ID>(idx[0]), lutb<LUT_ID>(idx[1]), lutb<LUT_ID>(idx[2]), lutb<LUT_ID>(idx[3]));
       }
     };

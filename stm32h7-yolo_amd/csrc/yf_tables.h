@@ -27,14 +27,19 @@ extern "C" {
  * followed by the clamp to [0, 255] (v_med3).  Four VALU instructions per output; bias, zero points and both rounding
  * constants live in C64 / ZR.  The host refuses a model with a channel outside 1 <= r <= 20, M <= 2^30 or
  * |bias'| + 255*sum|w| >= 2^29.
+ * FP32 (YF_ROUND_FP32, the kernel set built with YF_RQ_FP32): the same slots, other meanings.  The MFMA accumulator starts at bias' (the C operand
+ * is the pass's zr: acc = bias' + sum w*x_raw, the exact TFLite accumulator), and
+ *          p = fl32(fl32(acc) * fs),   r = bits(p + 0x1.8p23f) = 0x4B400000 + rne(p)  (|p| < 2^22),   idx = med3(r - K, 0, 255)
+ * mult2 = bits of fs = fl32(fl32(s_in * s_w) / s_out), zr = bias', rshift = K = 0x4B400000 - Z, c64 = 0.  The host refuses a channel whose
+ * reachable |acc * fs| is not below 2^21.
  * Layout is struct-of-arrays so that one vector load brings the four multipliers (VGPRs: the multiplicand and the 64-bit
  * addend cannot both come from SGPRs) and scalar loads bring the rest. */
 #define YF_ACC_OFFSET 0x40000000          /* O: bit pattern of the inline constant 2.0f */
 typedef struct {
-  uint32_t mult2[4];   /* 2 * M                                  (vector registers) */
-  uint32_t zr[4];      /* (zp_out + 128) << rshift               (vector registers) */
+  uint32_t mult2[4];   /* 2 * M                                  (vector registers)   FP32: bits of fs */
+  uint32_t zr[4];      /* (zp_out + 128) << rshift               (vector registers)   FP32: bias' */
   uint32_t c64[4][2];  /* C64: low dword, high dword             (scalar register pairs) */
-  int32_t  rshift[4];  /*                                        (scalar registers) */
+  int32_t  rshift[4];  /*                                        (scalar registers)   FP32: 0x4B400000 - (zp_out + 128) */
 } yf_pass;
 
 /* ---- dense (MFMA) stage ----------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ class Interpreter:
     # SURVEY 8(c).3 fixes as "the tflite int8 reference"; BUILTIN / BUILTIN_WITHOUT_DEFAULT_DELEGATES are the optimized kernels, whose dense convolutions go
     # through ruy (ties upward).  AUTO -- what the reference's script gets by passing nothing (tflite_prediction.py:23) -- maps to the library's DEFAULT,
     # which is the reference rounding by the project's contract although TensorFlow's AUTO is most likely the optimized set.
+    # The XNNPACK delegate's float32 requantisation, which AUTO / BUILTIN may apply, has no resolver name of its own: requant_rounding=YF_ROUND_FP32 selects it.
     _RESOLVER_ROUNDING = {"AUTO": None, "BUILTIN_REF": 0, "BUILTIN": 1, "BUILTIN_WITHOUT_DEFAULT_DELEGATES": 1}
 
     def __init__(self, model_path="yoloface_int8.tflite", device=0, experimental_op_resolver_type="AUTO", requant_rounding=None, **_ignored):

@@ -28,7 +28,7 @@ SELECT = {"R": "the default (YF_ROUND_TFLITE_REF / YF_REQUANT_ROUNDING=ref): not
           "U": "YF_ROUND_TIES_UP / YF_REQUANT_ROUNDING=ties_up (dense convs as ruy rounds them)",
           "U_all": "YF_ROUND_TIES_UP_ALL / YF_REQUANT_ROUNDING=ties_up_all",
           "S": "YF_ROUND_SINGLE / YF_REQUANT_ROUNDING=single (ruy's portable path)",
-          "X": "no library mode: fp32 requantisation (the XNNPACK delegate) -- build the interpreter with experimental_op_resolver_type=BUILTIN_WITHOUT_DEFAULT_DELEGATES"}
+          "X": "YF_ROUND_FP32 / YF_REQUANT_ROUNDING=fp32 (fp32 requantisation of the convs: the XNNPACK delegate)"}
 
 
 def main():
