@@ -957,20 +957,37 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
 }
 
 // ---- depthwise 3x3 (one-hot lane-private MFMA, see dw_mfma_stage): geometry of a stage instance
+// Output rows per lane and job.  R = 1: a job is 4 rows x 16 columns, lane (g, c) computes row g, column c from its own nine tap reads.
+// R > 1 (row window): lane (g, c) walks rows g*R .. g*R + R - 1 of the job's block down column c and keeps the last three input rows in
+// registers -- three new tap reads per output row instead of four and a half (R = 2) or nine.  The stride-1 stages of the 56x56 kernel with two
+// frames per group: conv2d_3 (28 rows = one block of 4 x 7; 8 jobs for 8 waves, as 56 jobs of one row) and conv2d_15 (14 rows = blocks of 4 x 2
+// at rows 0 and 6, as now 16 rows computed; 36 jobs of two rows, so the busiest wave has 10 rows instead of 9, and lanes g = 0, 1 are 2 rows = 288
+// dwords apart, a 2-way bank conflict on every tap read -- measured faster anyway: profiles/EXPERIMENTS.md, round 7).  The 7x7 stages (two frames per
+// job) keep R = 1, and so do the one-frame form and the 160x160 bands.
+template <int F, int STRIDE, int W, int H>
+constexpr int dw_rows_per_lane() {
+#if YF_H0 == 56
+  return STRIDE == 1 && F == 2 && W == 28 && H == 28 ? 7 : STRIDE == 1 && F == 2 && W == 14 && H == 14 ? 2 : 1;
+#else
+  return 1;
+#endif
+}
 template <int F, int STRIDE, class IN, class OUT>
 struct DwGeo {
   static constexpr int W = OUT::W, H = OUT::H;
+  static constexpr int R = dw_rows_per_lane<F, STRIDE, OUT::W, OUT::H>(), BR = 4 * R;     // rows per lane, rows per job block
   static constexpr int FL = (W <= 8 && F % 2 == 0) ? 2 : 1;
-  static constexpr int NSEG = (W + 15) / 16, NRB = (H + 3) / 4, NFP = F / FL;
+  static constexpr int NSEG = (W + 15) / 16, NRB = (H + BR - 1) / BR, NFP = F / FL;
   static constexpr int JPG = NFP * NRB * NSEG;                 // jobs per channel group
   static_assert(OUT::RS == W && OUT::PT == 0 && OUT::PL == 0, "depthwise outputs are plain buffers");
   static_assert(IN::FS == OUT::FS, "one frame stride per stage");
-  static_assert(H >= 4 && (W >= 16 || W * FL <= 16), "tile shape");
+  static_assert(H >= BR && (W >= 16 || W * FL <= 16), "tile shape");
+  static_assert(R == 1 || (STRIDE == 1 && FL == 1), "row window: stride-1 stages, one frame per job");
   // offsets (relative to the workgroup's frame arenas) of job jj: the top-left tap of lane (0,0) and its output pixel
   __device__ static __forceinline__ uint2 job(int jj) {
     const int fp = jj / (NRB * NSEG); int rem = jj - fp * (NRB * NSEG);
     const int rb = rem / NSEG, seg = rem - rb * NSEG;
-    const int oy0 = min(rb * 4, H - 4);
+    const int oy0 = min(rb * BR, H - BR);
     const int x0 = (W >= 16) ? min(seg * 16, W - 16) : 0;
     const int fb = fp * FL * IN::FS;
     return uint2{(uint32_t)(fb + IN::OFF + (oy0 * STRIDE) * IN::ROWB + x0 * STRIDE * IN::S), (uint32_t)(fb + OUT::OFF + (oy0 * W + x0) * OUT::S)};
@@ -1066,8 +1083,8 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
   const int g = lane >> 4, c = lane & 15;
   const int fl = (FL == 2) ? (c >> 3) : 0;
   const int xl = (FL == 2) ? min(c & 7, W - 1) : min(c, W - 1);      // surplus lanes duplicate the last column (idempotent)
-  const char* lane_in = frames + fl * IN::FS + g * DROW + xl * STRIDE * IN::S;     // this lane's pixel: row oy0+g, col x0+xl
-  char* lane_out = frames + fl * IN::FS + (g * W + xl) * OUT::S;
+  const char* lane_in = frames + fl * IN::FS + g * G::R * DROW + xl * STRIDE * IN::S;     // this lane's (first) pixel: row oy0+g*R, col x0+xl
+  char* lane_out = frames + fl * IN::FS + (g * G::R * W + xl) * OUT::S;
   const bool a_on = (c >> 2) == g;
   const uint32_t a_lane = a_on ? (uint32_t)(SLOT + 4 * (c & 3)) : (uint32_t)LAY::ZERO;   // masked weight dwords of channel c&3: +16*tap
   const uint32_t a_step = a_on ? (uint32_t)YF_DWV_GROUP_BYTES : 0u;
@@ -1091,17 +1108,6 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
     auto entry = [&](int job) { return *(lds_u2_ptr)(uint32_t)(LAY::JT + JTOFF + 8 * min(job, JPG - 1)); };    // {src, dst} offsets of a job
     auto taps = [&](const v2u e, v4i& b0, v4i& b1, v4i& b2, char*& dst) {
       const char* src = lin + e[0];
-#if defined(YF_LAB) && defined(YF_WHATIF_DW_ROWWIN)
-      // Timing-only what-if (WRONG results; profiles/EXPERIMENTS.md round 5): the bound for taps by KERNEL ROW with a three-row register window in the two
-      // stride-1 stages on the big grids (conv2d_3, conv2d_15) -- a lane walking down a column strip would read 3 new dwords per output row instead of 9.
-      // Here: three of the nine reads are issued, the other six operands reuse them; MFMAs, epilogue and stores unchanged.
-      if constexpr (STRIDE == 1 && G::W >= 14) {
-        b0[0] = (int)lds_u32(src + 2 * TR);    b0[1] = (int)lds_u32(src + 2 * TR + TS); b0[2] = (int)lds_u32(src + 2 * TR + 2 * TS);
-        b0[3] = b0[0]; b1[0] = b0[1]; b1[1] = b0[2]; b1[2] = b0[0]; b1[3] = b0[1]; b2[0] = b0[2];
-        dst = lout + e[1];
-        return;
-      }
-#endif
       b0[0] = (int)lds_u32(src);               b0[1] = (int)lds_u32(src + TS);          b0[2] = (int)lds_u32(src + 2 * TS);
       b0[3] = (int)lds_u32(src + TR);          b1[0] = (int)lds_u32(src + TR + TS);     b1[1] = (int)lds_u32(src + TR + 2 * TS);
       b1[2] = (int)lds_u32(src + 2 * TR);      b1[3] = (int)lds_u32(src + 2 * TR + TS); b2[0] = (int)lds_u32(src + 2 * TR + 2 * TS);
@@ -1125,6 +1131,33 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
       }
     };
     const int n = min(left, JPG - jj);
+    if constexpr (G::R > 1) {
+      // row window: the weights by kernel row (MFMA k = the three taps of row ky in dwords 0..2, dword 3 zero), one input row = one B operand;
+      // output row y of the lane reads input row y + 2 only, rows y and y + 1 are the previous output row's
+      const v4i ar[3] = {v4i{a0[0], a0[1], a0[2], 0}, v4i{a0[3], a1[0], a1[1], 0}, v4i{a1[2], a1[3], a2[0], 0}};
+      for (int i = 0; i < n; ++i) {
+        const v2u e = entry(jj + i);
+        const char* src = lin + e[0];
+        char* dst = lout + e[1];
+        auto row = [&](int r) {
+          const char* p = src + r * TR;
+          return v4i{(int)lds_u32(p), (int)lds_u32(p + TS), (int)lds_u32(p + 2 * TS), any_value()};
+        };
+        v4i w0 = row(0), w1 = row(1);
+#pragma unroll
+        for (int y = 0; y < G::R; ++y) {
+          const v4i w2 = row(y + 2);
+          v4i acc = acc_init(pv.zr);
+          acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[0], w0, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[1], w1, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[2], w2, acc, 0, 0, 0);
+          finish(acc, dst + y * W * OUT::S);
+          w0 = w1; w1 = w2;
+        }
+      }
+      left -= n; ++cg; jj = 0;
+      continue;
+    }
     int i = 0;
     v2u e0 = entry(jj), e1 = entry(jj + 1);     // the next pair's table entries are read one iteration ahead (behind this pair's tap reads)
     for (; i + 1 < n; i += 2) {               // two jobs in flight: the second job's tap reads and MFMAs overlap the first one's epilogue
