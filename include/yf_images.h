@@ -1,0 +1,74 @@
+/* C-ABI of libyf_images.so -- decoded images of any size to the network's int8 frames, resized as OpenCV's cv2.resize does
+ * (INTER_LINEAR, 11-bit fixed-point weights), and on to detection records in each image's own pixels.
+ *
+ * This is the front half of the reference's Python caller (yoloface/tflite/tflite_prediction.py:29-37,56-61): imread (BGR), BGR -> RGB,
+ * cv2.resize(img, (56, 56)), minus 128, int8; after the network, boxes scaled by W/56. and H/56.  The resize is bit-exact against
+ * ptq.resize_linear_u8, a restatement of OpenCV 4's imgproc/resize.cpp that has not been pinned against a real cv2 (none is available
+ * where this library is built), just as the oracle is not pinned against TFLite.
+ *
+ * The library links against libyf_network.so and reaches the network only through its public C-ABI (include/yf_network.h).
+ *
+ * Pointers prefixed d_ are device memory.  Every call is asynchronous on `stream` (a hipStream_t, NULL = default stream) on the calling
+ * thread's current device (the run_* calls: the network's device), does no host synchronisation and no allocation, and can be captured in
+ * a graph -- except that the first per-image-scale decode on a device uploads the 2 KB decode tables once (synchronously).
+ * Return values follow include/yf_network.h: n on success, <= 0 on error; yf_images_last_error_text() says why (per thread).
+ * d_frames must be 16-byte aligned. */
+#ifndef YF_IMAGES_H
+#define YF_IMAGES_H
+#include <stddef.h>
+#include <stdint.h>
+#include "yf_network.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One image of a ragged batch: its first pixel at byte `offset` of the pixel buffer, rows `row_stride` bytes apart.  24 bytes. */
+typedef struct yf_image {
+  uint64_t offset;
+  int32_t  height, width;
+  int64_t  row_stride;
+} yf_image;
+
+/* Pixel formats (bytes per pixel 3, 3, 4, 4); the alpha byte is never read.  Frames come out in RGB order whatever the format. */
+enum { YF_PIX_BGR8 = 0 /* cv2.imread */, YF_PIX_RGB8 = 1, YF_PIX_BGRA8 = 2, YF_PIX_RGBA8 = 3 };
+
+#define YF_IMAGES_MAX_SIDE 16384   /* 1 <= height, width <= this */
+
+/* frame[y][x][c] = (int8)(R[y][x][rgb(c)] - 128), R = cv2.resize(image, (out_hw, out_hw)).  out_hw = 56 (the network's input) or 160
+ * (frames for yf_network_run_device_hw; decode at 160 is not offered).  d_frames int8[n][out_hw][out_hw][3]. */
+
+/* Uniform batch: n images of height x width, image i at d_pixels + i * frame_stride, rows row_stride bytes apart (a video, an [n,H,W,C]
+ * tensor, or crops of one: row_stride >= width * C, frame_stride >= 0).  Every argument is checked before any launch; an image that
+ * would reach outside [0, pixels_bytes) is an error. */
+YF_API long yf_images_prepare_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                     long row_stride, long frame_stride, long n, int out_hw, void* d_frames, void* stream);
+/* Ragged batch: one descriptor per image (d_images, device memory).  The kernel checks each descriptor (1 <= h, w <= 16384,
+ * row_stride >= w * C, offset + (h - 1) * row_stride + w * C <= pixels_bytes): d_status[i] = 0 for a valid image, 1 for an invalid one,
+ * which is never read and whose frame is written as all -128.  No load touches a byte outside an image's own extent. */
+YF_API long yf_images_prepare_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                            int out_hw, void* d_frames, int32_t* d_status, void* stream);
+/* Images -> frames (the caller's workspace d_frames int8[n][56][56][3]) -> heads d_heads int8[n][7][7][18] -> yf_det records
+ * d_dets[n][cap], d_counts int32[n], boxes in each image's own pixels: w_scale = (float)((double)W / 56.0), h_scale likewise (the
+ * script's `W/56.` applied to a float32 array).  mode: YF_DECODE_PY (the script's), YF_DECODE_FW, YF_DECODE_FW_HOST.
+ * Uniform: the scales are scalars and decode stays fused in the network launch (yf_network_run_decode_device). */
+YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                        long row_stride, long frame_stride, long n, void* d_frames, void* d_heads, int mode,
+                                        void* d_dets, void* d_counts, int cap, void* stream);
+/* Ragged: yf_network_run_device, then a per-image-scale decode; an invalid image (d_status 1) gets count 0. */
+YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                               const yf_image* d_images, long n, void* d_frames, void* d_heads, int mode,
+                                               void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+/* Per-image scales for heads that already exist (d_heads int8[n][7][7][18]); a descriptor whose height or width is outside
+ * [1, 16384] gets count 0. */
+YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode,
+                                           void* d_dets, void* d_counts, int cap, void* stream);
+
+YF_API const char* yf_images_last_error_text(void);
+/* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
+YF_API const char* yf_images_build_id(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,319 @@
+// libyf_images.so: decoded images of any size -> the network's int8 frames, resized exactly as cv2.resize(img, (out, out)) (INTER_LINEAR,
+// the arithmetic of yf_images_taps.h), and on through libyf_network.so's public C-ABI to detection records in each image's own pixels.
+// C-ABI and semantics: include/yf_images.h.
+//
+// Kernel: one 256-thread workgroup per frame (grid-striding over the batch).  Lanes build the out_hw x-taps and y-taps in LDS, then each
+// lane computes whole output pixels: four byte-wide reads per channel (two source rows, two columns), horizontal then vertical pass, the
+// -128 and the channel order fused; lanes of a wave take consecutive output columns, so the reads of a sampled source row coalesce.  The
+// frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses inside
+// the image's extent: no load reaches past its last pixel.
+#include <hip/hip_runtime.h>
+#include <mutex>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/yf_images.h"
+#include "yf_images_taps.h"
+#include "yf_decode.hip.h"
+#include "gen/yf_decode_tables_gen.h"
+
+#ifndef YF_IMAGES_BUILD_ID
+#define YF_IMAGES_BUILD_ID "unknown"
+#endif
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kHeadBytes = 7 * 7 * 18;
+
+struct PrepArgs {
+  const uint8_t* px;
+  uint64_t bytes;
+  const yf_image* imgs;        // ragged
+  int32_t* status;             // ragged
+  int h, w;                    // uniform
+  int64_t rs, fs;              // uniform
+  long n;
+  int8_t* frames;
+};
+
+struct YTap { int64_t o0, o1; int32_t w0, w1; };
+
+template <int OUT> struct Band { static constexpr int ROWS = OUT == 56 ? 56 : 20; };
+
+template <int OUT, int C, bool BGR, bool RAGGED>
+__global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) {
+  constexpr int ROWS = Band<OUT>::ROWS;
+  constexpr int FRAME_BYTES = OUT * OUT * 3;
+  static_assert((ROWS * OUT * 3) % 16 == 0 && OUT % ROWS == 0, "bands of whole 16-byte vectors");
+  __shared__ int4 s_xt[OUT];                       // {s0 * C, s1 * C, w0, w1}
+  __shared__ YTap s_yt[OUT];
+  __shared__ int4 s_stage[ROWS * OUT * 3 / 16];
+  const int tid = threadIdx.x;
+  for (long f = blockIdx.x; f < a.n; f += gridDim.x) {
+    uint64_t off;
+    int h, w;
+    int64_t rs;
+    if (RAGGED) {
+      const yf_image im = a.imgs[f];
+      off = im.offset; h = im.height; w = im.width; rs = im.row_stride;
+    } else {
+      off = (uint64_t)f * (uint64_t)a.fs; h = a.h; w = a.w; rs = a.rs;
+    }
+    int4* out = (int4*)(a.frames + f * FRAME_BYTES);
+    __syncthreads();                               // the previous frame's readers of the tap tables and the stage are done
+    if (RAGGED) {
+      const bool ok = yfi_image_ok(off, h, w, rs, C, a.bytes);
+      if (tid == 0) a.status[f] = ok ? 0 : 1;
+      if (!ok) {                                   // never read: the frame is all -128
+        const int4 fill = make_int4((int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080);
+        for (int q = tid; q < FRAME_BYTES / 16; q += kThreads) out[q] = fill;
+        continue;
+      }
+    }
+    for (int t = tid; t < 2 * OUT; t += kThreads) {
+      if (t < OUT) {
+        const yfi_tap x = yfi_axis_tap(t, OUT, w);
+        s_xt[t] = make_int4(x.s0 * C, x.s1 * C, x.w0, x.w1);
+      } else {
+        const yfi_tap y = yfi_axis_tap(t - OUT, OUT, h);
+        s_yt[t - OUT] = YTap{(int64_t)y.s0 * rs, (int64_t)y.s1 * rs, y.w0, y.w1};
+      }
+    }
+    __syncthreads();
+    const uint8_t* base = a.px + off;
+    int8_t* stage = (int8_t*)s_stage;
+    for (int r0 = 0; r0 < OUT; r0 += ROWS) {
+      for (int p = tid; p < ROWS * OUT; p += kThreads) {
+        const int yy = p / OUT, xx = p - yy * OUT;
+        const int4 tx = s_xt[xx];
+        const YTap ty = s_yt[r0 + yy];
+        const uint8_t* ra = base + ty.o0;
+        const uint8_t* rb = base + ty.o1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int sc = BGR ? 2 - c : c;
+          const int32_t h0 = yfi_hpass(ra[tx.x + sc], ra[tx.y + sc], tx.z, tx.w);
+          const int32_t h1 = yfi_hpass(rb[tx.x + sc], rb[tx.y + sc], tx.z, tx.w);
+          stage[p * 3 + c] = (int8_t)(yfi_vpass(h0, h1, ty.w0, ty.w1) - 128);
+        }
+      }
+      __syncthreads();
+      int4* dst = out + r0 * OUT * 3 / 16;
+      for (int q = tid; q < ROWS * OUT * 3 / 16; q += kThreads) dst[q] = s_stage[q];
+      __syncthreads();
+    }
+  }
+}
+
+// Per-image-scale decode: one wave per frame, decode_frame of csrc/yf_decode.hip.h unchanged, the scales the script's W/56. and H/56. become
+// on a float32 array.  An image whose descriptor was flagged (status 1) or whose sides are out of range gets count 0.
+__global__ void __launch_bounds__(kThreads) decode_ragged_kernel(const int8_t* __restrict__ heads, const yf_image* __restrict__ imgs,
+                                                                 const int32_t* __restrict__ status, long n, int mode,
+                                                                 yf_det* __restrict__ dets, int* __restrict__ counts, int cap) {
+  const int lane = threadIdx.x & 63;
+  for (long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6); f < n; f += (long)gridDim.x * 4) {
+    const yf_image im = imgs[f];
+    const bool ok = im.height >= 1 && im.height <= YF_IMAGES_MAX_SIDE && im.width >= 1 && im.width <= YF_IMAGES_MAX_SIDE &&
+                    (status == nullptr || status[f] == 0);
+    if (!ok) {
+      if (lane == 0) counts[f] = 0;
+      continue;
+    }
+    const float w_scale = (float)((double)im.width / 56.0), h_scale = (float)((double)im.height / 56.0);
+    yfdec::decode_frame(heads + f * kHeadBytes, f, lane, mode, w_scale, h_scale, dets, counts, cap);
+  }
+}
+
+thread_local char g_err[256];
+
+long fail(const char* what) {
+  snprintf(g_err, sizeof g_err, "%s", what);
+  return 0;
+}
+
+long fail_hip(const char* what, hipError_t e) {
+  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
+  return 0;
+}
+
+int channels_of(int format) {
+  switch (format) {
+    case YF_PIX_BGR8: case YF_PIX_RGB8: return 3;
+    case YF_PIX_BGRA8: case YF_PIX_RGBA8: return 4;
+    default: return 0;
+  }
+}
+
+// workgroups in flight: 8 per CU (LDS per workgroup: 13.6 KB at 56, 14.6 KB at 160)
+long grid_for(long groups) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const long g = (long)cus * 8;
+  return groups < g ? groups : g;
+}
+
+template <int OUT, bool RAGGED>
+void launch_prepare(int format, const PrepArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)grid_for(a.n)), block(kThreads);
+  switch (format) {
+    case YF_PIX_BGR8:  hipLaunchKernelGGL((prepare_kernel<OUT, 3, true, RAGGED>), grid, block, 0, s, a); break;
+    case YF_PIX_RGB8:  hipLaunchKernelGGL((prepare_kernel<OUT, 3, false, RAGGED>), grid, block, 0, s, a); break;
+    case YF_PIX_BGRA8: hipLaunchKernelGGL((prepare_kernel<OUT, 4, true, RAGGED>), grid, block, 0, s, a); break;
+    default:           hipLaunchKernelGGL((prepare_kernel<OUT, 4, false, RAGGED>), grid, block, 0, s, a); break;
+  }
+}
+
+long prepare(int out_hw, int format, const PrepArgs& a, bool ragged, hipStream_t s) {
+  if (a.n == 0) return 0;
+  if (out_hw == 56) { if (ragged) launch_prepare<56, true>(format, a, s); else launch_prepare<56, false>(format, a, s); }
+  else { if (ragged) launch_prepare<160, true>(format, a, s); else launch_prepare<160, false>(format, a, s); }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip("prepare kernel launch", e);
+  return a.n;
+}
+
+// Every argument of a uniform batch, before any launch.  On success fills `a`.
+bool check_uniform(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long row_stride, long frame_stride,
+                   long n, int out_hw, void* d_frames, PrepArgs* a) {
+  const int C = channels_of(format);
+  if (!C) { fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8"); return false; }
+  if (out_hw != 56 && out_hw != 160) { fail("out_hw must be 56 or 160"); return false; }
+  if (n < 0) { fail("n < 0"); return false; }
+  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) { fail("d_frames is NULL or not 16-byte aligned"); return false; }
+  if (height < 1 || width < 1 || height > YF_IMAGES_MAX_SIDE || width > YF_IMAGES_MAX_SIDE) { fail("height and width must be in [1, 16384]"); return false; }
+  if (row_stride < (long)width * C) { fail("row_stride < width * bytes per pixel"); return false; }
+  if (frame_stride < 0) { fail("frame_stride < 0"); return false; }
+  if (n > 0) {
+    if (!d_pixels) { fail("d_pixels is NULL"); return false; }
+    if (!yfi_image_ok(0, height, width, row_stride, C, pixels_bytes)) { fail("the first image reaches outside [0, pixels_bytes)"); return false; }
+    const uint64_t extent = (uint64_t)(height - 1) * (uint64_t)row_stride + (uint64_t)width * C;
+    if (n > 1 && frame_stride > 0 && (uint64_t)(n - 1) > (pixels_bytes - extent) / (uint64_t)frame_stride) {
+      fail("the last image reaches outside [0, pixels_bytes)");
+      return false;
+    }
+  }
+  *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, nullptr, nullptr, height, width, (int64_t)row_stride, (int64_t)frame_stride,
+                n, (int8_t*)d_frames};
+  return true;
+}
+
+bool check_ragged(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n, int out_hw, void* d_frames,
+                  int32_t* d_status, PrepArgs* a) {
+  if (!channels_of(format)) { fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8"); return false; }
+  if (out_hw != 56 && out_hw != 160) { fail("out_hw must be 56 or 160"); return false; }
+  if (n < 0) { fail("n < 0"); return false; }
+  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) { fail("d_frames is NULL or not 16-byte aligned"); return false; }
+  if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0)) {
+    fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
+    return false;
+  }
+  *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, n, (int8_t*)d_frames};
+  return true;
+}
+
+bool check_decode(void* d_heads, int mode, void* d_dets, void* d_counts, int cap) {
+  if (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST) { fail("mode must be YF_DECODE_PY, YF_DECODE_FW or YF_DECODE_FW_HOST"); return false; }
+  if (!d_heads || !d_dets || !d_counts || cap <= 0) { fail("d_heads, d_dets or d_counts is NULL, or cap <= 0"); return false; }
+  if (((uintptr_t)d_dets & 3) != 0 || ((uintptr_t)d_counts & 3) != 0) { fail("d_dets and d_counts must be 4-byte aligned"); return false; }
+  return true;
+}
+
+// The decode tables (2 KB of __constant__ in this library's code object), uploaded once per device on first use.
+std::mutex g_tables_mu;
+bool g_tables_on[64];
+
+bool tables_ready(hipStream_t s) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) { fail_hip("hipGetDevice", e); return false; }
+  if (dev < 0 || dev >= 64) { fail("device index out of range"); return false; }
+  std::lock_guard<std::mutex> lk(g_tables_mu);
+  if (g_tables_on[dev]) return true;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+    fail("the first per-image-scale decode on a device uploads its tables: make one call outside stream capture first");
+    return false;
+  }
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) { fail_hip("hipMemcpyToSymbol(sigmoid)", e); return false; }
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) { fail_hip("hipMemcpyToSymbol(exp)", e); return false; }
+  g_tables_on[dev] = true;
+  return true;
+}
+
+long decode_ragged(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int mode, void* d_dets, void* d_counts,
+                   int cap, hipStream_t s) {
+  if (n == 0) return 0;
+  if (!tables_ready(s)) return 0;
+  const long groups = (n + 3) / 4;
+  hipLaunchKernelGGL(decode_ragged_kernel, dim3((unsigned)(groups < 65536 ? groups : 65536)), dim3(kThreads), 0, s,
+                     (const int8_t*)d_heads, d_images, d_status, n, mode, (yf_det*)d_dets, (int*)d_counts, cap);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip("decode kernel launch", e);
+  return n;
+}
+
+long network_failed(ai_handle net, const char* what) {
+  const char* t = yf_network_last_error_text(net);
+  snprintf(g_err, sizeof g_err, "%s: %s", what, t ? t : "(no text)");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+YF_API const char* yf_images_last_error_text(void) { return g_err; }
+YF_API const char* yf_images_build_id(void) { return YF_IMAGES_BUILD_ID; }
+
+YF_API long yf_images_prepare_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long row_stride,
+                                     long frame_stride, long n, int out_hw, void* d_frames, void* stream) {
+  PrepArgs a;
+  if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, out_hw, d_frames, &a)) return 0;
+  return prepare(out_hw, format, a, false, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                            int out_hw, void* d_frames, int32_t* d_status, void* stream) {
+  PrepArgs a;
+  if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, out_hw, d_frames, d_status, &a)) return 0;
+  return prepare(out_hw, format, a, true, (hipStream_t)stream);
+}
+
+YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                        long row_stride, long frame_stride, long n, void* d_frames, void* d_heads, int mode,
+                                        void* d_dets, void* d_counts, int cap, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 56, d_frames, &a)) return 0;
+  if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
+  if (n == 0) return 0;
+  if (prepare(56, format, a, false, (hipStream_t)stream) != n) return 0;
+  const float w_scale = (float)((double)width / 56.0), h_scale = (float)((double)height / 56.0);
+  if (yf_network_run_decode_device(net, d_frames, d_heads, n, mode, w_scale, h_scale, d_dets, d_counts, cap, stream) != n)
+    return network_failed(net, "yf_network_run_decode_device");
+  return n;
+}
+
+YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                               const yf_image* d_images, long n, void* d_frames, void* d_heads, int mode,
+                                               void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 56, d_frames, d_status, &a)) return 0;
+  if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
+  if (n == 0) return 0;
+  if (!tables_ready((hipStream_t)stream)) return 0;
+  if (prepare(56, format, a, true, (hipStream_t)stream) != n) return 0;
+  if (yf_network_run_device(net, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device");
+  return decode_ragged(d_heads, d_images, d_status, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode, void* d_dets, void* d_counts,
+                                           int cap, void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (!check_decode((void*)d_heads, mode, d_dets, d_counts, cap)) return 0;
+  if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
+  return decode_ragged(d_heads, d_images, nullptr, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,36 @@
+/* Host build of the resize arithmetic in yf_images_taps.h (the functions the device kernel calls), for the CPU tests only:
+ * libyf_images_host.so, no HIP. */
+#include <stddef.h>
+#include <stdint.h>
+#include "yf_images_taps.h"
+
+#define EXPORT __attribute__((visibility("default")))
+
+/* out[4] = {s0, s1, w0, w1} of output index d */
+EXPORT void yfi_tap_host(int d, int n_out, int n_in, int32_t* out) {
+  const yfi_tap t = yfi_axis_tap(d, n_out, n_in);
+  out[0] = t.s0; out[1] = t.s1; out[2] = t.w0; out[3] = t.w1;
+}
+
+/* cv2.resize(src, (out_w, out_h)) of an h x w image of C channels (rows rs bytes apart) -> dst uint8[out_h][out_w][C] */
+EXPORT int yfi_resize_host(const uint8_t* src, int h, int w, int C, long rs, int out_w, int out_h, uint8_t* dst) {
+  if (!yfi_image_ok(0, h, w, rs, C, (uint64_t)(h - 1) * (uint64_t)rs + (uint64_t)w * (uint64_t)C) || out_w < 1 || out_h < 1) return -1;
+  for (int y = 0; y < out_h; ++y) {
+    const yfi_tap ty = yfi_axis_tap(y, out_h, h);
+    const uint8_t* r0 = src + (size_t)ty.s0 * (size_t)rs;
+    const uint8_t* r1 = src + (size_t)ty.s1 * (size_t)rs;
+    for (int x = 0; x < out_w; ++x) {
+      const yfi_tap tx = yfi_axis_tap(x, out_w, w);
+      for (int c = 0; c < C; ++c) {
+        const int32_t h0 = yfi_hpass(r0[tx.s0 * C + c], r0[tx.s1 * C + c], tx.w0, tx.w1);
+        const int32_t h1 = yfi_hpass(r1[tx.s0 * C + c], r1[tx.s1 * C + c], tx.w0, tx.w1);
+        dst[((size_t)y * out_w + x) * C + c] = (uint8_t)yfi_vpass(h0, h1, ty.w0, ty.w1);
+      }
+    }
+  }
+  return 0;
+}
+
+EXPORT int yfi_image_ok_host(uint64_t offset, int64_t h, int64_t w, int64_t rs, int C, uint64_t bytes) {
+  return yfi_image_ok(offset, h, w, rs, C, bytes);
+}

@@ -1,0 +1,225 @@
+"""ctypes binding of libyf_images.so (include/yf_images.h): decoded images of any size -> the network's int8 frames, resized exactly as
+`cv2.resize(img, (out, out))` (INTER_LINEAR) computes -- "exactly" meaning bit-exact against `ptq.resize_linear_u8`, a restatement of OpenCV 4's
+imgproc/resize.cpp that has not been pinned against a real cv2 -- and on through the network to boxes in each image's own pixels.
+
+`detect(network, images)` is lines 29-61 of the reference's yoloface/tflite/tflite_prediction.py for a whole batch: imread (BGR), BGR -> RGB,
+cv2.resize to 56x56, minus 128, int8, the network, decode, boxes scaled by W/56. and H/56.
+"""
+import ctypes
+import hashlib
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from . import binding
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
+_CSRC = os.path.join(_PKG, "csrc")
+
+YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8 = 0, 1, 2, 3
+FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba": YF_PIX_RGBA8}
+CHANNELS = {YF_PIX_BGR8: 3, YF_PIX_RGB8: 3, YF_PIX_BGRA8: 4, YF_PIX_RGBA8: 4}
+MAX_SIDE = 16384
+FRAME_BYTES = {56: 56 * 56 * 3, 160: 160 * 160 * 3}
+
+
+class YfImage(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_uint64), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("row_stride", ctypes.c_int64)]
+
+
+IMAGE_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("row_stride", "<i8")])
+assert IMAGE_DTYPE.itemsize == ctypes.sizeof(YfImage) == 24
+
+
+class ImagesError(RuntimeError):
+    pass
+
+
+def lib_path():
+    """libyf_images.so sits beside the libyf_network.so that binding loads (its rpath $ORIGIN finds that one)."""
+    return os.path.join(os.path.dirname(binding.LIB_PATH), "libyf_images.so")
+
+
+def _images_srcs():
+    mk = open(os.path.join(_CSRC, "Makefile")).read()
+    return re.search(r"^IMAGES_SRCS\s*=\s*(.*)$", mk, re.M).group(1).split()
+
+
+def expected_build_id():
+    """The id csrc/Makefile bakes into libyf_images.so (yf_images_build_id): sha256 over IMAGES_SRCS and flags.mk."""
+    h = hashlib.sha256()
+    for f in _images_srcs() + ["flags.mk"]:
+        h.update(open(os.path.join(_CSRC, f), "rb").read())
+    return h.hexdigest()[:16]
+
+
+def library_is_current():
+    """True when the in-tree libyf_images.so can be loaded without running make: it is newer than its sources, the Makefile, flags.mk and
+    the libyf_network.so it links against.  Its baked-in id is still checked after loading."""
+    try:
+        built = os.path.getmtime(lib_path())
+        deps = [os.path.join(_CSRC, f) for f in _images_srcs() + ["Makefile", "flags.mk"]] + [binding.LIB_PATH]
+        return all(os.path.getmtime(p) <= built for p in deps)
+    except (OSError, AttributeError):
+        return False
+
+
+_lib = None
+
+
+def load():
+    """dlopen libyf_images.so after libyf_network.so (binding.load() first: one HIP runtime per process, binding._one_hip_runtime), rebuilding
+    it when its sources are newer; an existing file is used without a build only if it is current and carries the expected id."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    binding.load()
+    path = lib_path()
+    check_id = False
+    if os.environ.get("YF_LIB_PATH"):
+        pass                                    # developer override of the network library: its sibling, unchecked (like binding.load)
+    elif os.environ.get("YF_NO_BUILD") == "1" or library_is_current():
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} does not exist: build it first (python -c 'import __graft_entry__ as g; g.build()')")
+        check_id = True
+    else:
+        try:
+            binding.build()                     # `make all` builds both libraries
+        except (OSError, subprocess.CalledProcessError) as e:
+            if not os.path.exists(path):
+                raise
+            import warnings
+            warnings.warn(f"stm32h7-yolo_amd.images: could not run the build ({e}); loading the existing library after checking its build id")
+            check_id = True
+    lib = ctypes.CDLL(path)
+    lib.yf_images_build_id.restype = ctypes.c_char_p
+    lib.yf_images_build_id.argtypes = []
+    if check_id:
+        have, want = (lib.yf_images_build_id() or b"").decode(), expected_build_id()
+        if have != want:
+            raise RuntimeError(f"{path} was built from other sources (build id {have}, expected {want}) and is not being rebuilt here")
+    vp, cl, ci, cs = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_size_t
+    lib.yf_images_prepare_device.restype = cl
+    lib.yf_images_prepare_device.argtypes = [vp, cs, ci, ci, ci, cl, cl, cl, ci, vp, vp]
+    lib.yf_images_prepare_ragged_device.restype = cl
+    lib.yf_images_prepare_ragged_device.argtypes = [vp, cs, ci, vp, cl, ci, vp, vp, vp]
+    lib.yf_images_run_decode_device.restype = cl
+    lib.yf_images_run_decode_device.argtypes = [vp, vp, cs, ci, ci, ci, cl, cl, cl, vp, vp, ci, vp, vp, ci, vp]
+    lib.yf_images_run_decode_ragged_device.restype = cl
+    lib.yf_images_run_decode_ragged_device.argtypes = [vp, vp, cs, ci, vp, cl, vp, vp, ci, vp, vp, ci, vp, vp]
+    lib.yf_images_decode_ragged_device.restype = cl
+    lib.yf_images_decode_ragged_device.argtypes = [vp, vp, cl, ci, vp, vp, ci, vp]
+    lib.yf_images_last_error_text.restype = ctypes.c_char_p
+    lib.yf_images_last_error_text.argtypes = []
+    _lib = lib
+    return lib
+
+
+def format_code(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in FORMATS:
+            raise ValueError(f"format {fmt!r}: one of {sorted(FORMATS)}")
+        return FORMATS[fmt.lower()]
+    if int(fmt) not in CHANNELS:
+        raise ValueError(f"format {fmt!r}: one of YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8")
+    return int(fmt)
+
+
+def pack_images(images, fmt="bgr", align=16):
+    """uint8 images [H, W, C] (arrays or views, C = 3 or 4 as `fmt` says) -> (pixels uint8[bytes], descriptors IMAGE_DTYPE[n]).
+    An image whose pixels lie packed along its rows (channel stride 1, pixel stride C) keeps its row stride, so a crop of a larger picture is
+    copied as the span from its first to its last pixel, parent row stride and all; any other layout is made contiguous first.  Every image
+    starts on an `align`-byte boundary.  Negative strides are refused."""
+    code = format_code(fmt)
+    C = CHANNELS[code]
+    spans, desc, off = [], np.zeros(len(images), IMAGE_DTYPE), 0
+    for i, img in enumerate(images):
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != C:
+            raise ValueError(f"image {i}: expected uint8 [H, W, {C}] for format {fmt!r}, got {a.dtype} {a.shape}")
+        h, w = a.shape[:2]
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise ValueError(f"image {i}: {h}x{w} is outside 1..{MAX_SIDE} per side")
+        if any(s < 0 for s in a.strides):
+            raise ValueError(f"image {i}: negative strides {a.strides} (flip with np.ascontiguousarray first)")
+        if not (a.strides[2] == 1 and a.strides[1] == C and (h == 1 or a.strides[0] >= w * C)):
+            a = np.ascontiguousarray(a)
+        rs = a.strides[0] if h > 1 else w * C
+        extent = (h - 1) * rs + w * C
+        span = np.lib.stride_tricks.as_strided(a, shape=(extent,), strides=(1,))
+        off = -(-off // align) * align
+        desc[i] = (off, h, w, rs)
+        spans.append((off, span))
+        off += extent
+    buf = np.zeros(max(off, 1), np.uint8)
+    for o, span in spans:
+        buf[o:o + span.shape[0]] = span
+    return buf, desc
+
+
+def _check(lib, rc, n, what):
+    if rc != n:
+        raise ImagesError(f"{what}: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc}, expected {n})")
+
+
+def prepare_device(d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, out_hw, d_frames, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_prepare_device(d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n, out_hw,
+                                             d_frames, stream), n, "yf_images_prepare_device")
+
+
+def prepare_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_prepare_ragged_device(d_pixels, pixels_bytes, format_code(fmt), d_images, n, out_hw, d_frames, d_status, stream),
+           n, "yf_images_prepare_ragged_device")
+
+
+def run_decode_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames, d_heads, d_dets, d_counts,
+                      cap, mode=binding.YF_DECODE_PY, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_run_decode_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride,
+                                                n, d_frames, d_heads, mode, d_dets, d_counts, cap, stream), n, "yf_images_run_decode_device")
+
+
+def run_decode_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames, d_heads, d_dets, d_counts, cap, d_status,
+                             mode=binding.YF_DECODE_PY, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_run_decode_ragged_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames, d_heads,
+                                                       mode, d_dets, d_counts, cap, d_status, stream), n, "yf_images_run_decode_ragged_device")
+
+
+def decode_ragged_device(d_heads, d_images, n, d_dets, d_counts, cap, mode=binding.YF_DECODE_PY, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_decode_ragged_device(d_heads, d_images, n, mode, d_dets, d_counts, cap, stream), n, "yf_images_decode_ragged_device")
+
+
+def detect(network, images, fmt="bgr", cap=147, device=None):
+    """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
+    tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
+    of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network."""
+    import torch
+    n = len(images)
+    if n == 0:
+        return []
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    buf, desc = pack_images(images, fmt)
+    d_px = torch.from_numpy(buf).to(dev)
+    d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    d_frames = torch.empty((n, 56, 56, 3), dtype=torch.int8, device=dev)
+    d_heads = torch.empty((n, 7, 7, 18), dtype=torch.int8, device=dev)
+    d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
+    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    run_decode_ragged_device(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
+                             d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
+    counts = d_counts.cpu().numpy()
+    out = []
+    for i in range(n):
+        d = dets[i, :min(int(counts[i]), cap)]
+        out.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
+    return out
