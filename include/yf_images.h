@@ -64,6 +64,31 @@ YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixe
 YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode,
                                            void* d_dets, void* d_counts, int cap, void* stream);
 
+/* Greedy IoU suppression of decoded records: YoloFaceDetector.non_max_suppression of yoloface/tensorflow/yoloface_test.py:145-190
+ * (threshold 0.4 there, line 32), per frame, on the records of any decode above (or of yf_network_decode_device, the fused decode, the
+ * camera pipeline).  d_dets yf_det[n][cap], d_counts int32[n] -> d_out yf_det[n][cap], d_out_counts int32[n]; d_out may equal d_dets and
+ * d_out_counts d_counts (in place).  Records and counts 4-byte aligned.
+ *   input:  the first m = min(max(count, 0), cap) records of the frame, in decode order.  A frame whose count is above cap (the decode
+ *           wrote only cap records) is suppressed over the cap records that exist: cap >= 147, the number of candidates, gives the
+ *           reference's answer.  cap <= YF_IMAGES_NMS_MAX_CAP.
+ *   order:  descending conf, the float32 stored in the record; ties go later record first (np.argsort(conf, kind="stable")[::-1]).  The
+ *           reference's conf.argsort()[::-1] uses numpy's default sort, which is not stable, so its order among equal confidences depends
+ *           on the numpy build: this tie rule is the library's choice, and agrees with the reference whenever the confidences differ.
+ *           Ties are common: the confidence comes from an int8 logit, and the sigmoid table gives 1.0f to several of them.
+ *   arithmetic: float64, one IEEE operation per numpy operation, in the reference's order, no contraction (csrc/yf_images_nms.h):
+ *           area = (x2 - x1 + 1) * (y2 - y1 + 1); w = max(0.0, min(x2) - max(x1) + 1), h likewise; inter = w * h;
+ *           union = (area[i] + area[j]) - inter; record j survives the kept record i iff inter / union <= iou_threshold.  The int32 edges
+ *           convert exactly and products above 2^53 round as numpy's do.  Unions <= 0 occur (YF_DECODE_FW clamps can give x1 > x2, and
+ *           YF_DECODE_PY edges INT32_MIN): they follow IEEE, 0 / 0 = NaN is suppressed at every threshold, 0 / negative = -0.0.
+ *   output: the kept records byte for byte, in keep order (descending confidence, as boxes[keep]), at d_out[f][0..kept), kept in
+ *           d_out_counts[f].  Slots at and beyond the kept count are not written.
+ * iou_threshold: any value but NaN (at 0 overlapping records are suppressed and disjoint ones survive; at 1 or more only records whose
+ * union with a kept one is zero are).  One launch, no allocation, no synchronisation.  Returns n; n = 0 launches nothing and
+ * writes nothing. */
+#define YF_IMAGES_NMS_MAX_CAP 256
+YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold,
+                                 void* d_out, void* d_out_counts, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

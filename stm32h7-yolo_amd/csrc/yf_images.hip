@@ -7,12 +7,16 @@
 // -128 and the channel order fused; lanes of a wave take consecutive output columns, so the reads of a sampled source row coalesce.  The
 // frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses inside
 // the image's extent: no load reaches past its last pixel.
+//
+// NMS kernel: one 64-lane workgroup (one wave) per frame, grid-striding; see nms_kernel below.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <mutex>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/yf_images.h"
 #include "yf_images_taps.h"
+#include "yf_images_nms.h"
 #include "yf_decode.hip.h"
 #include "gen/yf_decode_tables_gen.h"
 
@@ -121,6 +125,110 @@ __global__ void __launch_bounds__(kThreads) decode_ragged_kernel(const int8_t* _
     }
     const float w_scale = (float)((double)im.width / 56.0), h_scale = (float)((double)im.height / 56.0);
     yfdec::decode_frame(heads + f * kHeadBytes, f, lane, mode, w_scale, h_scale, dets, counts, cap);
+  }
+}
+
+// Greedy IoU suppression of one frame's records per wave (yoloface_test.py:165-190; the semantics: include/yf_images.h).  The first
+// m = min(max(count, 0), cap) <= 256 records are read into LDS, all of them before anything is written (d_out may equal d_dets).
+//   rank:   lane L holds records L, L + 64, L + 128, L + 192; a record's rank is the number of larger keys (yfi_nms_key: conf descending,
+//           later record first), counted against the keys broadcast from LDS.  Edges and the other 12 bytes go to LDS at their rank.
+//   greedy: lane L takes ranks L + 64 s; the ranks still alive are four wave-uniform 64-bit masks.  For each alive rank t in ascending
+//           order, every lane tests its alive ranks above t against t's edges (an LDS broadcast) with yfi_nms_survives and the masks
+//           drop the suppressed ones -- the reference's loop, which removes a suppressed record before it can suppress.
+//   output: the alive ranks in ascending order are the kept records; a kept record's slot is the number of alive ranks below it.
+constexpr int kNmsMax = YF_IMAGES_NMS_MAX_CAP;
+
+__device__ __forceinline__ int nms_next_alive(const uint64_t (&alive)[4], int t) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int lo = t + 1 - 64 * s;
+    if (lo >= 64) continue;
+    const uint64_t mask = lo > 0 ? alive[s] & (~0ull << lo) : alive[s];
+    if (mask) return 64 * s + __builtin_ctzll(mask);
+  }
+  return kNmsMax;
+}
+
+__global__ void __launch_bounds__(64) nms_kernel(const yf_det* dets, const int* counts, long n, int cap, double thr, yf_det* out,
+                                                 int* out_counts) {
+  __shared__ uint64_t s_key[kNmsMax];          // by record
+  __shared__ int4 s_edge[kNmsMax];             // x1, y1, x2, y2 by rank
+  __shared__ int s_head[3][kNmsMax];           // frame, anchor | row | col | q_conf, conf bits, by rank
+  const int lane = threadIdx.x;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    const int c = counts[f];
+    const int m = c < 0 ? 0 : (c > cap ? cap : c);
+    const int* in = (const int*)(dets + f * cap);
+    uint64_t key[4];
+    int w[4][7];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int r = lane + 64 * s;
+      key[s] = 0;
+      if (r < m) {
+#pragma unroll
+        for (int q = 0; q < 7; ++q) w[s][q] = in[r * 7 + q];
+        key[s] = yfi_nms_key((uint32_t)w[s][2], (uint32_t)r);
+        s_key[r] = key[s];
+      }
+    }
+    __syncthreads();
+    int rank[4] = {0, 0, 0, 0};
+    for (int j = 0; j < m; ++j) {
+      const uint64_t kj = s_key[j];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        if (64 * s < m) rank[s] += kj > key[s];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (lane + 64 * s < m) {
+        const int p = rank[s];
+        s_edge[p] = make_int4(w[s][3], w[s][4], w[s][5], w[s][6]);
+        s_head[0][p] = w[s][0]; s_head[1][p] = w[s][1]; s_head[2][p] = w[s][2];
+      }
+    }
+    __syncthreads();
+    int4 e[4];
+    double area[4];
+    uint64_t alive[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int p = lane + 64 * s;
+      e[s] = make_int4(0, 0, 0, 0);
+      if (p < m) e[s] = s_edge[p];
+      area[s] = yfi_nms_area(e[s].x, e[s].y, e[s].z, e[s].w);
+      alive[s] = __ballot(p < m);
+    }
+    for (int t = m > 0 ? 0 : kNmsMax; t < m; t = nms_next_alive(alive, t)) {
+      const int4 a = s_edge[t];
+      const double area_a = yfi_nms_area(a.x, a.y, a.z, a.w);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int lo = t + 1 - 64 * s;                         // no alive rank above t in this slot: skip it
+        if (lo >= 64 || 64 * s >= m || (lo > 0 ? alive[s] & (~0ull << lo) : alive[s]) == 0) continue;
+        const int p = lane + 64 * s;
+        bool sup = false;
+        if (p > t && ((alive[s] >> lane) & 1ull))
+          sup = !yfi_nms_survives(a.x, a.y, a.z, a.w, area_a, e[s].x, e[s].y, e[s].z, e[s].w, area[s], thr);
+        alive[s] &= ~__ballot(sup);
+      }
+    }
+    int* o = (int*)(out + f * cap);
+    int kept = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int p = lane + 64 * s;
+      if (p < m && ((alive[s] >> lane) & 1ull)) {
+        const int slot = kept + __popcll(alive[s] & below);
+        o[slot * 7 + 0] = s_head[0][p]; o[slot * 7 + 1] = s_head[1][p]; o[slot * 7 + 2] = s_head[2][p];
+        o[slot * 7 + 3] = e[s].x; o[slot * 7 + 4] = e[s].y; o[slot * 7 + 5] = e[s].z; o[slot * 7 + 6] = e[s].w;
+      }
+      kept += __popcll(alive[s]);
+    }
+    if (lane == 0) out_counts[f] = kept;
+    __syncthreads();                           // the LDS of this frame is read before the next frame's records land
   }
 }
 
@@ -314,6 +422,29 @@ YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* 
   if (!check_decode((void*)d_heads, mode, d_dets, d_counts, cap)) return 0;
   if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
   return decode_ragged(d_heads, d_images, nullptr, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,
+                                 void* d_out_counts, void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (cap <= 0 || cap > YF_IMAGES_NMS_MAX_CAP) return fail("cap must be in [1, 256]");
+  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (!d_out) return fail("d_out is NULL");
+  if (!d_out_counts) return fail("d_out_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_out & 3) != 0) return fail("d_out is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_out_counts & 3) != 0) return fail("d_counts or d_out_counts is not 4-byte aligned");
+  if (n == 0) return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const long grid = n < (long)cus * 16 ? n : (long)cus * 16;     // 16 one-wave workgroups per CU (9 KB of LDS each)
+  hipLaunchKernelGGL(nms_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, (const yf_det*)d_dets, (const int*)d_counts, n, cap,
+                     iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip("nms kernel launch", e);
+  return n;
 }
 
 }  // extern "C"

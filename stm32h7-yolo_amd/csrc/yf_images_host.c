@@ -1,8 +1,9 @@
-/* Host build of the resize arithmetic in yf_images_taps.h (the functions the device kernel calls), for the CPU tests only:
- * libyf_images_host.so, no HIP. */
+/* Host build of the resize arithmetic in yf_images_taps.h and the suppression arithmetic in yf_images_nms.h (the functions the device
+ * kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
 #include "yf_images_taps.h"
+#include "yf_images_nms.h"
 
 #define EXPORT __attribute__((visibility("default")))
 
@@ -30,6 +31,21 @@ EXPORT int yfi_resize_host(const uint8_t* src, int h, int w, int C, long rs, int
   }
   return 0;
 }
+
+/* The suppression's pairwise decision (yf_images_nms.h) over n pairs: a[k], b[k] int32[4] edges (x1, y1, x2, y2), box a the kept one;
+ * out[k] = 1 if b survives a at thr.  area[2k], area[2k + 1] = the two areas when `area` is not NULL. */
+EXPORT void yfi_nms_pairs_host(const int32_t* a, const int32_t* b, long n, double thr, uint8_t* out, double* area) {
+  for (long k = 0; k < n; ++k) {
+    const int32_t* p = a + 4 * k;
+    const int32_t* q = b + 4 * k;
+    const double ap = yfi_nms_area(p[0], p[1], p[2], p[3]), aq = yfi_nms_area(q[0], q[1], q[2], q[3]);
+    out[k] = (uint8_t)yfi_nms_survives(p[0], p[1], p[2], p[3], ap, q[0], q[1], q[2], q[3], aq, thr);
+    if (area) { area[2 * k] = ap; area[2 * k + 1] = aq; }
+  }
+}
+
+/* the order key of a record (yfi_nms_key) */
+EXPORT uint64_t yfi_nms_key_host(uint32_t conf_bits, uint32_t index) { return yfi_nms_key(conf_bits, index); }
 
 EXPORT int yfi_image_ok_host(uint64_t offset, int64_t h, int64_t w, int64_t rs, int C, uint64_t bytes) {
   return yfi_image_ok(offset, h, w, rs, C, bytes);

@@ -3,7 +3,8 @@
 imgproc/resize.cpp that has not been pinned against a real cv2 -- and on through the network to boxes in each image's own pixels.
 
 `detect(network, images)` is lines 29-61 of the reference's yoloface/tflite/tflite_prediction.py for a whole batch: imread (BGR), BGR -> RGB,
-cv2.resize to 56x56, minus 128, int8, the network, decode, boxes scaled by W/56. and H/56.
+cv2.resize to 56x56, minus 128, int8, the network, decode, boxes scaled by W/56. and H/56.  With `iou_threshold` it adds the greedy IoU
+suppression of yoloface/tensorflow/yoloface_test.py:145-190 on the GPU (`nms_device`, include/yf_images.h).
 """
 import ctypes
 import hashlib
@@ -22,6 +23,7 @@ YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8 = 0, 1, 2, 3
 FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba": YF_PIX_RGBA8}
 CHANNELS = {YF_PIX_BGR8: 3, YF_PIX_RGB8: 3, YF_PIX_BGRA8: 4, YF_PIX_RGBA8: 4}
 MAX_SIDE = 16384
+NMS_MAX_CAP = 256
 FRAME_BYTES = {56: 56 * 56 * 3, 160: 160 * 160 * 3}
 
 
@@ -111,6 +113,8 @@ def load():
     lib.yf_images_run_decode_ragged_device.argtypes = [vp, vp, cs, ci, vp, cl, vp, vp, ci, vp, vp, ci, vp, vp]
     lib.yf_images_decode_ragged_device.restype = cl
     lib.yf_images_decode_ragged_device.argtypes = [vp, vp, cl, ci, vp, vp, ci, vp]
+    lib.yf_images_nms_device.restype = cl
+    lib.yf_images_nms_device.argtypes = [vp, vp, cl, ci, ctypes.c_double, vp, vp, vp]
     lib.yf_images_last_error_text.restype = ctypes.c_char_p
     lib.yf_images_last_error_text.argtypes = []
     _lib = lib
@@ -195,10 +199,22 @@ def decode_ragged_device(d_heads, d_images, n, d_dets, d_counts, cap, mode=bindi
     _check(lib, lib.yf_images_decode_ragged_device(d_heads, d_images, n, mode, d_dets, d_counts, cap, stream), n, "yf_images_decode_ragged_device")
 
 
-def detect(network, images, fmt="bgr", cap=147, device=None):
+def nms_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_counts=None, stream=None):
+    """Greedy IoU suppression of decoded records (yf_images_nms_device): d_dets yf_det[n][cap], d_counts int32[n] -> d_out, d_out_counts
+    (in place when not given).  Order: descending conf, ties later record first; float64 arithmetic as yoloface_test.py:165-190 states it."""
+    lib = load()
+    d_out = d_dets if d_out is None else d_out
+    d_out_counts = d_counts if d_out_counts is None else d_out_counts
+    _check(lib, lib.yf_images_nms_device(d_dets, d_counts, n, cap, float(iou_threshold), d_out, d_out_counts, stream), n,
+           "yf_images_nms_device")
+
+
+def detect(network, images, fmt="bgr", cap=147, device=None, iou_threshold=None):
     """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
     tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
-    of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network."""
+    of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network.  iou_threshold=None returns every record above the
+    confidence threshold in decode order; a float (yoloface_test.py uses 0.4) suppresses them in place on the same stream (nms_device) and
+    returns the kept boxes in keep order, highest confidence first."""
     import torch
     n = len(images)
     if n == 0:
@@ -215,6 +231,8 @@ def detect(network, images, fmt="bgr", cap=147, device=None):
     stream = torch.cuda.current_stream(dev)
     run_decode_ragged_device(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
                              d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    if iou_threshold is not None:
+        nms_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
     stream.synchronize()
     dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
     counts = d_counts.cpu().numpy()
