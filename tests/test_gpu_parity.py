@@ -133,32 +133,9 @@ def test_structured_extreme_frames(network, oracle, torch_cuda):
     that layer can produce, both signs), and per-pixel random extremes.  Every head byte must equal the oracle's, through the device path on a ragged batch."""
     torch = torch_cuda
     from oracle.np_restatement import load_yfm
-    m = load_yfm(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"))
-    frames = []
-    for r in (-128, 127):
-        for g in (-128, 127):
-            for b in (-128, 127):
-                frames.append(np.broadcast_to(np.array([r, g, b], np.int8), (56, 56, 3)).copy())
-    yy, xx = np.mgrid[0:56, 0:56]
-    for period in (1, 2, 4, 7):
-        for pat in ((xx // period) % 2, (yy // period) % 2, ((xx // period) + (yy // period)) % 2):
-            f = np.where(pat[..., None] == 1, 127, -128).astype(np.int8)
-            frames += [np.broadcast_to(f, (56, 56, 3)).copy(), (-1 - np.broadcast_to(f, (56, 56, 3))).astype(np.int8)]
-    for (y, x) in ((0, 0), (0, 55), (55, 0), (55, 55), (0, 27), (27, 0), (55, 28), (28, 55), (27, 27)):
-        for base, hot in ((-128, 127), (127, -128), (0, 127)):
-            f = np.full((56, 56, 3), base, np.int8)
-            f[y, x] = hot
-            frames.append(f)
-    conv1 = next(o for o in m["ops"] if o["op"] == 3)                            # CONV_2D #1: conv2d_1, 3x3 stride 2 behind the explicit top/left PAD
-    w = np.asarray(m["tensors"][conv1["ins"][1]]["data"]).reshape(8, 3, 3, 3)   # OHWI int8
-    ky = np.where((np.arange(56) + 1) % 2 == 1, 1, 0)                             # input row y is padded row y + 1: odd -> the window's middle tap, even -> its first
-    for o in range(8):
-        for sign in (1, -1):
-            t = w[o][ky][:, ky].astype(np.int32) * sign                           # [56, 56, 3]: the weight each input value meets in (one of) its windows
-            frames.append(np.where(t >= 0, 127, -128).astype(np.int8))
-    rng = np.random.default_rng(99)
-    frames += list(np.where(rng.integers(0, 2, (12, 56, 56, 3)) == 1, 127, -128).astype(np.int8))
-    x = np.stack(frames)
+    from model_variants import structured_extreme_frames                         # the generator: shared with the tests on other weight blobs
+    x = structured_extreme_frames(load_yfm(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm")))
+    assert x.shape == (87, 56, 56, 3) and x.dtype == np.int8
     ref = oracle.run(x, threads=16)
     d_in = torch.from_numpy(x).cuda()
     d_out = torch.full((x.shape[0] + 1, 7, 7, 18), 55, dtype=torch.int8, device="cuda")
@@ -607,30 +584,9 @@ def test_160x160_band_edges(network, oracle, torch_cuda):
     hot pixels and short vertical bars at input rows 30..33, 62..65, 94..97, 126..129 and at the image's first / last rows and columns, stripes whose period
     is the band height or half of it, a frame per band that is noise inside ONE band and constant elsewhere -- must give the oracle's heads bit for bit."""
     torch = torch_cuda
-    frames = []
-    for cut in (32, 64, 96, 128):
-        for dy in (-2, -1, 0, 1):
-            f = np.full((160, 160, 3), -128, np.int8)
-            f[cut + dy, :, :] = 127                                           # one hot row next to / on a band cut
-            frames.append(f)
-        f = np.full((160, 160, 3), 127, np.int8)
-        f[cut - 3:cut + 3, 40:43, :] = -128                                   # a short cold bar across the cut
-        f[cut - 1, 0, :] = -128; f[cut, 159, :] = -128                        # ... and cold pixels on the cut at both borders
-        frames.append(f)
-    for y, x in ((0, 0), (0, 159), (159, 0), (159, 159), (0, 80), (159, 79), (80, 0), (79, 159)):
-        f = np.zeros((160, 160, 3), np.int8)
-        f[y, x] = (127, -128, 127)
-        frames.append(f)
-    yy = np.arange(160)[:, None, None]
-    for period in (8, 16, 32):
-        frames.append(np.broadcast_to(np.where((yy // period) % 2 == 1, 127, -128), (160, 160, 3)).astype(np.int8).copy())
-        frames.append(np.broadcast_to(np.where(((yy + period // 2) // period) % 2 == 1, 127, -128), (160, 160, 3)).astype(np.int8).copy())
-    rng = np.random.default_rng(160)
-    for band in range(5):
-        f = np.full((160, 160, 3), 3, np.int8)
-        f[32 * band:32 * band + 32] = rng.integers(-128, 128, (32, 160, 3), dtype=np.int8)      # noise inside one band only
-        frames.append(f)
-    x = np.stack(frames)
+    from model_variants import band_edge_frames_160                              # the generator: shared with the tests on other weight blobs
+    x = band_edge_frames_160()
+    assert x.shape == (39, 160, 160, 3) and x.dtype == np.int8
     ref = oracle.run(x, threads=16)
     d_in = torch.from_numpy(x).cuda()
     d_out = torch.full((x.shape[0] + 1, 20, 20, 18), 77, dtype=torch.int8, device="cuda")
@@ -920,9 +876,10 @@ def test_run_argument_errors_are_latched(network):
     torch.cuda.synchronize()
 
 
-def test_weights_come_from_the_callers_blob(yf, network, oracle):
+def test_weights_come_from_the_callers_blob(yf, network, oracle, tmp_path):
     """ai_network_init reads the blob it is handed (network.c:3108-3267 binds the caller's blob): perturbing one
-    weight byte of a caller-owned copy changes the output; the pristine copy reproduces the oracle."""
+    weight byte of a caller-owned copy changes the output -- to what the oracle computes from a model file with the same
+    perturbation (tests/model_variants.py); the pristine copy reproduces the oracle."""
     lib = network.lib
     m = ctypes.cast(lib.ai_network_data_weights_get(), ctypes.POINTER(ctypes.c_void_p))
     blob = np.frombuffer((ctypes.c_uint8 * 11304).from_address(m[1]), np.uint8).copy()
@@ -932,9 +889,19 @@ def test_weights_come_from_the_callers_blob(yf, network, oracle):
     assert np.array_equal(network.run(x), ref)
     bad = blob.copy()
     bad[10656 + 5] ^= 0x40            # one weight of the head conv (ST blob offset 10656, network.c:3259)
-    network.init(weights=bad)
-    assert not np.array_equal(network.run(x), ref)
-    network.init()
+    import model_variants as mv
+    from oracle.oracle import Oracle
+    w = mv.model().w[53].copy()
+    w.reshape(-1)[5] ^= 0x40
+    same_blob, yfm_path = mv.model().write({53: w}, {}, tmp_path / "perturbed.yfm")
+    assert same_blob == bad.tobytes()
+    try:
+        network.init(weights=bad)
+        got = network.run(x)
+    finally:
+        network.init()
+    assert not np.array_equal(got, ref)
+    assert np.array_equal(got, Oracle(yfm_path).run(x))
     assert np.array_equal(network.run(x), ref)
 
 
