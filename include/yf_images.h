@@ -36,7 +36,7 @@ enum { YF_PIX_BGR8 = 0 /* cv2.imread */, YF_PIX_RGB8 = 1, YF_PIX_BGRA8 = 2, YF_P
 #define YF_IMAGES_MAX_SIDE 16384   /* 1 <= height, width <= this */
 
 /* frame[y][x][c] = (int8)(R[y][x][rgb(c)] - 128), R = cv2.resize(image, (out_hw, out_hw)).  out_hw = 56 (the network's input) or 160
- * (frames for yf_network_run_device_hw; decode at 160 is not offered).  d_frames int8[n][out_hw][out_hw][3]. */
+ * (frames for yf_network_run_device_hw; boxes at 160: the *160* entries below).  d_frames int8[n][out_hw][out_hw][3]. */
 
 /* Uniform batch: n images of height x width, image i at d_pixels + i * frame_stride, rows row_stride bytes apart (a video, an [n,H,W,C]
  * tensor, or crops of one: row_stride >= width * C, frame_stride >= 0).  Every argument is checked before any launch; an image that
@@ -88,6 +88,39 @@ YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* 
 #define YF_IMAGES_NMS_MAX_CAP 256
 YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold,
                                  void* d_out, void* d_out_counts, void* stream);
+
+/* ---- 160x160 frames: the network is fully convolutional and a larger input finds smaller faces (yf_network_run_device_hw: heads
+ * int8[n][20][20][18]).  The decode is tflite_prediction.py:43-63 with the hard-coded 7 of line 50 read as the script's own nx, ny (20):
+ * stride 8 and the anchors unchanged, W/56. read as W/160.  3 x 20 x 20 = 1200 candidates per frame.  Only the script's decode exists at
+ * this size: the firmware's loop (49 cells, clamp to 55, LCD axis swap) has no meaning here, so there is no mode argument. */
+#define YF_IMAGES_GRID160      20
+#define YF_IMAGES_CAND160    1200          /* 3 anchors x 20 x 20 */
+/* d_heads int8[n][20][20][18] (16-byte aligned) -> records as yf_network_decode_device writes them in YF_DECODE_PY: order (anchor, row,
+ * col), conf > 0.7f, d_counts int32[n] = the true count (may exceed cap), only the first cap records written (slots beyond
+ * min(count, cap) are not touched).  1 <= cap <= 1200.  One launch of its own; n = 0 launches nothing and returns 0. */
+YF_API long yf_images_decode160_device(const void* d_heads, long n, float w_scale, float h_scale,
+                                       void* d_dets, void* d_counts, int cap, void* stream);
+/* Per-image scales: w_scale = (float)((double)W / 160.0), h_scale likewise.  d_status (int32[n], as yf_images_prepare_ragged_device
+ * wrote it) may be NULL; status 1 or a side outside [1, 16384] gives count 0. */
+YF_API long yf_images_decode160_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n,
+                                              void* d_dets, void* d_counts, int cap, void* stream);
+/* Images -> frames (d_frames int8[n][160][160][3], the caller's workspace) -> yf_network_run_device_hw(net, 160, 160) -> heads ->
+ * records, on one stream: the prepare above at out_hw = 160, the network with the requantisation rounding selected on it, then the decode
+ * of 20x20 heads as a launch of its own.  Arguments are checked as by the 56x56 forms, all before the first launch; in the ragged form an
+ * invalid image (d_status 1) gets an all -128 frame and count 0. */
+YF_API long yf_images_run_decode160_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                           long row_stride, long frame_stride, long n, void* d_frames, void* d_heads,
+                                           void* d_dets, void* d_counts, int cap, void* stream);
+YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                  const yf_image* d_images, long n, void* d_frames, void* d_heads,
+                                                  void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+/* yf_images_nms_device for up to 1200 records per frame: the same input, order, arithmetic and output, word for word, with
+ * 1 <= cap <= YF_IMAGES_NMS_WIDE_MAX_CAP; on inputs both accept the two give identical bytes.  One workgroup per four frames; what a
+ * frame costs follows its own record count, not cap: a frame of up to 64 records is one wave's work in registers, a larger one is ranked
+ * and suppressed by the workgroup in LDS, serially in the number of kept records as the reference's loop is. */
+#define YF_IMAGES_NMS_WIDE_MAX_CAP 1200
+YF_API long yf_images_nms_wide_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold,
+                                      void* d_out, void* d_out_counts, void* stream);
 
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */

@@ -9,6 +9,7 @@
 // the image's extent: no load reaches past its last pixel.
 //
 // NMS kernel: one 64-lane workgroup (one wave) per frame, grid-striding; see nms_kernel below.
+// 160x160 frames: the decode of 20x20 heads and the suppression of up to 1200 records per frame are the kernels of yf_images_wide.hip.h.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <mutex>
@@ -19,6 +20,8 @@
 #include "yf_images_nms.h"
 #include "yf_decode.hip.h"
 #include "gen/yf_decode_tables_gen.h"
+#include "yf_images_decode160.h"
+#include "yf_images_wide.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -337,6 +340,7 @@ bool tables_ready(hipStream_t s) {
   if (dev < 0 || dev >= 64) { fail("device index out of range"); return false; }
   std::lock_guard<std::mutex> lk(g_tables_mu);
   if (g_tables_on[dev]) return true;
+  if (!yfi_d160_monotonic(yf_sigmoid_bits)) { fail("sigmoid table is not monotonic"); return false; }     // decode160 compares quantised confidences
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
     fail("the first per-image-scale decode on a device uploads its tables: make one call outside stream capture first");
@@ -357,6 +361,35 @@ long decode_ragged(const void* d_heads, const yf_image* d_images, const int32_t*
                      (const int8_t*)d_heads, d_images, d_status, n, mode, (yf_det*)d_dets, (int*)d_counts, cap);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip("decode kernel launch", e);
+  return n;
+}
+
+bool check_decode160(const void* d_heads, void* d_dets, void* d_counts, int cap) {
+  if (!d_heads) { fail("d_heads is NULL"); return false; }
+  if (((uintptr_t)d_heads & 15) != 0) { fail("d_heads is not 16-byte aligned"); return false; }
+  if (!d_dets) { fail("d_dets is NULL"); return false; }
+  if (!d_counts) { fail("d_counts is NULL"); return false; }
+  if (((uintptr_t)d_dets & 3) != 0) { fail("d_dets is not 4-byte aligned"); return false; }
+  if (((uintptr_t)d_counts & 3) != 0) { fail("d_counts is not 4-byte aligned"); return false; }
+  if (cap <= 0 || cap > YF_IMAGES_CAND160) { fail("cap must be in [1, 1200]"); return false; }
+  return true;
+}
+
+// d_images == nullptr: the scalar scales; else per-image scales (and d_status, which may be nullptr)
+long decode160(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, float w_scale, float h_scale, void* d_dets,
+               void* d_counts, int cap, hipStream_t s) {
+  if (n == 0) return 0;
+  if (!tables_ready(s)) return 0;
+  const int q_thr = yfi_d160_q_threshold(yf_sigmoid_bits);
+  const dim3 grid((unsigned)grid_for(n)), block(yfwide::kThreads);                // 9.2 KB of LDS per workgroup
+  if (d_images)
+    hipLaunchKernelGGL(yfwide::decode160_kernel<true>, grid, block, 0, s, (const int8_t*)d_heads, d_images, d_status, n, 0.f, 0.f, q_thr,
+                       (yf_det*)d_dets, (int*)d_counts, cap);
+  else
+    hipLaunchKernelGGL(yfwide::decode160_kernel<false>, grid, block, 0, s, (const int8_t*)d_heads, (const yf_image*)nullptr,
+                       (const int32_t*)nullptr, n, w_scale, h_scale, q_thr, (yf_det*)d_dets, (int*)d_counts, cap);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip("decode160 kernel launch", e);
   return n;
 }
 
@@ -444,6 +477,75 @@ YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long 
                      iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip("nms kernel launch", e);
+  return n;
+}
+
+YF_API long yf_images_decode160_device(const void* d_heads, long n, float w_scale, float h_scale, void* d_dets, void* d_counts, int cap,
+                                       void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  return decode160(d_heads, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode160_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, void* d_dets,
+                                              void* d_counts, int cap, void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
+  if (((uintptr_t)d_status & 3) != 0) return fail("d_status is not 4-byte aligned");
+  return decode160(d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_run_decode160_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                           long row_stride, long frame_stride, long n, void* d_frames, void* d_heads, void* d_dets,
+                                           void* d_counts, int cap, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 160, d_frames, &a)) return 0;
+  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  if (n == 0) return 0;
+  if (!tables_ready((hipStream_t)stream)) return 0;
+  if (prepare(160, format, a, false, (hipStream_t)stream) != n) return 0;
+  if (yf_network_run_device_hw(net, 160, 160, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device_hw");
+  const float w_scale = (float)((double)width / 160.0), h_scale = (float)((double)height / 160.0);
+  return decode160(d_heads, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                  const yf_image* d_images, long n, void* d_frames, void* d_heads, void* d_dets,
+                                                  void* d_counts, int cap, int32_t* d_status, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 160, d_frames, d_status, &a)) return 0;
+  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  if (n == 0) return 0;
+  if (!tables_ready((hipStream_t)stream)) return 0;
+  if (prepare(160, format, a, true, (hipStream_t)stream) != n) return 0;
+  if (yf_network_run_device_hw(net, 160, 160, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device_hw");
+  return decode160(d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_nms_wide_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,
+                                      void* d_out_counts, void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (cap <= 0 || cap > YF_IMAGES_NMS_WIDE_MAX_CAP) return fail("cap must be in [1, 1200]");
+  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (!d_out) return fail("d_out is NULL");
+  if (!d_out_counts) return fail("d_out_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_out & 3) != 0) return fail("d_out is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_out_counts & 3) != 0) return fail("d_counts or d_out_counts is not 4-byte aligned");
+  if (n == 0) return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const long groups = (n + yfwide::kWaves - 1) / yfwide::kWaves;                  // four frames per workgroup
+  const long grid = groups < (long)cus * 3 ? groups : (long)cus * 3;              // 3 workgroups per CU (43.5 KB of LDS each)
+  hipLaunchKernelGGL(yfwide::nms_wide_kernel, dim3((unsigned)grid), dim3(yfwide::kThreads), 0, (hipStream_t)stream, (const yf_det*)d_dets,
+                     (const int*)d_counts, n, cap, iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip("nms_wide kernel launch", e);
   return n;
 }
 

@@ -1,9 +1,11 @@
-/* Host build of the resize arithmetic in yf_images_taps.h and the suppression arithmetic in yf_images_nms.h (the functions the device
- * kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
+/* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h and the 20x20 decode arithmetic in
+ * yf_images_decode160.h (the functions the device kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
 #include "yf_images_taps.h"
 #include "yf_images_nms.h"
+#include "yf_images_decode160.h"
+#include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
 
@@ -46,6 +48,25 @@ EXPORT void yfi_nms_pairs_host(const int32_t* a, const int32_t* b, long n, doubl
 
 /* the order key of a record (yfi_nms_key) */
 EXPORT uint64_t yfi_nms_key_host(uint32_t conf_bits, uint32_t index) { return yfi_nms_key(conf_bits, index); }
+
+/* ... and with room for an 11-bit index (yfi_nms_key_wide) */
+EXPORT uint64_t yfi_nms_key_wide_host(uint32_t conf_bits, uint32_t index) { return yfi_nms_key_wide(conf_bits, index); }
+
+/* The decode of one 20x20 head as decode160_kernel computes it: the byte test q >= q_thr in candidate order (anchor, row, col), the
+ * per-candidate record of yf_images_decode160.h for the candidates that fire, the first `cap` written.  Returns the true count. */
+EXPORT int yfi_decode160_host(const int8_t* head, int32_t frame, float w_scale, float h_scale, yf_det* dets, int cap) {
+  const int q_thr = yfi_d160_q_threshold(yf_sigmoid_bits);
+  int n = 0;
+  for (int i = 0; i < YF_IMAGES_CAND160; ++i) {
+    const int8_t* p = head + yfi_d160_offset(i);
+    if (p[4] < q_thr) continue;
+    if (n < cap) dets[n] = yfi_d160_candidate(p, i, frame, yf_sigmoid_bits, yf_exp_bits, w_scale, h_scale);
+    ++n;
+  }
+  return n;
+}
+
+EXPORT int yfi_decode160_q_threshold_host(void) { return yfi_d160_monotonic(yf_sigmoid_bits) ? yfi_d160_q_threshold(yf_sigmoid_bits) : -129; }
 
 EXPORT int yfi_image_ok_host(uint64_t offset, int64_t h, int64_t w, int64_t rs, int C, uint64_t bytes) {
   return yfi_image_ok(offset, h, w, rs, C, bytes);

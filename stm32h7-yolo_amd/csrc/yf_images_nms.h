@@ -57,4 +57,10 @@ YFI_HD uint64_t yfi_nms_key(uint32_t conf_bits, uint32_t index) {
   return ((uint64_t)u << 8) | (uint64_t)index;
 }
 
+/* The same order for yf_images_nms_wide_device (up to 1200 records per frame): the same mapping of conf's bits above an 11-bit record
+ * index.  Index < 2048. */
+YFI_HD uint64_t yfi_nms_key_wide(uint32_t conf_bits, uint32_t index) {
+  return ((yfi_nms_key(conf_bits, 0u) >> 8) << 11) | (uint64_t)index;
+}
+
 #endif

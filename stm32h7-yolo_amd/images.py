@@ -4,7 +4,8 @@ imgproc/resize.cpp that has not been pinned against a real cv2 -- and on through
 
 `detect(network, images)` is lines 29-61 of the reference's yoloface/tflite/tflite_prediction.py for a whole batch: imread (BGR), BGR -> RGB,
 cv2.resize to 56x56, minus 128, int8, the network, decode, boxes scaled by W/56. and H/56.  With `iou_threshold` it adds the greedy IoU
-suppression of yoloface/tensorflow/yoloface_test.py:145-190 on the GPU (`nms_device`, include/yf_images.h).
+suppression of yoloface/tensorflow/yoloface_test.py:145-190 on the GPU (`nms_device`, include/yf_images.h).  `size=160` runs the same path
+on 160x160 frames (20x20 heads, 1200 candidates per image: `run_decode160_ragged_device`, `nms_wide_device`).
 """
 import ctypes
 import hashlib
@@ -24,6 +25,8 @@ FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba":
 CHANNELS = {YF_PIX_BGR8: 3, YF_PIX_RGB8: 3, YF_PIX_BGRA8: 4, YF_PIX_RGBA8: 4}
 MAX_SIDE = 16384
 NMS_MAX_CAP = 256
+NMS_WIDE_MAX_CAP = 1200
+GRID160, CAND160 = 20, 1200
 FRAME_BYTES = {56: 56 * 56 * 3, 160: 160 * 160 * 3}
 
 
@@ -115,6 +118,17 @@ def load():
     lib.yf_images_decode_ragged_device.argtypes = [vp, vp, cl, ci, vp, vp, ci, vp]
     lib.yf_images_nms_device.restype = cl
     lib.yf_images_nms_device.argtypes = [vp, vp, cl, ci, ctypes.c_double, vp, vp, vp]
+    cf = ctypes.c_float
+    lib.yf_images_decode160_device.restype = cl
+    lib.yf_images_decode160_device.argtypes = [vp, cl, cf, cf, vp, vp, ci, vp]
+    lib.yf_images_decode160_ragged_device.restype = cl
+    lib.yf_images_decode160_ragged_device.argtypes = [vp, vp, vp, cl, vp, vp, ci, vp]
+    lib.yf_images_run_decode160_device.restype = cl
+    lib.yf_images_run_decode160_device.argtypes = [vp, vp, cs, ci, ci, ci, cl, cl, cl, vp, vp, vp, vp, ci, vp]
+    lib.yf_images_run_decode160_ragged_device.restype = cl
+    lib.yf_images_run_decode160_ragged_device.argtypes = [vp, vp, cs, ci, vp, cl, vp, vp, vp, vp, ci, vp, vp]
+    lib.yf_images_nms_wide_device.restype = cl
+    lib.yf_images_nms_wide_device.argtypes = [vp, vp, cl, ci, ctypes.c_double, vp, vp, vp]
     lib.yf_images_last_error_text.restype = ctypes.c_char_p
     lib.yf_images_last_error_text.argtypes = []
     _lib = lib
@@ -209,12 +223,56 @@ def nms_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_counts
            "yf_images_nms_device")
 
 
-def detect(network, images, fmt="bgr", cap=147, device=None, iou_threshold=None):
+def decode160_device(d_heads, n, d_dets, d_counts, cap, w_scale=1.0, h_scale=1.0, stream=None):
+    """Decode of 20x20 heads (yf_images_decode160_device): d_heads int8[n][20][20][18] -> d_dets yf_det[n][cap], d_counts int32[n]."""
+    lib = load()
+    _check(lib, lib.yf_images_decode160_device(d_heads, n, w_scale, h_scale, d_dets, d_counts, cap, stream), n, "yf_images_decode160_device")
+
+
+def decode160_ragged_device(d_heads, d_images, n, d_dets, d_counts, cap, d_status=None, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_decode160_ragged_device(d_heads, d_images, d_status, n, d_dets, d_counts, cap, stream), n,
+           "yf_images_decode160_ragged_device")
+
+
+def run_decode160_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames, d_heads, d_dets, d_counts,
+                         cap, stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_run_decode160_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride,
+                                                   frame_stride, n, d_frames, d_heads, d_dets, d_counts, cap, stream), n,
+           "yf_images_run_decode160_device")
+
+
+def run_decode160_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames, d_heads, d_dets, d_counts, cap, d_status,
+                                stream=None):
+    lib = load()
+    _check(lib, lib.yf_images_run_decode160_ragged_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames,
+                                                          d_heads, d_dets, d_counts, cap, d_status, stream), n,
+           "yf_images_run_decode160_ragged_device")
+
+
+def nms_wide_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_counts=None, stream=None):
+    """nms_device for up to NMS_WIDE_MAX_CAP records per frame (yf_images_nms_wide_device): the same semantics, in place when d_out is not
+    given."""
+    lib = load()
+    d_out = d_dets if d_out is None else d_out
+    d_out_counts = d_counts if d_out_counts is None else d_out_counts
+    _check(lib, lib.yf_images_nms_wide_device(d_dets, d_counts, n, cap, float(iou_threshold), d_out, d_out_counts, stream), n,
+           "yf_images_nms_wide_device")
+
+
+def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56):
     """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
     tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
     of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network.  iou_threshold=None returns every record above the
     confidence threshold in decode order; a float (yoloface_test.py uses 0.4) suppresses them in place on the same stream (nms_device) and
-    returns the kept boxes in keep order, highest confidence first."""
+    returns the kept boxes in keep order, highest confidence first.  size: the side of the network's frames, 56 (7x7 heads) or 160 (20x20
+    heads, which find smaller faces; suppression through nms_wide_device); cap=None holds every candidate: 147 / 1200."""
+    if size not in (56, 160):
+        raise ValueError(f"size {size!r}: 56 or 160")
+    grid = size // 8
+    if cap is None:
+        cap = 3 * grid * grid
     import torch
     n = len(images)
     if n == 0:
@@ -223,16 +281,17 @@ def detect(network, images, fmt="bgr", cap=147, device=None, iou_threshold=None)
     buf, desc = pack_images(images, fmt)
     d_px = torch.from_numpy(buf).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
-    d_frames = torch.empty((n, 56, 56, 3), dtype=torch.int8, device=dev)
-    d_heads = torch.empty((n, 7, 7, 18), dtype=torch.int8, device=dev)
+    d_frames = torch.empty((n, size, size, 3), dtype=torch.int8, device=dev)
+    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.int8, device=dev)
     d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     d_counts = torch.empty(n, dtype=torch.int32, device=dev)
     d_status = torch.empty(n, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
-    run_decode_ragged_device(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
-                             d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
+    run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
+        d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
     if iou_threshold is not None:
-        nms_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
+        nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
     stream.synchronize()
     dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
     counts = d_counts.cpu().numpy()
