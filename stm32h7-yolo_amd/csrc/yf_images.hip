@@ -2,16 +2,18 @@
 // the arithmetic of yf_images_taps.h), and on through libyf_network.so's public C-ABI to detection records in each image's own pixels.
 // C-ABI and semantics: include/yf_images.h.
 //
-// Kernel: one 256-thread workgroup per frame (grid-striding over the batch).  Lanes build the out_hw x-taps and y-taps in LDS, then each
-// lane computes whole output pixels: four byte-wide reads per channel (two source rows, two columns), horizontal then vertical pass, the
-// -128 and the channel order fused; lanes of a wave take consecutive output columns, so the reads of a sampled source row coalesce.  The
-// frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses inside
-// the image's extent: no load reaches past its last pixel.
-//
-// NMS kernel: one 64-lane workgroup (one wave) per frame, grid-striding; see nms_kernel below.
-// 160x160 frames: the decode of 20x20 heads and the suppression of up to 1200 records per frame are the kernels of yf_images_wide.hip.h.
+// Prepare kernel: one 256-thread workgroup per frame (grid-striding over the batch).  Lanes build the out_hw x-taps and y-taps in LDS, then
+// each lane computes whole output pixels: four byte-wide reads per channel (two source rows, two columns), horizontal then vertical pass,
+// the -128 and the channel order fused; lanes of a wave take consecutive output columns, so the reads of a sampled source row coalesce.
+// The frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses
+// inside the image's extent: no load reaches past its last pixel.
+// The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame) and nms_kernel (up to 256 records, one
+// wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h.
+// After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
+// launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstdarg>
 #include <mutex>
 #include <stdint.h>
 #include <stdio.h>
@@ -235,16 +237,39 @@ __global__ void __launch_bounds__(64) nms_kernel(const yf_det* dets, const int* 
   }
 }
 
+// ---- host ----
+// Every entry point checks all of its arguments before its first launch and reports the first fault it finds (the order of the checks is
+// part of the behaviour).  fail() takes printf arguments and returns 0: "no frames" in an entry point, false in a check.
 thread_local char g_err[256];
 
-long fail(const char* what) {
-  snprintf(g_err, sizeof g_err, "%s", what);
+long fail(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
   return 0;
 }
 
-long fail_hip(const char* what, hipError_t e) {
-  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  return 0;
+long fail_hip(const char* what, hipError_t e) { return fail("%s: %s", what, hipGetErrorString(e)); }
+
+long network_failed(ai_handle net, const char* what) {
+  const char* t = yf_network_last_error_text(net);
+  return fail("%s: %s", what, t ? t : "(no text)");
+}
+
+// after a launch of n frames: n, or 0 and "<what>: <the runtime's text>"
+long launched(const char* what, long n) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(what, e);
+  return n;
+}
+
+// for `groups` grid-striding workgroups of which `per_cu` fit on a CU at once: no more than fill the device (256 CUs if the query fails)
+dim3 grid_for(long groups, int per_cu) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const long g = (long)cus * per_cu;
+  return dim3((unsigned)(groups < g ? groups : g));
 }
 
 int channels_of(int format) {
@@ -255,78 +280,97 @@ int channels_of(int format) {
   }
 }
 
-// workgroups in flight: 8 per CU (LDS per workgroup: 13.6 KB at 56, 14.6 KB at 160)
-long grid_for(long groups) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const long g = (long)cus * 8;
-  return groups < g ? groups : g;
+// ---- argument checks ----  what a uniform and a ragged batch share:
+bool check_batch(int format, long n, int out_hw, const void* d_frames) {
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  if (out_hw != 56 && out_hw != 160) return fail("out_hw must be 56 or 160");
+  if (n < 0) return fail("n < 0");
+  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) return fail("d_frames is NULL or not 16-byte aligned");
+  return true;
 }
 
-template <int OUT, bool RAGGED>
-void launch_prepare(int format, const PrepArgs& a, hipStream_t s) {
-  const dim3 grid((unsigned)grid_for(a.n)), block(kThreads);
-  switch (format) {
-    case YF_PIX_BGR8:  hipLaunchKernelGGL((prepare_kernel<OUT, 3, true, RAGGED>), grid, block, 0, s, a); break;
-    case YF_PIX_RGB8:  hipLaunchKernelGGL((prepare_kernel<OUT, 3, false, RAGGED>), grid, block, 0, s, a); break;
-    case YF_PIX_BGRA8: hipLaunchKernelGGL((prepare_kernel<OUT, 4, true, RAGGED>), grid, block, 0, s, a); break;
-    default:           hipLaunchKernelGGL((prepare_kernel<OUT, 4, false, RAGGED>), grid, block, 0, s, a); break;
-  }
-}
-
-long prepare(int out_hw, int format, const PrepArgs& a, bool ragged, hipStream_t s) {
-  if (a.n == 0) return 0;
-  if (out_hw == 56) { if (ragged) launch_prepare<56, true>(format, a, s); else launch_prepare<56, false>(format, a, s); }
-  else { if (ragged) launch_prepare<160, true>(format, a, s); else launch_prepare<160, false>(format, a, s); }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip("prepare kernel launch", e);
-  return a.n;
-}
-
-// Every argument of a uniform batch, before any launch.  On success fills `a`.
+// Every argument of a uniform batch.  On success fills `a` (a->imgs == nullptr says "uniform").
 bool check_uniform(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long row_stride, long frame_stride,
                    long n, int out_hw, void* d_frames, PrepArgs* a) {
+  if (!check_batch(format, n, out_hw, d_frames)) return false;
   const int C = channels_of(format);
-  if (!C) { fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8"); return false; }
-  if (out_hw != 56 && out_hw != 160) { fail("out_hw must be 56 or 160"); return false; }
-  if (n < 0) { fail("n < 0"); return false; }
-  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) { fail("d_frames is NULL or not 16-byte aligned"); return false; }
-  if (height < 1 || width < 1 || height > YF_IMAGES_MAX_SIDE || width > YF_IMAGES_MAX_SIDE) { fail("height and width must be in [1, 16384]"); return false; }
-  if (row_stride < (long)width * C) { fail("row_stride < width * bytes per pixel"); return false; }
-  if (frame_stride < 0) { fail("frame_stride < 0"); return false; }
+  if (height < 1 || width < 1 || height > YF_IMAGES_MAX_SIDE || width > YF_IMAGES_MAX_SIDE) return fail("height and width must be in [1, 16384]");
+  if (row_stride < (long)width * C) return fail("row_stride < width * bytes per pixel");
+  if (frame_stride < 0) return fail("frame_stride < 0");
   if (n > 0) {
-    if (!d_pixels) { fail("d_pixels is NULL"); return false; }
-    if (!yfi_image_ok(0, height, width, row_stride, C, pixels_bytes)) { fail("the first image reaches outside [0, pixels_bytes)"); return false; }
+    if (!d_pixels) return fail("d_pixels is NULL");
+    if (!yfi_image_ok(0, height, width, row_stride, C, pixels_bytes)) return fail("the first image reaches outside [0, pixels_bytes)");
     const uint64_t extent = (uint64_t)(height - 1) * (uint64_t)row_stride + (uint64_t)width * C;
-    if (n > 1 && frame_stride > 0 && (uint64_t)(n - 1) > (pixels_bytes - extent) / (uint64_t)frame_stride) {
-      fail("the last image reaches outside [0, pixels_bytes)");
-      return false;
-    }
+    if (n > 1 && frame_stride > 0 && (uint64_t)(n - 1) > (pixels_bytes - extent) / (uint64_t)frame_stride)
+      return fail("the last image reaches outside [0, pixels_bytes)");
   }
   *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, nullptr, nullptr, height, width, (int64_t)row_stride, (int64_t)frame_stride,
                 n, (int8_t*)d_frames};
   return true;
 }
 
+// ... and of a ragged batch: what the host can see (the descriptors are checked on the device, image by image: d_status).  With n > 0
+// a->imgs is not nullptr.
 bool check_ragged(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n, int out_hw, void* d_frames,
                   int32_t* d_status, PrepArgs* a) {
-  if (!channels_of(format)) { fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8"); return false; }
-  if (out_hw != 56 && out_hw != 160) { fail("out_hw must be 56 or 160"); return false; }
-  if (n < 0) { fail("n < 0"); return false; }
-  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) { fail("d_frames is NULL or not 16-byte aligned"); return false; }
-  if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0)) {
-    fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
-    return false;
-  }
+  if (!check_batch(format, n, out_hw, d_frames)) return false;
+  if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0))
+    return fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
   *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, n, (int8_t*)d_frames};
   return true;
 }
 
-bool check_decode(void* d_heads, int mode, void* d_dets, void* d_counts, int cap) {
-  if (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST) { fail("mode must be YF_DECODE_PY, YF_DECODE_FW or YF_DECODE_FW_HOST"); return false; }
-  if (!d_heads || !d_dets || !d_counts || cap <= 0) { fail("d_heads, d_dets or d_counts is NULL, or cap <= 0"); return false; }
-  if (((uintptr_t)d_dets & 3) != 0 || ((uintptr_t)d_counts & 3) != 0) { fail("d_dets and d_counts must be 4-byte aligned"); return false; }
+// the descriptors of a decode from heads alone
+bool check_descriptors(const yf_image* d_images, long n) {
+  if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
   return true;
+}
+
+bool check_decode(const void* d_heads, int mode, void* d_dets, void* d_counts, int cap) {
+  if (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST) return fail("mode must be YF_DECODE_PY, YF_DECODE_FW or YF_DECODE_FW_HOST");
+  if (!d_heads || !d_dets || !d_counts || cap <= 0) return fail("d_heads, d_dets or d_counts is NULL, or cap <= 0");
+  if (((uintptr_t)d_dets & 3) != 0 || ((uintptr_t)d_counts & 3) != 0) return fail("d_dets and d_counts must be 4-byte aligned");
+  return true;
+}
+
+bool check_decode160(const void* d_heads, void* d_dets, void* d_counts, int cap) {
+  if (!d_heads) return fail("d_heads is NULL");
+  if (((uintptr_t)d_heads & 15) != 0) return fail("d_heads is not 16-byte aligned");
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0) return fail("d_counts is not 4-byte aligned");
+  if (cap <= 0 || cap > YF_IMAGES_CAND160) return fail("cap must be in [1, 1200]");
+  return true;
+}
+
+// the arguments of either suppression; max_cap is its kernel's limit
+bool check_nms(const void* d_dets, const void* d_counts, long n, int cap, int max_cap, double iou_threshold, void* d_out, void* d_out_counts) {
+  if (n < 0) return fail("n < 0");
+  if (cap <= 0 || cap > max_cap) return fail("cap must be in [1, %d]", max_cap);
+  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (!d_out) return fail("d_out is NULL");
+  if (!d_out_counts) return fail("d_out_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_out & 3) != 0) return fail("d_out is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_out_counts & 3) != 0) return fail("d_counts or d_out_counts is not 4-byte aligned");
+  return true;
+}
+
+// ---- launches (of checked arguments; an empty batch launches nothing) ----
+using PrepKernel = void (*)(PrepArgs);
+template <int OUT, bool RAGGED>                                    // indexed by pixel format
+constexpr PrepKernel kPrepare[4] = {prepare_kernel<OUT, 3, true, RAGGED>, prepare_kernel<OUT, 3, false, RAGGED>,
+                                    prepare_kernel<OUT, 4, true, RAGGED>, prepare_kernel<OUT, 4, false, RAGGED>};
+static_assert(YF_PIX_BGR8 == 0 && YF_PIX_RGB8 == 1 && YF_PIX_BGRA8 == 2 && YF_PIX_RGBA8 == 3, "the order of kPrepare");
+
+long prepare(int out_hw, int format, const PrepArgs& a, hipStream_t s) {
+  if (a.n == 0) return 0;
+  const PrepKernel* k = out_hw == 56 ? (a.imgs ? kPrepare<56, true> : kPrepare<56, false>) : (a.imgs ? kPrepare<160, true> : kPrepare<160, false>);
+  hipLaunchKernelGGL(k[format], grid_for(a.n, 8), dim3(kThreads), 0, s, a);      // LDS per workgroup: 13.6 KB at 56, 14.6 KB at 160
+  return launched("prepare kernel launch", a.n);
 }
 
 // The decode tables (2 KB of __constant__ in this library's code object), uploaded once per device on first use.
@@ -336,18 +380,16 @@ bool g_tables_on[64];
 bool tables_ready(hipStream_t s) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) { fail_hip("hipGetDevice", e); return false; }
-  if (dev < 0 || dev >= 64) { fail("device index out of range"); return false; }
+  if (e != hipSuccess) return fail_hip("hipGetDevice", e);
+  if (dev < 0 || dev >= 64) return fail("device index out of range");
   std::lock_guard<std::mutex> lk(g_tables_mu);
   if (g_tables_on[dev]) return true;
-  if (!yfi_d160_monotonic(yf_sigmoid_bits)) { fail("sigmoid table is not monotonic"); return false; }     // decode160 compares quantised confidences
+  if (!yfi_d160_monotonic(yf_sigmoid_bits)) return fail("sigmoid table is not monotonic");     // decode160 compares quantised confidences
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-    fail("the first per-image-scale decode on a device uploads its tables: make one call outside stream capture first");
-    return false;
-  }
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) { fail_hip("hipMemcpyToSymbol(sigmoid)", e); return false; }
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) { fail_hip("hipMemcpyToSymbol(exp)", e); return false; }
+  if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail("the first per-image-scale decode on a device uploads its tables: make one call outside stream capture first");
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(sigmoid)", e);
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(exp)", e);
   g_tables_on[dev] = true;
   return true;
 }
@@ -359,20 +401,7 @@ long decode_ragged(const void* d_heads, const yf_image* d_images, const int32_t*
   const long groups = (n + 3) / 4;
   hipLaunchKernelGGL(decode_ragged_kernel, dim3((unsigned)(groups < 65536 ? groups : 65536)), dim3(kThreads), 0, s,
                      (const int8_t*)d_heads, d_images, d_status, n, mode, (yf_det*)d_dets, (int*)d_counts, cap);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip("decode kernel launch", e);
-  return n;
-}
-
-bool check_decode160(const void* d_heads, void* d_dets, void* d_counts, int cap) {
-  if (!d_heads) { fail("d_heads is NULL"); return false; }
-  if (((uintptr_t)d_heads & 15) != 0) { fail("d_heads is not 16-byte aligned"); return false; }
-  if (!d_dets) { fail("d_dets is NULL"); return false; }
-  if (!d_counts) { fail("d_counts is NULL"); return false; }
-  if (((uintptr_t)d_dets & 3) != 0) { fail("d_dets is not 4-byte aligned"); return false; }
-  if (((uintptr_t)d_counts & 3) != 0) { fail("d_counts is not 4-byte aligned"); return false; }
-  if (cap <= 0 || cap > YF_IMAGES_CAND160) { fail("cap must be in [1, 1200]"); return false; }
-  return true;
+  return launched("decode kernel launch", n);
 }
 
 // d_images == nullptr: the scalar scales; else per-image scales (and d_status, which may be nullptr)
@@ -381,22 +410,43 @@ long decode160(const void* d_heads, const yf_image* d_images, const int32_t* d_s
   if (n == 0) return 0;
   if (!tables_ready(s)) return 0;
   const int q_thr = yfi_d160_q_threshold(yf_sigmoid_bits);
-  const dim3 grid((unsigned)grid_for(n)), block(yfwide::kThreads);                // 9.2 KB of LDS per workgroup
+  const dim3 grid = grid_for(n, 8), block(yfwide::kThreads);                      // 9.2 KB of LDS per workgroup
   if (d_images)
     hipLaunchKernelGGL(yfwide::decode160_kernel<true>, grid, block, 0, s, (const int8_t*)d_heads, d_images, d_status, n, 0.f, 0.f, q_thr,
                        (yf_det*)d_dets, (int*)d_counts, cap);
   else
     hipLaunchKernelGGL(yfwide::decode160_kernel<false>, grid, block, 0, s, (const int8_t*)d_heads, (const yf_image*)nullptr,
                        (const int32_t*)nullptr, n, w_scale, h_scale, q_thr, (yf_det*)d_dets, (int*)d_counts, cap);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip("decode160 kernel launch", e);
-  return n;
+  return launched("decode160 kernel launch", n);
 }
 
-long network_failed(ai_handle net, const char* what) {
-  const char* t = yf_network_last_error_text(net);
-  snprintf(g_err, sizeof g_err, "%s: %s", what, t ? t : "(no text)");
-  return 0;
+// ---- images -> frames -> heads -> records, of a checked batch `a`, uniform or ragged; on the stream: tables, prepare, network, decode ----
+// 56x56: a uniform batch has one pair of scales, which the network's own fused decode takes; a ragged one needs this library's decode
+long run_decode56(ai_handle net, int format, const PrepArgs& a, void* d_heads, int mode, void* d_dets, void* d_counts, int cap, void* stream) {
+  const bool ragged = a.imgs != nullptr;
+  if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
+  if (a.n == 0) return 0;
+  if (ragged && !tables_ready((hipStream_t)stream)) return 0;
+  if (prepare(56, format, a, (hipStream_t)stream) != a.n) return 0;
+  if (ragged) {
+    if (yf_network_run_device(net, a.frames, d_heads, a.n, stream) != a.n) return network_failed(net, "yf_network_run_device");
+    return decode_ragged(d_heads, a.imgs, a.status, a.n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+  }
+  const float w_scale = (float)((double)a.w / 56.0), h_scale = (float)((double)a.h / 56.0);
+  if (yf_network_run_decode_device(net, a.frames, d_heads, a.n, mode, w_scale, h_scale, d_dets, d_counts, cap, stream) != a.n)
+    return network_failed(net, "yf_network_run_decode_device");
+  return a.n;
+}
+
+// 160x160: the scalar scales count in a uniform batch only (a ragged one has a.w = a.h = 0, and its decode reads the descriptors)
+long run_decode160(ai_handle net, int format, const PrepArgs& a, void* d_heads, void* d_dets, void* d_counts, int cap, void* stream) {
+  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  if (a.n == 0) return 0;
+  if (!tables_ready((hipStream_t)stream)) return 0;
+  if (prepare(160, format, a, (hipStream_t)stream) != a.n) return 0;
+  if (yf_network_run_device_hw(net, 160, 160, a.frames, d_heads, a.n, stream) != a.n) return network_failed(net, "yf_network_run_device_hw");
+  const float w_scale = (float)((double)a.w / 160.0), h_scale = (float)((double)a.h / 160.0);
+  return decode160(d_heads, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -410,14 +460,14 @@ YF_API long yf_images_prepare_device(const void* d_pixels, size_t pixels_bytes, 
                                      long frame_stride, long n, int out_hw, void* d_frames, void* stream) {
   PrepArgs a;
   if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, out_hw, d_frames, &a)) return 0;
-  return prepare(out_hw, format, a, false, (hipStream_t)stream);
+  return prepare(out_hw, format, a, (hipStream_t)stream);
 }
 
 YF_API long yf_images_prepare_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
                                             int out_hw, void* d_frames, int32_t* d_status, void* stream) {
   PrepArgs a;
   if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, out_hw, d_frames, d_status, &a)) return 0;
-  return prepare(out_hw, format, a, true, (hipStream_t)stream);
+  return prepare(out_hw, format, a, (hipStream_t)stream);
 }
 
 YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
@@ -426,13 +476,7 @@ YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, siz
   PrepArgs a;
   if (!net) return fail("network handle is NULL");
   if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 56, d_frames, &a)) return 0;
-  if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
-  if (n == 0) return 0;
-  if (prepare(56, format, a, false, (hipStream_t)stream) != n) return 0;
-  const float w_scale = (float)((double)width / 56.0), h_scale = (float)((double)height / 56.0);
-  if (yf_network_run_decode_device(net, d_frames, d_heads, n, mode, w_scale, h_scale, d_dets, d_counts, cap, stream) != n)
-    return network_failed(net, "yf_network_run_decode_device");
-  return n;
+  return run_decode56(net, format, a, d_heads, mode, d_dets, d_counts, cap, stream);
 }
 
 YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
@@ -441,43 +485,14 @@ YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixe
   PrepArgs a;
   if (!net) return fail("network handle is NULL");
   if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 56, d_frames, d_status, &a)) return 0;
-  if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
-  if (n == 0) return 0;
-  if (!tables_ready((hipStream_t)stream)) return 0;
-  if (prepare(56, format, a, true, (hipStream_t)stream) != n) return 0;
-  if (yf_network_run_device(net, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device");
-  return decode_ragged(d_heads, d_images, d_status, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+  return run_decode56(net, format, a, d_heads, mode, d_dets, d_counts, cap, stream);
 }
 
 YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode, void* d_dets, void* d_counts,
                                            int cap, void* stream) {
   if (n < 0) return fail("n < 0");
-  if (!check_decode((void*)d_heads, mode, d_dets, d_counts, cap)) return 0;
-  if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
+  if (!check_decode(d_heads, mode, d_dets, d_counts, cap) || !check_descriptors(d_images, n)) return 0;
   return decode_ragged(d_heads, d_images, nullptr, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
-}
-
-YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,
-                                 void* d_out_counts, void* stream) {
-  if (n < 0) return fail("n < 0");
-  if (cap <= 0 || cap > YF_IMAGES_NMS_MAX_CAP) return fail("cap must be in [1, 256]");
-  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
-  if (!d_dets) return fail("d_dets is NULL");
-  if (!d_counts) return fail("d_counts is NULL");
-  if (!d_out) return fail("d_out is NULL");
-  if (!d_out_counts) return fail("d_out_counts is NULL");
-  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
-  if (((uintptr_t)d_out & 3) != 0) return fail("d_out is not 4-byte aligned");
-  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_out_counts & 3) != 0) return fail("d_counts or d_out_counts is not 4-byte aligned");
-  if (n == 0) return 0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const long grid = n < (long)cus * 16 ? n : (long)cus * 16;     // 16 one-wave workgroups per CU (9 KB of LDS each)
-  hipLaunchKernelGGL(nms_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, (const yf_det*)d_dets, (const int*)d_counts, n, cap,
-                     iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip("nms kernel launch", e);
-  return n;
 }
 
 YF_API long yf_images_decode160_device(const void* d_heads, long n, float w_scale, float h_scale, void* d_dets, void* d_counts, int cap,
@@ -490,8 +505,7 @@ YF_API long yf_images_decode160_device(const void* d_heads, long n, float w_scal
 YF_API long yf_images_decode160_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, void* d_dets,
                                               void* d_counts, int cap, void* stream) {
   if (n < 0) return fail("n < 0");
-  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
-  if (n > 0 && (!d_images || ((uintptr_t)d_images & 7) != 0)) return fail("d_images is NULL or not 8-byte aligned");
+  if (!check_decode160(d_heads, d_dets, d_counts, cap) || !check_descriptors(d_images, n)) return 0;
   if (((uintptr_t)d_status & 3) != 0) return fail("d_status is not 4-byte aligned");
   return decode160(d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
 }
@@ -502,13 +516,7 @@ YF_API long yf_images_run_decode160_device(ai_handle net, const void* d_pixels, 
   PrepArgs a;
   if (!net) return fail("network handle is NULL");
   if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 160, d_frames, &a)) return 0;
-  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
-  if (n == 0) return 0;
-  if (!tables_ready((hipStream_t)stream)) return 0;
-  if (prepare(160, format, a, false, (hipStream_t)stream) != n) return 0;
-  if (yf_network_run_device_hw(net, 160, 160, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device_hw");
-  const float w_scale = (float)((double)width / 160.0), h_scale = (float)((double)height / 160.0);
-  return decode160(d_heads, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+  return run_decode160(net, format, a, d_heads, d_dets, d_counts, cap, stream);
 }
 
 YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
@@ -517,36 +525,26 @@ YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_p
   PrepArgs a;
   if (!net) return fail("network handle is NULL");
   if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 160, d_frames, d_status, &a)) return 0;
-  if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
+  return run_decode160(net, format, a, d_heads, d_dets, d_counts, cap, stream);
+}
+
+YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,
+                                 void* d_out_counts, void* stream) {
+  if (!check_nms(d_dets, d_counts, n, cap, YF_IMAGES_NMS_MAX_CAP, iou_threshold, d_out, d_out_counts)) return 0;
   if (n == 0) return 0;
-  if (!tables_ready((hipStream_t)stream)) return 0;
-  if (prepare(160, format, a, true, (hipStream_t)stream) != n) return 0;
-  if (yf_network_run_device_hw(net, 160, 160, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device_hw");
-  return decode160(d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
+  hipLaunchKernelGGL(nms_kernel, grid_for(n, 16), dim3(64), 0, (hipStream_t)stream, (const yf_det*)d_dets, (const int*)d_counts, n, cap,
+                     iou_threshold, (yf_det*)d_out, (int*)d_out_counts);                  // one-wave workgroups, 9 KB of LDS each
+  return launched("nms kernel launch", n);
 }
 
 YF_API long yf_images_nms_wide_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,
                                       void* d_out_counts, void* stream) {
-  if (n < 0) return fail("n < 0");
-  if (cap <= 0 || cap > YF_IMAGES_NMS_WIDE_MAX_CAP) return fail("cap must be in [1, 1200]");
-  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
-  if (!d_dets) return fail("d_dets is NULL");
-  if (!d_counts) return fail("d_counts is NULL");
-  if (!d_out) return fail("d_out is NULL");
-  if (!d_out_counts) return fail("d_out_counts is NULL");
-  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
-  if (((uintptr_t)d_out & 3) != 0) return fail("d_out is not 4-byte aligned");
-  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_out_counts & 3) != 0) return fail("d_counts or d_out_counts is not 4-byte aligned");
+  if (!check_nms(d_dets, d_counts, n, cap, YF_IMAGES_NMS_WIDE_MAX_CAP, iou_threshold, d_out, d_out_counts)) return 0;
   if (n == 0) return 0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const long groups = (n + yfwide::kWaves - 1) / yfwide::kWaves;                  // four frames per workgroup
-  const long grid = groups < (long)cus * 3 ? groups : (long)cus * 3;              // 3 workgroups per CU (43.5 KB of LDS each)
-  hipLaunchKernelGGL(yfwide::nms_wide_kernel, dim3((unsigned)grid), dim3(yfwide::kThreads), 0, (hipStream_t)stream, (const yf_det*)d_dets,
+  const long groups = (n + yfwide::kWaves - 1) / yfwide::kWaves;                  // four frames per workgroup, 43.5 KB of LDS each
+  hipLaunchKernelGGL(yfwide::nms_wide_kernel, grid_for(groups, 3), dim3(yfwide::kThreads), 0, (hipStream_t)stream, (const yf_det*)d_dets,
                      (const int*)d_counts, n, cap, iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip("nms_wide kernel launch", e);
-  return n;
+  return launched("nms_wide kernel launch", n);
 }
 
 }  // extern "C"

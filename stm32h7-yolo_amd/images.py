@@ -71,6 +71,28 @@ def library_is_current():
         return False
 
 
+def _entries():
+    """yf_images_<name> -> argument types, for every entry point that returns the number of frames it took (a long): include/yf_images.h"""
+    vp, cl, ci, cs, cf, cd = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
+    uniform = [vp, cs, ci, ci, ci, cl, cl, cl]          # d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n
+    ragged = [vp, cs, ci, vp, cl]                       # d_pixels, pixels_bytes, format, d_images, n
+    nms = [vp, vp, cl, ci, cd, vp, vp, vp]
+    return {
+        "prepare_device": uniform + [ci, vp, vp],
+        "prepare_ragged_device": ragged + [ci, vp, vp, vp],
+        "run_decode_device": [vp] + uniform + [vp, vp, ci, vp, vp, ci, vp],
+        "run_decode_ragged_device": [vp] + ragged + [vp, vp, ci, vp, vp, ci, vp, vp],
+        "decode_ragged_device": [vp, vp, cl, ci, vp, vp, ci, vp],
+        "nms_device": nms,
+        "decode160_device": [vp, cl, cf, cf, vp, vp, ci, vp],
+        "decode160_ragged_device": [vp, vp, vp, cl, vp, vp, ci, vp],
+        "run_decode160_device": [vp] + uniform + [vp, vp, vp, vp, ci, vp],
+        "run_decode160_ragged_device": [vp] + ragged + [vp, vp, vp, vp, ci, vp, vp],
+        "nms_wide_device": nms,
+    }
+
+
+_ENTRIES = _entries()
 _lib = None
 
 
@@ -105,30 +127,9 @@ def load():
         have, want = (lib.yf_images_build_id() or b"").decode(), expected_build_id()
         if have != want:
             raise RuntimeError(f"{path} was built from other sources (build id {have}, expected {want}) and is not being rebuilt here")
-    vp, cl, ci, cs = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_size_t
-    lib.yf_images_prepare_device.restype = cl
-    lib.yf_images_prepare_device.argtypes = [vp, cs, ci, ci, ci, cl, cl, cl, ci, vp, vp]
-    lib.yf_images_prepare_ragged_device.restype = cl
-    lib.yf_images_prepare_ragged_device.argtypes = [vp, cs, ci, vp, cl, ci, vp, vp, vp]
-    lib.yf_images_run_decode_device.restype = cl
-    lib.yf_images_run_decode_device.argtypes = [vp, vp, cs, ci, ci, ci, cl, cl, cl, vp, vp, ci, vp, vp, ci, vp]
-    lib.yf_images_run_decode_ragged_device.restype = cl
-    lib.yf_images_run_decode_ragged_device.argtypes = [vp, vp, cs, ci, vp, cl, vp, vp, ci, vp, vp, ci, vp, vp]
-    lib.yf_images_decode_ragged_device.restype = cl
-    lib.yf_images_decode_ragged_device.argtypes = [vp, vp, cl, ci, vp, vp, ci, vp]
-    lib.yf_images_nms_device.restype = cl
-    lib.yf_images_nms_device.argtypes = [vp, vp, cl, ci, ctypes.c_double, vp, vp, vp]
-    cf = ctypes.c_float
-    lib.yf_images_decode160_device.restype = cl
-    lib.yf_images_decode160_device.argtypes = [vp, cl, cf, cf, vp, vp, ci, vp]
-    lib.yf_images_decode160_ragged_device.restype = cl
-    lib.yf_images_decode160_ragged_device.argtypes = [vp, vp, vp, cl, vp, vp, ci, vp]
-    lib.yf_images_run_decode160_device.restype = cl
-    lib.yf_images_run_decode160_device.argtypes = [vp, vp, cs, ci, ci, ci, cl, cl, cl, vp, vp, vp, vp, ci, vp]
-    lib.yf_images_run_decode160_ragged_device.restype = cl
-    lib.yf_images_run_decode160_ragged_device.argtypes = [vp, vp, cs, ci, vp, cl, vp, vp, vp, vp, ci, vp, vp]
-    lib.yf_images_nms_wide_device.restype = cl
-    lib.yf_images_nms_wide_device.argtypes = [vp, vp, cl, ci, ctypes.c_double, vp, vp, vp]
+    for name, argtypes in _ENTRIES.items():
+        fn = getattr(lib, "yf_images_" + name)
+        fn.restype, fn.argtypes = ctypes.c_long, argtypes
     lib.yf_images_last_error_text.restype = ctypes.c_char_p
     lib.yf_images_last_error_text.argtypes = []
     _lib = lib
@@ -177,88 +178,75 @@ def pack_images(images, fmt="bgr", align=16):
     return buf, desc
 
 
-def _check(lib, rc, n, what):
+def _call(name, n, *args):
+    """yf_images_<name>(*args), which returns n or fails with a text"""
+    lib = load()
+    rc = getattr(lib, "yf_images_" + name)(*args)
     if rc != n:
-        raise ImagesError(f"{what}: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc}, expected {n})")
+        raise ImagesError(f"yf_images_{name}: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc}, expected {n})")
 
 
 def prepare_device(d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, out_hw, d_frames, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_prepare_device(d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n, out_hw,
-                                             d_frames, stream), n, "yf_images_prepare_device")
+    _call("prepare_device", n, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n, out_hw, d_frames, stream)
 
 
 def prepare_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_prepare_ragged_device(d_pixels, pixels_bytes, format_code(fmt), d_images, n, out_hw, d_frames, d_status, stream),
-           n, "yf_images_prepare_ragged_device")
+    _call("prepare_ragged_device", n, d_pixels, pixels_bytes, format_code(fmt), d_images, n, out_hw, d_frames, d_status, stream)
 
 
 def run_decode_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames, d_heads, d_dets, d_counts,
                       cap, mode=binding.YF_DECODE_PY, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_run_decode_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride,
-                                                n, d_frames, d_heads, mode, d_dets, d_counts, cap, stream), n, "yf_images_run_decode_device")
+    _call("run_decode_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n, d_frames,
+          d_heads, mode, d_dets, d_counts, cap, stream)
 
 
 def run_decode_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames, d_heads, d_dets, d_counts, cap, d_status,
                              mode=binding.YF_DECODE_PY, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_run_decode_ragged_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames, d_heads,
-                                                       mode, d_dets, d_counts, cap, d_status, stream), n, "yf_images_run_decode_ragged_device")
+    _call("run_decode_ragged_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames, d_heads, mode, d_dets,
+          d_counts, cap, d_status, stream)
 
 
 def decode_ragged_device(d_heads, d_images, n, d_dets, d_counts, cap, mode=binding.YF_DECODE_PY, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_decode_ragged_device(d_heads, d_images, n, mode, d_dets, d_counts, cap, stream), n, "yf_images_decode_ragged_device")
+    _call("decode_ragged_device", n, d_heads, d_images, n, mode, d_dets, d_counts, cap, stream)
+
+
+def _nms(name, d_dets, d_counts, n, cap, iou_threshold, d_out, d_out_counts, stream):
+    d_out = d_dets if d_out is None else d_out
+    d_out_counts = d_counts if d_out_counts is None else d_out_counts
+    _call(name, n, d_dets, d_counts, n, cap, float(iou_threshold), d_out, d_out_counts, stream)
 
 
 def nms_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_counts=None, stream=None):
     """Greedy IoU suppression of decoded records (yf_images_nms_device): d_dets yf_det[n][cap], d_counts int32[n] -> d_out, d_out_counts
     (in place when not given).  Order: descending conf, ties later record first; float64 arithmetic as yoloface_test.py:165-190 states it."""
-    lib = load()
-    d_out = d_dets if d_out is None else d_out
-    d_out_counts = d_counts if d_out_counts is None else d_out_counts
-    _check(lib, lib.yf_images_nms_device(d_dets, d_counts, n, cap, float(iou_threshold), d_out, d_out_counts, stream), n,
-           "yf_images_nms_device")
+    _nms("nms_device", d_dets, d_counts, n, cap, iou_threshold, d_out, d_out_counts, stream)
 
 
 def decode160_device(d_heads, n, d_dets, d_counts, cap, w_scale=1.0, h_scale=1.0, stream=None):
     """Decode of 20x20 heads (yf_images_decode160_device): d_heads int8[n][20][20][18] -> d_dets yf_det[n][cap], d_counts int32[n]."""
-    lib = load()
-    _check(lib, lib.yf_images_decode160_device(d_heads, n, w_scale, h_scale, d_dets, d_counts, cap, stream), n, "yf_images_decode160_device")
+    _call("decode160_device", n, d_heads, n, w_scale, h_scale, d_dets, d_counts, cap, stream)
 
 
 def decode160_ragged_device(d_heads, d_images, n, d_dets, d_counts, cap, d_status=None, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_decode160_ragged_device(d_heads, d_images, d_status, n, d_dets, d_counts, cap, stream), n,
-           "yf_images_decode160_ragged_device")
+    _call("decode160_ragged_device", n, d_heads, d_images, d_status, n, d_dets, d_counts, cap, stream)
 
 
 def run_decode160_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames, d_heads, d_dets, d_counts,
                          cap, stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_run_decode160_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride,
-                                                   frame_stride, n, d_frames, d_heads, d_dets, d_counts, cap, stream), n,
-           "yf_images_run_decode160_device")
+    _call("run_decode160_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n,
+          d_frames, d_heads, d_dets, d_counts, cap, stream)
 
 
 def run_decode160_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames, d_heads, d_dets, d_counts, cap, d_status,
                                 stream=None):
-    lib = load()
-    _check(lib, lib.yf_images_run_decode160_ragged_device(network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames,
-                                                          d_heads, d_dets, d_counts, cap, d_status, stream), n,
-           "yf_images_run_decode160_ragged_device")
+    _call("run_decode160_ragged_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames, d_heads, d_dets,
+          d_counts, cap, d_status, stream)
 
 
 def nms_wide_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_counts=None, stream=None):
     """nms_device for up to NMS_WIDE_MAX_CAP records per frame (yf_images_nms_wide_device): the same semantics, in place when d_out is not
     given."""
-    lib = load()
-    d_out = d_dets if d_out is None else d_out
-    d_out_counts = d_counts if d_out_counts is None else d_out_counts
-    _check(lib, lib.yf_images_nms_wide_device(d_dets, d_counts, n, cap, float(iou_threshold), d_out, d_out_counts, stream), n,
-           "yf_images_nms_wide_device")
+    _nms("nms_wide_device", d_dets, d_counts, n, cap, iou_threshold, d_out, d_out_counts, stream)
 
 
 def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56):

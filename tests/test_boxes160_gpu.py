@@ -1,104 +1,23 @@
 """Boxes at 160x160 on the MI355X: the decode of 20x20 heads (yf_images_decode160_device) against the oracle's yfo_decode_py, the
 suppression of up to 1200 records per frame (yf_images_nms_wide_device) against the restatement of yoloface_test.py:165-190
-(tests/test_nms_host.py) and against the 256-record kernel, the image path images -> 160x160 frames -> heads -> records on the reference's
+(tests/images_support.py) and against the 256-record kernel, the image path images -> 160x160 frames -> heads -> records on the reference's
 27 images, graph capture, and images.detect(size=160).  Every comparison is exact."""
-import importlib
-import importlib.util
-import os
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from images_support import Batch, check_nms, expect_frame, real_images, sentinels, suppress, synthetic_heads160, to_host, tuples
+from images_support import images_after_network, ptq, torch_cuda          # noqa: F401 (fixtures; `images` is images_after_network)
 
 pytestmark = pytest.mark.gpu
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(f"_boxes160_{name}", os.path.join(ROOT, "tests", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-restated = _load("test_nms_host")           # nms_restated, suppress
-img_tests = _load("test_images_gpu")        # _real_images, expect_frame, REF_SIZES
 
 THRESHOLDS = (0.0, 0.4, 0.5, 1.0)
 CAND = 1200
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def images(network):
-    return importlib.import_module("stm32h7-yolo_amd.images")
-
-
-@pytest.fixture(scope="module")
-def ptq():
-    return importlib.import_module("stm32h7-yolo_amd.ptq")
-
-
-def _host(yf, d_dets, d_counts, cap):
-    import torch
-    torch.cuda.synchronize()
-    return d_dets.cpu().numpy().view(yf.DET_DTYPE).reshape(-1, cap), d_counts.cpu().numpy()
-
-
-def _tuples(rows):
-    return [tuple(v.item() for v in r) for r in rows]
-
-
-def _sentinels(torch, n, cap):
-    return torch.full((max(n, 1), cap, 28), 0xA5, dtype=torch.uint8, device="cuda"), torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-
-
-def _expect_frame(rows, count, cap, thr):
-    """the kept rows of one frame: the restatement over its first min(max(count, 0), cap) records"""
-    m = min(max(int(count), 0), cap)
-    r = rows[:m]
-    boxes = np.stack([r["x1"], r["y1"], r["x2"], r["y2"], r["conf"]], axis=1).astype(np.float64)
-    return r[restated.nms_restated(boxes, thr)]
-
-
-def _check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, thr, frames=None):
-    """every frame's output equals the restatement, byte for byte and in keep order; slots beyond the kept count keep their sentinel"""
-    out, oc = _host(yf, d_out, d_oc, cap)
-    raw = out.view(np.uint8).reshape(out.shape[0], cap, 28)
-    lost = 0
-    for f in (range(dets_in.shape[0]) if frames is None else frames):
-        want = _expect_frame(dets_in[f], counts_in[f], cap, thr)
-        assert oc[f] == want.shape[0], (f, thr, oc[f], want.shape[0])
-        assert out[f, :want.shape[0]].tobytes() == want.tobytes(), (f, thr)
-        assert (raw[f, want.shape[0]:] == 0xA5).all(), (f, thr)
-        lost += min(max(int(counts_in[f]), 0), cap) - want.shape[0]
-    return lost
-
-
-def _synthetic_heads(rng, n):
-    """seeded 20x20 heads: random bytes (about half the 1200 candidates fire), every third frame sparse, every 64th frame all 1200
-    candidates at one shared q_conf"""
-    heads = rng.integers(-128, 128, (n, 20, 20, 18), dtype=np.int16)
-    sparse = heads[1::3, ..., 4::6]
-    heads[1::3, ..., 4::6] = np.where(rng.random(sparse.shape) < 0.01, sparse, rng.integers(-128, -20, sparse.shape))
-    for f in range(0, n, 64):
-        heads[f, ..., 4::6] = 96 + (f // 64) % 32
-    return heads.astype(np.int8)
-
-
 def _decode(torch, images, heads, cap, ws, hs):
     n = heads.shape[0]
     d_heads = torch.from_numpy(heads).cuda()
-    d_dets, d_counts = _sentinels(torch, n, cap)
+    d_dets, d_counts = sentinels(torch, n, cap)
     images.decode160_device(d_heads.data_ptr(), n, d_dets.data_ptr(), d_counts.data_ptr(), cap, w_scale=ws, h_scale=hs)
     return d_heads, d_dets, d_counts
 
@@ -107,10 +26,10 @@ def _decode(torch, images, heads, cap, ws, hs):
 def test_decode160_uniform_against_the_oracle(yf, network, oracle, torch_cuda, images, cap):
     torch = torch_cuda
     n = 1024
-    heads = _synthetic_heads(np.random.default_rng(160), n)
+    heads = synthetic_heads160(np.random.default_rng(160), n)
     ws, hs = float(np.float32(410 / 160.)), float(np.float32(362 / 160.))
     _, d_dets, d_counts = _decode(torch, images, heads, cap, ws, hs)
-    dets, counts = _host(yf, d_dets, d_counts, cap)
+    dets, counts = to_host(yf, d_dets, d_counts, cap)
     raw = dets.view(np.uint8).reshape(n, cap, 28)
     assert (counts[::64] == CAND).all()
     for i in range(n):
@@ -118,36 +37,15 @@ def test_decode160_uniform_against_the_oracle(yf, network, oracle, torch_cuda, i
         want = oracle.decode_py(heads[i], i, w_scale=ws, h_scale=hs, max_dets=cap)
         assert counts[i] == len(full), (i, counts[i], len(full))                 # the true count, which may exceed cap
         k = min(len(full), cap)
-        assert _tuples(dets[i, :k]) == want, i
+        assert tuples(dets[i, :k]) == want, i
         assert (raw[i, k:] == 0xA5).all(), i                                     # slots beyond min(count, cap) keep their sentinel
     idx = np.arange(n)
     dense, sparse = counts[(idx % 3 != 1) & (idx % 64 != 0)], counts[(idx % 3 == 1) & (idx % 64 != 0)]
     assert 500 < dense.min() and dense.max() < 760 and sparse.max() < 64 and (counts > cap).any() == (cap < CAND)
 
 
-class Batch160:
-    """a packed ragged batch on the device with the workspaces of the 160x160 path"""
-
-    def __init__(self, torch, images, imgs, fmt="bgr", cap=CAND, desc=None, buf=None):
-        if desc is None:
-            buf, desc = images.pack_images(imgs, fmt)
-        self.n, self.buf, self.desc, self.fmt, self.cap = desc.shape[0], buf, desc, fmt, cap
-        self.d_px = torch.from_numpy(buf).cuda()
-        self.d_desc = torch.from_numpy(desc.view(np.uint8).copy()).cuda()
-        n = self.n
-        self.d_frames = torch.full((n, 160, 160, 3), 77, dtype=torch.int8, device="cuda")
-        self.d_heads = torch.zeros((n, 20, 20, 18), dtype=torch.int8, device="cuda")
-        self.d_dets, self.d_counts = _sentinels(torch, n, cap)
-        self.d_status = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-
-    def run(self, images, network):
-        images.run_decode160_ragged_device(network, self.d_px.data_ptr(), self.buf.nbytes, self.fmt, self.d_desc.data_ptr(), self.n,
-                                           self.d_frames.data_ptr(), self.d_heads.data_ptr(), self.d_dets.data_ptr(), self.d_counts.data_ptr(),
-                                           self.cap, self.d_status.data_ptr())
-
-
 def _oracle_chain(oracle, ptq, imgs, variant=0):
-    frames = np.stack([img_tests.expect_frame(ptq, im, 0, 160) for im in imgs])
+    frames = np.stack([expect_frame(ptq, im, 0, 160) for im in imgs])
     heads = oracle.run(frames, variant=variant)
     recs = [oracle.decode_py(heads[i], i, w_scale=float(np.float32(im.shape[1] / 160.)), h_scale=float(np.float32(im.shape[0] / 160.)),
                               max_dets=CAND)
@@ -157,12 +55,12 @@ def _oracle_chain(oracle, ptq, imgs, variant=0):
 
 def _real_batch_check(yf, network, oracle, torch, images, ptq, variant):
     """the 27 real images and one deliberately invalid descriptor in one ragged batch; returns the batch and the oracle's records"""
-    imgs = img_tests._real_images(ptq)
+    imgs = real_images(ptq)
     buf, desc = images.pack_images(imgs + [imgs[0]], "bgr")
     bad = len(imgs)
     desc["row_stride"][bad] = desc["width"][bad] * 3 - 1                    # stride below a row: status 1
-    b = Batch160(torch, images, None, desc=desc, buf=buf)
-    b.run(images, network)
+    b = Batch(torch, images, None, "bgr", 160, desc=desc, buf=buf)
+    b.run_decode(images, network)
     torch.cuda.synchronize()
     assert b.d_status.cpu().numpy().tolist() == [0] * bad + [1]
     frames, heads, recs = _oracle_chain(oracle, ptq, imgs, variant)
@@ -170,10 +68,10 @@ def _real_batch_check(yf, network, oracle, torch, images, ptq, variant):
     assert np.array_equal(got_frames[:bad], frames)
     assert (got_frames[bad] == -128).all()
     assert np.array_equal(b.d_heads.cpu().numpy()[:bad], heads)
-    dets, counts = _host(yf, b.d_dets, b.d_counts, b.cap)
+    dets, counts = to_host(yf, b.d_dets, b.d_counts, b.cap)
     assert counts[bad] == 0
     for i in range(bad):
-        assert counts[i] == len(recs[i]) and _tuples(dets[i, :counts[i]]) == recs[i], i
+        assert counts[i] == len(recs[i]) and tuples(dets[i, :counts[i]]) == recs[i], i
     return b, imgs, recs, dets, counts
 
 
@@ -182,21 +80,21 @@ def test_real_images_to_records_and_suppression(yf, network, oracle, torch_cuda,
     b, imgs, recs, dets, counts = _real_batch_check(yf, network, oracle, torch, images, ptq, 0)
     assert sum(len(r) for r in recs) > 0, "no image has records"
     # the same records from the heads alone: with the status array, and without it on the valid images
-    d_dets, d_counts = _sentinels(torch, b.n, b.cap)
+    d_dets, d_counts = sentinels(torch, b.n, b.cap)
     images.decode160_ragged_device(b.d_heads.data_ptr(), b.d_desc.data_ptr(), b.n, d_dets.data_ptr(), d_counts.data_ptr(), b.cap,
                                    d_status=b.d_status.data_ptr())
-    again, cnt = _host(yf, d_dets, d_counts, b.cap)
+    again, cnt = to_host(yf, d_dets, d_counts, b.cap)
     assert np.array_equal(cnt, counts) and all(again[i, :cnt[i]].tobytes() == dets[i, :cnt[i]].tobytes() for i in range(b.n))
     images.decode160_ragged_device(b.d_heads.data_ptr(), b.d_desc.data_ptr(), b.n - 1, d_dets.data_ptr(), d_counts.data_ptr(), b.cap)
-    again, cnt = _host(yf, d_dets, d_counts, b.cap)
+    again, cnt = to_host(yf, d_dets, d_counts, b.cap)
     assert np.array_equal(cnt, counts)
     lost_at = {}
     for thr in THRESHOLDS:
-        d_out, d_oc = _sentinels(torch, b.n, b.cap)
+        d_out, d_oc = sentinels(torch, b.n, b.cap)
         images.nms_wide_device(b.d_dets.data_ptr(), b.d_counts.data_ptr(), b.n, b.cap, thr, d_out.data_ptr(), d_oc.data_ptr())
-        lost_at[thr] = _check_nms(yf, dets, counts, d_out, d_oc, b.cap, thr)
-        out, oc = _host(yf, d_out, d_oc, b.cap)
-        assert [_tuples(out[i, :oc[i]]) for i in range(len(imgs))] == [restated.suppress(r, thr) for r in recs], thr
+        lost_at[thr] = check_nms(yf, dets, counts, d_out, d_oc, b.cap, thr)
+        out, oc = to_host(yf, d_out, d_oc, b.cap)
+        assert [tuples(out[i, :oc[i]]) for i in range(len(imgs))] == [suppress(r, thr) for r in recs], thr
     assert lost_at[0.4] > 0, "no image lost a record at 0.4: suppression did not happen"
     assert lost_at[0.0] >= lost_at[0.4] >= lost_at[1.0]
 
@@ -217,13 +115,13 @@ def oracle_variant(name):
 def test_uniform_image_path_equals_ragged(yf, network, torch_cuda, images, ptq):
     torch = torch_cuda
     n, H, W = 64, 362, 410
-    real = img_tests._real_images(ptq)[0]
+    real = real_images(ptq)[0]
     g = torch.Generator(device="cuda").manual_seed(5)
     noise = torch.randint(-24, 25, (n, H, W, 3), device="cuda", generator=g, dtype=torch.int16)
     px = (torch.from_numpy(real).cuda().to(torch.int16)[None] + noise).clamp(0, 255).to(torch.uint8).contiguous()
     fs, rs, cap = H * W * 3, W * 3, CAND
     mk = lambda: (torch.empty((n, 160, 160, 3), dtype=torch.int8, device="cuda"), torch.empty((n, 20, 20, 18), dtype=torch.int8, device="cuda"),
-                  *_sentinels(torch, n, cap))
+                  *sentinels(torch, n, cap))
     f_u, h_u, d_u, c_u = mk()
     images.run_decode160_device(network, px.data_ptr(), px.numel(), "bgr", H, W, rs, fs, n, f_u.data_ptr(), h_u.data_ptr(), d_u.data_ptr(),
                                 c_u.data_ptr(), cap)
@@ -237,7 +135,7 @@ def test_uniform_image_path_equals_ragged(yf, network, torch_cuda, images, ptq):
     torch.cuda.synchronize()
     assert torch.equal(f_u, f_r) and torch.equal(h_u, h_r) and torch.equal(c_u, c_r) and torch.equal(d_u, d_r)
     assert (st == 0).all().item() and int(c_u.sum().item()) > 0
-    assert np.array_equal(f_u[0].cpu().numpy(), img_tests.expect_frame(ptq, px[0].cpu().numpy(), 0, 160))
+    assert np.array_equal(f_u[0].cpu().numpy(), expect_frame(ptq, px[0].cpu().numpy(), 0, 160))
 
 
 def _records(yf, rng, n, cap, counts):
@@ -262,25 +160,25 @@ def test_nms_wide_on_decoded_records(yf, network, oracle, torch_cuda, images):
     """the records of the decode test's heads: 256 frames (86 of them dense, four with all 1200 records tied), every threshold"""
     torch = torch_cuda
     n, cap = 256, CAND
-    heads = _synthetic_heads(np.random.default_rng(161), n)
+    heads = synthetic_heads160(np.random.default_rng(161), n)
     _, d_dets, d_counts = _decode(torch, images, heads, cap, float(np.float32(410 / 160.)), float(np.float32(362 / 160.)))
-    dets_in, counts_in = _host(yf, d_dets, d_counts, cap)
+    dets_in, counts_in = to_host(yf, d_dets, d_counts, cap)
     idx = np.arange(n)
     assert (counts_in[::64] == CAND).all() and (counts_in[(idx % 3 == 1) & (idx % 64 != 0)] <= 64).all() and (counts_in[2::3] > 256).all()
     saved = d_dets.clone()
     for thr in THRESHOLDS:
-        d_out, d_oc = _sentinels(torch, n, cap)
+        d_out, d_oc = sentinels(torch, n, cap)
         images.nms_wide_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, thr, d_out.data_ptr(), d_oc.data_ptr())
         frames = None if thr == 0.4 else range(0, n, 2)
-        lost = _check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, thr, frames)
+        lost = check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, thr, frames)
         assert lost > 0 or thr >= 1.0
     assert torch.equal(saved, d_dets)                       # out of place: the input is not touched
     # in place equals out of place
-    d_out, d_oc = _sentinels(torch, n, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     images.nms_wide_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, 0.4, d_out.data_ptr(), d_oc.data_ptr())
     images.nms_wide_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, 0.4)
-    a, ac = _host(yf, d_dets, d_counts, cap)
-    b, oc = _host(yf, d_out, d_oc, cap)
+    a, ac = to_host(yf, d_dets, d_counts, cap)
+    b, oc = to_host(yf, d_out, d_oc, cap)
     assert np.array_equal(ac, oc)
     for f in range(n):
         assert a[f, :oc[f]].tobytes() == b[f, :oc[f]].tobytes(), f
@@ -296,40 +194,40 @@ def test_nms_wide_exact_counts_odd_counts_and_small_caps(yf, network, torch_cuda
     recs, counts = _records(yf, rng, len(counts), CAND, counts)
     d_recs, d_cnt = _up(torch, recs, counts)
     for thr in THRESHOLDS:
-        d_out, d_oc = _sentinels(torch, recs.shape[0], CAND)
+        d_out, d_oc = sentinels(torch, recs.shape[0], CAND)
         images.nms_wide_device(d_recs.data_ptr(), d_cnt.data_ptr(), recs.shape[0], CAND, thr, d_out.data_ptr(), d_oc.data_ptr())
-        _check_nms(yf, recs, counts, d_out, d_oc, CAND, thr)
+        check_nms(yf, recs, counts, d_out, d_oc, CAND, thr)
     # negative counts, counts above cap, and in place on them
     odd = counts.copy()
     odd[1::5] = -3
     odd[2::5] = 5000
     d_odd = torch.from_numpy(odd).cuda()
-    d_out, d_oc = _sentinels(torch, recs.shape[0], CAND)
+    d_out, d_oc = sentinels(torch, recs.shape[0], CAND)
     images.nms_wide_device(d_recs.data_ptr(), d_odd.data_ptr(), recs.shape[0], CAND, 0.4, d_out.data_ptr(), d_oc.data_ptr())
-    _check_nms(yf, recs, odd, d_out, d_oc, CAND, 0.4)
+    check_nms(yf, recs, odd, d_out, d_oc, CAND, 0.4)
     d_copy = d_recs.clone()
     images.nms_wide_device(d_copy.data_ptr(), d_odd.data_ptr(), recs.shape[0], CAND, 0.4)
-    a, ac = _host(yf, d_copy, d_odd, CAND)
-    b, oc = _host(yf, d_out, d_oc, CAND)
+    a, ac = to_host(yf, d_copy, d_odd, CAND)
+    b, oc = to_host(yf, d_out, d_oc, CAND)
     assert np.array_equal(ac, oc) and all(a[f, :oc[f]].tobytes() == b[f, :oc[f]].tobytes() for f in range(recs.shape[0]))
     # cap below the count: the decode writes 100 records of frames that have more, the suppression runs over those 100
     cap = 100
-    heads = _synthetic_heads(np.random.default_rng(163), 128)
+    heads = synthetic_heads160(np.random.default_rng(163), 128)
     _, d100, k100 = _decode(torch, images, heads, cap, 2.5, 2.25)
-    in100, cnt100 = _host(yf, d100, k100, cap)
+    in100, cnt100 = to_host(yf, d100, k100, cap)
     assert (cnt100 > cap).any()
-    d_out, d_oc = _sentinels(torch, 128, cap)
+    d_out, d_oc = sentinels(torch, 128, cap)
     images.nms_wide_device(d100.data_ptr(), k100.data_ptr(), 128, cap, 0.4, d_out.data_ptr(), d_oc.data_ptr())
-    _check_nms(yf, in100, cnt100, d_out, d_oc, cap, 0.4)
+    check_nms(yf, in100, cnt100, d_out, d_oc, cap, 0.4)
     # n = 0: nothing launched, nothing written; n not a multiple of four
-    d_out, d_oc = _sentinels(torch, 1, CAND)
+    d_out, d_oc = sentinels(torch, 1, CAND)
     images.nms_wide_device(d_recs.data_ptr(), d_cnt.data_ptr(), 0, CAND, 0.4, d_out.data_ptr(), d_oc.data_ptr())
     torch.cuda.synchronize()
     assert (d_out == 0xA5).all().item() and (d_oc == -7).all().item()
     for n in (1, 2, 3, 5):
-        d_out, d_oc = _sentinels(torch, recs.shape[0], CAND)
+        d_out, d_oc = sentinels(torch, recs.shape[0], CAND)
         images.nms_wide_device(d_recs.data_ptr(), d_cnt.data_ptr(), n, CAND, 0.5, d_out.data_ptr(), d_oc.data_ptr())
-        _check_nms(yf, recs, counts, d_out, d_oc, CAND, 0.5, frames=range(n))
+        check_nms(yf, recs, counts, d_out, d_oc, CAND, 0.5, frames=range(n))
         assert (d_oc[n:] == -7).all().item() and (d_out[n:] == 0xA5).all().item()
 
 
@@ -344,8 +242,8 @@ def test_nms_wide_equals_the_256_record_kernel(yf, network, torch_cuda, images, 
     recs, counts = _records(yf, rng, n, cap, counts)
     d_recs, d_cnt = _up(torch, recs, counts)
     for thr in THRESHOLDS:
-        o1, c1 = _sentinels(torch, n, cap)
-        o2, c2 = _sentinels(torch, n, cap)
+        o1, c1 = sentinels(torch, n, cap)
+        o2, c2 = sentinels(torch, n, cap)
         images.nms_device(d_recs.data_ptr(), d_cnt.data_ptr(), n, cap, thr, o1.data_ptr(), c1.data_ptr())
         images.nms_wide_device(d_recs.data_ptr(), d_cnt.data_ptr(), n, cap, thr, o2.data_ptr(), c2.data_ptr())
         torch.cuda.synchronize()
@@ -357,14 +255,14 @@ def test_nms_wide_equals_the_256_record_kernel(yf, network, torch_cuda, images, 
 def test_graph_capture_of_decode_and_suppression(yf, network, torch_cuda, images):
     torch = torch_cuda
     n, cap = 96, CAND
-    heads = _synthetic_heads(np.random.default_rng(165), n)
+    heads = synthetic_heads160(np.random.default_rng(165), n)
     ws, hs = 2.5, 2.25
     d_heads, d_dets, d_counts = _decode(torch, images, heads, cap, ws, hs)            # the direct calls (and the one-time table upload)
-    d_out, d_oc = _sentinels(torch, n, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     images.nms_wide_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, 0.4, d_out.data_ptr(), d_oc.data_ptr())
     torch.cuda.synchronize()
-    g_dets, g_counts = _sentinels(torch, n, cap)
-    g_out, g_oc = _sentinels(torch, n, cap)
+    g_dets, g_counts = sentinels(torch, n, cap)
+    g_out, g_oc = sentinels(torch, n, cap)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     g = torch.cuda.CUDAGraph()
@@ -382,12 +280,12 @@ def test_graph_capture_of_decode_and_suppression(yf, network, torch_cuda, images
 
 
 def test_detect_at_160_and_at_56(yf, network, oracle, torch_cuda, images, ptq):
-    imgs = img_tests._real_images(ptq)
+    imgs = real_images(ptq)
     _, _, recs = _oracle_chain(oracle, ptq, imgs)
     plain = images.detect(network, imgs, "bgr", size=160)
     assert [bx.tolist() for bx in plain] == [[[r[6], r[7], r[8], r[9]] for r in rr] for rr in recs]
     boxes = images.detect(network, imgs, "bgr", size=160, iou_threshold=0.4)
-    assert [bx.tolist() for bx in boxes] == [[[r[6], r[7], r[8], r[9]] for r in restated.suppress(rr, 0.4)] for rr in recs]
+    assert [bx.tolist() for bx in boxes] == [[[r[6], r[7], r[8], r[9]] for r in suppress(rr, 0.4)] for rr in recs]
     assert all(bx.dtype == np.int32 and bx.shape[1] == 4 for bx in boxes)
     assert 0 < sum(len(b) for b in boxes) < sum(len(b) for b in plain)
     for kw in (dict(), dict(iou_threshold=0.4), dict(cap=20)):

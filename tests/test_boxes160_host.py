@@ -1,43 +1,18 @@
 """Boxes at 160x160 on the host (no GPU): the per-candidate decode of csrc/yf_images_decode160.h -- the function the device kernel calls,
 compiled for the host -- against the oracle's yfo_decode_py on 20x20 heads, the wide order key of the suppression, the argument checks of
 the five new entry points (which return before any launch) and the build-id coverage of the new sources."""
-import ctypes
-import importlib
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from conftest import ROOT
+from images_support import PKG, host, images, last_error          # noqa: F401 (host, images: fixtures)
 
 NEW_ENTRIES = ("yf_images_decode160_device", "yf_images_decode160_ragged_device", "yf_images_run_decode160_device",
                "yf_images_run_decode160_ragged_device", "yf_images_nms_wide_device")
 NEW_SOURCES = ("yf_images_decode160.h", "yf_images_wide.hip.h")
 SCALES = [np.float32(1.0), np.float32(410 / 160.), np.float32(16384 / 160.), np.float32(1 / 160.)]
-
-
-@pytest.fixture(scope="module")
-def host():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
-    lib.yfi_decode160_host.restype = ctypes.c_int
-    lib.yfi_decode160_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int]
-    lib.yfi_decode160_q_threshold_host.restype = ctypes.c_int
-    lib.yfi_nms_key_wide_host.restype = ctypes.c_uint64
-    lib.yfi_nms_key_wide_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    lib.yfi_nms_key_host.restype = ctypes.c_uint64
-    lib.yfi_nms_key_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def images():
-    return importlib.import_module("stm32h7-yolo_amd.images")
 
 
 def _decode_host(yf, lib, head, frame, ws, hs, cap):
@@ -116,19 +91,15 @@ def test_wide_order_key_is_the_stable_descending_argsort(host):
         assert host.yfi_nms_key_wide_host(int(c), 0) >> 11 == host.yfi_nms_key_host(int(c), 0) >> 8
 
 
-def _text(lib):
-    return (lib.yf_images_last_error_text() or b"").decode()
-
-
 def test_new_entry_points_check_every_argument_before_any_launch(images):
     lib = images.load()
     P, F, H, D, C, I, S, NET = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000, 0x70000, 0x80000      # never dereferenced
 
     def dec(heads=H, n=4, dets=D, counts=C, cap=1200):
-        return lib.yf_images_decode160_device(heads, n, 1.0, 1.0, dets, counts, cap, None), _text(lib)
+        return lib.yf_images_decode160_device(heads, n, 1.0, 1.0, dets, counts, cap, None), last_error(lib)
 
     def dec_r(heads=H, imgs=I, status=S, n=4, dets=D, counts=C, cap=1200):
-        return lib.yf_images_decode160_ragged_device(heads, imgs, status, n, dets, counts, cap, None), _text(lib)
+        return lib.yf_images_decode160_ragged_device(heads, imgs, status, n, dets, counts, cap, None), last_error(lib)
 
     decode_cases = [(dict(n=-1), "n < 0"), (dict(heads=None), "d_heads is NULL"), (dict(heads=H + 8), "d_heads is not 16-byte"),
                     (dict(dets=None), "d_dets is NULL"), (dict(counts=None), "d_counts is NULL"), (dict(dets=D + 2), "d_dets is not 4-byte"),
@@ -153,7 +124,7 @@ def test_new_entry_points_check_every_argument_before_any_launch(images):
         a = dict(good, **kw)
         rc = lib.yf_images_run_decode160_device(a["net"], a["d_pixels"], a["pixels_bytes"], a["format"], a["height"], a["width"], a["row_stride"],
                                                 a["frame_stride"], a["n"], a["d_frames"], a["heads"], a["dets"], a["counts"], a["cap"], None)
-        return rc, _text(lib)
+        return rc, last_error(lib)
 
     run_cases = [(dict(net=None), "handle"), (dict(format=4), "format"), (dict(n=-1), "n < 0"), (dict(d_frames=F + 4), "16-byte"),
                  (dict(d_frames=None), "d_frames"), (dict(height=0), "height and width"), (dict(width=16385, row_stride=16385 * 3), "height and width"),
@@ -171,7 +142,7 @@ def test_new_entry_points_check_every_argument_before_any_launch(images):
 
     def run_r(net=NET, d_pixels=P, fmt=0, imgs=I, n=3, d_frames=F, heads=H, dets=D, counts=C, cap=1200, status=S):
         rc = lib.yf_images_run_decode160_ragged_device(net, d_pixels, 100, fmt, imgs, n, d_frames, heads, dets, counts, cap, status, None)
-        return rc, _text(lib)
+        return rc, last_error(lib)
     for kw, word in [(dict(net=None), "handle"), (dict(fmt=7), "format"), (dict(n=-1), "n < 0"), (dict(d_frames=F + 8), "16-byte"),
                      (dict(imgs=None), "d_images"), (dict(status=None), "d_status"), (dict(d_pixels=None), "d_pixels"),
                      (dict(heads=H + 1), "d_heads is not 16-byte"), (dict(dets=D + 1), "d_dets is not 4-byte"), (dict(counts=None), "d_counts is NULL"),
@@ -185,7 +156,7 @@ def test_new_entry_points_check_every_argument_before_any_launch(images):
     def nms(**kw):
         a = dict(goodn, **kw)
         rc = lib.yf_images_nms_wide_device(a["dets"], a["counts"], a["n"], a["cap"], a["thr"], a["out"], a["out_counts"], None)
-        return rc, _text(lib)
+        return rc, last_error(lib)
     cases = [(dict(n=-1), "n < 0"), (dict(cap=0), "cap must be"), (dict(cap=-3), "cap must be"), (dict(cap=images.NMS_WIDE_MAX_CAP + 1), "cap must be"),
              (dict(thr=float("nan")), "NaN"), (dict(dets=None), "d_dets is NULL"), (dict(counts=None), "d_counts is NULL"),
              (dict(out=None), "d_out is NULL"), (dict(out_counts=None), "d_out_counts is NULL"), (dict(dets=D + 2), "d_dets is not 4-byte"),

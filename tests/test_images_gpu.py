@@ -1,93 +1,13 @@
 """libyf_images on the MI355X: frames bit-exact against ptq.resize_linear_u8 (the restatement of cv2.resize INTER_LINEAR, unpinned against a
 real cv2) for every tap table, every pixel format and layout, and on through the network to records equal to the oracle's decode with each
 image's own scales."""
-import ctypes
-import importlib
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from images_support import FMT_CH, REF_SIZES, Batch, expect_frame, host_lib, real_images
+from images_support import images_after_network, ptq, torch_cuda          # noqa: F401 (fixtures; `images` is images_after_network)
 
 pytestmark = pytest.mark.gpu
-
-# the reference's 27 sample images (yoloface/small_dataset, sorted by name), (width, height)
-REF_SIZES = [(410, 362), (389, 450), (410, 356), (299, 410), (331, 410), (327, 410), (410, 391), (410, 330), (301, 410), (410, 450),
-             (410, 283), (410, 281), (274, 410), (282, 410), (406, 450), (410, 312), (327, 410), (410, 273), (410, 295), (410, 297),
-             (305, 409), (410, 344), (306, 450), (278, 410), (410, 301), (253, 409), (410, 295)]
-FMT_CH = {0: 3, 1: 3, 2: 4, 3: 4}
-BGR = {0: True, 1: False, 2: True, 3: False}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def images(network):
-    return importlib.import_module("stm32h7-yolo_amd.images")
-
-
-@pytest.fixture(scope="module")
-def ptq():
-    return importlib.import_module("stm32h7-yolo_amd.ptq")
-
-
-def expect_frame(ptq, img, fmt, out):
-    """the restatement: RGB order, cv2.resize, minus 128, int8"""
-    rgb = img[..., :3][..., ::-1] if BGR[fmt] else img[..., :3]
-    return (ptq.resize_linear_u8(np.ascontiguousarray(rgb), out, out).astype(np.int16) - 128).astype(np.int8)
-
-
-class Batch:
-    """a packed ragged batch on the device with its workspaces"""
-
-    def __init__(self, torch, images, imgs, fmt, out=56, cap=147, desc=None, buf=None):
-        self.n = len(imgs) if desc is None else desc.shape[0]
-        if desc is None:
-            buf, desc = images.pack_images(imgs, fmt)
-        self.buf, self.desc, self.fmt, self.out, self.cap = buf, desc, fmt, out, cap
-        self.d_px = torch.from_numpy(buf).cuda()
-        self.d_desc = torch.from_numpy(desc.view(np.uint8).copy()).cuda()
-        n = max(self.n, 1)
-        self.d_frames = torch.full((n, out, out, 3), 77, dtype=torch.int8, device="cuda")
-        self.d_heads = torch.zeros((n, 7, 7, 18), dtype=torch.int8, device="cuda")
-        self.d_dets = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
-        self.d_counts = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-        self.d_status = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-
-    def prepare(self, images):
-        images.prepare_ragged_device(self.d_px.data_ptr(), self.buf.nbytes, self.fmt, self.d_desc.data_ptr(), self.n, self.out,
-                                     self.d_frames.data_ptr(), self.d_status.data_ptr())
-
-    def run_decode(self, images, network, mode=0):
-        images.run_decode_ragged_device(network, self.d_px.data_ptr(), self.buf.nbytes, self.fmt, self.d_desc.data_ptr(), self.n,
-                                        self.d_frames.data_ptr(), self.d_heads.data_ptr(), self.d_dets.data_ptr(), self.d_counts.data_ptr(),
-                                        self.cap, self.d_status.data_ptr(), mode=mode)
-
-    def records(self, yf):
-        import torch
-        torch.cuda.synchronize()
-        dets = self.d_dets.cpu().numpy().view(yf.DET_DTYPE).reshape(-1, self.cap)
-        counts = self.d_counts.cpu().numpy()
-        return [[tuple(r.item() for r in d) for d in dets[i, :min(int(counts[i]), self.cap)]] for i in range(self.n)], counts
-
-
-def host_lib():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
-    lib.yfi_resize_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int,
-                                    ctypes.c_void_p]
-    return lib
 
 
 @pytest.mark.parametrize("out", [56, 160])
@@ -161,13 +81,6 @@ def test_formats_strides_and_offsets(yf, network, oracle, torch_cuda, images, pt
         assert np.array_equal(d_out.cpu().numpy(), oracle.run(x))
 
 
-def _real_images(ptq):
-    """the 27 real frames (+128, RGB) upscaled by the restatement to the reference sizes, stored as BGR as cv2.imread gives them"""
-    real = np.fromfile(os.path.join(ROOT, "tests", "golden", "real_frames_56.bin"), np.int8).reshape(-1, 56, 56, 3)
-    rgb56 = (real.astype(np.int16) + 128).astype(np.uint8)
-    return [np.ascontiguousarray(ptq.resize_linear_u8(rgb56[i], w, h)[..., ::-1]) for i, (w, h) in enumerate(REF_SIZES)]
-
-
 def _check_against_oracle(yf, oracle, ptq, b, imgs, variant=0):
     frames_ref = np.stack([expect_frame(ptq, im, 0, 56) for im in imgs])
     assert np.array_equal(b.d_frames.cpu().numpy(), frames_ref)
@@ -183,7 +96,7 @@ def _check_against_oracle(yf, oracle, ptq, b, imgs, variant=0):
 
 
 def test_real_content_to_boxes(yf, network, oracle, torch_cuda, images, ptq):
-    imgs = _real_images(ptq)
+    imgs = real_images(ptq)
     b = Batch(torch_cuda, images, imgs, "bgr")
     b.run_decode(images, network)
     torch_cuda.cuda.synchronize()
@@ -199,7 +112,7 @@ def test_real_content_to_boxes(yf, network, oracle, torch_cuda, images, ptq):
 
 
 def test_rounding_is_honoured(yf, network, oracle, torch_cuda, images, ptq):
-    imgs = _real_images(ptq)
+    imgs = real_images(ptq)
     b = Batch(torch_cuda, images, imgs, "bgr")
     network.set_requant_rounding(yf.YF_ROUND_TIES_UP)
     try:
@@ -215,7 +128,7 @@ def test_uniform_equals_ragged(yf, network, torch_cuda, images, ptq):
     the scalar scales give the same records"""
     torch = torch_cuda
     n, H, W = 4096, 362, 410
-    real = _real_images(ptq)[0]
+    real = real_images(ptq)[0]
     assert real.shape == (H, W, 3)
     g = torch.Generator(device="cuda").manual_seed(5)
     base = torch.from_numpy(real).cuda()

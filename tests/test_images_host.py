@@ -5,39 +5,11 @@ import concurrent.futures
 import ctypes
 import importlib
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _host_lib(build=True):
-    if build:
-        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
-    lib.yfi_resize_host.restype = ctypes.c_int
-    lib.yfi_resize_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int,
-                                    ctypes.c_void_p]
-    lib.yfi_tap_host.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.yfi_image_ok_host.restype = ctypes.c_int
-    lib.yfi_image_ok_host.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def host():
-    return _host_lib()
-
-
-@pytest.fixture(scope="module")
-def images():
-    return importlib.import_module("stm32h7-yolo_amd.images")
+from images_support import PKG, host, host_lib, images, last_error          # noqa: F401 (host, images: fixtures)
 
 
 def _resize_host(lib, img, out):
@@ -52,7 +24,7 @@ def _sweep(args):
     """one worker: sizes [lo, hi) as 1 x W and H x 1 images at output size `out`; returns the sizes that differ"""
     lo, hi, out = args
     ptq = importlib.import_module("stm32h7-yolo_amd.ptq")
-    lib = _host_lib(build=False)
+    lib = host_lib(build=False)
     bad = []
     for s in range(lo, hi):
         rng = np.random.default_rng(s * 1000 + out)
@@ -160,7 +132,7 @@ def test_uniform_entry_points_check_every_argument_before_any_launch(images):
         a = dict(good, **kw)
         rc = lib.yf_images_prepare_device(a["d_pixels"], a["pixels_bytes"], a["format"], a["height"], a["width"], a["row_stride"],
                                           a["frame_stride"], a["n"], a["out_hw"], a["d_frames"], None)
-        return rc, (lib.yf_images_last_error_text() or b"").decode()
+        return rc, last_error(lib)
 
     cases = {
         "format": dict(format=4), "out_hw": dict(out_hw=112), "n < 0": dict(n=-1), "16-byte": dict(d_frames=F + 4),
@@ -180,18 +152,18 @@ def test_uniform_entry_points_check_every_argument_before_any_launch(images):
     def run(net=0x60000, mode=0, cap=147, heads=H, dets=D, counts=C):
         rc = lib.yf_images_run_decode_device(net, a["d_pixels"], a["pixels_bytes"], 0, 362, 410, 1230, 362 * 1230, 4, F, heads, mode,
                                              dets, counts, cap, None)
-        return rc, (lib.yf_images_last_error_text() or b"").decode()
+        return rc, last_error(lib)
     for kw, word in [(dict(net=None), "handle"), (dict(mode=3), "mode"), (dict(cap=0), "cap"), (dict(dets=None), "NULL"),
                      (dict(counts=C + 2), "aligned")]:
         rc, text = run(**kw)
         assert rc <= 0 and word in text, (kw, rc, text)
     rc = lib.yf_images_run_decode_device(0x60000, P, 100, 0, 362, 410, 1230, 0, 1, F, H, 0, D, C, 147, None)
-    assert rc <= 0 and "first image" in (lib.yf_images_last_error_text() or b"").decode()
+    assert rc <= 0 and "first image" in last_error(lib)
     # the ragged forms: host-side checks of what the host can see
     rc = lib.yf_images_prepare_ragged_device(P, 100, 0, None, 3, 56, F, 0x70000, None)
-    assert rc <= 0 and "d_images" in (lib.yf_images_last_error_text() or b"").decode()
+    assert rc <= 0 and "d_images" in last_error(lib)
     rc = lib.yf_images_decode_ragged_device(H, 0x70000, 3, 7, D, C, 147, None)
-    assert rc <= 0 and "mode" in (lib.yf_images_last_error_text() or b"").decode()
+    assert rc <= 0 and "mode" in last_error(lib)
     # n = 0 is a valid empty batch: nothing is launched
     assert prep(n=0, d_pixels=None, pixels_bytes=0)[0] == 0
 

@@ -1,105 +1,42 @@
 """IoU suppression of decoded records on the MI355X (yf_images_nms_device): every frame's output equals the restatement of
-YoloFaceDetector.non_max_suppression (yoloface/tensorflow/yoloface_test.py:165-190, stable tie order; tests/test_nms_host.py) applied to that
+YoloFaceDetector.non_max_suppression (yoloface/tensorflow/yoloface_test.py:165-190, stable tie order; tests/images_support.py) applied to that
 frame's input records, byte for byte and in keep order -- on the reference's 27 images against the oracle's records, on seeded synthetic
 heads in all three decode modes and four thresholds, in place, with cap below the count, and through images.detect()."""
-import importlib
-import importlib.util
-import os
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from images_support import Batch, check_nms, expect_frame, real_images, sentinels, suppress, synthetic_heads, to_host, tuples
+from images_support import images_after_network, ptq, torch_cuda          # noqa: F401 (fixtures; `images` is images_after_network)
 
 pytestmark = pytest.mark.gpu
 
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(f"_nms_{name}", os.path.join(ROOT, "tests", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-restated = _load("test_nms_host")           # nms_restated, suppress
-img_tests = _load("test_images_gpu")        # the 27 real images and the ragged-batch helper
-
 THRESHOLDS = (0.0, 0.4, 0.5, 1.0)
 I32_MIN = -2 ** 31
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def images(network):
-    return importlib.import_module("stm32h7-yolo_amd.images")
-
-
-@pytest.fixture(scope="module")
-def ptq():
-    return importlib.import_module("stm32h7-yolo_amd.ptq")
-
-
-def _host(yf, d_dets, d_counts, cap):
-    import torch
-    torch.cuda.synchronize()
-    return d_dets.cpu().numpy().view(yf.DET_DTYPE).reshape(-1, cap), d_counts.cpu().numpy()
-
-
-def _expect_frame(rows, count, cap, thr):
-    """the kept rows of one frame: the restatement over its first min(max(count, 0), cap) records"""
-    m = min(max(int(count), 0), cap)
-    r = rows[:m]
-    boxes = np.stack([r["x1"], r["y1"], r["x2"], r["y2"], r["conf"]], axis=1).astype(np.float64)      # what np.array(boxes) makes
-    return r[restated.nms_restated(boxes, thr)]
-
-
-def _check_batch(yf, dets_in, counts_in, d_out, d_oc, cap, thr, frames=None):
-    out, oc = _host(yf, d_out, d_oc, cap)
-    lost = 0
-    for f in (range(dets_in.shape[0]) if frames is None else frames):
-        want = _expect_frame(dets_in[f], counts_in[f], cap, thr)
-        assert oc[f] == want.shape[0], (f, thr, oc[f], want.shape[0])
-        assert out[f, :want.shape[0]].tobytes() == want.tobytes(), (f, thr)
-        lost += min(max(int(counts_in[f]), 0), cap) - want.shape[0]
-    return lost
 
 
 def _nms(images, d_dets, d_counts, n, cap, thr, d_out, d_oc):
     images.nms_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, thr, d_out.data_ptr(), d_oc.data_ptr())
 
 
-def _sentinels(torch, n, cap):
-    return torch.full((max(n, 1), cap, 28), 0xA5, dtype=torch.uint8, device="cuda"), torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-
-
 def test_real_images_against_the_oracle(yf, network, oracle, torch_cuda, images, ptq):
     torch = torch_cuda
-    imgs = img_tests._real_images(ptq)
-    b = img_tests.Batch(torch, images, imgs, "bgr")
+    imgs = real_images(ptq)
+    b = Batch(torch, images, imgs, "bgr")
     b.run_decode(images, network)
     torch.cuda.synchronize()
-    frames = np.stack([img_tests.expect_frame(ptq, im, 0, 56) for im in imgs])
+    frames = np.stack([expect_frame(ptq, im, 0, 56) for im in imgs])
     heads = oracle.run(frames)
     assert np.array_equal(b.d_heads.cpu().numpy(), heads)
     want_in = [oracle.decode_py(heads[i], i, w_scale=im.shape[1] / 56., h_scale=im.shape[0] / 56.) for i, im in enumerate(imgs)]
-    dets_in, counts_in = _host(yf, b.d_dets, b.d_counts, b.cap)
-    assert [[tuple(r.item() for r in d) for d in dets_in[i, :counts_in[i]]] for i in range(b.n)] == want_in
+    dets_in, counts_in = to_host(yf, b.d_dets, b.d_counts, b.cap)
+    assert [tuples(dets_in[i, :counts_in[i]]) for i in range(b.n)] == want_in
     lost_at = {}
     for thr in THRESHOLDS:
-        d_out, d_oc = _sentinels(torch, b.n, b.cap)
+        d_out, d_oc = sentinels(torch, b.n, b.cap)
         _nms(images, b.d_dets, b.d_counts, b.n, b.cap, thr, d_out, d_oc)
-        out, oc = _host(yf, d_out, d_oc, b.cap)
-        got = [[tuple(r.item() for r in d) for d in out[i, :oc[i]]] for i in range(b.n)]
-        assert got == [restated.suppress(w, thr) for w in want_in], thr
+        out, oc = to_host(yf, d_out, d_oc, b.cap)
+        got = [tuples(out[i, :oc[i]]) for i in range(b.n)]
+        assert got == [suppress(w, thr) for w in want_in], thr
         lost_at[thr] = sum(len(w) for w in want_in) - sum(len(g) for g in got)
         # slots beyond the kept count are not written
         raw = d_out.cpu().numpy()
@@ -109,22 +46,12 @@ def test_real_images_against_the_oracle(yf, network, oracle, torch_cuda, images,
     assert lost_at[0.0] >= lost_at[0.4] >= lost_at[1.0]
 
 
-def _synthetic_heads(rng, n):
-    """seeded heads: random bytes (about half the candidates fire: q_conf >= -9), every third frame sparse, every 64th frame all 147
-    candidates at one shared q_conf"""
-    heads = rng.integers(-128, 128, (n, 7, 7, 18), dtype=np.int16)
-    heads[1::3, ..., 4::6] = rng.integers(-128, 0, heads[1::3, ..., 4::6].shape)
-    for f in range(0, n, 64):
-        heads[f, ..., 4::6] = 96 + (f // 64) % 32
-    return heads.astype(np.int8)
-
-
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_synthetic_heads_every_mode_and_threshold(yf, network, torch_cuda, images, mode):
     torch = torch_cuda
     n, cap = 4096, 147
     rng = np.random.default_rng(100 + mode)
-    heads = _synthetic_heads(rng, n)
+    heads = synthetic_heads(rng, n)
     d_heads = torch.from_numpy(heads).cuda()
     d_dets = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
     d_counts = torch.zeros((n,), dtype=torch.int32, device="cuda")
@@ -138,7 +65,7 @@ def test_synthetic_heads_every_mode_and_threshold(yf, network, torch_cuda, image
     half = n // 2
     network.decode_device(d_heads[half:].data_ptr(), n - half, d_dets[half:].data_ptr(), d_counts[half:].data_ptr(), cap, mode=mode,
                           w_scale=6.0e7, h_scale=5.0e7)
-    dets_in, counts_in = _host(yf, d_dets, d_counts, cap)
+    dets_in, counts_in = to_host(yf, d_dets, d_counts, cap)
     assert (counts_in[::64] == 147).all() and counts_in.min() >= 0
     tied = dets_in[0, :147]
     assert (tied["q_conf"] == tied["q_conf"][0]).all()
@@ -147,9 +74,9 @@ def test_synthetic_heads_every_mode_and_threshold(yf, network, torch_cuda, image
         assert (edges == I32_MIN).any() and (edges != I32_MIN).any()
     saved = d_dets.clone()
     for thr in THRESHOLDS:
-        d_out, d_oc = _sentinels(torch, n, cap)
+        d_out, d_oc = sentinels(torch, n, cap)
         _nms(images, d_dets, d_counts, n, cap, thr, d_out, d_oc)
-        lost = _check_batch(yf, dets_in, counts_in, d_out, d_oc, cap, thr)
+        lost = check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, thr)
         if thr < 1.0:
             assert lost > 0
     assert torch.equal(saved, d_dets)                       # out of place: the input is not touched
@@ -158,23 +85,23 @@ def test_synthetic_heads_every_mode_and_threshold(yf, network, torch_cuda, image
 def test_in_place_cap_below_count_and_odd_counts(yf, network, torch_cuda, images):
     torch = torch_cuda
     n, cap = 4096, 147
-    heads = _synthetic_heads(np.random.default_rng(7), n)
+    heads = synthetic_heads(np.random.default_rng(7), n)
     d_heads = torch.from_numpy(heads).cuda()
     d_dets = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
     d_counts = torch.zeros((n,), dtype=torch.int32, device="cuda")
     network.decode_device(d_heads.data_ptr(), n, d_dets.data_ptr(), d_counts.data_ptr(), cap, w_scale=7.3, h_scale=8.1)
-    dets_in, counts_in = _host(yf, d_dets, d_counts, cap)
+    dets_in, counts_in = to_host(yf, d_dets, d_counts, cap)
     # in place equals out of place
-    d_out, d_oc = _sentinels(torch, n, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     _nms(images, d_dets, d_counts, n, cap, 0.4, d_out, d_oc)
     images.nms_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, 0.4)
     torch.cuda.synchronize()
     assert torch.equal(d_counts, d_oc)
-    a, _ = _host(yf, d_dets, d_counts, cap)
-    b, oc = _host(yf, d_out, d_oc, cap)
+    a, _ = to_host(yf, d_dets, d_counts, cap)
+    b, oc = to_host(yf, d_out, d_oc, cap)
     for f in range(n):
         assert a[f, :oc[f]].tobytes() == b[f, :oc[f]].tobytes(), f
-    _check_batch(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4)
+    check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4)
     # counts below zero and above cap: the first min(max(count, 0), cap) records
     odd = counts_in.copy()
     odd[1::5] = -3
@@ -182,19 +109,19 @@ def test_in_place_cap_below_count_and_odd_counts(yf, network, torch_cuda, images
     odd[3::5] = np.minimum(odd[3::5], 1)
     d_odd = torch.from_numpy(odd).cuda()
     d_src = torch.from_numpy(dets_in.view(np.uint8).reshape(n, cap, 28).copy()).cuda()
-    d_out, d_oc = _sentinels(torch, n, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     _nms(images, d_src, d_odd, n, cap, 0.4, d_out, d_oc)
-    _check_batch(yf, dets_in, odd, d_out, d_oc, cap, 0.4)
+    check_nms(yf, dets_in, odd, d_out, d_oc, cap, 0.4)
     # cap below the count: the decode writes 20 records of a frame that has more, the suppression runs over those 20
     c20 = 20
     d20 = torch.zeros((n, c20, 28), dtype=torch.uint8, device="cuda")
     k20 = torch.zeros((n,), dtype=torch.int32, device="cuda")
     network.decode_device(d_heads.data_ptr(), n, d20.data_ptr(), k20.data_ptr(), c20, w_scale=7.3, h_scale=8.1)
-    in20, cnt20 = _host(yf, d20, k20, c20)
+    in20, cnt20 = to_host(yf, d20, k20, c20)
     assert (cnt20 > c20).any()
-    d_out, d_oc = _sentinels(torch, n, c20)
+    d_out, d_oc = sentinels(torch, n, c20)
     _nms(images, d20, k20, n, c20, 0.4, d_out, d_oc)
-    _check_batch(yf, in20, cnt20, d_out, d_oc, c20, 0.4)
+    check_nms(yf, in20, cnt20, d_out, d_oc, c20, 0.4)
     # the largest cap, and records that are not a decode's (any conf bits, ties and all, -0.0 and NaN included)
     big = images.NMS_MAX_CAP
     rng = np.random.default_rng(12)
@@ -207,33 +134,33 @@ def test_in_place_cap_below_count_and_odd_counts(yf, network, torch_cuda, images
     cnt[0] = big
     d_recs = torch.from_numpy(recs.view(np.uint8).reshape(64, big, 28).copy()).cuda()
     d_cnt = torch.from_numpy(cnt).cuda()
-    d_out, d_oc = _sentinels(torch, 64, big)
+    d_out, d_oc = sentinels(torch, 64, big)
     _nms(images, d_recs, d_cnt, 64, big, 0.3, d_out, d_oc)
-    _check_batch(yf, recs, cnt, d_out, d_oc, big, 0.3)
+    check_nms(yf, recs, cnt, d_out, d_oc, big, 0.3)
 
 
 def test_zero_frames_and_100000(yf, network, torch_cuda, images):
     torch = torch_cuda
     cap = 147
     # n = 0: nothing launched, nothing written
-    d_dets, d_counts = _sentinels(torch, 1, cap)
-    d_out, d_oc = _sentinels(torch, 1, cap)
+    d_dets, d_counts = sentinels(torch, 1, cap)
+    d_out, d_oc = sentinels(torch, 1, cap)
     _nms(images, d_dets, d_counts, 0, cap, 0.4, d_out, d_oc)
     torch.cuda.synchronize()
     assert (d_out == 0xA5).all().item() and (d_oc == -7).all().item()
     # 100 000 frames: the heads of 4096 frames repeated; every frame's output is its own frame's suppression (frame field included)
     n, base = 100000, 4096
-    heads = _synthetic_heads(np.random.default_rng(21), base)
+    heads = synthetic_heads(np.random.default_rng(21), base)
     d_heads = torch.from_numpy(np.concatenate([heads] * (n // base + 1))[:n]).cuda()
     d_dets = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
     d_counts = torch.zeros((n,), dtype=torch.int32, device="cuda")
     network.decode_device(d_heads.data_ptr(), n, d_dets.data_ptr(), d_counts.data_ptr(), cap, w_scale=7.3, h_scale=8.1)
-    dets_in, counts_in = _host(yf, d_dets, d_counts, cap)
-    d_out, d_oc = _sentinels(torch, n, cap)
+    dets_in, counts_in = to_host(yf, d_dets, d_counts, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     _nms(images, d_dets, d_counts, n, cap, 0.4, d_out, d_oc)
-    out, oc = _host(yf, d_out, d_oc, cap)
+    out, oc = to_host(yf, d_out, d_oc, cap)
     sample = list(range(0, n, 37)) + list(range(n - 64, n))
-    _check_batch(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4, frames=sample)
+    check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4, frames=sample)
     # the same heads give the same records up to the frame field
     first = out[:base].copy()
     for r in range(1, n // base):
@@ -247,13 +174,13 @@ def test_zero_frames_and_100000(yf, network, torch_cuda, images):
 def test_graph_capture(yf, network, torch_cuda, images):
     torch = torch_cuda
     n, cap = 512, 147
-    heads = _synthetic_heads(np.random.default_rng(31), n)
+    heads = synthetic_heads(np.random.default_rng(31), n)
     d_heads = torch.from_numpy(heads).cuda()
     d_dets = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
     d_counts = torch.zeros((n,), dtype=torch.int32, device="cuda")
     network.decode_device(d_heads.data_ptr(), n, d_dets.data_ptr(), d_counts.data_ptr(), cap, w_scale=5.0, h_scale=6.0)
-    dets_in, counts_in = _host(yf, d_dets, d_counts, cap)
-    d_out, d_oc = _sentinels(torch, n, cap)
+    dets_in, counts_in = to_host(yf, d_dets, d_counts, cap)
+    d_out, d_oc = sentinels(torch, n, cap)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     g = torch.cuda.CUDAGraph()
@@ -264,19 +191,19 @@ def test_graph_capture(yf, network, torch_cuda, images):
     assert (d_oc == -7).all().item()                         # captured, not run
     g.replay()
     torch.cuda.synchronize()
-    _check_batch(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4)
+    check_nms(yf, dets_in, counts_in, d_out, d_oc, cap, 0.4)
 
 
 def test_detect_with_and_without_suppression(yf, network, oracle, torch_cuda, images, ptq):
-    imgs = img_tests._real_images(ptq)
-    frames = np.stack([img_tests.expect_frame(ptq, im, 0, 56) for im in imgs])
+    imgs = real_images(ptq)
+    frames = np.stack([expect_frame(ptq, im, 0, 56) for im in imgs])
     heads = oracle.run(frames)
     recs = [oracle.decode_py(heads[i], i, w_scale=im.shape[1] / 56., h_scale=im.shape[0] / 56.) for i, im in enumerate(imgs)]
     plain = images.detect(network, imgs, "bgr")
     assert [bx.tolist() for bx in plain] == [[[r[6], r[7], r[8], r[9]] for r in rr] for rr in recs]
     for thr in (0.4, 0.0):
         boxes = images.detect(network, imgs, "bgr", iou_threshold=thr)
-        want = [[[r[6], r[7], r[8], r[9]] for r in restated.suppress(rr, thr)] for rr in recs]
+        want = [[[r[6], r[7], r[8], r[9]] for r in suppress(rr, thr)] for rr in recs]
         assert [bx.tolist() for bx in boxes] == want, thr
         assert all(bx.dtype == np.int32 and bx.shape[1] == 4 for bx in boxes)
     assert sum(len(b) for b in images.detect(network, imgs, "bgr", iou_threshold=0.4)) < sum(len(b) for b in plain)

@@ -1,111 +1,16 @@
 """The IoU suppression of libyf_images on the host (no GPU): the pairwise decision of csrc/yf_images_nms.h -- the same function the device
 kernel calls, compiled for the host -- against numpy's float64 arithmetic, the record order key, the restatement of the reference's
 non_max_suppression against its literal code, and the argument checks of yf_images_nms_device (which return before any launch).
-
-`nms_restated` is the project's statement of YoloFaceDetector.non_max_suppression (yoloface/tensorflow/yoloface_test.py:165-190): a literal
-copy with one change, a stable sort (ties later record first).  `nms_reference_literal` keeps the reference's default argsort."""
-import ctypes
-import importlib
+The restatement itself (`nms_restated`, `nms_reference_literal`) is in tests/images_support.py."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from conftest import ROOT
+from images_support import PKG, host, images, last_error, nms_reference_literal, nms_restated          # noqa: F401 (host, images: fixtures)
 
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
-
-
-def _boxes(recs):
-    """records (DET_DTYPE rows or tuples (frame, anchor, row, col, q_conf, conf, x1, y1, x2, y2)) -> the reference's boxes list"""
-    return [[int(r[6]), int(r[7]), int(r[8]), int(r[9]), float(r[5])] for r in recs]
-
-
-def nms_reference_literal(boxes, iou_threshold):
-    """yoloface_test.py:165-190 as written (numpy's default argsort); returns `keep`, the indices boxes[keep] is taken with"""
-    if len(boxes) == 0:
-        return []
-    boxes = np.array(boxes)
-    x1 = boxes[:, 0]
-    y1 = boxes[:, 1]
-    x2 = boxes[:, 2]
-    y2 = boxes[:, 3]
-    conf = boxes[:, 4]
-    area = (x2 - x1 + 1) * (y2 - y1 + 1)
-    order = conf.argsort()[::-1]
-    keep = []
-    while order.size > 0:
-        i = order[0]
-        keep.append(i)
-        xx1 = np.maximum(x1[i], x1[order[1:]])
-        yy1 = np.maximum(y1[i], y1[order[1:]])
-        xx2 = np.minimum(x2[i], x2[order[1:]])
-        yy2 = np.minimum(y2[i], y2[order[1:]])
-        w = np.maximum(0.0, xx2 - xx1 + 1)
-        h = np.maximum(0.0, yy2 - yy1 + 1)
-        intersection = w * h
-        union = area[i] + area[order[1:]] - intersection
-        with np.errstate(divide="ignore", invalid="ignore"):
-            iou = intersection / union
-        inds = np.where(iou <= iou_threshold)[0]
-        order = order[inds + 1]
-    return [int(k) for k in keep]
-
-
-def nms_restated(boxes, iou_threshold):
-    """the same with the pinned order: np.argsort(conf, kind="stable")[::-1] (descending conf, ties later record first)"""
-    if len(boxes) == 0:
-        return []
-    boxes = np.array(boxes)
-    x1 = boxes[:, 0]
-    y1 = boxes[:, 1]
-    x2 = boxes[:, 2]
-    y2 = boxes[:, 3]
-    conf = boxes[:, 4]
-    area = (x2 - x1 + 1) * (y2 - y1 + 1)
-    order = np.argsort(conf, kind="stable")[::-1]
-    keep = []
-    while order.size > 0:
-        i = order[0]
-        keep.append(i)
-        xx1 = np.maximum(x1[i], x1[order[1:]])
-        yy1 = np.maximum(y1[i], y1[order[1:]])
-        xx2 = np.minimum(x2[i], x2[order[1:]])
-        yy2 = np.minimum(y2[i], y2[order[1:]])
-        w = np.maximum(0.0, xx2 - xx1 + 1)
-        h = np.maximum(0.0, yy2 - yy1 + 1)
-        intersection = w * h
-        union = area[i] + area[order[1:]] - intersection
-        with np.errstate(divide="ignore", invalid="ignore"):
-            iou = intersection / union
-        inds = np.where(iou <= iou_threshold)[0]
-        order = order[inds + 1]
-    return [int(k) for k in keep]
-
-
-def suppress(recs, iou_threshold):
-    """the kept records of one frame, in keep order"""
-    return [recs[k] for k in nms_restated(_boxes(recs), iou_threshold)]
-
-
-def _host_lib():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
-    lib.yfi_nms_pairs_host.restype = None
-    lib.yfi_nms_pairs_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
-    lib.yfi_nms_key_host.restype = ctypes.c_uint64
-    lib.yfi_nms_key_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def host():
-    return _host_lib()
 
 
 def _pairs_host(lib, a, b, thr):
@@ -226,11 +131,6 @@ def test_restatement_equals_the_reference_code_on_distinct_confidences():
     assert nms_restated(tie, 0.4) == [1, 2]
 
 
-@pytest.fixture(scope="module")
-def images():
-    return importlib.import_module("stm32h7-yolo_amd.images")
-
-
 def test_nms_entry_checks_every_argument_before_any_launch(images):
     lib = images.load()
     D, C, O, OC = 0x10000, 0x20000, 0x30000, 0x40000                    # never dereferenced: every call below fails its host checks
@@ -239,7 +139,7 @@ def test_nms_entry_checks_every_argument_before_any_launch(images):
     def nms(**kw):
         a = dict(good, **kw)
         rc = lib.yf_images_nms_device(a["dets"], a["counts"], a["n"], a["cap"], a["thr"], a["out"], a["out_counts"], None)
-        return rc, (lib.yf_images_last_error_text() or b"").decode()
+        return rc, last_error(lib)
 
     cases = [
         (dict(n=-1), "n < 0"), (dict(cap=0), "cap must be"), (dict(cap=-3), "cap must be"), (dict(cap=images.NMS_MAX_CAP + 1), "cap must be"),
