@@ -122,6 +122,45 @@ YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_p
 YF_API long yf_images_nms_wide_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold,
                                       void* d_out, void* d_out_counts, void* stream);
 
+/* ---- the fp16 network (yf_network_fp16_init / yf_network_fp16_run_device: fp16 frames [n][56][56][3] in, float32 logits [n][7][7][18]
+ * out): the reference's float caller, yoloface/tensorflow/h5_predition.py:29-73, for a batch.  The arithmetic is stated once, in
+ * csrc/yf_images_float.h, which the kernels and a host build share.
+ *   frames:  frame[y][x][c] = fp16(R[y][x][rgb(c)] / 255.), R = cv2.resize(image, (56, 56)) as above; 18 816 bytes per frame, d_frames_f16
+ *            16-byte aligned.  The script's float64 `/255.`, the model's float32 and the network's fp16 give the same half for each of
+ *            the 256 bytes.  Only 56x56: the fp16 network has no other size.  Arguments are checked as by the int8 forms; in the ragged
+ *            form an invalid image gets d_status 1 and a frame of fp16 zeros (pixel 0), and is never read.
+ *   decode:  d_logits float32 [n][7][7][18] (4-byte aligned) -> yf_det records in the order (anchor, row, col), conf > 0.7f (a NaN does
+ *            not fire), one IEEE float32 operation per numpy operation of h5_predition.py:51-72 in the script's order:
+ *            sigmoid(x) = 1.0f / (1.0f + E(-x)); cx = (sigmoid(tx) + col) * 8, cy likewise with row; w = E(tw) * anchor_w, h likewise;
+ *            edges cx -+ w / 2, cy -+ h / 2, times w_scale / h_scale, float32 -> int32 as YF_DECODE_PY (truncation; out of range and
+ *            NaN -> INT32_MIN).  E(x) is the float32 nearest to the float64 value of e^x, on the whole float32 domain (+inf above
+ *            ~88.72, subnormals, 0, NaN -> NaN) -- the library's choice: numpy's own float32 exp differs from it by up to 2 ulp,
+ *            depending on the numpy build and the CPU, which can move an edge of the script's by 1.
+ *            The record's q_conf is 0 (there is no int8 logit); conf is the float32 sigmoid above.  d_counts[f] is the true count, which
+ *            may exceed cap; only the first cap records are written, slots at and beyond min(count, cap) are not touched.
+ *            1 <= cap <= 147.  The records feed yf_images_nms_device unchanged.
+ * Each call: asynchronous on `stream`, no allocation, no host synchronisation, every argument checked before the first launch; n = 0
+ * launches nothing and returns 0. */
+YF_API long yf_images_prepare_f16_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                         long row_stride, long frame_stride, long n, void* d_frames_f16, void* stream);
+YF_API long yf_images_prepare_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                void* d_frames_f16, int32_t* d_status, void* stream);
+YF_API long yf_images_decode_f32_device(const void* d_logits, long n, float w_scale, float h_scale,
+                                        void* d_dets, void* d_counts, int cap, void* stream);
+/* Per-image scales: w_scale = (float)((double)W / 56.0), h_scale likewise.  d_status (int32[n], as the ragged prepare wrote it) may be
+ * NULL; status 1 or a side outside [1, 16384] gives count 0. */
+YF_API long yf_images_decode_f32_ragged_device(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n,
+                                               void* d_dets, void* d_counts, int cap, void* stream);
+/* Images -> fp16 frames (d_frames_f16, the caller's workspace) -> yf_network_fp16_run_device -> logits (d_logits) -> records, on one
+ * stream.  A network on which yf_network_fp16_init has not succeeded is an error (the network's own text is passed on) and nothing is
+ * launched. */
+YF_API long yf_images_run_decode_f16_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                            long row_stride, long frame_stride, long n, void* d_frames_f16, void* d_logits,
+                                            void* d_dets, void* d_counts, int cap, void* stream);
+YF_API long yf_images_run_decode_f16_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                   const yf_image* d_images, long n, void* d_frames_f16, void* d_logits,
+                                                   void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

@@ -324,6 +324,9 @@ YF_API long yf_network_time_stages(ai_handle network, const void* d_in, void* d_
  * (pixel/255), d_out_f32: fp32 logits [n][7][7][18].  Independent of ai_network_init; needs only ai_network_create. */
 YF_API int  yf_network_fp16_init(ai_handle network, const void* yfw, size_t bytes);
 YF_API long yf_network_fp16_run_device(ai_handle network, const void* d_in_f16, void* d_out_f32, long n, void* stream);
+/* 1 once yf_network_fp16_init has succeeded on this network; else 0 with the error yf_network_fp16_run_device would give latched
+ * ("yf_network_fp16_init first").  For a caller that launches work of its own before the network and must not start without it. */
+YF_API int  yf_network_fp16_ready(ai_handle network);
 /* Text of the last HIP/runtime failure (empty string if none). */
 /* Device scratch (the fused kernels' park slots, the 160x160 arena) is owned by the launch stream and bounded: at most eight regions per kind, a region
  * whose last launch has completed is handed to the next stream that asks.  Release a stream's regions before destroying the stream; the second call

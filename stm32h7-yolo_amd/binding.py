@@ -95,7 +95,7 @@ EXPORTS = ["ai_network_create", "ai_network_init", "ai_network_run", "ai_network
            "ai_network_data_params_get", "ai_platform_bind_network_params", "yf_network_set_device",
            "yf_network_configure", "yf_network_run_device", "yf_network_run_device_dump", "yf_network_dump_bytes", "yf_network_run_device_hw",
            "yf_network_decode_device", "yf_network_run_decode_device", "yf_network_pack_detections_device", "yf_network_unpack_detections_device", "yf_network_prepare_rgb565_device", "yf_network_run_camera_device", "yf_network_time_device",
-           "yf_network_time_stages", "yf_network_format_uart", "yf_network_shard_range", "yf_network_table_plan", "yf_network_all_gather_device", "yf_network_fp16_init", "yf_network_fp16_run_device", "yf_network_release_stream", "yf_network_scratch_bytes", "yf_network_scratch_stats", "yf_network_set_requant_rounding", "yf_network_get_requant_rounding", "yf_network_last_error_text",
+           "yf_network_time_stages", "yf_network_format_uart", "yf_network_shard_range", "yf_network_table_plan", "yf_network_all_gather_device", "yf_network_fp16_init", "yf_network_fp16_run_device", "yf_network_fp16_ready", "yf_network_release_stream", "yf_network_scratch_bytes", "yf_network_scratch_stats", "yf_network_set_requant_rounding", "yf_network_get_requant_rounding", "yf_network_last_error_text",
            "yf_network_kernel_name", "yf_network_kernel_name_for", "yf_network_build_id", "yf_network_host_id",
            "ai_platform_observer_node_info", "ai_platform_observer_register", "ai_platform_observer_register_s",
            "ai_platform_observer_unregister", "ai_platform_observer_unregister_s",
@@ -294,6 +294,9 @@ def load():
     lib.yf_network_fp16_init.argtypes = [vp, vp, ctypes.c_size_t]
     lib.yf_network_fp16_run_device.restype = cl
     lib.yf_network_fp16_run_device.argtypes = [vp, vp, vp, cl, vp]
+    if hasattr(lib, "yf_network_fp16_ready"):              # (as below: an older library does without)
+        lib.yf_network_fp16_ready.restype = ctypes.c_int
+        lib.yf_network_fp16_ready.argtypes = [vp]
     if hasattr(lib, "yf_network_release_stream"):          # (an older library loaded through YF_LIB_PATH for an A/B run does without)
         lib.yf_network_release_stream.restype = ctypes.c_int
         lib.yf_network_release_stream.argtypes = [vp, vp]

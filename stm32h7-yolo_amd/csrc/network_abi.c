@@ -574,6 +574,13 @@ YF_API long yf_network_fp16_run_device(ai_handle network, const void* d_in_f16, 
   return n;
 }
 
+YF_API int yf_network_fp16_ready(ai_handle network) {
+  yf_context* c = acquire(network);
+  if (!c) return 0;
+  if (!c->fp16) { latch(c, AI_ERROR_INVALID_STATE, AI_ERROR_CODE_MISSED_INIT, "yf_network_fp16_init first"); return 0; }
+  return 1;
+}
+
 /* Scratch regions (tail-batching slots, the fp16 park slots, the 160x160 arena) belong to the launch STREAM and are bounded (at most eight per kind,
  * recycled once their last launch has completed).  A caller that destroys a stream hands its regions back first. */
 YF_API int yf_network_release_stream(ai_handle network, void* stream) {

@@ -1,14 +1,16 @@
-// libyf_images.so: decoded images of any size -> the network's int8 frames, resized exactly as cv2.resize(img, (out, out)) (INTER_LINEAR,
-// the arithmetic of yf_images_taps.h), and on through libyf_network.so's public C-ABI to detection records in each image's own pixels.
+// libyf_images.so: decoded images of any size -> the network's int8 frames (fp16 frames for the fp16 network), resized exactly as
+// cv2.resize(img, (out, out)) (INTER_LINEAR, the arithmetic of yf_images_taps.h), and on through libyf_network.so's public C-ABI to
+// detection records in each image's own pixels.
 // C-ABI and semantics: include/yf_images.h.
 //
 // Prepare kernel: one 256-thread workgroup per frame (grid-striding over the batch).  Lanes build the out_hw x-taps and y-taps in LDS, then
 // each lane computes whole output pixels: four byte-wide reads per channel (two source rows, two columns), horizontal then vertical pass,
-// the -128 and the channel order fused; lanes of a wave take consecutive output columns, so the reads of a sampled source row coalesce.
+// the -128 (or, for fp16 frames, the look-up of the half of pixel / 255. in a 256-entry LDS table) and the channel order fused; lanes of a
+// wave take consecutive output columns, so the reads of a sampled source row coalesce.
 // The frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses
 // inside the image's extent: no load reaches past its last pixel.
-// The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame) and nms_kernel (up to 256 records, one
-// wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h.
+// The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame), decode_f32_kernel (the fp16 network's
+// float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -23,6 +25,7 @@
 #include "yf_decode.hip.h"
 #include "gen/yf_decode_tables_gen.h"
 #include "yf_images_decode160.h"
+#include "yf_images_float.h"
 #include "yf_images_wide.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
@@ -42,22 +45,27 @@ struct PrepArgs {
   int h, w;                    // uniform
   int64_t rs, fs;              // uniform
   long n;
-  int8_t* frames;
+  void* frames;                // int8, or fp16 bits (prepare_f16_kernel)
 };
 
 struct YTap { int64_t o0, o1; int32_t w0, w1; };
 
 template <int OUT> struct Band { static constexpr int ROWS = OUT == 56 ? 56 : 20; };
 
-template <int OUT, int C, bool BGR, bool RAGGED>
-__global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) {
+// T: the frame's element, int8_t (pixel - 128) or uint16_t (the fp16 bits of pixel / 255.: yfi_f16_of_u8)
+template <int OUT, int C, bool BGR, bool RAGGED, typename T>
+__device__ __forceinline__ void prepare_frames(const PrepArgs& a) {
   constexpr int ROWS = Band<OUT>::ROWS;
-  constexpr int FRAME_BYTES = OUT * OUT * 3;
+  constexpr bool F16 = sizeof(T) == 2;
+  constexpr int FRAME_BYTES = OUT * OUT * 3 * (int)sizeof(T);
+  constexpr int BAND_VECS = ROWS * OUT * 3 * (int)sizeof(T) / 16;
   static_assert((ROWS * OUT * 3) % 16 == 0 && OUT % ROWS == 0, "bands of whole 16-byte vectors");
   __shared__ int4 s_xt[OUT];                       // {s0 * C, s1 * C, w0, w1}
   __shared__ YTap s_yt[OUT];
-  __shared__ int4 s_stage[ROWS * OUT * 3 / 16];
+  __shared__ int4 s_stage[BAND_VECS];
+  __shared__ uint16_t s_half[F16 ? 256 : 1];
   const int tid = threadIdx.x;
+  if constexpr (F16) s_half[tid] = yfi_f16_of_u8(tid);       // kThreads == 256; the barrier at the head of the frame loop publishes it
   for (long f = blockIdx.x; f < a.n; f += gridDim.x) {
     uint64_t off;
     int h, w;
@@ -68,13 +76,14 @@ __global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) {
     } else {
       off = (uint64_t)f * (uint64_t)a.fs; h = a.h; w = a.w; rs = a.rs;
     }
-    int4* out = (int4*)(a.frames + f * FRAME_BYTES);
+    int4* out = (int4*)((char*)a.frames + f * FRAME_BYTES);
     __syncthreads();                               // the previous frame's readers of the tap tables and the stage are done
     if (RAGGED) {
       const bool ok = yfi_image_ok(off, h, w, rs, C, a.bytes);
       if (tid == 0) a.status[f] = ok ? 0 : 1;
-      if (!ok) {                                   // never read: the frame is all -128
-        const int4 fill = make_int4((int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080);
+      if (!ok) {                                   // never read: the frame is all -128 (fp16: all 0, pixel 0)
+        const int v = F16 ? 0 : (int)0x80808080;
+        const int4 fill = make_int4(v, v, v, v);
         for (int q = tid; q < FRAME_BYTES / 16; q += kThreads) out[q] = fill;
         continue;
       }
@@ -90,7 +99,7 @@ __global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) {
     }
     __syncthreads();
     const uint8_t* base = a.px + off;
-    int8_t* stage = (int8_t*)s_stage;
+    T* stage = (T*)s_stage;
     for (int r0 = 0; r0 < OUT; r0 += ROWS) {
       for (int p = tid; p < ROWS * OUT; p += kThreads) {
         const int yy = p / OUT, xx = p - yy * OUT;
@@ -103,16 +112,25 @@ __global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) {
           const int sc = BGR ? 2 - c : c;
           const int32_t h0 = yfi_hpass(ra[tx.x + sc], ra[tx.y + sc], tx.z, tx.w);
           const int32_t h1 = yfi_hpass(rb[tx.x + sc], rb[tx.y + sc], tx.z, tx.w);
-          stage[p * 3 + c] = (int8_t)(yfi_vpass(h0, h1, ty.w0, ty.w1) - 128);
+          const int32_t v = yfi_vpass(h0, h1, ty.w0, ty.w1);
+          if constexpr (F16) stage[p * 3 + c] = s_half[v];
+          else stage[p * 3 + c] = (int8_t)(v - 128);
         }
       }
       __syncthreads();
-      int4* dst = out + r0 * OUT * 3 / 16;
-      for (int q = tid; q < ROWS * OUT * 3 / 16; q += kThreads) dst[q] = s_stage[q];
+      int4* dst = out + r0 / ROWS * BAND_VECS;
+      for (int q = tid; q < BAND_VECS; q += kThreads) dst[q] = s_stage[q];
       __syncthreads();
     }
   }
 }
+
+template <int OUT, int C, bool BGR, bool RAGGED>
+__global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) { prepare_frames<OUT, C, BGR, RAGGED, int8_t>(a); }
+
+// fp16 frames [n][56][56][3] for yf_network_fp16_run_device: the fp16 network has no other size
+template <int C, bool BGR, bool RAGGED>
+__global__ void __launch_bounds__(kThreads) prepare_f16_kernel(PrepArgs a) { prepare_frames<56, C, BGR, RAGGED, uint16_t>(a); }
 
 // Per-image-scale decode: one wave per frame, decode_frame of csrc/yf_decode.hip.h unchanged, the scales the script's W/56. and H/56. become
 // on a float32 array.  An image whose descriptor was flagged (status 1) or whose sides are out of range gets count 0.
@@ -130,6 +148,55 @@ __global__ void __launch_bounds__(kThreads) decode_ragged_kernel(const int8_t* _
     }
     const float w_scale = (float)((double)im.width / 56.0), h_scale = (float)((double)im.height / 56.0);
     yfdec::decode_frame(heads + f * kHeadBytes, f, lane, mode, w_scale, h_scale, dets, counts, cap);
+  }
+}
+
+// Decode of the fp16 network's float32 logits [n][7][7][18] (h5_predition.py:51-72, the arithmetic of yf_images_float.h): four frames per
+// workgroup, one wave per frame.  A frame's 882 logits go to LDS with 14 lane-consecutive loads; the 147 candidates are visited in three
+// passes of 64 lanes in the order (anchor, row, col): the confidence of each, a ballot and a prefix count per pass, so a record's slot is
+// the number of firing candidates before it; boxes are assembled only for the candidates that fire and fit below cap, pass by pass.  RAGGED: each
+// image's own scales; status 1 or a side out of range gives count 0.  Every wave of a workgroup makes the same number of trips (the
+// barriers), a wave without a frame idles through them.
+template <bool RAGGED>
+__global__ void __launch_bounds__(kThreads) decode_f32_kernel(const float* __restrict__ logits, const yf_image* __restrict__ imgs,
+                                                              const int32_t* __restrict__ status, long n, float w_scale, float h_scale,
+                                                              yf_det* __restrict__ dets, int* __restrict__ counts, int cap) {
+  __shared__ float s_t[4][YFI_F32_LOGITS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  float* t = s_t[wave];
+  for (long g = blockIdx.x; g * 4 < n; g += gridDim.x) {
+    const long f = g * 4 + wave;
+    bool ok = f < n;
+    float ws = w_scale, hs = h_scale;
+    if (RAGGED && ok) {
+      const yf_image im = imgs[f];
+      ok = im.height >= 1 && im.height <= YF_IMAGES_MAX_SIDE && im.width >= 1 && im.width <= YF_IMAGES_MAX_SIDE &&
+           (status == nullptr || status[f] == 0);
+      if (!ok && lane == 0) counts[f] = 0;
+      ws = (float)((double)im.width / 56.0); hs = (float)((double)im.height / 56.0);
+    }
+    __syncthreads();                               // the previous frames' readers of s_t are done
+    if (ok) {
+      const float* src = logits + f * YFI_F32_LOGITS;
+      for (int q = lane; q < YFI_F32_LOGITS; q += 64) t[q] = src[q];
+    }
+    __syncthreads();
+    if (!ok) continue;
+    yf_det* out = dets + f * cap;
+    int total = 0;
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {                  // one copy of the arithmetic: a pass is complete before the next begins
+      const int i = 64 * c + lane;
+      const float* p = t + yfi_f32_offset(i < YFI_F32_CAND ? i : 0);
+      const float conf = yfi_sigmoid_f32(p[4]);
+      const bool keep = i < YFI_F32_CAND && conf > 0.7f;
+      const uint64_t mask = __ballot(keep);
+      const int pos = total + __popcll(mask & below);
+      total += __popcll(mask);
+      if (keep && pos < cap) out[pos] = yfi_f32_candidate(p, i, (int32_t)f, conf, ws, hs);
+    }
+    if (lane == 0) counts[f] = total;
   }
 }
 
@@ -305,7 +372,7 @@ bool check_uniform(const void* d_pixels, size_t pixels_bytes, int format, int he
       return fail("the last image reaches outside [0, pixels_bytes)");
   }
   *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, nullptr, nullptr, height, width, (int64_t)row_stride, (int64_t)frame_stride,
-                n, (int8_t*)d_frames};
+                n, d_frames};
   return true;
 }
 
@@ -316,7 +383,7 @@ bool check_ragged(const void* d_pixels, size_t pixels_bytes, int format, const y
   if (!check_batch(format, n, out_hw, d_frames)) return false;
   if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0))
     return fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
-  *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, n, (int8_t*)d_frames};
+  *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, n, d_frames};
   return true;
 }
 
@@ -341,6 +408,17 @@ bool check_decode160(const void* d_heads, void* d_dets, void* d_counts, int cap)
   if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
   if (((uintptr_t)d_counts & 3) != 0) return fail("d_counts is not 4-byte aligned");
   if (cap <= 0 || cap > YF_IMAGES_CAND160) return fail("cap must be in [1, 1200]");
+  return true;
+}
+
+bool check_decode_f32(const void* d_logits, void* d_dets, void* d_counts, int cap) {
+  if (!d_logits) return fail("d_logits is NULL");
+  if (((uintptr_t)d_logits & 3) != 0) return fail("d_logits is not 4-byte aligned");
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0) return fail("d_counts is not 4-byte aligned");
+  if (cap <= 0 || cap > YFI_F32_CAND) return fail("cap must be in [1, 147]");
   return true;
 }
 
@@ -371,6 +449,31 @@ long prepare(int out_hw, int format, const PrepArgs& a, hipStream_t s) {
   const PrepKernel* k = out_hw == 56 ? (a.imgs ? kPrepare<56, true> : kPrepare<56, false>) : (a.imgs ? kPrepare<160, true> : kPrepare<160, false>);
   hipLaunchKernelGGL(k[format], grid_for(a.n, 8), dim3(kThreads), 0, s, a);      // LDS per workgroup: 13.6 KB at 56, 14.6 KB at 160
   return launched("prepare kernel launch", a.n);
+}
+
+template <bool RAGGED>
+constexpr PrepKernel kPrepareF16[4] = {prepare_f16_kernel<3, true, RAGGED>, prepare_f16_kernel<3, false, RAGGED>,
+                                       prepare_f16_kernel<4, true, RAGGED>, prepare_f16_kernel<4, false, RAGGED>};
+
+long prepare_f16(int format, const PrepArgs& a, hipStream_t s) {
+  if (a.n == 0) return 0;
+  const PrepKernel* k = a.imgs ? kPrepareF16<true> : kPrepareF16<false>;
+  hipLaunchKernelGGL(k[format], grid_for(a.n, 6), dim3(kThreads), 0, s, a);      // LDS per workgroup: 23.5 KB
+  return launched("prepare_f16 kernel launch", a.n);
+}
+
+// d_images == nullptr: the scalar scales; else per-image scales (and d_status, which may be nullptr)
+long decode_f32(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n, float w_scale, float h_scale, void* d_dets,
+                void* d_counts, int cap, hipStream_t s) {
+  if (n == 0) return 0;
+  const dim3 grid = grid_for((n + 3) / 4, 8);                                     // 13.8 KB of LDS per workgroup
+  if (d_images)
+    hipLaunchKernelGGL(decode_f32_kernel<true>, grid, dim3(kThreads), 0, s, (const float*)d_logits, d_images, d_status, n, 0.f, 0.f,
+                       (yf_det*)d_dets, (int*)d_counts, cap);
+  else
+    hipLaunchKernelGGL(decode_f32_kernel<false>, grid, dim3(kThreads), 0, s, (const float*)d_logits, (const yf_image*)nullptr,
+                       (const int32_t*)nullptr, n, w_scale, h_scale, (yf_det*)d_dets, (int*)d_counts, cap);
+  return launched("decode_f32 kernel launch", n);
 }
 
 // The decode tables (2 KB of __constant__ in this library's code object), uploaded once per device on first use.
@@ -447,6 +550,18 @@ long run_decode160(ai_handle net, int format, const PrepArgs& a, void* d_heads, 
   if (yf_network_run_device_hw(net, 160, 160, a.frames, d_heads, a.n, stream) != a.n) return network_failed(net, "yf_network_run_device_hw");
   const float w_scale = (float)((double)a.w / 160.0), h_scale = (float)((double)a.h / 160.0);
   return decode160(d_heads, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+// fp16 network: images -> fp16 frames -> float32 logits -> records; the scalar scales count in a uniform batch only.  Nothing is launched
+// on a network without yf_network_fp16_init
+long run_decode_f16(ai_handle net, int format, const PrepArgs& a, void* d_logits, void* d_dets, void* d_counts, int cap, void* stream) {
+  if (!check_decode_f32(d_logits, d_dets, d_counts, cap)) return 0;
+  if (!yf_network_fp16_ready(net)) return network_failed(net, "yf_network_fp16_ready");
+  if (a.n == 0) return 0;
+  if (prepare_f16(format, a, (hipStream_t)stream) != a.n) return 0;
+  if (yf_network_fp16_run_device(net, a.frames, d_logits, a.n, stream) != a.n) return network_failed(net, "yf_network_fp16_run_device");
+  const float w_scale = (float)((double)a.w / 56.0), h_scale = (float)((double)a.h / 56.0);
+  return decode_f32(d_logits, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -526,6 +641,53 @@ YF_API long yf_images_run_decode160_ragged_device(ai_handle net, const void* d_p
   if (!net) return fail("network handle is NULL");
   if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 160, d_frames, d_status, &a)) return 0;
   return run_decode160(net, format, a, d_heads, d_dets, d_counts, cap, stream);
+}
+
+YF_API long yf_images_prepare_f16_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long row_stride,
+                                         long frame_stride, long n, void* d_frames_f16, void* stream) {
+  PrepArgs a;
+  if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 56, d_frames_f16, &a)) return 0;
+  return prepare_f16(format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                void* d_frames_f16, int32_t* d_status, void* stream) {
+  PrepArgs a;
+  if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 56, d_frames_f16, d_status, &a)) return 0;
+  return prepare_f16(format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode_f32_device(const void* d_logits, long n, float w_scale, float h_scale, void* d_dets, void* d_counts, int cap,
+                                        void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (!check_decode_f32(d_logits, d_dets, d_counts, cap)) return 0;
+  return decode_f32(d_logits, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode_f32_ragged_device(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n, void* d_dets,
+                                               void* d_counts, int cap, void* stream) {
+  if (n < 0) return fail("n < 0");
+  if (!check_decode_f32(d_logits, d_dets, d_counts, cap) || !check_descriptors(d_images, n)) return 0;
+  if (((uintptr_t)d_status & 3) != 0) return fail("d_status is not 4-byte aligned");
+  return decode_f32(d_logits, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_run_decode_f16_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,
+                                            long row_stride, long frame_stride, long n, void* d_frames_f16, void* d_logits, void* d_dets,
+                                            void* d_counts, int cap, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_uniform(d_pixels, pixels_bytes, format, height, width, row_stride, frame_stride, n, 56, d_frames_f16, &a)) return 0;
+  return run_decode_f16(net, format, a, d_logits, d_dets, d_counts, cap, stream);
+}
+
+YF_API long yf_images_run_decode_f16_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                   const yf_image* d_images, long n, void* d_frames_f16, void* d_logits, void* d_dets,
+                                                   void* d_counts, int cap, int32_t* d_status, void* stream) {
+  PrepArgs a;
+  if (!net) return fail("network handle is NULL");
+  if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, 56, d_frames_f16, d_status, &a)) return 0;
+  return run_decode_f16(net, format, a, d_logits, d_dets, d_counts, cap, stream);
 }
 
 YF_API long yf_images_nms_device(const void* d_dets, const void* d_counts, long n, int cap, double iou_threshold, void* d_out,

@@ -51,25 +51,30 @@ YFI_HD int yfi_d160_monotonic(const uint32_t* sig_bits) {
   return 1;
 }
 
-/* One record from candidate i (p = its six head bytes) of frame `frame`; sig_bits, exp_bits: the two 256-entry tables. */
-YFI_HD yf_det yfi_d160_candidate(const int8_t* p, int i, int32_t frame, const uint32_t* sig_bits, const uint32_t* exp_bits,
-                                 float w_scale, float h_scale) {
+/* The tail every YF_DECODE_PY-style decode shares, from the four transcendental values on: centre, size, edges, scales, float32 -> int32
+ * into d's x1, y1, x2, y2.  sx, sy: the sigmoids of the x and y logits; ew, eh: the exponentials of the w and h logits. */
+YFI_HD void yfi_d160_box(float sx, float sy, float ew, float eh, int a, int row, int col, float w_scale, float h_scale, yf_det* d) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
-  const int a = i / YFI_D160_CELLS, cell = i - a * YFI_D160_CELLS;
-  const int row = cell / YF_IMAGES_GRID160, col = cell - row * YF_IMAGES_GRID160;
   const float anc_w = a == 0 ? 9.f : (a == 1 ? 12.f : 22.f), anc_h = a == 0 ? 14.f : (a == 1 ? 17.f : 21.f);
-  const float sx = yfi_d160_bits(sig_bits[p[0] + 128]), sy = yfi_d160_bits(sig_bits[p[1] + 128]);
-  const float ew = yfi_d160_bits(exp_bits[p[2] + 128]), eh = yfi_d160_bits(exp_bits[p[3] + 128]);
   const float cx = (sx + (float)col) * 8.f, cy = (sy + (float)row) * 8.f;
   const float bw = ew * anc_w, bh = eh * anc_h;
   float x1 = cx - bw / 2, y1 = cy - bh / 2, x2 = cx + bw / 2, y2 = cy + bh / 2;
   x1 *= w_scale; x2 *= w_scale; y1 *= h_scale; y2 *= h_scale;
+  d->x1 = yfi_d160_f2i(x1); d->y1 = yfi_d160_f2i(y1); d->x2 = yfi_d160_f2i(x2); d->y2 = yfi_d160_f2i(y2);
+}
+
+/* One record from candidate i (p = its six head bytes) of frame `frame`; sig_bits, exp_bits: the two 256-entry tables. */
+YFI_HD yf_det yfi_d160_candidate(const int8_t* p, int i, int32_t frame, const uint32_t* sig_bits, const uint32_t* exp_bits,
+                                 float w_scale, float h_scale) {
+  const int a = i / YFI_D160_CELLS, cell = i - a * YFI_D160_CELLS;
+  const int row = cell / YF_IMAGES_GRID160, col = cell - row * YF_IMAGES_GRID160;
   yf_det d;
   d.frame = frame; d.anchor = (uint8_t)a; d.row = (uint8_t)row; d.col = (uint8_t)col;
   d.q_conf = p[4]; d.conf = yfi_d160_bits(sig_bits[p[4] + 128]);
-  d.x1 = yfi_d160_f2i(x1); d.y1 = yfi_d160_f2i(y1); d.x2 = yfi_d160_f2i(x2); d.y2 = yfi_d160_f2i(y2);
+  yfi_d160_box(yfi_d160_bits(sig_bits[p[0] + 128]), yfi_d160_bits(sig_bits[p[1] + 128]), yfi_d160_bits(exp_bits[p[2] + 128]),
+               yfi_d160_bits(exp_bits[p[3] + 128]), a, row, col, w_scale, h_scale, &d);
   return d;
 }
 

@@ -1,10 +1,12 @@
-/* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h and the 20x20 decode arithmetic in
- * yf_images_decode160.h (the functions the device kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
+/* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
+ * yf_images_decode160.h and the fp16 frames and float32 decode of yf_images_float.h (the functions the device kernels call), for the CPU
+ * tests only: libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
 #include "yf_images_taps.h"
 #include "yf_images_nms.h"
 #include "yf_images_decode160.h"
+#include "yf_images_float.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -70,4 +72,31 @@ EXPORT int yfi_decode160_q_threshold_host(void) { return yfi_d160_monotonic(yf_s
 
 EXPORT int yfi_image_ok_host(uint64_t offset, int64_t h, int64_t w, int64_t rs, int C, uint64_t bytes) {
   return yfi_image_ok(offset, h, w, rs, C, bytes);
+}
+
+/* ---- yf_images_float.h ----  the 256 halves of v / 255. */
+EXPORT void yfi_f16_of_u8_host(uint16_t* out) {
+  for (int v = 0; v < 256; ++v) out[v] = yfi_f16_of_u8(v);
+}
+
+EXPORT void yfi_exp_f32_host(const float* x, long n, float* out) {
+  for (long k = 0; k < n; ++k) out[k] = yfi_exp_f32(x[k]);
+}
+
+EXPORT void yfi_sigmoid_f32_host(const float* x, long n, float* out) {
+  for (long k = 0; k < n; ++k) out[k] = yfi_sigmoid_f32(x[k]);
+}
+
+/* The decode of one frame's float32 logits [7][7][18] as decode_f32_kernel computes it: candidates in the order (anchor, row, col), the
+ * confidence of each, the record of yf_images_float.h for those that fire, the first `cap` written.  Returns the true count. */
+EXPORT int yfi_decode_f32_host(const float* logits, int32_t frame, float w_scale, float h_scale, yf_det* dets, int cap) {
+  int n = 0;
+  for (int i = 0; i < YFI_F32_CAND; ++i) {
+    const float* p = logits + yfi_f32_offset(i);
+    const float conf = yfi_sigmoid_f32(p[4]);
+    if (!(conf > 0.7f)) continue;
+    if (n < cap) dets[n] = yfi_f32_candidate(p, i, frame, conf, w_scale, h_scale);
+    ++n;
+  }
+  return n;
 }

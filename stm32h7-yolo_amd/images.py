@@ -5,7 +5,9 @@ imgproc/resize.cpp that has not been pinned against a real cv2 -- and on through
 `detect(network, images)` is lines 29-61 of the reference's yoloface/tflite/tflite_prediction.py for a whole batch: imread (BGR), BGR -> RGB,
 cv2.resize to 56x56, minus 128, int8, the network, decode, boxes scaled by W/56. and H/56.  With `iou_threshold` it adds the greedy IoU
 suppression of yoloface/tensorflow/yoloface_test.py:145-190 on the GPU (`nms_device`, include/yf_images.h).  `size=160` runs the same path
-on 160x160 frames (20x20 heads, 1200 candidates per image: `run_decode160_ragged_device`, `nms_wide_device`).
+on 160x160 frames (20x20 heads, 1200 candidates per image: `run_decode160_ragged_device`, `nms_wide_device`).  `dtype="fp16"` runs the fp16
+network instead, as the reference's float caller yoloface/tensorflow/h5_predition.py:29-73 does: fp16 frames of pixel / 255., float32 logits,
+the decode in float32 (`run_decode_f16_ragged_device`; the arithmetic: csrc/yf_images_float.h).
 """
 import ctypes
 import hashlib
@@ -89,6 +91,12 @@ def _entries():
         "run_decode160_device": [vp] + uniform + [vp, vp, vp, vp, ci, vp],
         "run_decode160_ragged_device": [vp] + ragged + [vp, vp, vp, vp, ci, vp, vp],
         "nms_wide_device": nms,
+        "prepare_f16_device": uniform + [vp, vp],
+        "prepare_f16_ragged_device": ragged + [vp, vp, vp],
+        "decode_f32_device": [vp, cl, cf, cf, vp, vp, ci, vp],
+        "decode_f32_ragged_device": [vp, vp, vp, cl, vp, vp, ci, vp],
+        "run_decode_f16_device": [vp] + uniform + [vp, vp, vp, vp, ci, vp],
+        "run_decode_f16_ragged_device": [vp] + ragged + [vp, vp, vp, vp, ci, vp, vp],
     }
 
 
@@ -249,15 +257,53 @@ def nms_wide_device(d_dets, d_counts, n, cap, iou_threshold, d_out=None, d_out_c
     _nms("nms_wide_device", d_dets, d_counts, n, cap, iou_threshold, d_out, d_out_counts, stream)
 
 
-def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56):
+def prepare_f16_device(d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames_f16, stream=None):
+    """Images -> the fp16 network's frames (yf_images_prepare_f16_device): d_frames_f16 fp16 [n][56][56][3], pixel / 255. in RGB order."""
+    _call("prepare_f16_device", n, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n, d_frames_f16, stream)
+
+
+def prepare_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, stream=None):
+    _call("prepare_f16_ragged_device", n, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames_f16, d_status, stream)
+
+
+def decode_f32_device(d_logits, n, d_dets, d_counts, cap, w_scale=1.0, h_scale=1.0, stream=None):
+    """Decode of the fp16 network's logits (yf_images_decode_f32_device): d_logits float32 [n][7][7][18] -> d_dets yf_det[n][cap],
+    d_counts int32[n]; h5_predition.py:51-72 in float32 (csrc/yf_images_float.h)."""
+    _call("decode_f32_device", n, d_logits, n, w_scale, h_scale, d_dets, d_counts, cap, stream)
+
+
+def decode_f32_ragged_device(d_logits, d_images, n, d_dets, d_counts, cap, d_status=None, stream=None):
+    _call("decode_f32_ragged_device", n, d_logits, d_images, d_status, n, d_dets, d_counts, cap, stream)
+
+
+def run_decode_f16_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames_f16, d_logits, d_dets,
+                          d_counts, cap, stream=None):
+    _call("run_decode_f16_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), height, width, row_stride, frame_stride, n,
+          d_frames_f16, d_logits, d_dets, d_counts, cap, stream)
+
+
+def run_decode_f16_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_logits, d_dets, d_counts, cap, d_status,
+                                 stream=None):
+    _call("run_decode_f16_ragged_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames_f16, d_logits,
+          d_dets, d_counts, cap, d_status, stream)
+
+
+def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8"):
     """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
     tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
     of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network.  iou_threshold=None returns every record above the
     confidence threshold in decode order; a float (yoloface_test.py uses 0.4) suppresses them in place on the same stream (nms_device) and
     returns the kept boxes in keep order, highest confidence first.  size: the side of the network's frames, 56 (7x7 heads) or 160 (20x20
-    heads, which find smaller faces; suppression through nms_wide_device); cap=None holds every candidate: 147 / 1200."""
+    heads, which find smaller faces; suppression through nms_wide_device); cap=None holds every candidate: 147 / 1200.
+    dtype: "int8" (the quantised network) or "fp16" -- the fp16 network, which makes this h5_predition.py:29-73 for the batch: fp16 frames
+    of pixel / 255., float32 logits, the float32 decode (`run_decode_f16_ragged_device`).  Call `network.fp16_init()` first, as for
+    `fp16_run_device`: detect does not do it.  The fp16 network exists at 56 only."""
     if size not in (56, 160):
         raise ValueError(f"size {size!r}: 56 or 160")
+    if dtype not in ("int8", "fp16"):
+        raise ValueError(f"dtype {dtype!r}: 'int8' or 'fp16'")
+    if dtype == "fp16" and size != 56:
+        raise ValueError("dtype 'fp16': the fp16 network has 56x56 frames only")
     grid = size // 8
     if cap is None:
         cap = 3 * grid * grid
@@ -269,13 +315,16 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     buf, desc = pack_images(images, fmt)
     d_px = torch.from_numpy(buf).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
-    d_frames = torch.empty((n, size, size, 3), dtype=torch.int8, device=dev)
-    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.int8, device=dev)
+    f16 = dtype == "fp16"
+    d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
+    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
     d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     d_counts = torch.empty(n, dtype=torch.int32, device=dev)
     d_status = torch.empty(n, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
     run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
+    if f16:
+        run = run_decode_f16_ragged_device
     run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
         d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
     if iou_threshold is not None:
