@@ -24,7 +24,8 @@ int  yf_engine_set_tables(yf_engine* e, const uint8_t* table_blob, const yf_tabl
 /* 1 if a production kernel of that shape is compiled in (frames_per_wg may carry the +200 experimental-build tag) */
 int  yf_engine_variant_exists(int frames_per_wg, int waves_per_wg);
 int  yf_engine_configure(yf_engine* e, int frames_per_wg, int waves_per_wg);
-/* byte offsets compiled into the kernels: w_off[17], c_off[17] (dense stages), g_off[7] (depthwise), lut_off, total = 43 ints */
+/* byte offsets compiled into the kernels: w_off[17], c_off[17] (dense stages), g_off[7] (depthwise), lut_off, total,
+ * then vb_off[24], vb_bytes[24], sb_off[24] (the per-stage constant blocks, YF_N_CS) = 2*17 + 7 + 2 + 3*24 = 115 ints; returns that count */
 int  yf_engine_table_plan(int32_t* out, int cap);
 const char* yf_engine_error(const yf_engine* e);
 const char* yf_engine_kernel_name(const yf_engine* e);

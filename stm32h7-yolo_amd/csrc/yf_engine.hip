@@ -12,70 +12,28 @@
 #include "yf_engine.h"
 #include "yf_stream_scratch.h"
 #include "yf_decode.hip.h"
-#define YF_NS yf
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_STAGE_FN
-#undef YF_H0
-// 160x160 (BASELINE configs[4]): the same stage code on band-local buffers (three banded kernels; YF_LAB: also layer by layer over an HBM arena)
-#define YF_NS yf160
-#define YF_H0 160
-#define YF_GENERIC 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_H0
-#undef YF_GENERIC
-// The same kernels once more with the SIGN-FREE three-instruction epilogue on their dense convolutions (yf_kernels.hip.h, rq4 SIGNLESS): what runs when the network's
-// requantisation rounding has no sign term (yf_network_set_requant_rounding: ties upward / single rounding; the host then folds ZR into C64 for the dense stages).
-// Namespaces yfu (56x56) and yf160u (160x160).  The kernels of yf / yf160 above -- the reference rounding's -- are untouched by this.
-#undef YF_STAGE_FN
-#define YF_NS yfu
+// The int8 kernels, one kernel set (yf_kernel_set.hip.h: namespaces yf<set> for 56x56 and yf160<set> for 160x160) per requantisation arithmetic:
+#define YF_SET                      /* yf / yf160: the reference rounding's four-instruction epilogue */
+#include "yf_kernel_set.hip.h"
+// ... with the SIGN-FREE three-instruction epilogue on their dense convolutions (yf_kernels.hip.h, rq4 SIGNLESS): what runs when the network's requantisation
+// rounding has no sign term (yf_network_set_requant_rounding: ties upward / single rounding; the host then folds ZR into C64 for the dense stages)
+#define YF_SET u
 #define YF_RQ3_DENSE 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_STAGE_FN
-#undef YF_H0
-#define YF_NS yf160u
-#define YF_H0 160
-#define YF_GENERIC 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_H0
-#undef YF_GENERIC
-#undef YF_RQ3_DENSE
-// ... and a third time with the FLOAT32 requantisation on every convolution, dense and depthwise (yf_kernels.hip.h, rqf): YF_ROUND_FP32, the XNNPACK delegate's
-// arithmetic.  The MFMAs start from the channels' bias' and the epilogue is five VALU instructions.  Namespaces yfx (56x56) and yf160x (160x160).
-#undef YF_STAGE_FN
-#define YF_NS yfx
+#include "yf_kernel_set.hip.h"
+// ... and with the FLOAT32 requantisation on every convolution, dense and depthwise (yf_kernels.hip.h, rqf): YF_ROUND_FP32, the XNNPACK delegate's
+// arithmetic.  The MFMAs start from the channels' bias' and the epilogue is five VALU instructions.
+#define YF_SET x
 #define YF_RQ_FP32 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_STAGE_FN
-#undef YF_H0
-#define YF_NS yf160x
-#define YF_H0 160
-#define YF_GENERIC 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_H0
-#undef YF_GENERIC
-#undef YF_RQ_FP32
+#include "yf_kernel_set.hip.h"
 #ifdef YF_LAB
-// laboratory: the 56x56 kernel once more, as a dump build that keeps the PRODUCTION stage order (yf_fused56.hip.h, YF_PDUMP) -- per-stage parity of what ships
-#undef YF_STAGE_FN
-#define YF_NS yfpd
+// laboratory: the dump builds in the production stage order of the first two sets, yfpd and yfpdu
 #define YF_DUMP_PROD_ORDER 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_H0
-#undef YF_STAGE_FN
-#define YF_NS yfpdu                 /* ... and of the kernel set with the sign-free dense epilogue */
+#define YF_SET
+#include "yf_kernel_set.hip.h"
+#define YF_SET u
 #define YF_RQ3_DENSE 1
-#include "yf_kernels.hip.h"
-#undef YF_NS
-#undef YF_RQ3_DENSE
+#include "yf_kernel_set.hip.h"
 #undef YF_DUMP_PROD_ORDER
-#undef YF_H0
 #endif
 #include "gen/yf_decode_tables_gen.h"
 
@@ -161,37 +119,31 @@ __global__ void __launch_bounds__(256) prepare_rgb565_kernel(const uint8_t* __re
 }
 
 typedef void (*fused_fn)(const yf::NetParams);
-struct Variant { int f, nw; bool dump; bool cam; fused_fn fn; size_t lds; size_t park; const char* name; bool prod_order; int kset; };
-// park: scratch bytes per frame slot of a workgroup; prod_order: the laboratory's dump build in the production stage order; kset: the kernel set
-// (yf_rounding_kernel_set): 0 namespace yf (reference rounding's epilogue), 1 yfu (sign-free dense epilogue), 2 yfx (float32 requantisation)
+enum Build { RUN, DUMP, DUMP_PROD_ORDER, CAMERA };   // the per-stage dump / stop_stage build, the laboratory's dump build in the production stage order, RGB565 camera input
+struct Variant { int f, nw, kset; Build build; fused_fn fn; size_t lds; size_t park; const char* name; };
+// park: scratch bytes per frame slot of a workgroup; kset: the kernel set (yf_rounding_kernel_set): 0 namespace yf (reference rounding's epilogue),
+// 1 yfu (sign-free dense epilogue), 2 yfx (float32 requantisation)
 
-#define YF_VARIANT(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yf::yoloface56_fused<F, NW, DUMP>, yf::lds_bytes<F, NW, DUMP>(), yf::scratch_bytes_per_frame_slot<DUMP>(), \
-                                  "yoloface56_fused<F=" #F ",NW=" #NW ">" }
-#define YF_VARIANT_CAM(F, NW) { F, NW, false, true, (fused_fn)yf::yoloface56_fused<F, NW, false, true>, yf::lds_bytes<F, NW, false>(), \
-                                yf::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input>" }
-// The product: the batched shape <2,8>, the one-frame-per-workgroup shape <1,8> for small batches, the camera-input form of <2,8> and ONE debug
-// (per-stage dump / stop_stage) build for the per-node observer.  A -DYF_LAB build (make lab) adds the other shapes for tools and tests.
-#define YF_VARIANT_U(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yfu::yoloface56_fused<F, NW, DUMP>, yfu::lds_bytes<F, NW, DUMP>(), yfu::scratch_bytes_per_frame_slot<DUMP>(), \
-                                    "yoloface56_fused<F=" #F ",NW=" #NW ",sign-free dense epilogue>", false, 1 }
-#define YF_VARIANT_U_CAM(F, NW) { F, NW, false, true, (fused_fn)yfu::yoloface56_fused<F, NW, false, true>, yfu::lds_bytes<F, NW, false>(), \
-                                  yfu::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input,sign-free dense epilogue>", false, 1 }
-#define YF_VARIANT_X(F, NW, DUMP) { F, NW, DUMP, false, (fused_fn)yfx::yoloface56_fused<F, NW, DUMP>, yfx::lds_bytes<F, NW, DUMP>(), yfx::scratch_bytes_per_frame_slot<DUMP>(), \
-                                    "yoloface56_fused<F=" #F ",NW=" #NW ",fp32 requantisation>", false, 2 }
-#define YF_VARIANT_X_CAM(F, NW) { F, NW, false, true, (fused_fn)yfx::yoloface56_fused<F, NW, false, true>, yfx::lds_bytes<F, NW, false>(), \
-                                  yfx::scratch_bytes_per_frame_slot<false>(), "yoloface56_fused<F=" #F ",NW=" #NW ",RGB565 input,fp32 requantisation>", false, 2 }
+// The kernel sets, each stated once: X(namespace suffix, kset, label in a fused kernel's name, label in a band kernel's name).  In kset order.
+#define YF_KERNEL_SETS(X) \
+  X( , 0, "", "") \
+  X(u, 1, ",sign-free dense epilogue", " (sign-free dense epilogue)") \
+  X(x, 2, ",fp32 requantisation", " (fp32 requantisation)")
+#define YF_VARIANT(NS, KSET, F, NW, BUILD, TAG) { F, NW, KSET, BUILD, (fused_fn)NS::yoloface56_fused<F, NW, BUILD == DUMP || BUILD == DUMP_PROD_ORDER, BUILD == CAMERA>, \
+    NS::lds_bytes<F, NW, BUILD == DUMP || BUILD == DUMP_PROD_ORDER>(), NS::scratch_bytes_per_frame_slot<BUILD == DUMP || BUILD == DUMP_PROD_ORDER>(), \
+    "yoloface56_fused<F=" #F ",NW=" #NW TAG ">" },
+// The product, per kernel set: the batched shape <2,8>, the one-frame-per-workgroup shape <1,8> for small batches, ONE debug (per-stage dump / stop_stage)
+// build for the per-node observer and the camera-input form of <2,8>.  A -DYF_LAB build (make lab) adds the other shapes for tools and tests.
+#define YF_PRODUCT_VARIANTS(S, KSET, LABEL, BAND_LABEL) \
+  YF_VARIANT(yf##S, KSET, 2, 8, RUN, LABEL) YF_VARIANT(yf##S, KSET, 1, 8, RUN, LABEL) YF_VARIANT(yf##S, KSET, 2, 8, DUMP, LABEL) \
+  YF_VARIANT(yf##S, KSET, 2, 8, CAMERA, ",RGB565 input" LABEL)
 const Variant k_variants[] = {
-  YF_VARIANT(2, 8, false), YF_VARIANT(1, 8, false), YF_VARIANT(2, 8, true), YF_VARIANT_CAM(2, 8),
-  // ... and the same four with the three-instruction epilogue on the dense convolutions, for the roundings without a sign term
-  YF_VARIANT_U(2, 8, false), YF_VARIANT_U(1, 8, false), YF_VARIANT_U(2, 8, true), YF_VARIANT_U_CAM(2, 8),
-  // ... and with the float32 requantisation on every convolution (YF_ROUND_FP32)
-  YF_VARIANT_X(2, 8, false), YF_VARIANT_X(1, 8, false), YF_VARIANT_X(2, 8, true), YF_VARIANT_X_CAM(2, 8),
+  YF_KERNEL_SETS(YF_PRODUCT_VARIANTS)
 #ifdef YF_LAB
-  YF_VARIANT(1, 4, false), YF_VARIANT(2, 4, false), YF_VARIANT(4, 8, false), YF_VARIANT(2, 4, true),
+  YF_VARIANT(yf, 0, 1, 4, RUN, "") YF_VARIANT(yf, 0, 2, 4, RUN, "") YF_VARIANT(yf, 0, 4, 8, RUN, "") YF_VARIANT(yf, 0, 2, 4, DUMP, "")
   // the dump build in the production stage order (same NetParams layout; selected by YF_LAB_DUMP_PROD_ORDER=1 as the engine's dump variant)
-  { 2, 8, true, false, (fused_fn)yfpd::yoloface56_fused<2, 8, true>, yfpd::lds_bytes<2, 8, true>(), yfpd::scratch_bytes_per_frame_slot<true>(),
-    "yoloface56_fused<F=2,NW=8,dump in production order>", true },
-  { 2, 8, true, false, (fused_fn)yfpdu::yoloface56_fused<2, 8, true>, yfpdu::lds_bytes<2, 8, true>(), yfpdu::scratch_bytes_per_frame_slot<true>(),
-    "yoloface56_fused<F=2,NW=8,dump in production order,sign-free dense epilogue>", true, 1 },
+  YF_VARIANT(yfpd, 0, 2, 8, DUMP_PROD_ORDER, ",dump in production order")
+  YF_VARIANT(yfpdu, 1, 2, 8, DUMP_PROD_ORDER, ",dump in production order,sign-free dense epilogue")
 #endif
 };
 
@@ -289,8 +241,8 @@ struct Downloader {
     (e_)->err = std::string(#call) + ": " + hipGetErrorString(rc_); return YF_ENG_ERR_HIP; } } while (0)
 
 static const Variant* shape_for(const yf_engine* e, long n);
-static const Variant* find_variant(int f, int nw, bool dump, bool cam = false, bool prod_order = false, int kset = 0) {
-  for (const Variant& v : k_variants) if (v.f == f && v.nw == nw && v.dump == dump && v.cam == cam && v.prod_order == prod_order && v.kset == kset) return &v;
+static const Variant* find_variant(int f, int nw, int kset, Build build) {
+  for (const Variant& v : k_variants) if (v.f == f && v.nw == nw && v.kset == kset && v.build == build) return &v;
   return nullptr;
 }
 
@@ -299,17 +251,17 @@ static const Variant* find_variant(int f, int nw, bool dump, bool cam = false, b
 static const Variant* dump_variant_for(const yf_engine* e, int f, int nw) {
 #ifdef YF_LAB
   if (e->dump_prod_order) {                      // (none of the float32 set: the dump entry points refuse rather than run the staged-order build in its place)
-    const Variant* v = find_variant(f, nw, true, false, true, e->kset);
+    const Variant* v = find_variant(f, nw, e->kset, DUMP_PROD_ORDER);
     if (v || e->kset == 2) return v;
   }
 #endif
-  return find_variant(f, nw, true, false, false, e->kset);
+  return find_variant(f, nw, e->kset, DUMP);
 }
 // the engine's three kernel shapes for a configuration (f, nw; 0 = the automatic choice), in the kernel set its tables are built for
 static void select_variants(yf_engine* e, int f, int nw, bool automatic) {
-  e->var = find_variant(f, nw, false, false, false, e->kset);
+  e->var = find_variant(f, nw, e->kset, RUN);
   e->var_dump = dump_variant_for(e, f, nw);
-  e->var_small = automatic ? find_variant(1, 8, false, false, false, e->kset) : nullptr;
+  e->var_small = automatic ? find_variant(1, 8, e->kset, RUN) : nullptr;
 }
 
 #ifdef YF_LAB
@@ -333,17 +285,11 @@ struct BandKernel { const void* fn; const char* name; unsigned threads; size_t l
 #define YF_K1_NW 8
 #endif
 #define YF_K1_NW_ YF_K1_NW
-static const BandKernel k_band_fused[3][3] = {   // round 3: K2 and K3 fused (three tensors cross HBM instead of five); [1]: the set with the sign-free dense epilogue, [2]: float32 requantisation
-  {{(const void*)yf160::band::band_k1<YF_K1_NW_>, "band_k1", YF_K1_NW_ * 64, (size_t)yf160::band::K1_LDS, yf160::band::K1_BANDS},
-   {(const void*)yf160::band::band_k23<8>, "band_k23", 512, (size_t)yf160::band::K23_LDS, yf160::band::K23_BANDS},
-   {(const void*)yf160::band::band_k4<8>,  "band_k4", 512,  (size_t)yf160::band::K4_LDS, 1}},
-  {{(const void*)yf160u::band::band_k1<YF_K1_NW_>, "band_k1 (sign-free dense epilogue)", YF_K1_NW_ * 64, (size_t)yf160u::band::K1_LDS, yf160u::band::K1_BANDS},
-   {(const void*)yf160u::band::band_k23<8>, "band_k23 (sign-free dense epilogue)", 512, (size_t)yf160u::band::K23_LDS, yf160u::band::K23_BANDS},
-   {(const void*)yf160u::band::band_k4<8>,  "band_k4 (sign-free dense epilogue)", 512,  (size_t)yf160u::band::K4_LDS, 1}},
-  {{(const void*)yf160x::band::band_k1<YF_K1_NW_>, "band_k1 (fp32 requantisation)", YF_K1_NW_ * 64, (size_t)yf160x::band::K1_LDS, yf160x::band::K1_BANDS},
-   {(const void*)yf160x::band::band_k23<8>, "band_k23 (fp32 requantisation)", 512, (size_t)yf160x::band::K23_LDS, yf160x::band::K23_BANDS},
-   {(const void*)yf160x::band::band_k4<8>,  "band_k4 (fp32 requantisation)", 512,  (size_t)yf160x::band::K4_LDS, 1}},
-};
+#define YF_BAND_KERNELS(S, KSET, LABEL, BAND_LABEL) \
+  {{(const void*)yf160##S::band::band_k1<YF_K1_NW_>, "band_k1" BAND_LABEL, YF_K1_NW_ * 64, (size_t)yf160##S::band::K1_LDS, yf160##S::band::K1_BANDS}, \
+   {(const void*)yf160##S::band::band_k23<8>, "band_k23" BAND_LABEL, 512, (size_t)yf160##S::band::K23_LDS, yf160##S::band::K23_BANDS}, \
+   {(const void*)yf160##S::band::band_k4<8>,  "band_k4" BAND_LABEL, 512,  (size_t)yf160##S::band::K4_LDS, 1}},
+static const BandKernel k_band_fused[3][3] = { YF_KERNEL_SETS(YF_BAND_KERNELS) };   // [kset]; round 3: K2 and K3 fused (three tensors cross HBM instead of five)
 static int launch160_banded(yf_engine* e, const yf160::band::Params& prm, hipStream_t s) {
   for (int i = 0; i < 3; ++i) {
     const BandKernel& k = k_band_fused[e->kset][i];
@@ -358,6 +304,7 @@ static int launch160_banded(yf_engine* e, const yf160::band::Params& prm, hipStr
 }
 
 // the kernels address the tables at compiled-in offsets (yf_kernels.hip.h, TablePlan): the blob must be laid out that way
+static const char k_layout_refusal[] = "table blob layout differs from the layout compiled into the kernels";
 static bool layout_is_the_compiled_plan(const yf_table_index* ix) {
   bool same = (int)ix->lut_off == yf::PLAN.lut_off && (int)ix->total_bytes == yf::PLAN.total;
   for (int i = 0; i < YF_N_DENSE; ++i) same = same && (int)ix->dense[i].w_off == yf::PLAN.w_off[i] && (int)ix->dense[i].c_off == yf::PLAN.c_off[i];
@@ -365,6 +312,16 @@ static bool layout_is_the_compiled_plan(const yf_table_index* ix) {
   for (int i = 0; i < YF_N_CS; ++i)
     same = same && (int)ix->cs_v_off[i] == yf::PLAN.vb_off[i] && (int)ix->cs_v_bytes[i] == yf::PLAN.vb_bytes[i] && (int)ix->cs_s_off[i] == yf::PLAN.sb_off[i];
   return same;
+}
+
+// the small kernels (decode, pack, unpack, prepare_rgb565): one launch of `threads` threads in workgroups of 256, none for an empty batch.  Their entry points check the arguments.
+template <typename Kernel, typename... Args>
+static int launch_small(yf_engine* e, Kernel kernel, long threads, void* stream, Args... args) {
+  if (threads == 0) return YF_ENG_OK;
+  HIPCHK(e, hipSetDevice(e->device));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, args...);
+  HIPCHK(e, hipGetLastError());
+  return YF_ENG_OK;
 }
 
 extern "C" {
@@ -391,7 +348,7 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
   e->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;      // 160 KB on gfx950: how many workgroups of a shape a CU holds (grid size, scratch slots)
   for (const Variant& v : k_variants)
     if (e->lds_per_cu < v.lds) return quit("the device reports " + std::to_string(e->lds_per_cu) + " bytes of LDS per CU, " + v.name + " needs " + std::to_string(v.lds), YF_ENG_ERR_NO_DEVICE);
-  if (!layout_is_the_compiled_plan(ix)) return quit("table blob layout differs from the layout compiled into the kernels", YF_ENG_ERR_ARG);
+  if (!layout_is_the_compiled_plan(ix)) return quit(k_layout_refusal, YF_ENG_ERR_ARG);
   if ((rc = hipMalloc((void**)&e->d_tab, ix->total_bytes)) != hipSuccess) return bail(rc, "hipMalloc(tables)");
   if ((rc = hipMemcpy(e->d_tab, table_blob, ix->total_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(rc, "hipMemcpy(tables)");
   for (int i = 1; i < 256; ++i) {           // the fused decode compares quantised confidences (yf_decode_q_threshold): the table must not decrease
@@ -400,36 +357,32 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
   }
   if ((rc = hipMemcpyToSymbol(HIP_SYMBOL(d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) return bail(rc, "hipMemcpyToSymbol(sigmoid)");
   if ((rc = hipMemcpyToSymbol(HIP_SYMBOL(d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) return bail(rc, "hipMemcpyToSymbol(exp)");
-  for (const Variant& v : k_variants) {
-    // The byte LUTs are addressed absolutely (LDS offset LUT_ID*256): the dynamic segment must start at LDS address 0,
-    // i.e. the kernel must not have picked up any static LDS.
+  // The byte LUTs are addressed absolutely (LDS offset LUT_ID*256): the dynamic segment must start at LDS address 0, i.e. the kernel must not have picked up
+  // any static LDS (refusal: the error text if it has).  lds: the dynamic LDS its launches ask for (0: within the default limit, nothing to raise).
+  // wgs_per_cu, if given: receives the resident workgroups of `threads` threads per CU of this device.
+  auto prepare_kernel = [&](const void* fn, const std::string& refusal, size_t lds, unsigned threads = 0, int* wgs_per_cu = nullptr) -> int {
     hipFuncAttributes at;
-    if ((rc = hipFuncGetAttributes(&at, (const void*)v.fn)) != hipSuccess) return bail(rc, "hipFuncGetAttributes");
-    if (at.sharedSizeBytes != 0) return quit(std::string(v.name) + ": kernel has static LDS, absolute LUT addressing is invalid", YF_ENG_ERR_HIP);
-    if ((rc = hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds)) != hipSuccess)
-      return bail(rc, "hipFuncSetAttribute(max dynamic LDS)");
-  }
-#ifdef YF_LAB
-  {
-    hipFuncAttributes at;
-    if ((rc = hipFuncGetAttributes(&at, (const void*)yf160::generic_stage_kernel<1, 8>)) != hipSuccess) return bail(rc, "hipFuncGetAttributes");
-    if (at.sharedSizeBytes != 0) return quit("generic stage kernel has static LDS", YF_ENG_ERR_HIP);
-  }
-  { const char* lw = getenv("YF_160_LAYERWISE"); e->layerwise160 = lw && lw[0] == '1'; }     // the lab library's layer-by-layer form (debugging)
-#endif
-  auto prepare_band = [&](const BandKernel& k, int* wgs_per_cu) -> int {
-    hipFuncAttributes at;
-    if ((rc = hipFuncGetAttributes(&at, k.fn)) != hipSuccess) return bail(rc, "hipFuncGetAttributes");
-    if (at.sharedSizeBytes != 0) return quit(std::string(k.name) + ": kernel has static LDS, absolute LUT addressing is invalid", YF_ENG_ERR_HIP);
-    if ((rc = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds)) != hipSuccess)
-      return bail(rc, "hipFuncSetAttribute(max dynamic LDS)");
+    if ((rc = hipFuncGetAttributes(&at, fn)) != hipSuccess) return bail(rc, "hipFuncGetAttributes");
+    if (at.sharedSizeBytes != 0) return quit(refusal, YF_ENG_ERR_HIP);
+    if (lds && (rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return bail(rc, "hipFuncSetAttribute(max dynamic LDS)");
+    if (!wgs_per_cu) return YF_ENG_OK;
     int occ = 0;
-    if ((rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, (int)k.threads, k.lds)) != hipSuccess) return bail(rc, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+    if ((rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)threads, lds)) != hipSuccess) return bail(rc, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
     *wgs_per_cu = occ > 0 ? occ : 1;                          // a property of THIS engine's device (round 5 wrote it into the process-wide kernel table)
     return YF_ENG_OK;
   };
+  const std::string static_lds = ": kernel has static LDS, absolute LUT addressing is invalid";
+  int r;
+  for (const Variant& v : k_variants) if ((r = prepare_kernel((const void*)v.fn, v.name + static_lds, v.lds)) != YF_ENG_OK) return r;
+#ifdef YF_LAB
+  if ((r = prepare_kernel((const void*)yf160::generic_stage_kernel<1, 8>, "generic stage kernel has static LDS", 0)) != YF_ENG_OK) return r;
+  { const char* lw = getenv("YF_160_LAYERWISE"); e->layerwise160 = lw && lw[0] == '1'; }     // the lab library's layer-by-layer form (debugging)
+#endif
   for (int u = 0; u < 3; ++u)
-    for (int i = 0; i < 3; ++i) { const int r = prepare_band(k_band_fused[u][i], &e->band_wgs_per_cu[u][i]); if (r != YF_ENG_OK) return r; }
+    for (int i = 0; i < 3; ++i) {
+      const BandKernel& k = k_band_fused[u][i];
+      if ((r = prepare_kernel(k.fn, k.name + static_lds, k.lds, k.threads, &e->band_wgs_per_cu[u][i])) != YF_ENG_OK) return r;
+    }
   { const char* ck = getenv("YF_160_CHUNK"); if (ck && atol(ck) > 0) e->chunk160 = atol(ck); }
 #ifdef YF_LAB
   { const char* fl = getenv("YF_LAB_FAIL_LAUNCHES"); if (fl) e->fail_next_launch = atoi(fl); }
@@ -459,8 +412,8 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
 
 int yf_engine_set_tables(yf_engine* e, const uint8_t* table_blob, const yf_table_index* ix, int kernel_set) {
   if (!e || !table_blob || !ix) return YF_ENG_ERR_ARG;
-  if (!find_variant(e->var->f, e->var->nw, false, false, false, kernel_set)) { e->err = "the configured kernel shape has no build for this rounding"; return YF_ENG_ERR_VARIANT; }
-  if (!layout_is_the_compiled_plan(ix)) { e->err = "table blob layout differs from the layout compiled into the kernels"; return YF_ENG_ERR_ARG; }
+  if (!find_variant(e->var->f, e->var->nw, kernel_set, RUN)) { e->err = "the configured kernel shape has no build for this rounding"; return YF_ENG_ERR_VARIANT; }
+  if (!layout_is_the_compiled_plan(ix)) { e->err = k_layout_refusal; return YF_ENG_ERR_ARG; }
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipDeviceSynchronize());             // launches in flight read the old constants to their end
   HIPCHK(e, hipMemcpy(e->d_tab, table_blob, ix->total_bytes, hipMemcpyHostToDevice));
@@ -507,7 +460,7 @@ int yf_engine_table_plan(int32_t* out, int cap) {
   return need;
 }
 
-int yf_engine_variant_exists(int frames_per_wg, int waves_per_wg) { return find_variant(frames_per_wg, waves_per_wg, false) != nullptr; }
+int yf_engine_variant_exists(int frames_per_wg, int waves_per_wg) { return find_variant(frames_per_wg, waves_per_wg, 0, RUN) != nullptr; }
 
 int yf_engine_configure(yf_engine* e, int frames_per_wg, int waves_per_wg) {
   if (!e) return YF_ENG_ERR_ARG;
@@ -516,7 +469,7 @@ int yf_engine_configure(yf_engine* e, int frames_per_wg, int waves_per_wg) {
     return YF_ENG_OK;
   }
   const int f = frames_per_wg > 0 ? frames_per_wg : e->var->f, nw = waves_per_wg > 0 ? waves_per_wg : e->var->nw;
-  if (!find_variant(f, nw, false, false, false, e->kset)) { e->err = "no such kernel variant"; return YF_ENG_ERR_VARIANT; }
+  if (!find_variant(f, nw, e->kset, RUN)) { e->err = "no such kernel variant"; return YF_ENG_ERR_VARIANT; }
   select_variants(e, f, nw, false);              /* an explicitly configured shape runs every batch size; debug build of the SAME shape, or none: the dump / stage-timing
                                                     entry points refuse instead of running another shape */
   return YF_ENG_OK;
@@ -540,6 +493,7 @@ static int yf_decode_q_threshold(int mode) {
   }
   return 128;
 }
+static bool decode_mode_ok(int mode) { return mode == YF_DECODE_PY || mode == YF_DECODE_FW || mode == YF_DECODE_FW_HOST; }
 struct DecodeArgs { void* dets; void* counts; int cap, mode; float w_scale, h_scale; };
 
 // Kernel shape for a batch of n frames: up to SMALL_N frames run one frame per workgroup (every frame on a CU of its own: a 1-frame
@@ -595,7 +549,7 @@ int yf_engine_run_device(yf_engine* e, const void* d_in, void* d_out, void* d_du
 
 int yf_engine_run_decode_device(yf_engine* e, const void* d_in, void* d_out, long n, int mode, float w_scale, float h_scale,
                                 void* d_dets, void* d_counts, int cap, void* stream) {
-  if (!e || !d_in || !d_out || !d_dets || !d_counts || n < 0 || cap <= 0 || (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST)) return YF_ENG_ERR_ARG;
+  if (!e || !d_in || !d_out || !d_dets || !d_counts || n < 0 || cap <= 0 || !decode_mode_ok(mode)) return YF_ENG_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));
   const DecodeArgs dec = {d_dets, d_counts, cap, mode, w_scale, h_scale};
   return launch(e, shape_for(e, n), d_in, d_out, nullptr, n, (hipStream_t)stream, -1, &dec);
@@ -606,10 +560,10 @@ int yf_engine_run_decode_device(yf_engine* e, const void* d_in, void* d_out, lon
 int yf_engine_run_camera_device(yf_engine* e, const void* d_rgb565, void* d_out, long n, int mode, float w_scale, float h_scale,
                                 void* d_dets, void* d_counts, int cap, void* stream) {
   if (!e || !d_rgb565 || !d_out || n < 0) return YF_ENG_ERR_ARG;
-  if (d_dets && (!d_counts || cap <= 0 || (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST))) return YF_ENG_ERR_ARG;
+  if (d_dets && (!d_counts || cap <= 0 || !decode_mode_ok(mode))) return YF_ENG_ERR_ARG;
   if (((uintptr_t)d_rgb565 & 15) != 0) { e->err = "camera frames must be 16-byte aligned"; return YF_ENG_ERR_ARG; }
   HIPCHK(e, hipSetDevice(e->device));
-  const Variant* v = find_variant(e->var->f, e->var->nw, false, true, false, e->kset);
+  const Variant* v = find_variant(e->var->f, e->var->nw, e->kset, CAMERA);
   if (!v) { e->err = "no camera-input build of the configured kernel shape"; return YF_ENG_ERR_VARIANT; }
   const DecodeArgs dec = {d_dets, d_counts, cap, mode, w_scale, h_scale};
   return launch(e, v, d_rgb565, d_out, nullptr, n, (hipStream_t)stream, -1, d_dets ? &dec : nullptr);
@@ -732,18 +686,29 @@ long yf_engine_dump_offset(int tflite_op) {
   }
 }
 
-int yf_engine_time_device(yf_engine* e, const void* d_in, void* d_out, long n, int iters, void* stream, float* ms_per_launch) {
-  if (!e || !d_in || !d_out || n <= 0 || iters <= 0 || !ms_per_launch) return YF_ENG_ERR_ARG;
+// iters launches of v between two events on the stream: milliseconds per launch
+static int time_launches(yf_engine* e, const Variant* v, const void* d_in, void* d_out, long n, int iters, int stop_stage, void* stream, float* ms_per_launch) {
   HIPCHK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(e, hipEventRecord(e->ev0, s));
-  for (int i = 0; i < iters; ++i) { const int rc = launch(e, e->var, d_in, d_out, nullptr, n, s); if (rc) return rc; }
+  for (int i = 0; i < iters; ++i) { const int rc = launch(e, v, d_in, d_out, nullptr, n, s, stop_stage); if (rc) return rc; }
   HIPCHK(e, hipEventRecord(e->ev1, s));
   HIPCHK(e, hipEventSynchronize(e->ev1));
   float ms = 0.f;
   HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
   *ms_per_launch = ms / iters;
   return YF_ENG_OK;
+}
+
+int yf_engine_time_device(yf_engine* e, const void* d_in, void* d_out, long n, int iters, void* stream, float* ms_per_launch) {
+  if (!e || !d_in || !d_out || n <= 0 || iters <= 0 || !ms_per_launch) return YF_ENG_ERR_ARG;
+  return time_launches(e, e->var, d_in, d_out, n, iters, -1, stream, ms_per_launch);
+}
+
+int yf_engine_time_stages(yf_engine* e, const void* d_in, void* d_out, long n, int iters, int stop_stage, void* stream, float* ms_per_launch) {
+  if (!e || !d_in || !d_out || n <= 0 || iters <= 0 || !ms_per_launch) return YF_ENG_ERR_ARG;
+  if (!e->var_dump) { e->err = "no debug (stage-timing) build of the configured kernel shape"; return YF_ENG_ERR_VARIANT; }
+  return time_launches(e, e->var_dump, d_in, d_out, n, iters, stop_stage, stream, ms_per_launch);
 }
 
 // ---------------------------------------------------------------------------------------------- 160x160 variant
@@ -808,60 +773,26 @@ void yf_engine_scratch_stats(yf_engine* e, unsigned long long out[6]) {
   }
 }
 
-int yf_engine_time_stages(yf_engine* e, const void* d_in, void* d_out, long n, int iters, int stop_stage, void* stream, float* ms_per_launch) {
-  if (!e || !d_in || !d_out || n <= 0 || iters <= 0 || !ms_per_launch) return YF_ENG_ERR_ARG;
-  if (!e->var_dump) { e->err = "no debug (stage-timing) build of the configured kernel shape"; return YF_ENG_ERR_VARIANT; }
-  HIPCHK(e, hipSetDevice(e->device));
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(e, hipEventRecord(e->ev0, s));
-  for (int i = 0; i < iters; ++i) { const int rc = launch(e, e->var_dump, d_in, d_out, nullptr, n, s, stop_stage); if (rc) return rc; }
-  HIPCHK(e, hipEventRecord(e->ev1, s));
-  HIPCHK(e, hipEventSynchronize(e->ev1));
-  float ms = 0.f;
-  HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  *ms_per_launch = ms / iters;
-  return YF_ENG_OK;
-}
-
+// ---------------------------------------------------------------------------------------------- the small kernels
 int yf_engine_decode_device(yf_engine* e, const void* d_heads, long n, int mode, float w_scale, float h_scale,
                             void* d_dets, void* d_counts, int cap, void* stream) {
-  if (!e || !d_heads || !d_dets || !d_counts || n < 0 || cap <= 0 || (mode != YF_DECODE_PY && mode != YF_DECODE_FW && mode != YF_DECODE_FW_HOST)) return YF_ENG_ERR_ARG;
-  if (n == 0) return YF_ENG_OK;
-  HIPCHK(e, hipSetDevice(e->device));
-  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const int8_t*)d_heads, n, mode, w_scale, h_scale, (yf_det*)d_dets, (int*)d_counts, cap);
-  HIPCHK(e, hipGetLastError());
-  return YF_ENG_OK;
+  if (!e || !d_heads || !d_dets || !d_counts || n < 0 || cap <= 0 || !decode_mode_ok(mode)) return YF_ENG_ERR_ARG;
+  return launch_small(e, decode_kernel, n * 64, stream, (const int8_t*)d_heads, n, mode, w_scale, h_scale, (yf_det*)d_dets, (int*)d_counts, cap);   // one wave per frame
 }
 
 int yf_engine_pack_detections_device(yf_engine* e, const void* d_dets, const void* d_counts, const void* d_heads, void* d_wire, long n, int cap, void* stream) {
   if (!e || !d_dets || !d_counts || !d_heads || !d_wire || n < 0 || cap <= 0 || ((uintptr_t)d_wire & 3) != 0 || ((uintptr_t)d_dets & 3) != 0) return YF_ENG_ERR_ARG;
-  if (n == 0) return YF_ENG_OK;
-  HIPCHK(e, hipSetDevice(e->device));
-  hipLaunchKernelGGL(pack_dets_kernel, dim3((unsigned)((n * cap + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const yf_det*)d_dets, (const int*)d_counts, (const int8_t*)d_heads, (uint32_t*)d_wire, n, cap);
-  HIPCHK(e, hipGetLastError());
-  return YF_ENG_OK;
+  return launch_small(e, pack_dets_kernel, n * cap, stream, (const yf_det*)d_dets, (const int*)d_counts, (const int8_t*)d_heads, (uint32_t*)d_wire, n, cap);
 }
 
 int yf_engine_unpack_detections_device(yf_engine* e, const void* d_wire, const void* d_counts, void* d_heads, long n, int cap, void* stream) {
   if (!e || !d_wire || !d_counts || !d_heads || n < 0 || cap <= 0 || ((uintptr_t)d_wire & 3) != 0) return YF_ENG_ERR_ARG;
-  if (n == 0) return YF_ENG_OK;
-  HIPCHK(e, hipSetDevice(e->device));
-  hipLaunchKernelGGL(unpack_dets_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint32_t*)d_wire, (const int*)d_counts, (int8_t*)d_heads, n, cap);
-  HIPCHK(e, hipGetLastError());
-  return YF_ENG_OK;
+  return launch_small(e, unpack_dets_kernel, n * 64, stream, (const uint32_t*)d_wire, (const int*)d_counts, (int8_t*)d_heads, n, cap);   // one wave per frame
 }
 
 int yf_engine_prepare_rgb565_device(yf_engine* e, const void* d_rgb565, void* d_out, long n, void* stream) {
   if (!e || !d_rgb565 || !d_out || n < 0) return YF_ENG_ERR_ARG;
-  if (n == 0) return YF_ENG_OK;
-  HIPCHK(e, hipSetDevice(e->device));
-  hipLaunchKernelGGL(prepare_rgb565_kernel, dim3((unsigned)((n * 3136 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint8_t*)d_rgb565, (int8_t*)d_out, n);
-  HIPCHK(e, hipGetLastError());
-  return YF_ENG_OK;
+  return launch_small(e, prepare_rgb565_kernel, n * 3136, stream, (const uint8_t*)d_rgb565, (int8_t*)d_out, n);
 }
 
 }  // extern "C"

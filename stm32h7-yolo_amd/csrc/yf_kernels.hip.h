@@ -15,7 +15,7 @@
 //   max-pool              : separable, packed 2x int16 max on the byte lanes, clamped coordinates
 //   residual add          : TFLite int8 ADD arithmetic in the producing conv's epilogue
 //   concat                : producers write straight into the concat buffer (no copy)
-// Included twice by yf_engine.hip: namespace yf (56x56: the fused kernel) and namespace yf160 (YF_H0 160: the banded kernels).
+// Included twice per kernel set (yf_kernel_set.hip.h, from yf_engine.hip): namespace yf (56x56: the fused kernel) and namespace yf160 (YF_H0 160: the banded kernels).
 // This file holds what both share -- the LDS plan, the arithmetic, input staging, pools and the stage forms (namespace v2) -- and includes, from inside
 // the namespace:   yf_fused56.hip.h   the fused 56x56 kernel            (namespace yf)
 //                  yf_band160.hip.h   the three banded 160x160 kernels  (namespace yf160)

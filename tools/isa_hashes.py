@@ -5,7 +5,7 @@ Unbundles the gfx950 code objects (yf_engine.o, yf_fp16.o) out of libyf_network.
 kernel: sha256[:16] of its instruction text, its instruction count, its mangled name.  The int8 kernels are FROZEN since round 4 (DESIGN.md section 7);
 `profiles/isa_hashes_frozen.txt` is the list of the round-5 product library, and tests/test_abi.py::test_frozen_kernels_are_instruction_identical compares a
 fresh build with it -- a host-side edit of a device source file (round 6: yf_engine.hip, yf_stream_scratch.h, yf_fused56.hip.h for the laboratory's dump
-build) must leave every line unchanged.
+build; since then: yf_kernel_set.hip.h, which instantiates the kernel sets for yf_engine.hip, and the engine's variant tables) must leave every line unchanged.
 
     python tools/isa_hashes.py [library.so]              print
     python tools/isa_hashes.py --check [library.so]      compare with profiles/isa_hashes_frozen.txt, exit 1 on any difference
