@@ -958,38 +958,50 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
 
 // ---- depthwise 3x3 (one-hot lane-private MFMA, see dw_mfma_stage): geometry of a stage instance
 // Output rows per lane and job.  R = 1: a job is 4 rows x 16 columns, lane (g, c) computes row g, column c from its own nine tap reads.
-// R > 1 (row window): lane (g, c) walks rows g*R .. g*R + R - 1 of the job's block down column c and keeps the last three input rows in
-// registers -- three new tap reads per output row instead of four and a half (R = 2) or nine.  The stride-1 stages of the 56x56 kernel with two
-// frames per group: conv2d_3 (28 rows = one block of 4 x 7; 8 jobs for 8 waves, as 56 jobs of one row) and conv2d_15 (14 rows = blocks of 4 x 2
-// at rows 0 and 6, as now 16 rows computed; 36 jobs of two rows, so the busiest wave has 10 rows instead of 9, and lanes g = 0, 1 are 2 rows = 288
-// dwords apart, a 2-way bank conflict on every tap read -- measured faster anyway: profiles/EXPERIMENTS.md, round 7).  The 7x7 stages (two frames per
-// job) keep R = 1, and so do the one-frame form and the 160x160 bands.
+// R > 1 (row window): lane (g, c) walks R consecutive rows of the job's block down column c and keeps the input rows it shares with the next output row in
+// registers: at stride 1 the last two of three (three new tap reads per output row instead of nine), at stride 2 the last one (six instead of nine:
+// 3 (2R + 1) dwords for R rows).  The four lane groups g of a job are FG frames x 4 / FG row segments of R rows; a block taller than the frame moves its
+// last segment up (rows computed twice give the same bytes).  The stages of the 56x56 kernel with two frames per group:
+//   conv2d_3   28x28 stride 1   R = 7, FG = 1: one block of 4 x 7 rows; 8 jobs for 8 waves, as 56 jobs of one row before
+//   conv2d_15  14x14 stride 1   R = 2, FG = 1: blocks of 4 x 2 rows at rows 0 and 6 (16 rows computed, as before); 36 jobs, the busiest wave has 10 rows instead
+//                               of 9, and lanes g = 0, 1 are 288 dwords apart (2-way bank conflict) -- measured faster anyway: profiles/EXPERIMENTS.md, round 7
+//   conv2d_10  14x14 stride 2   R = 7, FG = 2: a job is both frames x rows 0-6 / 7-13 of one channel group: 5 jobs for the 5 waves beside pool_8 h, 7 rows and
+//                               45 tap dwords per lane instead of 8 rows (16 computed for 14) and 72
+//   conv2d_27   7x7  stride 2   R = 4, FG = 2 (four frames per tail run, two more across a row's 16 lanes): a job is four frames x rows 0-3 / 3-6: 6 jobs
+//                               for the 5 waves beside pool_25 -- 8 rows on the busiest wave instead of 5, 54 tap dwords instead of 45, measured faster anyway
+// (profiles/r08_dw_rows_ab.txt).  The 7x7 stride-1 stages keep R = 1 (measured: every window shape loses or stays inside the noise), and so do the
+// one-frame form and the 160x160 bands.
+struct DwWalk { int R, FG; };          // rows per lane; frames across the four lane groups (each frame gets 4 / FG row segments)
 template <int F, int STRIDE, int W, int H>
-constexpr int dw_rows_per_lane() {
+constexpr DwWalk dw_rows_per_lane() {
 #if YF_H0 == 56
-  return STRIDE == 1 && F == 2 && W == 28 && H == 28 ? 7 : STRIDE == 1 && F == 2 && W == 14 && H == 14 ? 2 : 1;
-#else
-  return 1;
+  if (STRIDE == 1 && F == 2 && W == 28 && H == 28) return DwWalk{7, 1};
+  if (STRIDE == 1 && F == 2 && W == 14 && H == 14) return DwWalk{2, 1};
+  if (STRIDE == 2 && F == 2 && W == 14 && H == 14) return DwWalk{7, 2};        // conv2d_10: lane groups = 2 frames x rows 0-6 / 7-13
+  if (STRIDE == 2 && F == 4 && W == 7 && H == 7) return DwWalk{4, 2};          // conv2d_27: lane groups = 2 frames x rows 0-3 / 3-6, two more frames across the 16 lanes
 #endif
+  return DwWalk{1, 1};
 }
 template <int F, int STRIDE, class IN, class OUT>
 struct DwGeo {
   static constexpr int W = OUT::W, H = OUT::H;
-  static constexpr int R = dw_rows_per_lane<F, STRIDE, OUT::W, OUT::H>(), BR = 4 * R;     // rows per lane, rows per job block
+  static constexpr DwWalk WK = dw_rows_per_lane<F, STRIDE, OUT::W, OUT::H>();
+  static constexpr int R = WK.R, FG = WK.FG, RG = 4 / FG, BR = RG * R;     // rows per lane, frames / row segments across the lane groups, rows per job block
   static constexpr int FL = (W <= 8 && F % 2 == 0) ? 2 : 1;
-  static constexpr int NSEG = (W + 15) / 16, NRB = (H + BR - 1) / BR, NFP = F / FL;
+  static constexpr int NSEG = (W + 15) / 16, NRB = (H + BR - 1) / BR, NFP = F / (FL * FG);
   static constexpr int JPG = NFP * NRB * NSEG;                 // jobs per channel group
   static_assert(OUT::RS == W && OUT::PT == 0 && OUT::PL == 0, "depthwise outputs are plain buffers");
   static_assert(IN::FS == OUT::FS, "one frame stride per stage");
-  static_assert(H >= BR && (W >= 16 || W * FL <= 16), "tile shape");
-  static_assert(R == 1 || (STRIDE == 1 && FL == 1), "row window: stride-1 stages, one frame per job");
+  static_assert((H >= BR || (R > 1 && H >= R)) && (W >= 16 || W * FL <= 16) && F % (FL * FG) == 0 && RG * FG == 4, "tile shape");
+  // first row (within the job's block) of row segment rs: a block taller than the frame (R > 1 only) moves its last segments up, as the last block of a frame is
+  __device__ static __forceinline__ int seg_row(int rs) { return BR > H ? min(rs * R, H - R) : rs * R; }
   // offsets (relative to the workgroup's frame arenas) of job jj: the top-left tap of lane (0,0) and its output pixel
   __device__ static __forceinline__ uint2 job(int jj) {
     const int fp = jj / (NRB * NSEG); int rem = jj - fp * (NRB * NSEG);
     const int rb = rem / NSEG, seg = rem - rb * NSEG;
-    const int oy0 = min(rb * BR, H - BR);
+    const int oy0 = BR > H ? 0 : min(rb * BR, H - BR);
     const int x0 = (W >= 16) ? min(seg * 16, W - 16) : 0;
-    const int fb = fp * FL * IN::FS;
+    const int fb = fp * FL * FG * IN::FS;
     return uint2{(uint32_t)(fb + IN::OFF + (oy0 * STRIDE) * IN::ROWB + x0 * STRIDE * IN::S), (uint32_t)(fb + OUT::OFF + (oy0 * W + x0) * OUT::S)};
   }
 };
@@ -1083,8 +1095,9 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
   const int g = lane >> 4, c = lane & 15;
   const int fl = (FL == 2) ? (c >> 3) : 0;
   const int xl = (FL == 2) ? min(c & 7, W - 1) : min(c, W - 1);      // surplus lanes duplicate the last column (idempotent)
-  const char* lane_in = frames + fl * IN::FS + g * G::R * DROW + xl * STRIDE * IN::S;     // this lane's (first) pixel: row oy0+g*R, col x0+xl
-  char* lane_out = frames + fl * IN::FS + (g * G::R * W + xl) * OUT::S;
+  const int fr = fl + FL * (g / G::RG), row0 = G::seg_row(g % G::RG);                    // this lane's frame of the job and its (first) row of the job's block
+  const char* lane_in = frames + fr * IN::FS + row0 * DROW + xl * STRIDE * IN::S;        // this lane's (first) pixel: row oy0+row0, col x0+xl
+  char* lane_out = frames + fr * IN::FS + (row0 * W + xl) * OUT::S;
   const bool a_on = (c >> 2) == g;
   const uint32_t a_lane = a_on ? (uint32_t)(SLOT + 4 * (c & 3)) : (uint32_t)LAY::ZERO;   // masked weight dwords of channel c&3: +16*tap
   const uint32_t a_step = a_on ? (uint32_t)YF_DWV_GROUP_BYTES : 0u;
@@ -1133,7 +1146,8 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
     const int n = min(left, JPG - jj);
     if constexpr (G::R > 1) {
       // row window: the weights by kernel row (MFMA k = the three taps of row ky in dwords 0..2, dword 3 zero), one input row = one B operand;
-      // output row y of the lane reads input row y + 2 only, rows y and y + 1 are the previous output row's
+      // stride 1: output row y of the lane reads input row y + 2 only, rows y and y + 1 are the previous output row's; stride 2: it reads rows 2y + 1 and
+      // 2y + 2, row 2y is the previous output row's last
       const v4i ar[3] = {v4i{a0[0], a0[1], a0[2], 0}, v4i{a0[3], a1[0], a1[1], 0}, v4i{a1[2], a1[3], a2[0], 0}};
       for (int i = 0; i < n; ++i) {
         const v2u e = entry(jj + i);
@@ -1146,13 +1160,15 @@ YF_STAGE_FN void dw2_stage(char* frames, const uint8_t* __restrict__ tab, int wa
         v4i w0 = row(0), w1 = row(1);
 #pragma unroll
         for (int y = 0; y < G::R; ++y) {
-          const v4i w2 = row(y + 2);
+          if constexpr (STRIDE == 2) { if (y > 0) w1 = row(2 * y + 1); }
+          const v4i w2 = row(STRIDE * y + 2);
           v4i acc = acc_init(pv.zr);
           acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[0], w0, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[1], w1, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[2], w2, acc, 0, 0, 0);
           finish(acc, dst + y * W * OUT::S);
-          w0 = w1; w1 = w2;
+          if constexpr (STRIDE == 2) w0 = w2;
+          else { w0 = w1; w1 = w2; }
         }
       }
       left -= n; ++cg; jj = 0;
