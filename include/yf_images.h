@@ -10,7 +10,8 @@
  *
  * Pointers prefixed d_ are device memory.  Every call is asynchronous on `stream` (a hipStream_t, NULL = default stream) on the calling
  * thread's current device (the run_* calls: the network's device), does no host synchronisation and no allocation, and can be captured in
- * a graph -- except that the first per-image-scale decode on a device uploads the 2 KB decode tables once (synchronously).
+ * a graph -- except that a decode of int8 heads whose 2 KB decode tables are not on the device yet uploads them first (synchronously; the rule
+ * is at yf_images_set_decode_tables below): always the first such decode on a device, later ones only when the tables changed.
  * Return values follow include/yf_network.h: n on success, <= 0 on error; yf_images_last_error_text() says why (per thread).
  * d_frames must be 16-byte aligned. */
 #ifndef YF_IMAGES_H
@@ -59,6 +60,17 @@ YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, siz
 YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
                                                const yf_image* d_images, long n, void* d_frames, void* d_heads, int mode,
                                                void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+/* Decode tables.  This library keeps its own copy of the sigmoid / exp tables on each device (the shipped pair at first) together with the id of
+ * what it uploaded.  An entry point that takes a network and decodes int8 heads here -- the ragged 56x56 run, both 160x160 runs -- compares
+ * yf_network_decode_tables' id with that id before it launches and, if they differ (the network was initialised from a model file with another
+ * output quantisation, or went back to the shipped model), uploads the network's pair again: synchronously, after waiting for the device, as the
+ * first upload is synchronous, and not inside stream capture.  The uniform 56x56 run decodes inside the network's own launch with the network's
+ * tables.  The entry points that take NO network (yf_images_decode_ragged_device, yf_images_decode160_device,
+ * yf_images_decode160_ragged_device) decode with the pair last given to this setter, under the same id rule; without a call that is the shipped
+ * pair.  sig_bits, exp_bits: float32 bits, index q + 128, the sigmoid table not decreasing; id: what yf_network_decode_tables returned with them
+ * (equal ids must mean equal tables).  Host-only, copies the tables.  0, or -1 (NULL or a decreasing sigmoid table).  The fp16 / float32 entries
+ * use no tables. */
+YF_API int yf_images_set_decode_tables(const uint32_t sig_bits[256], const uint32_t exp_bits[256], uint64_t id);
 /* Per-image scales for heads that already exist (d_heads int8[n][7][7][18]); a descriptor whose height or width is outside
  * [1, 16384] gets count 0. */
 YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode,

@@ -242,6 +242,39 @@ enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, 
 #endif
 YF_API int  yf_network_set_requant_rounding(ai_handle network, int rounding);
 YF_API int  yf_network_get_requant_rounding(ai_handle network);      /* the rounding in force, -1 for an invalid handle */
+/* A re-quantised model: ai_network_init's alternative for a network created with ai_network_create.  `yfm` is a .yfm image of `bytes` bytes (layout and
+ * writer: stm32h7-yolo_amd/model_file.py; `tflite_to_yfm` converts a .tflite; the oracle reads the same bytes) and is not referenced after the call.
+ * The kernels are built for ONE graph and table-driven in everything else, so the image may change every activation scale and zero point, every
+ * per-channel filter scale, the weights and the biases -- and nothing else.  The bytes are treated as untrusted.  Checked, in this order:
+ *   - magic 'YFM1', 104 tensors, 54 ops, input tensor 0, output tensor 100, and the size the counts give;
+ *   - per tensor: type, shape, constant or not, the number of scales (1, or the channels of its quantised dimension), scales and data inside the
+ *     data section, scales positive and finite, activation zero points in -128..127, filter and bias zero points 0;
+ *   - the 54 ops of the network in order: opcode, wiring, padding, strides, filter sizes, depth multiplier, axis, and
+ *     the LeakyReLU alpha 0.1f (0x3dcccccd); the PAD ops' paddings (top and left 1);
+ *   - the input quantisation the frame producers assume (pixel - 128: the prepare kernels, the camera staging, libyf_images): scale bits
+ *     0x3b808081 (1/255), zero point -128;
+ *   - what the table builder relies on: a PAD or MAX_POOL_2D output carries its input's scale and zero point, CONCATENATION inputs carry the
+ *     output's, a bias scale is s_in * s_w[c];
+ *   - then ai_network_init's admission of every channel under the rounding in force (shift in 1..20, multiplier > 2^30, |accumulator| < 2^29, and
+ *     |acc| * fs < 2^21 under YF_ROUND_FP32).
+ * Anything else is REFUSED: false, AI_ERROR_INIT_FAILED latched, and yf_network_last_error_text names the first mismatch -- for the graph
+ * "op 10: stride_w is 1, expected 2": the op (or tensor) index, the field, the value found, the value expected.  A refused image -- by the
+ * parser or by the admission of a channel -- leaves the network as it was; an accepted one on an initialised network does what a second
+ * ai_network_init does: the engine is destroyed and built anew (and if THAT fails -- no device, an invalid $YF_REQUANT_ROUNDING -- the network
+ * is left created but not initialised, as after a failed ai_network_init).
+ * yf_network_set_requant_rounding afterwards rebuilds from THIS model, for every rounding.  ai_network_get_report keeps describing the shipped
+ * network.c (same graph, same sizes); the ST-graph route (ai_platform_network_* with a caller's network.c) keeps verifying against the shipped
+ * quantisation.
+ * Decode tables: for a model whose OUTPUT scale and zero point are the shipped ones (0x3e11987e, -15) the committed tables stay (SURVEY.md
+ * 8(c).5); for any other they are built here, for q = -128..127, x = fl32(fl32(q - zp) * s), sigmoid = 1.0f / (1.0f + E(-x)), exp = E(x), E the
+ * correctly rounded float32 exponential of csrc/yf_exp_f32.h, and uploaded before the call returns.  E is THE LIBRARY'S CHOICE: the script's
+ * numpy float32 exp is not correctly rounded and differs between numpy builds, so for a model the reference never ran there is no literal answer
+ * to reproduce (the shipped tables, one numpy's answer, differ from the E-built ones in 124 of 512 entries). */
+YF_API ai_bool yf_network_init_model(ai_handle network, const void* yfm, size_t bytes);
+/* The decode tables in force on an initialised network (float32 bits, index q + 128; either array may be NULL) and an id of their contents
+ * (a 64-bit hash: equal tables, equal id).  libyf_images compares the id with that of its own copy before every int8 decode (include/yf_images.h).
+ * 0, or -1 (not initialised: error latched). */
+YF_API int  yf_network_decode_tables(ai_handle network, uint32_t sig_bits[256], uint32_t exp_bits[256], uint64_t* id);
 /* Select GPU (default 0 / $LOCAL_RANK is NOT read here; the caller decides).  Call before ai_network_init.  ONE DEVICE PER PROCESS: the library keeps
  * one network instance (like the reference: network.c:2929-2939) and its decode tables live in device symbols of the device the instance was
  * initialised on; a host that drives several GPUs starts one process per GPU (tools/c_host/yf_ranks.c, bench.py). */

@@ -95,7 +95,7 @@ EXPORTS = ["ai_network_create", "ai_network_init", "ai_network_run", "ai_network
            "ai_network_data_params_get", "ai_platform_bind_network_params", "yf_network_set_device",
            "yf_network_configure", "yf_network_run_device", "yf_network_run_device_dump", "yf_network_dump_bytes", "yf_network_run_device_hw",
            "yf_network_decode_device", "yf_network_run_decode_device", "yf_network_pack_detections_device", "yf_network_unpack_detections_device", "yf_network_prepare_rgb565_device", "yf_network_run_camera_device", "yf_network_time_device",
-           "yf_network_time_stages", "yf_network_format_uart", "yf_network_shard_range", "yf_network_table_plan", "yf_network_all_gather_device", "yf_network_fp16_init", "yf_network_fp16_run_device", "yf_network_fp16_ready", "yf_network_release_stream", "yf_network_scratch_bytes", "yf_network_scratch_stats", "yf_network_set_requant_rounding", "yf_network_get_requant_rounding", "yf_network_last_error_text",
+           "yf_network_time_stages", "yf_network_format_uart", "yf_network_shard_range", "yf_network_table_plan", "yf_network_all_gather_device", "yf_network_fp16_init", "yf_network_fp16_run_device", "yf_network_fp16_ready", "yf_network_release_stream", "yf_network_scratch_bytes", "yf_network_scratch_stats", "yf_network_set_requant_rounding", "yf_network_get_requant_rounding", "yf_network_init_model", "yf_network_decode_tables", "yf_network_last_error_text",
            "yf_network_kernel_name", "yf_network_kernel_name_for", "yf_network_build_id", "yf_network_host_id",
            "ai_platform_observer_node_info", "ai_platform_observer_register", "ai_platform_observer_register_s",
            "ai_platform_observer_unregister", "ai_platform_observer_unregister_s",
@@ -306,6 +306,10 @@ def load():
         lib.yf_network_set_requant_rounding.argtypes = [vp, ctypes.c_int]
         lib.yf_network_get_requant_rounding.argtypes = [vp]
         lib.yf_network_scratch_stats.argtypes = [vp, ctypes.POINTER(YfScratchStats)]
+    if hasattr(lib, "yf_network_init_model"):              # (an older library loaded through YF_LIB_PATH for an A/B run does without)
+        lib.yf_network_init_model.restype = ctypes.c_bool
+        lib.yf_network_init_model.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_network_decode_tables.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.yf_network_last_error_text.restype = ctypes.c_char_p
     lib.yf_network_last_error_text.argtypes = [vp]
     lib.yf_network_kernel_name.restype = ctypes.c_char_p
@@ -408,6 +412,22 @@ class Network:
             self._raise("ai_network_init")
         self.ready = True
         return self
+
+    def init_model(self, yfm_bytes):
+        """yf_network_init_model: initialise from a .yfm image (model_file.write_yfm / tflite_to_yfm) instead of the shipped model -- its
+        scales, zero points, weights and biases on the same kernels.  A refused image raises with the first mismatch in the text."""
+        b = bytes(yfm_bytes)
+        if not self.lib.yf_network_init_model(self.handle, b, len(b)):
+            self._raise("yf_network_init_model")
+        self.ready = True
+        return self
+
+    def decode_tables(self):
+        """(sigmoid float32[256], exp float32[256], id) in force (yf_network_decode_tables): index q + 128; the id names the contents."""
+        sig, ex, ident = np.zeros(256, np.uint32), np.zeros(256, np.uint32), ctypes.c_uint64()
+        if self.lib.yf_network_decode_tables(self.handle, sig.ctypes.data, ex.ctypes.data, ctypes.byref(ident)) != 0:
+            self._raise("yf_network_decode_tables")
+        return sig.view(np.float32), ex.view(np.float32), int(ident.value)
 
     def run(self, frames, out=None):
         """ai_network_run on host memory: int8 [n,56,56,3] -> int8 [n,7,7,18] (yoloface.c:216-240, n_batches = n).  `out`: the caller's

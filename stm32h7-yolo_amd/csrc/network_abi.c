@@ -13,6 +13,7 @@
 #include "../../include/yf_network.h"
 #include "yf_engine.h"
 #include "yf_host_prep.h"
+#include "yf_model_file.h"
 #include "yf_impl.h"
 #include "yf_fp16.h"
 #include "gen/yf_model_gen.h"
@@ -38,6 +39,8 @@ typedef struct {
   ai_platform_version tools_api;          /* what the network was created with (network.c:3376: AI_TOOLS_API_VERSION_*); reports return it */
   const void* bound_weights;              /* what ai_network_init was handed: the reports describe these buffers */
   ai_handle bound_activations;
+  yf_model_file* model_file;              /* yf_network_init_model: the parsed model (quantisation, weights in the ST layout), owned; NULL = the shipped model */
+  uint64_t decode_tables_id;              /* FNV-1a over the decode tables in force (yf_network_decode_tables) */
   char err_text[512];
 } yf_context;
 
@@ -82,6 +85,7 @@ ai_error yf_impl_create(ai_handle* network, const ai_buffer* network_config) {
   if (network_config != NULL) { *network = AI_HANDLE_NULL; return mk_error(AI_ERROR_CREATE_FAILED, AI_ERROR_CODE_NETWORK); }
   if (g_network.state == ST_READY && g_network.engine) { yf_engine_destroy(g_network.engine); }
   if (g_network.state != ST_NONE && g_network.fp16) { yf_fp16_destroy(g_network.fp16); }
+  free(g_network.model_file);
   const int dev = g_network.state != ST_NONE ? g_network.device : 0;
   const int cf = g_network.cfg_frames, cw = g_network.cfg_waves;
   memset(&g_network, 0, sizeof g_network);
@@ -98,6 +102,7 @@ ai_handle yf_impl_destroy(ai_handle network) {
   if (!c) return network;                       /* not destroyed: same handle comes back (network.h:155-157) */
   if (c->engine) yf_engine_destroy(c->engine);
   if (c->fp16) yf_fp16_destroy(c->fp16);
+  free(c->model_file);
   memset(c, 0, sizeof *c);
   return AI_HANDLE_NULL;
 }
@@ -136,6 +141,66 @@ const uint8_t* yf_impl_resolve_weights(const ai_network_params* p, size_t* bytes
   return (const uint8_t*)wb->data;                /* bare blob pointer */
 }
 
+static uint64_t fnv1a64(const void* p, size_t n, uint64_t h) {
+  const uint8_t* b = (const uint8_t*)p;
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  return h;
+}
+static uint64_t tables_id(const uint32_t* sig, const uint32_t* ex) { return fnv1a64(ex, 1024, fnv1a64(sig, 1024, 1469598103934665603ull)); }
+
+/* a refusal of the table builder; for a model file the admission bound is spelled out */
+static void latch_prep(yf_context* c, int prc, int model) {
+  char t[200];
+  if (prc == YF_PREP_ERR_SHIFT_RANGE && model) snprintf(t, sizeof t, "table preparation failed (code %d): a channel's requantisation is outside what the kernels compute exactly (1 <= shift <= 20, |accumulator| < 2^29)", prc);
+  else snprintf(t, sizeof t, "table preparation failed (code %d)", prc);
+  latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_WEIGHTS, t);
+}
+
+/* The common tail of ai_network_init and yf_network_init_model: (re)build the engine for `blob` (ST layout) under the quantisation of `mf`
+ * (NULL: the shipped model's).  Takes ownership of mf, also on failure. */
+static ai_bool start_engine(yf_context* c, yf_model_file* mf, const uint8_t* blob, size_t wbytes) {
+  if (c->engine) { yf_engine_destroy(c->engine); c->engine = NULL; c->state = ST_CREATED; }
+  if (c->model_file && c->bound_weights == (const void*)c->model_file->weights) { c->bound_weights = NULL; c->bound_weights_bytes = 0; }
+  free(c->model_file);
+  c->model_file = mf;
+  if (!rounding_is_valid(c->rounding)) {
+    latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, "YF_REQUANT_ROUNDING is none of ref, ties_up, ties_up_all, single (optionally followed by +generic), fp32"); return false;
+  }
+
+  uint8_t* tables = NULL;
+  yf_table_index ix;
+  const int prc = yf_prepare_tables_model(mf ? &mf->model : yf_default_model(), blob, wbytes, c->rounding, &tables, &ix);
+  if (prc != YF_PREP_OK) {
+    latch_prep(c, prc, mf != NULL); return false;
+  }
+  char etext[400] = "";
+  const int erc = yf_engine_create(c->device, tables, &ix, yf_rounding_kernel_set(c->rounding), &c->engine, etext, sizeof etext);
+  free(tables);
+  if (erc != YF_ENG_OK) { c->engine = NULL; latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK, etext); return false; }
+  if (c->cfg_frames || c->cfg_waves) {
+    if (yf_engine_configure(c->engine, c->cfg_frames, c->cfg_waves) != YF_ENG_OK) {
+      latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, yf_engine_error(c->engine));
+      yf_engine_destroy(c->engine); c->engine = NULL; return false;
+    }
+  }
+  /* decode tables: the engine has just uploaded the shipped pair, which stays the contract for the shipped output quantisation;
+   * any other output quantisation gets the pair built from it (yf_model_decode_tables) */
+  uint32_t sig[256], ex[256];
+  if (mf && (mf->out_scale_bits != YF_MODEL_SHIPPED_OUT_SCALE_BITS || mf->out_zero_point != YF_MODEL_SHIPPED_OUT_ZERO_POINT)) {
+    yf_model_decode_tables(mf->out_scale_bits, mf->out_zero_point, sig, ex);
+    if (yf_engine_set_decode_tables(c->engine, sig, ex) != YF_ENG_OK) {
+      latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK, yf_engine_error(c->engine));
+      yf_engine_destroy(c->engine); c->engine = NULL; return false;
+    }
+  }
+  yf_engine_get_decode_tables(c->engine, sig, ex);
+  c->decode_tables_id = tables_id(sig, ex);
+  c->state = ST_READY;
+  c->bound_weights = blob;
+  c->bound_weights_bytes = wbytes;
+  return true;
+}
+
 ai_bool yf_impl_init(ai_handle network, const ai_network_params* params) {
   yf_context* c = acquire(network);
   if (!c) return false;
@@ -150,32 +215,31 @@ ai_bool yf_impl_init(ai_handle network, const ai_network_params* params) {
   if (act && act->data && buffer_elems(act) < AI_NETWORK_DATA_ACTIVATIONS_SIZE) {
     latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_ACTIVATIONS, "activations buffer smaller than 29784 bytes"); return false;
   }
-  if (c->engine) { yf_engine_destroy(c->engine); c->engine = NULL; c->state = ST_CREATED; }
-  if (!rounding_is_valid(c->rounding)) {
-    latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, "YF_REQUANT_ROUNDING is none of ref, ties_up, ties_up_all, single (optionally followed by +generic), fp32"); return false;
-  }
-
-  uint8_t* tables = NULL;
-  yf_table_index ix;
-  const int prc = yf_prepare_tables_rounding(blob, wbytes, c->rounding, &tables, &ix);
-  if (prc != YF_PREP_OK) {
-    char t[96]; snprintf(t, sizeof t, "table preparation failed (code %d)", prc);
-    latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_WEIGHTS, t); return false;
-  }
-  char etext[400] = "";
-  const int erc = yf_engine_create(c->device, tables, &ix, yf_rounding_kernel_set(c->rounding), &c->engine, etext, sizeof etext);
-  free(tables);
-  if (erc != YF_ENG_OK) { c->engine = NULL; latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK, etext); return false; }
-  if (c->cfg_frames || c->cfg_waves) {
-    if (yf_engine_configure(c->engine, c->cfg_frames, c->cfg_waves) != YF_ENG_OK) {
-      latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, yf_engine_error(c->engine));
-      yf_engine_destroy(c->engine); c->engine = NULL; return false;
-    }
-  }
-  c->state = ST_READY;
-  c->bound_weights = blob;
-  c->bound_weights_bytes = wbytes;
+  if (!start_engine(c, NULL, blob, wbytes)) return false;
   c->bound_activations = act ? act->data : NULL;
+  return true;
+}
+
+/* A model file instead of the shipped model (include/yf_network.h).  The image is parsed, checked and admitted by the table builder first: a
+ * refused image leaves the network as it was.  From there on this is ai_network_init: an initialised network's engine is destroyed and built anew. */
+static ai_bool yf_impl_init_model(ai_handle network, const void* yfm, size_t bytes) {
+  yf_context* c = acquire(network);
+  if (!c) return false;
+  if (!yfm) { latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_INVALID_PTR, "model image is NULL"); return false; }
+  yf_model_file* mf = (yf_model_file*)malloc(sizeof *mf);
+  if (!mf) { latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK, "out of memory"); return false; }
+  char t[400] = "";
+  if (yf_model_file_parse(yfm, bytes, mf, t, sizeof t) != 0) { free(mf); latch(c, AI_ERROR_INIT_FAILED, AI_ERROR_CODE_NETWORK_PARAMS, t); return false; }
+  /* ... and so does an image the table builder does not admit under the rounding in force: built once here, before anything is torn down */
+  if (rounding_is_valid(c->rounding)) {
+    uint8_t* trial = NULL;
+    yf_table_index ix;
+    const int prc = yf_prepare_tables_model(&mf->model, mf->weights, sizeof mf->weights, c->rounding, &trial, &ix);
+    free(trial);
+    if (prc != YF_PREP_OK) { free(mf); latch_prep(c, prc, 1); return false; }
+  }
+  if (!start_engine(c, mf, mf->weights, sizeof mf->weights)) return false;
+  c->bound_activations = NULL;
   return true;
 }
 
@@ -364,7 +428,8 @@ YF_API int yf_network_set_requant_rounding(ai_handle network, int rounding) {
     /* same weights (still the caller's, as on the MCU: network.c:3108-3267 keeps pointers into the blob), other constants, same layout */
     uint8_t* tables = NULL;
     yf_table_index ix;
-    const int prc = yf_prepare_tables_rounding((const uint8_t*)c->bound_weights, c->bound_weights_bytes, rounding, &tables, &ix);
+    const yf_model* m = c->model_file ? &c->model_file->model : yf_default_model();     /* the model in force */
+    const int prc = yf_prepare_tables_model(m, (const uint8_t*)c->bound_weights, c->bound_weights_bytes, rounding, &tables, &ix);
     if (prc != YF_PREP_OK) { latch(c, AI_ERROR_INVALID_STATE, AI_ERROR_CODE_NETWORK_WEIGHTS, "table preparation failed"); return -1; }
     const int erc = yf_engine_set_tables(c->engine, tables, &ix, yf_rounding_kernel_set(rounding));
     free(tables);
@@ -431,6 +496,19 @@ YF_API long yf_network_run_device_hw(ai_handle network, int height, int width, c
   if (height == 56 && width == 56) return finish(c, yf_engine_run_device(c->engine, d_in, d_out, NULL, n, stream), n);
   if (height == 160 && width == 160) return finish(c, yf_engine_run_device_160(c->engine, d_in, d_out, n, stream), n);
   latch(c, AI_ERROR_INVALID_INPUT, AI_ERROR_CODE_INVALID_SIZE, "supported input sizes: 56x56 (one fused kernel) and 160x160 (banded kernels)");
+  return 0;
+}
+
+YF_API ai_bool yf_network_init_model(ai_handle network, const void* yfm, size_t bytes) { return yf_impl_init_model(network, yfm, bytes); }
+
+YF_API int yf_network_decode_tables(ai_handle network, uint32_t sig_bits[256], uint32_t exp_bits[256], uint64_t* id) {
+  yf_context* c = ready(network);
+  if (!c) return -1;
+  uint32_t sig[256], ex[256];
+  if (sig_bits || exp_bits) yf_engine_get_decode_tables(c->engine, sig, ex);
+  if (sig_bits) memcpy(sig_bits, sig, sizeof sig);
+  if (exp_bits) memcpy(exp_bits, ex, sizeof ex);
+  if (id) *id = c->decode_tables_id;
   return 0;
 }
 

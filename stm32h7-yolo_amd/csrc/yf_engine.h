@@ -21,6 +21,11 @@ int  yf_engine_create(int device, const uint8_t* table_blob, const yf_table_inde
 void yf_engine_destroy(yf_engine* e);
 /* replace the table blob of a live engine (same layout, other constants: yf_network_set_requant_rounding); waits for the device first */
 int  yf_engine_set_tables(yf_engine* e, const uint8_t* table_blob, const yf_table_index* ix, int kernel_set);
+/* The decode tables (sigmoid and exp of the dequantised head value, float32 bits, index q + 128).  yf_engine_create uploads the shipped pair
+ * (gen/yf_decode_tables_gen.h); a model file with another output quantisation brings its own (yf_model_decode_tables).  The upload waits for
+ * the device; the sigmoid table must not decrease.  get: the pair in force. */
+int  yf_engine_set_decode_tables(yf_engine* e, const uint32_t* sig_bits, const uint32_t* exp_bits);
+void yf_engine_get_decode_tables(const yf_engine* e, uint32_t* sig_bits, uint32_t* exp_bits);
 /* 1 if a production kernel of that shape is compiled in (frames_per_wg may carry the +200 experimental-build tag) */
 int  yf_engine_variant_exists(int frames_per_wg, int waves_per_wg);
 int  yf_engine_configure(yf_engine* e, int frames_per_wg, int waves_per_wg);

@@ -174,6 +174,7 @@ struct yf_engine {
   hipStream_t own_stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::string err;
+  uint32_t sig_bits[256], exp_bits[256];         // the decode tables in force on the device (host copy: the quantised confidence threshold is found in sig_bits)
   // ---- host-buffer path (ai_network_run on the caller's arrays, yf_engine_run_host)
   const Variant* var_small = nullptr;            // batches of at most SMALL_N frames: one frame per workgroup (lowest latency); null once a shape is configured
   hipStream_t pipe_stream[2] = {nullptr, nullptr};   // large batches: chunks alternate between two streams (upload of chunk k+1 behind the kernel of chunk k)
@@ -324,7 +325,30 @@ static int launch_small(yf_engine* e, Kernel kernel, long threads, void* stream,
   return YF_ENG_OK;
 }
 
+// The decode tables live in __constant__ memory of this library's code object, one copy per device: whichever engine uploaded last owns them (the
+// library has one network instance).  Synchronous: the device is idle on return, so no launch reads half a table.
+static int upload_decode_tables(yf_engine* e, const uint32_t* sig, const uint32_t* ex) {
+  for (int i = 1; i < 256; ++i) {           // the fused decode compares quantised confidences (yf_decode_q_threshold): the table must not decrease
+    float a, b; memcpy(&a, &sig[i - 1], 4); memcpy(&b, &sig[i], 4);
+    if (!(b >= a)) { e->err = "sigmoid table is not monotonic"; return YF_ENG_ERR_ARG; }
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  HIPCHK(e, hipDeviceSynchronize());
+  HIPCHK(e, hipMemcpyToSymbol(HIP_SYMBOL(d_sig_bits), sig, 1024));
+  HIPCHK(e, hipMemcpyToSymbol(HIP_SYMBOL(d_exp_bits), ex, 1024));
+  memcpy(e->sig_bits, sig, 1024); memcpy(e->exp_bits, ex, 1024);
+  return YF_ENG_OK;
+}
+
 extern "C" {
+
+int yf_engine_set_decode_tables(yf_engine* e, const uint32_t* sig_bits, const uint32_t* exp_bits) {
+  if (!e || !sig_bits || !exp_bits) return YF_ENG_ERR_ARG;
+  return upload_decode_tables(e, sig_bits, exp_bits);
+}
+void yf_engine_get_decode_tables(const yf_engine* e, uint32_t* sig_bits, uint32_t* exp_bits) {
+  memcpy(sig_bits, e->sig_bits, 1024); memcpy(exp_bits, e->exp_bits, 1024);
+}
 
 int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index* ix, int kernel_set, yf_engine** out, char* err, size_t errlen) {
   auto fail = [&](const std::string& m, int code) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; };
@@ -351,12 +375,7 @@ int yf_engine_create(int device, const uint8_t* table_blob, const yf_table_index
   if (!layout_is_the_compiled_plan(ix)) return quit(k_layout_refusal, YF_ENG_ERR_ARG);
   if ((rc = hipMalloc((void**)&e->d_tab, ix->total_bytes)) != hipSuccess) return bail(rc, "hipMalloc(tables)");
   if ((rc = hipMemcpy(e->d_tab, table_blob, ix->total_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(rc, "hipMemcpy(tables)");
-  for (int i = 1; i < 256; ++i) {           // the fused decode compares quantised confidences (yf_decode_q_threshold): the table must not decrease
-    float a, b; memcpy(&a, &yf_sigmoid_bits[i - 1], 4); memcpy(&b, &yf_sigmoid_bits[i], 4);
-    if (b < a) return bail(hipErrorInvalidValue, "sigmoid table is not monotonic");
-  }
-  if ((rc = hipMemcpyToSymbol(HIP_SYMBOL(d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) return bail(rc, "hipMemcpyToSymbol(sigmoid)");
-  if ((rc = hipMemcpyToSymbol(HIP_SYMBOL(d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) return bail(rc, "hipMemcpyToSymbol(exp)");
+  if (upload_decode_tables(e, yf_sigmoid_bits, yf_exp_bits) != YF_ENG_OK) { const std::string m = e->err; return quit(m, YF_ENG_ERR_HIP); }   // the shipped pair; a model file's own: yf_engine_set_decode_tables
   // The byte LUTs are addressed absolutely (LDS offset LUT_ID*256): the dynamic segment must start at LDS address 0, i.e. the kernel must not have picked up
   // any static LDS (refusal: the error text if it has).  lds: the dynamic LDS its launches ask for (0: within the default limit, nothing to raise).
   // wgs_per_cu, if given: receives the resident workgroups of `threads` threads per CU of this device.
@@ -486,9 +505,9 @@ long yf_engine_dump_bytes(void) { return yf::DumpOffsets::TOTAL; }
 
 // The fused decode tests the QUANTISED confidence: the first entry of the (monotonic) sigmoid table that passes the mode's comparison --
 // conf > 0.7f for the Python decode, (double)conf >= 0.7 for the firmware's -- as an int8 value; 128 = none passes.
-static int yf_decode_q_threshold(int mode) {
+static int yf_decode_q_threshold(const yf_engine* e, int mode) {
   for (int i = 0; i < 256; ++i) {
-    float v; memcpy(&v, &yf_sigmoid_bits[i], 4);
+    float v; memcpy(&v, &e->sig_bits[i], 4);
     if (mode == YF_DECODE_PY ? (v > 0.7f) : ((double)v >= 0.7)) return i - 128;
   }
   return 128;
@@ -510,7 +529,7 @@ static int launch(yf_engine* e, const Variant* v, const void* d_in, void* d_out,
   prm.dets = nullptr; prm.counts = nullptr; prm.cap = 0; prm.mode = 0; prm.w_scale = prm.h_scale = 1.f;
   prm.q_thr = 128;
   if (dec) { prm.dets = (yf_det*)dec->dets; prm.counts = (int*)dec->counts; prm.cap = dec->cap; prm.mode = dec->mode; prm.w_scale = dec->w_scale; prm.h_scale = dec->h_scale;
-             prm.q_thr = yf_decode_q_threshold(dec->mode); }
+             prm.q_thr = yf_decode_q_threshold(e, dec->mode); }
   const long groups = (n + v->f - 1) / v->f;
   const int per_cu = (int)(e->lds_per_cu / v->lds) > 0 ? (int)(e->lds_per_cu / v->lds) : 1;
   long grid = (long)e->cus * per_cu;

@@ -25,8 +25,19 @@
 #include <string.h>
 
 static float f32_from_bits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
-static float t_scale(int t) { return f32_from_bits(yf_tensor_scale_bits[t]); }
-static int32_t t_zp(int t) { return yf_tensor_zero_point[t]; }
+static float t_scale(const yf_model* m, int t) { return f32_from_bits(m->scale_bits[t]); }
+static int32_t t_zp(const yf_model* m, int t) { return m->zero_point[t]; }
+
+/* The quantisation the tables are built from (yf_host_prep.h, yf_model).  The default is the shipped model's, gen/yf_model_gen.h;
+ * yf_model_file.c fills one from a .yfm image. */
+#define W(c) {yf_conv##c##_wscale_bits, (int)(sizeof yf_conv##c##_wscale_bits / 4)}
+static const yf_wscale k_default_wscale[YF_N_CONVS] = {      /* in yf_convs[] order */
+  W(1), W(3), W(5), W(6), W(10), W(12), W(13), W(15), W(17), W(19), W(23), W(27), W(29), W(30), W(32), W(34), W(36), W(38), W(40), W(42),
+  W(47), W(49), W(51), W(53),
+};
+#undef W
+static const yf_model k_default_model = {yf_tensor_scale_bits, yf_tensor_zero_point, YF_N_TENSORS, k_default_wscale, YF_N_CONVS};
+const yf_model* yf_default_model(void) { return &k_default_model; }
 
 /* ---- TFLite fixed-point helpers (own statement; the oracle has an independent one) ---------------------- */
 void yf_quantize_multiplier(double real, int32_t* mult, int* shift) {
@@ -82,25 +93,25 @@ static int8_t sat8(int32_t v) { return (int8_t)(v < -128 ? -128 : v > 127 ? 127 
 
 /* ---- LUT builders ------------------------------------------------------------------------------------------ */
 /* TFLite int8 LEAKY_RELU as a table over q in [-128,127] (index q+128). */
-static void build_leaky_lut(int t_in, int t_out, uint8_t* lut, int form) {
-  const float s_in = t_scale(t_in), s_out = t_scale(t_out);
+static void build_leaky_lut(const yf_model* m, int t_in, int t_out, uint8_t* lut, int form) {
+  const float s_in = t_scale(m, t_in), s_out = t_scale(m, t_out);
   const float alpha = 0.1f;                              /* LeakyReluOptions.alpha of all 17 ops (0x3dcccccd) */
   int32_t m_a, m_i; int sh_a, sh_i;
   yf_quantize_multiplier((double)(float)(s_in * alpha / s_out), &m_a, &sh_a);
   yf_quantize_multiplier((double)(float)(s_in / s_out), &m_i, &sh_i);
   for (int q = -128; q < 128; ++q) {
-    const int32_t v = q - t_zp(t_in);
+    const int32_t v = q - t_zp(m, t_in);
     const int32_t u = v >= 0 ? yf_mbqm_form(v, m_i, sh_i, form) : yf_mbqm_form(v, m_a, sh_a, form);
-    lut[q + 128] = (uint8_t)sat8(t_zp(t_out) + u);
+    lut[q + 128] = (uint8_t)sat8(t_zp(m, t_out) + u);
   }
 }
 
 /* TFLite int8->int8 QUANTIZE (requantize) as a table. */
-static void build_requant_lut(int t_in, int t_out, uint8_t* lut, int form) {
-  int32_t m; int sh;
-  yf_quantize_multiplier((double)t_scale(t_in) / (double)t_scale(t_out), &m, &sh);
+static void build_requant_lut(const yf_model* m, int t_in, int t_out, uint8_t* lut, int form) {
+  int32_t mq; int sh;
+  yf_quantize_multiplier((double)t_scale(m, t_in) / (double)t_scale(m, t_out), &mq, &sh);
   for (int q = -128; q < 128; ++q)
-    lut[q + 128] = (uint8_t)sat8(yf_mbqm_form(q - t_zp(t_in), m, sh, form) + t_zp(t_out));
+    lut[q + 128] = (uint8_t)sat8(yf_mbqm_form(q - t_zp(m, t_in), mq, sh, form) + t_zp(m, t_out));
 }
 
 /* ---- per-channel requantisation constants (device form: yf_tables.h, yf_pass) -------------------------------- */
@@ -143,29 +154,29 @@ static int build_chan_fp32(float s_in, float s_w, float s_out, long long bias2, 
 }
 
 /* Channel j of pass p.  abs_w = sum |w| (bounds the accumulator).  Returns 0 or an error code. */
-static int build_chan(const yf_conv_desc* d, const uint8_t* blob, int ch, int32_t sum_w, int32_t abs_w, yf_pass* p, int j, int form, int fold) {
-  const float s_in = t_scale(d->t_in), s_out = t_scale(d->t_out);
-  const float s_w = f32_from_bits(d->wscale_bits[ch]);
+static int build_chan(const yf_model* m, const yf_conv_desc* d, const uint8_t* blob, int ch, int32_t sum_w, int32_t abs_w, yf_pass* p, int j, int form, int fold) {
+  const float s_in = t_scale(m, d->t_in), s_out = t_scale(m, d->t_out);
+  const float s_w = f32_from_bits(m->wscale[d - yf_convs].bits[ch]);
   if (form == RQ_FP32) {
     int32_t bias;
     memcpy(&bias, blob + d->b_off + 4 * (size_t)ch, 4);
-    const long long bias2 = (long long)bias - (long long)t_zp(d->t_in) * sum_w;
+    const long long bias2 = (long long)bias - (long long)t_zp(m, d->t_in) * sum_w;
     const long long acc_max = (bias2 < 0 ? -bias2 : bias2) + 255ll * abs_w;
     if (acc_max >= (1ll << 29)) return YF_PREP_ERR_SHIFT_RANGE;
-    return build_chan_fp32(s_in, s_w, s_out, bias2, acc_max, t_zp(d->t_out) + 128, p, j);
+    return build_chan_fp32(s_in, s_w, s_out, bias2, acc_max, t_zp(m, d->t_out) + 128, p, j);
   }
-  int32_t m; int sh;
-  yf_quantize_multiplier((double)s_in * (double)s_w / (double)s_out, &m, &sh);
+  int32_t mq; int sh;
+  yf_quantize_multiplier((double)s_in * (double)s_w / (double)s_out, &mq, &sh);
   if (sh > -1 || sh < -20) return YF_PREP_ERR_SHIFT_RANGE;      /* fused epilogue needs 1 <= rshift <= 20 */
-  if (m <= (1 << 30)) return YF_PREP_ERR_SHIFT_RANGE;           /* normalised multiplier (frexp) is > 2^30 unless exact pow2 */
+  if (mq <= (1 << 30)) return YF_PREP_ERR_SHIFT_RANGE;           /* normalised multiplier (frexp) is > 2^30 unless exact pow2 */
   int32_t bias;
   memcpy(&bias, blob + d->b_off + 4 * (size_t)ch, 4);
   const int rs = -sh;
-  const long long bias2 = (long long)bias - (long long)t_zp(d->t_in) * sum_w;
+  const long long bias2 = (long long)bias - (long long)t_zp(m, d->t_in) * sum_w;
   /* O + sum w*x_raw must stay a positive 32-bit multiplicand and the true accumulator below 2^29 in magnitude */
   if ((bias2 < 0 ? -bias2 : bias2) + 255ll * abs_w >= (1ll << 29)) return YF_PREP_ERR_SHIFT_RANGE;
-  p->mult2[j] = (uint32_t)m << 1;
-  build_c64(bias2 - (long long)YF_ACC_OFFSET, m, rs, form, t_zp(d->t_out) + 128, p->c64[j], &p->zr[j], fold);
+  p->mult2[j] = (uint32_t)mq << 1;
+  build_c64(bias2 - (long long)YF_ACC_OFFSET, mq, rs, form, t_zp(m, d->t_out) + 128, p->c64[j], &p->zr[j], fold);
   p->rshift[j] = rs;
   return 0;
 }
@@ -227,6 +238,12 @@ int yf_prepare_tables(const uint8_t* weights_blob, size_t blob_bytes, uint8_t** 
 }
 
 int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, int rounding, uint8_t** out_blob, yf_table_index* ix) {
+  return yf_prepare_tables_model(&k_default_model, weights_blob, blob_bytes, rounding, out_blob, ix);
+}
+
+int yf_prepare_tables_model(const yf_model* m, const uint8_t* weights_blob, size_t blob_bytes, int rounding, uint8_t** out_blob, yf_table_index* ix) {
+  if (!m || !m->scale_bits || !m->zero_point || m->n_tensors != YF_N_TENSORS || !m->wscale || m->n_convs != YF_N_CONVS) return YF_PREP_ERR_ARGS;
+  for (int i = 0; i < YF_N_CONVS; ++i) if (!m->wscale[i].bits || m->wscale[i].count != yf_convs[i].cout) return YF_PREP_ERR_ARGS;
   if (!weights_blob || blob_bytes < YF_WEIGHTS_BLOB_BYTES || !out_blob || !ix) return YF_PREP_ERR_ARGS;
   const int generic = (rounding & YF_ROUND_GENERIC_KERNELS) != 0;      /* constants for the four-instruction kernels (any rounding) instead of the sign-free dense form */
   const int fp32 = rounding == YF_ROUND_FP32;                          /* float32 epilogue on every conv (no "+generic": no integer kernel computes it) */
@@ -273,7 +290,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
       } else {
         memcpy(row, w + (size_t)ch * kk, (size_t)kk);
       }
-      rc = build_chan(d, weights_blob, ch, sum_w, abs_w, (yf_pass*)(b.p + o->c_off) + ch / 4, ch & 3, fd, fold);
+      rc = build_chan(m, d, weights_blob, ch, sum_w, abs_w, (yf_pass*)(b.p + o->c_off) + ch / 4, ch & 3, fd, fold);
       if (rc) break;
     }
   }
@@ -285,7 +302,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
     yf_dw* o = &ix->dw[s];
     o->c = d->cout; o->ngroups = (uint16_t)((d->cout + 3) / 4);
     o->g_off = (uint32_t)blob_alloc(&b, (size_t)o->ngroups * YF_DW_GROUP_BYTES);
-    ix->halo_zp[s] = t_zp(d->t_in);
+    ix->halo_zp[s] = t_zp(m, d->t_in);
     const int8_t* w = (const int8_t*)weights_blob + d->w_off;                      /* 1HWC */
     for (int g = 0; g < o->ngroups; ++g) {
       uint32_t* wd = (uint32_t*)(b.p + o->g_off + (size_t)g * YF_DW_GROUP_BYTES);  /* [9 taps][4 lanes] */
@@ -303,7 +320,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
           sum_w += wv; abs_w += wv < 0 ? -wv : wv;
           wd[t * 4 + j] = ((uint32_t)(uint8_t)wv) << (8 * j);      /* byte j of the tap's dword carries channel j */
         }
-        rc = build_chan(d, weights_blob, ch, sum_w, abs_w, cc, j, fw, 0);
+        rc = build_chan(m, d, weights_blob, ch, sum_w, abs_w, cc, j, fw, 0);
         if (rc) break;
       }
       if (rc) break;
@@ -313,7 +330,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
   /* ---------------- residual adds ---------------- */
   static const int add_t[YF_N_ADD][3] = {{62, 67, 68}, {78, 83, 84}, {84, 89, 90}};   /* tfl tensors in1,in2,out */
   for (int s = 0; s < YF_N_ADD && !rc; ++s) {
-    const float s1 = t_scale(add_t[s][0]), s2 = t_scale(add_t[s][1]), so = t_scale(add_t[s][2]);
+    const float s1 = t_scale(m, add_t[s][0]), s2 = t_scale(m, add_t[s][1]), so = t_scale(m, add_t[s][2]);
     const double twice_max = (double)(2 * (s1 > s2 ? s1 : s2));
     yf_add* a = &ix->add[s];
     int sh;
@@ -321,7 +338,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
     yf_quantize_multiplier((double)s2 / twice_max, &a->m2, &sh); a->s2 = sh;
     yf_quantize_multiplier(twice_max / (double)((float)(1 << 20) * so), &a->mo, &sh); a->so = sh;
     if (a->s1 > 0 || a->s2 > 0 || a->so > -1 || a->so < -30 || a->mo <= (1 << 30)) rc = YF_PREP_ERR_SHIFT_RANGE;
-    a->zp1 = t_zp(add_t[s][0]); a->zp2 = t_zp(add_t[s][1]); a->zpo = t_zp(add_t[s][2]);
+    a->zp1 = t_zp(m, add_t[s][0]); a->zp2 = t_zp(m, add_t[s][1]); a->zpo = t_zp(m, add_t[s][2]);
     a->rso = -a->so;
     a->kco = ((int32_t)1 << (a->rso - 1)) + a->zpo * ((int32_t)1 << a->rso);
     if (!rc && a->rso > 20) rc = YF_PREP_ERR_SHIFT_RANGE;
@@ -348,16 +365,16 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
       {YF_L_LEAKY39, 87, 88}, {YF_L_LEAKY48, 94, 95}, {YF_L_LEAKY50, 96, 97}, {YF_L_LEAKY52, 98, 99},
     };
     for (unsigned i = 0; i < sizeof leaky / sizeof leaky[0]; ++i)
-      build_leaky_lut(leaky[i][1], leaky[i][2], L + 256 * leaky[i][0], fo);
+      build_leaky_lut(m, leaky[i][1], leaky[i][2], L + 256 * leaky[i][0], fo);
     /* the two pool LUTs are RAW-indexed (index = the int8 bit pattern, not q + 128): the pooling code extracts bytes
      * straight out of its packed maxima */
     uint8_t q21[256], q45[256];
-    build_requant_lut(58, 103, q21, fo);                         /* QUANTIZE #21: pool_8 branch of concat_22 */
-    build_requant_lut(74, 101, q45, fo);                         /* QUANTIZE #45: pool_25 branch of concat_46 */
+    build_requant_lut(m, 58, 103, q21, fo);                         /* QUANTIZE #21: pool_8 branch of concat_22 */
+    build_requant_lut(m, 74, 101, q45, fo);                         /* QUANTIZE #45: pool_25 branch of concat_46 */
     for (int i = 0; i < 256; ++i) { L[256 * YF_L_Q21 + i] = q21[i ^ 128]; L[256 * YF_L_Q45 + i] = q45[i ^ 128]; }
     uint8_t l43[256], q44[256];
-    build_leaky_lut(91, 92, l43, fo);                            /* LEAKY_RELU #43 */
-    build_requant_lut(92, 102, q44, fo);                         /* QUANTIZE #44 */
+    build_leaky_lut(m, 91, 92, l43, fo);                            /* LEAKY_RELU #43 */
+    build_requant_lut(m, 92, 102, q44, fo);                         /* QUANTIZE #44 */
     for (int i = 0; i < 256; ++i) L[256 * YF_L_L43Q44 + i] = q44[(int)(int8_t)l43[i] + 128];
     memcpy(L + YF_N_LUT * 256 + YF_ADDLUT_BYTES, l43, 256);   /* LEAKY_RELU #43 alone: the debug builds' per-node dump (tensor 92 is never materialised otherwise) */
   }
@@ -405,7 +422,7 @@ int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, i
     ix->cs_s_off[cs] = (uint32_t)off;
   }
 
-  ix->in_zp = t_zp(0);
+  ix->in_zp = t_zp(m, 0);
   if (rc) { free(b.p); *out_blob = NULL; return rc; }
   blob_alloc(&b, 64);                       /* zeroed tail so 16-byte reads past the last row stay in bounds */
   ix->total_bytes = (uint32_t)b.size;

@@ -25,6 +25,23 @@ enum { YF_ROUND_TFLITE_REF = 0, YF_ROUND_TIES_UP = 1, YF_ROUND_TIES_UP_ALL = 2, 
  * yf_prepare_tables = rounding YF_ROUND_TFLITE_REF; every rounding gives a blob of the SAME layout (only constants differ). */
 int yf_prepare_tables(const uint8_t* weights_blob, size_t blob_bytes, uint8_t** out_blob, yf_table_index* ix);
 int yf_prepare_tables_rounding(const uint8_t* weights_blob, size_t blob_bytes, int rounding, uint8_t** out_blob, yf_table_index* ix);
+/* The quantisation of one model of this graph: what the table builder reads besides the weight blob.  scale_bits / zero_point are indexed by tflite
+ * tensor id (n_tensors = 104); wscale[i] are the per-channel filter scales of convolution i in the order of yf_convs[] (gen/yf_model_gen.h),
+ * count = its output channels (n_convs = 24).  Everything is borrowed: the pointers must outlive the call. */
+typedef struct { const uint32_t* bits; int count; } yf_wscale;
+typedef struct {
+  const uint32_t* scale_bits;       /* float32 bit patterns */
+  const int16_t*  zero_point;
+  int             n_tensors;
+  const yf_wscale* wscale;
+  int             n_convs;
+} yf_model;
+/* the shipped model's (gen/yf_model_gen.h): what yf_prepare_tables and yf_prepare_tables_rounding pass */
+const yf_model* yf_default_model(void);
+/* The same builder on any model's numbers (yf_network_init_model: yf_model_file.c parses them out of a .yfm image; the blob is then the model's
+ * weights and biases in the ST layout).  The admission checks are the same -- 1 <= rshift <= 20, multiplier > 2^30, |accumulator| < 2^29, and
+ * |acc| * fs < 2^21 under YF_ROUND_FP32 -- and a model that fails one is refused with YF_PREP_ERR_SHIFT_RANGE. */
+int yf_prepare_tables_model(const yf_model* m, const uint8_t* weights_blob, size_t blob_bytes, int rounding, uint8_t** out_blob, yf_table_index* ix);
 /* `rounding` may carry YF_ROUND_GENERIC_KERNELS.  Without it the dense stages of a rounding that has no sign term get the FOLDED constants of the three-instruction
  * epilogue (ZR inside C64), and the engine must launch the kernels built for them: */
 int yf_rounding_signless_dense(int rounding);

@@ -476,31 +476,62 @@ long decode_f32(const void* d_logits, const yf_image* d_images, const int32_t* d
   return launched("decode_f32 kernel launch", n);
 }
 
-// The decode tables (2 KB of __constant__ in this library's code object), uploaded once per device on first use.
+// The decode tables: 2 KB of __constant__ in this library's code object, one copy per device.  Every int8 decode first makes sure that copy is the
+// pair it has to decode with -- the network's own (yf_network_decode_tables: a model file may bring another output quantisation) when the entry
+// point takes a network, else the pair last given to yf_images_set_decode_tables (at first the shipped one) -- by comparing ids, and uploads when
+// they differ.  The upload is synchronous (the first one on a device as every later one, which also waits for the device: a decode in flight
+// reads the old pair to its end) and is refused inside stream capture.
 std::mutex g_tables_mu;
 bool g_tables_on[64];
+uint64_t g_tables_id[64];
+int g_q_thr160[64];                              // decode160's quantised confidence threshold under the pair on the device
+uint32_t g_set_sig[256], g_set_exp[256];         // yf_images_set_decode_tables
+uint64_t g_set_id;
+bool g_set_valid;
 
-bool tables_ready(hipStream_t s) {
+// FNV-1a over sigmoid then exp: the id yf_network_decode_tables gives for the same contents
+uint64_t tables_id(const uint32_t* sig, const uint32_t* ex) {
+  uint64_t h = 1469598103934665603ull;
+  for (int i = 0; i < 2048; ++i) { h ^= reinterpret_cast<const uint8_t*>(i < 1024 ? sig : ex)[i & 1023]; h *= 1099511628211ull; }
+  return h;
+}
+
+bool tables_ready(ai_handle net, hipStream_t s, int* q_thr160 = nullptr) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return fail_hip("hipGetDevice", e);
   if (dev < 0 || dev >= 64) return fail("device index out of range");
   std::lock_guard<std::mutex> lk(g_tables_mu);
-  if (g_tables_on[dev]) return true;
-  if (!yfi_d160_monotonic(yf_sigmoid_bits)) return fail("sigmoid table is not monotonic");     // decode160 compares quantised confidences
+  if (!g_set_valid) {                            // the shipped pair (gen/yf_decode_tables_gen.h); its id as yf_network_decode_tables computes it
+    memcpy(g_set_sig, yf_sigmoid_bits, sizeof g_set_sig); memcpy(g_set_exp, yf_exp_bits, sizeof g_set_exp);
+    g_set_id = tables_id(g_set_sig, g_set_exp); g_set_valid = true;
+  }
+  uint64_t want = g_set_id;
+  if (net && yf_network_decode_tables(net, nullptr, nullptr, &want) != 0) return network_failed(net, "yf_network_decode_tables");
+  if (g_tables_on[dev] && g_tables_id[dev] == want) { if (q_thr160) *q_thr160 = g_q_thr160[dev]; return true; }
+  uint32_t sig[256], ex[256];
+  if (net) { if (yf_network_decode_tables(net, sig, ex, &want) != 0) return network_failed(net, "yf_network_decode_tables"); }
+  else { memcpy(sig, g_set_sig, sizeof sig); memcpy(ex, g_set_exp, sizeof ex); }
+  if (!yfi_d160_monotonic(sig)) return fail("sigmoid table is not monotonic");     // decode160 compares quantised confidences
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail("the first per-image-scale decode on a device uploads its tables: make one call outside stream capture first");
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_sig_bits), yf_sigmoid_bits, sizeof yf_sigmoid_bits)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(sigmoid)", e);
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_exp_bits), yf_exp_bits, sizeof yf_exp_bits)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(exp)", e);
+    return fail("a decode whose tables are not on the device yet uploads them: make one call outside stream capture first");
+  if (g_tables_on[dev] && (e = hipDeviceSynchronize()) != hipSuccess) return fail_hip("hipDeviceSynchronize", e);
+  g_tables_on[dev] = false;
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_sig_bits), sig, sizeof sig)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(sigmoid)", e);
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(yfdec::d_exp_bits), ex, sizeof ex)) != hipSuccess) return fail_hip("hipMemcpyToSymbol(exp)", e);
   g_tables_on[dev] = true;
+  g_tables_id[dev] = want;
+  g_q_thr160[dev] = yfi_d160_q_threshold(sig);
+  if (q_thr160) *q_thr160 = g_q_thr160[dev];
   return true;
 }
 
-long decode_ragged(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int mode, void* d_dets, void* d_counts,
+// net: the network whose tables decode (nullptr: the pair of yf_images_set_decode_tables)
+long decode_ragged(ai_handle net, const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int mode, void* d_dets, void* d_counts,
                    int cap, hipStream_t s) {
   if (n == 0) return 0;
-  if (!tables_ready(s)) return 0;
+  if (!tables_ready(net, s)) return 0;
   const long groups = (n + 3) / 4;
   hipLaunchKernelGGL(decode_ragged_kernel, dim3((unsigned)(groups < 65536 ? groups : 65536)), dim3(kThreads), 0, s,
                      (const int8_t*)d_heads, d_images, d_status, n, mode, (yf_det*)d_dets, (int*)d_counts, cap);
@@ -508,11 +539,11 @@ long decode_ragged(const void* d_heads, const yf_image* d_images, const int32_t*
 }
 
 // d_images == nullptr: the scalar scales; else per-image scales (and d_status, which may be nullptr)
-long decode160(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, float w_scale, float h_scale, void* d_dets,
+long decode160(ai_handle net, const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, float w_scale, float h_scale, void* d_dets,
                void* d_counts, int cap, hipStream_t s) {
   if (n == 0) return 0;
-  if (!tables_ready(s)) return 0;
-  const int q_thr = yfi_d160_q_threshold(yf_sigmoid_bits);
+  int q_thr = 128;
+  if (!tables_ready(net, s, &q_thr)) return 0;
   const dim3 grid = grid_for(n, 8), block(yfwide::kThreads);                      // 9.2 KB of LDS per workgroup
   if (d_images)
     hipLaunchKernelGGL(yfwide::decode160_kernel<true>, grid, block, 0, s, (const int8_t*)d_heads, d_images, d_status, n, 0.f, 0.f, q_thr,
@@ -529,11 +560,11 @@ long run_decode56(ai_handle net, int format, const PrepArgs& a, void* d_heads, i
   const bool ragged = a.imgs != nullptr;
   if (!check_decode(d_heads, mode, d_dets, d_counts, cap)) return 0;
   if (a.n == 0) return 0;
-  if (ragged && !tables_ready((hipStream_t)stream)) return 0;
+  if (ragged && !tables_ready(net, (hipStream_t)stream)) return 0;
   if (prepare(56, format, a, (hipStream_t)stream) != a.n) return 0;
   if (ragged) {
     if (yf_network_run_device(net, a.frames, d_heads, a.n, stream) != a.n) return network_failed(net, "yf_network_run_device");
-    return decode_ragged(d_heads, a.imgs, a.status, a.n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+    return decode_ragged(net, d_heads, a.imgs, a.status, a.n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
   }
   const float w_scale = (float)((double)a.w / 56.0), h_scale = (float)((double)a.h / 56.0);
   if (yf_network_run_decode_device(net, a.frames, d_heads, a.n, mode, w_scale, h_scale, d_dets, d_counts, cap, stream) != a.n)
@@ -545,11 +576,11 @@ long run_decode56(ai_handle net, int format, const PrepArgs& a, void* d_heads, i
 long run_decode160(ai_handle net, int format, const PrepArgs& a, void* d_heads, void* d_dets, void* d_counts, int cap, void* stream) {
   if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
   if (a.n == 0) return 0;
-  if (!tables_ready((hipStream_t)stream)) return 0;
+  if (!tables_ready(net, (hipStream_t)stream)) return 0;
   if (prepare(160, format, a, (hipStream_t)stream) != a.n) return 0;
   if (yf_network_run_device_hw(net, 160, 160, a.frames, d_heads, a.n, stream) != a.n) return network_failed(net, "yf_network_run_device_hw");
   const float w_scale = (float)((double)a.w / 160.0), h_scale = (float)((double)a.h / 160.0);
-  return decode160(d_heads, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+  return decode160(net, d_heads, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 // fp16 network: images -> fp16 frames -> float32 logits -> records; the scalar scales count in a uniform batch only.  Nothing is launched
@@ -603,18 +634,27 @@ YF_API long yf_images_run_decode_ragged_device(ai_handle net, const void* d_pixe
   return run_decode56(net, format, a, d_heads, mode, d_dets, d_counts, cap, stream);
 }
 
+YF_API int yf_images_set_decode_tables(const uint32_t sig_bits[256], const uint32_t exp_bits[256], uint64_t id) {
+  if (!sig_bits || !exp_bits) { fail("sig_bits or exp_bits is NULL"); return -1; }
+  if (!yfi_d160_monotonic(sig_bits)) { fail("sigmoid table is not monotonic"); return -1; }
+  std::lock_guard<std::mutex> lk(g_tables_mu);
+  memcpy(g_set_sig, sig_bits, sizeof g_set_sig); memcpy(g_set_exp, exp_bits, sizeof g_set_exp);
+  g_set_id = id; g_set_valid = true;
+  return 0;
+}
+
 YF_API long yf_images_decode_ragged_device(const void* d_heads, const yf_image* d_images, long n, int mode, void* d_dets, void* d_counts,
                                            int cap, void* stream) {
   if (n < 0) return fail("n < 0");
   if (!check_decode(d_heads, mode, d_dets, d_counts, cap) || !check_descriptors(d_images, n)) return 0;
-  return decode_ragged(d_heads, d_images, nullptr, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
+  return decode_ragged(nullptr, d_heads, d_images, nullptr, n, mode, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 YF_API long yf_images_decode160_device(const void* d_heads, long n, float w_scale, float h_scale, void* d_dets, void* d_counts, int cap,
                                        void* stream) {
   if (n < 0) return fail("n < 0");
   if (!check_decode160(d_heads, d_dets, d_counts, cap)) return 0;
-  return decode160(d_heads, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
+  return decode160(nullptr, d_heads, nullptr, nullptr, n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 YF_API long yf_images_decode160_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, void* d_dets,
@@ -622,7 +662,7 @@ YF_API long yf_images_decode160_ragged_device(const void* d_heads, const yf_imag
   if (n < 0) return fail("n < 0");
   if (!check_decode160(d_heads, d_dets, d_counts, cap) || !check_descriptors(d_images, n)) return 0;
   if (((uintptr_t)d_status & 3) != 0) return fail("d_status is not 4-byte aligned");
-  return decode160(d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
+  return decode160(nullptr, d_heads, d_images, d_status, n, 0.f, 0.f, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
 YF_API long yf_images_run_decode160_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,

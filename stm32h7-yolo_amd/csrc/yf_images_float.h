@@ -32,6 +32,7 @@
 #include <string.h>
 #include "../../include/yf_images.h"
 #include "yf_images_decode160.h"
+#include "yf_exp_f32.h"                    /* E and the sigmoid built on it: yfi_exp_f32, yfi_sigmoid_f32 */
 
 #define YFI_F32_CAND 147                   /* 3 anchors x 7 x 7 */
 #define YFI_F32_LOGITS (7 * 7 * 18)        /* float32 values per frame */
@@ -47,56 +48,6 @@ YFI_HD uint16_t yfi_f16_of_u8(int v) {
   const uint32_t rem = u & 0x1FFFu;
   if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;
   return (uint16_t)h;
-}
-
-YFI_HD double yfi_f64_of_bits(uint64_t u) {
-  double d;
-  memcpy(&d, &u, 8);
-  return d;
-}
-
-/* E(x): the float32 nearest to the float64 value of e^x */
-YFI_HD float yfi_exp_f32(float xf) {
-#ifdef __clang__
-#pragma clang fp contract(off)
-#endif
-  if (xf != xf) return xf;
-  if (xf > 89.0f) return yfi_d160_bits(0x7F800000u);          /* e^89 > 2^128: +inf (and +inf itself) */
-  if (xf < -104.0f) return 0.0f;                               /* e^-104 < 2^-150: 0 (and -inf itself) */
-  const double x = (double)xf;
-  /* k = the integer nearest to x / ln 2 (|k| <= 151); r = x - k ln 2 in two parts, |r| <= 0.3466 + rounding.  LN2_HI has 32 significant
-   * bits, so k * LN2_HI is exact */
-  const double t = x * 1.44269504088896338700e+00;
-  const int k = (int)(t + (t < 0.0 ? -0.5 : 0.5));
-  const double kd = (double)k;
-  const double r = (x - kd * 6.93147180369123816490e-01) - kd * 1.90821492927058770002e-10;
-  /* e^r = sum r^j / j!, j <= 13: the first term left out is below 5e-18 */
-  double p = 1.0 / 6227020800.0;
-  p = p * r + 1.0 / 479001600.0;
-  p = p * r + 1.0 / 39916800.0;
-  p = p * r + 1.0 / 3628800.0;
-  p = p * r + 1.0 / 362880.0;
-  p = p * r + 1.0 / 40320.0;
-  p = p * r + 1.0 / 5040.0;
-  p = p * r + 1.0 / 720.0;
-  p = p * r + 1.0 / 120.0;
-  p = p * r + 1.0 / 24.0;
-  p = p * r + 1.0 / 6.0;
-  p = p * r + 0.5;
-  p = p * r + 1.0;
-  p = p * r + 1.0;
-  double y = p * yfi_f64_of_bits((uint64_t)(k + 1023) << 52);  /* 2^k, a normal double: exact scaling */
-  /* below 2^-126 the float32 is subnormal, a multiple of 2^-149: round y to one here (adding 1.5 x 2^-97 leaves a double whose last
-   * place is 2^-149, ties to even), so that the conversion below is exact whatever the converting instruction does with subnormals */
-  if (y < 0x1p-126) y = (y + 0x1.8p-97) - 0x1.8p-97;
-  return (float)y;
-}
-
-YFI_HD float yfi_sigmoid_f32(float x) {
-#ifdef __clang__
-#pragma clang fp contract(off)
-#endif
-  return 1.0f / (1.0f + yfi_exp_f32(-x));
 }
 
 /* index in a frame's logits of candidate i's six values (x, y, w, h, conf, class) */

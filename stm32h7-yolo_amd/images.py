@@ -140,6 +140,8 @@ def load():
         fn.restype, fn.argtypes = ctypes.c_long, argtypes
     lib.yf_images_last_error_text.restype = ctypes.c_char_p
     lib.yf_images_last_error_text.argtypes = []
+    lib.yf_images_set_decode_tables.restype = ctypes.c_int
+    lib.yf_images_set_decode_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     _lib = lib
     return lib
 
@@ -192,6 +194,14 @@ def _call(name, n, *args):
     rc = getattr(lib, "yf_images_" + name)(*args)
     if rc != n:
         raise ImagesError(f"yf_images_{name}: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc}, expected {n})")
+
+
+def set_decode_tables(sig, ex, ident):
+    """The tables the decodes that take no network use from now on (yf_images_set_decode_tables): what `network.decode_tables()` returned."""
+    lib = load()
+    sig, ex = np.ascontiguousarray(sig, np.float32), np.ascontiguousarray(ex, np.float32)
+    if sig.size != 256 or ex.size != 256 or lib.yf_images_set_decode_tables(sig.ctypes.data, ex.ctypes.data, int(ident)) != 0:
+        raise ImagesError(f"yf_images_set_decode_tables: {(lib.yf_images_last_error_text() or b'').decode() or 'two tables of 256 float32'}")
 
 
 def prepare_device(d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, out_hw, d_frames, stream=None):
@@ -325,6 +335,8 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
     if f16:
         run = run_decode_f16_ragged_device
+    else:
+        set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
     run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
         d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
     if iou_threshold is not None:

@@ -19,6 +19,17 @@ ANCHORS = np.array([[9, 14], [12, 17], [22, 21]], dtype=np.float32)   # tflite_p
 _TABLES = None
 
 
+def model_decode_tables(scale, zero_point):
+    """(sigmoid, exp) float32[256] for an output tensor of that scale and zero point: the shipped tables for the shipped parameters (they are the
+    contract), else what yf_network_init_model builds -- x = fl32(fl32(q - zp) * s), 1 / (1 + E(-x)), E(x) with E the correctly rounded float32
+    exponential, here float64 exp rounded once (equal unless the float64 value falls within its own error of a float32 tie)."""
+    if np.float32(scale) == np.float32(OUTPUT_SCALE) and int(zero_point) == OUTPUT_ZERO_POINT:
+        return decode_tables()
+    x = ((np.arange(-128, 128) - int(zero_point)).astype(np.float32) * np.float32(scale)).astype(np.float32)
+    E = lambda v: np.exp(v.astype(np.float64)).astype(np.float32)      # noqa: E731
+    return (np.float32(1) / (np.float32(1) + E(-x))).astype(np.float32), E(x)
+
+
 def decode_tables():
     """(sigmoid, exp) float32[256] indexed by q+128; baked in the library as gen/yf_decode_tables_gen.h."""
     global _TABLES
@@ -47,9 +58,23 @@ class Interpreter:
     # The XNNPACK delegate's float32 requantisation, which AUTO / BUILTIN may apply, has no resolver name of its own: requant_rounding=YF_ROUND_FP32 selects it.
     _RESOLVER_ROUNDING = {"AUTO": None, "BUILTIN_REF": 0, "BUILTIN": 1, "BUILTIN_WITHOUT_DEFAULT_DELEGATES": 1}
 
-    def __init__(self, model_path="yoloface_int8.tflite", device=0, experimental_op_resolver_type="AUTO", requant_rounding=None, **_ignored):
-        # the model is baked into the library; model_path is accepted for call-site compatibility
+    def __init__(self, model_path="yoloface_int8.tflite", device=0, experimental_op_resolver_type="AUTO", requant_rounding=None, model_content=None,
+                 **_ignored):
+        # A model_path that names an existing .tflite or .yfm file, or model_content (the bytes of either), is loaded (yf_network_init_model);
+        # a path that does not exist -- the reference's call site passes a bare file name -- means the model baked into the library.
         self.model_path = model_path
+        self._yfm = None
+        self._quant = ((INPUT_SCALE, INPUT_ZERO_POINT), (OUTPUT_SCALE, OUTPUT_ZERO_POINT))      # of the input and the output tensor
+        content = model_content
+        if content is None and model_path and os.path.isfile(model_path):
+            with open(model_path, "rb") as f:
+                content = f.read()
+        if content is not None:
+            from . import model_file
+            content = bytes(content)
+            self._yfm = content if content[:4] == b"YFM1" else model_file.tflite_to_yfm(content)
+            m = model_file.load_yfm(self._yfm)
+            self._quant = tuple((float(m["tensors"][t]["scale"][0]), int(m["tensors"][t]["zp"])) for t in (m["input"], m["output"]))
         self._net = Network(device=device)
         name = getattr(experimental_op_resolver_type, "name", experimental_op_resolver_type)      # an enum member or its name
         if name not in self._RESOLVER_ROUNDING:
@@ -62,18 +87,21 @@ class Interpreter:
         self._allocated = False
 
     def allocate_tensors(self):
-        self._net.init()
+        if self._yfm is not None:
+            self._net.init_model(self._yfm)
+        else:
+            self._net.init()
         self._in = np.zeros((1, IN_H, IN_W, IN_C), np.int8)
         self._out = np.zeros((1, OUT_H, OUT_W, OUT_C), np.int8)
         self._allocated = True
 
     def get_input_details(self):
         return [dict(name="Input", index=0, shape=np.array([1, IN_H, IN_W, IN_C], np.int32), dtype=np.int8,
-                     quantization=(INPUT_SCALE, INPUT_ZERO_POINT))]
+                     quantization=self._quant[0])]
 
     def get_output_details(self):
         return [dict(name="Identity", index=100, shape=np.array([1, OUT_H, OUT_W, OUT_C], np.int32), dtype=np.int8,
-                     quantization=(OUTPUT_SCALE, OUTPUT_ZERO_POINT))]
+                     quantization=self._quant[1])]
 
     def resize_tensor_input(self, index, shape):
         """Batch dimension only (the engine runs any number of frames per invoke)."""
@@ -100,9 +128,10 @@ class Interpreter:
         return self._out.copy()
 
 
-def decode_boxes(head, conf_thres=0.7, w_scale=1.0, h_scale=1.0):
-    """tflite_prediction.py:42-63 for one int8 head [7,7,18]: int32 boxes [k,4] in (a,row,col) order."""
-    sig, ex = decode_tables()
+def decode_boxes(head, conf_thres=0.7, w_scale=1.0, h_scale=1.0, output_scale=OUTPUT_SCALE, output_zero_point=OUTPUT_ZERO_POINT):
+    """tflite_prediction.py:42-63 for one int8 head [7,7,18]: int32 boxes [k,4] in (a,row,col) order.  output_scale, output_zero_point: the
+    output tensor's quantisation (get_output_details), the shipped model's by default."""
+    sig, ex = model_decode_tables(output_scale, output_zero_point)
     idx = np.asarray(head, np.int8).astype(np.int32) + 128
     nx, ny = idx.shape[0], idx.shape[1]
     idx = idx.reshape((nx, ny, 3, 6)).transpose([2, 0, 1, 3])

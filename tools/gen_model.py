@@ -10,18 +10,13 @@ Reads (never copies source text from) /root/reference:
 Writes:
   oracle/model/yoloface_int8.yfm                 generic op-by-op model pack for the CPU oracle
   stm32h7-yolo_amd/csrc/gen/yf_model_gen.h       baked quant tables + blob offsets for the product
+  stm32h7-yolo_amd/csrc/gen/yf_graph_gen.h       the graph a model file must have (yf_network_init_model)
   stm32h7-yolo_amd/csrc/gen/yf_weights_blob_gen.c the 11304-byte weight blob in the ST layout
   stm32h7-yolo_amd/csrc/gen/yf_decode_tables_gen.h  sigmoid/exp float32 tables for the box decode
   tests/golden/st_leaky_luts.bin                 17 x 256 int8, ST's LUTs in tflite op order (2,4,7,...)
   tests/golden/decode_tables_f32.bin             2 x 256 float32 (sigmoid, exp)
 
-.yfm layout (little endian):
-  header  : 'YFM1', u32 n_tensors, u32 n_ops, u32 input_tensor, u32 output_tensor, u32 data_bytes
-  tensor  : i32 shape[4], u32 type(0=i8,1=i32), i32 zero_point, u32 n_scales, u32 scales_off,
-            i32 quantized_dimension, u32 data_off(0xFFFFFFFF=none), u32 data_bytes           (44 B)
-  op      : u32 opcode, i32 inputs[3], i32 output, i32 padding, i32 stride_w, i32 stride_h,
-            i32 filter_w, i32 filter_h, i32 depth_multiplier, i32 axis, u32 alpha_bits           (52 B)
-  data    : scales (f32) and constant tensor bytes, each 4-byte aligned
+The .yfm layout, its writer and the .tflite reader: stm32h7-yolo_amd/model_file.py.
 """
 import os
 import re
@@ -31,8 +26,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-sys.path.insert(0, HERE)
-from tflite_reader import read_tflite  # noqa: E402
+sys.path.insert(0, ROOT)
+import importlib  # noqa: E402
+model_file = importlib.import_module("stm32h7-yolo_amd.model_file")      # the .tflite reader and the .yfm writer live in the package
+read_tflite, f32bits = model_file.read_tflite, model_file.f32bits
 
 REF = "/root/reference"
 TFL = f"{REF}/yoloface/tflite/yoloface_int8.tflite"
@@ -40,53 +37,6 @@ NETC = f"{REF}/stm32/X-CUBE-AI/App/network.c"
 NETD = f"{REF}/stm32/X-CUBE-AI/App/network_data.c"
 PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
 OUT_ROOT = ROOT        # --out-root DIR: write everything under DIR (same relative paths) instead of into the tree (tests compare the bytes)
-
-OPCODE = {"ADD": 0, "CONCATENATION": 2, "CONV_2D": 3, "DEPTHWISE_CONV_2D": 4, "MAX_POOL_2D": 17,
-          "PAD": 34, "LEAKY_RELU": 98, "QUANTIZE": 114}
-
-
-def f32bits(x):
-    return struct.unpack("<I", struct.pack("<f", float(x)))[0]
-
-
-def write_yfm(m, path):
-    data = bytearray()
-
-    def put(b):
-        while len(data) % 4:
-            data.append(0)
-        off = len(data)
-        data.extend(b)
-        return off
-
-    trecs = []
-    for t in m["tensors"]:
-        shape = (list(t["shape"]) + [1, 1, 1, 1])[:4] if len(t["shape"]) < 4 else list(t["shape"])
-        ttype = {"INT8": 0, "INT32": 1}[t["type"]]
-        zp = int(t["zero_point"][0]) if len(t["zero_point"]) else 0
-        ns = len(t["scale"])
-        soff = put(t["scale"].astype("<f4").tobytes()) if ns else 0
-        if t["data"] is not None:
-            raw = t["data"].tobytes()
-            doff, dbytes = put(raw), len(raw)
-        else:
-            doff, dbytes = 0xFFFFFFFF, 0
-        trecs.append(struct.pack("<4iIiIIiII", *shape, ttype, zp, ns, soff, t["quantized_dimension"], doff, dbytes))
-    orecs = []
-    for op in m["ops"]:
-        o = op["options"]
-        ins = (op["inputs"] + [-1, -1, -1])[:3]
-        orecs.append(struct.pack("<I3ii7iI", OPCODE[op["op"]], *ins, op["outputs"][0],
-                                 o.get("padding", 0), o.get("stride_w", 1), o.get("stride_h", 1),
-                                 o.get("filter_w", 0), o.get("filter_h", 0), o.get("depth_multiplier", 0),
-                                 o.get("axis", 0), f32bits(o.get("alpha", 0.0))))
-    while len(data) % 4:
-        data.append(0)
-    hdr = b"YFM1" + struct.pack("<5I", len(trecs), len(orecs), m["inputs"][0], m["outputs"][0], len(data))
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "wb") as f:
-        f.write(hdr + b"".join(trecs) + b"".join(orecs) + bytes(data))
-
 
 def st_offsets():
     """{ 'conv2d_N': (w_off, b_off) } from network_configure_weights (network.c:3120-3263)."""
@@ -143,7 +93,8 @@ def main():
     m = read_tflite(TFL)
     T = m["tensors"]
     os.makedirs(os.path.join(OUT_ROOT, "oracle", "model"), exist_ok=True)
-    write_yfm(m, os.path.join(OUT_ROOT, "oracle", "model", "yoloface_int8.yfm"))
+    packed = model_file.tflite_model_to_dict(m)
+    model_file.write_yfm(packed, os.path.join(OUT_ROOT, "oracle", "model", "yoloface_int8.yfm"))
 
     # ---- conv table: tflite op index -> ST c-layer id -----------------------
     convs = [(i, op) for i, op in enumerate(m["ops"]) if op["op"] in ("CONV_2D", "DEPTHWISE_CONV_2D")]
@@ -174,6 +125,10 @@ def main():
 
     gen = os.path.join(OUT_ROOT, "stm32h7-yolo_amd", "csrc", "gen")
     os.makedirs(gen, exist_ok=True)
+
+    # ---- the graph a model file must have (csrc/yf_model_file.c) ------------------------------------
+    with open(os.path.join(gen, "yf_graph_gen.h"), "w") as f:
+        f.write(model_file.graph_header(packed))
 
     # ---- weight blob as a byte array (own formatting; identical bytes) ---------------------------
     with open(os.path.join(gen, "yf_weights_blob_gen.c"), "w") as f:
