@@ -1,0 +1,266 @@
+// libyf_calib.so (include/yf_calib.h): the float32 evaluation of the network over a batch of int8 frames on gfx950, with the running extremes
+// of the 47 tensors calibration observes.  The arithmetic is csrc/yf_calib_arith.h's, compiled with -ffp-contract=off.
+//
+// One workgroup of 1024 threads per frame in flight, the frame's activations as float32 in LDS (the arena of yf_calib_arith.h, 156.8 KB of
+// the CU's 160 KB: one workgroup per CU), a grid-stride loop over the frames.  A stage's output elements are dealt to the threads round
+// robin; every thread keeps the extremes of what it computed, a wave folds them with shuffles, the waves' results meet in LDS, and the
+// workgroup carries its running extremes in LDS across its frames.  Each workgroup leaves one partial table in global memory; a second,
+// one-workgroup launch folds the partials into the handle's ranges.  Minimum and maximum are exact, so the result does not depend on which
+// workgroup saw which frame, and nothing is ordered by arrival: no atomics.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+#include <new>
+#include "../../include/yf_calib.h"
+#include "yf_calib_arith.h"
+#include "yf_yfw.h"
+
+#ifndef YF_CALIB_BUILD_ID
+#define YF_CALIB_BUILD_ID "unknown"
+#endif
+
+namespace {
+
+constexpr int kThreads = 1024, kWaves = kThreads / 64, kPerStage = 6;                // a stage observes up to three tensors: 3 x {min, max}
+constexpr int kRedFloats = 2 * kWaves * kPerStage, kWgFloats = 2 * YFC_N_RANGES;
+constexpr size_t kLdsBytes = sizeof(float) * (YFC_ARENA_FLOATS + kRedFloats + kWgFloats);
+constexpr int kParamFloats = YFC_INPUT_TABLE + YF_YFW_FLOATS;
+static_assert(kLdsBytes <= 160 * 1024, "the arena and the reduction scratch must fit the CU's LDS");
+static_assert(YFC_LOGITS_OFF + YFC_LOGITS <= YFC_ARENA_FLOATS, "logits inside the arena");
+
+__device__ inline float wave_min(float v) {
+  for (int o = 32; o; o >>= 1) { const float t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+  return v;
+}
+__device__ inline float wave_max(float v) {
+  for (int o = 32; o; o >>= 1) { const float t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+  return v;
+}
+
+// Folds the threads' extremes of one stage (mn / mx [3], slots[3] with -1 for none) into the workgroup's table.  `red` alternates between two
+// halves from one call to the next: the threads that read a half after the barrier are past the NEXT barrier before anybody writes it again.
+__device__ inline void fold(const float mn[3], const float mx[3], const int slots[3], float* red, float* wg, int& parity) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* half = red + parity * kWaves * kPerStage;
+  for (int j = 0; j < 3; ++j) {
+    if (slots[j] < 0) continue;                                                     // uniform
+    const float a = wave_min(mn[j]), b = wave_max(mx[j]);
+    if (lane == 0) { half[wave * kPerStage + 2 * j] = a; half[wave * kPerStage + 2 * j + 1] = b; }
+  }
+  __syncthreads();                                                                  // also: the stage's output is in the arena
+  const int slot = tid < 2 ? slots[0] : tid < 4 ? slots[1] : slots[2];
+  if (tid < kPerStage && slot >= 0) {
+    float v = wg[2 * slot + (tid & 1)];
+    for (int w = 0; w < kWaves; ++w) {
+      const float t = half[w * kPerStage + tid];
+      v = (tid & 1) ? (t > v ? t : v) : (t < v ? t : v);
+    }
+    wg[2 * slot + (tid & 1)] = v;
+  }
+  parity ^= 1;
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_observe_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                const yfc_stage* __restrict__ stages, float* __restrict__ logits,
+                                                                float* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* arena = lds;
+  float* red = lds + YFC_ARENA_FLOATS;
+  float* wg = red + kRedFloats;
+  const int tid = threadIdx.x;
+  const float inf = __builtin_inff();
+  if (tid < kWgFloats) wg[tid] = (tid & 1) ? -inf : inf;
+  __syncthreads();
+  int parity = 0;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    {
+      const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
+      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+      const int slots[3] = {0, -1, -1};
+      for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) {
+        const float v = params[(int)q[i] + 128];
+        arena[i] = v;
+        mn[0] = v < mn[0] ? v : mn[0];
+        mx[0] = v > mx[0] ? v : mx[0];
+      }
+      fold(mn, mx, slots, red, wg, parity);
+    }
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
+      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+        for (int j = 0; j < 3; ++j) {
+          if (slots[j] < 0) continue;
+          mn[j] = v[j] < mn[j] ? v[j] : mn[j];
+          mx[j] = v[j] > mx[j] ? v[j] : mx[j];
+        }
+      }
+      fold(mn, mx, slots, red, wg, parity);
+    }
+    // (the logits stay where they are until the next frame's third stage writes T54 over them, several barriers from here)
+    if (logits)
+      for (int i = tid; i < YFC_LOGITS; i += kThreads) logits[(size_t)f * YFC_LOGITS + i] = arena[YFC_LOGITS_OFF + i];
+  }
+  __syncthreads();
+  if (tid < kWgFloats) partials[(size_t)blockIdx.x * kWgFloats + tid] = wg[tid];
+}
+
+// ranges[t] = min / max (even / odd t) of ranges[t] and partials[0 .. parts)[t]
+__global__ __launch_bounds__(128) void yfc_merge_kernel(const float* __restrict__ partials, int parts, float* __restrict__ ranges) {
+  const int t = threadIdx.x;
+  if (t >= kWgFloats) return;
+  float v = ranges[t];
+  for (int p = 0; p < parts; ++p) {
+    const float x = partials[(size_t)p * kWgFloats + t];
+    v = (t & 1) ? (x > v ? x : v) : (x < v ? x : v);
+  }
+  ranges[t] = v;
+}
+
+thread_local char g_err[320];
+
+#define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
+
+bool hip_ok(hipError_t e, const char* what) {
+  if (e == hipSuccess) return true;
+  set_error("%s: %s", what, hipGetErrorString(e));
+  return false;
+}
+
+// the caller's current device is restored when a call ends
+struct DeviceScope {
+  int prev = -1;
+  bool ok = false;
+  explicit DeviceScope(int device) {
+    if (!hip_ok(hipGetDevice(&prev), "hipGetDevice")) { prev = -1; return; }
+    ok = prev == device || hip_ok(hipSetDevice(device), "hipSetDevice");
+    if (!ok || prev == device) prev = -1;
+  }
+  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+}  // namespace
+
+struct yf_calib {
+  int device = 0, grid_max = 0;
+  long frames = 0;
+  float* d_params = nullptr;
+  yfc_stage* d_stages = nullptr;
+  float* d_partials = nullptr;
+  float* d_ranges = nullptr;
+  int32_t tensors[YFC_N_RANGES];
+};
+
+static bool upload_empty_ranges(yf_calib* c) {
+  float init[kWgFloats];
+  for (int t = 0; t < kWgFloats; ++t) init[t] = (t & 1) ? -INFINITY : INFINITY;
+  return hip_ok(hipMemcpy(c->d_ranges, init, sizeof init, hipMemcpyHostToDevice), "hipMemcpy(ranges)");
+}
+
+extern "C" {
+
+YF_CALIB_API const char* yf_calib_last_error_text(void) { return g_err; }
+YF_CALIB_API const char* yf_calib_build_id(void) { return YF_CALIB_BUILD_ID; }
+
+YF_CALIB_API void yf_calib_destroy(yf_calib* c) {
+  if (!c) return;
+  {
+    DeviceScope scope(c->device);
+    if (scope.ok) (void)hipDeviceSynchronize();
+    (void)hipFree(c->d_params); (void)hipFree(c->d_stages); (void)hipFree(c->d_partials); (void)hipFree(c->d_ranges);
+  }
+  delete c;
+}
+
+YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device) {
+  g_err[0] = 0;
+  float* p = new (std::nothrow) float[kParamFloats];
+  if (!p) { set_error("yf_calib_create: out of memory"); return nullptr; }
+  yfc_input_table(p);
+  if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, g_err, sizeof g_err)) { delete[] p; return nullptr; }
+  yf_calib* c = new (std::nothrow) yf_calib;
+  if (!c) { delete[] p; set_error("yf_calib_create: out of memory"); return nullptr; }
+  c->device = device;
+  yfc_stage stages[YFC_N_STAGES];
+  yfc_build_stages(stages, c->tensors);
+  const yfc_stage& last = stages[YFC_N_STAGES - 1];
+  bool ok = last.b_off + last.cout == kParamFloats && last.out_off == YFC_LOGITS_OFF;
+  if (!ok) set_error("yf_calib_create: the stage table gives %d parameter floats, the graph %d", last.b_off + last.cout, kParamFloats);
+  if (ok) {
+    DeviceScope scope(device);
+    int cus = 0;
+    ok = scope.ok && hip_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "hipDeviceGetAttribute(multiprocessors)");
+    if (ok && cus < 1) { ok = false; set_error("yf_calib_create: device %d reports %d compute units", device, cus); }
+    c->grid_max = cus;                                     // 156.8 KB of LDS: one workgroup per CU
+    ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_observe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes),
+                      "hipFuncSetAttribute(max dynamic LDS)")
+         && hip_ok(hipMalloc((void**)&c->d_params, sizeof(float) * kParamFloats), "hipMalloc(params)")
+         && hip_ok(hipMalloc((void**)&c->d_stages, sizeof stages), "hipMalloc(stages)")
+         && hip_ok(hipMalloc((void**)&c->d_partials, sizeof(float) * kWgFloats * (size_t)cus), "hipMalloc(partials)")
+         && hip_ok(hipMalloc((void**)&c->d_ranges, sizeof(float) * kWgFloats), "hipMalloc(ranges)")
+         && hip_ok(hipMemcpy(c->d_params, p, sizeof(float) * kParamFloats, hipMemcpyHostToDevice), "hipMemcpy(params)")
+         && hip_ok(hipMemcpy(c->d_stages, stages, sizeof stages, hipMemcpyHostToDevice), "hipMemcpy(stages)")
+         && upload_empty_ranges(c) && hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  }
+  delete[] p;
+  if (!ok) {
+    char keep[sizeof g_err];
+    memcpy(keep, g_err, sizeof keep);
+    yf_calib_destroy(c);
+    memcpy(g_err, keep, sizeof keep);
+    return nullptr;
+  }
+  return c;
+}
+
+YF_CALIB_API long yf_calib_observe_device(yf_calib* c, const void* d_frames, long n, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c || !d_frames) { set_error("yf_calib_observe_device: NULL %s", c ? "d_frames" : "handle"); return -1; }
+  if (n < 1) { set_error("yf_calib_observe_device: n is %ld, expected at least 1", n); return -1; }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
+  hipLaunchKernelGGL(yfc_observe_kernel, dim3(grid), dim3(kThreads), kLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
+                     (const yfc_stage*)c->d_stages, (float*)d_logits, c->d_partials);
+  if (!hip_ok(hipGetLastError(), "yf_calib_observe_device: launch of the evaluation")) return -2;
+  hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, s, (const float*)c->d_partials, grid, c->d_ranges);
+  if (!hip_ok(hipGetLastError(), "yf_calib_observe_device: launch of the merge")) return -2;
+  c->frames += n;
+  return n;
+}
+
+YF_CALIB_API int yf_calib_ranges(yf_calib* c, float* minmax, int32_t* tensors) {
+  g_err[0] = 0;
+  if (!c || !minmax || !tensors) { set_error("yf_calib_ranges: NULL argument"); return -1; }
+  if (c->frames < 1) { set_error("yf_calib_ranges: no frame has been observed yet: there are no ranges"); return -1; }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -2;
+  if (!hip_ok(hipDeviceSynchronize(), "yf_calib_ranges: hipDeviceSynchronize") ||
+      !hip_ok(hipMemcpy(minmax, c->d_ranges, sizeof(float) * kWgFloats, hipMemcpyDeviceToHost), "yf_calib_ranges: hipMemcpy"))
+    return -2;
+  for (int t = 0; t < kWgFloats; ++t) minmax[t] = minmax[t] + 0.0f;                 // (a zero comes out as +0 whichever sign was met first)
+  memcpy(tensors, c->tensors, sizeof c->tensors);
+  return YFC_N_RANGES;
+}
+
+YF_CALIB_API int yf_calib_reset(yf_calib* c) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_reset: NULL handle"); return -1; }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -2;
+  if (!hip_ok(hipDeviceSynchronize(), "yf_calib_reset: hipDeviceSynchronize") || !upload_empty_ranges(c) ||
+      !hip_ok(hipDeviceSynchronize(), "yf_calib_reset: hipDeviceSynchronize"))
+    return -2;
+  c->frames = 0;
+  return 0;
+}
+
+YF_CALIB_API long yf_calib_frames_observed(const yf_calib* c) { return c ? c->frames : -1; }
+
+}  // extern "C"

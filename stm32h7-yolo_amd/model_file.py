@@ -1,4 +1,5 @@
-"""Model files of the int8 network: the .yfm pack (what yf_network_init_model and the oracle read) and the conversion from a .tflite.
+"""Model files of the int8 network: the .yfm pack (what yf_network_init_model and the oracle read), the conversion from a .tflite, and the
+.yfw pack of a float model (what yf_network_fp16_init and the calibration library read; layout at read_yfw).
 
 .yfm layout (little endian):
   header  : 'YFM1', u32 n_tensors, u32 n_ops, u32 input_tensor, u32 output_tensor, u32 data_bytes
@@ -13,6 +14,8 @@ tools/gen_model.py runs to produce oracle/model/yoloface_int8.yfm.  The .tflite 
 handful of schema tables this model uses; field slot numbers follow the public TFLite schema (tensorflow/lite/schema/schema.fbs, TF 2.10; SURVEY.md
 Appendix C lists the ones relied on).  Nothing here needs the native library or a GPU.
 """
+import os
+import re
 import struct
 
 import numpy as np
@@ -89,6 +92,84 @@ def write_yfm(model, path=None):
         with open(path, "wb") as f:
             f.write(out)
     return out
+
+
+def load_graph():
+    """The graph the library is built for (csrc/gen/yf_graph_gen.h) in the dict form of load_yfm, without numbers: every op with its wiring and
+    options; every tensor with shape, type, qdim, `n_scales` and `is_const`, zero point 0, no scale, and no data except the PAD ops' paddings."""
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "gen", "yf_graph_gen.h")).read()
+    ops_src, tensors_src = src.split("yf_graph_ops[YF_GRAPH_N_OPS] = {")[1].split("};")[0], src.split("yf_graph_tensors[")[1].split("};")[0]
+    ops = []
+    for r in re.findall(r"^\s*\{(\d+), \{(-?\d+), (-?\d+), (-?\d+)\}, ((?:-?\d+, ){8})0x([0-9a-f]{8})u\},", ops_src, re.M):
+        v = [int(x) for x in r[4].rstrip(", ").split(", ")]
+        ops.append(dict(op=int(r[0]), ins=[int(r[1]), int(r[2]), int(r[3])], out=v[0], padding=v[1], sw=v[2], sh=v[3], fw=v[4], fh=v[5], dm=v[6],
+                        axis=v[7], alpha_bits=int(r[5], 16)))
+    tensors = []
+    for r in re.findall(r"^\s*\{\{(\d+), (\d+), (\d+), (\d+)\}, (\d+), (\d+), (-?\d+), (\d+)\},", tensors_src, re.M):
+        v = [int(x) for x in r]
+        tensors.append(dict(shape=v[:4], type=v[4], zp=0, qdim=v[6], scale=np.zeros(0, np.float32), data=None, n_scales=v[7], is_const=bool(v[5])))
+    pad_t = int(re.search(r"#define YF_GRAPH_PAD_TENSOR (\d+)", src).group(1))
+    tensors[pad_t]["data"] = np.array([int(x) for x in re.search(r"yf_graph_paddings\[\d+\] = \{([^}]*)\}", src).group(1).split(",")], "<i4")
+    n_ops, t_in, t_out = (int(re.search(r"#define YF_GRAPH_%s (\d+)" % k, src).group(1)) for k in ("N_OPS", "INPUT", "OUTPUT"))
+    assert len(ops) == n_ops and len(tensors) > t_out
+    return dict(tensors=tensors, ops=ops, input=t_in, output=t_out)
+
+
+def graph_convs(graph=None):
+    """The graph's convolutions in order: dict(op, depthwise, cin, cout, k, stride, shape) -- shape the filter's in tflite layout (OHWI / 1HWC)."""
+    g = load_graph() if graph is None else graph
+    out = []
+    for i, o in enumerate(g["ops"]):
+        if o["op"] in (OPCODE["CONV_2D"], OPCODE["DEPTHWISE_CONV_2D"]):
+            sh = g["tensors"][o["ins"][1]]["shape"]
+            dw = o["op"] == OPCODE["DEPTHWISE_CONV_2D"]
+            out.append(dict(op=i, depthwise=dw, cin=sh[3], cout=sh[3] if dw else sh[0], k=sh[1], stride=o["sw"], shape=tuple(sh)))
+    return out
+
+
+def write_yfw(convs, path=None):
+    """[(weights, bias, depthwise)] in tflite layout and graph order (dense OHWI, depthwise 1HWC) -> .yfw bytes:
+    'YFW1', u32 n_conv, then per convolution u32 depthwise, cin, cout, k, stride, n_weights; f32 weights; f32 bias[cout].
+    The channels, kernels and strides are the graph's: anything else raises ValueError."""
+    g = graph_convs()
+    if len(convs) != len(g):
+        raise ValueError(f"{len(convs)} convs, the graph has {len(g)}")
+    out = [b"YFW1", struct.pack("<I", len(g))]
+    for c, ((w, b, dw), d) in enumerate(zip(convs, g)):
+        w, b = np.asarray(w, "<f4"), np.asarray(b, "<f4")
+        if bool(dw) != d["depthwise"] or w.size != int(np.prod(d["shape"])) or (w.ndim == 4 and tuple(w.shape) != d["shape"]) or b.size != d["cout"]:
+            raise ValueError(f"conv {c}: depthwise {bool(dw)}, weights {w.shape}, bias {b.shape}; the graph has depthwise {d['depthwise']}, "
+                             f"{d['shape']}, ({d['cout']},)")
+        out += [struct.pack("<6I", int(d["depthwise"]), d["cin"], d["cout"], d["k"], d["stride"], w.size), w.tobytes(), b.tobytes()]
+    out = b"".join(out)
+    if path is not None:
+        with open(path, "wb") as f:
+            f.write(out)
+    return out
+
+
+def read_yfw(path_or_bytes):
+    """A .yfw file (path) or its bytes -> [(weights, bias, depthwise)] in tflite layout, what write_yfw takes.  Raises ValueError on a file that
+    is not this network (the calibration library's parser, csrc/yf_yfw.c, is the one that faces untrusted bytes)."""
+    b = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else open(path_or_bytes, "rb").read()
+    g = graph_convs()
+    if len(b) < 8 or b[:4] != b"YFW1" or struct.unpack_from("<I", b, 4)[0] != len(g):
+        raise ValueError(f"not a .yfw image of {len(g)} convs (magic, count)")
+    off, convs = 8, []
+    for c, d in enumerate(g):
+        want = (int(d["depthwise"]), d["cin"], d["cout"], d["k"], d["stride"], int(np.prod(d["shape"])))
+        if off + 24 > len(b) or struct.unpack_from("<6I", b, off) != want:
+            raise ValueError(f"conv {c}: record {struct.unpack_from('<6I', b, off) if off + 24 <= len(b) else 'truncated'}, the graph has {want}")
+        off += 24
+        if off + 4 * (want[5] + d["cout"]) > len(b):
+            raise ValueError(f"conv {c}: weights and biases end past the file")
+        w = np.frombuffer(b, "<f4", want[5], off).reshape(d["shape"]).copy()
+        bias = np.frombuffer(b, "<f4", d["cout"], off + 4 * want[5]).copy()
+        off += 4 * (want[5] + d["cout"])
+        convs.append((w, bias, d["depthwise"]))
+    if off != len(b):
+        raise ValueError(f"{len(b)} bytes, the convs' counts give {off}")
+    return convs
 
 
 def tflite_model_to_dict(m):

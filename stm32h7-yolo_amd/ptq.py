@@ -18,8 +18,15 @@ on the reference's representative dataset prepared as its script prepares it (`r
 INTER_LINEAR resize, which is what makes the difference: PIL's antialiased resize left the first layers 10-27 % off): every
 activation zero point and 42 of 46 scales are reproduced (float32 rounding noise), four scales within 0.8 %.
 This is an offline tool; it is not on the inference path.
+
+`quantize_model` applies the rules to a whole float model: .yfw bytes and calibrated ranges in, a .yfm image out that yf_network_init_model
+admits.  The ranges come from the calibration library (calib.py: the float32 evaluation on the GPU, or its host build).
 """
 import numpy as np
+
+from . import model_file
+
+INPUT_SCALE_BITS, INPUT_ZERO_POINT = 0x3B808081, -128           # what every frame producer assumes: pixel - 128 in units of 1/255
 
 
 def quantize_conv_weights(w, channel_axis):
@@ -49,6 +56,65 @@ def activation_qparams(rmin, rmax):
     scale = (rmax - rmin) / 255.0
     zp = int(np.clip(np.round(-128.0 - rmin / scale), -128, 127))
     return np.float32(scale), zp
+
+
+def quantize_model(yfw_bytes, ranges):
+    """Float weights (.yfw bytes, model_file.read_yfw) and calibrated ranges {tensor id: (min, max)} -> the bytes of a .yfm image.
+    The graph is the library's (model_file.load_graph: csrc/gen/yf_graph_gen.h); only the numbers are new:
+      * filters by quantize_conv_weights, biases by quantize_bias on the scale finally assigned to the convolution's input;
+      * every CONV_2D, DEPTHWISE_CONV_2D, LEAKY_RELU and ADD output by activation_qparams of its own range;
+      * the input pinned to (0x3b808081, -128), the bits the frame producers assume;
+      * a CONCATENATION output by the union of its inputs' ranges (a QUANTIZE or MAX_POOL_2D output's range is the range observed for the
+        pool's output), and EVERY input of a CONCATENATION -- a QUANTIZE output or a tensor wired in directly -- carries the output's parameters;
+      * PAD and MAX_POOL_2D outputs carry their input's parameters.
+    `ranges` must hold the input, every convolution, LeakyReLU and ADD output and the two pool outputs (calib.Calibration.ranges()).
+    A filter channel that is all zero would get scale 0, which no parser admits: ValueError names the convolution and the channel."""
+    O = model_file.OPCODE
+    convs = model_file.read_yfw(yfw_bytes)
+    g = model_file.load_graph()
+    T, ops = g["tensors"], g["ops"]
+    ranges = {int(k): (float(v[0]), float(v[1])) for k, v in ranges.items()}
+    producer = {o["out"]: o for o in ops}
+
+    def range_of(t):
+        """the range of the values tensor t holds: observed, or that of the tensor a QUANTIZE copies"""
+        while t not in ranges:
+            o = producer.get(t)
+            if o is None or o["op"] != O["QUANTIZE"]:
+                raise ValueError(f"ranges: tensor {t} is missing")
+            t = o["ins"][0]
+        return ranges[t]
+
+    q = {g["input"]: (np.array([INPUT_SCALE_BITS], "<u4").view("<f4")[0], INPUT_ZERO_POINT)}
+    for o in ops:
+        if o["op"] in (O["CONV_2D"], O["DEPTHWISE_CONV_2D"], O["LEAKY_RELU"], O["ADD"]):
+            q[o["out"]] = activation_qparams(*range_of(o["out"]))
+        elif o["op"] == O["CONCATENATION"]:
+            r = [range_of(t) for t in o["ins"][:2]]
+            q[o["out"]] = activation_qparams(min(r[0][0], r[1][0]), max(r[0][1], r[1][1]))
+    for o in ops:
+        if o["op"] == O["CONCATENATION"]:
+            for t in o["ins"][:2]:
+                q[t] = q[o["out"]]
+    for o in ops:                                   # (in op order: a PAD or pool behind a tensor whose parameters were just replaced follows it)
+        if o["op"] in (O["PAD"], O["MAX_POOL_2D"]):
+            q[o["out"]] = q[o["ins"][0]]
+    for t, (scale, zp) in q.items():
+        T[t]["scale"], T[t]["zp"] = np.array([scale], "<f4"), int(zp)
+    for c, (d, (w, b, dw)) in enumerate(zip(model_file.graph_convs(g), convs)):
+        o = ops[d["op"]]
+        wq, s_w = quantize_conv_weights(w, 3 if dw else 0)
+        if (s_w == 0).any():
+            raise ValueError(f"conv {c} (op {d['op']}): filter channel {int(np.argmax(s_w == 0))} is all zero: its scale would be 0")
+        s_in = T[o["ins"][0]]["scale"][0]
+        wt, bt = T[o["ins"][1]], T[o["ins"][2]]
+        wt["scale"], wt["data"] = s_w.astype("<f4"), wq.reshape(-1)
+        bt["scale"] = (np.float64(np.float32(s_in)) * s_w.astype(np.float64)).astype("<f4")
+        bt["data"] = quantize_bias(b, s_in, s_w).astype("<i4")
+    missing = [i for i, t in enumerate(T) if len(t["scale"]) != t["n_scales"] or (t["data"] is None) == t["is_const"]]
+    if missing:
+        raise ValueError(f"tensors {missing} were left without numbers")
+    return model_file.write_yfm(g)
 
 
 class Calibrator:
