@@ -173,6 +173,55 @@ YF_API long yf_images_run_decode_f16_ragged_device(ai_handle net, const void* d_
                                                    const yf_image* d_images, long n, void* d_frames_f16, void* d_logits,
                                                    void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
 
+/* ---- scoring records against ground truth: calculate_iou / calculate_ap / calculate_map of yoloface/tensorflow/yolov3_train_tf.py:657-759
+ * (what evaluate_model, :809-869, reports) on the records of any decode or suppression above, without the records leaving the device.  The
+ * arithmetic is stated once, in csrc/yf_images_eval.h, which the kernels and a host build share: float64, one IEEE operation per Python
+ * operation, in the reference's order, no contraction.
+ *   input:  d_dets yf_det[n][cap], d_counts int32[n]: the first min(max(count, 0), cap) records of each frame, as for the suppression;
+ *           a record's frame is its place in the array (the `frame` field is not read).  1 <= cap <= YF_IMAGES_NMS_WIDE_MAX_CAP.
+ *           d_gt yf_gt_box[n][gt_cap] (8-byte aligned), d_gt_counts int32[n], clamped the same way; 1 <= gt_cap <= YF_IMAGES_EVAL_MAX_GT.
+ *           A ground-truth row may hold anything, infinities and NaN included: it behaves as it does in Python.
+ *   iou:    NOT the suppression's formula -- there is no + 1: w = max(0, min(x2) - max(x1)), h likewise, inter = w * h,
+ *           union = (area_d + area_g) - inter, iou = inter / union if union > 0 else 0.0.
+ *   match:  per record the ground truth of its frame with the largest IoU, the first one among equals, none at IoU 0 (d_best: its
+ *           index, or -1).  The record is a candidate iff that IoU >= iou_threshold.
+ *   order:  descending conf, the float32 stored in the record; ties go EARLIER record first (lower frame, then lower slot: the stable
+ *           list.sort of :713) -- the opposite of the suppression's tie rule.  -0.0 ties with +0.0.  The reference's comment says "by
+ *           confidence"; the key it wrote, x[4] behind an image id, reads the box's y2.  By confidence is the library's choice.
+ *           Python's sort is not defined for a NaN confidence, which no decode produces; the library's choice: NaN sorts after every
+ *           number.
+ *   claim:  in that order a candidate whose ground truth is unclaimed claims it and is a true positive (d_tp 1); every other record is a
+ *           false positive (d_tp 0), also a candidate whose ground truth was claimed before: there is no second choice.
+ *   curve:  over the m records of the batch in that order: precision = ctp / (ctp + cfp + 1e-16), recall = ctp / max(1, num_gt), the
+ *           precision made non-increasing from the back, ap = sum over i = 1 .. m - 1 of (recall[i] - recall[i - 1]) * precision[i],
+ *           added in that order.  The reference leaves the term of i = 0 out, and so does this: m <= 1 gives 0.0. */
+typedef struct yf_gt_box { double x1, y1, x2, y2; } yf_gt_box;                       /* 32 bytes */
+typedef struct yf_eval_result { double ap; int64_t detections, ground_truths, true_positives; } yf_eval_result;
+#define YF_IMAGES_EVAL_MAX_GT 256
+#define YF_IMAGES_EVAL_SORT_TILE 1024      /* records per tile of the sort below (yf_images_eval_sort_tile returns it) */
+/* Match and claim.  Writes d_tp[n][cap] and, unless it is NULL, d_best int32[n][cap] for the records that exist; slots beyond them are not
+ * written.  One launch, one wave per frame in passes of 64 records: what a frame costs follows its own counts, not the caps.
+ * iou_threshold: any value but NaN.  No allocation, no synchronisation; returns n; n = 0 launches nothing -- after the checks, as
+ * everywhere in this library: d_dets, d_counts, d_gt, d_gt_counts and d_tp must be valid pointers for an empty batch too. */
+YF_API long yf_images_match_device(const void* d_dets, const void* d_counts, long n, int cap,
+                                   const yf_gt_box* d_gt, const int32_t* d_gt_counts, int gt_cap, double iou_threshold,
+                                   uint8_t* d_tp, int32_t* d_best, void* stream);
+/* Average precision of the batch from the flags of the match.  The order is a stable least-significant-digit radix sort of the mapped
+ * confidence bits (the input position already ascends with frame and slot); the cumulative counts and the envelope are scans over tiles
+ * of YF_IMAGES_EVAL_SORT_TILE records; the terms of the true positives are added in order by one wave.  All scratch is the caller's:
+ * d_work (16-byte aligned) of at least yf_images_average_precision_workspace(n, cap) bytes (0 for arguments the call would refuse); a
+ * smaller work_bytes is an error and nothing is launched.  num_gt is the sum of the clamped d_gt_counts.  d_result receives one
+ * yf_eval_result; d_curve, unless NULL, double[m][2] = (recall, envelope precision) in the order above -- its capacity n * cap is the
+ * caller's to provide.  n * cap < 2^31.  20 launches on `stream` whatever the counts (2 to gather the keys, 4 x 3 to sort, 6 for the
+ * curve and the sum), nothing is read back, no allocation, no synchronisation; returns n; n = 0 launches nothing and writes nothing --
+ * after the checks: every pointer but d_curve, d_work included, must be valid for an empty batch too.  Five of the launches are one
+ * workgroup each (the scans over frames, digits and tiles); their time grows with the number of tiles, see profiles/eval_bench.txt. */
+YF_API size_t yf_images_average_precision_workspace(long n, int cap);
+YF_API long yf_images_average_precision_device(const void* d_dets, const void* d_counts, const uint8_t* d_tp, long n, int cap,
+                                               const int32_t* d_gt_counts, int gt_cap, void* d_work, size_t work_bytes,
+                                               yf_eval_result* d_result, double* d_curve, void* stream);
+YF_API int yf_images_eval_sort_tile(void);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

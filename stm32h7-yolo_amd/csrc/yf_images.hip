@@ -10,7 +10,8 @@
 // The frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses
 // inside the image's extent: no load reaches past its last pixel.
 // The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame), decode_f32_kernel (the fp16 network's
-// float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h.
+// float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h;
+// the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 #include "yf_images_decode160.h"
 #include "yf_images_float.h"
 #include "yf_images_wide.hip.h"
+#include "yf_images_eval.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -437,6 +439,19 @@ bool check_nms(const void* d_dets, const void* d_counts, long n, int cap, int ma
   return true;
 }
 
+// what the match and the average precision share: the batch, the caps and the records
+bool check_eval(const void* d_dets, const void* d_counts, long n, int cap, const int32_t* d_gt_counts, int gt_cap) {
+  if (n < 0) return fail("n < 0");
+  if (cap <= 0 || cap > YF_IMAGES_NMS_WIDE_MAX_CAP) return fail("cap must be in [1, %d]", YF_IMAGES_NMS_WIDE_MAX_CAP);
+  if (gt_cap <= 0 || gt_cap > YF_IMAGES_EVAL_MAX_GT) return fail("gt_cap must be in [1, %d]", YF_IMAGES_EVAL_MAX_GT);
+  if (!d_dets) return fail("d_dets is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (!d_gt_counts) return fail("d_gt_counts is NULL");
+  if (((uintptr_t)d_dets & 3) != 0) return fail("d_dets is not 4-byte aligned");
+  if (((uintptr_t)d_counts & 3) != 0 || ((uintptr_t)d_gt_counts & 3) != 0) return fail("d_counts or d_gt_counts is not 4-byte aligned");
+  return true;
+}
+
 // ---- launches (of checked arguments; an empty batch launches nothing) ----
 using PrepKernel = void (*)(PrepArgs);
 template <int OUT, bool RAGGED>                                    // indexed by pixel format
@@ -747,6 +762,62 @@ YF_API long yf_images_nms_wide_device(const void* d_dets, const void* d_counts, 
   hipLaunchKernelGGL(yfwide::nms_wide_kernel, grid_for(groups, 3), dim3(yfwide::kThreads), 0, (hipStream_t)stream, (const yf_det*)d_dets,
                      (const int*)d_counts, n, cap, iou_threshold, (yf_det*)d_out, (int*)d_out_counts);
   return launched("nms_wide kernel launch", n);
+}
+
+YF_API long yf_images_match_device(const void* d_dets, const void* d_counts, long n, int cap, const yf_gt_box* d_gt,
+                                   const int32_t* d_gt_counts, int gt_cap, double iou_threshold, uint8_t* d_tp, int32_t* d_best,
+                                   void* stream) {
+  if (!check_eval(d_dets, d_counts, n, cap, d_gt_counts, gt_cap)) return 0;
+  if (std::isnan(iou_threshold)) return fail("iou_threshold is NaN");
+  if (!d_gt) return fail("d_gt is NULL");
+  if (!d_tp) return fail("d_tp is NULL");
+  if (((uintptr_t)d_gt & 7) != 0) return fail("d_gt is not 8-byte aligned");
+  if (((uintptr_t)d_best & 3) != 0) return fail("d_best is not 4-byte aligned");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(yfeval::match_kernel, grid_for(n, 12), dim3(64), 0, (hipStream_t)stream, (const yf_det*)d_dets, (const int*)d_counts,
+                     n, cap, d_gt, d_gt_counts, gt_cap, iou_threshold, d_tp, d_best);      // one-wave workgroups, 12.4 KB of LDS each
+  return launched("match kernel launch", n);
+}
+
+YF_API int yf_images_eval_sort_tile(void) { return yfeval::kTile; }
+
+YF_API size_t yf_images_average_precision_workspace(long n, int cap) {
+  if (n < 0 || cap <= 0 || cap > YF_IMAGES_NMS_WIDE_MAX_CAP || (uint64_t)n * (uint64_t)cap >= (1ull << 31)) return 0;
+  return yfeval::layout(nullptr, n, cap).bytes;
+}
+
+YF_API long yf_images_average_precision_device(const void* d_dets, const void* d_counts, const uint8_t* d_tp, long n, int cap,
+                                               const int32_t* d_gt_counts, int gt_cap, void* d_work, size_t work_bytes,
+                                               yf_eval_result* d_result, double* d_curve, void* stream) {
+  if (!check_eval(d_dets, d_counts, n, cap, d_gt_counts, gt_cap)) return 0;
+  if ((uint64_t)n * (uint64_t)cap >= (1ull << 31)) return fail("n * cap must be below 2^31");
+  if (!d_tp) return fail("d_tp is NULL");
+  if (!d_work || ((uintptr_t)d_work & 15) != 0) return fail("d_work is NULL or not 16-byte aligned");
+  if (!d_result || ((uintptr_t)d_result & 7) != 0) return fail("d_result is NULL or not 8-byte aligned");
+  if (((uintptr_t)d_curve & 7) != 0) return fail("d_curve is not 8-byte aligned");
+  const yfeval::Work w = yfeval::layout(d_work, n, cap);
+  if (work_bytes < w.bytes)
+    return fail("work_bytes %zu is below yf_images_average_precision_workspace(n, cap) = %zu", work_bytes, w.bytes);
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  const long tiles = ((long)n * cap + yfeval::kTile - 1) / yfeval::kTile;           // of the capacity: the kernels stride over the true number
+  const dim3 one(1), scan(yfeval::kScan), wave(64), by_tile = grid_for(tiles, 16);
+  hipLaunchKernelGGL(yfeval::offsets_kernel, one, scan, 0, s, (const int*)d_counts, d_gt_counts, n, cap, gt_cap, w.offsets, w.head);
+  hipLaunchKernelGGL(yfeval::gather_kernel, grid_for((n + 3) / 4, 8), dim3(256), 0, s, (const yf_det*)d_dets, (const int*)d_counts, d_tp, n, cap,
+                     w.offsets, w.key[0], w.val[0]);
+  for (int pass = 0; pass < 4; ++pass) {                                            // the sorted keys and flags end in key[0], val[0]
+    const int a = pass & 1, b = a ^ 1;
+    hipLaunchKernelGGL(yfeval::hist_kernel, by_tile, wave, 0, s, w.key[a], 8 * pass, w.head, w.hist);
+    hipLaunchKernelGGL(yfeval::digit_scan_kernel, one, scan, 0, s, w.head, w.hist);
+    hipLaunchKernelGGL(yfeval::scatter_kernel, by_tile, wave, 0, s, w.key[a], w.val[a], w.key[b], w.val[b], 8 * pass, w.head, w.hist);
+  }
+  hipLaunchKernelGGL(yfeval::tile_count_kernel, by_tile, wave, 0, s, w.val[0], w.head, w.tile_sum);
+  hipLaunchKernelGGL(yfeval::tile_base_kernel, one, scan, 0, s, w.head, w.tile_sum, w.tile_base);
+  hipLaunchKernelGGL(yfeval::tile_max_kernel, by_tile, wave, 0, s, w.val[0], w.head, w.tile_base, w.tile_max);
+  hipLaunchKernelGGL(yfeval::tile_sufmax_kernel, one, scan, 0, s, w.head, w.tile_max, w.tile_sufmax);
+  hipLaunchKernelGGL(yfeval::curve_kernel, by_tile, wave, 0, s, w.val[0], w.head, w.tile_base, w.tile_sufmax, w.terms, d_curve);
+  hipLaunchKernelGGL(yfeval::sum_kernel, one, wave, 0, s, w.head, w.terms, d_result);
+  return launched("average precision kernel launches", n);
 }
 
 }  // extern "C"

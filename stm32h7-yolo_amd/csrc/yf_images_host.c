@@ -1,12 +1,15 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
- * yf_images_decode160.h and the fp16 frames and float32 decode of yf_images_float.h (the functions the device kernels call), for the CPU
- * tests only: libyf_images_host.so, no HIP. */
+ * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
+ * functions the device kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include "yf_images_taps.h"
 #include "yf_images_nms.h"
 #include "yf_images_decode160.h"
 #include "yf_images_float.h"
+#include "yf_images_eval.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -99,4 +102,108 @@ EXPORT int yfi_decode_f32_host(const float* logits, int32_t frame, float w_scale
     ++n;
   }
   return n;
+}
+
+/* ---- yf_images_eval.h ----  calculate_iou over n pairs: d[k] int32[4] edges of a detection, g[k] double[4] of a ground truth */
+EXPORT void yfi_eval_iou_host(const int32_t* d, const double* g, long n, double* out) {
+  for (long k = 0; k < n; ++k) out[k] = yfi_eval_iou(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3], g[4 * k], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3]);
+}
+
+/* the order key of a confidence (yfi_eval_key) */
+EXPORT uint32_t yfi_eval_key_host(uint32_t conf_bits) { return yfi_eval_key(conf_bits); }
+
+/* order[0 .. m): the positions 0 .. m - 1 sorted by key[], equal keys in input order (least significant byte first, counting); 0 on
+ * success */
+static int eval_order(const uint32_t* key, long m, int32_t* order) {
+  int32_t* tmp = malloc((size_t)(m > 0 ? m : 1) * sizeof *tmp);
+  if (!tmp) return -1;
+  for (long i = 0; i < m; ++i) order[i] = (int32_t)i;
+  for (int shift = 0; shift < 32; shift += 8) {
+    long at[257] = {0};
+    for (long i = 0; i < m; ++i) ++at[((key[order[i]] >> shift) & 255u) + 1];
+    for (int d = 0; d < 256; ++d) at[d + 1] += at[d];
+    for (long i = 0; i < m; ++i) tmp[at[(key[order[i]] >> shift) & 255u]++] = order[i];
+    memcpy(order, tmp, (size_t)m * sizeof *tmp);
+  }
+  free(tmp);
+  return 0;
+}
+
+/* yf_images_match_device as the reference's loop states it: per frame, the records in order (descending conf, earlier slot first), each
+ * one's best ground truth, and a set of the claimed ones.  tp[n][cap], best[n][cap] (may be NULL); slots beyond a frame's records are
+ * not written.  Returns n, or -1 without memory. */
+EXPORT long yfi_eval_match_host(const yf_det* dets, const int32_t* counts, long n, int cap, const yf_gt_box* gt, const int32_t* gt_counts,
+                                int gt_cap, double thr, uint8_t* tp, int32_t* best) {
+  uint32_t* key = malloc((size_t)cap * sizeof *key);
+  int32_t* order = malloc((size_t)cap * sizeof *order);
+  uint8_t* claimed = malloc((size_t)gt_cap);
+  long rc = n;
+  if (!key || !order || !claimed) rc = -1;
+  for (long f = 0; rc == n && f < n; ++f) {
+    const int m = yfi_eval_clamp(counts[f], cap), k = yfi_eval_clamp(gt_counts[f], gt_cap);
+    const yf_det* d = dets + f * cap;
+    const yf_gt_box* g = gt + f * gt_cap;
+    for (int r = 0; r < m; ++r) { uint32_t u; memcpy(&u, &d[r].conf, 4); key[r] = yfi_eval_key(u); }
+    if (eval_order(key, m, order) != 0) { rc = -1; break; }
+    memset(claimed, 0, (size_t)gt_cap);
+    for (int o = 0; o < m; ++o) {
+      const int r = order[o];
+      double best_iou = 0.0;
+      int b = -1;
+      for (int j = 0; j < k; ++j) {
+        const double iou = yfi_eval_iou(d[r].x1, d[r].y1, d[r].x2, d[r].y2, g[j].x1, g[j].y1, g[j].x2, g[j].y2);
+        if (iou > best_iou) { best_iou = iou; b = j; }
+      }
+      uint8_t hit = 0;
+      if (best_iou >= thr && b >= 0 && !claimed[b]) { claimed[b] = 1; hit = 1; }
+      tp[f * cap + r] = hit;
+      if (best) best[f * cap + r] = b;
+    }
+  }
+  free(key); free(order); free(claimed);
+  return rc;
+}
+
+/* yf_images_average_precision_device as the reference states it: the records of the batch in order, the cumulative counts, precision and
+ * recall, the envelope from the back, the sum from i = 1.  curve (may be NULL): double[m][2] = (recall, envelope).  Returns n, or -1
+ * without memory. */
+EXPORT long yfi_eval_ap_host(const yf_det* dets, const int32_t* counts, const uint8_t* tp, long n, int cap, const int32_t* gt_counts, int gt_cap,
+                             yf_eval_result* result, double* curve) {
+  long m = 0;
+  int64_t num_gt = 0;
+  for (long f = 0; f < n; ++f) { m += yfi_eval_clamp(counts[f], cap); num_gt += yfi_eval_clamp(gt_counts[f], gt_cap); }
+  const size_t room = (size_t)(m > 0 ? m : 1);
+  uint32_t* key = malloc(room * sizeof *key);
+  uint8_t* flag = malloc(room);
+  int32_t* order = malloc(room * sizeof *order);
+  double* precision = malloc(room * sizeof *precision);
+  double* recall = malloc(room * sizeof *recall);
+  long rc = n;
+  if (!key || !flag || !order || !precision || !recall) rc = -1;
+  if (rc == n) {
+    long at = 0;
+    for (long f = 0; f < n; ++f)
+      for (int r = 0; r < yfi_eval_clamp(counts[f], cap); ++r, ++at) {
+        uint32_t u;
+        memcpy(&u, &dets[f * cap + r].conf, 4);
+        key[at] = yfi_eval_key(u);
+        flag[at] = tp[f * cap + r] != 0;
+      }
+    if (eval_order(key, m, order) != 0) rc = -1;
+  }
+  if (rc == n) {
+    double ctp = 0.0, cfp = 0.0;
+    for (long i = 0; i < m; ++i) {
+      if (flag[order[i]]) ctp += 1.0; else cfp += 1.0;
+      precision[i] = yfi_eval_precision(ctp, cfp);
+      recall[i] = yfi_eval_recall(ctp, num_gt);
+    }
+    for (long i = m - 2; i >= 0; --i) precision[i] = precision[i + 1] > precision[i] ? precision[i + 1] : precision[i];
+    double ap = 0.0;
+    for (long i = 1; i < m; ++i) ap += (recall[i] - recall[i - 1]) * precision[i];
+    if (curve) for (long i = 0; i < m; ++i) { curve[2 * i] = recall[i]; curve[2 * i + 1] = precision[i]; }
+    result->ap = ap; result->detections = m; result->ground_truths = num_gt; result->true_positives = (int64_t)ctp;
+  }
+  free(key); free(flag); free(order); free(precision); free(recall);
+  return rc;
 }

@@ -8,6 +8,10 @@ suppression of yoloface/tensorflow/yoloface_test.py:145-190 on the GPU (`nms_dev
 on 160x160 frames (20x20 heads, 1200 candidates per image: `run_decode160_ragged_device`, `nms_wide_device`).  `dtype="fp16"` runs the fp16
 network instead, as the reference's float caller yoloface/tensorflow/h5_predition.py:29-73 does: fp16 frames of pixel / 255., float32 logits,
 the decode in float32 (`run_decode_f16_ragged_device`; the arithmetic: csrc/yf_images_float.h).
+
+`evaluate(network, images, ground_truths)` scores those boxes against labelled ones as the reference's training script does
+(yoloface/tensorflow/yolov3_train_tf.py:657-759, calculate_iou / calculate_ap / calculate_map): `match_device` and
+`average_precision_device` on the same stream, without the records leaving the GPU (the arithmetic: csrc/yf_images_eval.h).
 """
 import ctypes
 import hashlib
@@ -30,6 +34,8 @@ NMS_MAX_CAP = 256
 NMS_WIDE_MAX_CAP = 1200
 GRID160, CAND160 = 20, 1200
 FRAME_BYTES = {56: 56 * 56 * 3, 160: 160 * 160 * 3}
+EVAL_MAX_GT = 256
+EVAL_SORT_TILE = 1024            # records per tile of average_precision_device's sort (YF_IMAGES_EVAL_SORT_TILE; checked in load())
 
 
 class YfImage(ctypes.Structure):
@@ -38,6 +44,12 @@ class YfImage(ctypes.Structure):
 
 IMAGE_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("row_stride", "<i8")])
 assert IMAGE_DTYPE.itemsize == ctypes.sizeof(YfImage) == 24
+
+
+# a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
+GT_DTYPE = np.dtype([("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8")])
+EVAL_RESULT_DTYPE = np.dtype([("ap", "<f8"), ("detections", "<i8"), ("ground_truths", "<i8"), ("true_positives", "<i8")])
+assert GT_DTYPE.itemsize == 32 and EVAL_RESULT_DTYPE.itemsize == 32
 
 
 class ImagesError(RuntimeError):
@@ -97,6 +109,8 @@ def _entries():
         "decode_f32_ragged_device": [vp, vp, vp, cl, vp, vp, ci, vp],
         "run_decode_f16_device": [vp] + uniform + [vp, vp, vp, vp, ci, vp],
         "run_decode_f16_ragged_device": [vp] + ragged + [vp, vp, vp, vp, ci, vp, vp],
+        "match_device": [vp, vp, cl, ci, vp, vp, ci, cd, vp, vp, vp],
+        "average_precision_device": [vp, vp, vp, cl, ci, vp, ci, vp, cs, vp, vp, vp],
     }
 
 
@@ -142,6 +156,12 @@ def load():
     lib.yf_images_last_error_text.argtypes = []
     lib.yf_images_set_decode_tables.restype = ctypes.c_int
     lib.yf_images_set_decode_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    lib.yf_images_average_precision_workspace.restype = ctypes.c_size_t
+    lib.yf_images_average_precision_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
+    lib.yf_images_eval_sort_tile.restype = ctypes.c_int
+    lib.yf_images_eval_sort_tile.argtypes = []
+    if lib.yf_images_eval_sort_tile() != EVAL_SORT_TILE:
+        raise RuntimeError(f"{path}: sort tile {lib.yf_images_eval_sort_tile()}, images.EVAL_SORT_TILE says {EVAL_SORT_TILE}")
     _lib = lib
     return lib
 
@@ -296,6 +316,115 @@ def run_decode_f16_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images,
                                  stream=None):
     _call("run_decode_f16_ragged_device", n, network.handle, d_pixels, pixels_bytes, format_code(fmt), d_images, n, d_frames_f16, d_logits,
           d_dets, d_counts, cap, d_status, stream)
+
+
+def match_device(d_dets, d_counts, n, cap, d_gt, d_gt_counts, gt_cap, iou_threshold, d_tp, d_best=None, stream=None):
+    """Records against their frame's ground truths (yf_images_match_device): d_dets yf_det[n][cap], d_counts int32[n], d_gt GT_DTYPE[n][gt_cap],
+    d_gt_counts int32[n] -> d_tp uint8[n][cap] (1 true positive, 0 false positive) and, if given, d_best int32[n][cap] (the best ground
+    truth's index or -1).  Order of the claim: descending conf, ties earlier record first; float64 as yolov3_train_tf.py:657-746 states it."""
+    _call("match_device", n, d_dets, d_counts, n, cap, d_gt, d_gt_counts, gt_cap, float(iou_threshold), d_tp, d_best, stream)
+
+
+def average_precision_workspace(n, cap):
+    """Bytes of scratch average_precision_device needs for n frames of cap records (0 for arguments it would refuse)."""
+    return int(load().yf_images_average_precision_workspace(n, cap))
+
+
+def average_precision_device(d_dets, d_counts, d_tp, n, cap, d_gt_counts, gt_cap, d_work, work_bytes, d_result, d_curve=None, stream=None):
+    """Average precision of the batch from match_device's flags (yf_images_average_precision_device): d_result one EVAL_RESULT_DTYPE,
+    d_curve (optional) float64 [n * cap][2] = (recall, envelope precision) of the first `detections` records in order; d_work at least
+    average_precision_workspace(n, cap) bytes, 16-byte aligned."""
+    _call("average_precision_device", n, d_dets, d_counts, d_tp, n, cap, d_gt_counts, gt_cap, d_work, work_bytes, d_result, d_curve, stream)
+
+
+def pack_ground_truths(ground_truths):
+    """one [k, 4] array (x1, y1, x2, y2) per image -> (GT_DTYPE [n, gt_cap], int32 [n]), gt_cap the largest k (at least 1)"""
+    gts = [np.asarray(g, np.float64).reshape(-1, 4) for g in ground_truths]
+    gt_cap = max([1] + [g.shape[0] for g in gts])
+    if gt_cap > EVAL_MAX_GT:
+        raise ValueError(f"{gt_cap} ground-truth boxes in one image: at most {EVAL_MAX_GT}")
+    packed = np.zeros((len(gts), gt_cap), GT_DTYPE)
+    for i, g in enumerate(gts):
+        packed[i, :g.shape[0]] = np.ascontiguousarray(g).view(GT_DTYPE).reshape(-1)
+    return packed, np.array([g.shape[0] for g in gts], np.int32)
+
+
+def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype):
+    """What `detect` launches, with the records left on the device: checks size and dtype as it does, packs the images, allocates the
+    workspaces, runs images -> frames -> network -> records (and the suppression when iou_threshold is not None) on the device's current
+    stream without synchronising.  -> (d_dets uint8 [n, cap, 28], d_counts int32 [n], d_status int32 [n], stream, keep), `keep` the
+    tensors that must outlive the launches.  `detect` keeps its own copy of these lines (it predates this helper and is left as it is);
+    a change to one belongs in the other."""
+    if size not in (56, 160):
+        raise ValueError(f"size {size!r}: 56 or 160")
+    if dtype not in ("int8", "fp16"):
+        raise ValueError(f"dtype {dtype!r}: 'int8' or 'fp16'")
+    if dtype == "fp16" and size != 56:
+        raise ValueError("dtype 'fp16': the fp16 network has 56x56 frames only")
+    import torch
+    grid = size // 8
+    if cap is None:
+        cap = 3 * grid * grid
+    n = len(images)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    buf, desc = pack_images(images, fmt)
+    d_px = torch.from_numpy(buf).to(dev)
+    d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    f16 = dtype == "fp16"
+    d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
+    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
+    d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
+    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
+    if f16:
+        run = run_decode_f16_ragged_device
+    else:
+        set_decode_tables(*network.decode_tables())
+    run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
+        d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    if iou_threshold is not None:
+        nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
+    return d_dets, d_counts, d_status, stream, (d_px, d_desc, d_frames, d_heads)
+
+
+def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None):
+    """Average precision of the network's boxes against labelled ones: what evaluate_model (yolov3_train_tf.py:809-869) reports, for the
+    batch `detect` takes.  `ground_truths`: one [k, 4] array (x1, y1, x2, y2) per image, in that image's pixels.  The records are decoded as
+    by `detect` (fmt, size, dtype as there; iou_threshold=None scores every record, a float suppresses first, as evaluate_model does),
+    matched at IoU `conf_iou` (match_device) and scored (average_precision_device) on the same stream; only the 32-byte result and the
+    per-image status come back.  An image the library refused (status 1; `pack_images` produces none) raises ImagesError.
+    Returns {"ap", "detections", "ground_truths", "true_positives", "precision", "recall"}; the last two are the end of the curve:
+    true_positives / (detections + 1e-16) and true_positives / max(1, ground_truths)."""
+    n = len(images)
+    if len(ground_truths) != n:
+        raise ValueError(f"{n} images, {len(ground_truths)} lists of ground truths")
+    gt, gt_counts = pack_ground_truths(ground_truths)
+    if n == 0:
+        return {"ap": 0.0, "detections": 0, "ground_truths": 0, "true_positives": 0, "precision": 0.0, "recall": 0.0}
+    d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, None, device, iou_threshold, size, dtype)
+    import torch
+    dev, cap, gt_cap = d_dets.device, d_dets.shape[1], gt.shape[1]
+    d_gt = torch.from_numpy(gt.view(np.float64).reshape(n, gt_cap, 4)).to(dev)
+    d_gt_counts = torch.from_numpy(gt_counts).to(dev)
+    d_tp = torch.empty((n, cap), dtype=torch.uint8, device=dev)
+    work_bytes = average_precision_workspace(n, cap)
+    d_work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+    d_result = torch.empty(4, dtype=torch.float64, device=dev)
+    match_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, d_gt.data_ptr(), d_gt_counts.data_ptr(), gt_cap, conf_iou,
+                 d_tp.data_ptr(), stream=stream.cuda_stream)
+    average_precision_device(d_dets.data_ptr(), d_counts.data_ptr(), d_tp.data_ptr(), n, cap, d_gt_counts.data_ptr(), gt_cap,
+                             d_work.data_ptr(), work_bytes, d_result.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    del keep
+    bad = np.nonzero(d_status.cpu().numpy())[0]
+    if bad.size:
+        raise ImagesError(f"evaluate: the library refused image(s) {bad.tolist()} (status 1): their frames hold no picture")
+    res = d_result.cpu().numpy().view(EVAL_RESULT_DTYPE)[0]
+    m, num_gt, tp = int(res["detections"]), int(res["ground_truths"]), int(res["true_positives"])
+    return {"ap": float(res["ap"]), "detections": m, "ground_truths": num_gt, "true_positives": tp,
+            "precision": tp / (m + 1e-16), "recall": tp / max(1, num_gt)}
 
 
 def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8"):
