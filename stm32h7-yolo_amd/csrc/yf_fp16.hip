@@ -12,7 +12,9 @@
 //   epilogue: bias rides in the accumulator's initial value; LeakyReLU = max(x, 0.1 x); two v_cvt_pk_f16_f32; one 8-byte
 //     LDS store (residual add: the stored fp16 operand is added in fp32 first)
 //   max-pools: v_pk_max_f16 on channel pairs, separable 8x8, clamped coordinates (padding never wins)
-// Tolerance-checked against an fp32 numpy evaluation of the same graph (tests/test_gpu_parity.py, atol/rtol 2e-2).  gfx950 only.
+// Tolerance-checked against an fp32 numpy evaluation of the same graph (tests/test_gpu_parity.py, atol/rtol 2e-2); bit for bit against
+// oracle/np_fp16.py on designed weight packs, with distinct frames in every batch slot and a non-finite neighbour frame
+// (tests/test_fp16_packs_gpu.py).  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
