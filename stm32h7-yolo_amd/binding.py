@@ -8,10 +8,11 @@ The library has no CPU compute path: without a gfx950 GPU `init()` raises.
 import ctypes
 import os
 import sys
-import subprocess
 import weakref
 
 import numpy as np
+
+from . import libs
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libyf_network.so")
@@ -111,46 +112,17 @@ EXPORTS = ["ai_network_create", "ai_network_init", "ai_network_run", "ai_network
 
 def expected_build_id(extra_hipflags="", extra_fp16flags=""):
     """The id csrc/Makefile bakes into the library (yf_network_build_id): sha256 over the device sources, flags.mk and the extra flags."""
-    import hashlib
-    csrc = os.path.join(_PKG, "csrc")
-    flags = open(os.path.join(csrc, "flags.mk"), "rb").read()
-    srcs = [ln.split(b"=", 1)[1].split() for ln in flags.splitlines() if ln.startswith(b"DEVICE_SRCS")][0]
-    h = hashlib.sha256()
-    for f in srcs:
-        h.update(open(os.path.join(csrc, f.decode()), "rb").read())
-    h.update(flags)
-    h.update(f"{extra_hipflags}|{extra_fp16flags}\n".encode())
-    return h.hexdigest()[:16]
+    return libs.source_id(libs.make_var("DEVICE_SRCS").split() + ["flags.mk"], f"{extra_hipflags}|{extra_fp16flags}\n")
 
 
 def expected_host_id():
     """The id of the C host layer csrc/Makefile bakes into the library (yf_network_host_id): sha256 over HOST_SRCS and the C flags."""
-    import hashlib
-    import re
-    csrc = os.path.join(_PKG, "csrc")
-    flags = open(os.path.join(csrc, "flags.mk")).read()
-    srcs = re.search(r"^HOST_SRCS\s*=\s*(.*)$", flags, re.M).group(1).split()
-    cflags = re.search(r"^CFLAGS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).strip()
-    h = hashlib.sha256()
-    for f in srcs:
-        h.update(open(os.path.join(csrc, f), "rb").read())
-    h.update((cflags + "\n").encode())
-    return h.hexdigest()[:16]
+    return libs.source_id(libs.make_var("HOST_SRCS").split(), libs.make_var("CFLAGS") + "\n")
 
 
 def build(force=False):
-    """Compile the library in-tree for gfx950 (hipcc cross-compiles without a GPU).  One build at a time: the processes that share a checkout
-    (the two ranks of bench.py's self-launch, parallel test workers, profiler-wrapped tools) serialise on a lock file beside the Makefile -- not
-    in the output directory, which `make clean` empties while a forced build holds the lock."""
-    import fcntl
-    out = os.path.join(_PKG, "lib")
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(_PKG, "csrc", ".build.lock"), "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if force:
-            subprocess.check_call(["make", "-C", os.path.join(_PKG, "csrc"), "clean"], stdout=subprocess.DEVNULL)
-        subprocess.check_call(["make", "-C", os.path.join(_PKG, "csrc"), "-j4", "all", "../lib/libyf_hostprep.so"],
-                              stdout=subprocess.DEVNULL)
+    """Compile the libraries in-tree for gfx950 (libs.make: one build at a time in a checkout)."""
+    libs.make(*libs.ALL, force=force)
     return LIB_PATH
 
 
@@ -159,20 +131,13 @@ def library_is_current():
     lib/host_id.stamp) are the ids of the sources as they stand, and it is newer than every one of them.  load() then starts no child process --
     under rocprofv3 every child of a GPU-holding process is instrumented by the profiler's preloaded tool (round 5: make, sh, cut and sha256sum
     in the middle of a counter pass).  The ids baked into the library are still checked after it is loaded."""
-    import re
-    csrc, lib = os.path.join(_PKG, "csrc"), os.path.join(_PKG, "lib")
     try:
-        if open(os.path.join(lib, "build_id.stamp")).read().strip() != expected_build_id():
+        if open(os.path.join(libs.LIB_DIR, "build_id.stamp")).read().strip() != expected_build_id():
             return False
-        if open(os.path.join(lib, "host_id.stamp")).read().strip() != expected_host_id():
+        if open(os.path.join(libs.LIB_DIR, "host_id.stamp")).read().strip() != expected_host_id():
             return False
-        built = os.path.getmtime(LIB_PATH)
-        flags = open(os.path.join(csrc, "flags.mk")).read()
-        srcs = ["Makefile", "flags.mk"]
-        for var in ("DEVICE_SRCS", "HOST_SRCS"):
-            srcs += re.search(r"^%s\s*=\s*(.*)$" % var, flags, re.M).group(1).split()
-        return all(os.path.getmtime(os.path.join(csrc, f)) <= built for f in srcs)
-    except (OSError, AttributeError):
+        return libs.newer_than(LIB_PATH, ["Makefile", "flags.mk"] + libs.make_var("DEVICE_SRCS").split() + libs.make_var("HOST_SRCS").split())
+    except OSError:
         return False
 
 
@@ -203,40 +168,12 @@ def _one_hip_runtime():
 
 
 def load():
-    """dlopen the library (building it first if the .so is missing) and declare the prototypes."""
+    """dlopen the library (libs.open_library: built first unless it is current, its two ids checked unless it was) and declare the prototypes."""
     global _lib
     if _lib is not None:
         return _lib
-    check_id = False
-    if os.environ.get("YF_LIB_PATH"):
-        pass
-    elif os.environ.get("YF_NO_BUILD") == "1" or library_is_current():
-        # no child process at all (profiler runs set YF_NO_BUILD=1: tools/profile_*.sh); a library built from other sources is refused below
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"YF_NO_BUILD=1 and {LIB_PATH} does not exist: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        check_id = True
-    else:
-        try:
-            build()              # `make`: a stale .so is never loaded under fresh sources
-        except (OSError, subprocess.CalledProcessError) as e:
-            # no make / no hipcc on this box (or the build failed): an existing library is used if -- and only if -- it was built from these
-            # sources with these flags (its baked-in id against the id computed here)
-            if not os.path.exists(LIB_PATH):
-                raise
-            import warnings
-            warnings.warn(f"stm32h7-yolo_amd: could not run the build ({e}); loading the existing library after checking its device and host build ids")
-            check_id = True
-    _one_hip_runtime()
-    lib = ctypes.CDLL(LIB_PATH)
-    if check_id:
-        lib.yf_network_build_id.restype = ctypes.c_char_p
-        have, want = (lib.yf_network_build_id() or b"").decode(), expected_build_id()
-        if have != want:
-            raise RuntimeError(f"{LIB_PATH} was built from other sources or flags (build id {have}, expected {want}) and is not being rebuilt here (no make / YF_NO_BUILD=1)")
-        lib.yf_network_host_id.restype = ctypes.c_char_p
-        have, want = (lib.yf_network_host_id() or b"").decode(), expected_host_id()
-        if have != want:
-            raise RuntimeError(f"{LIB_PATH}: its C host layer was built from other sources (host id {have}, expected {want}) and is not being rebuilt here (no make / YF_NO_BUILD=1)")
+    lib = libs.open_library(LIB_PATH, library_is_current, [("yf_network_build_id", expected_build_id), ("yf_network_host_id", expected_host_id)],
+                            unchecked_override=True, preload=_one_hip_runtime)
     vp, cl = ctypes.c_void_p, ctypes.c_long
     lib.ai_network_create.restype = AiError
     lib.ai_network_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(AiBuffer)]

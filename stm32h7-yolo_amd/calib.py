@@ -8,17 +8,12 @@ The evaluation is float32 with the arithmetic csrc/yf_calib_arith.h defines (DES
 arithmetic on the CPU (libyf_calib_host.so), bit for bit.  Unlike libyf_images.so the library needs no network: it links the HIP runtime only.
 """
 import ctypes
-import hashlib
 import os
-import re
-import subprocess
 
 import numpy as np
 
-from . import binding
+from . import binding, libs
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_PKG, "csrc")
 N_RANGES = 47
 FRAME_BYTES = 56 * 56 * 3
 LOGITS = 7 * 7 * 18
@@ -30,35 +25,22 @@ class CalibError(RuntimeError):
 
 def lib_path():
     """libyf_calib.so in the package's lib/: it shares nothing with libyf_network.so, so a YF_LIB_PATH override of that one does not move it."""
-    return os.path.join(_PKG, "lib", "libyf_calib.so")
+    return os.path.join(libs.LIB_DIR, "libyf_calib.so")
 
 
 def host_lib_path():
-    return os.path.join(_PKG, "lib", "libyf_calib_host.so")
-
-
-def _makefile_var(name):
-    mk = open(os.path.join(_CSRC, "Makefile")).read()
-    return re.search(r"^%s\s*=\s*(.*)$" % name, mk, re.M).group(1).strip()
+    return os.path.join(libs.LIB_DIR, "libyf_calib_host.so")
 
 
 def expected_build_id():
     """The id csrc/Makefile bakes into libyf_calib.so (yf_calib_build_id): sha256 over CALIB_SRCS, CALIBFLAGS and the CFLAGS of the parser."""
-    h = hashlib.sha256()
-    for f in _makefile_var("CALIB_SRCS").split():
-        h.update(open(os.path.join(_CSRC, f), "rb").read())
-    h.update((_makefile_var("CALIBFLAGS") + "|" + _makefile_var("CFLAGS") + "\n").encode())
-    return h.hexdigest()[:16]
+    return libs.source_id(libs.make_var("CALIB_SRCS").split(), libs.make_var("CALIBFLAGS") + "|" + libs.make_var("CFLAGS") + "\n")
 
 
 def library_is_current():
     """True when the in-tree libyf_calib.so can be loaded without running make: it is newer than its sources and the Makefile.  Its baked-in
     id is still checked after loading."""
-    try:
-        built = os.path.getmtime(lib_path())
-        return all(os.path.getmtime(os.path.join(_CSRC, f)) <= built for f in _makefile_var("CALIB_SRCS").split() + ["Makefile"])
-    except (OSError, AttributeError):
-        return False
+    return libs.newer_than(lib_path(), libs.make_var("CALIB_SRCS").split() + ["Makefile"])
 
 
 _lib = None
@@ -71,29 +53,9 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    path = lib_path()
-    check_id = False
-    if os.environ.get("YF_NO_BUILD") == "1" or library_is_current():
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} does not exist: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        check_id = True
-    else:
-        try:
-            binding.build()                     # `make all` builds every library
-        except (OSError, subprocess.CalledProcessError) as e:
-            if not os.path.exists(path):
-                raise
-            import warnings
-            warnings.warn(f"stm32h7-yolo_amd.calib: could not run the build ({e}); loading the existing library after checking its build id")
-            check_id = True
-    binding._one_hip_runtime()
-    lib = ctypes.CDLL(path)
+    lib = libs.open_library(lib_path(), library_is_current, [("yf_calib_build_id", expected_build_id)], preload=binding._one_hip_runtime)
     lib.yf_calib_build_id.restype = ctypes.c_char_p
     lib.yf_calib_build_id.argtypes = []
-    if check_id:
-        have, want = (lib.yf_calib_build_id() or b"").decode(), expected_build_id()
-        if have != want:
-            raise RuntimeError(f"{path} was built from other sources (build id {have}, expected {want}) and is not being rebuilt here")
     vp = ctypes.c_void_p
     lib.yf_calib_create.restype, lib.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
     lib.yf_calib_observe_device.restype, lib.yf_calib_observe_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp]
@@ -106,26 +68,11 @@ def load():
     return lib
 
 
-def host_library_is_current():
-    try:
-        built = os.path.getmtime(host_lib_path())
-        srcs = ["yf_calib_host.c", "yf_calib_arith.h", "yf_yfw.c", "yf_yfw.h", "gen/yf_graph_gen.h", "../../include/yf_calib.h", "Makefile"]
-        return all(os.path.getmtime(os.path.join(_CSRC, f)) <= built for f in srcs)
-    except OSError:
-        return False
-
-
 def load_host():
-    """libyf_calib_host.so (no HIP, no GPU), built on first use when it is missing or older than its sources, under the lock file that
-    binding.build takes: one make at a time in a checkout."""
+    """libyf_calib_host.so (no HIP, no GPU) through libs.host_library, which brings it up to date first."""
     global _host
     if _host is None:
-        if not host_library_is_current():
-            import fcntl
-            with open(os.path.join(_CSRC, ".build.lock"), "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                subprocess.check_call(["make", "-C", _CSRC, "../lib/libyf_calib_host.so"], stdout=subprocess.DEVNULL)
-        lib = ctypes.CDLL(host_lib_path())
+        lib = libs.host_library("libyf_calib_host.so")
         vp = ctypes.c_void_p
         lib.yf_calib_host_run.restype = ctypes.c_long
         lib.yf_calib_host_run.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]

@@ -14,17 +14,11 @@ the decode in float32 (`run_decode_f16_ragged_device`; the arithmetic: csrc/yf_i
 `average_precision_device` on the same stream, without the records leaving the GPU (the arithmetic: csrc/yf_images_eval.h).
 """
 import ctypes
-import hashlib
 import os
-import re
-import subprocess
 
 import numpy as np
 
-from . import binding
-
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_PKG, "csrc")
+from . import binding, libs
 
 YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8 = 0, 1, 2, 3
 FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba": YF_PIX_RGBA8}
@@ -62,27 +56,18 @@ def lib_path():
 
 
 def _images_srcs():
-    mk = open(os.path.join(_CSRC, "Makefile")).read()
-    return re.search(r"^IMAGES_SRCS\s*=\s*(.*)$", mk, re.M).group(1).split()
+    return libs.make_var("IMAGES_SRCS").split()
 
 
 def expected_build_id():
     """The id csrc/Makefile bakes into libyf_images.so (yf_images_build_id): sha256 over IMAGES_SRCS and flags.mk."""
-    h = hashlib.sha256()
-    for f in _images_srcs() + ["flags.mk"]:
-        h.update(open(os.path.join(_CSRC, f), "rb").read())
-    return h.hexdigest()[:16]
+    return libs.source_id(_images_srcs() + ["flags.mk"], "")
 
 
 def library_is_current():
     """True when the in-tree libyf_images.so can be loaded without running make: it is newer than its sources, the Makefile, flags.mk and
     the libyf_network.so it links against.  Its baked-in id is still checked after loading."""
-    try:
-        built = os.path.getmtime(lib_path())
-        deps = [os.path.join(_CSRC, f) for f in _images_srcs() + ["Makefile", "flags.mk"]] + [binding.LIB_PATH]
-        return all(os.path.getmtime(p) <= built for p in deps)
-    except (OSError, AttributeError):
-        return False
+    return libs.newer_than(lib_path(), _images_srcs() + ["Makefile", "flags.mk", binding.LIB_PATH])
 
 
 def _entries():
@@ -126,29 +111,10 @@ def load():
         return _lib
     binding.load()
     path = lib_path()
-    check_id = False
-    if os.environ.get("YF_LIB_PATH"):
-        pass                                    # developer override of the network library: its sibling, unchecked (like binding.load)
-    elif os.environ.get("YF_NO_BUILD") == "1" or library_is_current():
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} does not exist: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        check_id = True
-    else:
-        try:
-            binding.build()                     # `make all` builds both libraries
-        except (OSError, subprocess.CalledProcessError) as e:
-            if not os.path.exists(path):
-                raise
-            import warnings
-            warnings.warn(f"stm32h7-yolo_amd.images: could not run the build ({e}); loading the existing library after checking its build id")
-            check_id = True
-    lib = ctypes.CDLL(path)
+    # (a YF_LIB_PATH override of the network library: its sibling, unchecked like binding.load; `make all` builds both libraries)
+    lib = libs.open_library(path, library_is_current, [("yf_images_build_id", expected_build_id)], unchecked_override=True)
     lib.yf_images_build_id.restype = ctypes.c_char_p
     lib.yf_images_build_id.argtypes = []
-    if check_id:
-        have, want = (lib.yf_images_build_id() or b"").decode(), expected_build_id()
-        if have != want:
-            raise RuntimeError(f"{path} was built from other sources (build id {have}, expected {want}) and is not being rebuilt here")
     for name, argtypes in _ENTRIES.items():
         fn = getattr(lib, "yf_images_" + name)
         fn.restype, fn.argtypes = ctypes.c_long, argtypes

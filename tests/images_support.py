@@ -7,12 +7,12 @@ copy with one change, a stable sort (ties later record first).  `nms_reference_l
 import ctypes
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_libs import host_library
 
 PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
 
@@ -55,10 +55,8 @@ def host():
 
 # ---- the host build of the library's arithmetic ----
 def host_lib(build=True):
-    """libyf_images_host.so (csrc/yf_images_host.c) with every prototype set"""
-    if build:
-        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
+    """libyf_images_host.so (csrc/yf_images_host.c) with every prototype set; build=False: the file as it is, without make"""
+    lib = host_library("libyf_images_host.so") if build else ctypes.CDLL(os.path.join(PKG, "lib", "libyf_images_host.so"))
     lib.yfi_resize_host.restype = ctypes.c_int
     lib.yfi_resize_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_void_p]

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_libs import host_library
 
-PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
 FP32, GENERIC = 0x10, 0x100
 N_DENSE, N_DW, N_ADD, N_CS = 17, 7, 3, 24
 DENSE_OPS = [1, 5, 6, 12, 13, 17, 19, 23, 29, 30, 34, 36, 40, 42, 47, 51, 53]
@@ -48,8 +48,7 @@ class Index(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def prep():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_hostprep.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_hostprep.so"))
+    lib = host_library("libyf_hostprep.so")
     lib.yf_prepare_tables_rounding.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(Index)]
     blob = (ctypes.c_uint8 * 11304).in_dll(lib, "yf_weights_blob")
 

@@ -3,12 +3,12 @@ against the oracle's independent fixed-point statement.  No GPU, no compute call
 import ctypes
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_libs import host_library, libs
 
 PKG = os.path.join(ROOT, "stm32h7-yolo_amd")
 N_DENSE, N_DW, N_ADD, N_LUT, N_CS = 17, 7, 3, 19, 24
@@ -43,8 +43,7 @@ class Index(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def prep():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_hostprep.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_hostprep.so"))
+    lib = host_library("libyf_hostprep.so")
     lib.yf_prepare_tables.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(Index)]
     lib.yf_quantize_multiplier.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]
     lib.yf_mbqm.restype = ctypes.c_int32
@@ -66,7 +65,7 @@ def pack():
 def test_table_layout_matches_the_plan_compiled_into_the_kernels(prep):
     """The kernels address the table blob at compile-time offsets (yf_kernels.hip.h, TablePlan); the host preparation
     lays the blob out at run time.  Both must agree (the engine refuses to start otherwise)."""
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc")], stdout=subprocess.DEVNULL)
+    libs.make("all")
     net = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_network.so"))
     n = 43 + 3 * N_CS
     plan = (ctypes.c_int32 * n)()

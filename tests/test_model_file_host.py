@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, GOLDEN, REFERENCE, has_reference
+from host_libs import host_library
 import requant_models as rm
 from oracle.np_restatement import quantize_multiplier, mbqm
 from test_host_logic import Index, N_LUT, DENSE_OPS, DW_OPS, LEAKY_LUT_IDS, _chan, O as ACC_OFFSET
@@ -41,8 +42,7 @@ class ModelFile(ctypes.Structure):                  # yf_model_file, csrc/yf_mod
 
 @pytest.fixture(scope="module")
 def hp():
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_hostprep.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_hostprep.so"))
+    lib = host_library("libyf_hostprep.so")
     lib.yf_model_file_parse.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ModelFile), ctypes.c_char_p, ctypes.c_size_t]
     lib.yf_prepare_tables_model.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(Index)]

@@ -3,13 +3,13 @@ epilogue's identities on the tables prepared from blobs that sit on that bound, 
 informative (a green GPU run must not mean "everything saturated to one answer").  No GPU, no compute calls of the product."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import model_variants as mv
 from conftest import ROOT
+from host_libs import host_library
 from test_host_logic import Index, O, PKG, _chan, _device_requant, _device_requant3
 
 INT_ROUNDINGS = [0, 1, 2, 3, 0x100, 0x101, 0x102, 0x103]
@@ -19,8 +19,7 @@ SENTINEL = 0x5A5A5A5A           # *out_blob before the call
 @pytest.fixture(scope="module")
 def prepare():
     """prepare(blob, rounding) -> (return code, index, table bytes or None, *out_blob afterwards) of yf_prepare_tables_rounding"""
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "../lib/libyf_hostprep.so"], stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(PKG, "lib", "libyf_hostprep.so"))
+    lib = host_library("libyf_hostprep.so")
     lib.yf_prepare_tables_rounding.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(Index)]
     libc = ctypes.CDLL(None)
     libc.free.argtypes = [ctypes.c_void_p]

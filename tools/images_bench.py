@@ -13,7 +13,6 @@ import argparse
 import ctypes
 import importlib
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -69,8 +68,7 @@ def main():
     images = importlib.import_module("stm32h7-yolo_amd.images")
     net = yf.Network(device=0).init()
     lib = images.load()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "stm32h7-yolo_amd", "csrc"), "../lib/libyf_images_host.so"], stdout=subprocess.DEVNULL)
-    host = ctypes.CDLL(os.path.join(ROOT, "stm32h7-yolo_amd", "lib", "libyf_images_host.so"))
+    host = importlib.import_module("stm32h7-yolo_amd.libs").host_library("libyf_images_host.so")
     host.yfi_tap_host.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
