@@ -60,10 +60,39 @@ YF_CALIB_API const char* yf_calib_last_error_text(void);
 /* sha256 (16 hex digits) over the library's sources and flags, as csrc/Makefile computed it (calib.py recomputes it). */
 YF_CALIB_API const char* yf_calib_build_id(void);
 
+/* ---- Quantisation error per tensor: an int8 run of the network against the float32 evaluation of the same frames (csrc/yf_calib_compare.h,
+ * DESIGN.md "Comparison arithmetic").  An entry names one of the 46 tensors the evaluation produces (the tensors of yf_calib_ranges without
+ * the input) and where some int8 run left its values: unpadded NHWC bytes, frame f's at q + f * frame_stride, with the scale and zero point
+ * that give them a real value.  yf_network_run_device_dump writes such tensors (yf_network_dump_offset), and the heads are tensor 100. */
+typedef struct {
+  int32_t tensor, zero_point;
+  float scale;
+  uint32_t reserved;
+  const void* q;        /* frame 0's first byte of this tensor */
+  size_t frame_stride;
+} yf_calib_qtensor;
+
+#define YF_CALIB_FRAME_STATS_BYTES 32 /* {double sum_err, sum_sq_err, sum_sq_ref; float max_abs_err; int32_t saturated}: error = dequantised - float */
+#define YF_CALIB_TOTALS_BYTES 48      /* {double sum_err, sum_sq_err, sum_sq_ref; float max_abs_err; uint32_t reserved; int64_t saturated, elements} */
+
+/* Evaluates d_frames int8 [n][56][56][3] and compares every listed tensor with its int8 values (device memory): one record per frame and
+ * entry to d_frame_stats [n][count], and, unless d_totals is NULL, the sums over the frames in ascending order to d_totals [count].
+ * Asynchronous on `stream`; `entries` is host memory and is not referenced after the call returns.  Touches neither the handle's ranges nor
+ * yf_calib_frames_observed.  Returns n, or a value <= 0 after a failure: yf_calib_last_error_text() then names the entry index, the field,
+ * the value found and the value expected (a tensor outside the 46 or listed twice, a scale that is not finite and positive, a zero point
+ * outside -128..127, a NULL q, frame_stride below the tensor's elements, count outside 1..46, n < 1). */
+YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                                          void* d_frame_stats, void* d_totals, void* stream);
+
 /* ---- libyf_calib_host.so only: the same evaluation on host arrays, on `threads` threads.  minmax / tensors as yf_calib_ranges fills them
  * (the ranges of these n frames alone), logits float [n][7][7][18] or NULL.  Returns n, or <= 0 with a text in err. */
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors,
                                     float* logits, int threads, char* err, size_t errlen);
+
+/* ... and the same comparison: q of every entry is a host pointer, frame_stats [n][count] and totals [count] (or NULL) host arrays.  If
+ * tensors_out is not NULL it receives the float32 tensors of the listed entries, [n][elements] per entry, concatenated in entry order. */
+YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_qtensor* entries, int count,
+                                        void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

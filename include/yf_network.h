@@ -290,6 +290,9 @@ YF_API long yf_network_run_device(ai_handle network, const void* d_in, void* d_o
  * reference observer API, ai_platform_interface.h:684-731).  d_dump int8[n][yf_network_dump_bytes()]. */
 YF_API long yf_network_run_device_dump(ai_handle network, const void* d_in, void* d_out, void* d_dump, long n, void* stream);
 YF_API long yf_network_dump_bytes(void);
+/* Byte offset of the output of tflite op `tflite_op` (its index in the graph, 0-based) inside one frame's dump record, or -1 where the dump has
+ * no record of that op.  The record is the op's int8 tensor, unpadded NHWC. */
+YF_API long yf_network_dump_offset(int tflite_op);
 /* The network is fully convolutional; the reference ABI fixes 56x56 (network.h:48-50).  This extension also runs
  * 160x160 frames (BASELINE configs[4]): d_in int8[n][h][w][3] -> d_out int8[n][h/8][w/8][18].  56x56 takes the fused
  * LDS-resident kernel, 160x160 runs the same stage code as four banded kernels (each a group of fused stages over row bands

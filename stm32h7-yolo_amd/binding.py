@@ -94,7 +94,7 @@ assert DET_DTYPE.itemsize == ctypes.sizeof(YfDet) == 28
 EXPORTS = ["ai_network_create", "ai_network_init", "ai_network_run", "ai_network_forward", "ai_network_get_error",
            "ai_network_destroy", "ai_network_get_info", "ai_network_get_report", "ai_network_data_weights_get",
            "ai_network_data_params_get", "ai_platform_bind_network_params", "yf_network_set_device",
-           "yf_network_configure", "yf_network_run_device", "yf_network_run_device_dump", "yf_network_dump_bytes", "yf_network_run_device_hw",
+           "yf_network_configure", "yf_network_run_device", "yf_network_run_device_dump", "yf_network_dump_bytes", "yf_network_dump_offset", "yf_network_run_device_hw",
            "yf_network_decode_device", "yf_network_run_decode_device", "yf_network_pack_detections_device", "yf_network_unpack_detections_device", "yf_network_prepare_rgb565_device", "yf_network_run_camera_device", "yf_network_time_device",
            "yf_network_time_stages", "yf_network_format_uart", "yf_network_shard_range", "yf_network_table_plan", "yf_network_all_gather_device", "yf_network_fp16_init", "yf_network_fp16_run_device", "yf_network_fp16_ready", "yf_network_release_stream", "yf_network_scratch_bytes", "yf_network_scratch_stats", "yf_network_set_requant_rounding", "yf_network_get_requant_rounding", "yf_network_init_model", "yf_network_decode_tables", "yf_network_last_error_text",
            "yf_network_kernel_name", "yf_network_kernel_name_for", "yf_network_build_id", "yf_network_host_id",
@@ -204,6 +204,7 @@ def load():
     lib.yf_network_run_device_dump.restype = cl
     lib.yf_network_run_device_dump.argtypes = [vp, vp, vp, vp, cl, vp]
     lib.yf_network_dump_bytes.restype = cl
+    lib.yf_network_dump_offset.restype, lib.yf_network_dump_offset.argtypes = cl, [ctypes.c_int]
     lib.yf_network_run_device_hw.restype = cl
     lib.yf_network_run_device_hw.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, cl, vp]
     lib.yf_network_decode_device.restype = cl
@@ -491,6 +492,10 @@ class Network:
 
     def dump_bytes(self):
         return self.lib.yf_network_dump_bytes()
+
+    def dump_offset(self, tflite_op):
+        """Byte offset of the output of tflite op `tflite_op` inside one frame's dump record, or -1: the dump has no record of that op."""
+        return self.lib.yf_network_dump_offset(int(tflite_op))
 
     def report(self):
         r = AiNetworkReport()

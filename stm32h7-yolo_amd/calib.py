@@ -6,8 +6,14 @@ retrained float weights to a model the int8 engine runs:
 
 The evaluation is float32 with the arithmetic csrc/yf_calib_arith.h defines ("Calibration arithmetic"); `host_run` is the same
 arithmetic on the CPU (libyf_calib_host.so), bit for bit.  Unlike libyf_images.so the library needs no network: it links the HIP runtime only.
+
+Where a quantised model lost precision: Calibration.compare sets the int8 tensors of a run of the engine (Network.run_device with a dump, the
+heads) against the float32 tensors of the same frames, per tensor, with the arithmetic csrc/yf_calib_compare.h defines (DESIGN.md,
+"Comparison arithmetic"); host_compare is the same on the CPU, bit for bit; quantisation_report makes the table of a .yfw / .yfm pair.
 """
+import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -17,6 +23,22 @@ from . import binding, libs
 N_RANGES = 47
 FRAME_BYTES = 56 * 56 * 3
 LOGITS = 7 * 7 * 18
+MAX_ENTRIES = N_RANGES - 1
+# the records of a comparison (csrc/yf_calib_compare.h): per frame and entry, and per entry over the frames.  error = dequantised - float
+FRAME_STATS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("saturated", "<i4")])
+TOTALS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("reserved", "<u4"),
+                   ("saturated", "<i8"), ("elements", "<i8")])
+assert FRAME_STATS.itemsize == 32 and TOTALS.itemsize == 48
+
+# One tensor of an int8 run: the tflite tensor id, its scale and zero point, and where its values lie -- q: frame 0's first byte (a device tensor
+# or address for Calibration.compare, an int8 numpy array for host_compare), frame_stride: bytes from one frame's tensor to the next's.
+Entry = collections.namedtuple("Entry", "tensor scale zero_point q frame_stride")
+
+
+class QTensor(ctypes.Structure):
+    """yf_calib_qtensor (include/yf_calib.h)"""
+    _fields_ = [("tensor", ctypes.c_int32), ("zero_point", ctypes.c_int32), ("scale", ctypes.c_float), ("reserved", ctypes.c_uint32),
+                ("q", ctypes.c_void_p), ("frame_stride", ctypes.c_size_t)]
 
 
 class CalibError(RuntimeError):
@@ -59,6 +81,8 @@ def load():
     vp = ctypes.c_void_p
     lib.yf_calib_create.restype, lib.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
     lib.yf_calib_observe_device.restype, lib.yf_calib_observe_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp]
+    lib.yf_calib_compare_device.restype = ctypes.c_long
+    lib.yf_calib_compare_device.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
     lib.yf_calib_ranges.restype, lib.yf_calib_ranges.argtypes = ctypes.c_int, [vp, vp, vp]
     lib.yf_calib_reset.restype, lib.yf_calib_reset.argtypes = ctypes.c_int, [vp]
     lib.yf_calib_frames_observed.restype, lib.yf_calib_frames_observed.argtypes = ctypes.c_long, [vp]
@@ -76,8 +100,57 @@ def load_host():
         vp = ctypes.c_void_p
         lib.yf_calib_host_run.restype = ctypes.c_long
         lib.yf_calib_host_run.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_host_compare.restype = ctypes.c_long
+        lib.yf_calib_host_compare.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp,
+                                              ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
         _host = lib
     return _host
+
+
+def _address(q):
+    if q is None:
+        return None
+    if hasattr(q, "data_ptr"):
+        return q.data_ptr()
+    if isinstance(q, np.ndarray):
+        return q.ctypes.data
+    return int(q)
+
+
+def _qtensors(entries):
+    """[Entry] -> a ctypes array of yf_calib_qtensor.  Nothing is checked here: the library's one validation names what it refuses."""
+    arr = (QTensor * max(len(entries), 1))()
+    for i, e in enumerate(entries):
+        arr[i] = QTensor(int(e.tensor), int(e.zero_point), float(e.scale), 0, _address(e.q), int(e.frame_stride))
+    return arr
+
+
+def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elements=None):
+    """The comparison on the CPU: int8 frames [n, 56, 56, 3] and entries whose q are int8 numpy arrays -> (per-frame records, a FRAME_STATS
+    array [n, count]; totals, a TOTALS array [count]; and, with want_tensors, the float32 tensors of the listed entries, one [n, elements]
+    array per entry -- `elements` then gives each entry's element count).  A refused argument raises CalibError with the library's text."""
+    lib = load_host()
+    x = np.ascontiguousarray(frames, np.int8).reshape(-1, 56, 56, 3)
+    n, count = x.shape[0], len(entries)
+    stats, totals = np.zeros((n, max(count, 1)), FRAME_STATS), np.zeros(max(count, 1), TOTALS)
+    flat = None
+    if want_tensors:
+        if elements is None or len(elements) != count:
+            raise ValueError("want_tensors: `elements` must give every entry's element count")
+        flat = np.zeros(n * int(sum(elements)), np.float32)
+    err = ctypes.create_string_buffer(400)
+    rc = lib.yf_calib_host_compare(bytes(yfw_bytes), len(yfw_bytes), x.ctypes.data, n, _qtensors(entries), count, stats.ctypes.data,
+                                   totals.ctypes.data, flat.ctypes.data if want_tensors else None, int(threads), err, 400)
+    if rc != n or n < 1:
+        raise CalibError(f"yf_calib_host_compare: {err.value.decode()} (returned {rc}, expected {n})")
+    stats, totals = stats[:, :count], totals[:count]
+    if not want_tensors:
+        return stats, totals
+    at, tensors = 0, []
+    for e in elements:
+        tensors.append(flat[at:at + n * e].reshape(n, e))
+        at += n * e
+    return stats, totals, tensors
 
 
 def _ranges_dict(minmax, ids):
@@ -143,6 +216,31 @@ class Calibration:
         self._keep, self.logits = frames, out       # the launch is asynchronous: the frames stay alive until the next call
         return n
 
+    def compare(self, frames, entries, stream=None):
+        """The per-tensor error of an int8 run against the float32 evaluation of the same `frames` (as observe takes them).  entries: a list of
+        Entry whose q are int8 device tensors (or device addresses).  Returns (the per-frame records, a uint8 device tensor [n, count, 32]:
+        FRAME_STATS, see frame_stats_array; the totals, a TOTALS numpy array [count]).  Launches on torch's current stream (or `stream`, a raw
+        hipStream_t) and synchronises the device for the totals.  The handle's ranges and frames_observed are not touched."""
+        import torch
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.array(frames, np.int8))
+        dev = torch.device("cuda", self.device)
+        if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES:
+            raise ValueError(f"frames: expected int8 [n, 56, 56, 3], got {frames.dtype} {tuple(frames.shape)}")
+        frames = frames.to(dev).contiguous()
+        n, count = frames.numel() // FRAME_BYTES, len(entries)
+        d_stats = torch.zeros((n, max(count, 1), FRAME_STATS.itemsize), dtype=torch.uint8, device=dev)
+        d_totals = torch.zeros((max(count, 1), TOTALS.itemsize), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if stream is not None:
+            torch.cuda.synchronize(dev)                                              # the zeroed outputs were made on torch's stream
+        rc = self._lib.yf_calib_compare_device(self.handle, frames.data_ptr() if n else None, n, _qtensors(entries), count, d_stats.data_ptr(),
+                                               d_totals.data_ptr(), s)
+        if rc != n or n < 1:
+            raise CalibError(f"yf_calib_compare_device: {self._text()} (returned {rc}, expected {n})")
+        torch.cuda.synchronize(dev)                                                  # frames and the entries' tensors are no longer read
+        return d_stats[:, :count], d_totals[:count].cpu().numpy().view(TOTALS).reshape(count)
+
     @property
     def frames_observed(self):
         return self._lib.yf_calib_frames_observed(self.handle)
@@ -183,3 +281,74 @@ def quantize_on_device(yfw_bytes, frames, device=None):
         return ptq.quantize_model(yfw_bytes, cal.ranges())
     finally:
         cal.destroy()
+
+
+def frame_stats_array(d_stats):
+    """The per-frame records of Calibration.compare (a device tensor) -> a FRAME_STATS numpy array [n, count]."""
+    a = d_stats.contiguous().cpu().numpy()
+    return a.view(FRAME_STATS).reshape(a.shape[0], a.shape[1])
+
+
+# the ops whose output the float evaluation holds as a tensor of its own: PAD, QUANTIZE and CONCATENATION only move values
+_EVALUATED = ("CONV_2D", "DEPTHWISE_CONV_2D", "LEAKY_RELU", "ADD", "MAX_POOL_2D")
+
+
+def report_tensors(dump_offset, yfm_bytes):
+    """The tensors a run of the engine leaves for a comparison, in op order: [dict(tensor, op, elements (per frame), scale, zero_point,
+    offset)].  The ops and shapes come from the graph the library is built for (model_file.load_graph), scale and zero point from the .yfm,
+    `offset` from dump_offset(op) (Network.dump_offset): every evaluated op the dump has a record of, and the network's output, whose
+    `offset` is None -- its values are the heads, not part of the dump."""
+    from . import model_file
+    graph, model = model_file.load_graph(), model_file.load_yfm(yfm_bytes)
+    codes = {model_file.OPCODE[k] for k in _EVALUATED}
+    out = []
+    for i, op in enumerate(graph["ops"]):
+        off, t = dump_offset(i), op["out"]
+        if op["op"] not in codes or (off < 0 and t != graph["output"]):
+            continue
+        q = model["tensors"][t]
+        out.append(dict(tensor=t, op=i, elements=int(np.prod(graph["tensors"][t]["shape"][1:])), scale=np.float32(q["scale"][0]),
+                        zero_point=int(q["zp"]), offset=None if t == graph["output"] else int(off)))
+    return out
+
+
+def report_rows(tensors, totals):
+    """report_tensors' list and the totals of a comparison of exactly these entries -> the table: one dict per tensor with tensor, op,
+    elements (all frames), scale, zero_point, mean_error, max_abs_error, mean_squared_error, rmse_over_scale, sqnr_db and saturated (the share
+    of the elements at -128 or 127).  error = dequantised int8 value - float32 value."""
+    rows = []
+    for t, r in zip(tensors, totals):
+        k, scale = int(r["elements"]), float(t["scale"])
+        mse, ref, err = float(r["sum_sq_err"]) / k, float(r["sum_sq_ref"]), float(r["sum_sq_err"])
+        rows.append(dict(tensor=t["tensor"], op=t["op"], elements=k, scale=scale, zero_point=t["zero_point"], mean_error=float(r["sum_err"]) / k,
+                         max_abs_error=float(r["max_abs_err"]), mean_squared_error=mse, rmse_over_scale=math.sqrt(mse) / scale,
+                         sqnr_db=10.0 * math.log10(ref / err) if err > 0.0 and ref > 0.0 else (math.inf if ref > 0.0 else -math.inf),
+                         saturated=int(r["saturated"]) / k))
+    return rows
+
+
+def quantisation_report(network, yfw_bytes, yfm_bytes, frames):
+    """Where the int8 model `yfm_bytes` loses precision against the float model `yfw_bytes` it was quantised from, over `frames` (int8
+    [n, 56, 56, 3], numpy or device): one row per tensor in op order (report_rows), TFLite's quantisation-debugger table for the model that
+    runs, under the rounding in force.  `network` is a Network initialised from yfm_bytes (init_model): it runs the frames with a dump of every
+    fused stage's tensor, and the dumped tensors and the heads are compared with the float32 evaluation on the GPU."""
+    import torch
+    dev = torch.device("cuda", network._device)
+    if not isinstance(frames, torch.Tensor):
+        frames = torch.from_numpy(np.ascontiguousarray(frames, np.int8))
+    if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES or frames.numel() == 0:
+        raise ValueError(f"frames: expected int8 [n, 56, 56, 3] with n >= 1, got {frames.dtype} {tuple(frames.shape)}")
+    d_x = frames.to(dev).contiguous()
+    n, dump_bytes = d_x.numel() // FRAME_BYTES, network.dump_bytes()
+    d_out = torch.zeros((n, LOGITS), dtype=torch.int8, device=dev)
+    d_dump = torch.zeros((n, dump_bytes), dtype=torch.int8, device=dev)
+    network.run_device(d_x.data_ptr(), d_out.data_ptr(), n, torch.cuda.current_stream(dev).cuda_stream, d_dump.data_ptr())
+    tensors = report_tensors(network.dump_offset, yfm_bytes)
+    entries = [Entry(t["tensor"], t["scale"], t["zero_point"], d_out.data_ptr() if t["offset"] is None else d_dump.data_ptr() + t["offset"],
+                     LOGITS if t["offset"] is None else dump_bytes) for t in tensors]
+    cal = Calibration(yfw_bytes, dev.index)
+    try:
+        _, totals = cal.compare(d_x, entries)
+    finally:
+        cal.destroy()
+    return report_rows(tensors, totals)

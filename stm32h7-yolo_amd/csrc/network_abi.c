@@ -489,6 +489,7 @@ YF_API long yf_network_run_device_dump(ai_handle network, const void* d_in, void
 }
 
 YF_API long yf_network_dump_bytes(void) { return yf_engine_dump_bytes(); }
+YF_API long yf_network_dump_offset(int tflite_op) { return yf_impl_dump_offset(tflite_op); }
 
 YF_API long yf_network_run_device_hw(ai_handle network, int height, int width, const void* d_in, void* d_out, long n, void* stream) {
   yf_context* c = ready(network);

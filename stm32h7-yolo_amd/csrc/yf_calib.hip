@@ -7,6 +7,11 @@
 // workgroup carries its running extremes in LDS across its frames.  Each workgroup leaves one partial table in global memory; a second,
 // one-workgroup launch folds the partials into the handle's ranges.  Minimum and maximum are exact, so the result does not depend on which
 // workgroup saw which frame, and nothing is ordered by arrival: no atomics.
+//
+// The comparing form (yf_calib_compare_device, csrc/yf_calib_compare.h) is the same evaluation without the extremes: where a stage produces a
+// listed tensor every thread reads the int8 value of each element it computed and accumulates the error terms in the defined order (a thread
+// is a lane, a wave a group); one record per frame and entry goes to global memory, and a second, one-workgroup launch adds the frames'
+// records in ascending frame order.  The entries travel as a kernel argument: a launch refers to nothing a later call rewrites.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -14,6 +19,7 @@
 #include <new>
 #include "../../include/yf_calib.h"
 #include "yf_calib_arith.h"
+#include "yf_calib_compare.h"
 #include "yf_yfw.h"
 
 #ifndef YF_CALIB_BUILD_ID
@@ -28,6 +34,14 @@ constexpr size_t kLdsBytes = sizeof(float) * (YFC_ARENA_FLOATS + kRedFloats + kW
 constexpr int kParamFloats = YFC_INPUT_TABLE + YF_YFW_FLOATS;
 static_assert(kLdsBytes <= 160 * 1024, "the arena and the reduction scratch must fit the CU's LDS");
 static_assert(YFC_LOGITS_OFF + YFC_LOGITS <= YFC_ARENA_FLOATS, "logits inside the arena");
+// the comparing form: three tensors x 16 waves x one record, double-buffered like `red`, beside the arena (and it would fit beside the
+// extremes' scratch as well)
+constexpr int kCmpRecords = 2 * 3 * kWaves;
+constexpr size_t kCmpLdsBytes = sizeof(float) * YFC_ARENA_FLOATS + sizeof(yfc_cmp_frame) * kCmpRecords;
+static_assert(kLdsBytes + sizeof(yfc_cmp_frame) * kCmpRecords <= 160 * 1024, "the arena and both reduction scratches must fit the CU's LDS");
+static_assert(sizeof(float) * YFC_ARENA_FLOATS % alignof(yfc_cmp_frame) == 0 && kThreads == YFC_CMP_LANES && kWaves == YFC_CMP_GROUPS, "compare layout");
+constexpr int kTotalsThreads = 320;
+static_assert(kTotalsThreads >= YFC_CMP_MAX_ENTRIES * YFC_CMP_FIELDS, "one thread per entry and field");
 
 __device__ inline float wave_min(float v) {
   for (int o = 32; o; o >>= 1) { const float t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
@@ -122,6 +136,88 @@ __global__ __launch_bounds__(128) void yfc_merge_kernel(const float* __restrict_
   ranges[t] = v;
 }
 
+// s[l] = s[l] + s[l + h] for l < h, h = 32 .. 1: lane 0 ends with the group's value (the other lanes' values are not used)
+__device__ inline void wave_join(yfc_cmp_frame& a) {
+  for (int h = 32; h; h >>= 1) {
+    yfc_cmp_frame b;
+    b.sum_err = __shfl_down(a.sum_err, h, 64);
+    b.sum_sq_err = __shfl_down(a.sum_sq_err, h, 64);
+    b.sum_sq_ref = __shfl_down(a.sum_sq_ref, h, 64);
+    b.max_abs_err = __shfl_down(a.max_abs_err, h, 64);
+    b.saturated = __shfl_down(a.saturated, h, 64);
+    yfc_cmp_join(&a, &b);
+  }
+}
+
+// The threads' accumulators of one stage (acc[3], entries[3] with -1 for none) -> the frame's records row[entry]: the 16 wave values meet in
+// LDS and one thread per tensor adds them in wave order.  `red` alternates between two halves as in fold().
+__device__ inline void compare_fold(const yfc_cmp_frame acc[3], const int entries[3], yfc_cmp_frame* red, yfc_cmp_frame* row, int& parity) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  yfc_cmp_frame* half = red + parity * 3 * kWaves;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if (entries[j] < 0) continue;                                                   // uniform
+    yfc_cmp_frame a = acc[j];
+    wave_join(a);
+    if (lane == 0) half[j * kWaves + wave] = a;
+  }
+  __syncthreads();                                                                  // also: the stage's output is in the arena
+  const int entry = tid == 0 ? entries[0] : tid == 1 ? entries[1] : entries[2];
+  if (tid < 3 && entry >= 0) {
+    yfc_cmp_frame a = half[tid * kWaves];
+    for (int w = 1; w < kWaves; ++w) yfc_cmp_join(&a, &half[tid * kWaves + w]);
+    row[entry] = a;
+  }
+  parity ^= 1;
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_compare_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                const yfc_stage* __restrict__ stages, const yfc_cmp_plan plan,
+                                                                yfc_cmp_frame* __restrict__ frame_stats) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* arena = lds;
+  yfc_cmp_frame* red = reinterpret_cast<yfc_cmp_frame*>(lds + YFC_ARENA_FLOATS);
+  const int tid = threadIdx.x;
+  int parity = 0;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
+    for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) arena[i] = params[(int)q[i] + 128];
+    __syncthreads();
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int entries[3] = {plan.entry[s][0], plan.entry[s][1], plan.entry[s][2]};
+      const int8_t* qt[3] = {nullptr, nullptr, nullptr};
+      float scale[3] = {0.0f, 0.0f, 0.0f};
+      int zp[3] = {0, 0, 0};
+      yfc_cmp_frame acc[3];                                                         // (per frame and stage: every frame starts from +0)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        yfc_cmp_zero(&acc[j]);
+        if (entries[j] < 0) continue;
+        qt[j] = plan.q[entries[j]] + (size_t)f * plan.frame_stride[entries[j]];
+        scale[j] = plan.scale[entries[j]];
+        zp[j] = plan.zero_point[entries[j]];
+      }
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (entries[j] >= 0) yfc_cmp_add(&acc[j], qt[j][idx], zp[j], scale[j], v[j]);
+      }
+      compare_fold(acc, entries, red, frame_stats + (size_t)f * plan.count, parity);
+    }
+  }
+}
+
+// totals[entry] = the frames' records added in ascending frame order: one thread per entry and field
+__global__ __launch_bounds__(kTotalsThreads) void yfc_totals_kernel(const yfc_cmp_frame* __restrict__ frame_stats, long n, const yfc_cmp_plan plan,
+                                                                     yfc_cmp_total* __restrict__ totals) {
+  const int entry = threadIdx.x / YFC_CMP_FIELDS, field = threadIdx.x % YFC_CMP_FIELDS;
+  if (entry < plan.count) yfc_cmp_total_field(frame_stats, n, plan.count, entry, plan.elements[entry], field, &totals[entry]);
+}
+
 thread_local char g_err[320];
 
 #define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
@@ -154,6 +250,7 @@ struct yf_calib {
   float* d_partials = nullptr;
   float* d_ranges = nullptr;
   int32_t tensors[YFC_N_RANGES];
+  yfc_stage stages[YFC_N_STAGES];
 };
 
 static bool upload_empty_ranges(yf_calib* c) {
@@ -186,7 +283,7 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
   yf_calib* c = new (std::nothrow) yf_calib;
   if (!c) { delete[] p; set_error("yf_calib_create: out of memory"); return nullptr; }
   c->device = device;
-  yfc_stage stages[YFC_N_STAGES];
+  yfc_stage (&stages)[YFC_N_STAGES] = c->stages;
   yfc_build_stages(stages, c->tensors);
   const yfc_stage& last = stages[YFC_N_STAGES - 1];
   bool ok = last.b_off + last.cout == kParamFloats && last.out_off == YFC_LOGITS_OFF;
@@ -199,6 +296,8 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
     c->grid_max = cus;                                     // 156.8 KB of LDS: one workgroup per CU
     ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_observe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes),
                       "hipFuncSetAttribute(max dynamic LDS)")
+         && hip_ok(hipFuncSetAttribute((const void*)yfc_compare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCmpLdsBytes),
+                   "hipFuncSetAttribute(max dynamic LDS, compare)")
          && hip_ok(hipMalloc((void**)&c->d_params, sizeof(float) * kParamFloats), "hipMalloc(params)")
          && hip_ok(hipMalloc((void**)&c->d_stages, sizeof stages), "hipMalloc(stages)")
          && hip_ok(hipMalloc((void**)&c->d_partials, sizeof(float) * kWgFloats * (size_t)cus), "hipMalloc(partials)")
@@ -232,6 +331,27 @@ YF_CALIB_API long yf_calib_observe_device(yf_calib* c, const void* d_frames, lon
   hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, s, (const float*)c->d_partials, grid, c->d_ranges);
   if (!hip_ok(hipGetLastError(), "yf_calib_observe_device: launch of the merge")) return -2;
   c->frames += n;
+  return n;
+}
+
+YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                                          void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_compare_device: NULL handle"); return -1; }
+  yfc_cmp_plan plan;
+  if (yfc_cmp_validate(c->stages, entries, count, n, &plan, g_err, sizeof g_err)) return -1;
+  if (!d_frames || !d_frame_stats) { set_error("yf_calib_compare_device: NULL %s", d_frames ? "d_frame_stats" : "d_frames"); return -1; }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
+  hipLaunchKernelGGL(yfc_compare_kernel, dim3(grid), dim3(kThreads), kCmpLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
+                     (const yfc_stage*)c->d_stages, plan, (yfc_cmp_frame*)d_frame_stats);
+  if (!hip_ok(hipGetLastError(), "yf_calib_compare_device: launch of the evaluation")) return -2;
+  if (d_totals) {
+    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
+    if (!hip_ok(hipGetLastError(), "yf_calib_compare_device: launch of the totals")) return -2;
+  }
   return n;
 }
 

@@ -6,6 +6,7 @@
 #include <string.h>
 #include "../../include/yf_calib.h"
 #include "yf_calib_arith.h"
+#include "yf_calib_compare.h"
 #include "yf_yfw.h"
 
 typedef struct {
@@ -93,5 +94,99 @@ YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t*
   free(jobs);
   free(p);
   if (failed) REFUSE("yf_calib_host_run: could not start a thread or allocate its arena");
+  return n;
+}
+
+/* ---- the comparison (yf_calib_compare.h): the evaluation again, with the lanes of the defined order as an array ---- */
+typedef struct {
+  const yfc_stage* stages;
+  const float* params;
+  const int8_t* frames;
+  const yfc_cmp_plan* plan;
+  const size_t* out_off;                                /* where entry e's [n][elements] block starts in tensors_out */
+  yfc_cmp_frame* stats;
+  float* tensors_out;
+  long n, first, step;
+  int failed;
+} cmp_job;
+
+static void* run_cmp_job(void* arg) {
+  cmp_job* j = (cmp_job*)arg;
+  const yfc_cmp_plan* p = j->plan;
+  float* arena = (float*)malloc(sizeof(float) * YFC_ARENA_FLOATS);
+  yfc_cmp_frame* lanes = (yfc_cmp_frame*)malloc(sizeof(yfc_cmp_frame) * 3 * YFC_CMP_LANES);
+  if (!arena || !lanes) { free(arena); free(lanes); j->failed = 1; return NULL; }
+  for (long f = j->first; f < j->n; f += j->step) {
+    const int8_t* q = j->frames + (size_t)f * YFC_FRAME_BYTES;
+    for (int i = 0; i < YFC_FRAME_BYTES; ++i) arena[i] = j->params[q[i] + 128];
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &j->stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int8_t* qt[3] = {NULL, NULL, NULL};
+      float* xt[3] = {NULL, NULL, NULL};
+      for (int k = 0; k < 3; ++k) {
+        const int e = p->entry[s][k];
+        if (e < 0) continue;
+        qt[k] = p->q[e] + (size_t)f * p->frame_stride[e];
+        if (j->tensors_out) xt[k] = j->tensors_out + j->out_off[e] + (size_t)f * count;
+        for (int l = 0; l < YFC_CMP_LANES; ++l) yfc_cmp_zero(&lanes[k * YFC_CMP_LANES + l]);
+      }
+      for (int idx = 0; idx < count; ++idx) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, j->params, idx, v);
+        for (int k = 0; k < 3; ++k) {
+          const int e = p->entry[s][k];
+          if (e < 0) continue;
+          yfc_cmp_add(&lanes[k * YFC_CMP_LANES + idx % YFC_CMP_LANES], qt[k][idx], p->zero_point[e], p->scale[e], v[k]);
+          if (xt[k]) xt[k][idx] = v[k];
+        }
+      }
+      for (int k = 0; k < 3; ++k)
+        if (p->entry[s][k] >= 0) yfc_cmp_frame_value(&lanes[k * YFC_CMP_LANES], &j->stats[(size_t)f * p->count + p->entry[s][k]]);
+    }
+  }
+  free(arena);
+  free(lanes);
+  return NULL;
+}
+
+YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_qtensor* entries, int count,
+                                        void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen) {
+  enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
+  if (!p) REFUSE("yf_calib_host_compare: out of memory");
+  yfc_input_table(p);
+  if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, err, errlen)) { free(p); return -1; }
+  if (!frames || !frame_stats) { free(p); REFUSE("yf_calib_host_compare: frames or frame_stats is NULL"); }
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t range_tensors[YFC_N_RANGES];
+  yfc_build_stages(stages, range_tensors);
+  yfc_cmp_plan plan;
+  if (yfc_cmp_validate(stages, entries, count, n, &plan, err, errlen)) { free(p); return -1; }
+  size_t out_off[YFC_CMP_MAX_ENTRIES], at = 0;
+  for (int e = 0; e < count; ++e) { out_off[e] = at; at += (size_t)n * (size_t)plan.elements[e]; }
+  if (threads < 1) threads = 1;
+  if (threads > MAX_THREADS) threads = MAX_THREADS;
+  if ((long)threads > n) threads = (int)n;
+  cmp_job jobs[MAX_THREADS];
+  pthread_t tid[MAX_THREADS];
+  int started = 0, failed = 0;
+  for (int t = 0; t < threads; ++t) {
+    const cmp_job j = {stages, p, frames, &plan, out_off, (yfc_cmp_frame*)frame_stats, tensors_out, n, t, threads, 0};
+    jobs[t] = j;
+  }
+  for (int t = 1; t < threads; ++t) {
+    if (pthread_create(&tid[t], NULL, run_cmp_job, &jobs[t]) != 0) { jobs[t].failed = 1; break; }
+    started = t;
+  }
+  run_cmp_job(&jobs[0]);
+  for (int t = 1; t <= started; ++t) pthread_join(tid[t], NULL);
+  for (int t = 0; t < threads; ++t) failed |= jobs[t].failed;
+  free(p);
+  if (failed) REFUSE("yf_calib_host_compare: could not start a thread or allocate its arena");
+  if (totals)
+    for (int e = 0; e < count; ++e)
+      for (int field = 0; field < YFC_CMP_FIELDS; ++field)
+        yfc_cmp_total_field((const yfc_cmp_frame*)frame_stats, n, count, e, plan.elements[e], field, (yfc_cmp_total*)totals + e);
   return n;
 }
