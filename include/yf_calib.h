@@ -84,6 +84,21 @@ typedef struct {
 YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
                                           void* d_frame_stats, void* d_totals, void* stream);
 
+/* ---- Histograms of the 47 tensors over calibration frames, for clipped ranges (csrc/yf_calib_hist.h, DESIGN.md "Histogram arithmetic";
+ * ptq.clip_ranges chooses a range from them by percentile or by least modelled error).  A second pass over the frames: the same float32
+ * evaluation as yf_calib_observe_device, with every value of the input and of every convolution, LeakyReLU, ADD and pool output counted in
+ * one of `bins` equal bins of its tensor's axis.  Row r of minmax (host memory, float [YF_CALIB_N_RANGES][2], the slot order and tensor ids
+ * of yf_calib_ranges, whose output it usually is) gives tensor r's axis: a value outside {min, max} is counted in an end bin, v == max in
+ * the last bin, a NaN in bin 0.  minmax is read during the call only: the axes travel to the kernel as a launch argument, by value.
+ * d_counts uint64 [YF_CALIB_N_RANGES][bins] (device memory, 8-byte aligned) is ADDED to: the caller zeroes it once and may call again with
+ * more frames, on the same axes.  Asynchronous on `stream`; allocates nothing and does not synchronise the host.  Touches neither the
+ * handle's ranges nor yf_calib_frames_observed.  Counts are integers: the result equals the host build's exactly, whatever the grid.
+ * Returns n, or a value <= 0 with nothing launched: yf_calib_last_error_text() then names what was refused (a NULL handle, d_frames, minmax
+ * or d_counts, n < 1, bins outside 1..YF_CALIB_HIST_MAX_BINS, or the tensor id of a row that is not finite or has max < min). */
+#define YF_CALIB_HIST_MAX_BINS 4096
+YF_CALIB_API long yf_calib_histogram_device(yf_calib* c, const void* d_frames, long n, const float* minmax, int bins, uint64_t* d_counts,
+                                            void* stream);
+
 /* ---- libyf_calib_host.so only: the same evaluation on host arrays, on `threads` threads.  minmax / tensors as yf_calib_ranges fills them
  * (the ranges of these n frames alone), logits float [n][7][7][18] or NULL.  Returns n, or <= 0 with a text in err. */
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors,
@@ -93,6 +108,11 @@ YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t*
  * tensors_out is not NULL it receives the float32 tensors of the listed entries, [n][elements] per entry, concatenated in entry order. */
 YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_qtensor* entries, int count,
                                         void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen);
+
+/* ... and the same histograms: counts uint64 [YF_CALIB_N_RANGES][bins] (host memory) is added to.  The arguments are checked as
+ * yf_calib_histogram_device checks them. */
+YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const int8_t* frames, long n, const float* minmax, int bins,
+                                          uint64_t* counts, int threads, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

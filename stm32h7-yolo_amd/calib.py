@@ -10,6 +10,11 @@ arithmetic on the CPU (libyf_calib_host.so), bit for bit.  Unlike libyf_images.s
 Where a quantised model lost precision: Calibration.compare sets the int8 tensors of a run of the engine (Network.run_device with a dump, the
 heads) against the float32 tensors of the same frames, per tensor, with the arithmetic csrc/yf_calib_compare.h defines (DESIGN.md,
 "Comparison arithmetic"); host_compare is the same on the CPU, bit for bit; quantisation_report makes the table of a .yfw / .yfm pair.
+
+Acting on that table: Calibration.histogram counts every tensor's values over the frames in equal bins of its range (csrc/yf_calib_hist.h,
+DESIGN.md "Histogram arithmetic"; host_histogram is the same on the CPU, count for count), ptq.clip_ranges chooses a clipped range from the
+counts by percentile or by least modelled error, and quantize_on_device(..., ranges="percentile" / "mse") does all of it.  The default stays
+min/max.
 """
 import collections
 import ctypes
@@ -24,6 +29,7 @@ N_RANGES = 47
 FRAME_BYTES = 56 * 56 * 3
 LOGITS = 7 * 7 * 18
 MAX_ENTRIES = N_RANGES - 1
+HIST_MAX_BINS = 4096
 # the records of a comparison (csrc/yf_calib_compare.h): per frame and entry, and per entry over the frames.  error = dequantised - float
 FRAME_STATS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("saturated", "<i4")])
 TOTALS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("reserved", "<u4"),
@@ -83,6 +89,8 @@ def load():
     lib.yf_calib_observe_device.restype, lib.yf_calib_observe_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp]
     lib.yf_calib_compare_device.restype = ctypes.c_long
     lib.yf_calib_compare_device.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
+    lib.yf_calib_histogram_device.restype = ctypes.c_long
+    lib.yf_calib_histogram_device.argtypes = [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
     lib.yf_calib_ranges.restype, lib.yf_calib_ranges.argtypes = ctypes.c_int, [vp, vp, vp]
     lib.yf_calib_reset.restype, lib.yf_calib_reset.argtypes = ctypes.c_int, [vp]
     lib.yf_calib_frames_observed.restype, lib.yf_calib_frames_observed.argtypes = ctypes.c_long, [vp]
@@ -103,6 +111,9 @@ def load_host():
         lib.yf_calib_host_compare.restype = ctypes.c_long
         lib.yf_calib_host_compare.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp,
                                               ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_host_histogram.restype = ctypes.c_long
+        lib.yf_calib_host_histogram.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                ctypes.c_char_p, ctypes.c_size_t]
         _host = lib
     return _host
 
@@ -173,6 +184,34 @@ def host_run(yfw_bytes, frames, threads=1, want_logits=True):
     return _ranges_dict(minmax, ids), logits
 
 
+def _minmax_array(ranges):
+    """{tensor id: (min, max)} -> float32 [47, 2] in the slot order of yf_calib_ranges (ascending tensor id).  Only the count is checked
+    here: the library names a row it refuses."""
+    ids = sorted(ranges)
+    if len(ids) != N_RANGES:
+        raise ValueError(f"ranges: {len(ids)} tensors, expected the {N_RANGES} of Calibration.ranges()")
+    return np.ascontiguousarray([ranges[t] for t in ids], np.float32)
+
+
+def host_histogram(yfw_bytes, frames, ranges, bins=2048, threads=1, counts=None):
+    """The histograms on the CPU: int8 frames [n, 56, 56, 3] and the ranges {tensor id: (min, max)} that give every tensor its axis -> a
+    uint64 array [47, bins], rows in the order of sorted(ranges).  `counts` (such an array) is added to and returned.  A refused argument
+    raises CalibError with the library's text."""
+    lib = load_host()
+    x = np.ascontiguousarray(frames, np.int8).reshape(-1, 56, 56, 3)
+    n, minmax = x.shape[0], _minmax_array(ranges)
+    if counts is None:
+        counts = np.zeros((N_RANGES, max(int(bins), 1)), np.uint64)
+    elif counts.dtype != np.uint64 or counts.shape != (N_RANGES, bins) or not counts.flags.c_contiguous:
+        raise ValueError(f"counts: expected a contiguous uint64 array [{N_RANGES}, {bins}]")
+    err = ctypes.create_string_buffer(400)
+    rc = lib.yf_calib_host_histogram(bytes(yfw_bytes), len(yfw_bytes), x.ctypes.data, n, minmax.ctypes.data, int(bins), counts.ctypes.data,
+                                     int(threads), err, 400)
+    if rc != n or n < 1:
+        raise CalibError(f"yf_calib_host_histogram: {err.value.decode()} (returned {rc}, expected {n})")
+    return counts
+
+
 class Calibration:
     """A calibration of the float model `yfw_bytes` on GPU `device` (None: torch's current device).
 
@@ -241,6 +280,37 @@ class Calibration:
         torch.cuda.synchronize(dev)                                                  # frames and the entries' tensors are no longer read
         return d_stats[:, :count], d_totals[:count].cpu().numpy().view(TOTALS).reshape(count)
 
+    def histogram(self, frames, ranges=None, bins=2048, counts=None, stream=None):
+        """A second pass over `frames` (as observe takes them): every value of the 47 tensors counted in one of `bins` equal bins of its
+        tensor's range -- `ranges` {tensor id: (min, max)}, None: self.ranges().  Returns a uint64 device tensor [47, bins], rows in the
+        order of sorted(ranges); passing it back as `counts` accumulates further frames into it.  Asynchronous: the launch goes to torch's
+        current stream, or to `stream` (a raw hipStream_t), which is first made to wait, on the device, for what torch's current stream holds
+        at this moment -- the upload or copy of `frames`, the zeroing of new counts, earlier histogram calls on the current stream.  Work on
+        `counts` or `frames` that the caller queued on any OTHER stream is the caller's to order.  The handle's ranges and frames_observed are
+        not touched."""
+        import torch
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, np.int8))
+        dev = torch.device("cuda", self.device)
+        if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES:
+            raise ValueError(f"frames: expected int8 [n, 56, 56, 3], got {frames.dtype} {tuple(frames.shape)}")
+        frames = frames.to(dev).contiguous()
+        n, minmax = frames.numel() // FRAME_BYTES, _minmax_array(self.ranges() if ranges is None else ranges)
+        if counts is None:
+            counts = torch.zeros((N_RANGES, max(int(bins), 1)), dtype=torch.int64, device=dev).view(torch.uint64)
+        elif counts.dtype != torch.uint64 or tuple(counts.shape) != (N_RANGES, bins) or counts.device != dev or not counts.is_contiguous():
+            raise ValueError(f"counts: expected a contiguous uint64 tensor [{N_RANGES}, {bins}] on {dev}")
+        current = torch.cuda.current_stream(dev)
+        s = current.cuda_stream if stream is None else stream
+        if s != current.cuda_stream:                                                 # frames and counts were made ready on torch's stream
+            torch.cuda.ExternalStream(s, device=dev).wait_event(current.record_event())
+        rc = self._lib.yf_calib_histogram_device(self.handle, frames.data_ptr() if n else None, n, minmax.ctypes.data, int(bins),
+                                                 counts.data_ptr(), s)
+        if rc != n or n < 1:
+            raise CalibError(f"yf_calib_histogram_device: {self._text()} (returned {rc}, expected {n})")
+        self._keep_hist = frames                    # the launch is asynchronous: the frames stay alive until the next call
+        return counts
+
     @property
     def frames_observed(self):
         return self._lib.yf_calib_frames_observed(self.handle)
@@ -269,16 +339,24 @@ class Calibration:
             pass
 
 
-def quantize_on_device(yfw_bytes, frames, device=None):
+def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percentile=0.9999, bins=2048, keep=(0,)):
     """Float weights (.yfw bytes) and calibration frames -> the bytes of a .yfm image for Network.init_model: the frames are evaluated on the
     GPU, the ranges go through ptq.quantize_model.  `frames`: an int8 DEVICE tensor [n, 56, 56, 3] of the network's frames (pixel - 128,
     RGB).  Decoded images of any size become such frames through images.prepare_device / prepare_ragged_device first; this function does
-    not wrap that step."""
+    not wrap that step.
+    ranges: "minmax" (the default) gives every tensor the extremes observed; "percentile" and "mse" clip them (ptq.clip_ranges with
+    `percentile` and `keep`) on histograms of `bins` bins taken in a second pass over the same frames."""
     from . import ptq
+    if ranges not in ptq.CLIP_METHODS:
+        raise ValueError(f"ranges: {ranges!r}, expected one of {ptq.CLIP_METHODS}")
     cal = Calibration(yfw_bytes, device)
     try:
         cal.observe(frames, logits=False)
-        return ptq.quantize_model(yfw_bytes, cal.ranges())
+        if ranges == "minmax":
+            return ptq.quantize_model(yfw_bytes, cal.ranges())
+        observed = cal.ranges()
+        counts = cal.histogram(frames, observed, bins).cpu().numpy()
+        return ptq.quantize_model(yfw_bytes, ptq.clip_ranges(counts, observed, ranges, percentile, keep))
     finally:
         cal.destroy()
 

@@ -12,6 +12,13 @@
 // listed tensor every thread reads the int8 value of each element it computed and accumulates the error terms in the defined order (a thread
 // is a lane, a wave a group); one record per frame and entry goes to global memory, and a second, one-workgroup launch adds the frames'
 // records in ascending frame order.  The entries travel as a kernel argument: a launch refers to nothing a later call rewrites.
+//
+// The histogram form (yf_calib_histogram_device, csrc/yf_calib_hist.h) is the same evaluation with a bin where the observing form keeps an
+// extreme.  A stage's tables (one uint32 count per bin and tensor) live in LDS, in the run of the arena that is dead during that stage
+// (yfc_hist_windows: never less than 47 KB, enough for 4096 bins of every tensor a stage has); every lane adds its value's bin with one LDS
+// atomic -- activations pile up around zero, and the LDS takes that contention better than a per-wave pre-count does (measured) --; after the
+// stage the workgroup adds its non-empty bins to the caller's uint64 counts with vector atomics on consecutive addresses.  Integer sums are exact, so
+// this is the one place where an atomic has no numerical meaning.  The axes and the windows travel as a kernel argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -20,6 +27,7 @@
 #include "../../include/yf_calib.h"
 #include "yf_calib_arith.h"
 #include "yf_calib_compare.h"
+#include "yf_calib_hist.h"
 #include "yf_yfw.h"
 
 #ifndef YF_CALIB_BUILD_ID
@@ -218,6 +226,110 @@ __global__ __launch_bounds__(kTotalsThreads) void yfc_totals_kernel(const yfc_cm
   if (entry < plan.count) yfc_cmp_total_field(frame_stats, n, plan.count, entry, plan.elements[entry], field, &totals[entry]);
 }
 
+// ---- the histogram form ----
+constexpr size_t kHistLdsBytes = sizeof(float) * YFC_ARENA_FLOATS;
+// Bins a wave adds as one atomic each (the lanes that share a bin counted with a ballot) before its lanes go one by one.  0: every lane adds
+// for itself, which is what ships -- the LDS absorbs 64 adds to one address better than the wave can pre-count them: measured at 1, 4 and 8
+// bins, every one slower (profiles/calib_histogram.txt (b); tools/calib_histogram_bench.py --variant-lib times such builds).
+#ifndef YFC_HIST_PEEL
+#define YFC_HIST_PEEL 0
+#endif
+constexpr int kHistPeel = YFC_HIST_PEEL;
+
+struct yfc_hist_plan {
+  yfc_hist_axes axes;
+  int32_t off[YFC_N_STAGES + 1];                                                      // arena floats: the tables of the input's step and of every stage
+  int32_t bins;
+};
+
+// table[bin] += 1 for every calling lane.  With kHistPeel > 0 the lanes that share the first pending lane's bin are counted with a ballot and
+// added by one of them, kHistPeel times over; what is left adds for itself.  Any split gives the same sums.
+__device__ inline void hist_add(uint32_t* table, int bin) {
+  bool todo = true;
+  for (int k = 0; k < kHistPeel; ++k) {
+    if (todo) {
+      const int first = __builtin_amdgcn_readfirstlane(bin);
+      const bool same = bin == first;
+      const unsigned long long m = __ballot(same);
+      if (same) {
+        if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&table[first], (uint32_t)__popcll(m));
+        todo = false;
+      }
+    }
+  }
+  if (todo) atomicAdd(&table[bin], 1u);
+}
+
+__device__ inline void hist_clear(uint32_t* table, int entries) {
+  for (int i = threadIdx.x; i < entries; i += kThreads) table[i] = 0;
+  __syncthreads();
+}
+
+// The stage's tables (tables x bins, all threads past their adds) -> counts[slot][bin]; a barrier on either side
+__device__ inline void hist_flush(const uint32_t* table, const int slots[3], int bins, unsigned long long* __restrict__ counts) {
+  __syncthreads();                                                                  // also: the stage's output is in the arena
+  int at = 0;
+  for (int j = 0; j < 3; ++j) {
+    if (slots[j] < 0) continue;                                                     // uniform
+    unsigned long long* row = counts + (size_t)slots[j] * bins;
+    for (int i = threadIdx.x; i < bins; i += kThreads) {
+      const uint32_t k = table[at * bins + i];
+      if (k) atomicAdd(&row[i], (unsigned long long)k);
+    }
+    ++at;
+  }
+  __syncthreads();                                                                  // the next step may write where the tables were
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                  const yfc_stage* __restrict__ stages, const yfc_hist_plan plan,
+                                                                  unsigned long long* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* arena = lds;
+  const int tid = threadIdx.x, bins = plan.bins;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    {
+      const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
+      uint32_t* table = reinterpret_cast<uint32_t*>(arena + plan.off[0]);
+      const int slots[3] = {0, -1, -1};
+      const float lo = plan.axes.lo[0], inv = plan.axes.inv[0];
+      hist_clear(table, bins);
+      for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) {
+        const float v = params[(int)q[i] + 128];
+        arena[i] = v;
+        hist_add(table, yfc_hist_bin(v, lo, inv, bins));
+      }
+      hist_flush(table, slots, bins, counts);
+    }
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
+      uint32_t* table = reinterpret_cast<uint32_t*>(arena + plan.off[s + 1]);
+      int tab[3] = {0, 0, 0};                                                       // (offsets, not pointers: the adds stay LDS instructions)
+      float lo[3] = {0.0f, 0.0f, 0.0f}, inv[3] = {0.0f, 0.0f, 0.0f};
+      int tables = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (slots[j] < 0) continue;
+        tab[j] = tables * bins;
+        lo[j] = plan.axes.lo[slots[j]];
+        inv[j] = plan.axes.inv[slots[j]];
+        ++tables;
+      }
+      hist_clear(table, tables * bins);
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (slots[j] >= 0) hist_add(table, tab[j] + yfc_hist_bin(v[j], lo[j], inv[j], bins));
+      }
+      hist_flush(table, slots, bins, counts);
+    }
+  }
+}
+
 thread_local char g_err[320];
 
 #define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
@@ -251,7 +363,28 @@ struct yf_calib {
   float* d_ranges = nullptr;
   int32_t tensors[YFC_N_RANGES];
   yfc_stage stages[YFC_N_STAGES];
+  int32_t hist_off[YFC_N_STAGES + 1];                      // where each step's histogram tables live in the arena (yfc_hist_windows)
 };
+
+// The windows of the histogram kernel's tables; every one must hold YFC_HIST_MAX_BINS bins of each tensor its step has.
+static bool place_histogram_tables(yf_calib* c) {
+  int8_t* writer = new (std::nothrow) int8_t[YFC_ARENA_FLOATS];
+  uint32_t* busy = new (std::nothrow) uint32_t[YFC_ARENA_FLOATS];
+  int32_t floats[YFC_N_STAGES + 1];
+  bool ok = writer && busy;
+  if (!ok) set_error("yf_calib_create: out of memory");
+  if (ok) yfc_hist_windows(c->stages, c->hist_off, floats, writer, busy);
+  for (int step = 0; step <= YFC_N_STAGES && ok; ++step) {
+    const yfc_stage* g = step ? &c->stages[step - 1] : nullptr;
+    const int tables = g ? (g->r_conv >= 0) + (g->r_leaky >= 0) + (g->r_add >= 0) : 1;
+    ok = c->hist_off[step] >= 0 && floats[step] >= tables * YFC_HIST_MAX_BINS && c->hist_off[step] + floats[step] <= YFC_ARENA_FLOATS;
+    if (!ok) set_error("yf_calib_create: step %d leaves %d dead arena floats at %d, its %d histogram tables need %d", step, (int)floats[step],
+                       (int)c->hist_off[step], tables, tables * YFC_HIST_MAX_BINS);
+  }
+  delete[] writer;
+  delete[] busy;
+  return ok;
+}
 
 static bool upload_empty_ranges(yf_calib* c) {
   float init[kWgFloats];
@@ -288,6 +421,7 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
   const yfc_stage& last = stages[YFC_N_STAGES - 1];
   bool ok = last.b_off + last.cout == kParamFloats && last.out_off == YFC_LOGITS_OFF;
   if (!ok) set_error("yf_calib_create: the stage table gives %d parameter floats, the graph %d", last.b_off + last.cout, kParamFloats);
+  ok = ok && place_histogram_tables(c);
   if (ok) {
     DeviceScope scope(device);
     int cus = 0;
@@ -305,6 +439,8 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
          && hip_ok(hipMemcpy(c->d_params, p, sizeof(float) * kParamFloats, hipMemcpyHostToDevice), "hipMemcpy(params)")
          && hip_ok(hipMemcpy(c->d_stages, stages, sizeof stages, hipMemcpyHostToDevice), "hipMemcpy(stages)")
          && upload_empty_ranges(c) && hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_histogram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHistLdsBytes),
+                      "hipFuncSetAttribute(max dynamic LDS, histogram)");
   }
   delete[] p;
   if (!ok) {
@@ -352,6 +488,24 @@ YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, lon
     hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
     if (!hip_ok(hipGetLastError(), "yf_calib_compare_device: launch of the totals")) return -2;
   }
+  return n;
+}
+
+YF_CALIB_API long yf_calib_histogram_device(yf_calib* c, const void* d_frames, long n, const float* minmax, int bins, uint64_t* d_counts,
+                                            void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_histogram_device: NULL handle"); return -1; }
+  yfc_hist_plan plan;
+  if (yfc_hist_validate(d_frames, n, minmax, bins, d_counts, &plan.axes, g_err, sizeof g_err)) return -1;
+  if ((uintptr_t)d_counts % sizeof(uint64_t)) { set_error("histogram: counts is at %p, expected an address aligned to 8 bytes", (void*)d_counts); return -1; }
+  memcpy(plan.off, c->hist_off, sizeof plan.off);
+  plan.bins = bins;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
+  hipLaunchKernelGGL(yfc_histogram_kernel, dim3(grid), dim3(kThreads), kHistLdsBytes, (hipStream_t)stream, (const int8_t*)d_frames, n,
+                     (const float*)c->d_params, (const yfc_stage*)c->d_stages, plan, (unsigned long long*)d_counts);
+  if (!hip_ok(hipGetLastError(), "yf_calib_histogram_device: launch of the evaluation")) return -2;
   return n;
 }
 

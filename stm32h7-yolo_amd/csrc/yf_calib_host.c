@@ -7,6 +7,7 @@
 #include "../../include/yf_calib.h"
 #include "yf_calib_arith.h"
 #include "yf_calib_compare.h"
+#include "yf_calib_hist.h"
 #include "yf_yfw.h"
 
 typedef struct {
@@ -188,5 +189,84 @@ YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int
     for (int e = 0; e < count; ++e)
       for (int field = 0; field < YFC_CMP_FIELDS; ++field)
         yfc_cmp_total_field((const yfc_cmp_frame*)frame_stats, n, count, e, plan.elements[e], field, (yfc_cmp_total*)totals + e);
+  return n;
+}
+
+/* ---- the histograms (yf_calib_hist.h): the evaluation again, every value counted in its bin; a table per thread, added up at the end ---- */
+typedef struct {
+  const yfc_stage* stages;
+  const float* params;
+  const int8_t* frames;
+  const yfc_hist_axes* axes;
+  uint64_t* counts;                                     /* [YFC_N_RANGES][bins], this thread's own */
+  long n, first, step;
+  int bins, failed;
+} hist_job;
+
+static void* run_hist_job(void* arg) {
+  hist_job* j = (hist_job*)arg;
+  const yfc_hist_axes* a = j->axes;
+  const int bins = j->bins;
+  float* arena = (float*)malloc(sizeof(float) * YFC_ARENA_FLOATS);
+  if (!arena) { j->failed = 1; return NULL; }
+  for (long f = j->first; f < j->n; f += j->step) {
+    const int8_t* q = j->frames + (size_t)f * YFC_FRAME_BYTES;
+    for (int i = 0; i < YFC_FRAME_BYTES; ++i) {
+      arena[i] = j->params[q[i] + 128];
+      j->counts[yfc_hist_bin(arena[i], a->lo[0], a->inv[0], bins)] += 1;
+    }
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &j->stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
+      for (int idx = 0; idx < count; ++idx) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, j->params, idx, v);
+        for (int k = 0; k < 3; ++k)
+          if (slots[k] >= 0) j->counts[(size_t)slots[k] * bins + yfc_hist_bin(v[k], a->lo[slots[k]], a->inv[slots[k]], bins)] += 1;
+      }
+    }
+  }
+  free(arena);
+  return NULL;
+}
+
+YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const int8_t* frames, long n, const float* minmax, int bins,
+                                          uint64_t* counts, int threads, char* err, size_t errlen) {
+  enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
+  if (!p) REFUSE("yf_calib_host_histogram: out of memory");
+  yfc_input_table(p);
+  if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, err, errlen)) { free(p); return -1; }
+  yfc_hist_axes axes;
+  if (yfc_hist_validate(frames, n, minmax, bins, counts, &axes, err, errlen)) { free(p); return -1; }
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t range_tensors[YFC_N_RANGES];
+  yfc_build_stages(stages, range_tensors);
+  if (threads < 1) threads = 1;
+  if (threads > MAX_THREADS) threads = MAX_THREADS;
+  if ((long)threads > n) threads = (int)n;
+  const size_t entries = (size_t)YFC_N_RANGES * (size_t)bins;
+  uint64_t* tables = (uint64_t*)calloc((size_t)threads * entries, sizeof(uint64_t));
+  if (!tables) { free(p); REFUSE("yf_calib_host_histogram: out of memory"); }
+  hist_job jobs[MAX_THREADS];
+  pthread_t tid[MAX_THREADS];
+  int started = 0, failed = 0;
+  for (int t = 0; t < threads; ++t) {
+    const hist_job j = {stages, p, frames, &axes, tables + (size_t)t * entries, n, t, threads, bins, 0};
+    jobs[t] = j;
+  }
+  for (int t = 1; t < threads; ++t) {
+    if (pthread_create(&tid[t], NULL, run_hist_job, &jobs[t]) != 0) { jobs[t].failed = 1; break; }
+    started = t;
+  }
+  run_hist_job(&jobs[0]);
+  for (int t = 1; t <= started; ++t) pthread_join(tid[t], NULL);
+  for (int t = 0; t < threads; ++t) failed |= jobs[t].failed;
+  for (int t = 0; t < threads && !failed; ++t)
+    for (size_t i = 0; i < entries; ++i) counts[i] += jobs[t].counts[i];
+  free(tables);
+  free(p);
+  if (failed) REFUSE("yf_calib_host_histogram: could not start a thread or allocate its arena");
   return n;
 }

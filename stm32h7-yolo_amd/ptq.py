@@ -19,6 +19,9 @@ INTER_LINEAR resize, which is what makes the difference: PIL's antialiased resiz
 activation zero point and 42 of 46 scales are reproduced (float32 rounding noise), four scales within 0.8 %.
 This is an offline tool; it is not on the inference path.
 
+`clip_ranges` chooses a clipped range per tensor from a histogram of its values over the calibration frames (calib.Calibration.histogram
+or calib.host_histogram: csrc/yf_calib_hist.h), by percentile or by least modelled quantisation error; min/max stays the default everywhere.
+
 `quantize_model` applies the rules to a whole float model: .yfw bytes and calibrated ranges in, a .yfm image out that yf_network_init_model
 admits.  The ranges come from the calibration library (calib.py: the float32 evaluation on the GPU, or its host build).
 """
@@ -115,6 +118,88 @@ def quantize_model(yfw_bytes, ranges):
     if missing:
         raise ValueError(f"tensors {missing} were left without numbers")
     return model_file.write_yfm(g)
+
+
+CLIP_METHODS = ("minmax", "percentile", "mse")
+
+
+def _edges(lo, hi, bins):
+    """edge[k] = min + k * (max - min) / bins in float64: bin k of the histogram spans edge[k] .. edge[k + 1]"""
+    return lo + np.arange(bins + 1, dtype=np.float64) * (hi - lo) / bins
+
+
+def _clipped(lo, hi, edges, a, b):
+    """the range with `a` leading and `b` trailing bins cut: a bound that is not cut is the given one, unchanged"""
+    bins = len(edges) - 1
+    return (lo if a == 0 else float(edges[a]), hi if b == 0 else float(edges[bins - b]))
+
+
+def clip_error(counts, lo, hi, rmin, rmax):
+    """The modelled error of quantising a tensor whose histogram over [lo, hi] is `counts` with activation_qparams(rmin, rmax):
+    sum_k n_k * (dequant(quant(c_k)) - c_k)^2 over the bin centres c_k, quantised with round-half-even and clipped to -128..127.  float64."""
+    n = np.asarray(counts).astype(np.float64)
+    e = _edges(float(lo), float(hi), n.size)
+    return _centre_error(n, (e[:-1] + e[1:]) / 2, rmin, rmax)
+
+
+def _centre_error(n, c, rmin, rmax):
+    scale, zp = activation_qparams(rmin, rmax)
+    scale = float(scale)
+    q = np.clip(np.rint(c / scale) + zp, -128, 127)
+    return float((n * ((q - zp) * scale - c) ** 2).sum())
+
+
+def clip_ranges(counts, ranges, method, percentile=0.9999, keep=(0,)):
+    """Clipped calibration ranges from histograms: counts [47, bins] (row i belongs to the i-th tensor id of `ranges` in ascending order,
+    the slot order of yf_calib_ranges), ranges {tensor: (min, max)} the axes of the histograms were built from -> {tensor: (min, max)}.
+      "minmax"      `ranges`, unchanged.
+      "percentile"  tail = floor((1 - percentile) / 2 * total); `a` is the largest number of leading bins whose summed count is <= tail, `b`
+                    the same from the trailing end; the range is edge[a] .. edge[bins - b].  A bound with a == 0 (b == 0) is the given
+                    one, unchanged, so percentile=1.0 over the frames the ranges came from changes nothing.  If a + b >= bins the range is
+                    the one fullest bin.
+      "mse"         the candidate (a, b), a and b multiples of max(1, bins // 64) up to bins / 2, with the least clip_error; ties go to the
+                    smaller a + b, then to the smaller a.  (0, 0) is a candidate: the error is never above min/max's.
+    The tensors of `keep` are never clipped (the default: the input, whose parameters quantize_model pins anyway), nor is a tensor whose
+    histogram is empty.  Host, numpy, float64: an offline step."""
+    if method not in CLIP_METHODS:
+        raise ValueError(f"method: {method!r}, expected one of {CLIP_METHODS}")
+    ranges = {int(t): (float(v[0]), float(v[1])) for t, v in ranges.items()}
+    if method == "minmax":
+        return ranges
+    counts = np.asarray(counts)
+    ids = sorted(ranges)
+    if counts.ndim != 2 or counts.shape[0] != len(ids) or counts.shape[1] < 1:
+        raise ValueError(f"counts: shape {counts.shape}, expected [{len(ids)}, bins], one row per tensor of `ranges`")
+    if not 0.0 <= percentile <= 1.0:
+        raise ValueError(f"percentile: {percentile}, expected 0 to 1")
+    bins, keep, out = counts.shape[1], {int(t) for t in keep}, {}
+    if method == "mse":
+        # (with an even `bins` the grid reaches a = b = bins / 2, a range of no width: activation_qparams widens every range to hold 0 and gives
+        # (1.0, 0) for {0, 0}, so such a candidate has a finite error like any other and never wins against one that keeps values)
+        step = max(1, bins // 64)
+        grid = [k for k in range(0, bins + 1, step) if 2 * k <= bins]
+        cands = sorted(((a, b) for a in grid for b in grid), key=lambda ab: (ab[0] + ab[1], ab[0]))
+    for t, row in zip(ids, counts):
+        lo, hi = ranges[t]
+        total = int(row.astype(np.uint64).sum())
+        if t in keep or total == 0:
+            out[t] = (lo, hi)
+            continue
+        edges = _edges(lo, hi, bins)
+        if method == "percentile":
+            tail = int(np.floor((1.0 - percentile) / 2.0 * total))
+            a = int(np.searchsorted(np.cumsum(row.astype(np.float64)), tail, side="right"))
+            b = int(np.searchsorted(np.cumsum(row[::-1].astype(np.float64)), tail, side="right"))
+            if a + b >= bins:
+                k = int(np.argmax(row))
+                out[t] = (float(edges[k]), float(edges[k + 1]))
+            else:
+                out[t] = _clipped(lo, hi, edges, a, b)
+        else:
+            n, c = row.astype(np.float64), (edges[:-1] + edges[1:]) / 2
+            errors = [_centre_error(n, c, *_clipped(lo, hi, edges, a, b)) for a, b in cands]
+            out[t] = _clipped(lo, hi, edges, *cands[int(np.argmin(errors))])
+    return out
 
 
 class Calibrator:

@@ -10,6 +10,9 @@ and the time of a compare launch (all 28 tensors, totals included) beside an obs
 median of --launches calls after --warmup, each bracketed by HIP events on its stream.
 
     python tools/quant_report.py > profiles/quant_report.txt
+
+--ranges {minmax,percentile,mse}, --percentile and --bins choose the calibration ranges of the model it quantises on the device (section 2;
+calib.quantize_on_device: clipped ranges from histograms, ptq.clip_ranges); the default is min/max, the record's.
 """
 import argparse
 import importlib
@@ -100,6 +103,9 @@ def main():
     ap.add_argument("--bench-frames", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--ranges", choices=("minmax", "percentile", "mse"), default="minmax")
+    ap.add_argument("--percentile", type=float, default=0.9999)
+    ap.add_argument("--bins", type=int, default=2048)
     a = ap.parse_args()
     if bool(a.yfw) != bool(a.yfm):
         ap.error("--yfw and --yfm go together")
@@ -132,8 +138,9 @@ def main():
     print("\n1. oracle/model/yoloface_int8.yfm (the shipped model) against tests/golden/ptq_float_convs.npz (the float weights it came from)")
     net.init_model(shipped_yfm)
     print_table(calib.quantisation_report(net, npz_yfw, shipped_yfm, x))
-    print("\n2. calib.quantize_on_device(stm32h7-yolo_amd/model/yoloface_fp32.yfw, the same frames) against that .yfw")
-    new_yfm = calib.quantize_on_device(shipped_yfw, torch.from_numpy(x).cuda())
+    how = "" if a.ranges == "minmax" else f", ranges={a.ranges}" + (f", percentile={a.percentile}" if a.ranges == "percentile" else "") + f", bins={a.bins}"
+    print(f"\n2. calib.quantize_on_device(stm32h7-yolo_amd/model/yoloface_fp32.yfw, the same frames{how}) against that .yfw")
+    new_yfm = calib.quantize_on_device(shipped_yfw, torch.from_numpy(x).cuda(), ranges=a.ranges, percentile=a.percentile, bins=a.bins)
     net.init_model(new_yfm)
     print_table(calib.quantisation_report(net, shipped_yfw, new_yfm, x))
     net.init_model(shipped_yfm)
