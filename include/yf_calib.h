@@ -9,7 +9,12 @@
  * host, and tests/test_calib_gpu.py requires the two to agree bit for bit.
  *
  * Calls on one handle are ordered by the caller: the launches of yf_calib_observe_device accumulate into the handle's device-side ranges in
- * stream order, so two calls on different streams need an event between them (or yf_calib_ranges, which synchronises the device). */
+ * stream order, so two calls on different streams need an event between them (or yf_calib_ranges, which synchronises the device).
+ *
+ * Two forms of every evaluation.  The entries without _hw take the network's 56x56 frames and keep a frame's activations in the CU's LDS.
+ * The _hw entries take frames of h x w, h and w each a multiple of 8 from 8 to YF_CALIB_MAX_SIDE (160x160 is the engine's other size), and
+ * keep the activations in a slab of global memory the handle owns, one slab per workgroup in flight; they compute the same arithmetic, and
+ * at (56, 56) the same bits.  The handle orders the launches that share its slabs itself (see yf_calib_observe_hw_device). */
 #ifndef YF_CALIB_H
 #define YF_CALIB_H
 #include <stddef.h>
@@ -30,6 +35,9 @@ extern "C" {
                                          inputs' ranges, and the minimum of a max-pool is not its input's */
 #define YF_CALIB_FRAME_BYTES 9408     /* int8 [56][56][3] */
 #define YF_CALIB_LOGITS 882           /* float [7][7][18] */
+
+#define YF_CALIB_MAX_SIDE 160          /* the _hw entries: h and w are multiples of 8 from 8 to this */
+#define YF_CALIB_ARENA_FLOATS_PER_CELL 800   /* a slab of the _hw entries: this many floats per cell, cells = (h / 8) * (w / 8) */
 
 typedef struct yf_calib yf_calib;
 
@@ -99,6 +107,33 @@ YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, lon
 YF_CALIB_API long yf_calib_histogram_device(yf_calib* c, const void* d_frames, long n, const float* minmax, int bins, uint64_t* d_counts,
                                             void* stream);
 
+/* ---- Frames of h x w: the general form of the three evaluations above.  Argument lists and contracts are those of the 56x56 entries, with
+ * d_frames int8 [n][h][w][3], d_logits float [n][h / 8][w / 8][18], and, in a compare entry, a tensor of elements * cells / 49 elements
+ * (cells = (h / 8) * (w / 8)), which frame_stride is checked against.  These entries always run the general kernels, at (56, 56) too, where
+ * their results equal the 56x56 entries' bit for bit.  Ranges and yf_calib_frames_observed accumulate across sizes and across both forms: a
+ * range is the extremes of everything observed.  A refused size names h, w and the rule in yf_calib_last_error_text(), with nothing launched.
+ *
+ * SCRATCH.  A frame's activations live in a slab of YF_CALIB_ARENA_FLOATS_PER_CELL * cells floats of global memory (1.28 MB at 160x160),
+ * one slab per workgroup of the launch: yf_calib_workgroups(c, h, w) slabs, a number fixed at yf_calib_create from an occupancy query.  The
+ * handle owns the slabs and grows them when a call needs more than it has: THAT call synchronises the device and allocates -- the one place
+ * where a general call may do either; a later call at the same or a smaller size does neither.
+ * ORDER.  The slabs are shared by every general launch of the handle, so the library orders them: it records an event behind each general
+ * launch and makes the next general launch's stream wait for it (on the same stream the wait is already satisfied).  Two _hw calls on different streams
+ * therefore need nothing from the caller for the slabs' sake; what the caller still orders is what it always did -- the handle's ranges
+ * between observing calls (above), and its own buffers.  Calls on one handle come from one thread at a time. */
+YF_CALIB_API long yf_calib_observe_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, void* d_logits, void* stream);
+YF_CALIB_API long yf_calib_compare_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                                             void* d_frame_stats, void* d_totals, void* stream);
+YF_CALIB_API long yf_calib_histogram_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const float* minmax, int bins,
+                                               uint64_t* d_counts, void* stream);
+
+/* The number of workgroups a general launch at (h, w) uses when n is at least that: the slab count.  A launch's scratch is this times
+ * YF_CALIB_ARENA_FLOATS_PER_CELL * cells * 4 bytes.  <= 0 for a NULL handle or a refused size (yf_calib_last_error_text()). */
+YF_CALIB_API int yf_calib_workgroups(const yf_calib* c, int h, int w);
+
+/* The bytes of scratch the handle holds now (0 before the first general call). */
+YF_CALIB_API size_t yf_calib_scratch_bytes(const yf_calib* c);
+
 /* ---- libyf_calib_host.so only: the same evaluation on host arrays, on `threads` threads.  minmax / tensors as yf_calib_ranges fills them
  * (the ranges of these n frames alone), logits float [n][7][7][18] or NULL.  Returns n, or <= 0 with a text in err. */
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors,
@@ -113,6 +148,15 @@ YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int
  * yf_calib_histogram_device checks them. */
 YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const int8_t* frames, long n, const float* minmax, int bins,
                                           uint64_t* counts, int threads, char* err, size_t errlen);
+
+/* ... and the three at h x w (the three above are these at (56, 56)): frames int8 [n][h][w][3], logits float [n][h / 8][w / 8][18], a compare
+ * entry's tensor elements * cells / 49 elements.  A refused size is named in err, and nothing is written to the outputs. */
+YF_CALIB_API long yf_calib_host_run_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, float* minmax, int32_t* tensors,
+                                       float* logits, int threads, char* err, size_t errlen);
+YF_CALIB_API long yf_calib_host_compare_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, const yf_calib_qtensor* entries,
+                                           int count, void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen);
+YF_CALIB_API long yf_calib_host_histogram_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, const float* minmax, int bins,
+                                             uint64_t* counts, int threads, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

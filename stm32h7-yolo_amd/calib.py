@@ -15,6 +15,11 @@ Acting on that table: Calibration.histogram counts every tensor's values over th
 DESIGN.md "Histogram arithmetic"; host_histogram is the same on the CPU, count for count), ptq.clip_ranges chooses a clipped range from the
 counts by percentile or by least modelled error, and quantize_on_device(..., ranges="percentile" / "mse") does all of it.  The default stays
 min/max.
+
+Frames of another size: every function here that takes frames takes [n, h, w, 3] with h and w multiples of 8 up to 160 (160x160 is the
+engine's other size) and infers the size from the shape; such frames go through the library's _hw entries, whose kernels keep a frame's
+activations in global memory (DESIGN.md, "Calibration at h x w").  A flat or [n, 56, 56, 3] input means 56x56 and takes the 56x56 entries;
+general=True sends 56x56 frames through the _hw entries too, which give the same bits.
 """
 import collections
 import ctypes
@@ -30,6 +35,7 @@ FRAME_BYTES = 56 * 56 * 3
 LOGITS = 7 * 7 * 18
 MAX_ENTRIES = N_RANGES - 1
 HIST_MAX_BINS = 4096
+MAX_SIDE = 160                  # the _hw entries: h and w are multiples of 8 from 8 to this
 # the records of a comparison (csrc/yf_calib_compare.h): per frame and entry, and per entry over the frames.  error = dequantised - float
 FRAME_STATS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("saturated", "<i4")])
 TOTALS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("reserved", "<u4"),
@@ -71,6 +77,32 @@ def library_is_current():
     return libs.newer_than(lib_path(), libs.make_var("CALIB_SRCS").split() + ["Makefile"])
 
 
+def frame_size(frames, general=False):
+    """(h, w, hw) of frames as the functions here take them: a [n, h, w, 3] array or tensor has its shape's size, anything else (flat,
+    [n, 9408], ...) means 56x56.  hw: the call goes to the _hw entries -- every size but 56x56, and 56x56 with general=True.  Whether the
+    size is admitted is the library's to say: its text names the rule."""
+    shape = tuple(frames.shape)
+    h, w = (int(shape[1]), int(shape[2])) if len(shape) == 4 and shape[3] == 3 else (56, 56)
+    return h, w, bool(general) or (h, w) != (56, 56)
+
+
+def elements_at(elements, h, w):
+    """A tensor's elements per frame at h x w, from its elements at 56x56 (what the graph's shapes give)."""
+    return int(elements) * (h // 8) * (w // 8) // 49
+
+
+def _host_frames(frames, general):
+    """-> (contiguous int8 [n, h, w, 3], h, w, hw).  An input that is not [n, h, w, 3] means 56x56 frames, whichever entries it goes to: a
+    length that is no multiple of 9408 is refused here."""
+    x = np.ascontiguousarray(frames, np.int8)
+    h, w, hw = frame_size(x, general)
+    if x.ndim != 4 or x.shape[3] != 3:
+        if x.size % FRAME_BYTES:
+            raise ValueError(f"frames: expected int8 [n, h, w, 3] or whole 56x56 frames of {FRAME_BYTES} bytes, got {x.shape}")
+        x = x.reshape(-1, 56, 56, 3)
+    return x, h, w, hw
+
+
 _lib = None
 _host = None
 
@@ -91,6 +123,14 @@ def load():
     lib.yf_calib_compare_device.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
     lib.yf_calib_histogram_device.restype = ctypes.c_long
     lib.yf_calib_histogram_device.argtypes = [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
+    ci = ctypes.c_int
+    lib.yf_calib_observe_hw_device.restype, lib.yf_calib_observe_hw_device.argtypes = ctypes.c_long, [vp, ci, ci, vp, ctypes.c_long, vp, vp]
+    lib.yf_calib_compare_hw_device.restype = ctypes.c_long
+    lib.yf_calib_compare_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
+    lib.yf_calib_histogram_hw_device.restype = ctypes.c_long
+    lib.yf_calib_histogram_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
+    lib.yf_calib_workgroups.restype, lib.yf_calib_workgroups.argtypes = ctypes.c_int, [vp, ci, ci]
+    lib.yf_calib_scratch_bytes.restype, lib.yf_calib_scratch_bytes.argtypes = ctypes.c_size_t, [vp]
     lib.yf_calib_ranges.restype, lib.yf_calib_ranges.argtypes = ctypes.c_int, [vp, vp, vp]
     lib.yf_calib_reset.restype, lib.yf_calib_reset.argtypes = ctypes.c_int, [vp]
     lib.yf_calib_frames_observed.restype, lib.yf_calib_frames_observed.argtypes = ctypes.c_long, [vp]
@@ -114,6 +154,16 @@ def load_host():
         lib.yf_calib_host_histogram.restype = ctypes.c_long
         lib.yf_calib_host_histogram.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
                                                 ctypes.c_char_p, ctypes.c_size_t]
+        ci = ctypes.c_int
+        lib.yf_calib_host_run_hw.restype = ctypes.c_long
+        lib.yf_calib_host_run_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
+                                             ctypes.c_size_t]
+        lib.yf_calib_host_compare_hw.restype = ctypes.c_long
+        lib.yf_calib_host_compare_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp,
+                                                 vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_host_histogram_hw.restype = ctypes.c_long
+        lib.yf_calib_host_histogram_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                   ctypes.c_char_p, ctypes.c_size_t]
         _host = lib
     return _host
 
@@ -136,12 +186,13 @@ def _qtensors(entries):
     return arr
 
 
-def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elements=None):
-    """The comparison on the CPU: int8 frames [n, 56, 56, 3] and entries whose q are int8 numpy arrays -> (per-frame records, a FRAME_STATS
+def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elements=None, general=False):
+    """The comparison on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) and entries whose q are int8 numpy arrays -> (per-frame records, a FRAME_STATS
     array [n, count]; totals, a TOTALS array [count]; and, with want_tensors, the float32 tensors of the listed entries, one [n, elements]
-    array per entry -- `elements` then gives each entry's element count).  A refused argument raises CalibError with the library's text."""
+    array per entry -- `elements` then gives each entry's element count at this frame size).  A refused argument raises CalibError with the
+    library's text."""
     lib = load_host()
-    x = np.ascontiguousarray(frames, np.int8).reshape(-1, 56, 56, 3)
+    x, h, w, hw = _host_frames(frames, general)
     n, count = x.shape[0], len(entries)
     stats, totals = np.zeros((n, max(count, 1)), FRAME_STATS), np.zeros(max(count, 1), TOTALS)
     flat = None
@@ -150,8 +201,12 @@ def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elem
             raise ValueError("want_tensors: `elements` must give every entry's element count")
         flat = np.zeros(n * int(sum(elements)), np.float32)
     err = ctypes.create_string_buffer(400)
-    rc = lib.yf_calib_host_compare(bytes(yfw_bytes), len(yfw_bytes), x.ctypes.data, n, _qtensors(entries), count, stats.ctypes.data,
-                                   totals.ctypes.data, flat.ctypes.data if want_tensors else None, int(threads), err, 400)
+    tail = (x.ctypes.data, n, _qtensors(entries), count, stats.ctypes.data, totals.ctypes.data, flat.ctypes.data if want_tensors else None,
+            int(threads), err, 400)
+    if hw:
+        rc = lib.yf_calib_host_compare_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
+    else:
+        rc = lib.yf_calib_host_compare(bytes(yfw_bytes), len(yfw_bytes), *tail)
     if rc != n or n < 1:
         raise CalibError(f"yf_calib_host_compare: {err.value.decode()} (returned {rc}, expected {n})")
     stats, totals = stats[:, :count], totals[:count]
@@ -168,17 +223,20 @@ def _ranges_dict(minmax, ids):
     return {int(t): (float(minmax[i, 0]), float(minmax[i, 1])) for i, t in enumerate(ids)}
 
 
-def host_run(yfw_bytes, frames, threads=1, want_logits=True):
-    """The evaluation on the CPU: int8 frames [n, 56, 56, 3] -> ({tensor id: (min, max)} of these frames, float32 logits [n, 7, 7, 18] or
-    None).  A refused .yfw raises CalibError with the parser's text."""
+def host_run(yfw_bytes, frames, threads=1, want_logits=True, general=False):
+    """The evaluation on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) -> ({tensor id: (min, max)} of these frames, float32 logits
+    [n, h / 8, w / 8, 18] or None).  A refused .yfw or frame size raises CalibError with the library's text."""
     lib = load_host()
-    x = np.ascontiguousarray(frames, np.int8).reshape(-1, 56, 56, 3)
+    x, h, w, hw = _host_frames(frames, general)
     n = x.shape[0]
     minmax, ids = np.zeros((N_RANGES, 2), np.float32), np.zeros(N_RANGES, np.int32)
-    logits = np.zeros((n, 7, 7, 18), np.float32) if want_logits else None
+    logits = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32) if want_logits else None
     err = ctypes.create_string_buffer(400)
-    rc = lib.yf_calib_host_run(bytes(yfw_bytes), len(yfw_bytes), x.ctypes.data, n, minmax.ctypes.data, ids.ctypes.data,
-                               logits.ctypes.data if want_logits else None, int(threads), err, 400)
+    tail = (x.ctypes.data, n, minmax.ctypes.data, ids.ctypes.data, logits.ctypes.data if want_logits else None, int(threads), err, 400)
+    if hw:
+        rc = lib.yf_calib_host_run_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
+    else:
+        rc = lib.yf_calib_host_run(bytes(yfw_bytes), len(yfw_bytes), *tail)
     if rc != n:
         raise CalibError(f"yf_calib_host_run: {err.value.decode()} (returned {rc}, expected {n})")
     return _ranges_dict(minmax, ids), logits
@@ -193,20 +251,23 @@ def _minmax_array(ranges):
     return np.ascontiguousarray([ranges[t] for t in ids], np.float32)
 
 
-def host_histogram(yfw_bytes, frames, ranges, bins=2048, threads=1, counts=None):
-    """The histograms on the CPU: int8 frames [n, 56, 56, 3] and the ranges {tensor id: (min, max)} that give every tensor its axis -> a
+def host_histogram(yfw_bytes, frames, ranges, bins=2048, threads=1, counts=None, general=False):
+    """The histograms on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) and the ranges {tensor id: (min, max)} that give every tensor its axis -> a
     uint64 array [47, bins], rows in the order of sorted(ranges).  `counts` (such an array) is added to and returned.  A refused argument
     raises CalibError with the library's text."""
     lib = load_host()
-    x = np.ascontiguousarray(frames, np.int8).reshape(-1, 56, 56, 3)
+    x, h, w, hw = _host_frames(frames, general)
     n, minmax = x.shape[0], _minmax_array(ranges)
     if counts is None:
         counts = np.zeros((N_RANGES, max(int(bins), 1)), np.uint64)
     elif counts.dtype != np.uint64 or counts.shape != (N_RANGES, bins) or not counts.flags.c_contiguous:
         raise ValueError(f"counts: expected a contiguous uint64 array [{N_RANGES}, {bins}]")
     err = ctypes.create_string_buffer(400)
-    rc = lib.yf_calib_host_histogram(bytes(yfw_bytes), len(yfw_bytes), x.ctypes.data, n, minmax.ctypes.data, int(bins), counts.ctypes.data,
-                                     int(threads), err, 400)
+    tail = (x.ctypes.data, n, minmax.ctypes.data, int(bins), counts.ctypes.data, int(threads), err, 400)
+    if hw:
+        rc = lib.yf_calib_host_histogram_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
+    else:
+        rc = lib.yf_calib_host_histogram(bytes(yfw_bytes), len(yfw_bytes), *tail)
     if rc != n or n < 1:
         raise CalibError(f"yf_calib_host_histogram: {err.value.decode()} (returned {rc}, expected {n})")
     return counts
@@ -217,9 +278,13 @@ class Calibration:
 
     observe(frames)  frames: an int8 device tensor [n, 56, 56, 3] (or a numpy array, which is uploaded).  Asynchronous on torch's current
                      stream (or `stream`, a raw hipStream_t); folds the frames' extremes into the ranges so far.
+                     Frames [n, h, w, 3] of another size (h, w multiples of 8 up to 160) take the library's _hw entries (general=True:
+                     56x56 frames too); ranges and frames_observed accumulate across sizes.  The first general call at a size larger than
+                     any before it allocates the handle's scratch and synchronises the device (workgroups(h, w), scratch_bytes).
     ranges()         synchronises: {tflite tensor id: (min, max)} over everything observed since creation or reset() -- the input, every
                      convolution, LeakyReLU and ADD output and the two pool outputs: what ptq.quantize_model takes.
-    logits           the float32 logits [n, 7, 7, 18] of the last observe (a device tensor; None before the first, or with logits=False)."""
+    logits           the float32 logits [n, h / 8, w / 8, 18] of the last observe (a device tensor; None before the first, or with
+                     logits=False)."""
 
     def __init__(self, yfw_bytes, device=None):
         import torch
@@ -238,49 +303,66 @@ class Calibration:
     def _text(self):
         return (self._lib.yf_calib_last_error_text() or b"").decode()
 
-    def observe(self, frames, logits=True, stream=None):
+    def _frames(self, frames, general, at_least_one=False):
+        """-> (contiguous int8 device tensor, n, h, w, hw) of frames as observe takes them (frame_size)"""
         import torch
         if not isinstance(frames, torch.Tensor):
             frames = torch.from_numpy(np.ascontiguousarray(frames, np.int8))
-        dev = torch.device("cuda", self.device)
-        if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES or frames.numel() == 0:
-            raise ValueError(f"frames: expected int8 [n, 56, 56, 3] with n >= 1, got {frames.dtype} {tuple(frames.shape)}")
-        frames = frames.to(dev).contiguous()
-        n = frames.numel() // FRAME_BYTES
-        out = torch.empty((n, 7, 7, 18), dtype=torch.float32, device=dev) if logits else None
+        h, w, hw = frame_size(frames, general)
+        shaped = len(frames.shape) == 4 and frames.shape[3] == 3           # anything else means whole 56x56 frames, whichever entries it goes to
+        if frames.dtype != torch.int8 or (not shaped and frames.numel() % FRAME_BYTES) or (at_least_one and frames.numel() == 0):
+            raise ValueError(f"frames: expected int8 [n, h, w, 3]{' with n >= 1' if at_least_one else ''} (flat: 56x56), got {frames.dtype} "
+                             f"{tuple(frames.shape)}")
+        frames = frames.to(torch.device("cuda", self.device)).contiguous()
+        return frames, (frames.shape[0] if shaped else frames.numel() // FRAME_BYTES), h, w, hw
+
+    def workgroups(self, h, w):
+        """The workgroups a general launch at (h, w) uses, which is the number of scratch slabs of 800 * (h / 8) * (w / 8) floats each."""
+        k = self._lib.yf_calib_workgroups(self.handle, int(h), int(w))
+        if k < 1:
+            raise CalibError(f"yf_calib_workgroups: {self._text()} (returned {k})")
+        return k
+
+    @property
+    def scratch_bytes(self):
+        return self._lib.yf_calib_scratch_bytes(self.handle)
+
+    def observe(self, frames, logits=True, stream=None, general=False):
+        import torch
+        frames, n, h, w, hw = self._frames(frames, general, at_least_one=True)
+        dev = frames.device
+        out = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device=dev) if logits else None
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        rc = self._lib.yf_calib_observe_device(self.handle, frames.data_ptr(), n, out.data_ptr() if logits else None, s)
+        if hw:
+            rc = self._lib.yf_calib_observe_hw_device(self.handle, h, w, frames.data_ptr(), n, out.data_ptr() if logits else None, s)
+        else:
+            rc = self._lib.yf_calib_observe_device(self.handle, frames.data_ptr(), n, out.data_ptr() if logits else None, s)
         if rc != n:
-            raise CalibError(f"yf_calib_observe_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"yf_calib_observe{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
         self._keep, self.logits = frames, out       # the launch is asynchronous: the frames stay alive until the next call
         return n
 
-    def compare(self, frames, entries, stream=None):
+    def compare(self, frames, entries, stream=None, general=False):
         """The per-tensor error of an int8 run against the float32 evaluation of the same `frames` (as observe takes them).  entries: a list of
         Entry whose q are int8 device tensors (or device addresses).  Returns (the per-frame records, a uint8 device tensor [n, count, 32]:
         FRAME_STATS, see frame_stats_array; the totals, a TOTALS numpy array [count]).  Launches on torch's current stream (or `stream`, a raw
         hipStream_t) and synchronises the device for the totals.  The handle's ranges and frames_observed are not touched."""
         import torch
-        if not isinstance(frames, torch.Tensor):
-            frames = torch.from_numpy(np.array(frames, np.int8))
-        dev = torch.device("cuda", self.device)
-        if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES:
-            raise ValueError(f"frames: expected int8 [n, 56, 56, 3], got {frames.dtype} {tuple(frames.shape)}")
-        frames = frames.to(dev).contiguous()
-        n, count = frames.numel() // FRAME_BYTES, len(entries)
+        frames, n, h, w, hw = self._frames(frames, general)
+        dev, count = frames.device, len(entries)
         d_stats = torch.zeros((n, max(count, 1), FRAME_STATS.itemsize), dtype=torch.uint8, device=dev)
         d_totals = torch.zeros((max(count, 1), TOTALS.itemsize), dtype=torch.uint8, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         if stream is not None:
             torch.cuda.synchronize(dev)                                              # the zeroed outputs were made on torch's stream
-        rc = self._lib.yf_calib_compare_device(self.handle, frames.data_ptr() if n else None, n, _qtensors(entries), count, d_stats.data_ptr(),
-                                               d_totals.data_ptr(), s)
+        tail = (frames.data_ptr() if n else None, n, _qtensors(entries), count, d_stats.data_ptr(), d_totals.data_ptr(), s)
+        rc = self._lib.yf_calib_compare_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_compare_device(self.handle, *tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_compare_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"yf_calib_compare{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
         torch.cuda.synchronize(dev)                                                  # frames and the entries' tensors are no longer read
         return d_stats[:, :count], d_totals[:count].cpu().numpy().view(TOTALS).reshape(count)
 
-    def histogram(self, frames, ranges=None, bins=2048, counts=None, stream=None):
+    def histogram(self, frames, ranges=None, bins=2048, counts=None, stream=None, general=False):
         """A second pass over `frames` (as observe takes them): every value of the 47 tensors counted in one of `bins` equal bins of its
         tensor's range -- `ranges` {tensor id: (min, max)}, None: self.ranges().  Returns a uint64 device tensor [47, bins], rows in the
         order of sorted(ranges); passing it back as `counts` accumulates further frames into it.  Asynchronous: the launch goes to torch's
@@ -289,13 +371,8 @@ class Calibration:
         `counts` or `frames` that the caller queued on any OTHER stream is the caller's to order.  The handle's ranges and frames_observed are
         not touched."""
         import torch
-        if not isinstance(frames, torch.Tensor):
-            frames = torch.from_numpy(np.ascontiguousarray(frames, np.int8))
-        dev = torch.device("cuda", self.device)
-        if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES:
-            raise ValueError(f"frames: expected int8 [n, 56, 56, 3], got {frames.dtype} {tuple(frames.shape)}")
-        frames = frames.to(dev).contiguous()
-        n, minmax = frames.numel() // FRAME_BYTES, _minmax_array(self.ranges() if ranges is None else ranges)
+        frames, n, h, w, hw = self._frames(frames, general)
+        dev, minmax = frames.device, _minmax_array(self.ranges() if ranges is None else ranges)
         if counts is None:
             counts = torch.zeros((N_RANGES, max(int(bins), 1)), dtype=torch.int64, device=dev).view(torch.uint64)
         elif counts.dtype != torch.uint64 or tuple(counts.shape) != (N_RANGES, bins) or counts.device != dev or not counts.is_contiguous():
@@ -304,10 +381,10 @@ class Calibration:
         s = current.cuda_stream if stream is None else stream
         if s != current.cuda_stream:                                                 # frames and counts were made ready on torch's stream
             torch.cuda.ExternalStream(s, device=dev).wait_event(current.record_event())
-        rc = self._lib.yf_calib_histogram_device(self.handle, frames.data_ptr() if n else None, n, minmax.ctypes.data, int(bins),
-                                                 counts.data_ptr(), s)
+        tail = (frames.data_ptr() if n else None, n, minmax.ctypes.data, int(bins), counts.data_ptr(), s)
+        rc = self._lib.yf_calib_histogram_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_histogram_device(self.handle, *tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_histogram_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"yf_calib_histogram{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
         self._keep_hist = frames                    # the launch is asynchronous: the frames stay alive until the next call
         return counts
 
@@ -342,8 +419,10 @@ class Calibration:
 def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percentile=0.9999, bins=2048, keep=(0,)):
     """Float weights (.yfw bytes) and calibration frames -> the bytes of a .yfm image for Network.init_model: the frames are evaluated on the
     GPU, the ranges go through ptq.quantize_model.  `frames`: an int8 DEVICE tensor [n, 56, 56, 3] of the network's frames (pixel - 128,
-    RGB).  Decoded images of any size become such frames through images.prepare_device / prepare_ragged_device first; this function does
-    not wrap that step.
+    RGB), or [n, h, w, 3] with h and w multiples of 8 up to 160: a model meant for the engine's 160x160 configuration is calibrated on
+    [n, 160, 160, 3] frames, so that its ranges are those the int8 network meets at that size (a .yfm carries no size).  Decoded images of
+    any size become such frames through images.prepare_device(..., out_hw=160) (or out_hw=56) / prepare_ragged_device first, then this; this
+    function does not wrap that step.
     ranges: "minmax" (the default) gives every tensor the extremes observed; "percentile" and "mse" clip them (ptq.clip_ranges with
     `percentile` and `keep`) on histograms of `bins` bins taken in a second pass over the same frames."""
     from . import ptq
@@ -405,15 +484,38 @@ def report_rows(tensors, totals):
     return rows
 
 
+def _head_report(network, yfw_bytes, yfm_bytes, d_x, h, w):
+    """quantisation_report at a size other than 56x56: the head alone (see there)"""
+    import torch
+    dev, n, logits = d_x.device, d_x.shape[0], (h // 8) * (w // 8) * 18
+    d_out = torch.zeros((n, logits), dtype=torch.int8, device=dev)
+    network.run_device_hw(h, w, d_x.data_ptr(), d_out.data_ptr(), n, torch.cuda.current_stream(dev).cuda_stream)
+    tensors = [t for t in report_tensors(network.dump_offset, yfm_bytes) if t["offset"] is None]
+    entries = [Entry(t["tensor"], t["scale"], t["zero_point"], d_out.data_ptr(), logits) for t in tensors]
+    cal = Calibration(yfw_bytes, dev.index)
+    try:
+        _, totals = cal.compare(d_x, entries)
+    finally:
+        cal.destroy()
+    return report_rows(tensors, totals)
+
+
 def quantisation_report(network, yfw_bytes, yfm_bytes, frames):
     """Where the int8 model `yfm_bytes` loses precision against the float model `yfw_bytes` it was quantised from, over `frames` (int8
     [n, 56, 56, 3], numpy or device): one row per tensor in op order (report_rows), TFLite's quantisation-debugger table for the model that
     runs, under the rounding in force.  `network` is a Network initialised from yfm_bytes (init_model): it runs the frames with a dump of every
-    fused stage's tensor, and the dumped tensors and the heads are compared with the float32 evaluation on the GPU."""
+    fused stage's tensor, and the dumped tensors and the heads are compared with the float32 evaluation on the GPU.
+    Frames [n, h, w, 3] of another size the engine runs (160x160) give the head's row alone (tensor 100, from run_device_hw): the engine's
+    per-stage dump exists at 56x56 only (yf_network_run_device_dump), so there is nothing to set the inner tensors against."""
     import torch
     dev = torch.device("cuda", network._device)
     if not isinstance(frames, torch.Tensor):
         frames = torch.from_numpy(np.ascontiguousarray(frames, np.int8))
+    h, w, hw = frame_size(frames)
+    if hw:
+        if frames.dtype != torch.int8 or frames.numel() == 0:
+            raise ValueError(f"frames: expected int8 [n, h, w, 3] with n >= 1, got {frames.dtype} {tuple(frames.shape)}")
+        return _head_report(network, yfw_bytes, yfm_bytes, frames.to(dev).contiguous(), h, w)
     if frames.dtype != torch.int8 or frames.numel() % FRAME_BYTES or frames.numel() == 0:
         raise ValueError(f"frames: expected int8 [n, 56, 56, 3] with n >= 1, got {frames.dtype} {tuple(frames.shape)}")
     d_x = frames.to(dev).contiguous()

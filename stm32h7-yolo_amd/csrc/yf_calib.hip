@@ -19,6 +19,19 @@
 // atomic -- activations pile up around zero, and the LDS takes that contention better than a per-wave pre-count does (measured) --; after the
 // stage the workgroup adds its non-empty bins to the caller's uint64 counts with vector atomics on consecutive addresses.  Integer sums are exact, so
 // this is the one place where an atomic has no numerical meaning.  The axes and the windows travel as a kernel argument.
+//
+// The general forms (the _hw entries: frames of h x w, multiples of 8 up to 160) are the same three loops over the same yfc_stage_element with
+// the arena in global memory: a slab of 800 * (h / 8) * (w / 8) floats per workgroup in flight, owned by the handle (1.28 MB at 160x160, which
+// no LDS holds).  Still one workgroup per frame, a grid-stride loop over the frames and the round-robin deal of a stage's elements -- the deal
+// is part of the comparing form's summation order.  The barrier that ends a stage is what hands the slab from the threads that wrote it to
+// the threads that read it: the waves of a workgroup run on one CU and share its vector L1, and __syncthreads() orders global memory at
+// workgroup scope (every wave's stores are waited for before the barrier); nothing here needs an agent-scope fence, because no other
+// workgroup ever reads a slab during a launch.  LDS holds the reduction scratch only, and in the histogram form the stage's tables at a
+// fixed place (3 x 4096 x 4 B): there is no dead arena to borrow.  The LDS no longer limits a CU to one workgroup, so the grid comes from an
+// occupancy query at yf_calib_create, not from the CU count alone (as compiled now the kernels' registers still allow one 16-wave workgroup
+// per CU: profiles/calib160.txt).  Every size's stage table is uploaded once at creation (400 sizes, 1 MB): a launch
+// refers to nothing a later call rewrites.  The launches of one handle share its slabs, so each waits for the event recorded behind the one
+// before it, whichever stream that went to.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -330,6 +343,146 @@ __global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* _
   }
 }
 
+// ---- the general forms: the arena is this workgroup's slab of global memory, the sizes come from `dims` ----
+__global__ __launch_bounds__(kThreads) void yfc_observe_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                   float* __restrict__ logits, float* __restrict__ partials) {
+  __shared__ float red[kRedFloats];
+  __shared__ float wg[kWgFloats];
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  const int tid = threadIdx.x;
+  const float inf = __builtin_inff();
+  if (tid < kWgFloats) wg[tid] = (tid & 1) ? -inf : inf;
+  __syncthreads();
+  int parity = 0;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    {
+      const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
+      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+      const int slots[3] = {0, -1, -1};
+      for (int i = tid; i < dims.frame_bytes; i += kThreads) {
+        const float v = params[(int)q[i] + 128];
+        arena[i] = v;
+        mn[0] = v < mn[0] ? v : mn[0];
+        mx[0] = v > mx[0] ? v : mx[0];
+      }
+      fold(mn, mx, slots, red, wg, parity);
+    }
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
+      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+        for (int j = 0; j < 3; ++j) {
+          if (slots[j] < 0) continue;
+          mn[j] = v[j] < mn[j] ? v[j] : mn[j];
+          mx[j] = v[j] > mx[j] ? v[j] : mx[j];
+        }
+      }
+      fold(mn, mx, slots, red, wg, parity);                                           // (its barrier: the stage's output is in the slab)
+    }
+    // (the logits stay where they are until the next frame's third stage writes T54 over them, several barriers from here)
+    if (logits)
+      for (int i = tid; i < dims.logits; i += kThreads) logits[(size_t)f * (size_t)dims.logits + i] = arena[dims.logits_off + i];
+  }
+  __syncthreads();
+  if (tid < kWgFloats) partials[(size_t)blockIdx.x * kWgFloats + tid] = wg[tid];
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_compare_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                   const yfc_cmp_plan plan, yfc_cmp_frame* __restrict__ frame_stats) {
+  __shared__ yfc_cmp_frame red[kCmpRecords];
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  const int tid = threadIdx.x;
+  int parity = 0;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
+    for (int i = tid; i < dims.frame_bytes; i += kThreads) arena[i] = params[(int)q[i] + 128];
+    __syncthreads();
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int entries[3] = {plan.entry[s][0], plan.entry[s][1], plan.entry[s][2]};
+      const int8_t* qt[3] = {nullptr, nullptr, nullptr};
+      float scale[3] = {0.0f, 0.0f, 0.0f};
+      int zp[3] = {0, 0, 0};
+      yfc_cmp_frame acc[3];                                                         // (per frame and stage: every frame starts from +0)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        yfc_cmp_zero(&acc[j]);
+        if (entries[j] < 0) continue;
+        qt[j] = plan.q[entries[j]] + (size_t)f * plan.frame_stride[entries[j]];
+        scale[j] = plan.scale[entries[j]];
+        zp[j] = plan.zero_point[entries[j]];
+      }
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (entries[j] >= 0) yfc_cmp_add(&acc[j], qt[j][idx], zp[j], scale[j], v[j]);
+      }
+      compare_fold(acc, entries, red, frame_stats + (size_t)f * plan.count, parity);
+    }
+  }
+}
+
+struct yfc_hist_hw_plan {
+  yfc_hist_axes axes;
+  int32_t bins;
+};
+
+__global__ __launch_bounds__(kThreads) void yfc_histogram_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                     const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                     const yfc_hist_hw_plan plan, unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t table[3 * YFC_HIST_MAX_BINS];                                   // a stage has up to three tensors
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  const int tid = threadIdx.x, bins = plan.bins;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    {
+      const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
+      const int slots[3] = {0, -1, -1};
+      const float lo = plan.axes.lo[0], inv = plan.axes.inv[0];
+      hist_clear(table, bins);
+      for (int i = tid; i < dims.frame_bytes; i += kThreads) {
+        const float v = params[(int)q[i] + 128];
+        arena[i] = v;
+        hist_add(table, yfc_hist_bin(v, lo, inv, bins));
+      }
+      hist_flush(table, slots, bins, counts);
+    }
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
+      int tab[3] = {0, 0, 0};
+      float lo[3] = {0.0f, 0.0f, 0.0f}, inv[3] = {0.0f, 0.0f, 0.0f};
+      int tables = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (slots[j] < 0) continue;
+        tab[j] = tables * bins;
+        lo[j] = plan.axes.lo[slots[j]];
+        inv[j] = plan.axes.inv[slots[j]];
+        ++tables;
+      }
+      hist_clear(table, tables * bins);
+      for (int idx = tid; idx < count; idx += kThreads) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        yfc_stage_element(g, arena, params, idx, v);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (slots[j] >= 0) hist_add(table, tab[j] + yfc_hist_bin(v[j], lo[j], inv[j], bins));
+      }
+      hist_flush(table, slots, bins, counts);                                         // (its first barrier: the stage's output is in the slab)
+    }
+  }
+}
+
 thread_local char g_err[320];
 
 #define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
@@ -364,6 +517,13 @@ struct yf_calib {
   int32_t tensors[YFC_N_RANGES];
   yfc_stage stages[YFC_N_STAGES];
   int32_t hist_off[YFC_N_STAGES + 1];                      // where each step's histogram tables live in the arena (yfc_hist_windows)
+  // the general forms
+  int hw_grid = 0;                                         // workgroups of a general launch = slabs: CUs x resident workgroups per CU
+  yfc_stage* d_stages_hw = nullptr;                        // [YFC_N_SIDES][YFC_N_SIDES][YFC_N_STAGES]: the table of every admitted size
+  float* d_slabs = nullptr;
+  size_t slab_bytes = 0;
+  hipEvent_t slabs_free = nullptr;                         // recorded behind the last general launch
+  bool slabs_used = false;
 };
 
 // The windows of the histogram kernel's tables; every one must hold YFC_HIST_MAX_BINS bins of each tensor its step has.
@@ -386,10 +546,72 @@ static bool place_histogram_tables(yf_calib* c) {
   return ok;
 }
 
+// The general forms' share of yf_calib_create (the device is current): the grid from an occupancy query, every size's stage table, the event.
+static bool general_setup(yf_calib* c, int cus) {
+  int per_cu = 0;
+  const void* kernels[3] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel};
+  for (int k = 0; k < 3; ++k) {                            // one slab count for the three: the fewest resident workgroups any of them has
+    int blocks = 0;
+    if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], kThreads, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
+      return false;
+    if (blocks < 1) { set_error("yf_calib_create: general kernel %d: the occupancy query gives %d resident workgroups", k, blocks); return false; }
+    per_cu = k == 0 || blocks < per_cu ? blocks : per_cu;
+  }
+  c->hw_grid = cus * per_cu;
+  const size_t tables = (size_t)YFC_N_SIDES * YFC_N_SIDES;
+  yfc_stage* all = new (std::nothrow) yfc_stage[tables * YFC_N_STAGES];
+  if (!all) { set_error("yf_calib_create: out of memory"); return false; }
+  int32_t ids[YFC_N_RANGES];
+  for (int i = 0; i < YFC_N_SIDES; ++i)
+    for (int j = 0; j < YFC_N_SIDES; ++j)
+      yfc_build_stages_hw(all + ((size_t)i * YFC_N_SIDES + j) * YFC_N_STAGES, ids, (i + 1) * YFC_SIDE_STEP, (j + 1) * YFC_SIDE_STEP);
+  const size_t bytes = sizeof(yfc_stage) * tables * YFC_N_STAGES;
+  const bool ok = hip_ok(hipMalloc((void**)&c->d_stages_hw, bytes), "hipMalloc(stage tables)")
+               && hip_ok(hipMemcpy(c->d_stages_hw, all, bytes, hipMemcpyHostToDevice), "hipMemcpy(stage tables)")
+               && hip_ok(hipEventCreateWithFlags(&c->slabs_free, hipEventDisableTiming), "hipEventCreateWithFlags");
+  delete[] all;
+  return ok;
+}
+
 static bool upload_empty_ranges(yf_calib* c) {
   float init[kWgFloats];
   for (int t = 0; t < kWgFloats; ++t) init[t] = (t & 1) ? -INFINITY : INFINITY;
   return hip_ok(hipMemcpy(c->d_ranges, init, sizeof init, hipMemcpyHostToDevice), "hipMemcpy(ranges)");
+}
+
+// the one check of a frame size, for every _hw entry: true and the text when it is refused
+static bool size_refused(const char* name, int h, int w) {
+  if (yfc_size_ok(h, w)) return false;
+  set_error("%s: the frame size is h = %d, w = %d, expected " YFC_SIZE_RULE " each", name, h, w);
+  return true;
+}
+
+// What a general call does before it launches, at an admitted size: the dims and the stage table, slabs enough for it, and the launch before
+// it out of the way.  0, or a negative value with the text set and nothing launched.
+static int general_begin(yf_calib* c, int h, int w, hipStream_t s, yfc_dims* dims, const yfc_stage** d_stages) {
+  yfc_dims_of(h, w, dims);
+  *d_stages = c->d_stages_hw + ((size_t)(h / YFC_SIDE_STEP - 1) * YFC_N_SIDES + (size_t)(w / YFC_SIDE_STEP - 1)) * YFC_N_STAGES;
+  const size_t need = (size_t)c->hw_grid * (size_t)dims->arena_floats * sizeof(float);
+  if (need > c->slab_bytes) {                              // the one place where a general call synchronises and allocates
+    if (!hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize (growing the scratch)")) return -2;
+    (void)hipFree(c->d_slabs);
+    c->d_slabs = nullptr;
+    c->slab_bytes = 0;
+    if (!hip_ok(hipMalloc((void**)&c->d_slabs, need), "hipMalloc(scratch slabs)")) return -2;
+    c->slab_bytes = need;
+    c->slabs_used = false;                                 // (the device is idle: nothing to wait for)
+  }
+  // (unconditional: behind a launch on the same stream the wait is already satisfied, and a stream handle's value says nothing -- a
+  // destroyed stream's successor may carry it)
+  if (c->slabs_used && !hip_ok(hipStreamWaitEvent(s, c->slabs_free, 0), "hipStreamWaitEvent(slabs)")) return -2;
+  return 0;
+}
+
+// ... and after it: the event the next general launch waits for
+static bool general_end(yf_calib* c, hipStream_t s) {
+  if (!hip_ok(hipEventRecord(c->slabs_free, s), "hipEventRecord(slabs)")) return false;
+  c->slabs_used = true;
+  return true;
 }
 
 extern "C" {
@@ -403,6 +625,8 @@ YF_CALIB_API void yf_calib_destroy(yf_calib* c) {
     DeviceScope scope(c->device);
     if (scope.ok) (void)hipDeviceSynchronize();
     (void)hipFree(c->d_params); (void)hipFree(c->d_stages); (void)hipFree(c->d_partials); (void)hipFree(c->d_ranges);
+    (void)hipFree(c->d_stages_hw); (void)hipFree(c->d_slabs);
+    if (c->slabs_free) (void)hipEventDestroy(c->slabs_free);
   }
   delete c;
 }
@@ -434,7 +658,8 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
                    "hipFuncSetAttribute(max dynamic LDS, compare)")
          && hip_ok(hipMalloc((void**)&c->d_params, sizeof(float) * kParamFloats), "hipMalloc(params)")
          && hip_ok(hipMalloc((void**)&c->d_stages, sizeof stages), "hipMalloc(stages)")
-         && hip_ok(hipMalloc((void**)&c->d_partials, sizeof(float) * kWgFloats * (size_t)cus), "hipMalloc(partials)")
+         && general_setup(c, cus)
+         && hip_ok(hipMalloc((void**)&c->d_partials, sizeof(float) * kWgFloats * (size_t)(c->hw_grid > cus ? c->hw_grid : cus)), "hipMalloc(partials)")
          && hip_ok(hipMalloc((void**)&c->d_ranges, sizeof(float) * kWgFloats), "hipMalloc(ranges)")
          && hip_ok(hipMemcpy(c->d_params, p, sizeof(float) * kParamFloats, hipMemcpyHostToDevice), "hipMemcpy(params)")
          && hip_ok(hipMemcpy(c->d_stages, stages, sizeof stages, hipMemcpyHostToDevice), "hipMemcpy(stages)")
@@ -508,6 +733,92 @@ YF_CALIB_API long yf_calib_histogram_device(yf_calib* c, const void* d_frames, l
   if (!hip_ok(hipGetLastError(), "yf_calib_histogram_device: launch of the evaluation")) return -2;
   return n;
 }
+
+YF_CALIB_API long yf_calib_observe_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c || !d_frames) { set_error("yf_calib_observe_hw_device: NULL %s", c ? "d_frames" : "handle"); return -1; }
+  if (n < 1) { set_error("yf_calib_observe_hw_device: n is %ld, expected at least 1", n); return -1; }
+  if (size_refused("yf_calib_observe_hw_device", h, w)) return -1;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
+  if (rc) return rc;
+  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
+  hipLaunchKernelGGL(yfc_observe_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
+                     c->d_slabs, (float*)d_logits, c->d_partials);
+  if (!hip_ok(hipGetLastError(), "yf_calib_observe_hw_device: launch of the evaluation")) return -2;
+  hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, s, (const float*)c->d_partials, grid, c->d_ranges);
+  if (!hip_ok(hipGetLastError(), "yf_calib_observe_hw_device: launch of the merge")) return -2;
+  if (!general_end(c, s)) return -2;
+  c->frames += n;
+  return n;
+}
+
+YF_CALIB_API long yf_calib_compare_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                                             void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_compare_hw_device: NULL handle"); return -1; }
+  if (size_refused("yf_calib_compare_hw_device", h, w)) return -1;
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t ids[YFC_N_RANGES];
+  yfc_build_stages_hw(stages, ids, h, w);
+  yfc_cmp_plan plan;
+  if (yfc_cmp_validate(stages, entries, count, n, &plan, g_err, sizeof g_err)) return -1;
+  if (!d_frames || !d_frame_stats) { set_error("yf_calib_compare_hw_device: NULL %s", d_frames ? "d_frame_stats" : "d_frames"); return -1; }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
+  if (rc) return rc;
+  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
+  hipLaunchKernelGGL(yfc_compare_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
+                     c->d_slabs, plan, (yfc_cmp_frame*)d_frame_stats);
+  if (!hip_ok(hipGetLastError(), "yf_calib_compare_hw_device: launch of the evaluation")) return -2;
+  if (!general_end(c, s)) return -2;
+  if (d_totals) {
+    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
+    if (!hip_ok(hipGetLastError(), "yf_calib_compare_hw_device: launch of the totals")) return -2;
+  }
+  return n;
+}
+
+YF_CALIB_API long yf_calib_histogram_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const float* minmax, int bins,
+                                               uint64_t* d_counts, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_histogram_hw_device: NULL handle"); return -1; }
+  if (size_refused("yf_calib_histogram_hw_device", h, w)) return -1;
+  yfc_hist_hw_plan plan;
+  if (yfc_hist_validate(d_frames, n, minmax, bins, d_counts, &plan.axes, g_err, sizeof g_err)) return -1;
+  if ((uintptr_t)d_counts % sizeof(uint64_t)) { set_error("histogram: counts is at %p, expected an address aligned to 8 bytes", (void*)d_counts); return -1; }
+  plan.bins = bins;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
+  if (rc) return rc;
+  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
+  hipLaunchKernelGGL(yfc_histogram_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
+                     c->d_slabs, plan, (unsigned long long*)d_counts);
+  if (!hip_ok(hipGetLastError(), "yf_calib_histogram_hw_device: launch of the evaluation")) return -2;
+  if (!general_end(c, s)) return -2;
+  return n;
+}
+
+YF_CALIB_API int yf_calib_workgroups(const yf_calib* c, int h, int w) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_workgroups: NULL handle"); return -1; }
+  if (size_refused("yf_calib_workgroups", h, w)) return -1;
+  return c->hw_grid;
+}
+
+YF_CALIB_API size_t yf_calib_scratch_bytes(const yf_calib* c) { return c ? c->slab_bytes : 0; }
 
 YF_CALIB_API int yf_calib_ranges(yf_calib* c, float* minmax, int32_t* tensors) {
   g_err[0] = 0;

@@ -17,7 +17,8 @@
  * Nothing here relies on intrinsics for that.
  *
  * Activations live in one arena of YFC_ARENA_FLOATS floats per frame in flight (LDS on the device: 156.8 KB of the CU's 160 KB); the
- * offsets below reuse the space of tensors that are dead.  A stage is one convolution with the LeakyReLU and / or ADD that follows it, or
+ * offsets below reuse the space of tensors that are dead.  At another frame size the same layout scales with the frame (yfc_build_stages_hw
+ * below; the arena is then global memory on the device).  A stage is one convolution with the LeakyReLU and / or ADD that follows it, or
  * one pool; each output element is computed by yfc_stage_element from the arena and written back to it. */
 #ifndef YF_CALIB_ARITH_H
 #define YF_CALIB_ARITH_H
@@ -84,10 +85,42 @@ typedef struct {
   0, 51, 52, 53, 54, 55, 56, 57, 58, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 72, 73, 74, 76, 77, 78, 79, 80, 81, 82, 83, 84, 85, 86, 87, 88, 89, 90, \
   91, 92, 94, 95, 96, 97, 98, 99, 100
 
-/* The stage table with the derived fields filled in (host only; the kernel reads the copy the library uploads). */
-static inline void yfc_build_stages(yfc_stage out[YFC_N_STAGES], int32_t range_tensors[YFC_N_RANGES]) {
+/* The evaluation at another frame size.  Admitted: h and w each a multiple of 8 from 8 to YFC_MAX_SIDE, so the three stride-2 stages halve
+ * exactly, nothing is larger than what the engine runs, and the arena stays bounded.  With cells = (h / 8) * (w / 8) -- 49 at 56x56 --
+ * every tensor has cells / 49 times its 56x56 elements and every arena offset above is a multiple of 49, so the layout at h x w is the
+ * 56x56 layout with every offset divided by 49 and multiplied by cells: the liveness argument carries over unchanged, because every tensor
+ * scales by the same factor.  The arena is 800 * cells floats (320 000 floats = 1.28 MB at 160x160: global memory on the device). */
+enum { YFC_MAX_SIDE = 160, YFC_SIDE_STEP = 8, YFC_BASE_CELLS = 49, YFC_ARENA_PER_CELL = YFC_ARENA_FLOATS / 49, YFC_LOGITS_PER_CELL = 18,
+       YFC_N_SIDES = YFC_MAX_SIDE / YFC_SIDE_STEP };
+#define YFC_SIZE_RULE "multiples of 8 from 8 to 160"
+
+typedef struct {
+  int32_t h, w, cells;
+  int32_t frame_bytes;                             /* int8 [h][w][3] */
+  int32_t logits, logits_off;                      /* float [h / 8][w / 8][18] and where the last stage leaves them in the arena */
+  int32_t arena_floats;
+} yfc_dims;
+
+static inline int yfc_size_ok(long h, long w) {
+  return h >= YFC_SIDE_STEP && h <= YFC_MAX_SIDE && h % YFC_SIDE_STEP == 0 && w >= YFC_SIDE_STEP && w <= YFC_MAX_SIDE && w % YFC_SIDE_STEP == 0;
+}
+
+/* (h, w) must be admitted */
+static inline void yfc_dims_of(int h, int w, yfc_dims* d) {
+  d->h = h; d->w = w;
+  d->cells = (h / YFC_SIDE_STEP) * (w / YFC_SIDE_STEP);
+  d->frame_bytes = h * w * 3;
+  d->logits = d->cells * YFC_LOGITS_PER_CELL;
+  d->logits_off = YFC_LOGITS_OFF / YFC_BASE_CELLS * d->cells;
+  d->arena_floats = YFC_ARENA_PER_CELL * d->cells;
+}
+
+/* The stage table for a frame of h x w (admitted, see yfc_size_ok) with the derived fields filled in (host only; the kernel reads the copy
+ * the library uploads). */
+static inline void yfc_build_stages_hw(yfc_stage out[YFC_N_STAGES], int32_t range_tensors[YFC_N_RANGES], int h, int w) {
   static const int32_t rows[YFC_N_STAGES][18] = { YFC_STAGE_ROWS };
   static const int32_t slots[YFC_N_RANGES] = { YFC_RANGE_TENSORS };
+  const int32_t h8 = h / YFC_SIDE_STEP, w8 = w / YFC_SIDE_STEP, cells = h8 * w8;
   int32_t w_off[YFC_N_CONVS], b_off[YFC_N_CONVS], at = YFC_INPUT_TABLE;
   for (int s = 0; s < YFC_N_STAGES; ++s) {                 /* (the convolutions appear in file order) */
     const int32_t* r = rows[s];
@@ -102,8 +135,9 @@ static inline void yfc_build_stages(yfc_stage out[YFC_N_STAGES], int32_t range_t
     const int32_t* r = rows[s];
     yfc_stage* g = &out[s];
     g->kind = r[0]; g->conv = r[1]; g->dw = r[2]; g->k = r[3]; g->stride = r[4]; g->leaky = r[5];
-    g->h = r[6]; g->w = r[7]; g->cin = r[8]; g->cout = r[9];
-    g->in_off = r[10]; g->out_off = r[11]; g->out_cstride = r[12]; g->out_coff = r[13]; g->add_off = r[14];
+    g->h = r[6] / 7 * h8; g->w = r[7] / 7 * w8; g->cin = r[8]; g->cout = r[9];       /* the rows' sides are 56, 28, 14, 7 */
+    g->in_off = r[10] / YFC_BASE_CELLS * cells; g->out_off = r[11] / YFC_BASE_CELLS * cells;
+    g->out_cstride = r[12]; g->out_coff = r[13]; g->add_off = r[14] < 0 ? -1 : r[14] / YFC_BASE_CELLS * cells;
     g->t_conv = r[15]; g->t_leaky = r[16]; g->t_add = r[17];
     /* one row / column of padding before the first at 3x3 (PAD + VALID at stride 2, SAME at stride 1); a pool's SAME padding: (k - 2) / 2 */
     g->pad = g->kind == YFC_POOL ? (g->k - 2) / 2 : (g->k - 1) / 2;
@@ -118,6 +152,11 @@ static inline void yfc_build_stages(yfc_stage out[YFC_N_STAGES], int32_t range_t
       if (slots[i] == g->t_add) g->r_add = i;
     }
   }
+}
+
+/* ... and at 56x56, where h8 * w8 = 49 and every row stands as written */
+static inline void yfc_build_stages(yfc_stage out[YFC_N_STAGES], int32_t range_tensors[YFC_N_RANGES]) {
+  yfc_build_stages_hw(out, range_tensors, 56, 56);
 }
 
 /* T[p] = float32(p / 255.0), the division in double: what `img.astype(np.float32) / 255.0` ... astype(np.float32) gives a pixel */

@@ -12,6 +12,7 @@
 
 typedef struct {
   const yfc_stage* stages;
+  const yfc_dims* dims;
   const float* params;
   const int8_t* frames;
   float* logits;
@@ -27,11 +28,11 @@ static void observe(float mm[2], float v) {
 
 static void* run_job(void* arg) {
   job* j = (job*)arg;
-  float* arena = (float*)malloc(sizeof(float) * YFC_ARENA_FLOATS);
+  float* arena = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);
   if (!arena) { j->failed = 1; return NULL; }
   for (long f = j->first; f < j->n; f += j->step) {
-    const int8_t* q = j->frames + (size_t)f * YFC_FRAME_BYTES;
-    for (int i = 0; i < YFC_FRAME_BYTES; ++i) {
+    const int8_t* q = j->frames + (size_t)f * (size_t)j->dims->frame_bytes;
+    for (int i = 0; i < j->dims->frame_bytes; ++i) {
       arena[i] = j->params[q[i] + 128];
       observe(j->mm[0], arena[i]);
     }
@@ -46,7 +47,7 @@ static void* run_job(void* arg) {
         if (g->r_add >= 0) observe(j->mm[g->r_add], v[2]);
       }
     }
-    if (j->logits) memcpy(j->logits + (size_t)f * YFC_LOGITS, arena + YFC_LOGITS_OFF, sizeof(float) * YFC_LOGITS);
+    if (j->logits) memcpy(j->logits + (size_t)f * (size_t)j->dims->logits, arena + j->dims->logits_off, sizeof(float) * (size_t)j->dims->logits);
   }
   free(arena);
   return NULL;
@@ -54,16 +55,27 @@ static void* run_job(void* arg) {
 
 #define REFUSE(...) do { if (err && errlen) snprintf(err, errlen, __VA_ARGS__); return -1; } while (0)
 
+/* the one check of a frame size, for the three functions below */
+#define REFUSE_SIZE(name) do { if (!yfc_size_ok(h, w)) REFUSE(name ": the frame size is h = %d, w = %d, expected " YFC_SIZE_RULE " each", h, w); } while (0)
+
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors, float* logits,
                                     int threads, char* err, size_t errlen) {
+  return yf_calib_host_run_hw(yfw, bytes, 56, 56, frames, n, minmax, tensors, logits, threads, err, errlen);
+}
+
+YF_CALIB_API long yf_calib_host_run_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, float* minmax, int32_t* tensors,
+                                       float* logits, int threads, char* err, size_t errlen) {
   enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  REFUSE_SIZE("yf_calib_host_run");
   float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
   if (!p) REFUSE("yf_calib_host_run: out of memory");
   yfc_input_table(p);
   if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, err, errlen)) { free(p); return -1; }
   if (!frames || !minmax || !tensors || n < 1) { free(p); REFUSE("yf_calib_host_run: frames, minmax or tensors is NULL, or n = %ld is below 1", n); }
   yfc_stage stages[YFC_N_STAGES];
-  yfc_build_stages(stages, tensors);
+  yfc_dims dims;
+  yfc_build_stages_hw(stages, tensors, h, w);
+  yfc_dims_of(h, w, &dims);
   if (threads < 1) threads = 1;
   if (threads > MAX_THREADS) threads = MAX_THREADS;
   if ((long)threads > n) threads = (int)n;
@@ -73,7 +85,7 @@ YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t*
   int started = 0, failed = 0;
   for (int t = 0; t < threads; ++t) {
     job* j = &jobs[t];
-    j->stages = stages; j->params = p; j->frames = frames; j->logits = logits; j->n = n; j->first = t; j->step = threads; j->failed = 0;
+    j->stages = stages; j->dims = &dims; j->params = p; j->frames = frames; j->logits = logits; j->n = n; j->first = t; j->step = threads; j->failed = 0;
     for (int r = 0; r < YFC_N_RANGES; ++r) { j->mm[r][0] = __builtin_inff(); j->mm[r][1] = -__builtin_inff(); }
   }
   for (int t = 1; t < threads; ++t) {
@@ -101,6 +113,7 @@ YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t*
 /* ---- the comparison (yf_calib_compare.h): the evaluation again, with the lanes of the defined order as an array ---- */
 typedef struct {
   const yfc_stage* stages;
+  const yfc_dims* dims;
   const float* params;
   const int8_t* frames;
   const yfc_cmp_plan* plan;
@@ -114,12 +127,12 @@ typedef struct {
 static void* run_cmp_job(void* arg) {
   cmp_job* j = (cmp_job*)arg;
   const yfc_cmp_plan* p = j->plan;
-  float* arena = (float*)malloc(sizeof(float) * YFC_ARENA_FLOATS);
+  float* arena = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);
   yfc_cmp_frame* lanes = (yfc_cmp_frame*)malloc(sizeof(yfc_cmp_frame) * 3 * YFC_CMP_LANES);
   if (!arena || !lanes) { free(arena); free(lanes); j->failed = 1; return NULL; }
   for (long f = j->first; f < j->n; f += j->step) {
-    const int8_t* q = j->frames + (size_t)f * YFC_FRAME_BYTES;
-    for (int i = 0; i < YFC_FRAME_BYTES; ++i) arena[i] = j->params[q[i] + 128];
+    const int8_t* q = j->frames + (size_t)f * (size_t)j->dims->frame_bytes;
+    for (int i = 0; i < j->dims->frame_bytes; ++i) arena[i] = j->params[q[i] + 128];
     for (int s = 0; s < YFC_N_STAGES; ++s) {
       const yfc_stage* g = &j->stages[s];
       const int count = g->oh * g->ow * g->cout;
@@ -153,7 +166,13 @@ static void* run_cmp_job(void* arg) {
 
 YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_qtensor* entries, int count,
                                         void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen) {
+  return yf_calib_host_compare_hw(yfw, bytes, 56, 56, frames, n, entries, count, frame_stats, totals, tensors_out, threads, err, errlen);
+}
+
+YF_CALIB_API long yf_calib_host_compare_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, const yf_calib_qtensor* entries,
+                                           int count, void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen) {
   enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  REFUSE_SIZE("yf_calib_host_compare");
   float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
   if (!p) REFUSE("yf_calib_host_compare: out of memory");
   yfc_input_table(p);
@@ -161,7 +180,9 @@ YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int
   if (!frames || !frame_stats) { free(p); REFUSE("yf_calib_host_compare: frames or frame_stats is NULL"); }
   yfc_stage stages[YFC_N_STAGES];
   int32_t range_tensors[YFC_N_RANGES];
-  yfc_build_stages(stages, range_tensors);
+  yfc_dims dims;
+  yfc_build_stages_hw(stages, range_tensors, h, w);
+  yfc_dims_of(h, w, &dims);
   yfc_cmp_plan plan;
   if (yfc_cmp_validate(stages, entries, count, n, &plan, err, errlen)) { free(p); return -1; }
   size_t out_off[YFC_CMP_MAX_ENTRIES], at = 0;
@@ -173,7 +194,7 @@ YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int
   pthread_t tid[MAX_THREADS];
   int started = 0, failed = 0;
   for (int t = 0; t < threads; ++t) {
-    const cmp_job j = {stages, p, frames, &plan, out_off, (yfc_cmp_frame*)frame_stats, tensors_out, n, t, threads, 0};
+    const cmp_job j = {stages, &dims, p, frames, &plan, out_off, (yfc_cmp_frame*)frame_stats, tensors_out, n, t, threads, 0};
     jobs[t] = j;
   }
   for (int t = 1; t < threads; ++t) {
@@ -195,6 +216,7 @@ YF_CALIB_API long yf_calib_host_compare(const void* yfw, size_t bytes, const int
 /* ---- the histograms (yf_calib_hist.h): the evaluation again, every value counted in its bin; a table per thread, added up at the end ---- */
 typedef struct {
   const yfc_stage* stages;
+  const yfc_dims* dims;
   const float* params;
   const int8_t* frames;
   const yfc_hist_axes* axes;
@@ -207,11 +229,11 @@ static void* run_hist_job(void* arg) {
   hist_job* j = (hist_job*)arg;
   const yfc_hist_axes* a = j->axes;
   const int bins = j->bins;
-  float* arena = (float*)malloc(sizeof(float) * YFC_ARENA_FLOATS);
+  float* arena = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);
   if (!arena) { j->failed = 1; return NULL; }
   for (long f = j->first; f < j->n; f += j->step) {
-    const int8_t* q = j->frames + (size_t)f * YFC_FRAME_BYTES;
-    for (int i = 0; i < YFC_FRAME_BYTES; ++i) {
+    const int8_t* q = j->frames + (size_t)f * (size_t)j->dims->frame_bytes;
+    for (int i = 0; i < j->dims->frame_bytes; ++i) {
       arena[i] = j->params[q[i] + 128];
       j->counts[yfc_hist_bin(arena[i], a->lo[0], a->inv[0], bins)] += 1;
     }
@@ -233,7 +255,13 @@ static void* run_hist_job(void* arg) {
 
 YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const int8_t* frames, long n, const float* minmax, int bins,
                                           uint64_t* counts, int threads, char* err, size_t errlen) {
+  return yf_calib_host_histogram_hw(yfw, bytes, 56, 56, frames, n, minmax, bins, counts, threads, err, errlen);
+}
+
+YF_CALIB_API long yf_calib_host_histogram_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, const float* minmax, int bins,
+                                             uint64_t* counts, int threads, char* err, size_t errlen) {
   enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  REFUSE_SIZE("yf_calib_host_histogram");
   float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
   if (!p) REFUSE("yf_calib_host_histogram: out of memory");
   yfc_input_table(p);
@@ -242,7 +270,9 @@ YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const i
   if (yfc_hist_validate(frames, n, minmax, bins, counts, &axes, err, errlen)) { free(p); return -1; }
   yfc_stage stages[YFC_N_STAGES];
   int32_t range_tensors[YFC_N_RANGES];
-  yfc_build_stages(stages, range_tensors);
+  yfc_dims dims;
+  yfc_build_stages_hw(stages, range_tensors, h, w);
+  yfc_dims_of(h, w, &dims);
   if (threads < 1) threads = 1;
   if (threads > MAX_THREADS) threads = MAX_THREADS;
   if ((long)threads > n) threads = (int)n;
@@ -253,7 +283,7 @@ YF_CALIB_API long yf_calib_host_histogram(const void* yfw, size_t bytes, const i
   pthread_t tid[MAX_THREADS];
   int started = 0, failed = 0;
   for (int t = 0; t < threads; ++t) {
-    const hist_job j = {stages, p, frames, &axes, tables + (size_t)t * entries, n, t, threads, bins, 0};
+    const hist_job j = {stages, &dims, p, frames, &axes, tables + (size_t)t * entries, n, t, threads, bins, 0};
     jobs[t] = j;
   }
   for (int t = 1; t < threads; ++t) {

@@ -8,6 +8,13 @@ stream it runs on: evaluation and merge launch together, logits written.  The ho
 is what was measured; if the kernel is not faster than the host build on 16 threads, the last line says so.
 
     python tools/calib_bench.py > profiles/calib_bench.txt
+
+--size H W times the general launch instead (yf_calib_observe_hw_device: frames of H x W, the activations in global memory), in frames and
+in output elements per second -- a frame of H x W is (H / 8) * (W / 8) / 49 times the work of a 56x56 one --, with the slab count and the
+scratch it holds; at --size 56 56 the LDS kernel is timed beside it in the same run.  (The LDS kernel beside the parent commit's build:
+tools/calib_histogram_bench.py --parent-lib.)
+
+    python tools/calib_bench.py --size 160 160 --frames 1024
 """
 import argparse
 import importlib
@@ -46,8 +53,62 @@ def device_rate(a, calib, torch, yfw, x):
     return dev_fps, dev_ranges
 
 
+def stage_elements(calib):
+    """output elements of the 26 stages per 56x56 frame, from the graph's shapes: what one frame's evaluation computes"""
+    model_file = importlib.import_module("stm32h7-yolo_amd.model_file")
+    shapes = model_file.load_graph()["tensors"]
+    produced = (51, 53, 55, 56, 58, 60, 62, 63, 65, 67, 69, 72, 74, 76, 78, 79, 81, 83, 85, 87, 89, 91, 94, 96, 98, 100)   # each stage's first tensor
+    return sum(int(np.prod(shapes[t]["shape"][1:])) for t in produced)
+
+
+def timed_observe(a, torch, cal, d_x, general):
+    for _ in range(a.warmup):
+        cal.observe(d_x, general=general)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(a.launches):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        cal.observe(d_x, general=general)
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def general_rate(a, calib, torch, yfw):
+    h, w = a.size
+    x = np.random.default_rng(4096).integers(-128, 128, (a.frames, h, w, 3), dtype=np.int8)
+    cal = calib.Calibration(yfw)
+    d_x = torch.from_numpy(x).cuda()
+    per_frame = stage_elements(calib) * (h // 8) * (w // 8) // 49
+    print(f"device: {torch.cuda.get_device_name(0)}, libyf_calib.so build id {cal._lib.yf_calib_build_id().decode()}")
+    med, lo, hi = timed_observe(a, torch, cal, d_x, True)
+    print(f"yf_calib_observe_hw_device at {h}x{w}, {a.frames} frames from HBM, logits written, {a.launches} launches after {a.warmup} warm-up, HIP events:")
+    print(f"  median {med:.3f} ms  (min {lo:.3f}, max {hi:.3f})  ->  {a.frames / med * 1e3:,.0f} frames/s, "
+          f"{a.frames * per_frame / med * 1e3 / 1e9:.2f} G output elements/s ({per_frame} per frame)")
+    print(f"  workgroups (= slabs): {cal.workgroups(h, w)}; scratch held: {cal.scratch_bytes} bytes")
+    same = calib.host_run(yfw, x[:64], 16)[0] == _ranges_of(cal, d_x[:64])
+    print(f"ranges of the first 64 frames, device against host build: {'bit-equal' if same else 'DIFFERENT'}")
+    if (h, w) == (56, 56):
+        med2, lo2, hi2 = timed_observe(a, torch, cal, d_x, False)
+        print(f"yf_calib_observe_device (the LDS kernel), the same frames, the same run:")
+        print(f"  median {med2:.3f} ms  (min {lo2:.3f}, max {hi2:.3f})  ->  {a.frames / med2 * 1e3:,.0f} frames/s, "
+              f"{a.frames * per_frame / med2 * 1e3 / 1e9:.2f} G output elements/s")
+        print(f"  general / LDS time: {med / med2:.2f}x")
+    cal.destroy()
+    return 0 if same else 1
+
+
+def _ranges_of(cal, d_x):
+    cal.reset()
+    cal.observe(d_x, logits=False, general=True)
+    return cal.ranges()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"))
     ap.add_argument("--frames", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -60,6 +121,10 @@ def main():
     calib = importlib.import_module("stm32h7-yolo_amd.calib")
     model_file = importlib.import_module("stm32h7-yolo_amd.model_file")
     yfw = open(os.path.join(ROOT, "stm32h7-yolo_amd", "model", "yoloface_fp32.yfw"), "rb").read()
+    if a.size:
+        if not torch.cuda.is_available():
+            sys.exit("calib_bench: --size needs a GPU")
+        return general_rate(a, calib, torch, yfw)
     x = np.random.default_rng(4096).integers(-128, 128, (a.frames, 56, 56, 3), dtype=np.int8)
 
     dev_fps = dev_ranges = None

@@ -11,6 +11,9 @@ median of --launches calls after --warmup, each bracketed by HIP events on its s
 
     python tools/quant_report.py > profiles/quant_report.txt
 
+--size S reads the frames as int8 [n][S][S][3] (160: the engine's other size) and needs --yfw / --yfm.  At a size other than 56 the table has
+the head's row alone (tensor 100, from yf_network_run_device_hw): the engine's per-stage dump exists at 56x56 only.
+
 --ranges {minmax,percentile,mse}, --percentile and --bins choose the calibration ranges of the model it quantises on the device (section 2;
 calib.quantize_on_device: clipped ranges from histograms, ptq.clip_ranges); the default is min/max, the record's.
 """
@@ -106,9 +109,12 @@ def main():
     ap.add_argument("--ranges", choices=("minmax", "percentile", "mse"), default="minmax")
     ap.add_argument("--percentile", type=float, default=0.9999)
     ap.add_argument("--bins", type=int, default=2048)
+    ap.add_argument("--size", type=int, default=56, help="the side of the frames in --frames (56 or 160)")
     a = ap.parse_args()
     if bool(a.yfw) != bool(a.yfm):
         ap.error("--yfw and --yfm go together")
+    if a.size != 56 and not a.yfw:
+        ap.error("--size: the record without --yfw / --yfm is taken at 56x56")
     import torch
     if not torch.cuda.is_available():
         sys.exit("quant_report: needs a GPU (the engine and the comparison run there)")
@@ -116,14 +122,16 @@ def main():
     calib = importlib.import_module("stm32h7-yolo_amd.calib")
     model_file = importlib.import_module("stm32h7-yolo_amd.model_file")
     x = np.fromfile(a.frames, np.int8)
-    if x.size == 0 or x.size % calib.FRAME_BYTES:
-        sys.exit(f"quant_report: {a.frames} holds {x.size} bytes, expected a multiple of {calib.FRAME_BYTES}")
-    x = x.reshape(-1, 56, 56, 3)
+    if x.size == 0 or x.size % (a.size * a.size * 3):
+        sys.exit(f"quant_report: {a.frames} holds {x.size} bytes, expected a multiple of {a.size * a.size * 3}")
+    x = x.reshape(-1, a.size, a.size, 3)
     net = yf.Network(device=0)
     if a.yfw:
         yfw, yfm = open(a.yfw, "rb").read(), open(a.yfm, "rb").read()
         net.init_model(yfm)
         print(f"{a.yfm} against {a.yfw} over the {x.shape[0]} frames of {a.frames}")
+        if a.size != 56:
+            print(f"frames of {a.size}x{a.size}: the head alone -- the engine dumps its stages' tensors at 56x56 only")
         print_table(calib.quantisation_report(net, yfw, yfm, x))
         net.destroy()
         return 0
