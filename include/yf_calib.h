@@ -134,6 +134,29 @@ YF_CALIB_API int yf_calib_workgroups(const yf_calib* c, int h, int w);
 /* The bytes of scratch the handle holds now (0 before the first general call). */
 YF_CALIB_API size_t yf_calib_scratch_bytes(const yf_calib* c);
 
+/* ---- Simulated quantisation: what ONE tensor's quantisation costs the logits (csrc/yf_calib_sim.h, DESIGN.md "Simulation arithmetic";
+ * TFLite's quantisation debugger in its per-layer mode).  The float32 evaluation again, with every tensor whose entry is enabled put on its
+ * int8 grid where it is produced: v -> clamp(rint(v / scale), -128 - zero_point, 127 - zero_point) * scale, in float32.  The table has
+ * YF_CALIB_SIM_ENTRIES entries: 0 .. 46 are the range slots in the order of yf_calib_ranges (the input, every convolution, LeakyReLU, ADD
+ * and pool output), 47 .. 49 the outputs of the graph's three QUANTIZE ops in ascending tensor id (101, 102, 103).  scale == 0: the tensor
+ * stays float, and with every entry disabled the logits are yf_calib_observe_device's bit for bit.
+ * d_frames int8 [n][56][56][3]; `table` is host memory, read during the call only (it travels to the kernel by value); d_logits float
+ * [n][7][7][18] receives the simulated logits unless it is NULL.  With d_ref_logits (float [n][7][7][18], usually the logits of a call with
+ * every entry disabled) the call also writes one record per frame to d_frame_stats [n] (YF_CALIB_FRAME_STATS_BYTES each: error = simulated -
+ * reference over the frame's logits, `saturated` = the values of the frame that were clipped, over all enabled entries) and, unless d_totals
+ * is NULL, their sums in ascending frame order to d_totals [1] (YF_CALIB_TOTALS_BYTES).  Without d_ref_logits both must be NULL.
+ * Asynchronous on `stream`; touches neither the handle's ranges nor yf_calib_frames_observed.  Returns n, or a value <= 0 with nothing
+ * launched: yf_calib_last_error_text() then names the entry point and what was refused (a NULL handle, frames or table; n < 1; frame_stats
+ * or totals without ref_logits; ref_logits without frame_stats; a table entry, with its tensor id, whose scale is negative, NaN or infinite
+ * or so small that its reciprocal is not a finite float32, or whose zero point is outside -128..127). */
+#define YF_CALIB_SIM_ENTRIES 50
+typedef struct { float scale; int32_t zero_point; } yf_calib_sim_entry;
+YF_CALIB_API long yf_calib_simulate_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, const void* d_ref_logits,
+                                           void* d_logits, void* d_frame_stats, void* d_totals, void* stream);
+/* ... and at h x w: the general form, with the scratch and the ordering of the _hw entries above; at (56, 56) the same bits. */
+YF_CALIB_API long yf_calib_simulate_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                                              const void* d_ref_logits, void* d_logits, void* d_frame_stats, void* d_totals, void* stream);
+
 /* ---- libyf_calib_host.so only: the same evaluation on host arrays, on `threads` threads.  minmax / tensors as yf_calib_ranges fills them
  * (the ranges of these n frames alone), logits float [n][7][7][18] or NULL.  Returns n, or <= 0 with a text in err. */
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors,
@@ -157,6 +180,14 @@ YF_CALIB_API long yf_calib_host_compare_hw(const void* yfw, size_t bytes, int h,
                                            int count, void* frame_stats, void* totals, float* tensors_out, int threads, char* err, size_t errlen);
 YF_CALIB_API long yf_calib_host_histogram_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n, const float* minmax, int bins,
                                              uint64_t* counts, int threads, char* err, size_t errlen);
+
+/* ... and the simulation (yf_calib_simulate_device's arguments as host arrays), at 56x56 and at h x w: bit for bit what the device gives. */
+YF_CALIB_API long yf_calib_host_simulate(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_sim_entry* table,
+                                         const float* ref_logits, float* logits, void* frame_stats, void* totals, int threads, char* err,
+                                         size_t errlen);
+YF_CALIB_API long yf_calib_host_simulate_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n,
+                                            const yf_calib_sim_entry* table, const float* ref_logits, float* logits, void* frame_stats,
+                                            void* totals, int threads, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,12 @@ DESIGN.md "Histogram arithmetic"; host_histogram is the same on the CPU, count f
 counts by percentile or by least modelled error, and quantize_on_device(..., ranges="percentile" / "mse") does all of it.  The default stays
 min/max.
 
+What ONE tensor's quantisation costs the logits: Calibration.simulate runs the float32 evaluation with the tensors of a table's enabled
+entries put on their int8 grids (csrc/yf_calib_sim.h, DESIGN.md "Simulation arithmetic"; host_simulate is the same on the CPU, bit for bit);
+simulation_table makes the table of a .yfm, sensitivity the table of rows -- every tensor alone, every convolution's weights alone, all
+activations, all weights, everything -- and quantize_on_device(..., ranges="head") chooses each tensor's range among the min/max, percentile
+and mse candidates by the head error its quantisation alone causes.
+
 Frames of another size: every function here that takes frames takes [n, h, w, 3] with h and w multiples of 8 up to 160 (160x160 is the
 engine's other size) and infers the size from the shape; such frames go through the library's _hw entries, whose kernels keep a frame's
 activations in global memory (DESIGN.md, "Calibration at h x w").  A flat or [n, 56, 56, 3] input means 56x56 and takes the 56x56 entries;
@@ -41,6 +47,14 @@ FRAME_STATS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref"
 TOTALS = np.dtype([("sum_err", "<f8"), ("sum_sq_err", "<f8"), ("sum_sq_ref", "<f8"), ("max_abs_err", "<f4"), ("reserved", "<u4"),
                    ("saturated", "<i8"), ("elements", "<i8")])
 assert FRAME_STATS.itemsize == 32 and TOTALS.itemsize == 48
+
+# The table of a simulation (csrc/yf_calib_sim.h): 50 entries {scale, zero_point}; scale 0: the tensor stays float.  Entries 0 .. 46 are the
+# range slots in the order of Calibration.ranges() (ascending tensor id), 47 .. 49 the outputs of the graph's QUANTIZE ops.
+SIM_ENTRIES = 50
+SIM_ENTRY = np.dtype([("scale", "<f4"), ("zero_point", "<i4")])
+assert SIM_ENTRY.itemsize == 8
+RANGE_TENSORS = (0, 51, 52, 53, 54, 55, 56, 57, 58, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 72, 73, 74, 76, 77, 78, 79, 80, 81, 82, 83, 84, 85, 86,
+                 87, 88, 89, 90, 91, 92, 94, 95, 96, 97, 98, 99, 100)
 
 # One tensor of an int8 run: the tflite tensor id, its scale and zero point, and where its values lie -- q: frame 0's first byte (a device tensor
 # or address for Calibration.compare, an int8 numpy array for host_compare), frame_stride: bytes from one frame's tensor to the next's.
@@ -129,6 +143,9 @@ def load():
     lib.yf_calib_compare_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
     lib.yf_calib_histogram_hw_device.restype = ctypes.c_long
     lib.yf_calib_histogram_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
+    lib.yf_calib_simulate_device.restype, lib.yf_calib_simulate_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
+    lib.yf_calib_simulate_hw_device.restype = ctypes.c_long
+    lib.yf_calib_simulate_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
     lib.yf_calib_workgroups.restype, lib.yf_calib_workgroups.argtypes = ctypes.c_int, [vp, ci, ci]
     lib.yf_calib_scratch_bytes.restype, lib.yf_calib_scratch_bytes.argtypes = ctypes.c_size_t, [vp]
     lib.yf_calib_ranges.restype, lib.yf_calib_ranges.argtypes = ctypes.c_int, [vp, vp, vp]
@@ -164,6 +181,12 @@ def load_host():
         lib.yf_calib_host_histogram_hw.restype = ctypes.c_long
         lib.yf_calib_host_histogram_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
                                                    ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_host_simulate.restype = ctypes.c_long
+        lib.yf_calib_host_simulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
+                                               ctypes.c_size_t]
+        lib.yf_calib_host_simulate_hw.restype = ctypes.c_long
+        lib.yf_calib_host_simulate_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                  ctypes.c_char_p, ctypes.c_size_t]
         _host = lib
     return _host
 
@@ -217,6 +240,69 @@ def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elem
         tensors.append(flat[at:at + n * e].reshape(n, e))
         at += n * e
     return stats, totals, tensors
+
+
+def sim_tensors():
+    """The tensor id of each of the 50 entries of a simulation table: the 47 range slots, then the outputs of the graph's QUANTIZE ops in
+    ascending tensor id."""
+    from . import model_file
+    g = model_file.load_graph()
+    return RANGE_TENSORS + tuple(sorted(o["out"] for o in g["ops"] if o["op"] == model_file.OPCODE["QUANTIZE"]))
+
+
+def empty_table():
+    """A table with every entry disabled."""
+    return np.zeros(SIM_ENTRIES, SIM_ENTRY)
+
+
+def simulation_table(yfm_bytes, tensors=None):
+    """The 50 entries of a simulation from a model's own scales and zero points (a SIM_ENTRY array).  `tensors`: the tensor ids to enable
+    (None: all); an id that is not one of the 50 raises ValueError."""
+    from . import model_file
+    ids, T = sim_tensors(), model_file.load_yfm(yfm_bytes)["tensors"]
+    want = set(ids) if tensors is None else {int(t) for t in tensors}
+    bad = sorted(want - set(ids))
+    if bad:
+        raise ValueError(f"tensors: {bad} are not among the {SIM_ENTRIES} tensors of a simulation table ({ids})")
+    table = empty_table()
+    for i, t in enumerate(ids):
+        if t in want:
+            table[i] = (np.float32(T[t]["scale"][0]), int(T[t]["zp"]))
+    return table
+
+
+def _table(table):
+    t = np.ascontiguousarray(table, SIM_ENTRY) if table is not None else None
+    if t is not None and t.shape != (SIM_ENTRIES,):
+        raise ValueError(f"table: shape {t.shape}, expected [{SIM_ENTRIES}] entries (simulation_table)")
+    return t
+
+
+def host_simulate(yfw_bytes, frames, table, ref_logits=None, threads=1, general=False, want_stats=False):
+    """The simulation on the CPU: int8 frames [n, h, w, 3] (flat: 56x56), a table (simulation_table) and, optionally, reference logits
+    [n, h / 8, w / 8, 18] -> (float32 logits, totals: a TOTALS array [1] of the head's error against ref_logits, or None without them); with
+    want_stats also the per-frame records, a FRAME_STATS array [n] (None without ref_logits).  A refused argument raises CalibError with the
+    library's text."""
+    lib = load_host()
+    x, h, w, hw = _host_frames(frames, general)
+    n, t = x.shape[0], _table(table)
+    logits = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32)
+    ref = stats = totals = None
+    if ref_logits is not None:
+        ref = np.ascontiguousarray(ref_logits, np.float32)
+        if ref.size != logits.size:
+            raise ValueError(f"ref_logits: {ref.shape}, expected {logits.shape}")
+        stats, totals = np.zeros(max(n, 1), FRAME_STATS), np.zeros(1, TOTALS)
+    err = ctypes.create_string_buffer(400)
+    tail = (x.ctypes.data, n, None if t is None else t.ctypes.data, None if ref is None else ref.ctypes.data, logits.ctypes.data,
+            None if stats is None else stats.ctypes.data, None if totals is None else totals.ctypes.data, int(threads), err, 400)
+    if hw:
+        rc = lib.yf_calib_host_simulate_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
+    else:
+        rc = lib.yf_calib_host_simulate(bytes(yfw_bytes), len(yfw_bytes), *tail)
+    if rc != n or n < 1:
+        raise CalibError(f"yf_calib_host_simulate: {err.value.decode()} (returned {rc}, expected {n})")
+    return (logits, totals, None if stats is None else stats[:n]) if want_stats else (logits, totals)
 
 
 def _ranges_dict(minmax, ids):
@@ -388,6 +474,38 @@ class Calibration:
         self._keep_hist = frames                    # the launch is asynchronous: the frames stay alive until the next call
         return counts
 
+    def simulate(self, frames, table, ref_logits=None, stream=None, general=False, want_stats=False):
+        """The float32 evaluation of `frames` (as observe takes them) with the tensors of the table's enabled entries (simulation_table) on
+        their int8 grids.  Returns (the simulated logits, a float32 device tensor [n, h / 8, w / 8, 18]; the totals of the head's error against
+        `ref_logits`, a TOTALS numpy array [1] whose `saturated` counts the clipped values over all enabled entries -- None without
+        ref_logits, a float32 device tensor or array of the logits' shape); with want_stats also the per-frame records, a uint8 device tensor
+        [n, 1, 32] (frame_stats_array), or None.  Launches on torch's current stream (or `stream`, a raw hipStream_t) and synchronises the
+        device, as compare does.  The handle's ranges and frames_observed are not touched."""
+        import torch
+        frames, n, h, w, hw = self._frames(frames, general)
+        dev, t = frames.device, _table(table)
+        out = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device=dev)
+        ref = d_stats = d_totals = None
+        if ref_logits is not None:
+            ref = ref_logits if isinstance(ref_logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref_logits, np.float32))
+            if ref.dtype != torch.float32 or ref.numel() != out.numel():
+                raise ValueError(f"ref_logits: {ref.dtype} {tuple(ref.shape)}, expected float32 {tuple(out.shape)}")
+            ref = ref.to(dev).contiguous()
+            d_stats = torch.zeros((max(n, 1), 1, FRAME_STATS.itemsize), dtype=torch.uint8, device=dev)
+            d_totals = torch.zeros((1, TOTALS.itemsize), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if stream is not None:
+            torch.cuda.synchronize(dev)                                              # the outputs and uploads were made on torch's stream
+        ptr = lambda v: None if v is None else v.data_ptr()
+        tail = (frames.data_ptr() if n else None, n, None if t is None else t.ctypes.data, ptr(ref), out.data_ptr() if n else None, ptr(d_stats),
+                ptr(d_totals), s)
+        rc = self._lib.yf_calib_simulate_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_simulate_device(self.handle, *tail)
+        if rc != n or n < 1:
+            raise CalibError(f"yf_calib_simulate{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+        torch.cuda.synchronize(dev)                                                  # frames and ref_logits are no longer read
+        totals = None if ref is None else d_totals.cpu().numpy().view(TOTALS).reshape(1)
+        return (out, totals, None if ref is None else d_stats[:n]) if want_stats else (out, totals)
+
     @property
     def frames_observed(self):
         return self._lib.yf_calib_frames_observed(self.handle)
@@ -424,17 +542,23 @@ def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percenti
     any size become such frames through images.prepare_device(..., out_hw=160) (or out_hw=56) / prepare_ragged_device first, then this; this
     function does not wrap that step.
     ranges: "minmax" (the default) gives every tensor the extremes observed; "percentile" and "mse" clip them (ptq.clip_ranges with
-    `percentile` and `keep`) on histograms of `bins` bins taken in a second pass over the same frames."""
+    `percentile` and `keep`) on histograms of `bins` bins taken in a second pass over the same frames; "head" gives every tensor but those
+    of `keep` the one of its min/max, percentile and mse ranges whose quantisation, alone in an otherwise float evaluation of the same
+    frames, leaves the least squared error on the logits (head_ranges: some 140 further passes)."""
     from . import ptq
-    if ranges not in ptq.CLIP_METHODS:
-        raise ValueError(f"ranges: {ranges!r}, expected one of {ptq.CLIP_METHODS}")
+    if ranges not in ptq.CLIP_METHODS + ("head",):
+        raise ValueError(f"ranges: {ranges!r}, expected one of {ptq.CLIP_METHODS + ('head',)}")
     cal = Calibration(yfw_bytes, device)
     try:
+        frames = cal._frames(frames, False, at_least_one=True)[0]        # (on the device once, for every pass below)
         cal.observe(frames, logits=False)
         if ranges == "minmax":
             return ptq.quantize_model(yfw_bytes, cal.ranges())
         observed = cal.ranges()
         counts = cal.histogram(frames, observed, bins).cpu().numpy()
+        if ranges == "head":
+            cands = range_candidates(counts, observed, percentile, keep)
+            return ptq.quantize_model(yfw_bytes, head_ranges(cands, lambda table, ref: cal.simulate(frames, table, ref), keep))
         return ptq.quantize_model(yfw_bytes, ptq.clip_ranges(counts, observed, ranges, percentile, keep))
     finally:
         cal.destroy()
@@ -532,3 +656,113 @@ def quantisation_report(network, yfw_bytes, yfm_bytes, frames):
     finally:
         cal.destroy()
     return report_rows(tensors, totals)
+
+
+# ---------------------------------------------------------------------------------------------------------------- sensitivity
+def range_candidates(counts, observed, percentile=0.9999, keep=(0,)):
+    """{tensor: [its "minmax", "percentile" and "mse" range]} (the order of ptq.CLIP_METHODS) from the histograms `counts` on the axes of the
+    ranges `observed`: what ranges="head" chooses among."""
+    from . import ptq
+    by_method = [ptq.clip_ranges(counts, observed, m, percentile, keep) for m in ptq.CLIP_METHODS]
+    return {t: [r[t] for r in by_method] for t in sorted(by_method[0])}
+
+
+def head_ranges(candidates, simulate, keep=(0,)):
+    """The choice of ranges="head": candidates {tensor: [range, ...]} over the 47 range tensors, simulate(table, ref_logits) -> (logits,
+    totals) on the calibration frames (Calibration.simulate or host_simulate with the weights and frames bound).  For every tensor not in
+    `keep` each candidate's error is the head's sum_sq_err when that tensor alone is quantised with ptq.activation_qparams of the candidate,
+    against the logits of the all-float evaluation; a candidate equal to an earlier one of the same tensor takes that one's error.
+    ptq.choose_ranges picks.  The tensors of `keep` take their first candidate."""
+    from . import ptq
+    keep = {int(t) for t in keep}
+    ref, _ = simulate(empty_table(), None)
+    errors = {}
+    for t, cands in candidates.items():
+        slot, done = RANGE_TENSORS.index(int(t)), {}
+        if int(t) in keep:
+            errors[t] = [0.0] * len(cands)
+            continue
+        errors[t] = []
+        for r in cands:
+            key = (float(r[0]), float(r[1]))
+            if key not in done:
+                table = empty_table()
+                table[slot] = ptq.activation_qparams(*key)
+                done[key] = float(simulate(table, ref)[1][0]["sum_sq_err"])
+            errors[t].append(done[key])
+    return ptq.choose_ranges(candidates, errors)
+
+
+def _sim_elements(h, w):
+    """elements per frame of each of the 50 entries at h x w"""
+    from . import model_file
+    shapes = model_file.load_graph()["tensors"]
+    return [elements_at(int(np.prod(shapes[t]["shape"][1:])), h, w) for t in sim_tensors()]
+
+
+def sensitivity_row(name, op, tensor, conv, totals, head_scale, quantised):
+    """One row of the sensitivity table from the totals of a simulation against the float logits: head SQNR in dB, rmse and maximum error in
+    head LSB (head_scale: the model's output scale), and the share of the `quantised` values (all frames) that were clipped."""
+    r = totals[0]
+    k, err, ref = int(r["elements"]), float(r["sum_sq_err"]), float(r["sum_sq_ref"])
+    return dict(name=name, op=op, tensor=tensor, conv=conv,
+                sqnr_db=10.0 * math.log10(ref / err) if err > 0.0 and ref > 0.0 else (math.inf if ref > 0.0 else -math.inf),
+                rmse_lsb=math.sqrt(err / k) / head_scale, max_lsb=float(r["max_abs_err"]) / head_scale,
+                clipped=int(r["saturated"]) / quantised if quantised else 0.0)
+
+
+def sensitivity(yfw_bytes, yfm_bytes, frames, device=None, simulate=None):
+    """What each tensor's quantisation costs the logits of the float model `yfw_bytes` under the scales and zero points of the int8 model
+    `yfm_bytes`, over `frames` (int8 [n, h, w, 3] of any admitted size, numpy or device; flat: 56x56).  The reference is the evaluation with
+    every entry disabled.  Rows (sensitivity_row), in this order: one per table entry enabled alone (50, `op` the name of the op that makes
+    the tensor, "INPUT" for the input); one per convolution whose weights and bias alone are the model's dequantised numbers
+    (ptq.dequantized_yfw; 24, op "WEIGHTS"); "activations" (all 50 entries), "weights" (all 24 convolutions) and "all".
+    The evaluations run on GPU `device` (None: torch's current device), each weight set on a handle of its own; `simulate`, if given,
+    replaces them: simulate(yfw_bytes, frames, table, ref_logits) -> (logits, totals), e.g. host_simulate."""
+    from . import model_file, ptq
+    h, w, _ = frame_size(frames)
+    n = int(frames.shape[0]) if len(frames.shape) == 4 and frames.shape[3] == 3 else int(np.prod(tuple(frames.shape))) // FRAME_BYTES
+    graph, model = model_file.load_graph(), model_file.load_yfm(yfm_bytes)
+    head_scale = float(model["tensors"][graph["output"]]["scale"][0])
+    names = {v: k for k, v in model_file.OPCODE.items()}
+    made_by = {o["out"]: names[o["op"]] for o in graph["ops"]}
+    ids, elements, full = sim_tensors(), _sim_elements(h, w), simulation_table(yfm_bytes)
+    handles = []
+
+    def on(yfw):
+        """a simulate(table, ref) of one weight set: on the device one handle serves all its calls"""
+        if simulate is not None:
+            return lambda table, ref: simulate(yfw, frames, table, ref)
+        cal = Calibration(yfw, device)
+        handles.append(cal)
+        return lambda table, ref: cal.simulate(frames, table, ref)
+
+    rows = []
+    try:
+        base = on(yfw_bytes)
+        ref, _ = base(empty_table(), None)
+        for i, t in enumerate(ids):
+            table = empty_table()
+            table[i] = full[i]
+            rows.append(sensitivity_row(f"tensor {t}", made_by.get(t, "INPUT"), t, None, base(table, ref)[1], head_scale, n * elements[i]))
+        for c in range(len(model_file.graph_convs(graph))):
+            one = on(ptq.dequantized_yfw(yfw_bytes, yfm_bytes, [c]))
+            rows.append(sensitivity_row(f"conv {c}", "WEIGHTS", None, c, one(empty_table(), ref)[1], head_scale, 0))
+            if handles:
+                handles.pop().destroy()
+        rows.append(sensitivity_row("activations", "", None, None, base(full, ref)[1], head_scale, n * sum(elements)))
+        deq = on(ptq.dequantized_yfw(yfw_bytes, yfm_bytes))
+        rows.append(sensitivity_row("weights", "", None, None, deq(empty_table(), ref)[1], head_scale, 0))
+        rows.append(sensitivity_row("all", "", None, None, deq(full, ref)[1], head_scale, n * sum(elements)))
+    finally:
+        for cal in handles:
+            cal.destroy()
+    return rows
+
+
+def format_sensitivity(rows):
+    """the table of sensitivity() as text, one line per row"""
+    out = [f"{'what':<14} {'op':<18} {'head SQNR dB':>12} {'rmse LSB':>9} {'max LSB':>8} {'clipped':>9}"]
+    for r in rows:
+        out.append(f"{r['name']:<14} {r['op']:<18} {r['sqnr_db']:>12.2f} {r['rmse_lsb']:>9.4f} {r['max_lsb']:>8.3f} {r['clipped']:>9.6f}")
+    return "\n".join(out)

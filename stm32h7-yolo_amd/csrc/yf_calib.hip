@@ -32,6 +32,12 @@
 // per CU: profiles/calib160.txt).  Every size's stage table is uploaded once at creation (400 sizes, 1 MB): a launch
 // refers to nothing a later call rewrites.  The launches of one handle share its slabs, so each waits for the event recorded behind the one
 // before it, whichever stream that went to.
+//
+// The simulating form (yf_calib_simulate_device and its _hw form, csrc/yf_calib_sim.h) is the same stage loop over yfc_stage_element_sim, which
+// puts the tensors of the enabled entries on their int8 grids; the derived table travels as a kernel argument.  With reference logits every
+// thread accumulates the head's error terms of the logits it copies out (a thread is a lane, a wave a group: compare_fold's order for one
+// entry), and the frame's count of clipped values goes through a wave reduction and one LDS add per wave.  One body serves both kernels: the
+// LDS form calls it with the 56x56 sizes as constants.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -41,6 +47,7 @@
 #include "yf_calib_arith.h"
 #include "yf_calib_compare.h"
 #include "yf_calib_hist.h"
+#include "yf_calib_sim.h"
 #include "yf_yfw.h"
 
 #ifndef YF_CALIB_BUILD_ID
@@ -483,6 +490,78 @@ __global__ __launch_bounds__(kThreads) void yfc_histogram_hw_kernel(const int8_t
   }
 }
 
+// ---- the simulating form: one body, the arena in LDS (the 56x56 sizes as constants) or in this workgroup's slab ----
+constexpr int kSimRecords = kWaves;
+constexpr size_t kSimLdsBytes = sizeof(float) * YFC_ARENA_FLOATS + sizeof(yfc_cmp_frame) * kSimRecords + sizeof(int32_t) * 2;
+static_assert(kSimLdsBytes <= kCmpLdsBytes && kSimLdsBytes <= 160 * 1024, "the arena, the head's reduction scratch and the clip count must fit the CU's LDS");
+
+__device__ inline int wave_sum(int v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// red: kSimRecords records; clip: one count (both LDS).  frame_bytes, n_logits and logits_off describe the arena.
+__device__ __forceinline__ void simulate_frames(float* arena, yfc_cmp_frame* red, int32_t* clip, const int frame_bytes, const int n_logits,
+                                                const int logits_off, const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                const yfc_stage* __restrict__ stages, const yfc_sim_plan& plan, const float* __restrict__ ref,
+                                                float* __restrict__ logits, yfc_cmp_frame* __restrict__ frame_stats) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    const int8_t* q = frames + (size_t)f * (size_t)frame_bytes;
+    int32_t clipped = 0;
+    for (int i = tid; i < frame_bytes; i += kThreads) arena[i] = yfc_sim_input(&plan, params[(int)q[i] + 128], &clipped);
+    if (tid == 0) *clip = 0;                                                          // (read last behind the barrier that ended the frame before)
+    __syncthreads();
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      for (int idx = tid; idx < count; idx += kThreads) yfc_stage_element_sim(g, s, arena, params, idx, &plan, &clipped);
+      __syncthreads();                                                                // the stage's output is in the arena
+    }
+    // (the logits stay where they are until the next frame's second stage writes T54 over them, two barriers from here)
+    yfc_cmp_frame acc;
+    yfc_cmp_zero(&acc);
+    for (int i = tid; i < n_logits; i += kThreads) {
+      const float y = arena[logits_off + i];
+      if (logits) logits[(size_t)f * (size_t)n_logits + i] = y;
+      if (ref) yfc_sim_cmp_add(&acc, y, ref[(size_t)f * (size_t)n_logits + i]);
+    }
+    if (ref) {                                                                        // uniform
+      wave_join(acc);
+      const int k = wave_sum(clipped);
+      if (lane == 0) { red[wave] = acc; atomicAdd(clip, k); }
+      __syncthreads();
+      if (tid == 0) {
+        yfc_cmp_frame a = red[0];
+        for (int w = 1; w < kWaves; ++w) yfc_cmp_join(&a, &red[w]);
+        a.saturated = *clip;
+        frame_stats[f] = a;
+      }
+      // (red and clip are written again only behind the next frame's barriers)
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_simulate_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                 const yfc_stage* __restrict__ stages, const yfc_sim_plan plan,
+                                                                 const float* __restrict__ ref, float* __restrict__ logits,
+                                                                 yfc_cmp_frame* __restrict__ frame_stats) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  yfc_cmp_frame* red = reinterpret_cast<yfc_cmp_frame*>(lds + YFC_ARENA_FLOATS);
+  int32_t* clip = reinterpret_cast<int32_t*>(red + kSimRecords);
+  simulate_frames(lds, red, clip, YFC_FRAME_BYTES, YFC_LOGITS, YFC_LOGITS_OFF, frames, n, params, stages, plan, ref, logits, frame_stats);
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_simulate_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                    const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                    const yfc_sim_plan plan, const float* __restrict__ ref,
+                                                                    float* __restrict__ logits, yfc_cmp_frame* __restrict__ frame_stats) {
+  __shared__ yfc_cmp_frame red[kSimRecords];
+  __shared__ int32_t clip;
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  simulate_frames(arena, red, &clip, dims.frame_bytes, dims.logits, dims.logits_off, frames, n, params, stages, plan, ref, logits, frame_stats);
+}
+
 thread_local char g_err[320];
 
 #define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
@@ -549,8 +628,9 @@ static bool place_histogram_tables(yf_calib* c) {
 // The general forms' share of yf_calib_create (the device is current): the grid from an occupancy query, every size's stage table, the event.
 static bool general_setup(yf_calib* c, int cus) {
   int per_cu = 0;
-  const void* kernels[3] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel};
-  for (int k = 0; k < 3; ++k) {                            // one slab count for the three: the fewest resident workgroups any of them has
+  const void* kernels[4] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel,
+                            (const void*)yfc_simulate_hw_kernel};
+  for (int k = 0; k < 4; ++k) {                            // one slab count for the four: the fewest resident workgroups any of them has
     int blocks = 0;
     if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], kThreads, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
       return false;
@@ -665,7 +745,9 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
          && hip_ok(hipMemcpy(c->d_stages, stages, sizeof stages, hipMemcpyHostToDevice), "hipMemcpy(stages)")
          && upload_empty_ranges(c) && hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
     ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_histogram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHistLdsBytes),
-                      "hipFuncSetAttribute(max dynamic LDS, histogram)");
+                      "hipFuncSetAttribute(max dynamic LDS, histogram)")
+         && hip_ok(hipFuncSetAttribute((const void*)yfc_simulate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSimLdsBytes),
+                   "hipFuncSetAttribute(max dynamic LDS, simulate)");
   }
   delete[] p;
   if (!ok) {
@@ -808,6 +890,63 @@ YF_CALIB_API long yf_calib_histogram_hw_device(yf_calib* c, int h, int w, const 
                      c->d_slabs, plan, (unsigned long long*)d_counts);
   if (!hip_ok(hipGetLastError(), "yf_calib_histogram_hw_device: launch of the evaluation")) return -2;
   if (!general_end(c, s)) return -2;
+  return n;
+}
+
+// the totals of a simulate call are those of a comparison with one entry: the head
+static yfc_cmp_plan head_totals_plan(int logits) {
+  yfc_cmp_plan plan;
+  memset(&plan, 0, sizeof plan);
+  plan.count = 1;
+  plan.elements[0] = logits;
+  return plan;
+}
+
+YF_CALIB_API long yf_calib_simulate_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, const void* d_ref_logits,
+                                           void* d_logits, void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_simulate_device: NULL handle"); return -1; }
+  yfc_sim_plan plan;
+  if (yfc_sim_validate("yf_calib_simulate_device", c->stages, d_frames, n, table, d_ref_logits, d_frame_stats, d_totals, &plan, g_err, sizeof g_err)) return -1;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
+  hipLaunchKernelGGL(yfc_simulate_kernel, dim3(grid), dim3(kThreads), kSimLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
+                     (const yfc_stage*)c->d_stages, plan, (const float*)d_ref_logits, (float*)d_logits, (yfc_cmp_frame*)d_frame_stats);
+  if (!hip_ok(hipGetLastError(), "yf_calib_simulate_device: launch of the evaluation")) return -2;
+  if (d_totals) {
+    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, head_totals_plan(YFC_LOGITS),
+                       (yfc_cmp_total*)d_totals);
+    if (!hip_ok(hipGetLastError(), "yf_calib_simulate_device: launch of the totals")) return -2;
+  }
+  return n;
+}
+
+YF_CALIB_API long yf_calib_simulate_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                                              const void* d_ref_logits, void* d_logits, void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_simulate_hw_device: NULL handle"); return -1; }
+  if (size_refused("yf_calib_simulate_hw_device", h, w)) return -1;
+  yfc_sim_plan plan;
+  if (yfc_sim_validate("yf_calib_simulate_hw_device", c->stages, d_frames, n, table, d_ref_logits, d_frame_stats, d_totals, &plan, g_err, sizeof g_err)) return -1;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
+  if (rc) return rc;
+  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
+  hipLaunchKernelGGL(yfc_simulate_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
+                     c->d_slabs, plan, (const float*)d_ref_logits, (float*)d_logits, (yfc_cmp_frame*)d_frame_stats);
+  if (!hip_ok(hipGetLastError(), "yf_calib_simulate_hw_device: launch of the evaluation")) return -2;
+  if (!general_end(c, s)) return -2;
+  if (d_totals) {
+    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, head_totals_plan(dims.logits),
+                       (yfc_cmp_total*)d_totals);
+    if (!hip_ok(hipGetLastError(), "yf_calib_simulate_hw_device: launch of the totals")) return -2;
+  }
   return n;
 }
 

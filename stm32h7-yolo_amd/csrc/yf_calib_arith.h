@@ -165,7 +165,8 @@ static inline void yfc_input_table(float T[YFC_INPUT_TABLE]) {
 }
 
 /* One output element of a stage: idx = (oy * ow + ox) * cout + co.  v[0] the convolution's (or pool's) value, v[1] after the LeakyReLU,
- * v[2] after the ADD -- each meaningful only where the stage has that tensor.  The value the stage ends with is stored. */
+ * v[2] after the ADD -- each meaningful only where the stage has that tensor.  The value the stage ends with is stored.
+ * (yf_calib_sim.h holds a twin, yfc_stage_element_sim, with the simulated quantisation inserted: an edit here belongs there too.) */
 YFC_FN void yfc_stage_element(const yfc_stage* s, float* arena, const float* params, int idx, float v[3]) {
   const int co = idx % s->cout, px = idx / s->cout;
   const int ox = px % s->ow, oy = px / s->ow;

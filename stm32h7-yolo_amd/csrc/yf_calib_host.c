@@ -8,6 +8,7 @@
 #include "yf_calib_arith.h"
 #include "yf_calib_compare.h"
 #include "yf_calib_hist.h"
+#include "yf_calib_sim.h"
 #include "yf_yfw.h"
 
 typedef struct {
@@ -298,5 +299,97 @@ YF_CALIB_API long yf_calib_host_histogram_hw(const void* yfw, size_t bytes, int 
   free(tables);
   free(p);
   if (failed) REFUSE("yf_calib_host_histogram: could not start a thread or allocate its arena");
+  return n;
+}
+
+/* ---- the simulation (yf_calib_sim.h): the evaluation with the enabled tensors on their int8 grids, and the head's record against reference logits ---- */
+typedef struct {
+  const yfc_stage* stages;
+  const yfc_dims* dims;
+  const float* params;
+  const int8_t* frames;
+  const yfc_sim_plan* plan;
+  const float* ref;
+  float* logits;
+  yfc_cmp_frame* stats;
+  long n, first, step;
+  int failed;
+} sim_job;
+
+static void* run_sim_job(void* arg) {
+  sim_job* j = (sim_job*)arg;
+  const yfc_sim_plan* p = j->plan;
+  const size_t logits = (size_t)j->dims->logits;
+  float* arena = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);
+  yfc_cmp_frame* lanes = (yfc_cmp_frame*)malloc(sizeof(yfc_cmp_frame) * YFC_CMP_LANES);
+  if (!arena || !lanes) { free(arena); free(lanes); j->failed = 1; return NULL; }
+  for (long f = j->first; f < j->n; f += j->step) {
+    const int8_t* q = j->frames + (size_t)f * (size_t)j->dims->frame_bytes;
+    int32_t clipped = 0;
+    for (int i = 0; i < j->dims->frame_bytes; ++i) arena[i] = yfc_sim_input(p, j->params[q[i] + 128], &clipped);
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &j->stages[s];
+      const int count = g->oh * g->ow * g->cout;
+      for (int idx = 0; idx < count; ++idx) yfc_stage_element_sim(g, s, arena, j->params, idx, p, &clipped);
+    }
+    const float* y = arena + j->dims->logits_off;
+    if (j->logits) memcpy(j->logits + (size_t)f * logits, y, sizeof(float) * logits);
+    if (j->ref) {
+      const float* x = j->ref + (size_t)f * logits;
+      for (int l = 0; l < YFC_CMP_LANES; ++l) yfc_cmp_zero(&lanes[l]);
+      for (size_t i = 0; i < logits; ++i) yfc_sim_cmp_add(&lanes[i % YFC_CMP_LANES], y[i], x[i]);
+      yfc_cmp_frame_value(lanes, &j->stats[f]);
+      j->stats[f].saturated = clipped;
+    }
+  }
+  free(arena);
+  free(lanes);
+  return NULL;
+}
+
+YF_CALIB_API long yf_calib_host_simulate(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_sim_entry* table,
+                                         const float* ref_logits, float* logits, void* frame_stats, void* totals, int threads, char* err,
+                                         size_t errlen) {
+  return yf_calib_host_simulate_hw(yfw, bytes, 56, 56, frames, n, table, ref_logits, logits, frame_stats, totals, threads, err, errlen);
+}
+
+YF_CALIB_API long yf_calib_host_simulate_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n,
+                                            const yf_calib_sim_entry* table, const float* ref_logits, float* logits, void* frame_stats,
+                                            void* totals, int threads, char* err, size_t errlen) {
+  enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  REFUSE_SIZE("yf_calib_host_simulate");
+  float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
+  if (!p) REFUSE("yf_calib_host_simulate: out of memory");
+  yfc_input_table(p);
+  if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, err, errlen)) { free(p); return -1; }
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t range_tensors[YFC_N_RANGES];
+  yfc_dims dims;
+  yfc_build_stages_hw(stages, range_tensors, h, w);
+  yfc_dims_of(h, w, &dims);
+  yfc_sim_plan plan;
+  if (yfc_sim_validate("yf_calib_host_simulate", stages, frames, n, table, ref_logits, frame_stats, totals, &plan, err, errlen)) { free(p); return -1; }
+  if (threads < 1) threads = 1;
+  if (threads > MAX_THREADS) threads = MAX_THREADS;
+  if ((long)threads > n) threads = (int)n;
+  sim_job jobs[MAX_THREADS];
+  pthread_t tid[MAX_THREADS];
+  int started = 0, failed = 0;
+  for (int t = 0; t < threads; ++t) {
+    const sim_job j = {stages, &dims, p, frames, &plan, ref_logits, logits, ref_logits ? (yfc_cmp_frame*)frame_stats : NULL, n, t, threads, 0};
+    jobs[t] = j;
+  }
+  for (int t = 1; t < threads; ++t) {
+    if (pthread_create(&tid[t], NULL, run_sim_job, &jobs[t]) != 0) { jobs[t].failed = 1; break; }
+    started = t;
+  }
+  run_sim_job(&jobs[0]);
+  for (int t = 1; t <= started; ++t) pthread_join(tid[t], NULL);
+  for (int t = 0; t < threads; ++t) failed |= jobs[t].failed;
+  free(p);
+  if (failed) REFUSE("yf_calib_host_simulate: could not start a thread or allocate its arena");
+  if (ref_logits && totals)
+    for (int field = 0; field < YFC_CMP_FIELDS; ++field)
+      yfc_cmp_total_field((const yfc_cmp_frame*)frame_stats, n, 1, 0, dims.logits, field, (yfc_cmp_total*)totals);
   return n;
 }

@@ -120,7 +120,50 @@ def quantize_model(yfw_bytes, ranges):
     return model_file.write_yfm(g)
 
 
+def dequantized_yfw(yfw_bytes, yfm_bytes, convs=None):
+    """.yfw bytes in which the convolutions listed in `convs` (indices in graph order; None: all) carry the numbers the int8 model
+    `yfm_bytes` gives them, dequantised: w = float32(q) * s_c (one float32 multiply), b = float32(double(q) * double(s_bias)).  The others
+    keep the float values of `yfw_bytes`; with no convolution listed the input bytes come back unchanged."""
+    g = model_file.graph_convs()
+    which = range(len(g)) if convs is None else sorted({int(c) for c in convs})
+    bad = [c for c in which if not 0 <= c < len(g)]
+    if bad:
+        raise ValueError(f"convs: {bad}, expected indices 0 to {len(g) - 1}")
+    if not len(which):
+        return bytes(yfw_bytes)
+    out = list(model_file.read_yfw(yfw_bytes))
+    m = model_file.load_yfm(yfm_bytes)
+    T, ops = m["tensors"], m["ops"]
+    for c in which:
+        d = g[c]
+        wt, bt = T[ops[d["op"]]["ins"][1]], T[ops[d["op"]]["ins"][2]]
+        shape = [1, 1, 1, 1]
+        shape[3 if d["depthwise"] else 0] = -1
+        w = wt["data"].reshape(d["shape"]).astype(np.float32) * wt["scale"].astype(np.float32).reshape(shape)
+        b = (bt["data"].astype(np.float64) * bt["scale"].astype(np.float32).astype(np.float64)).astype(np.float32)
+        out[c] = (w.astype(np.float32), b, d["depthwise"])
+    return model_file.write_yfw(out)
+
+
 CLIP_METHODS = ("minmax", "percentile", "mse")
+
+
+def choose_ranges(candidates, errors):
+    """{tensor: [range, ...]} and {tensor: [error of each candidate]} -> {tensor: the candidate with the least error}; ties go to the earlier
+    candidate (a candidate replaces the choice only when its error is strictly below it, so a NaN never wins).  What
+    calib.quantize_on_device(..., ranges="head") chooses with, the candidates being the "minmax", "percentile" and "mse" ranges in that order
+    and the errors the head's squared error when that tensor alone is quantised."""
+    out = {}
+    for t, cands in candidates.items():
+        e = list(errors[t])
+        if len(e) != len(cands) or not len(cands):
+            raise ValueError(f"tensor {t}: {len(cands)} candidates and {len(e)} errors")
+        best = 0
+        for i in range(1, len(e)):
+            if e[i] < e[best]:
+                best = i
+        out[t] = (float(cands[best][0]), float(cands[best][1]))
+    return out
 
 
 def _edges(lo, hi, bins):

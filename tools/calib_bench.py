@@ -15,6 +15,13 @@ scratch it holds; at --size 56 56 the LDS kernel is timed beside it in the same 
 tools/calib_histogram_bench.py --parent-lib.)
 
     python tools/calib_bench.py --size 160 160 --frames 1024
+
+--simulate times one launch of the simulating form (yf_calib_simulate_device, or yf_calib_simulate_hw_device with --size: csrc/yf_calib_sim.h)
+beside observe in the same run, on the same frames: every entry disabled, every entry enabled, and every entry enabled with reference logits
+(records and totals written).  --parent-lib DIR/libyf_calib.so (built from the parent commit) has that build's observe timed in the same
+process, in rounds that alternate with this build's: the existing kernels did not move.
+
+    python tools/calib_bench.py --simulate [--size 160 160 --frames 1024] [--parent-lib DIR/libyf_calib.so]
 """
 import argparse
 import importlib
@@ -106,6 +113,92 @@ def _ranges_of(cal, d_x):
     return cal.ranges()
 
 
+def simulate_rate(a, calib, torch, yfw):
+    import ctypes
+    h, w = a.size or (56, 56)
+    hw = bool(a.size)
+    n = a.frames
+    d_x = torch.from_numpy(np.random.default_rng(4096).integers(-128, 128, (n, h, w, 3), dtype=np.int8)).cuda()
+    d_l = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device="cuda")
+    d_ref = torch.empty_like(d_l)
+    d_s = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+    d_t = torch.zeros((48,), dtype=torch.uint8, device="cuda")
+    cal = calib.Calibration(yfw)
+    lib, hd, stream = cal._lib, cal.handle, torch.cuda.current_stream().cuda_stream
+    yfm = open(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"), "rb").read()
+    none, full = calib.empty_table(), calib.simulation_table(yfm)
+    size = (h, w) if hw else ()
+
+    def observe_of(library, handle):
+        fn = library.yf_calib_observe_hw_device if hw else library.yf_calib_observe_device
+        def call():
+            if fn(handle, *size, d_x.data_ptr(), n, d_l.data_ptr(), stream) != n:
+                sys.exit("calib_bench: observe failed")
+        return call
+
+    def simulate_of(table, ref):
+        fn = lib.yf_calib_simulate_hw_device if hw else lib.yf_calib_simulate_device
+        def call():
+            rc = fn(hd, *size, d_x.data_ptr(), n, table.ctypes.data, d_ref.data_ptr() if ref else None, d_l.data_ptr(), d_s.data_ptr() if ref else None,
+                    d_t.data_ptr() if ref else None, stream)
+            if rc != n:
+                sys.exit(f"calib_bench: simulate failed: {cal._text()}")
+        return call
+
+    def timed(call):
+        for _ in range(a.warmup):
+            call()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.launches):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            t1.synchronize()
+            ms.append(t0.elapsed_time(t1))
+        return statistics.median(ms), min(ms), max(ms)
+
+    name = f"yf_calib_simulate{'_hw' if hw else ''}_device"
+    print(f"device: {torch.cuda.get_device_name(0)}, libyf_calib.so build id {lib.yf_calib_build_id().decode()}")
+    print(f"One launch at {h}x{w} ({'the general kernels' if hw else 'the LDS kernels'}) over {n} random frames resident in HBM, {a.launches} launches after "
+          f"{a.warmup} warm-up, HIP events, median (min, max) in ms")
+    builds = [("this build", observe_of(lib, hd))]
+    parent = None
+    if a.parent_lib:
+        parent = ctypes.CDLL(a.parent_lib)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        parent.yf_calib_create.restype, parent.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ci]
+        parent.yf_calib_observe_device.restype, parent.yf_calib_observe_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp]
+        parent.yf_calib_observe_hw_device.restype, parent.yf_calib_observe_hw_device.argtypes = ctypes.c_long, [vp, ci, ci, vp, ctypes.c_long, vp, vp]
+        parent.yf_calib_destroy.restype, parent.yf_calib_destroy.argtypes = None, [vp]
+        parent.yf_calib_build_id.restype = ctypes.c_char_p
+        ph = parent.yf_calib_create(yfw, len(yfw), 0)
+        if not ph:
+            sys.exit("calib_bench: yf_calib_create of the parent library failed")
+        builds.append(("parent commit", observe_of(parent, ph)))
+        print(f"  libyf_calib.so of the parent commit: build id {parent.yf_calib_build_id().decode()}, loaded beside this build's; rounds alternate")
+    results = {k: [] for k, _ in builds}
+    for _ in range(3 if parent else 1):
+        for k, call in builds:
+            results[k].append(timed(call))
+    for k, _ in builds:
+        for r, (med, lo, hi) in enumerate(results[k]):
+            print(f"  observe (evaluation + merge, logits written), {k:13s} round {r + 1}   {med:.3f}  ({lo:.3f}, {hi:.3f})")
+    obs = statistics.median(m for m, _, _ in results["this build"])
+    builds[0][1]()
+    torch.cuda.synchronize()
+    d_ref.copy_(d_l)
+    for label, table, ref in (("every entry disabled, logits written", none, False), ("every entry enabled, logits written", full, False),
+                              ("every entry enabled, logits, records and totals", full, True)):
+        med, lo, hi = timed(simulate_of(table, ref))
+        print(f"  {name}, {label:48s} {med:.3f}  ({lo:.3f}, {hi:.3f})   {med / obs:.2f}x observe")
+    if parent:
+        parent.yf_calib_destroy(ph)
+    cal.destroy()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"))
@@ -114,6 +207,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-frames", type=int, default=512)
     ap.add_argument("--restatement-frames", type=int, default=8)
+    ap.add_argument("--simulate", action="store_true", help="time the simulating form beside observe")
+    ap.add_argument("--parent-lib", help="with --simulate: libyf_calib.so built from the parent commit, whose observe is timed beside this build's")
     a = ap.parse_args()
     if a.launches < 20:
         ap.error("--launches: at least 20")
@@ -121,6 +216,10 @@ def main():
     calib = importlib.import_module("stm32h7-yolo_amd.calib")
     model_file = importlib.import_module("stm32h7-yolo_amd.model_file")
     yfw = open(os.path.join(ROOT, "stm32h7-yolo_amd", "model", "yoloface_fp32.yfw"), "rb").read()
+    if a.simulate:
+        if not torch.cuda.is_available():
+            sys.exit("calib_bench: --simulate needs a GPU")
+        return simulate_rate(a, calib, torch, yfw)
     if a.size:
         if not torch.cuda.is_available():
             sys.exit("calib_bench: --size needs a GPU")

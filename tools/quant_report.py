@@ -14,7 +14,14 @@ median of --launches calls after --warmup, each bracketed by HIP events on its s
 --size S reads the frames as int8 [n][S][S][3] (160: the engine's other size) and needs --yfw / --yfm.  At a size other than 56 the table has
 the head's row alone (tensor 100, from yf_network_run_device_hw): the engine's per-stage dump exists at 56x56 only.
 
---ranges {minmax,percentile,mse}, --percentile and --bins choose the calibration ranges of the model it quantises on the device (section 2;
+--sensitivity writes the record profiles/quant_sensitivity.txt holds instead: what each tensor's quantisation alone costs the logits
+(calib.sensitivity: the float evaluation with that tensor on its int8 grid, csrc/yf_calib_sim.h) for the shipped pair, for the model
+quantised on the device at 56x56 and for one calibrated at 160x160; the wall time of a whole table on --bench-frames frames; how close the
+full simulation is to the engine's own head; and what ranges="head" does to section 2 of profiles/quant_report.txt.
+
+    python tools/quant_report.py --sensitivity > profiles/quant_sensitivity.txt
+
+--ranges {minmax,percentile,mse,head}, --percentile and --bins choose the calibration ranges of the model it quantises on the device (section 2;
 calib.quantize_on_device: clipped ranges from histograms, ptq.clip_ranges); the default is min/max, the record's.
 """
 import argparse
@@ -98,6 +105,84 @@ def ctypes_last(entries, count):
     return one
 
 
+def sensitivity_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw, shipped_yfm):
+    """the record of profiles/quant_sensitivity.txt"""
+    import time
+    ptq = importlib.import_module("stm32h7-yolo_amd.ptq")
+    d_x = torch.from_numpy(x).cuda()
+    print("What each tensor's quantisation costs the logits: the float32 evaluation with the named tensor (or the named convolution's weights and")
+    print("bias) on the int8 model's grid and everything else float, against the all-float logits (calib.sensitivity; csrc/yf_calib_sim.h), as")
+    print(f"tools/quant_report.py --sensitivity printed it on: {torch.cuda.get_device_name(0)}, libyf_calib.so build id "
+          f"{calib.load().yf_calib_build_id().decode()}, libyf_network.so build id {net.build_id}")
+    print(f"Frames: the {x.shape[0]} of {os.path.relpath(a.frames, ROOT)}.  rmse and max in LSB of the model's head; clipped: the share of the quantised values")
+    print("that fell outside -128..127.  This is float arithmetic on the int8 grid, not the engine's fixed-point requantisation.")
+
+    def table(title, yfw, yfm, frames):
+        rows = calib.sensitivity(yfw, yfm, frames)
+        print("\n" + title)
+        print(calib.format_sensitivity(rows))
+        single = rows[:50]
+        worst = min(single, key=lambda r: r["sqnr_db"])
+        print(f"  the most damaging single tensor: {worst['name']} ({worst['op']}), {worst['sqnr_db']:.2f} dB; tensor 67 alone: "
+              f"{single[calib.sim_tensors().index(67)]['sqnr_db']:.2f} dB")
+        return rows
+
+    table("1a. oracle/model/yoloface_int8.yfm (the shipped model) on tests/golden/ptq_float_convs.npz (the float weights it came from), 56x56", npz_yfw,
+          shipped_yfm, d_x)
+    new_yfm = calib.quantize_on_device(shipped_yfw, d_x)
+    table("1b. calib.quantize_on_device(stm32h7-yolo_amd/model/yoloface_fp32.yfw, the same frames) on that .yfw, 56x56", shipped_yfw, new_yfm, d_x)
+    real = np.fromfile(os.path.join(ROOT, "tests", "golden", "real_frames_56.bin"), np.int8).reshape(-1, 56, 56, 3)
+    u = (real.astype(np.int16) + 128).astype(np.uint8)
+    x160 = np.stack([ptq.resize_linear_u8(f, 160, 160) for f in u]).reshape(-1, 160, 160, 3)
+    d_160 = torch.from_numpy(np.ascontiguousarray((x160.astype(np.int16) - 128).astype(np.int8))).cuda()
+    yfm160 = calib.quantize_on_device(shipped_yfw, d_160)
+    table(f"1c. the same .yfw calibrated and simulated at 160x160: the {d_160.shape[0]} frames of tests/golden/real_frames_56.bin resized as OpenCV does",
+          shipped_yfw, yfm160, d_160)
+
+    big = torch.from_numpy(np.random.default_rng(4096).integers(-128, 128, (a.bench_frames, 56, 56, 3), dtype=np.int8)).cuda()
+    calib.sensitivity(npz_yfw, shipped_yfm, d_x)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    rows = calib.sensitivity(npz_yfw, shipped_yfm, big)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t
+    handles = 2 + sum(1 for r in rows if r["op"] == "WEIGHTS")        # the float weights, every convolution's own, all dequantised
+    print("\n2. Time of one simulate launch: tools/calib_bench.py --simulate prints it (beside observe, and beside the parent commit's observe)")
+    print(f"\n3. Wall time of one calib.sensitivity call at 56x56 on {a.bench_frames} random frames resident in HBM ({len(rows)} rows: {len(rows) + 1} evaluations, "
+          f"{handles} handles created): {wall:.3f} s")
+
+    # 4. the full simulation against the engine's own head on the same frames
+    cal = calib.Calibration(ptq.dequantized_yfw(npz_yfw, shipped_yfm))
+    ref_cal = calib.Calibration(npz_yfw)
+    ref = ref_cal.simulate(d_x, calib.empty_table())[0]
+    sim = cal.simulate(d_x, calib.simulation_table(shipped_yfm), ref)[0].cpu().numpy().reshape(x.shape[0], -1)
+    cal.destroy(); ref_cal.destroy()
+    T = model_file.load_yfm(shipped_yfm)["tensors"][100]
+    scale, zp = float(T["scale"][0]), int(T["zp"])
+    net.init_model(shipped_yfm)
+    d_out = torch.zeros((x.shape[0], calib.LOGITS), dtype=torch.int8, device="cuda")
+    net.run_device(d_x.data_ptr(), d_out.data_ptr(), x.shape[0], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    heads = d_out.cpu().numpy().astype(np.int64)
+    sim_q = np.rint(sim.astype(np.float64) / scale).astype(np.int64) + zp
+    d = sim_q - heads
+    flt = ref.cpu().numpy().reshape(x.shape[0], -1).astype(np.float64)
+    rms = lambda e: float(np.sqrt(np.mean(e * e)))
+    print(f"\n4. The `all` simulation of 1a against the int8 engine's head on the same {x.shape[0]} frames (head scale {scale:.8f}, zero point {zp}):")
+    print(f"   simulation - engine: rms {rms(d.astype(np.float64)):.3f} LSB; equal bytes {100.0 * np.mean(d == 0):.1f} %; within one LSB {100.0 * np.mean(np.abs(d) <= 1):.1f} %")
+    print(f"   against the float logits: simulation rms {rms(sim - flt) / scale:.3f} LSB, engine rms {rms((heads - zp) * scale - flt) / scale:.3f} LSB")
+
+    print("\n5. Section 2 of profiles/quant_report.txt under each choice of ranges (the model quantised on the device from the shipped .yfw, run on the engine,")
+    print("   int8 tensors against float32 tensors): head sqnr_db, mean sqnr_db over the report's tensors, lowest sqnr_db (tensor)")
+    for method in ("minmax", "percentile", "mse", "head"):
+        yfm = calib.quantize_on_device(shipped_yfw, d_x, ranges=method, percentile=a.percentile, bins=a.bins)
+        net.init_model(yfm)
+        rep = calib.quantisation_report(net, shipped_yfw, yfm, x)
+        low = min(rep, key=lambda r: r["sqnr_db"])
+        print(f"   {method:10s}  head {rep[-1]['sqnr_db']:6.2f}   mean {float(np.mean([r['sqnr_db'] for r in rep])):6.2f}   lowest {low['sqnr_db']:6.2f} ({low['tensor']})")
+    net.init_model(shipped_yfm)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--yfw")
@@ -106,7 +191,8 @@ def main():
     ap.add_argument("--bench-frames", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--ranges", choices=("minmax", "percentile", "mse"), default="minmax")
+    ap.add_argument("--ranges", choices=("minmax", "percentile", "mse", "head"), default="minmax")
+    ap.add_argument("--sensitivity", action="store_true", help="write the record of profiles/quant_sensitivity.txt instead")
     ap.add_argument("--percentile", type=float, default=0.9999)
     ap.add_argument("--bins", type=int, default=2048)
     ap.add_argument("--size", type=int, default=56, help="the side of the frames in --frames (56 or 160)")
@@ -139,6 +225,10 @@ def main():
     npz_yfw = model_file.write_yfw([(z[f"w{k}"], z[f"b{k}"], bool(z[f"dw{k}"])) for k in range(24)])
     shipped_yfm = open(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"), "rb").read()
     shipped_yfw = open(os.path.join(ROOT, "stm32h7-yolo_amd", "model", "yoloface_fp32.yfw"), "rb").read()
+    if a.sensitivity:
+        sensitivity_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw, shipped_yfm)
+        net.destroy()
+        return 0
     print("Quantisation error per tensor, int8 engine against the float32 evaluation (calib.quantisation_report; csrc/yf_calib_compare.h), as")
     print(f"tools/quant_report.py printed it on: {torch.cuda.get_device_name(0)}, libyf_calib.so build id {calib.load().yf_calib_build_id().decode()}, "
           f"libyf_network.so build id {net.build_id}")
