@@ -71,12 +71,20 @@ def quantize_model(yfw_bytes, ranges):
         pool's output), and EVERY input of a CONCATENATION -- a QUANTIZE output or a tensor wired in directly -- carries the output's parameters;
       * PAD and MAX_POOL_2D outputs carry their input's parameters.
     `ranges` must hold the input, every convolution, LeakyReLU and ADD output and the two pool outputs (calib.Calibration.ranges()).
-    A filter channel that is all zero would get scale 0, which no parser admits: ValueError names the convolution and the channel."""
+    A filter channel that is all zero would get scale 0, which no parser admits: ValueError names the convolution and the channel.
+    A range with an end that is not finite, or with min above max, is refused before anything is computed: ValueError names the tensor and
+    the two ends.  Calibration hands over such a range when the float network overflowed on the frames (an infinite end), and (+inf, -inf),
+    the value a slot starts from, for a tensor that was NaN at every element."""
     O = model_file.OPCODE
+    ranges = {int(k): (float(v[0]), float(v[1])) for k, v in ranges.items()}
+    for t in sorted(ranges):
+        lo, hi = ranges[t]
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"ranges: tensor {t}: the range is ({lo}, {hi}), expected two finite numbers with min <= max: the float network "
+                             f"overflowed, or computed nothing but NaN, on the calibration frames")
     convs = model_file.read_yfw(yfw_bytes)
     g = model_file.load_graph()
     T, ops = g["tensors"], g["ops"]
-    ranges = {int(k): (float(v[0]), float(v[1])) for k, v in ranges.items()}
     producer = {o["out"]: o for o in ops}
 
     def range_of(t):
