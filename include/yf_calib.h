@@ -157,6 +157,31 @@ YF_CALIB_API long yf_calib_simulate_device(yf_calib* c, const void* d_frames, lo
 YF_CALIB_API long yf_calib_simulate_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
                                               const void* d_ref_logits, void* d_logits, void* d_frame_stats, void* d_totals, void* stream);
 
+/* ---- Per-channel sums of every convolution's raw output, for bias correction (csrc/yf_calib_chan.h, DESIGN.md "Channel-sum arithmetic";
+ * calib.correct_biases folds the difference of the simulated and the float means into the biases).  The evaluation of
+ * yf_calib_simulate_device again, under the same table: for every convolution, in file order, and every output channel of it the sum over
+ * the frame's pixels of y = acc + bias, the float32 value BEFORE the convolution's own entry quantises it, added in double in the defined
+ * order (chunks of 64 consecutive pixels, the halving of the comparison, the chunks in ascending order).  With every entry disabled these
+ * are the sums of the float evaluation.  Channel first[k] + co belongs to channel co of convolution k (yf_calib_channel_layout);
+ * YF_CALIB_CHANNELS in all.  Pools contribute nothing.
+ * d_frames int8 [n][56][56][3]; `table` is host memory, read during the call only (it travels to the kernel by value); d_frame_sums double
+ * [n][YF_CALIB_CHANNELS] (device memory, the caller's: 4352 bytes per frame) is OVERWRITTEN with one row per frame; d_sums double
+ * [YF_CALIB_CHANNELS] receives the rows added in ascending frame order unless it is NULL; d_logits float [n][7][7][18] receives the logits
+ * unless it is NULL: yf_calib_simulate_device's bits for the same table.  The result does not depend on the grid: device and host build agree
+ * bit for bit.  Asynchronous on `stream`; allocates nothing and does not synchronise the host; touches neither the handle's ranges nor
+ * yf_calib_frames_observed.  Returns n, or a value <= 0 with nothing launched: yf_calib_last_error_text() then names the entry point and what
+ * was refused (a NULL handle, frames, table or frame_sums; n < 1; a table entry, in yf_calib_simulate_device's words). */
+#define YF_CALIB_CHANNELS 544
+#define YF_CALIB_N_CONVS 24
+YF_CALIB_API long yf_calib_channel_sums_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, double* d_frame_sums,
+                                               double* d_sums, void* d_logits, void* stream);
+/* ... and at h x w: the general form, with the scratch and the ordering of the _hw entries above; at (56, 56) the same bits. */
+YF_CALIB_API long yf_calib_channel_sums_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                                                  double* d_frame_sums, double* d_sums, void* d_logits, void* stream);
+/* The channels' layout (both libraries): first[k] and cout[k] of convolution k, and pixels56[k] = the pixels per frame of its output at 56x56
+ * (at h x w: pixels56 * (h / 8) * (w / 8) / 49).  Returns YF_CALIB_CHANNELS, or <= 0 if an argument is NULL. */
+YF_CALIB_API int yf_calib_channel_layout(int32_t first[YF_CALIB_N_CONVS], int32_t cout[YF_CALIB_N_CONVS], int32_t pixels56[YF_CALIB_N_CONVS]);
+
 /* ---- libyf_calib_host.so only: the same evaluation on host arrays, on `threads` threads.  minmax / tensors as yf_calib_ranges fills them
  * (the ranges of these n frames alone), logits float [n][7][7][18] or NULL.  Returns n, or <= 0 with a text in err. */
 YF_CALIB_API long yf_calib_host_run(const void* yfw, size_t bytes, const int8_t* frames, long n, float* minmax, int32_t* tensors,
@@ -188,6 +213,13 @@ YF_CALIB_API long yf_calib_host_simulate(const void* yfw, size_t bytes, const in
 YF_CALIB_API long yf_calib_host_simulate_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n,
                                             const yf_calib_sim_entry* table, const float* ref_logits, float* logits, void* frame_stats,
                                             void* totals, int threads, char* err, size_t errlen);
+
+/* ... and the channel sums (yf_calib_channel_sums_device's arguments as host arrays), at 56x56 and at h x w: bit for bit what the device gives. */
+YF_CALIB_API long yf_calib_host_channel_sums(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_sim_entry* table,
+                                             double* frame_sums, double* sums, float* logits, int threads, char* err, size_t errlen);
+YF_CALIB_API long yf_calib_host_channel_sums_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n,
+                                                const yf_calib_sim_entry* table, double* frame_sums, double* sums, float* logits, int threads,
+                                                char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,12 @@ simulation_table makes the table of a .yfm, sensitivity the table of rows -- eve
 activations, all weights, everything -- and quantize_on_device(..., ranges="head") chooses each tensor's range among the min/max, percentile
 and mse candidates by the head error its quantisation alone causes.
 
+Changing a number the engine runs with: Calibration.channel_sums gives, per output channel of each of the 24 convolutions, the sum of the
+convolution's raw output over the frames, in the float evaluation or under a simulation table (csrc/yf_calib_chan.h, DESIGN.md "Channel-sum
+arithmetic"; host_channel_sums is the same on the CPU, bit for bit); correct_biases folds the difference of the simulated and the float means
+into the biases (empirical bias correction), and quantize_on_device(..., bias_correction="sequential" / "once") applies it to the model it
+returns.
+
 Frames of another size: every function here that takes frames takes [n, h, w, 3] with h and w multiples of 8 up to 160 (160x160 is the
 engine's other size) and infers the size from the shape; such frames go through the library's _hw entries, whose kernels keep a frame's
 activations in global memory (DESIGN.md, "Calibration at h x w").  A flat or [n, 56, 56, 3] input means 56x56 and takes the 56x56 entries;
@@ -53,6 +59,10 @@ assert FRAME_STATS.itemsize == 32 and TOTALS.itemsize == 48
 SIM_ENTRIES = 50
 SIM_ENTRY = np.dtype([("scale", "<f4"), ("zero_point", "<i4")])
 assert SIM_ENTRY.itemsize == 8
+# The channel sums (csrc/yf_calib_chan.h): one double per output channel of every convolution, the convolutions in file order
+CHANNELS = 544
+N_CONVS = 24
+BIAS_MODES = ("sequential", "once")
 RANGE_TENSORS = (0, 51, 52, 53, 54, 55, 56, 57, 58, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 72, 73, 74, 76, 77, 78, 79, 80, 81, 82, 83, 84, 85, 86,
                  87, 88, 89, 90, 91, 92, 94, 95, 96, 97, 98, 99, 100)
 
@@ -146,6 +156,10 @@ def load():
     lib.yf_calib_simulate_device.restype, lib.yf_calib_simulate_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
     lib.yf_calib_simulate_hw_device.restype = ctypes.c_long
     lib.yf_calib_simulate_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
+    lib.yf_calib_channel_sums_device.restype, lib.yf_calib_channel_sums_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp, vp, vp, vp]
+    lib.yf_calib_channel_sums_hw_device.restype = ctypes.c_long
+    lib.yf_calib_channel_sums_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp]
+    lib.yf_calib_channel_layout.restype, lib.yf_calib_channel_layout.argtypes = ctypes.c_int, [vp, vp, vp]
     lib.yf_calib_workgroups.restype, lib.yf_calib_workgroups.argtypes = ctypes.c_int, [vp, ci, ci]
     lib.yf_calib_scratch_bytes.restype, lib.yf_calib_scratch_bytes.argtypes = ctypes.c_size_t, [vp]
     lib.yf_calib_ranges.restype, lib.yf_calib_ranges.argtypes = ctypes.c_int, [vp, vp, vp]
@@ -187,6 +201,13 @@ def load_host():
         lib.yf_calib_host_simulate_hw.restype = ctypes.c_long
         lib.yf_calib_host_simulate_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, ctypes.c_int,
                                                   ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_host_channel_sums.restype = ctypes.c_long
+        lib.yf_calib_host_channel_sums.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
+                                                   ctypes.c_size_t]
+        lib.yf_calib_host_channel_sums_hw.restype = ctypes.c_long
+        lib.yf_calib_host_channel_sums_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, ctypes.c_int,
+                                                      ctypes.c_char_p, ctypes.c_size_t]
+        lib.yf_calib_channel_layout.restype, lib.yf_calib_channel_layout.argtypes = ctypes.c_int, [vp, vp, vp]
         _host = lib
     return _host
 
@@ -303,6 +324,45 @@ def host_simulate(yfw_bytes, frames, table, ref_logits=None, threads=1, general=
     if rc != n or n < 1:
         raise CalibError(f"yf_calib_host_simulate: {err.value.decode()} (returned {rc}, expected {n})")
     return (logits, totals, None if stats is None else stats[:n]) if want_stats else (logits, totals)
+
+
+def channel_layout():
+    """(first, cout, pixels56): int32 arrays [24] -- channel first[k] + co of the channel sums is channel co of convolution k (file order),
+    and pixels56[k] the pixels per frame of its output at 56x56 (elements_at gives another size's).  From whichever of the two libraries is
+    loaded already, else the host build."""
+    lib = _lib if _lib is not None else load_host()
+    first, cout, pixels = (np.zeros(N_CONVS, np.int32) for _ in range(3))
+    rc = lib.yf_calib_channel_layout(first.ctypes.data, cout.ctypes.data, pixels.ctypes.data)
+    if rc != CHANNELS:
+        raise CalibError(f"yf_calib_channel_layout: returned {rc}, expected {CHANNELS}")
+    return first, cout, pixels
+
+
+def channel_pixels(h, w):
+    """float64 [544]: the pixels per frame each channel's sum runs over at h x w -- what a sum over n frames is divided by, times n, for a mean"""
+    first, cout, pixels = channel_layout()
+    return np.repeat([float(elements_at(p, h, w)) for p in pixels], cout)
+
+
+def host_channel_sums(yfw_bytes, frames, table=None, threads=1, general=False, want_frames=False, logits=False):
+    """The channel sums on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) and a table (simulation_table; None: every entry disabled, the float
+    evaluation) -> float64 [544], the sums over all frames; with want_frames (sums, the per-frame sums float64 [n, 544]); with logits the
+    float32 logits [n, h / 8, w / 8, 18] as the last item.  A refused argument raises CalibError with the library's text."""
+    lib = load_host()
+    x, h, w, hw = _host_frames(frames, general)
+    n, t = x.shape[0], _table(empty_table() if table is None else table)
+    rows, sums = np.zeros((max(n, 1), CHANNELS), np.float64), np.zeros(CHANNELS, np.float64)
+    lg = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32) if logits else None
+    err = ctypes.create_string_buffer(400)
+    tail = (x.ctypes.data, n, t.ctypes.data, rows.ctypes.data, sums.ctypes.data, lg.ctypes.data if logits else None, int(threads), err, 400)
+    if hw:
+        rc = lib.yf_calib_host_channel_sums_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
+    else:
+        rc = lib.yf_calib_host_channel_sums(bytes(yfw_bytes), len(yfw_bytes), *tail)
+    if rc != n or n < 1:
+        raise CalibError(f"yf_calib_host_channel_sums: {err.value.decode()} (returned {rc}, expected {n})")
+    out = (sums,) + ((rows[:n],) if want_frames else ()) + ((lg,) if logits else ())
+    return out[0] if len(out) == 1 else out
 
 
 def _ranges_dict(minmax, ids):
@@ -506,6 +566,30 @@ class Calibration:
         totals = None if ref is None else d_totals.cpu().numpy().view(TOTALS).reshape(1)
         return (out, totals, None if ref is None else d_stats[:n]) if want_stats else (out, totals)
 
+    def channel_sums(self, frames, table=None, general=False, want_frames=False, logits=False, stream=None):
+        """Per output channel of each of the 24 convolutions (channel_layout) the sum over `frames` (as observe takes them) of the convolution's
+        raw output y = acc + bias, in the float evaluation (table None: every entry disabled) or under a simulation table, where it is the value
+        before the convolution's own entry quantises it.  Returns float64 [544] (numpy); with want_frames (sums, the per-frame sums: a float64
+        device tensor [n, 544]); with logits the float32 logits, a device tensor [n, h / 8, w / 8, 18], as the last item: simulate's bits for the
+        same table.  Launches on torch's current stream (or `stream`, a raw hipStream_t) and synchronises the device for the sums.  The
+        handle's ranges and frames_observed are not touched."""
+        import torch
+        frames, n, h, w, hw = self._frames(frames, general)
+        dev, t = frames.device, _table(empty_table() if table is None else table)
+        d_rows = torch.empty((max(n, 1), CHANNELS), dtype=torch.float64, device=dev)
+        d_sums = torch.empty((CHANNELS,), dtype=torch.float64, device=dev)
+        out = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device=dev) if logits else None
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if stream is not None:
+            torch.cuda.synchronize(dev)                                              # the upload was made on torch's stream
+        tail = (frames.data_ptr() if n else None, n, t.ctypes.data, d_rows.data_ptr(), d_sums.data_ptr(), out.data_ptr() if logits and n else None, s)
+        rc = self._lib.yf_calib_channel_sums_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_channel_sums_device(self.handle, *tail)
+        if rc != n or n < 1:
+            raise CalibError(f"yf_calib_channel_sums{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+        torch.cuda.synchronize(dev)                                                  # frames are no longer read
+        res = (d_sums.cpu().numpy(),) + ((d_rows[:n],) if want_frames else ()) + ((out,) if logits else ())
+        return res[0] if len(res) == 1 else res
+
     @property
     def frames_observed(self):
         return self._lib.yf_calib_frames_observed(self.handle)
@@ -534,7 +618,7 @@ class Calibration:
             pass
 
 
-def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percentile=0.9999, bins=2048, keep=(0,)):
+def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percentile=0.9999, bins=2048, keep=(0,), bias_correction=None):
     """Float weights (.yfw bytes) and calibration frames -> the bytes of a .yfm image for Network.init_model: the frames are evaluated on the
     GPU, the ranges go through ptq.quantize_model.  `frames`: an int8 DEVICE tensor [n, 56, 56, 3] of the network's frames (pixel - 128,
     RGB), or [n, h, w, 3] with h and w multiples of 8 up to 160: a model meant for the engine's 160x160 configuration is calibrated on
@@ -544,24 +628,95 @@ def quantize_on_device(yfw_bytes, frames, device=None, ranges="minmax", percenti
     ranges: "minmax" (the default) gives every tensor the extremes observed; "percentile" and "mse" clip them (ptq.clip_ranges with
     `percentile` and `keep`) on histograms of `bins` bins taken in a second pass over the same frames; "head" gives every tensor but those
     of `keep` the one of its min/max, percentile and mse ranges whose quantisation, alone in an otherwise float evaluation of the same
-    frames, leaves the least squared error on the logits (head_ranges: some 140 further passes)."""
+    frames, leaves the least squared error on the logits (head_ranges: some 140 further passes).
+    bias_correction: None (the default: the model is quantize_model's of the ranges, byte for byte), or "sequential" / "once": the biases are
+    corrected on the same frames after the ranges are chosen, whichever method chose them (correct_biases)."""
     from . import ptq
     if ranges not in ptq.CLIP_METHODS + ("head",):
         raise ValueError(f"ranges: {ranges!r}, expected one of {ptq.CLIP_METHODS + ('head',)}")
+    if bias_correction is not None and bias_correction not in BIAS_MODES:
+        raise ValueError(f"bias_correction: {bias_correction!r}, expected None or one of {BIAS_MODES}")
     cal = Calibration(yfw_bytes, device)
     try:
         frames = cal._frames(frames, False, at_least_one=True)[0]        # (on the device once, for every pass below)
         cal.observe(frames, logits=False)
-        if ranges == "minmax":
-            return ptq.quantize_model(yfw_bytes, cal.ranges())
-        observed = cal.ranges()
-        counts = cal.histogram(frames, observed, bins).cpu().numpy()
-        if ranges == "head":
-            cands = range_candidates(counts, observed, percentile, keep)
-            return ptq.quantize_model(yfw_bytes, head_ranges(cands, lambda table, ref: cal.simulate(frames, table, ref), keep))
-        return ptq.quantize_model(yfw_bytes, ptq.clip_ranges(counts, observed, ranges, percentile, keep))
+        chosen = cal.ranges()
+        if ranges != "minmax":
+            observed = chosen
+            counts = cal.histogram(frames, observed, bins).cpu().numpy()
+            if ranges == "head":
+                cands = range_candidates(counts, observed, percentile, keep)
+                chosen = head_ranges(cands, lambda table, ref: cal.simulate(frames, table, ref), keep)
+            else:
+                chosen = ptq.clip_ranges(counts, observed, ranges, percentile, keep)
+        device = cal.device
     finally:
         cal.destroy()
+    if bias_correction is None:
+        return ptq.quantize_model(yfw_bytes, chosen)
+    return correct_biases(yfw_bytes, chosen, frames, device, bias_correction)[0]
+
+
+def _frame_count(frames):
+    return int(frames.shape[0]) if len(frames.shape) == 4 and frames.shape[3] == 3 else int(np.prod(tuple(frames.shape))) // FRAME_BYTES
+
+
+def correct_biases(yfw_bytes, ranges, frames, device=None, mode="sequential", channel_sums=None):
+    """Empirical bias correction: float weights (.yfw bytes), the ranges chosen for them ({tensor id: (min, max)}: they are used as given, not
+    derived again) and calibration frames (as observe takes them) -> (the bytes of a .yfm image, report).  Per output channel of each
+    convolution the mean of the raw output y = acc + bias over the frames is measured in the float evaluation of `yfw_bytes` (mean_float: one
+    pass with every entry disabled; a mean is the channel's sum divided by n * pixels, in Python floats) and in the full simulation of the
+    quantised model (mean_sim: its dequantised weights, ptq.dequantized_yfw, under its whole table, simulation_table), and the difference err =
+    mean_sim - mean_float is taken out of the bias: the convolution's new float bias is float32(q * s_bias - err), its current quantised bias
+    dequantised, in double.  The engine adds the bias into its int32 accumulator: the correction costs nothing at run time.
+      "sequential"  for k = 0 .. 23 in graph order: quantise the current weights, one simulated pass, correct convolution k alone.  A
+                    convolution's output depends on earlier convolutions only, so convolution k's offset in the final model is what step k left.
+      "once"        one simulated pass, every convolution corrected from it.
+    report: one dict per convolution -- conv, tensor (the convolution's output), max_err and rms_err: the largest and the root-mean-square
+    |err| over its channels before its correction, in units of the output tensor's scale.
+    The passes run on GPU `device` (None: torch's current), each weight set on a handle of its own that is destroyed after its pass;
+    `channel_sums`, if given, replaces them: channel_sums(yfw_bytes, frames, table) -> float64 [544], e.g. host_channel_sums."""
+    from . import model_file, ptq
+    if mode not in BIAS_MODES:
+        raise ValueError(f"mode: {mode!r}, expected one of {BIAS_MODES}")
+    h, w, _ = frame_size(frames)
+    n = _frame_count(frames)
+
+    def sums(yfw, table):
+        if channel_sums is not None:
+            return np.asarray(channel_sums(yfw, frames, table), np.float64).reshape(CHANNELS)
+        cal = Calibration(yfw, device)
+        try:
+            return cal.channel_sums(frames, table)
+        finally:
+            cal.destroy()
+
+    first, cout, _ = channel_layout()
+    count = channel_pixels(h, w) * float(n)
+    mean_float = sums(bytes(yfw_bytes), empty_table()) / count
+    convs, current, report = model_file.graph_convs(), bytes(yfw_bytes), []
+    for step in (range(N_CONVS) if mode == "sequential" else (None,)):
+        yfm = ptq.quantize_model(current, ranges)
+        err = sums(ptq.dequantized_yfw(current, yfm), simulation_table(yfm)) / count - mean_float
+        m = model_file.load_yfm(yfm)
+        biases = [None] * N_CONVS
+        for k in (range(N_CONVS) if step is None else (step,)):
+            op = m["ops"][convs[k]["op"]]
+            bt, e = m["tensors"][op["ins"][2]], err[first[k]:first[k] + cout[k]]
+            deq = bt["data"].astype(np.float64) * bt["scale"].astype(np.float32).astype(np.float64)
+            biases[k] = (deq - e).astype(np.float32)
+            lsb = np.abs(e) / float(m["tensors"][op["out"]]["scale"][0])
+            report.append(dict(conv=k, tensor=int(op["out"]), max_err=float(lsb.max()), rms_err=float(np.sqrt((lsb * lsb).mean()))))
+        current = ptq.with_biases(current, biases)
+    return ptq.quantize_model(current, ranges), report
+
+
+def format_bias_report(report):
+    """the report of correct_biases as text, one line per convolution"""
+    out = [f"{'conv':>4} {'tensor':>6} {'max |err| / scale':>18} {'rms |err| / scale':>18}"]
+    for r in report:
+        out.append(f"{r['conv']:>4} {r['tensor']:>6} {r['max_err']:>18.4f} {r['rms_err']:>18.4f}")
+    return "\n".join(out)
 
 
 def frame_stats_array(d_stats):
@@ -721,7 +876,7 @@ def sensitivity(yfw_bytes, yfm_bytes, frames, device=None, simulate=None):
     replaces them: simulate(yfw_bytes, frames, table, ref_logits) -> (logits, totals), e.g. host_simulate."""
     from . import model_file, ptq
     h, w, _ = frame_size(frames)
-    n = int(frames.shape[0]) if len(frames.shape) == 4 and frames.shape[3] == 3 else int(np.prod(tuple(frames.shape))) // FRAME_BYTES
+    n = _frame_count(frames)
     graph, model = model_file.load_graph(), model_file.load_yfm(yfm_bytes)
     head_scale = float(model["tensors"][graph["output"]]["scale"][0])
     names = {v: k for k, v in model_file.OPCODE.items()}

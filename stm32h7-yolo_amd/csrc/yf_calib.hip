@@ -38,6 +38,16 @@
 // thread accumulates the head's error terms of the logits it copies out (a thread is a lane, a wave a group: compare_fold's order for one
 // entry), and the frame's count of clipped values goes through a wave reduction and one LDS add per wave.  One body serves both kernels: the
 // LDS form calls it with the 56x56 sizes as constants.
+//
+// The channel-summing form (yf_calib_channel_sums_device and its _hw form, csrc/yf_calib_chan.h) is the simulating form's stage loop with another
+// deal of a stage's elements -- free here, because an element's stored bits do not depend on who computes it.  A task is one (channel, chunk
+// of 64 consecutive pixels) pair and a wave takes whole tasks: its 64 lanes compute the chunk's pixels of that channel through the two parts
+// of yfc_stage_element_sim, store the stage's result in the arena as always, and reduce the raw y = acc + bias in double with __shfl_down
+// (wave_join's pattern: s[l] = s[l] + s[l + h]); lane 0 leaves the chunk's value in an LDS scratch [cout][chunks].  Behind the barrier that ends
+// the stage thread c < cout adds its channel's chunks in ascending order and writes d_frame_sums[f][first + c].  The scratch alternates
+// between two halves from one stage to the next, as `red` does in fold(): 2 x 18 x 13 doubles beside the arena at 56x56, 2 x 18 x 100 in the slab
+// form.  Pool stages run as in the simulation.  A second launch, one thread per channel, adds the frames in ascending order.  Nothing is
+// ordered by arrival: no atomics, and the result does not depend on the grid.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -48,6 +58,7 @@
 #include "yf_calib_compare.h"
 #include "yf_calib_hist.h"
 #include "yf_calib_sim.h"
+#include "yf_calib_chan.h"
 #include "yf_yfw.h"
 
 #ifndef YF_CALIB_BUILD_ID
@@ -562,6 +573,89 @@ __global__ __launch_bounds__(kThreads) void yfc_simulate_hw_kernel(const int8_t*
   simulate_frames(arena, red, &clip, dims.frame_bytes, dims.logits, dims.logits_off, frames, n, params, stages, plan, ref, logits, frame_stats);
 }
 
+// ---- the channel-summing form: one body, the arena in LDS (the 56x56 sizes as constants) or in this workgroup's slab ----
+constexpr size_t kChanLdsBytes = sizeof(float) * YFC_ARENA_FLOATS + sizeof(double) * 2 * YFC_CHAN_SCRATCH_56;
+static_assert(sizeof(double) * 2 * YFC_CHAN_SCRATCH_56 == 3744 && kChanLdsBytes <= 160 * 1024,
+              "the arena and both halves of the chunk scratch (18 channels x 13 chunks of doubles each) must fit the CU's LDS");
+static_assert(sizeof(float) * YFC_ARENA_FLOATS % alignof(double) == 0, "the chunk scratch behind the arena is aligned");
+static_assert(YFC_CHAN_SCRATCH_MAX == 18 * (((YFC_MAX_SIDE / 2) * (YFC_MAX_SIDE / 2) + YFC_CHAN_CHUNK - 1) / YFC_CHAN_CHUNK) && YFC_CHAN_CHUNK == 64,
+              "the slab form's scratch is the 18-channel stage at the largest size; a chunk is a wave");
+constexpr int kChanTotalsThreads = 256;
+
+// scratch: two halves of half_doubles doubles (LDS).  frame_bytes, n_logits and logits_off describe the arena.
+__device__ __forceinline__ void channel_sum_frames(float* arena, double* scratch, const int half_doubles, const int frame_bytes, const int n_logits,
+                                                   const int logits_off, const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                   const yfc_stage* __restrict__ stages, const yfc_chan_plan& plan, double* __restrict__ frame_sums,
+                                                   float* __restrict__ logits) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                          // (uniform: a task's channel and chunk are scalars)
+  int parity = 0;
+  for (long f = blockIdx.x; f < n; f += gridDim.x) {
+    const int8_t* q = frames + (size_t)f * (size_t)frame_bytes;
+    int32_t clipped = 0;                                                              // (counted by the element function; not reported here)
+    for (int i = tid; i < frame_bytes; i += kThreads) arena[i] = yfc_sim_input(&plan.sim, params[(int)q[i] + 128], &clipped);
+    __syncthreads();
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &stages[s];
+      const int pixels = g->oh * g->ow, cout = g->cout;
+      if (g->kind != YFC_CONV) {                                                      // uniform: a pool, as the simulation runs it
+        for (int idx = tid; idx < pixels * cout; idx += kThreads) yfc_stage_element_sim(g, s, arena, params, idx, &plan.sim, &clipped);
+        __syncthreads();
+        continue;
+      }
+      const int chunks = yfc_chan_chunks(pixels);
+      double* half = scratch + parity * half_doubles;
+      for (int task = wave; task < cout * chunks; task += kWaves) {
+        const int co = task / chunks, chunk = task - co * chunks;
+        const int px = chunk * YFC_CHAN_CHUNK + lane;
+        double v = 0.0;
+        if (px < pixels) {
+          const int idx = px * cout + co;
+          const float y = yfc_stage_element_sim_raw(g, arena, params, idx);
+          yfc_stage_element_sim_finish(g, s, arena, idx, y, &plan.sim, &clipped);
+          v = (double)y;
+        }
+        for (int h = 32; h; h >>= 1) v = v + __shfl_down(v, h, 64);                   // lane 0 ends with the chunk's value
+        if (lane == 0) half[co * chunks + chunk] = v;
+      }
+      __syncthreads();                                                                // the stage's output is in the arena, its chunks in `half`
+      if (tid < cout) {
+        double a = half[tid * chunks];
+        for (int k = 1; k < chunks; ++k) a = a + half[tid * chunks + k];
+        frame_sums[(size_t)f * YFC_CHANNELS + plan.first[s] + tid] = a;
+      }
+      parity ^= 1;                                                                    // (this half is written again two stages, and so two barriers, on)
+    }
+    // (the logits stay where they are until the next frame's second stage writes T54 over them, two barriers from here)
+    if (logits)
+      for (int i = tid; i < n_logits; i += kThreads) logits[(size_t)f * (size_t)n_logits + i] = arena[logits_off + i];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_channel_sums_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                     const yfc_stage* __restrict__ stages, const yfc_chan_plan plan,
+                                                                     double* __restrict__ frame_sums, float* __restrict__ logits) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  double* scratch = reinterpret_cast<double*>(lds + YFC_ARENA_FLOATS);
+  channel_sum_frames(lds, scratch, YFC_CHAN_SCRATCH_56, YFC_FRAME_BYTES, YFC_LOGITS, YFC_LOGITS_OFF, frames, n, params, stages, plan, frame_sums, logits);
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_channel_sums_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                        const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                        const yfc_chan_plan plan, double* __restrict__ frame_sums,
+                                                                        float* __restrict__ logits) {
+  __shared__ double scratch[2 * YFC_CHAN_SCRATCH_MAX];
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  channel_sum_frames(arena, scratch, YFC_CHAN_SCRATCH_MAX, dims.frame_bytes, dims.logits, dims.logits_off, frames, n, params, stages, plan, frame_sums,
+                     logits);
+}
+
+// sums[c] = the frames' rows added in ascending frame order: one thread per channel
+__global__ __launch_bounds__(kChanTotalsThreads) void yfc_channel_totals_kernel(const double* __restrict__ frame_sums, long n, double* __restrict__ sums) {
+  const int c = blockIdx.x * kChanTotalsThreads + threadIdx.x;
+  if (c < YFC_CHANNELS) sums[c] = yfc_chan_total(frame_sums, n, c);
+}
+
 thread_local char g_err[320];
 
 #define set_error(...) snprintf(g_err, sizeof g_err, __VA_ARGS__)
@@ -628,9 +722,9 @@ static bool place_histogram_tables(yf_calib* c) {
 // The general forms' share of yf_calib_create (the device is current): the grid from an occupancy query, every size's stage table, the event.
 static bool general_setup(yf_calib* c, int cus) {
   int per_cu = 0;
-  const void* kernels[4] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel,
-                            (const void*)yfc_simulate_hw_kernel};
-  for (int k = 0; k < 4; ++k) {                            // one slab count for the four: the fewest resident workgroups any of them has
+  const void* kernels[5] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel,
+                            (const void*)yfc_simulate_hw_kernel, (const void*)yfc_channel_sums_hw_kernel};
+  for (int k = 0; k < 5; ++k) {                            // one slab count for the five: the fewest resident workgroups any of them has
     int blocks = 0;
     if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], kThreads, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
       return false;
@@ -727,6 +821,13 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
   if (!ok) set_error("yf_calib_create: the stage table gives %d parameter floats, the graph %d", last.b_off + last.cout, kParamFloats);
   ok = ok && place_histogram_tables(c);
   if (ok) {
+    int32_t first[YFC_N_CONVS], cout[YFC_N_CONVS], pixels[YFC_N_CONVS];
+    const int channels = yfc_chan_layout(stages, first, cout, pixels), scratch = yfc_chan_scratch_doubles(stages);
+    ok = channels == YFC_CHANNELS && scratch == YFC_CHAN_SCRATCH_56;
+    if (!ok) set_error("yf_calib_create: the stage table gives %d channels and a chunk scratch of %d doubles, expected %d of the graph and %d", channels,
+                       scratch, (int)YFC_CHANNELS, (int)YFC_CHAN_SCRATCH_56);
+  }
+  if (ok) {
     DeviceScope scope(device);
     int cus = 0;
     ok = scope.ok && hip_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "hipDeviceGetAttribute(multiprocessors)");
@@ -747,7 +848,9 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
     ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_histogram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHistLdsBytes),
                       "hipFuncSetAttribute(max dynamic LDS, histogram)")
          && hip_ok(hipFuncSetAttribute((const void*)yfc_simulate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSimLdsBytes),
-                   "hipFuncSetAttribute(max dynamic LDS, simulate)");
+                   "hipFuncSetAttribute(max dynamic LDS, simulate)")
+         && hip_ok(hipFuncSetAttribute((const void*)yfc_channel_sums_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChanLdsBytes),
+                   "hipFuncSetAttribute(max dynamic LDS, channel sums)");
   }
   delete[] p;
   if (!ok) {
@@ -948,6 +1051,70 @@ YF_CALIB_API long yf_calib_simulate_hw_device(yf_calib* c, int h, int w, const v
     if (!hip_ok(hipGetLastError(), "yf_calib_simulate_hw_device: launch of the totals")) return -2;
   }
   return n;
+}
+
+YF_CALIB_API long yf_calib_channel_sums_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, double* d_frame_sums,
+                                               double* d_sums, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_channel_sums_device: NULL handle"); return -1; }
+  yfc_chan_plan plan;
+  if (yfc_chan_validate("yf_calib_channel_sums_device", c->stages, d_frames, n, table, d_frame_sums, &plan, g_err, sizeof g_err)) return -1;
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
+  hipLaunchKernelGGL(yfc_channel_sums_kernel, dim3(grid), dim3(kThreads), kChanLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
+                     (const yfc_stage*)c->d_stages, plan, d_frame_sums, (float*)d_logits);
+  if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_device: launch of the evaluation")) return -2;
+  if (d_sums) {
+    hipLaunchKernelGGL(yfc_channel_totals_kernel, dim3((YFC_CHANNELS + kChanTotalsThreads - 1) / kChanTotalsThreads), dim3(kChanTotalsThreads), 0, s,
+                       (const double*)d_frame_sums, n, d_sums);
+    if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_device: launch of the totals")) return -2;
+  }
+  return n;
+}
+
+YF_CALIB_API long yf_calib_channel_sums_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                                                  double* d_frame_sums, double* d_sums, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("yf_calib_channel_sums_hw_device: NULL handle"); return -1; }
+  if (size_refused("yf_calib_channel_sums_hw_device", h, w)) return -1;
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t ids[YFC_N_RANGES];
+  yfc_build_stages_hw(stages, ids, h, w);
+  yfc_chan_plan plan;
+  if (yfc_chan_validate("yf_calib_channel_sums_hw_device", stages, d_frames, n, table, d_frame_sums, &plan, g_err, sizeof g_err)) return -1;
+  if (yfc_chan_scratch_doubles(stages) > YFC_CHAN_SCRATCH_MAX) {
+    set_error("yf_calib_channel_sums_hw_device: h = %d, w = %d needs a chunk scratch of %d doubles, the kernel has %d", h, w,
+              yfc_chan_scratch_doubles(stages), (int)YFC_CHAN_SCRATCH_MAX);
+    return -1;
+  }
+  DeviceScope scope(c->device);
+  if (!scope.ok) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
+  if (rc) return rc;
+  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
+  hipLaunchKernelGGL(yfc_channel_sums_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
+                     c->d_slabs, plan, d_frame_sums, (float*)d_logits);
+  if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_hw_device: launch of the evaluation")) return -2;
+  if (!general_end(c, s)) return -2;
+  if (d_sums) {
+    hipLaunchKernelGGL(yfc_channel_totals_kernel, dim3((YFC_CHANNELS + kChanTotalsThreads - 1) / kChanTotalsThreads), dim3(kChanTotalsThreads), 0, s,
+                       (const double*)d_frame_sums, n, d_sums);
+    if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_hw_device: launch of the totals")) return -2;
+  }
+  return n;
+}
+
+YF_CALIB_API int yf_calib_channel_layout(int32_t first[YF_CALIB_N_CONVS], int32_t cout[YF_CALIB_N_CONVS], int32_t pixels56[YF_CALIB_N_CONVS]) {
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t ids[YFC_N_RANGES];
+  if (!first || !cout || !pixels56) return -1;
+  yfc_build_stages(stages, ids);
+  return yfc_chan_layout(stages, first, cout, pixels56);
 }
 
 YF_CALIB_API int yf_calib_workgroups(const yf_calib* c, int h, int w) {

@@ -9,6 +9,7 @@
 #include "yf_calib_compare.h"
 #include "yf_calib_hist.h"
 #include "yf_calib_sim.h"
+#include "yf_calib_chan.h"
 #include "yf_yfw.h"
 
 typedef struct {
@@ -392,4 +393,100 @@ YF_CALIB_API long yf_calib_host_simulate_hw(const void* yfw, size_t bytes, int h
     for (int field = 0; field < YFC_CMP_FIELDS; ++field)
       yfc_cmp_total_field((const yfc_cmp_frame*)frame_stats, n, 1, 0, dims.logits, field, (yfc_cmp_total*)totals);
   return n;
+}
+
+/* ---- the channel sums (yf_calib_chan.h): the simulation again, the raw value of every convolution kept for the stage and added per channel in
+ * the defined order ---- */
+typedef struct {
+  const yfc_stage* stages;
+  const yfc_dims* dims;
+  const float* params;
+  const int8_t* frames;
+  const yfc_chan_plan* plan;
+  double* frame_sums;
+  float* logits;
+  long n, first, step;
+  int failed;
+} chan_job;
+
+static void* run_chan_job(void* arg) {
+  chan_job* j = (chan_job*)arg;
+  const yfc_sim_plan* p = &j->plan->sim;
+  const size_t logits = (size_t)j->dims->logits;
+  float* arena = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);
+  float* raw = (float*)malloc(sizeof(float) * (size_t)j->dims->arena_floats);      /* (no stage has more elements than the arena has floats) */
+  if (!arena || !raw) { free(arena); free(raw); j->failed = 1; return NULL; }
+  for (long f = j->first; f < j->n; f += j->step) {
+    const int8_t* q = j->frames + (size_t)f * (size_t)j->dims->frame_bytes;
+    double* row = j->frame_sums + (size_t)f * YFC_CHANNELS;
+    int32_t clipped = 0;
+    for (int i = 0; i < j->dims->frame_bytes; ++i) arena[i] = yfc_sim_input(p, j->params[q[i] + 128], &clipped);
+    for (int s = 0; s < YFC_N_STAGES; ++s) {
+      const yfc_stage* g = &j->stages[s];
+      const int pixels = g->oh * g->ow, count = pixels * g->cout;
+      for (int idx = 0; idx < count; ++idx) {
+        raw[idx] = yfc_stage_element_sim_raw(g, arena, j->params, idx);
+        yfc_stage_element_sim_finish(g, s, arena, idx, raw[idx], p, &clipped);
+      }
+      if (g->kind != YFC_CONV) continue;
+      for (int co = 0; co < g->cout; ++co) row[j->plan->first[s] + co] = yfc_chan_frame_value(raw, pixels, g->cout, co);
+    }
+    if (j->logits) memcpy(j->logits + (size_t)f * logits, arena + j->dims->logits_off, sizeof(float) * logits);
+  }
+  free(arena);
+  free(raw);
+  return NULL;
+}
+
+YF_CALIB_API long yf_calib_host_channel_sums(const void* yfw, size_t bytes, const int8_t* frames, long n, const yf_calib_sim_entry* table,
+                                             double* frame_sums, double* sums, float* logits, int threads, char* err, size_t errlen) {
+  return yf_calib_host_channel_sums_hw(yfw, bytes, 56, 56, frames, n, table, frame_sums, sums, logits, threads, err, errlen);
+}
+
+YF_CALIB_API long yf_calib_host_channel_sums_hw(const void* yfw, size_t bytes, int h, int w, const int8_t* frames, long n,
+                                                const yf_calib_sim_entry* table, double* frame_sums, double* sums, float* logits, int threads,
+                                                char* err, size_t errlen) {
+  enum { MAX_THREADS = 64, PARAM_FLOATS = YFC_INPUT_TABLE + YF_YFW_FLOATS };
+  REFUSE_SIZE("yf_calib_host_channel_sums");
+  float* p = (float*)malloc(sizeof(float) * PARAM_FLOATS);
+  if (!p) REFUSE("yf_calib_host_channel_sums: out of memory");
+  yfc_input_table(p);
+  if (yf_yfw_parse(yfw, bytes, p + YFC_INPUT_TABLE, err, errlen)) { free(p); return -1; }
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t range_tensors[YFC_N_RANGES];
+  yfc_dims dims;
+  yfc_build_stages_hw(stages, range_tensors, h, w);
+  yfc_dims_of(h, w, &dims);
+  yfc_chan_plan plan;
+  if (yfc_chan_validate("yf_calib_host_channel_sums", stages, frames, n, table, frame_sums, &plan, err, errlen)) { free(p); return -1; }
+  if (threads < 1) threads = 1;
+  if (threads > MAX_THREADS) threads = MAX_THREADS;
+  if ((long)threads > n) threads = (int)n;
+  chan_job jobs[MAX_THREADS];
+  pthread_t tid[MAX_THREADS];
+  int started = 0, failed = 0;
+  for (int t = 0; t < threads; ++t) {
+    const chan_job j = {stages, &dims, p, frames, &plan, frame_sums, logits, n, t, threads, 0};
+    jobs[t] = j;
+  }
+  for (int t = 1; t < threads; ++t) {
+    if (pthread_create(&tid[t], NULL, run_chan_job, &jobs[t]) != 0) { jobs[t].failed = 1; break; }
+    started = t;
+  }
+  run_chan_job(&jobs[0]);
+  for (int t = 1; t <= started; ++t) pthread_join(tid[t], NULL);
+  for (int t = 0; t < threads; ++t) failed |= jobs[t].failed;
+  free(p);
+  if (failed) REFUSE("yf_calib_host_channel_sums: could not start a thread or allocate its arena");
+  if (sums)
+    for (int c = 0; c < YFC_CHANNELS; ++c) sums[c] = yfc_chan_total(frame_sums, n, c);
+  return n;
+}
+
+YF_CALIB_API int yf_calib_channel_layout(int32_t first[YF_CALIB_N_CONVS], int32_t cout[YF_CALIB_N_CONVS], int32_t pixels56[YF_CALIB_N_CONVS]) {
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t range_tensors[YFC_N_RANGES];
+  if (!first || !cout || !pixels56) return -1;
+  yfc_build_stages(stages, range_tensors);
+  return yfc_chan_layout(stages, first, cout, pixels56);
 }

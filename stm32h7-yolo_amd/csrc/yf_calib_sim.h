@@ -99,8 +99,11 @@ YFC_FN void yfc_sim_cmp_add(yfc_cmp_frame* a, float y, float x) {
 
 /* One output element of stage `si` (s = &stages[si]) with the plan's quantisation: yfc_stage_element, and the four points above.  A COPY of
  * yfc_stage_element (yf_calib_arith.h), kept apart so that the bits of the existing kernels stay frozen: whoever edits one edits the other; the
- * all-disabled tests (equal to host_run / observe bit for bit) are what keeps the two in step. */
-YFC_FN void yfc_stage_element_sim(const yfc_stage* s, int si, float* arena, const float* params, int idx, const yfc_sim_plan* p, int32_t* clipped) {
+ * all-disabled tests (equal to host_run / observe bit for bit) are what keeps the two in step.
+ * In two parts, so that the channel sums (yf_calib_chan.h) can read the value between them: yfc_stage_element_sim_raw ends with the raw
+ * value -- a convolution's y = acc + bias, a pool's maximum, before the stage's r_conv entry quantises it --, yfc_stage_element_sim_finish
+ * is everything after and stores the element.  yfc_stage_element_sim is the two in a row. */
+YFC_FN float yfc_stage_element_sim_raw(const yfc_stage* s, const float* arena, const float* params, int idx) {
   const int co = idx % s->cout, px = idx / s->cout;
   const int ox = px % s->ow, oy = px / s->ow;
   const int k = s->k, h = s->h, w = s->w, cin = s->cin;
@@ -119,7 +122,6 @@ YFC_FN void yfc_stage_element_sim(const yfc_stage* s, int si, float* arena, cons
         y = t > y ? t : y;
       }
     }
-    if (p->e[s->r_conv].scale != 0.0f) y = yfc_sim_q(&p->e[s->r_conv], y, clipped);
   } else {
     const float* wt = params + s->w_off;
     float acc = 0.0f;
@@ -139,7 +141,14 @@ YFC_FN void yfc_stage_element_sim(const yfc_stage* s, int si, float* arena, cons
       }
     }
     y = acc + params[s->b_off + co];
-    if (p->e[s->r_conv].scale != 0.0f) y = yfc_sim_q(&p->e[s->r_conv], y, clipped);
+  }
+  return y;
+}
+
+YFC_FN void yfc_stage_element_sim_finish(const yfc_stage* s, int si, float* arena, int idx, float y, const yfc_sim_plan* p, int32_t* clipped) {
+  const int co = idx % s->cout, px = idx / s->cout;
+  if (p->e[s->r_conv].scale != 0.0f) y = yfc_sim_q(&p->e[s->r_conv], y, clipped);
+  if (s->kind != YFC_POOL) {
     if (s->leaky) {
       y = y >= 0.0f ? y : y * YFC_LEAKY_ALPHA;
       if (p->e[s->r_leaky].scale != 0.0f) y = yfc_sim_q(&p->e[s->r_leaky], y, clipped);
@@ -152,6 +161,10 @@ YFC_FN void yfc_stage_element_sim(const yfc_stage* s, int si, float* arena, cons
   const int q = p->stage_q[si];
   if (q >= 0 && p->e[q].scale != 0.0f) y = yfc_sim_q(&p->e[q], y, clipped);
   arena[s->out_off + px * s->out_cstride + s->out_coff + co] = y;
+}
+
+YFC_FN void yfc_stage_element_sim(const yfc_stage* s, int si, float* arena, const float* params, int idx, const yfc_sim_plan* p, int32_t* clipped) {
+  yfc_stage_element_sim_finish(s, si, arena, idx, yfc_stage_element_sim_raw(s, arena, params, idx), p, clipped);
 }
 
 /* ---- host only ----

@@ -153,6 +153,29 @@ def dequantized_yfw(yfw_bytes, yfm_bytes, convs=None):
     return model_file.write_yfw(out)
 
 
+def with_biases(yfw_bytes, biases):
+    """.yfw bytes with the same weights and the given biases: `biases` has one item per convolution in graph order -- float32 [cout], or None
+    for a convolution that keeps its bias -- or is a dict {convolution: bias}.  A bias of another length or with a value that is not finite
+    raises ValueError naming the convolution."""
+    convs = list(model_file.read_yfw(yfw_bytes))
+    if isinstance(biases, dict):
+        bad = [c for c in biases if not 0 <= int(c) < len(convs)]
+        if bad:
+            raise ValueError(f"biases: convolutions {sorted(bad)}, expected indices 0 to {len(convs) - 1}")
+        biases = [biases.get(c) for c in range(len(convs))]
+    if len(biases) != len(convs):
+        raise ValueError(f"biases: {len(biases)} items, expected one per convolution ({len(convs)})")
+    for c, b in enumerate(biases):
+        if b is None:
+            continue
+        b = np.asarray(b, np.float32).reshape(-1)
+        if b.size != convs[c][1].size or not np.isfinite(b).all():
+            raise ValueError(f"biases: conv {c}: {b.size} values{'' if np.isfinite(b).all() else ', not all finite'}, expected {convs[c][1].size} "
+                             f"finite float32")
+        convs[c] = (convs[c][0], b, convs[c][2])
+    return model_file.write_yfw(convs)
+
+
 CLIP_METHODS = ("minmax", "percentile", "mse")
 
 

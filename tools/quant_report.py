@@ -21,6 +21,15 @@ full simulation is to the engine's own head; and what ranges="head" does to sect
 
     python tools/quant_report.py --sensitivity > profiles/quant_sensitivity.txt
 
+--bias-correction MODE (sequential or once) writes the record profiles/bias_correction.txt holds instead: the time of one channel-sums launch
+(calib.Calibration.channel_sums; csrc/yf_calib_chan.h) beside a simulate launch under the same tables, at 56x56 and at 160x160, and, with
+--parent-lib DIR/libyf_calib.so (built from the parent commit), that build's simulate and observe in the same run; the wall time of a whole
+calib.correct_biases call in each mode; and what the correction does to the shipped pair and to the model quantised on the device -- the
+rows of correct_biases' report, the head's SQNR by the full simulation and by the engine before and after, and the engine's per-tensor table
+(mean_error among its columns) before and after in MODE -- on min/max ranges and on ranges="mse".
+
+    python tools/quant_report.py --bias-correction sequential [--parent-lib DIR/libyf_calib.so] > profiles/bias_correction.txt
+
 --ranges {minmax,percentile,mse,head}, --percentile and --bins choose the calibration ranges of the model it quantises on the device (section 2;
 calib.quantize_on_device: clipped ranges from histograms, ptq.clip_ranges); the default is min/max, the record's.
 """
@@ -183,6 +192,199 @@ def sensitivity_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw
     net.init_model(shipped_yfm)
 
 
+def kernel_registers(names):
+    """one line per kernel of csrc/yf_calib.hip whose name holds one of `names`: VGPRs, SGPRs, spills, scratch and static LDS as the code object's
+    metadata states them (hipcc -S --cuda-device-only with CALIBFLAGS)"""
+    import re
+    import subprocess
+    import tempfile
+    libs = importlib.import_module("stm32h7-yolo_amd.libs")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "yf_calib.s")
+        cmd = [os.environ.get("HIPCC", os.path.join(os.environ.get("ROCM", "/opt/rocm"), "bin", "hipcc"))] + libs.make_var("CALIBFLAGS").split() + ["-S", "--cuda-device-only", os.path.join(libs.CSRC, "yf_calib.hip"), "-o", out]
+        try:
+            subprocess.check_call(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            text = open(out).read()
+        except (OSError, subprocess.CalledProcessError) as e:
+            return [f"not read: {e}"]
+    lines = []
+    for blk in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, flags=re.S):
+        g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
+        name = re.search(r"yfc_\w+?_kernel", g("name"))
+        if name and any(k in name.group(0) for k in names):
+            lines.append(f"{name.group(0):28s} {g('vgpr_count'):>3} VGPRs  {g('sgpr_count'):>3} SGPRs  VGPR spill {g('vgpr_spill_count')}  scratch "
+                         f"{g('private_segment_fixed_size')} B  static LDS {g('group_segment_fixed_size')} B")
+    return lines
+
+
+def bias_correction_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw):
+    """the record of profiles/bias_correction.txt"""
+    import ctypes
+    import math
+    import time
+    ptq = importlib.import_module("stm32h7-yolo_amd.ptq")
+    lib = calib.load()
+    print("Empirical bias correction (calib.correct_biases): per output channel of each convolution the mean of the simulated network's raw output")
+    print("against the float network's, folded into the bias; the sums come from yf_calib_channel_sums_device (csrc/yf_calib_chan.h).  As")
+    print(f"tools/quant_report.py --bias-correction {a.bias_correction} printed it on: {torch.cuda.get_device_name(0)}, libyf_calib.so build id "
+          f"{lib.yf_calib_build_id().decode()}, libyf_network.so build id {net.build_id}")
+
+    # (a) one launch
+    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+    parent = None
+    if a.parent_lib:
+        parent = ctypes.CDLL(a.parent_lib)
+        parent.yf_calib_create.restype, parent.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ci]
+        parent.yf_calib_observe_device.restype, parent.yf_calib_observe_device.argtypes = cl, [vp, vp, cl, vp, vp]
+        parent.yf_calib_observe_hw_device.restype, parent.yf_calib_observe_hw_device.argtypes = cl, [vp, ci, ci, vp, cl, vp, vp]
+        parent.yf_calib_simulate_device.restype, parent.yf_calib_simulate_device.argtypes = cl, [vp, vp, cl, vp, vp, vp, vp, vp, vp]
+        parent.yf_calib_simulate_hw_device.restype, parent.yf_calib_simulate_hw_device.argtypes = cl, [vp, ci, ci, vp, cl, vp, vp, vp, vp, vp, vp]
+        parent.yf_calib_destroy.restype, parent.yf_calib_destroy.argtypes = None, [vp]
+        parent.yf_calib_build_id.restype = ctypes.c_char_p
+    shipped_yfm = open(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"), "rb").read()
+    tables = (("all entries disabled", calib.empty_table()), ("all entries enabled", calib.simulation_table(shipped_yfm)))
+    print(f"\n(a) One launch over random frames resident in HBM, {a.launches} launches after {a.warmup} warm-up, HIP events, median (min, max) in ms.")
+    print("    channel sums: per-frame sums, totals and logits written; simulate: logits written, no reference; observe: logits written.")
+    if parent:
+        print(f"    libyf_calib.so of the parent commit: build id {parent.yf_calib_build_id().decode()}, loaded beside this build's, timed in the same run")
+    for h, n in ((56, a.bench_frames), (160, max(a.bench_frames // 4, 1))):
+        hw = h != 56
+        d_x = torch.from_numpy(np.random.default_rng(n + h).integers(-128, 128, (n, h, h, 3), dtype=np.int8)).cuda()
+        cal = calib.Calibration(npz_yfw)
+        d_rows = torch.empty((n, calib.CHANNELS), dtype=torch.float64, device="cuda")
+        d_sums = torch.empty((calib.CHANNELS,), dtype=torch.float64, device="cuda")
+        d_l = torch.empty((n, h // 8, h // 8, 18), dtype=torch.float32, device="cuda")
+        stream, X, L = torch.cuda.current_stream().cuda_stream, d_x.data_ptr(), d_l.data_ptr()
+        ph = parent.yf_calib_create(npz_yfw, len(npz_yfw), 0) if parent else None
+        if parent and not ph:
+            sys.exit("quant_report: yf_calib_create of the parent library failed")
+
+        def chan(t):
+            tail = (X, n, t.ctypes.data, d_rows.data_ptr(), d_sums.data_ptr(), L, stream)
+            rc = lib.yf_calib_channel_sums_hw_device(cal.handle, h, h, *tail) if hw else lib.yf_calib_channel_sums_device(cal.handle, *tail)
+            assert rc == n, cal._text()
+
+        def sim(which, handle, t):
+            tail = (X, n, t.ctypes.data, None, L, None, None, stream)
+            rc = which.yf_calib_simulate_hw_device(handle, h, h, *tail) if hw else which.yf_calib_simulate_device(handle, *tail)
+            assert rc == n
+
+        def obs(which, handle):
+            rc = which.yf_calib_observe_hw_device(handle, h, h, X, n, L, stream) if hw else which.yf_calib_observe_device(handle, X, n, L, stream)
+            assert rc == n
+
+        print(f"\n    {h}x{h}, {n} frames ({'yfc_channel_sums_hw_kernel, the arena in a slab' if hw else 'yfc_channel_sums_kernel, the arena in LDS'})")
+        for name, t in tables:
+            c = timed(torch, lambda: chan(t), a.launches, a.warmup)
+            s = timed(torch, lambda: sim(lib, cal.handle, t), a.launches, a.warmup)
+            print(f"    {name:22s} channel sums {c[0]:8.3f}  ({c[1]:.3f}, {c[2]:.3f})   simulate {s[0]:8.3f}  ({s[1]:.3f}, {s[2]:.3f})   ratio {c[0] / s[0]:.2f}x")
+            if parent:
+                ps = timed(torch, lambda: sim(parent, ph, t), a.launches, a.warmup)
+                print(f"    {'':22s} simulate of the parent commit's library {ps[0]:8.3f}  ({ps[1]:.3f}, {ps[2]:.3f})   this build / parent {s[0] / ps[0]:.3f}")
+        o = timed(torch, lambda: obs(lib, cal.handle), a.launches, a.warmup)
+        print(f"    {'observe':22s} this build {o[0]:8.3f}  ({o[1]:.3f}, {o[2]:.3f})", end="")
+        if parent:
+            po = timed(torch, lambda: obs(parent, ph), a.launches, a.warmup)
+            print(f"   parent commit {po[0]:8.3f}  ({po[1]:.3f}, {po[2]:.3f})   this build / parent {o[0] / po[0]:.3f}", end="")
+            parent.yf_calib_destroy(ph)
+        print()
+        cal.destroy()
+        del d_x, d_rows, d_l
+    print("    Registers, from the code object's metadata (csrc/yf_calib.hip compiled to assembly with the library's flags):")
+    for line in kernel_registers(("channel_sums", "simulate")):
+        print("    " + line)
+
+    # (b) a whole call
+    big = torch.from_numpy(np.random.default_rng(4096).integers(-128, 128, (a.bench_frames, 56, 56, 3), dtype=np.int8)).cuda()
+    cal = calib.Calibration(shipped_yfw)
+    cal.observe(big, logits=False)
+    big_ranges = cal.ranges()
+    cal.destroy()
+    print(f"\n(b) Wall time of one calib.correct_biases call at 56x56 on {a.bench_frames} random frames resident in HBM (the shipped .yfw, min/max ranges of the same frames)")
+    for mode in calib.BIAS_MODES:
+        calib.correct_biases(shipped_yfw, big_ranges, big[:64], mode=mode)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        calib.correct_biases(shipped_yfw, big_ranges, big, mode=mode)
+        torch.cuda.synchronize()
+        print(f"    {mode:10s} {time.perf_counter() - t:.3f} s  ({1 + (24 if mode == 'sequential' else 1)} passes, a handle created and destroyed for each)")
+    del big
+
+    # (c) the effect
+    d_x = torch.from_numpy(x).cuda()
+    first, cout, _ = calib.channel_layout()
+
+    def head_sim(yfw, yfm):
+        """the head's SQNR in the full simulation of yfm against the float logits of yfw"""
+        ref_cal, cal = calib.Calibration(yfw), calib.Calibration(ptq.dequantized_yfw(yfw, yfm))
+        try:
+            ref = ref_cal.simulate(d_x, calib.empty_table())[0]
+            r = cal.simulate(d_x, calib.simulation_table(yfm), ref)[1][0]
+        finally:
+            ref_cal.destroy(); cal.destroy()
+        return 10.0 * math.log10(float(r["sum_sq_ref"]) / float(r["sum_sq_err"])), float(r["sum_err"]) / int(r["elements"])
+
+    def engine(yfw, yfm):
+        net.init_model(yfm)
+        return calib.quantisation_report(net, yfw, yfm, x)
+
+    def head_row(rows):
+        return [r for r in rows if r["tensor"] == 100][0]
+
+    def effect(title, yfw, ranges):
+        print("\n" + title)
+        plain = ptq.quantize_model(yfw, ranges)
+        models = {None: plain}
+        reports = {}
+        for mode in calib.BIAS_MODES:
+            models[mode], reports[mode] = calib.correct_biases(yfw, ranges, d_x, mode=mode)
+        tables = {mode: engine(yfw, m) for mode, m in models.items()}
+        print("    head (tensor 100)          simulation sqnr_db  simulation mean_error   engine sqnr_db  engine mean_error  engine mean sqnr_db over the tensors")
+        for mode in (None,) + calib.BIAS_MODES:
+            s, e = head_sim(yfw, models[mode]), head_row(tables[mode])
+            print(f"    {'uncorrected' if mode is None else mode:26s} {s[0]:18.2f}  {s[1]:+21.6e}   {e['sqnr_db']:14.2f}  {e['mean_error']:+17.6e}  "
+                  f"{float(np.mean([r['sqnr_db'] for r in tables[mode]])):10.2f}")
+        print("    per tensor, the engine against the float evaluation: mean_error uncorrected -> sequential | once, and sqnr_db likewise")
+        for r0, r1, r2 in zip(tables[None], tables["sequential"], tables["once"]):
+            print(f"    tensor {r0['tensor']:3d}  scale {r0['scale']:.6f}  mean_error {r0['mean_error']:+.5f} -> {r1['mean_error']:+.5f} | {r2['mean_error']:+.5f}"
+                  f"   sqnr_db {r0['sqnr_db']:6.2f} -> {r1['sqnr_db']:6.2f} | {r2['sqnr_db']:6.2f}")
+        mode = a.bias_correction
+        print(f"    the report of correct_biases(mode={mode!r}): the largest and rms |mean_sim - mean_float| over a convolution's channels before its correction,")
+        print("    in units of its output's scale")
+        for line in calib.format_bias_report(reports[mode]).split("\n"):
+            print("    " + line)
+        return tables, models
+
+    cal = calib.Calibration(npz_yfw)
+    cal.observe(d_x, logits=False)
+    npz_ranges = cal.ranges()
+    cal.destroy()
+    cal = calib.Calibration(shipped_yfw)
+    cal.observe(d_x, logits=False)
+    observed = cal.ranges()
+    counts = cal.histogram(d_x, observed, a.bins).cpu().numpy()
+    cal.destroy()
+    print(f"\n(c) The effect, over the {x.shape[0]} frames of {os.path.relpath(a.frames, ROOT)} (the frames the ranges and the correction are taken on).  error = dequantised int8 -")
+    print("    float32; simulation: the model's dequantised weights under its whole table against the float logits (float arithmetic on the int8 grid);")
+    print("    engine: calib.quantisation_report, the int8 network that runs.")
+    t1, m1 = effect("(c1) tests/golden/ptq_float_convs.npz (the float weights the shipped model came from), min/max ranges of these frames", npz_yfw, npz_ranges)
+    t2, m2 = effect("(c2) stm32h7-yolo_amd/model/yoloface_fp32.yfw (the shipped .yfw), min/max ranges: quantize_on_device's model", shipped_yfw, observed)
+    assert m2[None] == calib.quantize_on_device(shipped_yfw, d_x) and m2["sequential"] == calib.quantize_on_device(shipped_yfw, d_x, bias_correction="sequential")
+    t3, _ = effect('(c3) the same .yfw on ranges="mse"', shipped_yfw, ptq.clip_ranges(counts, observed, "mse", a.percentile))
+    print(f"\n    the engine's own table of (c2), uncorrected and then with mode={a.bias_correction!r}:")
+    print_table(t2[None])
+    print_table(t2[a.bias_correction])
+    print("\nVERDICT.  Head SQNR on the engine, uncorrected -> sequential | once:")
+    for name, t in (("c1", t1), ("c2", t2), ("c3", t3)):
+        h0, h1, h2 = (head_row(t[m])["sqnr_db"] for m in (None,) + calib.BIAS_MODES)
+        print(f"    {name}: {h0:.2f} dB -> {h1:.2f} dB | {h2:.2f} dB   ({'improves' if h1 > h0 else 'does NOT improve'} under sequential, "
+              f"{'improves' if h2 > h0 else 'does NOT improve'} under once)")
+    print("    These are the frames the ranges and the correction were taken on: no held-out frames are scored here.")
+    print("    `once` measures every convolution's offset with the offsets of the convolutions before it still in its input, and then removes those")
+    print("    as well: the corrections compound.  It is kept for comparison; `sequential` is the mode to use.")
+    net.init_model(shipped_yfm)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--yfw")
@@ -193,6 +395,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ranges", choices=("minmax", "percentile", "mse", "head"), default="minmax")
     ap.add_argument("--sensitivity", action="store_true", help="write the record of profiles/quant_sensitivity.txt instead")
+    ap.add_argument("--bias-correction", choices=("sequential", "once"), help="write the record of profiles/bias_correction.txt instead")
+    ap.add_argument("--parent-lib", help="with --bias-correction: libyf_calib.so built from the parent commit, timed beside this build's")
     ap.add_argument("--percentile", type=float, default=0.9999)
     ap.add_argument("--bins", type=int, default=2048)
     ap.add_argument("--size", type=int, default=56, help="the side of the frames in --frames (56 or 160)")
@@ -225,6 +429,10 @@ def main():
     npz_yfw = model_file.write_yfw([(z[f"w{k}"], z[f"b{k}"], bool(z[f"dw{k}"])) for k in range(24)])
     shipped_yfm = open(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"), "rb").read()
     shipped_yfw = open(os.path.join(ROOT, "stm32h7-yolo_amd", "model", "yoloface_fp32.yfw"), "rb").read()
+    if a.bias_correction:
+        bias_correction_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw)
+        net.destroy()
+        return 0
     if a.sensitivity:
         sensitivity_record(a, torch, calib, model_file, net, x, npz_yfw, shipped_yfw, shipped_yfm)
         net.destroy()
