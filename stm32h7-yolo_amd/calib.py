@@ -130,6 +130,23 @@ def _host_frames(frames, general):
 _lib = None
 _host = None
 
+_vp, _ci, _cl, _cp, _cz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_char_p, ctypes.c_size_t
+# The entries that come as a 56x56 and an _hw form, each signature once: the _hw form has (int h, int w) inserted behind the handle (device),
+# behind the .yfw and its length (host).  Device: what follows the handle; host: what lies between (yfw, bytes) and (threads, err, errlen).
+_DEVICE_ENTRIES = {"observe": [_vp, _cl, _vp, _vp], "compare": [_vp, _cl, ctypes.POINTER(QTensor), _ci, _vp, _vp, _vp],
+                   "histogram": [_vp, _cl, _vp, _ci, _vp, _vp], "simulate": [_vp, _cl, _vp, _vp, _vp, _vp, _vp, _vp],
+                   "channel_sums": [_vp, _cl, _vp, _vp, _vp, _vp, _vp]}
+_HOST_ENTRIES = {"run": [_vp, _cl, _vp, _vp, _vp], "compare": [_vp, _cl, ctypes.POINTER(QTensor), _ci, _vp, _vp, _vp],
+                 "histogram": [_vp, _cl, _vp, _ci, _vp], "simulate": [_vp, _cl, _vp, _vp, _vp, _vp, _vp], "channel_sums": [_vp, _cl, _vp, _vp, _vp, _vp]}
+
+
+def declare_device(lib):
+    """restype and argtypes of the ten evaluating entries of a libyf_calib.so (this build's, or another build's loaded beside it)"""
+    for op, args in _DEVICE_ENTRIES.items():
+        for hw in ("", "_hw"):
+            fn = getattr(lib, f"yf_calib_{op}{hw}_device")
+            fn.restype, fn.argtypes = _cl, [_vp] + ([_ci, _ci] if hw else []) + args
+
 
 def load():
     """dlopen libyf_calib.so after the HIP runtime PyTorch uses (binding._one_hip_runtime: one runtime per process), rebuilding it when its
@@ -140,25 +157,9 @@ def load():
     lib = libs.open_library(lib_path(), library_is_current, [("yf_calib_build_id", expected_build_id)], preload=binding._one_hip_runtime)
     lib.yf_calib_build_id.restype = ctypes.c_char_p
     lib.yf_calib_build_id.argtypes = []
-    vp = ctypes.c_void_p
+    vp, ci = _vp, _ci
     lib.yf_calib_create.restype, lib.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
-    lib.yf_calib_observe_device.restype, lib.yf_calib_observe_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp]
-    lib.yf_calib_compare_device.restype = ctypes.c_long
-    lib.yf_calib_compare_device.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
-    lib.yf_calib_histogram_device.restype = ctypes.c_long
-    lib.yf_calib_histogram_device.argtypes = [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
-    ci = ctypes.c_int
-    lib.yf_calib_observe_hw_device.restype, lib.yf_calib_observe_hw_device.argtypes = ctypes.c_long, [vp, ci, ci, vp, ctypes.c_long, vp, vp]
-    lib.yf_calib_compare_hw_device.restype = ctypes.c_long
-    lib.yf_calib_compare_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp]
-    lib.yf_calib_histogram_hw_device.restype = ctypes.c_long
-    lib.yf_calib_histogram_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp]
-    lib.yf_calib_simulate_device.restype, lib.yf_calib_simulate_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
-    lib.yf_calib_simulate_hw_device.restype = ctypes.c_long
-    lib.yf_calib_simulate_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
-    lib.yf_calib_channel_sums_device.restype, lib.yf_calib_channel_sums_device.argtypes = ctypes.c_long, [vp, vp, ctypes.c_long, vp, vp, vp, vp, vp]
-    lib.yf_calib_channel_sums_hw_device.restype = ctypes.c_long
-    lib.yf_calib_channel_sums_hw_device.argtypes = [vp, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp]
+    declare_device(lib)
     lib.yf_calib_channel_layout.restype, lib.yf_calib_channel_layout.argtypes = ctypes.c_int, [vp, vp, vp]
     lib.yf_calib_workgroups.restype, lib.yf_calib_workgroups.argtypes = ctypes.c_int, [vp, ci, ci]
     lib.yf_calib_scratch_bytes.restype, lib.yf_calib_scratch_bytes.argtypes = ctypes.c_size_t, [vp]
@@ -176,40 +177,29 @@ def load_host():
     global _host
     if _host is None:
         lib = libs.host_library("libyf_calib_host.so")
-        vp = ctypes.c_void_p
-        lib.yf_calib_host_run.restype = ctypes.c_long
-        lib.yf_calib_host_run.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_host_compare.restype = ctypes.c_long
-        lib.yf_calib_host_compare.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp, vp, vp,
-                                              ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_host_histogram.restype = ctypes.c_long
-        lib.yf_calib_host_histogram.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
-                                                ctypes.c_char_p, ctypes.c_size_t]
-        ci = ctypes.c_int
-        lib.yf_calib_host_run_hw.restype = ctypes.c_long
-        lib.yf_calib_host_run_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
-                                             ctypes.c_size_t]
-        lib.yf_calib_host_compare_hw.restype = ctypes.c_long
-        lib.yf_calib_host_compare_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, ctypes.POINTER(QTensor), ctypes.c_int, vp,
-                                                 vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_host_histogram_hw.restype = ctypes.c_long
-        lib.yf_calib_host_histogram_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int,
-                                                   ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_host_simulate.restype = ctypes.c_long
-        lib.yf_calib_host_simulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
-                                               ctypes.c_size_t]
-        lib.yf_calib_host_simulate_hw.restype = ctypes.c_long
-        lib.yf_calib_host_simulate_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, vp, ctypes.c_int,
-                                                  ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_host_channel_sums.restype = ctypes.c_long
-        lib.yf_calib_host_channel_sums.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_long, vp, vp, vp, vp, ctypes.c_int, ctypes.c_char_p,
-                                                   ctypes.c_size_t]
-        lib.yf_calib_host_channel_sums_hw.restype = ctypes.c_long
-        lib.yf_calib_host_channel_sums_hw.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci, ci, vp, ctypes.c_long, vp, vp, vp, vp, ctypes.c_int,
-                                                      ctypes.c_char_p, ctypes.c_size_t]
-        lib.yf_calib_channel_layout.restype, lib.yf_calib_channel_layout.argtypes = ctypes.c_int, [vp, vp, vp]
+        for op, args in _HOST_ENTRIES.items():
+            for hw in ("", "_hw"):
+                fn = getattr(lib, f"yf_calib_host_{op}{hw}")
+                fn.restype, fn.argtypes = _cl, [_cp, _cz] + ([_ci, _ci] if hw else []) + args + [_ci, _cp, _cz]
+        lib.yf_calib_channel_layout.restype, lib.yf_calib_channel_layout.argtypes = ctypes.c_int, [_vp, _vp, _vp]
         _host = lib
     return _host
+
+
+def _entry(lib, stem, suffix, hw, h, w, head, tail):
+    """One call of an entry that has two forms, `stem + suffix` (56x56) or `stem + "_hw" + suffix` with (h, w) behind `head` -> (what it
+    returned, the name of the entry called: what an error text starts with)"""
+    name = f"{stem}{'_hw' if hw else ''}{suffix}"
+    return getattr(lib, name)(*head, *((h, w) if hw else ()), *tail), name
+
+
+def _host_call(op, yfw_bytes, x, h, w, hw, args, threads):
+    """yf_calib_host_<op>, or with hw its _hw form, over the frames x [n, h, w, 3].  A refusal, or no frame at all, raises CalibError with the
+    library's text."""
+    n, err = x.shape[0], ctypes.create_string_buffer(400)
+    rc, _ = _entry(load_host(), f"yf_calib_host_{op}", "", hw, h, w, (bytes(yfw_bytes), len(yfw_bytes)), (x.ctypes.data, n, *args, int(threads), err, 400))
+    if rc != n or n < 1:
+        raise CalibError(f"yf_calib_host_{op}: {err.value.decode()} (returned {rc}, expected {n})")
 
 
 def _address(q):
@@ -235,7 +225,6 @@ def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elem
     array [n, count]; totals, a TOTALS array [count]; and, with want_tensors, the float32 tensors of the listed entries, one [n, elements]
     array per entry -- `elements` then gives each entry's element count at this frame size).  A refused argument raises CalibError with the
     library's text."""
-    lib = load_host()
     x, h, w, hw = _host_frames(frames, general)
     n, count = x.shape[0], len(entries)
     stats, totals = np.zeros((n, max(count, 1)), FRAME_STATS), np.zeros(max(count, 1), TOTALS)
@@ -244,15 +233,8 @@ def host_compare(yfw_bytes, frames, entries, threads=1, want_tensors=False, elem
         if elements is None or len(elements) != count:
             raise ValueError("want_tensors: `elements` must give every entry's element count")
         flat = np.zeros(n * int(sum(elements)), np.float32)
-    err = ctypes.create_string_buffer(400)
-    tail = (x.ctypes.data, n, _qtensors(entries), count, stats.ctypes.data, totals.ctypes.data, flat.ctypes.data if want_tensors else None,
-            int(threads), err, 400)
-    if hw:
-        rc = lib.yf_calib_host_compare_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
-    else:
-        rc = lib.yf_calib_host_compare(bytes(yfw_bytes), len(yfw_bytes), *tail)
-    if rc != n or n < 1:
-        raise CalibError(f"yf_calib_host_compare: {err.value.decode()} (returned {rc}, expected {n})")
+    _host_call("compare", yfw_bytes, x, h, w, hw, (_qtensors(entries), count, stats.ctypes.data, totals.ctypes.data,
+                                               flat.ctypes.data if want_tensors else None), threads)
     stats, totals = stats[:, :count], totals[:count]
     if not want_tensors:
         return stats, totals
@@ -304,7 +286,6 @@ def host_simulate(yfw_bytes, frames, table, ref_logits=None, threads=1, general=
     [n, h / 8, w / 8, 18] -> (float32 logits, totals: a TOTALS array [1] of the head's error against ref_logits, or None without them); with
     want_stats also the per-frame records, a FRAME_STATS array [n] (None without ref_logits).  A refused argument raises CalibError with the
     library's text."""
-    lib = load_host()
     x, h, w, hw = _host_frames(frames, general)
     n, t = x.shape[0], _table(table)
     logits = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32)
@@ -314,15 +295,8 @@ def host_simulate(yfw_bytes, frames, table, ref_logits=None, threads=1, general=
         if ref.size != logits.size:
             raise ValueError(f"ref_logits: {ref.shape}, expected {logits.shape}")
         stats, totals = np.zeros(max(n, 1), FRAME_STATS), np.zeros(1, TOTALS)
-    err = ctypes.create_string_buffer(400)
-    tail = (x.ctypes.data, n, None if t is None else t.ctypes.data, None if ref is None else ref.ctypes.data, logits.ctypes.data,
-            None if stats is None else stats.ctypes.data, None if totals is None else totals.ctypes.data, int(threads), err, 400)
-    if hw:
-        rc = lib.yf_calib_host_simulate_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
-    else:
-        rc = lib.yf_calib_host_simulate(bytes(yfw_bytes), len(yfw_bytes), *tail)
-    if rc != n or n < 1:
-        raise CalibError(f"yf_calib_host_simulate: {err.value.decode()} (returned {rc}, expected {n})")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _host_call("simulate", yfw_bytes, x, h, w, hw, (ptr(t), ptr(ref), logits.ctypes.data, ptr(stats), ptr(totals)), threads)
     return (logits, totals, None if stats is None else stats[:n]) if want_stats else (logits, totals)
 
 
@@ -348,19 +322,11 @@ def host_channel_sums(yfw_bytes, frames, table=None, threads=1, general=False, w
     """The channel sums on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) and a table (simulation_table; None: every entry disabled, the float
     evaluation) -> float64 [544], the sums over all frames; with want_frames (sums, the per-frame sums float64 [n, 544]); with logits the
     float32 logits [n, h / 8, w / 8, 18] as the last item.  A refused argument raises CalibError with the library's text."""
-    lib = load_host()
     x, h, w, hw = _host_frames(frames, general)
     n, t = x.shape[0], _table(empty_table() if table is None else table)
     rows, sums = np.zeros((max(n, 1), CHANNELS), np.float64), np.zeros(CHANNELS, np.float64)
     lg = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32) if logits else None
-    err = ctypes.create_string_buffer(400)
-    tail = (x.ctypes.data, n, t.ctypes.data, rows.ctypes.data, sums.ctypes.data, lg.ctypes.data if logits else None, int(threads), err, 400)
-    if hw:
-        rc = lib.yf_calib_host_channel_sums_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
-    else:
-        rc = lib.yf_calib_host_channel_sums(bytes(yfw_bytes), len(yfw_bytes), *tail)
-    if rc != n or n < 1:
-        raise CalibError(f"yf_calib_host_channel_sums: {err.value.decode()} (returned {rc}, expected {n})")
+    _host_call("channel_sums", yfw_bytes, x, h, w, hw, (t.ctypes.data, rows.ctypes.data, sums.ctypes.data, lg.ctypes.data if logits else None), threads)
     out = (sums,) + ((rows[:n],) if want_frames else ()) + ((lg,) if logits else ())
     return out[0] if len(out) == 1 else out
 
@@ -372,19 +338,11 @@ def _ranges_dict(minmax, ids):
 def host_run(yfw_bytes, frames, threads=1, want_logits=True, general=False):
     """The evaluation on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) -> ({tensor id: (min, max)} of these frames, float32 logits
     [n, h / 8, w / 8, 18] or None).  A refused .yfw or frame size raises CalibError with the library's text."""
-    lib = load_host()
     x, h, w, hw = _host_frames(frames, general)
     n = x.shape[0]
     minmax, ids = np.zeros((N_RANGES, 2), np.float32), np.zeros(N_RANGES, np.int32)
     logits = np.zeros((n, max(h // 8, 0), max(w // 8, 0), 18), np.float32) if want_logits else None
-    err = ctypes.create_string_buffer(400)
-    tail = (x.ctypes.data, n, minmax.ctypes.data, ids.ctypes.data, logits.ctypes.data if want_logits else None, int(threads), err, 400)
-    if hw:
-        rc = lib.yf_calib_host_run_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
-    else:
-        rc = lib.yf_calib_host_run(bytes(yfw_bytes), len(yfw_bytes), *tail)
-    if rc != n:
-        raise CalibError(f"yf_calib_host_run: {err.value.decode()} (returned {rc}, expected {n})")
+    _host_call("run", yfw_bytes, x, h, w, hw, (minmax.ctypes.data, ids.ctypes.data, logits.ctypes.data if want_logits else None), threads)
     return _ranges_dict(minmax, ids), logits
 
 
@@ -401,21 +359,13 @@ def host_histogram(yfw_bytes, frames, ranges, bins=2048, threads=1, counts=None,
     """The histograms on the CPU: int8 frames [n, h, w, 3] (flat: 56x56) and the ranges {tensor id: (min, max)} that give every tensor its axis -> a
     uint64 array [47, bins], rows in the order of sorted(ranges).  `counts` (such an array) is added to and returned.  A refused argument
     raises CalibError with the library's text."""
-    lib = load_host()
     x, h, w, hw = _host_frames(frames, general)
-    n, minmax = x.shape[0], _minmax_array(ranges)
+    minmax = _minmax_array(ranges)
     if counts is None:
         counts = np.zeros((N_RANGES, max(int(bins), 1)), np.uint64)
     elif counts.dtype != np.uint64 or counts.shape != (N_RANGES, bins) or not counts.flags.c_contiguous:
         raise ValueError(f"counts: expected a contiguous uint64 array [{N_RANGES}, {bins}]")
-    err = ctypes.create_string_buffer(400)
-    tail = (x.ctypes.data, n, minmax.ctypes.data, int(bins), counts.ctypes.data, int(threads), err, 400)
-    if hw:
-        rc = lib.yf_calib_host_histogram_hw(bytes(yfw_bytes), len(yfw_bytes), h, w, *tail)
-    else:
-        rc = lib.yf_calib_host_histogram(bytes(yfw_bytes), len(yfw_bytes), *tail)
-    if rc != n or n < 1:
-        raise CalibError(f"yf_calib_host_histogram: {err.value.decode()} (returned {rc}, expected {n})")
+    _host_call("histogram", yfw_bytes, x, h, w, hw, (minmax.ctypes.data, int(bins), counts.ctypes.data), threads)
     return counts
 
 
@@ -462,6 +412,10 @@ class Calibration:
         frames = frames.to(torch.device("cuda", self.device)).contiguous()
         return frames, (frames.shape[0] if shaped else frames.numel() // FRAME_BYTES), h, w, hw
 
+    def _call(self, op, hw, h, w, tail):
+        """yf_calib_<op>_device, or with hw yf_calib_<op>_hw_device at (h, w) -> (what it returned, the entry's name)"""
+        return _entry(self._lib, f"yf_calib_{op}", "_device", hw, h, w, (self.handle,), tail)
+
     def workgroups(self, h, w):
         """The workgroups a general launch at (h, w) uses, which is the number of scratch slabs of 800 * (h / 8) * (w / 8) floats each."""
         k = self._lib.yf_calib_workgroups(self.handle, int(h), int(w))
@@ -479,12 +433,9 @@ class Calibration:
         dev = frames.device
         out = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device=dev) if logits else None
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        if hw:
-            rc = self._lib.yf_calib_observe_hw_device(self.handle, h, w, frames.data_ptr(), n, out.data_ptr() if logits else None, s)
-        else:
-            rc = self._lib.yf_calib_observe_device(self.handle, frames.data_ptr(), n, out.data_ptr() if logits else None, s)
+        rc, name = self._call("observe", hw, h, w, (frames.data_ptr(), n, out.data_ptr() if logits else None, s))
         if rc != n:
-            raise CalibError(f"yf_calib_observe{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"{name}: {self._text()} (returned {rc}, expected {n})")
         self._keep, self.logits = frames, out       # the launch is asynchronous: the frames stay alive until the next call
         return n
 
@@ -502,9 +453,9 @@ class Calibration:
         if stream is not None:
             torch.cuda.synchronize(dev)                                              # the zeroed outputs were made on torch's stream
         tail = (frames.data_ptr() if n else None, n, _qtensors(entries), count, d_stats.data_ptr(), d_totals.data_ptr(), s)
-        rc = self._lib.yf_calib_compare_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_compare_device(self.handle, *tail)
+        rc, name = self._call("compare", hw, h, w, tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_compare{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"{name}: {self._text()} (returned {rc}, expected {n})")
         torch.cuda.synchronize(dev)                                                  # frames and the entries' tensors are no longer read
         return d_stats[:, :count], d_totals[:count].cpu().numpy().view(TOTALS).reshape(count)
 
@@ -528,9 +479,9 @@ class Calibration:
         if s != current.cuda_stream:                                                 # frames and counts were made ready on torch's stream
             torch.cuda.ExternalStream(s, device=dev).wait_event(current.record_event())
         tail = (frames.data_ptr() if n else None, n, minmax.ctypes.data, int(bins), counts.data_ptr(), s)
-        rc = self._lib.yf_calib_histogram_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_histogram_device(self.handle, *tail)
+        rc, name = self._call("histogram", hw, h, w, tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_histogram{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"{name}: {self._text()} (returned {rc}, expected {n})")
         self._keep_hist = frames                    # the launch is asynchronous: the frames stay alive until the next call
         return counts
 
@@ -559,9 +510,9 @@ class Calibration:
         ptr = lambda v: None if v is None else v.data_ptr()
         tail = (frames.data_ptr() if n else None, n, None if t is None else t.ctypes.data, ptr(ref), out.data_ptr() if n else None, ptr(d_stats),
                 ptr(d_totals), s)
-        rc = self._lib.yf_calib_simulate_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_simulate_device(self.handle, *tail)
+        rc, name = self._call("simulate", hw, h, w, tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_simulate{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"{name}: {self._text()} (returned {rc}, expected {n})")
         torch.cuda.synchronize(dev)                                                  # frames and ref_logits are no longer read
         totals = None if ref is None else d_totals.cpu().numpy().view(TOTALS).reshape(1)
         return (out, totals, None if ref is None else d_stats[:n]) if want_stats else (out, totals)
@@ -583,9 +534,9 @@ class Calibration:
         if stream is not None:
             torch.cuda.synchronize(dev)                                              # the upload was made on torch's stream
         tail = (frames.data_ptr() if n else None, n, t.ctypes.data, d_rows.data_ptr(), d_sums.data_ptr(), out.data_ptr() if logits and n else None, s)
-        rc = self._lib.yf_calib_channel_sums_hw_device(self.handle, h, w, *tail) if hw else self._lib.yf_calib_channel_sums_device(self.handle, *tail)
+        rc, name = self._call("channel_sums", hw, h, w, tail)
         if rc != n or n < 1:
-            raise CalibError(f"yf_calib_channel_sums{'_hw' if hw else ''}_device: {self._text()} (returned {rc}, expected {n})")
+            raise CalibError(f"{name}: {self._text()} (returned {rc}, expected {n})")
         torch.cuda.synchronize(dev)                                                  # frames are no longer read
         res = (d_sums.cpu().numpy(),) + ((d_rows[:n],) if want_frames else ()) + ((out,) if logits else ())
         return res[0] if len(res) == 1 else res

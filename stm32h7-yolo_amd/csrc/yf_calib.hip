@@ -20,18 +20,22 @@
 // stage the workgroup adds its non-empty bins to the caller's uint64 counts with vector atomics on consecutive addresses.  Integer sums are exact, so
 // this is the one place where an atomic has no numerical meaning.  The axes and the windows travel as a kernel argument.
 //
-// The general forms (the _hw entries: frames of h x w, multiples of 8 up to 160) are the same three loops over the same yfc_stage_element with
-// the arena in global memory: a slab of 800 * (h / 8) * (w / 8) floats per workgroup in flight, owned by the handle (1.28 MB at 160x160, which
-// no LDS holds).  Still one workgroup per frame, a grid-stride loop over the frames and the round-robin deal of a stage's elements -- the deal
-// is part of the comparing form's summation order.  The barrier that ends a stage is what hands the slab from the threads that wrote it to
-// the threads that read it: the waves of a workgroup run on one CU and share its vector L1, and __syncthreads() orders global memory at
-// workgroup scope (every wave's stores are waited for before the barrier); nothing here needs an agent-scope fence, because no other
-// workgroup ever reads a slab during a launch.  LDS holds the reduction scratch only, and in the histogram form the stage's tables at a
-// fixed place (3 x 4096 x 4 B): there is no dead arena to borrow.  The LDS no longer limits a CU to one workgroup, so the grid comes from an
-// occupancy query at yf_calib_create, not from the CU count alone (as compiled now the kernels' registers still allow one 16-wave workgroup
-// per CU: profiles/calib160.txt).  Every size's stage table is uploaded once at creation (400 sizes, 1 MB): a launch
-// refers to nothing a later call rewrites.  The launches of one handle share its slabs, so each waits for the event recorded behind the one
-// before it, whichever stream that went to.
+// The general forms (the _hw entries: frames of h x w, multiples of 8 up to 160) are the same bodies with the arena in another place.  Every
+// form's loop over frames and stages exists once, as a __forceinline__ function (observe_frames, compare_frames, histogram_frames,
+// simulate_frames, channel_sum_frames) of the arena pointer, the LDS scratch and the arena's sizes, and the form's two kernels only say
+// where these are: the LDS kernel passes the dynamic LDS and the 56x56 sizes as constants, the slab kernel a slab of global memory -- 800 *
+// (h / 8) * (w / 8) floats per workgroup in flight, owned by the handle (1.28 MB at 160x160, which no LDS holds) --, static LDS for the
+// scratch and the sizes of `dims`.  So both have one workgroup per frame, a grid-stride loop over the frames and the round-robin deal of a
+// stage's elements -- the deal is part of the comparing form's summation order.  The barrier that ends a stage is what hands the slab from
+// the threads that wrote it to the threads that read it: the waves of a workgroup run on one CU and share its vector L1, and __syncthreads()
+// orders global memory at workgroup scope (every wave's stores are waited for before the barrier); nothing here needs an agent-scope fence,
+// because no other workgroup ever reads a slab during a launch.  In the slab kernels LDS holds the reduction scratch only, and in the
+// histogram form the stage's tables at a fixed place (3 x 4096 x 4 B): there is no dead arena to borrow.  The LDS no longer limits a CU to
+// one workgroup, so the grid comes from an occupancy query at yf_calib_create, not from the CU count alone (as compiled now the kernels'
+// registers still allow one 16-wave workgroup per CU: profiles/calib160.txt).  Every size's stage table is uploaded once at creation (400
+// sizes, 1 MB): a launch refers to nothing a later call rewrites.  The launches of one handle share its slabs, so each waits for the event
+// recorded behind the one before it, whichever stream that went to.  On the host side each operation is one function too (observe, compare,
+// ... below) behind its two entries, and `Evaluation` holds what all of them do around the launch.
 //
 // The simulating form (yf_calib_simulate_device and its _hw form, csrc/yf_calib_sim.h) is the same stage loop over yfc_stage_element_sim, which
 // puts the tensors of the enabled entries on their int8 grids; the derived table travels as a kernel argument.  With reference logits every
@@ -114,13 +118,11 @@ __device__ inline void fold(const float mn[3], const float mx[3], const int slot
   parity ^= 1;
 }
 
-__global__ __launch_bounds__(kThreads) void yfc_observe_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
-                                                                const yfc_stage* __restrict__ stages, float* __restrict__ logits,
-                                                                float* __restrict__ partials) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* arena = lds;
-  float* red = lds + YFC_ARENA_FLOATS;
-  float* wg = red + kRedFloats;
+// The observing form's body: `arena` is the LDS arena or this workgroup's slab; red (kRedFloats floats) and wg (kWgFloats floats) are LDS;
+// frame_bytes, n_logits and logits_off describe the arena.
+__device__ __forceinline__ void observe_frames(float* arena, float* red, float* wg, const int frame_bytes, const int n_logits, const int logits_off,
+                                               const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                               const yfc_stage* __restrict__ stages, float* __restrict__ logits, float* __restrict__ partials) {
   const int tid = threadIdx.x;
   const float inf = __builtin_inff();
   if (tid < kWgFloats) wg[tid] = (tid & 1) ? -inf : inf;
@@ -128,10 +130,10 @@ __global__ __launch_bounds__(kThreads) void yfc_observe_kernel(const int8_t* __r
   int parity = 0;
   for (long f = blockIdx.x; f < n; f += gridDim.x) {
     {
-      const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
+      const int8_t* q = frames + (size_t)f * (size_t)frame_bytes;
       float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
       const int slots[3] = {0, -1, -1};
-      for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) {
+      for (int i = tid; i < frame_bytes; i += kThreads) {
         const float v = params[(int)q[i] + 128];
         arena[i] = v;
         mn[0] = v < mn[0] ? v : mn[0];
@@ -153,14 +155,31 @@ __global__ __launch_bounds__(kThreads) void yfc_observe_kernel(const int8_t* __r
           mx[j] = v[j] > mx[j] ? v[j] : mx[j];
         }
       }
-      fold(mn, mx, slots, red, wg, parity);
+      fold(mn, mx, slots, red, wg, parity);                                           // (its barrier: the stage's output is in the arena)
     }
     // (the logits stay where they are until the next frame's third stage writes T54 over them, several barriers from here)
     if (logits)
-      for (int i = tid; i < YFC_LOGITS; i += kThreads) logits[(size_t)f * YFC_LOGITS + i] = arena[YFC_LOGITS_OFF + i];
+      for (int i = tid; i < n_logits; i += kThreads) logits[(size_t)f * (size_t)n_logits + i] = arena[logits_off + i];
   }
   __syncthreads();
   if (tid < kWgFloats) partials[(size_t)blockIdx.x * kWgFloats + tid] = wg[tid];
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_observe_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                const yfc_stage* __restrict__ stages, float* __restrict__ logits,
+                                                                float* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* red = lds + YFC_ARENA_FLOATS;
+  observe_frames(lds, red, red + kRedFloats, YFC_FRAME_BYTES, YFC_LOGITS, YFC_LOGITS_OFF, frames, n, params, stages, logits, partials);
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_observe_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                   float* __restrict__ logits, float* __restrict__ partials) {
+  __shared__ float red[kRedFloats];
+  __shared__ float wg[kWgFloats];
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  observe_frames(arena, red, wg, dims.frame_bytes, dims.logits, dims.logits_off, frames, n, params, stages, logits, partials);
 }
 
 // ranges[t] = min / max (even / odd t) of ranges[t] and partials[0 .. parts)[t]
@@ -210,17 +229,15 @@ __device__ inline void compare_fold(const yfc_cmp_frame acc[3], const int entrie
   parity ^= 1;
 }
 
-__global__ __launch_bounds__(kThreads) void yfc_compare_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
-                                                                const yfc_stage* __restrict__ stages, const yfc_cmp_plan plan,
-                                                                yfc_cmp_frame* __restrict__ frame_stats) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* arena = lds;
-  yfc_cmp_frame* red = reinterpret_cast<yfc_cmp_frame*>(lds + YFC_ARENA_FLOATS);
+// ... and the comparing form's.  red: kCmpRecords records (LDS)
+__device__ __forceinline__ void compare_frames(float* arena, yfc_cmp_frame* red, const int frame_bytes, const int8_t* __restrict__ frames, long n,
+                                               const float* __restrict__ params, const yfc_stage* __restrict__ stages, const yfc_cmp_plan& plan,
+                                               yfc_cmp_frame* __restrict__ frame_stats) {
   const int tid = threadIdx.x;
   int parity = 0;
   for (long f = blockIdx.x; f < n; f += gridDim.x) {
-    const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
-    for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) arena[i] = params[(int)q[i] + 128];
+    const int8_t* q = frames + (size_t)f * (size_t)frame_bytes;
+    for (int i = tid; i < frame_bytes; i += kThreads) arena[i] = params[(int)q[i] + 128];
     __syncthreads();
     for (int s = 0; s < YFC_N_STAGES; ++s) {
       const yfc_stage* g = &stages[s];
@@ -248,6 +265,21 @@ __global__ __launch_bounds__(kThreads) void yfc_compare_kernel(const int8_t* __r
       compare_fold(acc, entries, red, frame_stats + (size_t)f * plan.count, parity);
     }
   }
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_compare_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                const yfc_stage* __restrict__ stages, const yfc_cmp_plan plan,
+                                                                yfc_cmp_frame* __restrict__ frame_stats) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  compare_frames(lds, reinterpret_cast<yfc_cmp_frame*>(lds + YFC_ARENA_FLOATS), YFC_FRAME_BYTES, frames, n, params, stages, plan, frame_stats);
+}
+
+__global__ __launch_bounds__(kThreads) void yfc_compare_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
+                                                                   const yfc_cmp_plan plan, yfc_cmp_frame* __restrict__ frame_stats) {
+  __shared__ yfc_cmp_frame red[kCmpRecords];
+  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
+  compare_frames(arena, red, dims.frame_bytes, frames, n, params, stages, plan, frame_stats);
 }
 
 // totals[entry] = the frames' records added in ascending frame order: one thread per entry and field
@@ -312,20 +344,22 @@ __device__ inline void hist_flush(const uint32_t* table, const int slots[3], int
   __syncthreads();                                                                  // the next step may write where the tables were
 }
 
-__global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
-                                                                  const yfc_stage* __restrict__ stages, const yfc_hist_plan plan,
-                                                                  unsigned long long* __restrict__ counts) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* arena = lds;
-  const int tid = threadIdx.x, bins = plan.bins;
+// ... and the histogram form's.  tables: the LDS the steps' tables are placed in, uint32 counts; off: where each step's tables start in it (the input's step, then every
+// stage), or nullptr for "at `tables`, every step" -- a constant at the call, so that the choice is made when the body is inlined.  The tables
+// are reached as `tables` plus an offset, never through a pointer kept per tensor: the adds stay LDS instructions.
+__device__ __forceinline__ void histogram_frames(float* arena, uint32_t* tables, const int32_t* off, const int frame_bytes,
+                                                 const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                 const yfc_stage* __restrict__ stages, const yfc_hist_axes& axes, const int bins,
+                                                 unsigned long long* __restrict__ counts) {
+  const int tid = threadIdx.x;
   for (long f = blockIdx.x; f < n; f += gridDim.x) {
     {
-      const int8_t* q = frames + (size_t)f * YFC_FRAME_BYTES;
-      uint32_t* table = reinterpret_cast<uint32_t*>(arena + plan.off[0]);
+      const int8_t* q = frames + (size_t)f * (size_t)frame_bytes;
+      uint32_t* table = off ? tables + off[0] : tables;
       const int slots[3] = {0, -1, -1};
-      const float lo = plan.axes.lo[0], inv = plan.axes.inv[0];
+      const float lo = axes.lo[0], inv = axes.inv[0];
       hist_clear(table, bins);
-      for (int i = tid; i < YFC_FRAME_BYTES; i += kThreads) {
+      for (int i = tid; i < frame_bytes; i += kThreads) {
         const float v = params[(int)q[i] + 128];
         arena[i] = v;
         hist_add(table, yfc_hist_bin(v, lo, inv, bins));
@@ -336,19 +370,19 @@ __global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* _
       const yfc_stage* g = &stages[s];
       const int count = g->oh * g->ow * g->cout;
       const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
-      uint32_t* table = reinterpret_cast<uint32_t*>(arena + plan.off[s + 1]);
-      int tab[3] = {0, 0, 0};                                                       // (offsets, not pointers: the adds stay LDS instructions)
+      uint32_t* table = off ? tables + off[s + 1] : tables;
+      int tab[3] = {0, 0, 0};
       float lo[3] = {0.0f, 0.0f, 0.0f}, inv[3] = {0.0f, 0.0f, 0.0f};
-      int tables = 0;
+      int n_tables = 0;
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         if (slots[j] < 0) continue;
-        tab[j] = tables * bins;
-        lo[j] = plan.axes.lo[slots[j]];
-        inv[j] = plan.axes.inv[slots[j]];
-        ++tables;
+        tab[j] = n_tables * bins;
+        lo[j] = axes.lo[slots[j]];
+        inv[j] = axes.inv[slots[j]];
+        ++n_tables;
       }
-      hist_clear(table, tables * bins);
+      hist_clear(table, n_tables * bins);
       for (int idx = tid; idx < count; idx += kThreads) {
         float v[3] = {0.0f, 0.0f, 0.0f};
         yfc_stage_element(g, arena, params, idx, v);
@@ -356,149 +390,32 @@ __global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* _
         for (int j = 0; j < 3; ++j)
           if (slots[j] >= 0) hist_add(table, tab[j] + yfc_hist_bin(v[j], lo[j], inv[j], bins));
       }
-      hist_flush(table, slots, bins, counts);
+      hist_flush(table, slots, bins, counts);                                         // (its first barrier: the stage's output is in the arena)
     }
   }
 }
 
-// ---- the general forms: the arena is this workgroup's slab of global memory, the sizes come from `dims` ----
-__global__ __launch_bounds__(kThreads) void yfc_observe_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
-                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
-                                                                   float* __restrict__ logits, float* __restrict__ partials) {
-  __shared__ float red[kRedFloats];
-  __shared__ float wg[kWgFloats];
-  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
-  const int tid = threadIdx.x;
-  const float inf = __builtin_inff();
-  if (tid < kWgFloats) wg[tid] = (tid & 1) ? -inf : inf;
-  __syncthreads();
-  int parity = 0;
-  for (long f = blockIdx.x; f < n; f += gridDim.x) {
-    {
-      const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
-      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-      const int slots[3] = {0, -1, -1};
-      for (int i = tid; i < dims.frame_bytes; i += kThreads) {
-        const float v = params[(int)q[i] + 128];
-        arena[i] = v;
-        mn[0] = v < mn[0] ? v : mn[0];
-        mx[0] = v > mx[0] ? v : mx[0];
-      }
-      fold(mn, mx, slots, red, wg, parity);
-    }
-    for (int s = 0; s < YFC_N_STAGES; ++s) {
-      const yfc_stage* g = &stages[s];
-      const int count = g->oh * g->ow * g->cout;
-      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
-      float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-      for (int idx = tid; idx < count; idx += kThreads) {
-        float v[3] = {0.0f, 0.0f, 0.0f};
-        yfc_stage_element(g, arena, params, idx, v);
-        for (int j = 0; j < 3; ++j) {
-          if (slots[j] < 0) continue;
-          mn[j] = v[j] < mn[j] ? v[j] : mn[j];
-          mx[j] = v[j] > mx[j] ? v[j] : mx[j];
-        }
-      }
-      fold(mn, mx, slots, red, wg, parity);                                           // (its barrier: the stage's output is in the slab)
-    }
-    // (the logits stay where they are until the next frame's third stage writes T54 over them, several barriers from here)
-    if (logits)
-      for (int i = tid; i < dims.logits; i += kThreads) logits[(size_t)f * (size_t)dims.logits + i] = arena[dims.logits_off + i];
-  }
-  __syncthreads();
-  if (tid < kWgFloats) partials[(size_t)blockIdx.x * kWgFloats + tid] = wg[tid];
+// the tables in the run of the arena that is dead during the step (plan.off, in arena floats: a count is as wide as a float)
+__global__ __launch_bounds__(kThreads) void yfc_histogram_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
+                                                                  const yfc_stage* __restrict__ stages, const yfc_hist_plan plan,
+                                                                  unsigned long long* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  histogram_frames(lds, reinterpret_cast<uint32_t*>(lds), plan.off, YFC_FRAME_BYTES, frames, n, params, stages, plan.axes, plan.bins, counts);
 }
 
-__global__ __launch_bounds__(kThreads) void yfc_compare_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
-                                                                   const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
-                                                                   const yfc_cmp_plan plan, yfc_cmp_frame* __restrict__ frame_stats) {
-  __shared__ yfc_cmp_frame red[kCmpRecords];
-  float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
-  const int tid = threadIdx.x;
-  int parity = 0;
-  for (long f = blockIdx.x; f < n; f += gridDim.x) {
-    const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
-    for (int i = tid; i < dims.frame_bytes; i += kThreads) arena[i] = params[(int)q[i] + 128];
-    __syncthreads();
-    for (int s = 0; s < YFC_N_STAGES; ++s) {
-      const yfc_stage* g = &stages[s];
-      const int count = g->oh * g->ow * g->cout;
-      const int entries[3] = {plan.entry[s][0], plan.entry[s][1], plan.entry[s][2]};
-      const int8_t* qt[3] = {nullptr, nullptr, nullptr};
-      float scale[3] = {0.0f, 0.0f, 0.0f};
-      int zp[3] = {0, 0, 0};
-      yfc_cmp_frame acc[3];                                                         // (per frame and stage: every frame starts from +0)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        yfc_cmp_zero(&acc[j]);
-        if (entries[j] < 0) continue;
-        qt[j] = plan.q[entries[j]] + (size_t)f * plan.frame_stride[entries[j]];
-        scale[j] = plan.scale[entries[j]];
-        zp[j] = plan.zero_point[entries[j]];
-      }
-      for (int idx = tid; idx < count; idx += kThreads) {
-        float v[3] = {0.0f, 0.0f, 0.0f};
-        yfc_stage_element(g, arena, params, idx, v);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (entries[j] >= 0) yfc_cmp_add(&acc[j], qt[j][idx], zp[j], scale[j], v[j]);
-      }
-      compare_fold(acc, entries, red, frame_stats + (size_t)f * plan.count, parity);
-    }
-  }
-}
-
-struct yfc_hist_hw_plan {
+struct yfc_hist_hw_plan {                                                             // (the LDS form's plan without the offsets)
   yfc_hist_axes axes;
   int32_t bins;
+  yfc_hist_hw_plan(const yfc_hist_plan& p) : axes(p.axes), bins(p.bins) {}
 };
 
+// the tables at a fixed place: a slab leaves no dead arena to borrow
 __global__ __launch_bounds__(kThreads) void yfc_histogram_hw_kernel(const int8_t* __restrict__ frames, long n, const float* __restrict__ params,
                                                                      const yfc_stage* __restrict__ stages, const yfc_dims dims, float* slabs,
                                                                      const yfc_hist_hw_plan plan, unsigned long long* __restrict__ counts) {
   __shared__ uint32_t table[3 * YFC_HIST_MAX_BINS];                                   // a stage has up to three tensors
   float* arena = slabs + (size_t)blockIdx.x * (size_t)dims.arena_floats;
-  const int tid = threadIdx.x, bins = plan.bins;
-  for (long f = blockIdx.x; f < n; f += gridDim.x) {
-    {
-      const int8_t* q = frames + (size_t)f * (size_t)dims.frame_bytes;
-      const int slots[3] = {0, -1, -1};
-      const float lo = plan.axes.lo[0], inv = plan.axes.inv[0];
-      hist_clear(table, bins);
-      for (int i = tid; i < dims.frame_bytes; i += kThreads) {
-        const float v = params[(int)q[i] + 128];
-        arena[i] = v;
-        hist_add(table, yfc_hist_bin(v, lo, inv, bins));
-      }
-      hist_flush(table, slots, bins, counts);
-    }
-    for (int s = 0; s < YFC_N_STAGES; ++s) {
-      const yfc_stage* g = &stages[s];
-      const int count = g->oh * g->ow * g->cout;
-      const int slots[3] = {g->r_conv, g->r_leaky, g->r_add};
-      int tab[3] = {0, 0, 0};
-      float lo[3] = {0.0f, 0.0f, 0.0f}, inv[3] = {0.0f, 0.0f, 0.0f};
-      int tables = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        if (slots[j] < 0) continue;
-        tab[j] = tables * bins;
-        lo[j] = plan.axes.lo[slots[j]];
-        inv[j] = plan.axes.inv[slots[j]];
-        ++tables;
-      }
-      hist_clear(table, tables * bins);
-      for (int idx = tid; idx < count; idx += kThreads) {
-        float v[3] = {0.0f, 0.0f, 0.0f};
-        yfc_stage_element(g, arena, params, idx, v);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (slots[j] >= 0) hist_add(table, tab[j] + yfc_hist_bin(v[j], lo[j], inv[j], bins));
-      }
-      hist_flush(table, slots, bins, counts);                                         // (its first barrier: the stage's output is in the slab)
-    }
-  }
+  histogram_frames(arena, table, nullptr, dims.frame_bytes, frames, n, params, stages, plan.axes, plan.bins, counts);
 }
 
 // ---- the simulating form: one body, the arena in LDS (the 56x56 sizes as constants) or in this workgroup's slab ----
@@ -719,14 +636,25 @@ static bool place_histogram_tables(yf_calib* c) {
   return ok;
 }
 
+// The evaluation kernels, a row per form.  The LDS kernels: the dynamic LDS yf_calib_create allows each, and what it says if it cannot ...
+static const struct { const void* kernel; size_t lds_bytes; const char* what; } kLdsKernels[] = {
+    {(const void*)yfc_observe_kernel, kLdsBytes, "hipFuncSetAttribute(max dynamic LDS)"},
+    {(const void*)yfc_compare_kernel, kCmpLdsBytes, "hipFuncSetAttribute(max dynamic LDS, compare)"},
+    {(const void*)yfc_histogram_kernel, kHistLdsBytes, "hipFuncSetAttribute(max dynamic LDS, histogram)"},
+    {(const void*)yfc_simulate_kernel, kSimLdsBytes, "hipFuncSetAttribute(max dynamic LDS, simulate)"},
+    {(const void*)yfc_channel_sums_kernel, kChanLdsBytes, "hipFuncSetAttribute(max dynamic LDS, channel sums)"}};
+// ... and the slab kernels, for general_setup's occupancy query
+static const void* const kSlabKernels[] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel,
+                                           (const void*)yfc_simulate_hw_kernel, (const void*)yfc_channel_sums_hw_kernel};
+constexpr int kForms = sizeof kSlabKernels / sizeof kSlabKernels[0];
+static_assert(sizeof kLdsKernels / sizeof kLdsKernels[0] == kForms, "every form has an LDS and a slab kernel");
+
 // The general forms' share of yf_calib_create (the device is current): the grid from an occupancy query, every size's stage table, the event.
 static bool general_setup(yf_calib* c, int cus) {
   int per_cu = 0;
-  const void* kernels[5] = {(const void*)yfc_observe_hw_kernel, (const void*)yfc_compare_hw_kernel, (const void*)yfc_histogram_hw_kernel,
-                            (const void*)yfc_simulate_hw_kernel, (const void*)yfc_channel_sums_hw_kernel};
-  for (int k = 0; k < 5; ++k) {                            // one slab count for the five: the fewest resident workgroups any of them has
+  for (int k = 0; k < kForms; ++k) {                       // one slab count for all: the fewest resident workgroups any of them has
     int blocks = 0;
-    if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], kThreads, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
+    if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kSlabKernels[k], kThreads, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
       return false;
     if (blocks < 1) { set_error("yf_calib_create: general kernel %d: the occupancy query gives %d resident workgroups", k, blocks); return false; }
     per_cu = k == 0 || blocks < per_cu ? blocks : per_cu;
@@ -760,12 +688,11 @@ static bool size_refused(const char* name, int h, int w) {
   return true;
 }
 
-// What a general call does before it launches, at an admitted size: the dims and the stage table, slabs enough for it, and the launch before
-// it out of the way.  0, or a negative value with the text set and nothing launched.
-static int general_begin(yf_calib* c, int h, int w, hipStream_t s, yfc_dims* dims, const yfc_stage** d_stages) {
-  yfc_dims_of(h, w, dims);
-  *d_stages = c->d_stages_hw + ((size_t)(h / YFC_SIDE_STEP - 1) * YFC_N_SIDES + (size_t)(w / YFC_SIDE_STEP - 1)) * YFC_N_STAGES;
-  const size_t need = (size_t)c->hw_grid * (size_t)dims->arena_floats * sizeof(float);
+// What a general call does before it launches, at an admitted size: the stage table, slabs enough for it, and the launch before it out of
+// the way.  0, or a negative value with the text set and nothing launched.
+static int general_begin(yf_calib* c, const yfc_dims& dims, hipStream_t s, const yfc_stage** d_stages) {
+  *d_stages = c->d_stages_hw + ((size_t)(dims.h / YFC_SIDE_STEP - 1) * YFC_N_SIDES + (size_t)(dims.w / YFC_SIDE_STEP - 1)) * YFC_N_STAGES;
+  const size_t need = (size_t)c->hw_grid * (size_t)dims.arena_floats * sizeof(float);
   if (need > c->slab_bytes) {                              // the one place where a general call synchronises and allocates
     if (!hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize (growing the scratch)")) return -2;
     (void)hipFree(c->d_slabs);
@@ -786,6 +713,153 @@ static bool general_end(yf_calib* c, hipStream_t s) {
   if (!hip_ok(hipEventRecord(c->slabs_free, s), "hipEventRecord(slabs)")) return false;
   c->slabs_used = true;
   return true;
+}
+
+// What the ten evaluating entries share around their launch.  Made: the handle's device is current until the entry returns, the grid is one
+// workgroup per frame up to grid_max (the LDS kernels, hw false: the size is 56x56) or hw_grid (the slab kernels, at an admitted h x w), and
+// for the slab kernels the size's stage table is chosen and the stream waits for the slabs; rc is then 0, or what the entry returns.
+// launch(): the evaluation and its check.  launched(): the check of any later launch.  record(): the slab kernels' event; the LDS kernels
+// touch neither the event nor the slabs.
+struct Evaluation {
+  const char* name;
+  yf_calib* c;
+  bool hw;
+  DeviceScope scope;
+  hipStream_t s;
+  int grid;
+  yfc_dims dims;
+  const yfc_stage* d_stages;
+  long rc = 0;
+
+  Evaluation(const char* name, yf_calib* c, bool hw, int h, int w, long n, void* stream)
+      : name(name), c(c), hw(hw), scope(c->device), s((hipStream_t)stream), grid((int)(n < (hw ? c->hw_grid : c->grid_max) ? n : hw ? c->hw_grid : c->grid_max)),
+        d_stages(c->d_stages) {
+    yfc_dims_of(h, w, &dims);
+    if (!scope.ok) rc = -1;
+    else if (hw) rc = general_begin(c, dims, s, &d_stages);
+  }
+  // args: what follows `stages` in the LDS kernel's parameters and `slabs` in the slab kernel's
+  template <class Lds, class Slab, class... Args>
+  bool launch(Lds lds_kernel, size_t lds_bytes, Slab slab_kernel, const void* d_frames, long n, Args... args) {
+    if (hw) hipLaunchKernelGGL(slab_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims, c->d_slabs, args...);
+    else hipLaunchKernelGGL(lds_kernel, dim3(grid), dim3(kThreads), lds_bytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, args...);
+    return launched("evaluation");
+  }
+  bool launched(const char* what) {
+    char text[96];
+    snprintf(text, sizeof text, "%s: launch of the %s", name, what);
+    return hip_ok(hipGetLastError(), text);
+  }
+  bool record() { return !hw || general_end(c, s); }
+};
+
+// totals[entry] of the frames' records, behind the evaluation on its stream
+static bool launch_totals(Evaluation& e, const void* d_frame_stats, long n, const yfc_cmp_plan& plan, void* d_totals) {
+  hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, e.s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
+  return e.launched("totals");
+}
+
+static bool launch_channel_totals(Evaluation& e, const double* d_frame_sums, long n, double* d_sums) {
+  hipLaunchKernelGGL(yfc_channel_totals_kernel, dim3((YFC_CHANNELS + kChanTotalsThreads - 1) / kChanTotalsThreads), dim3(kChanTotalsThreads), 0, e.s,
+                     d_frame_sums, n, d_sums);
+  return e.launched("totals");
+}
+
+// the totals of a simulate call are those of a comparison with one entry: the head
+static yfc_cmp_plan head_totals_plan(int logits) {
+  yfc_cmp_plan plan;
+  memset(&plan, 0, sizeof plan);
+  plan.count = 1;
+  plan.elements[0] = logits;
+  return plan;
+}
+
+// ---- the five operations, each once: `name` is the entry's own, for its texts; hw: the _hw entry, at h x w (else 56x56) ----
+static long observe(const char* name, yf_calib* c, bool hw, int h, int w, const void* d_frames, long n, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c || !d_frames) { set_error("%s: NULL %s", name, c ? "d_frames" : "handle"); return -1; }
+  if (n < 1) { set_error("%s: n is %ld, expected at least 1", name, n); return -1; }
+  if (hw && size_refused(name, h, w)) return -1;
+  Evaluation e(name, c, hw, h, w, n, stream);
+  if (e.rc) return e.rc;
+  if (!e.launch(yfc_observe_kernel, kLdsBytes, yfc_observe_hw_kernel, d_frames, n, (float*)d_logits, c->d_partials)) return -2;
+  hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, e.s, (const float*)c->d_partials, e.grid, c->d_ranges);
+  if (!e.launched("merge") || !e.record()) return -2;        // (the merge reads the handle's partials: the event comes behind it)
+  c->frames += n;
+  return n;
+}
+
+static long compare(const char* name, yf_calib* c, bool hw, int h, int w, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                    void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("%s: NULL handle", name); return -1; }
+  if (hw && size_refused(name, h, w)) return -1;
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t ids[YFC_N_RANGES];
+  if (hw) yfc_build_stages_hw(stages, ids, h, w);
+  yfc_cmp_plan plan;
+  if (yfc_cmp_validate(hw ? stages : c->stages, entries, count, n, &plan, g_err, sizeof g_err)) return -1;
+  if (!d_frames || !d_frame_stats) { set_error("%s: NULL %s", name, d_frames ? "d_frame_stats" : "d_frames"); return -1; }
+  Evaluation e(name, c, hw, h, w, n, stream);
+  if (e.rc) return e.rc;
+  if (!e.launch(yfc_compare_kernel, kCmpLdsBytes, yfc_compare_hw_kernel, d_frames, n, plan, (yfc_cmp_frame*)d_frame_stats) || !e.record()) return -2;
+  if (d_totals && !launch_totals(e, d_frame_stats, n, plan, d_totals)) return -2;
+  return n;
+}
+
+static long histogram(const char* name, yf_calib* c, bool hw, int h, int w, const void* d_frames, long n, const float* minmax, int bins,
+                      uint64_t* d_counts, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("%s: NULL handle", name); return -1; }
+  if (hw && size_refused(name, h, w)) return -1;
+  yfc_hist_plan plan;                                      // (the slab kernel takes it without the offsets)
+  if (yfc_hist_validate(d_frames, n, minmax, bins, d_counts, &plan.axes, g_err, sizeof g_err)) return -1;
+  if ((uintptr_t)d_counts % sizeof(uint64_t)) { set_error("histogram: counts is at %p, expected an address aligned to 8 bytes", (void*)d_counts); return -1; }
+  memcpy(plan.off, c->hist_off, sizeof plan.off);
+  plan.bins = bins;
+  Evaluation e(name, c, hw, h, w, n, stream);
+  if (e.rc) return e.rc;
+  if (!e.launch(yfc_histogram_kernel, kHistLdsBytes, yfc_histogram_hw_kernel, d_frames, n, plan, (unsigned long long*)d_counts) || !e.record()) return -2;
+  return n;
+}
+
+static long simulate(const char* name, yf_calib* c, bool hw, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                     const void* d_ref_logits, void* d_logits, void* d_frame_stats, void* d_totals, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("%s: NULL handle", name); return -1; }
+  if (hw && size_refused(name, h, w)) return -1;
+  yfc_sim_plan plan;
+  if (yfc_sim_validate(name, c->stages, d_frames, n, table, d_ref_logits, d_frame_stats, d_totals, &plan, g_err, sizeof g_err)) return -1;
+  Evaluation e(name, c, hw, h, w, n, stream);
+  if (e.rc) return e.rc;
+  if (!e.launch(yfc_simulate_kernel, kSimLdsBytes, yfc_simulate_hw_kernel, d_frames, n, plan, (const float*)d_ref_logits, (float*)d_logits,
+                (yfc_cmp_frame*)d_frame_stats) || !e.record())
+    return -2;
+  if (d_totals && !launch_totals(e, d_frame_stats, n, head_totals_plan(e.dims.logits), d_totals)) return -2;
+  return n;
+}
+
+static long channel_sums(const char* name, yf_calib* c, bool hw, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
+                         double* d_frame_sums, double* d_sums, void* d_logits, void* stream) {
+  g_err[0] = 0;
+  if (!c) { set_error("%s: NULL handle", name); return -1; }
+  if (hw && size_refused(name, h, w)) return -1;
+  yfc_stage stages[YFC_N_STAGES];
+  int32_t ids[YFC_N_RANGES];
+  if (hw) yfc_build_stages_hw(stages, ids, h, w);
+  yfc_chan_plan plan;
+  if (yfc_chan_validate(name, hw ? stages : c->stages, d_frames, n, table, d_frame_sums, &plan, g_err, sizeof g_err)) return -1;
+  if (hw && yfc_chan_scratch_doubles(stages) > YFC_CHAN_SCRATCH_MAX) {      // (the 56x56 scratch was checked at yf_calib_create)
+    set_error("%s: h = %d, w = %d needs a chunk scratch of %d doubles, the kernel has %d", name, h, w, yfc_chan_scratch_doubles(stages),
+              (int)YFC_CHAN_SCRATCH_MAX);
+    return -1;
+  }
+  Evaluation e(name, c, hw, h, w, n, stream);
+  if (e.rc) return e.rc;
+  if (!e.launch(yfc_channel_sums_kernel, kChanLdsBytes, yfc_channel_sums_hw_kernel, d_frames, n, plan, d_frame_sums, (float*)d_logits) || !e.record())
+    return -2;
+  if (d_sums && !launch_channel_totals(e, d_frame_sums, n, d_sums)) return -2;
+  return n;
 }
 
 extern "C" {
@@ -833,11 +907,9 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
     ok = scope.ok && hip_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "hipDeviceGetAttribute(multiprocessors)");
     if (ok && cus < 1) { ok = false; set_error("yf_calib_create: device %d reports %d compute units", device, cus); }
     c->grid_max = cus;                                     // 156.8 KB of LDS: one workgroup per CU
-    ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_observe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes),
-                      "hipFuncSetAttribute(max dynamic LDS)")
-         && hip_ok(hipFuncSetAttribute((const void*)yfc_compare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCmpLdsBytes),
-                   "hipFuncSetAttribute(max dynamic LDS, compare)")
-         && hip_ok(hipMalloc((void**)&c->d_params, sizeof(float) * kParamFloats), "hipMalloc(params)")
+    for (int k = 0; k < kForms && ok; ++k)
+      ok = hip_ok(hipFuncSetAttribute(kLdsKernels[k].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsKernels[k].lds_bytes), kLdsKernels[k].what);
+    ok = ok && hip_ok(hipMalloc((void**)&c->d_params, sizeof(float) * kParamFloats), "hipMalloc(params)")
          && hip_ok(hipMalloc((void**)&c->d_stages, sizeof stages), "hipMalloc(stages)")
          && general_setup(c, cus)
          && hip_ok(hipMalloc((void**)&c->d_partials, sizeof(float) * kWgFloats * (size_t)(c->hw_grid > cus ? c->hw_grid : cus)), "hipMalloc(partials)")
@@ -845,12 +917,6 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
          && hip_ok(hipMemcpy(c->d_params, p, sizeof(float) * kParamFloats, hipMemcpyHostToDevice), "hipMemcpy(params)")
          && hip_ok(hipMemcpy(c->d_stages, stages, sizeof stages, hipMemcpyHostToDevice), "hipMemcpy(stages)")
          && upload_empty_ranges(c) && hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    ok = ok && hip_ok(hipFuncSetAttribute((const void*)yfc_histogram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHistLdsBytes),
-                      "hipFuncSetAttribute(max dynamic LDS, histogram)")
-         && hip_ok(hipFuncSetAttribute((const void*)yfc_simulate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSimLdsBytes),
-                   "hipFuncSetAttribute(max dynamic LDS, simulate)")
-         && hip_ok(hipFuncSetAttribute((const void*)yfc_channel_sums_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChanLdsBytes),
-                   "hipFuncSetAttribute(max dynamic LDS, channel sums)");
   }
   delete[] p;
   if (!ok) {
@@ -864,249 +930,46 @@ YF_CALIB_API yf_calib* yf_calib_create(const void* yfw, size_t bytes, int device
 }
 
 YF_CALIB_API long yf_calib_observe_device(yf_calib* c, const void* d_frames, long n, void* d_logits, void* stream) {
-  g_err[0] = 0;
-  if (!c || !d_frames) { set_error("yf_calib_observe_device: NULL %s", c ? "d_frames" : "handle"); return -1; }
-  if (n < 1) { set_error("yf_calib_observe_device: n is %ld, expected at least 1", n); return -1; }
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
-  hipLaunchKernelGGL(yfc_observe_kernel, dim3(grid), dim3(kThreads), kLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
-                     (const yfc_stage*)c->d_stages, (float*)d_logits, c->d_partials);
-  if (!hip_ok(hipGetLastError(), "yf_calib_observe_device: launch of the evaluation")) return -2;
-  hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, s, (const float*)c->d_partials, grid, c->d_ranges);
-  if (!hip_ok(hipGetLastError(), "yf_calib_observe_device: launch of the merge")) return -2;
-  c->frames += n;
-  return n;
+  return observe("yf_calib_observe_device", c, false, 56, 56, d_frames, n, d_logits, stream);
+}
+YF_CALIB_API long yf_calib_observe_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, void* d_logits, void* stream) {
+  return observe("yf_calib_observe_hw_device", c, true, h, w, d_frames, n, d_logits, stream);
 }
 
 YF_CALIB_API long yf_calib_compare_device(yf_calib* c, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
                                           void* d_frame_stats, void* d_totals, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_compare_device: NULL handle"); return -1; }
-  yfc_cmp_plan plan;
-  if (yfc_cmp_validate(c->stages, entries, count, n, &plan, g_err, sizeof g_err)) return -1;
-  if (!d_frames || !d_frame_stats) { set_error("yf_calib_compare_device: NULL %s", d_frames ? "d_frame_stats" : "d_frames"); return -1; }
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
-  hipLaunchKernelGGL(yfc_compare_kernel, dim3(grid), dim3(kThreads), kCmpLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
-                     (const yfc_stage*)c->d_stages, plan, (yfc_cmp_frame*)d_frame_stats);
-  if (!hip_ok(hipGetLastError(), "yf_calib_compare_device: launch of the evaluation")) return -2;
-  if (d_totals) {
-    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
-    if (!hip_ok(hipGetLastError(), "yf_calib_compare_device: launch of the totals")) return -2;
-  }
-  return n;
+  return compare("yf_calib_compare_device", c, false, 56, 56, d_frames, n, entries, count, d_frame_stats, d_totals, stream);
+}
+YF_CALIB_API long yf_calib_compare_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
+                                             void* d_frame_stats, void* d_totals, void* stream) {
+  return compare("yf_calib_compare_hw_device", c, true, h, w, d_frames, n, entries, count, d_frame_stats, d_totals, stream);
 }
 
 YF_CALIB_API long yf_calib_histogram_device(yf_calib* c, const void* d_frames, long n, const float* minmax, int bins, uint64_t* d_counts,
                                             void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_histogram_device: NULL handle"); return -1; }
-  yfc_hist_plan plan;
-  if (yfc_hist_validate(d_frames, n, minmax, bins, d_counts, &plan.axes, g_err, sizeof g_err)) return -1;
-  if ((uintptr_t)d_counts % sizeof(uint64_t)) { set_error("histogram: counts is at %p, expected an address aligned to 8 bytes", (void*)d_counts); return -1; }
-  memcpy(plan.off, c->hist_off, sizeof plan.off);
-  plan.bins = bins;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
-  hipLaunchKernelGGL(yfc_histogram_kernel, dim3(grid), dim3(kThreads), kHistLdsBytes, (hipStream_t)stream, (const int8_t*)d_frames, n,
-                     (const float*)c->d_params, (const yfc_stage*)c->d_stages, plan, (unsigned long long*)d_counts);
-  if (!hip_ok(hipGetLastError(), "yf_calib_histogram_device: launch of the evaluation")) return -2;
-  return n;
+  return histogram("yf_calib_histogram_device", c, false, 56, 56, d_frames, n, minmax, bins, d_counts, stream);
 }
-
-YF_CALIB_API long yf_calib_observe_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, void* d_logits, void* stream) {
-  g_err[0] = 0;
-  if (!c || !d_frames) { set_error("yf_calib_observe_hw_device: NULL %s", c ? "d_frames" : "handle"); return -1; }
-  if (n < 1) { set_error("yf_calib_observe_hw_device: n is %ld, expected at least 1", n); return -1; }
-  if (size_refused("yf_calib_observe_hw_device", h, w)) return -1;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  yfc_dims dims;
-  const yfc_stage* d_stages;
-  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
-  if (rc) return rc;
-  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
-  hipLaunchKernelGGL(yfc_observe_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
-                     c->d_slabs, (float*)d_logits, c->d_partials);
-  if (!hip_ok(hipGetLastError(), "yf_calib_observe_hw_device: launch of the evaluation")) return -2;
-  hipLaunchKernelGGL(yfc_merge_kernel, dim3(1), dim3(128), 0, s, (const float*)c->d_partials, grid, c->d_ranges);
-  if (!hip_ok(hipGetLastError(), "yf_calib_observe_hw_device: launch of the merge")) return -2;
-  if (!general_end(c, s)) return -2;
-  c->frames += n;
-  return n;
-}
-
-YF_CALIB_API long yf_calib_compare_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_qtensor* entries, int count,
-                                             void* d_frame_stats, void* d_totals, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_compare_hw_device: NULL handle"); return -1; }
-  if (size_refused("yf_calib_compare_hw_device", h, w)) return -1;
-  yfc_stage stages[YFC_N_STAGES];
-  int32_t ids[YFC_N_RANGES];
-  yfc_build_stages_hw(stages, ids, h, w);
-  yfc_cmp_plan plan;
-  if (yfc_cmp_validate(stages, entries, count, n, &plan, g_err, sizeof g_err)) return -1;
-  if (!d_frames || !d_frame_stats) { set_error("yf_calib_compare_hw_device: NULL %s", d_frames ? "d_frame_stats" : "d_frames"); return -1; }
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  yfc_dims dims;
-  const yfc_stage* d_stages;
-  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
-  if (rc) return rc;
-  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
-  hipLaunchKernelGGL(yfc_compare_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
-                     c->d_slabs, plan, (yfc_cmp_frame*)d_frame_stats);
-  if (!hip_ok(hipGetLastError(), "yf_calib_compare_hw_device: launch of the evaluation")) return -2;
-  if (!general_end(c, s)) return -2;
-  if (d_totals) {
-    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, plan, (yfc_cmp_total*)d_totals);
-    if (!hip_ok(hipGetLastError(), "yf_calib_compare_hw_device: launch of the totals")) return -2;
-  }
-  return n;
-}
-
 YF_CALIB_API long yf_calib_histogram_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const float* minmax, int bins,
                                                uint64_t* d_counts, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_histogram_hw_device: NULL handle"); return -1; }
-  if (size_refused("yf_calib_histogram_hw_device", h, w)) return -1;
-  yfc_hist_hw_plan plan;
-  if (yfc_hist_validate(d_frames, n, minmax, bins, d_counts, &plan.axes, g_err, sizeof g_err)) return -1;
-  if ((uintptr_t)d_counts % sizeof(uint64_t)) { set_error("histogram: counts is at %p, expected an address aligned to 8 bytes", (void*)d_counts); return -1; }
-  plan.bins = bins;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  yfc_dims dims;
-  const yfc_stage* d_stages;
-  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
-  if (rc) return rc;
-  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
-  hipLaunchKernelGGL(yfc_histogram_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
-                     c->d_slabs, plan, (unsigned long long*)d_counts);
-  if (!hip_ok(hipGetLastError(), "yf_calib_histogram_hw_device: launch of the evaluation")) return -2;
-  if (!general_end(c, s)) return -2;
-  return n;
-}
-
-// the totals of a simulate call are those of a comparison with one entry: the head
-static yfc_cmp_plan head_totals_plan(int logits) {
-  yfc_cmp_plan plan;
-  memset(&plan, 0, sizeof plan);
-  plan.count = 1;
-  plan.elements[0] = logits;
-  return plan;
+  return histogram("yf_calib_histogram_hw_device", c, true, h, w, d_frames, n, minmax, bins, d_counts, stream);
 }
 
 YF_CALIB_API long yf_calib_simulate_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, const void* d_ref_logits,
                                            void* d_logits, void* d_frame_stats, void* d_totals, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_simulate_device: NULL handle"); return -1; }
-  yfc_sim_plan plan;
-  if (yfc_sim_validate("yf_calib_simulate_device", c->stages, d_frames, n, table, d_ref_logits, d_frame_stats, d_totals, &plan, g_err, sizeof g_err)) return -1;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
-  hipLaunchKernelGGL(yfc_simulate_kernel, dim3(grid), dim3(kThreads), kSimLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
-                     (const yfc_stage*)c->d_stages, plan, (const float*)d_ref_logits, (float*)d_logits, (yfc_cmp_frame*)d_frame_stats);
-  if (!hip_ok(hipGetLastError(), "yf_calib_simulate_device: launch of the evaluation")) return -2;
-  if (d_totals) {
-    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, head_totals_plan(YFC_LOGITS),
-                       (yfc_cmp_total*)d_totals);
-    if (!hip_ok(hipGetLastError(), "yf_calib_simulate_device: launch of the totals")) return -2;
-  }
-  return n;
+  return simulate("yf_calib_simulate_device", c, false, 56, 56, d_frames, n, table, d_ref_logits, d_logits, d_frame_stats, d_totals, stream);
 }
-
 YF_CALIB_API long yf_calib_simulate_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
                                               const void* d_ref_logits, void* d_logits, void* d_frame_stats, void* d_totals, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_simulate_hw_device: NULL handle"); return -1; }
-  if (size_refused("yf_calib_simulate_hw_device", h, w)) return -1;
-  yfc_sim_plan plan;
-  if (yfc_sim_validate("yf_calib_simulate_hw_device", c->stages, d_frames, n, table, d_ref_logits, d_frame_stats, d_totals, &plan, g_err, sizeof g_err)) return -1;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  yfc_dims dims;
-  const yfc_stage* d_stages;
-  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
-  if (rc) return rc;
-  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
-  hipLaunchKernelGGL(yfc_simulate_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
-                     c->d_slabs, plan, (const float*)d_ref_logits, (float*)d_logits, (yfc_cmp_frame*)d_frame_stats);
-  if (!hip_ok(hipGetLastError(), "yf_calib_simulate_hw_device: launch of the evaluation")) return -2;
-  if (!general_end(c, s)) return -2;
-  if (d_totals) {
-    hipLaunchKernelGGL(yfc_totals_kernel, dim3(1), dim3(kTotalsThreads), 0, s, (const yfc_cmp_frame*)d_frame_stats, n, head_totals_plan(dims.logits),
-                       (yfc_cmp_total*)d_totals);
-    if (!hip_ok(hipGetLastError(), "yf_calib_simulate_hw_device: launch of the totals")) return -2;
-  }
-  return n;
+  return simulate("yf_calib_simulate_hw_device", c, true, h, w, d_frames, n, table, d_ref_logits, d_logits, d_frame_stats, d_totals, stream);
 }
 
 YF_CALIB_API long yf_calib_channel_sums_device(yf_calib* c, const void* d_frames, long n, const yf_calib_sim_entry* table, double* d_frame_sums,
                                                double* d_sums, void* d_logits, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_channel_sums_device: NULL handle"); return -1; }
-  yfc_chan_plan plan;
-  if (yfc_chan_validate("yf_calib_channel_sums_device", c->stages, d_frames, n, table, d_frame_sums, &plan, g_err, sizeof g_err)) return -1;
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (int)(n < c->grid_max ? n : c->grid_max);
-  hipLaunchKernelGGL(yfc_channel_sums_kernel, dim3(grid), dim3(kThreads), kChanLdsBytes, s, (const int8_t*)d_frames, n, (const float*)c->d_params,
-                     (const yfc_stage*)c->d_stages, plan, d_frame_sums, (float*)d_logits);
-  if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_device: launch of the evaluation")) return -2;
-  if (d_sums) {
-    hipLaunchKernelGGL(yfc_channel_totals_kernel, dim3((YFC_CHANNELS + kChanTotalsThreads - 1) / kChanTotalsThreads), dim3(kChanTotalsThreads), 0, s,
-                       (const double*)d_frame_sums, n, d_sums);
-    if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_device: launch of the totals")) return -2;
-  }
-  return n;
+  return channel_sums("yf_calib_channel_sums_device", c, false, 56, 56, d_frames, n, table, d_frame_sums, d_sums, d_logits, stream);
 }
-
 YF_CALIB_API long yf_calib_channel_sums_hw_device(yf_calib* c, int h, int w, const void* d_frames, long n, const yf_calib_sim_entry* table,
                                                   double* d_frame_sums, double* d_sums, void* d_logits, void* stream) {
-  g_err[0] = 0;
-  if (!c) { set_error("yf_calib_channel_sums_hw_device: NULL handle"); return -1; }
-  if (size_refused("yf_calib_channel_sums_hw_device", h, w)) return -1;
-  yfc_stage stages[YFC_N_STAGES];
-  int32_t ids[YFC_N_RANGES];
-  yfc_build_stages_hw(stages, ids, h, w);
-  yfc_chan_plan plan;
-  if (yfc_chan_validate("yf_calib_channel_sums_hw_device", stages, d_frames, n, table, d_frame_sums, &plan, g_err, sizeof g_err)) return -1;
-  if (yfc_chan_scratch_doubles(stages) > YFC_CHAN_SCRATCH_MAX) {
-    set_error("yf_calib_channel_sums_hw_device: h = %d, w = %d needs a chunk scratch of %d doubles, the kernel has %d", h, w,
-              yfc_chan_scratch_doubles(stages), (int)YFC_CHAN_SCRATCH_MAX);
-    return -1;
-  }
-  DeviceScope scope(c->device);
-  if (!scope.ok) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  yfc_dims dims;
-  const yfc_stage* d_stages;
-  const int rc = general_begin(c, h, w, s, &dims, &d_stages);
-  if (rc) return rc;
-  const int grid = (int)(n < c->hw_grid ? n : c->hw_grid);
-  hipLaunchKernelGGL(yfc_channel_sums_hw_kernel, dim3(grid), dim3(kThreads), 0, s, (const int8_t*)d_frames, n, (const float*)c->d_params, d_stages, dims,
-                     c->d_slabs, plan, d_frame_sums, (float*)d_logits);
-  if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_hw_device: launch of the evaluation")) return -2;
-  if (!general_end(c, s)) return -2;
-  if (d_sums) {
-    hipLaunchKernelGGL(yfc_channel_totals_kernel, dim3((YFC_CHANNELS + kChanTotalsThreads - 1) / kChanTotalsThreads), dim3(kChanTotalsThreads), 0, s,
-                       (const double*)d_frame_sums, n, d_sums);
-    if (!hip_ok(hipGetLastError(), "yf_calib_channel_sums_hw_device: launch of the totals")) return -2;
-  }
-  return n;
+  return channel_sums("yf_calib_channel_sums_hw_device", c, true, h, w, d_frames, n, table, d_frame_sums, d_sums, d_logits, stream);
 }
 
 YF_CALIB_API int yf_calib_channel_layout(int32_t first[YF_CALIB_N_CONVS], int32_t cout[YF_CALIB_N_CONVS], int32_t pixels56[YF_CALIB_N_CONVS]) {

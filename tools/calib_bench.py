@@ -22,6 +22,16 @@ beside observe in the same run, on the same frames: every entry disabled, every 
 process, in rounds that alternate with this build's: the existing kernels did not move.
 
     python tools/calib_bench.py --simulate [--size 160 160 --frames 1024] [--parent-lib DIR/libyf_calib.so]
+
+--ab DIR/libyf_calib.so (built from the parent commit) times the observing, the comparing and the histogram form of both builds in one process,
+LDS kernels at 56x56 and slab kernels at 56x56 (4096 frames) and at 160x160 (1024 frames): --rounds rounds (at least 5) per build, each the
+median of --launches launches.  Every round has a handle of its own in either build, all created up front in alternation, and the build that
+goes first alternates from round to round: where a handle's buffers lie and who follows whom moves a median by more than repeated launches on
+one handle scatter, and both belong to the parent's own scatter.  Compare takes the tensors of calib.report_tensors (random int8 values), with
+totals; histogram 2048 bins on the ranges observed.  A round median of this build passes inside the span of the parent's round medians, or
+above it by no more than that span's width; the exit status is 1 if any fails.
+
+    python tools/calib_bench.py --ab DIR/libyf_calib.so
 """
 import argparse
 import importlib
@@ -199,6 +209,103 @@ def simulate_rate(a, calib, torch, yfw):
     return 0
 
 
+AB_SHAPES = (("LDS", 56, 56, 4096, False), ("slab", 56, 56, 4096, True), ("slab", 160, 160, 1024, True))
+
+
+def ab_rate(a, calib, torch, yfw):
+    import ctypes
+    yf = importlib.import_module("stm32h7-yolo_amd")
+    yfm = open(os.path.join(ROOT, "oracle", "model", "yoloface_int8.yfm"), "rb").read()
+    network = yf.load()
+    tensors = calib.report_tensors(lambda op: network.yf_network_dump_offset(int(op)), yfm)
+    cal = calib.Calibration(yfw)
+    parent = ctypes.CDLL(a.ab)
+    vp = ctypes.c_void_p
+    parent.yf_calib_create.restype, parent.yf_calib_create.argtypes = vp, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
+    parent.yf_calib_destroy.restype, parent.yf_calib_destroy.argtypes = None, [vp]
+    parent.yf_calib_build_id.restype = parent.yf_calib_last_error_text.restype = ctypes.c_char_p
+    calib.declare_device(parent)
+    builds = (("this build", cal._lib, []), ("parent commit", parent, []))
+    for _ in range(a.rounds):                                              # a handle per round and build, created in alternation
+        for k, lib, handles in builds:
+            handles.append(lib.yf_calib_create(yfw, len(yfw), cal.device))
+            if not handles[-1]:
+                sys.exit(f"calib_bench: yf_calib_create failed ({k}): {lib.yf_calib_last_error_text().decode()}")
+    stream, bins, rng = torch.cuda.current_stream().cuda_stream, 2048, np.random.default_rng(4096)
+    print(f"device: {torch.cuda.get_device_name(0)}")
+    for k, lib, _ in builds:
+        print(f"libyf_calib.so, {k}: build id {lib.yf_calib_build_id().decode()}")
+    print(f"Both libraries in one process.  Per entry and shape {a.rounds} rounds per build, each round on a handle of its own, the build that goes first "
+          f"alternating; a round is the median of {a.launches} launches after {a.warmup} warm-up, each launch between two HIP events on its stream, "
+          f"frames resident in HBM.")
+    print(f"observe: evaluation + merge, logits written.  compare: the {len(tensors)} tensors of calib.report_tensors, random int8 values, with totals.  "
+          f"histogram: {bins} bins on the ranges observed.")
+    print("pass: every round of this build inside the span of the parent's rounds, or above it by no more than the span's width")
+
+    def timed(call):
+        for _ in range(a.warmup):
+            call()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.launches):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            t1.synchronize()
+            ms.append(t0.elapsed_time(t1))
+        return statistics.median(ms)
+
+    failed = 0
+    for kernels, h, w, n, hw in AB_SHAPES:
+        d_x = torch.from_numpy(rng.integers(-128, 128, (n, h, w, 3), dtype=np.int8)).cuda()
+        d_l = torch.empty((n, h // 8, w // 8, 18), dtype=torch.float32, device="cuda")
+        elements = [calib.elements_at(t["elements"], h, w) for t in tensors]
+        offsets = np.concatenate([[0], np.cumsum(elements)])
+        d_q = torch.from_numpy(rng.integers(-128, 128, (n, int(offsets[-1])), dtype=np.int8)).cuda()
+        entries = calib._qtensors([calib.Entry(t["tensor"], t["scale"], t["zero_point"], d_q.data_ptr() + int(o), int(offsets[-1]))
+                                   for t, o in zip(tensors, offsets)])
+        d_stats = torch.zeros((n, len(tensors), 32), dtype=torch.uint8, device="cuda")
+        d_totals = torch.zeros((len(tensors), 48), dtype=torch.uint8, device="cuda")
+        d_counts = torch.zeros((calib.N_RANGES, bins), dtype=torch.int64, device="cuda")
+        cal.reset()
+        cal.observe(d_x, logits=False, general=hw)
+        minmax = calib._minmax_array(cal.ranges())
+        size, sfx = ((h, w), "_hw") if hw else ((), "")
+        args = {"observe": (d_x.data_ptr(), n, d_l.data_ptr(), stream),
+                "compare": (d_x.data_ptr(), n, entries, len(tensors), d_stats.data_ptr(), d_totals.data_ptr(), stream),
+                "histogram": (d_x.data_ptr(), n, minmax.ctypes.data, bins, d_counts.data_ptr(), stream)}
+        print(f"\n{kernels} kernels, {h}x{w}, {n} frames: round medians in ms")
+        for op, tail in args.items():
+            name = f"yf_calib_{op}{sfx}_device"
+
+            def call_of(lib, handle):
+                fn = getattr(lib, name)
+                def call():
+                    if fn(handle, *size, *tail) != n:
+                        sys.exit(f"calib_bench: {name} failed: {lib.yf_calib_last_error_text().decode()}")
+                return call
+
+            rounds = {k: [] for k, _, _ in builds}
+            for r in range(a.rounds):
+                for k, lib, handles in builds[::-1 if r % 2 else 1]:
+                    rounds[k].append(timed(call_of(lib, handles[r])))
+            lo, hi = min(rounds["parent commit"]), max(rounds["parent commit"])
+            ok = max(rounds["this build"]) <= hi + (hi - lo)
+            failed += not ok
+            for k, _, _ in builds:
+                print(f"  {name:32s} {k:13s} " + " ".join(f"{m:7.3f}" for m in rounds[k]) + f"   median {statistics.median(rounds[k]):.3f}")
+            print(f"  {'':32s} parent span {lo:.3f} .. {hi:.3f} (width {hi - lo:.3f}), this build {min(rounds['this build']):.3f} .. "
+                  f"{max(rounds['this build']):.3f}: {'pass' if ok else 'FAIL'}")
+        torch.cuda.synchronize()
+    for _, lib, handles in builds:
+        for handle in handles:
+            lib.yf_calib_destroy(handle)
+    cal.destroy()
+    print(f"\n{'every entry passes' if not failed else f'{failed} entries FAIL'}")
+    return 1 if failed else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"))
@@ -209,13 +316,21 @@ def main():
     ap.add_argument("--restatement-frames", type=int, default=8)
     ap.add_argument("--simulate", action="store_true", help="time the simulating form beside observe")
     ap.add_argument("--parent-lib", help="with --simulate: libyf_calib.so built from the parent commit, whose observe is timed beside this build's")
+    ap.add_argument("--ab", metavar="PARENT_LIB", help="libyf_calib.so built from the parent commit: observe, compare and histogram of both builds")
+    ap.add_argument("--rounds", type=int, default=5, help="with --ab: rounds per build")
     a = ap.parse_args()
     if a.launches < 20:
         ap.error("--launches: at least 20")
+    if a.rounds < 5:
+        ap.error("--rounds: at least 5")
     import torch
     calib = importlib.import_module("stm32h7-yolo_amd.calib")
     model_file = importlib.import_module("stm32h7-yolo_amd.model_file")
     yfw = open(os.path.join(ROOT, "stm32h7-yolo_amd", "model", "yoloface_fp32.yfw"), "rb").read()
+    if a.ab:
+        if not torch.cuda.is_available():
+            sys.exit("calib_bench: --ab needs a GPU")
+        return ab_rate(a, calib, torch, yfw)
     if a.simulate:
         if not torch.cuda.is_available():
             sys.exit("calib_bench: --simulate needs a GPU")
