@@ -284,7 +284,11 @@ YF_API int  yf_network_set_device(ai_handle network, int device);
  * 24 us instead of 34) -- and frames_per_wg = -1 returns to that.  A configured shape runs every batch size. */
 YF_API int  yf_network_configure(ai_handle network, int frames_per_wg, int waves_per_wg);
 /* Device-resident batch: d_in int8[n][56][56][3], d_out int8[n][7][7][18], both in HBM, d_in 4-byte aligned.
- * stream is a hipStream_t (NULL = default stream); asynchronous.  Returns n or <= 0 (error latched). */
+ * stream is a hipStream_t (NULL = default stream); asynchronous.  Returns n or <= 0 (error latched).
+ * LIMIT on n, for every entry point that runs the 56x56 int8 kernel on n frames (this one, _run_device_dump, _run_decode_device,
+ * _run_camera_device, _time_device, _time_stages, ai_network_run): the kernel counts frames and groups of frames in 32 bits, so one launch takes
+ * n <= INT32_MAX - 2 * frames_per_wg * workgroups (the launch's grid: the workgroups resident on the device, a few per compute unit).  A larger n is
+ * refused as a bad argument before anything is enqueued; split such a batch. */
 YF_API long yf_network_run_device(ai_handle network, const void* d_in, void* d_out, long n, void* stream);
 /* Same, and additionally dumps every fused stage's tensor (per-layer parity debugging, the counterpart of the
  * reference observer API, ai_platform_interface.h:684-731).  d_dump int8[n][yf_network_dump_bytes()]. */

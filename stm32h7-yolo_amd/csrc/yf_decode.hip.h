@@ -83,10 +83,13 @@ __device__ __forceinline__ void decode_frame(const int8_t* head, long frame, int
 // table look-up, ballot -- back to back before any record is assembled.  With the tables in global memory every chunk was two dependent
 // global round trips, six in a row per frame on one wave (2.7 us per launch of 4096 frames; tools/probe/decode_cost.py).
 typedef const __attribute__((address_space(3))) uint32_t* dec_lds_u32;
-__device__ __forceinline__ void decode_frame_lds(const int8_t* head, long frame, int lane, int mode, float w_scale, float h_scale,
+__device__ __forceinline__ void decode_frame_lds(const int8_t* head, int frame, int lane, int mode, float w_scale, float h_scale,
                                                  yf_det* __restrict__ dets, int* __restrict__ counts, int cap, uint32_t lds_tabs, int q_thr) {
-  yf_det* out = dets + frame * cap;
-  const float anc_w[3] = {9.f, 12.f, 22.f}, anc_h[3] = {14.f, 17.f, 21.f};
+  // the frame is wave-uniform: its records' base is scalar arithmetic, a record's place a 32-bit lane offset
+  char* out = reinterpret_cast<char*>(dets) + (size_t)(uint32_t)frame * (size_t)(uint32_t)cap * sizeof(yf_det);
+  // the anchors by selects: as arrays indexed by a lane's anchor they are two global loads (and 64-bit lane arithmetic) in front of every record
+  auto anc_w = [](int a) { return a == 0 ? 9.f : a == 1 ? 12.f : 22.f; };
+  auto anc_h = [](int a) { return a == 0 ? 14.f : a == 1 ? 17.f : 21.f; };
   auto sig = [&](int q) { return __uint_as_float(*(dec_lds_u32)(lds_tabs + 4u * (uint32_t)(q + 128))); };
   auto ex = [&](int q) { return __uint_as_float(*(dec_lds_u32)(lds_tabs + 1024u + 4u * (uint32_t)(q + 128))); };
   // phase 1: the confidence test on the QUANTISED value (the sigmoid table is monotonic: conf > 0.7 <=> q >= q_thr, the first table entry that
@@ -122,7 +125,7 @@ __device__ __forceinline__ void decode_frame_lds(const int8_t* head, long frame,
       d.frame = (int32_t)frame; d.anchor = (uint8_t)a; d.row = (uint8_t)row; d.col = (uint8_t)col;
       d.q_conf = (int8_t)q4[c]; d.conf = sig(q4[c]);
       const float cx = (sx + (float)col) * 8.f, cy = (sy + (float)row) * 8.f;
-      const float bw = ew * anc_w[a], bh = eh * anc_h[a];
+      const float bw = ew * anc_w(a), bh = eh * anc_h(a);
       if (mode == YF_DECODE_PY) {
         float x1 = cx - bw / 2, y1 = cy - bh / 2, x2 = cx + bw / 2, y2 = cy + bh / 2;
         x1 *= w_scale; x2 *= w_scale; y1 *= h_scale; y2 *= h_scale;
@@ -138,10 +141,10 @@ __device__ __forceinline__ void decode_frame_lds(const int8_t* head, long frame,
         if (y2 > 55) y2 = 55;
         d.x1 = dbl_wrap(x1); d.y1 = dbl_wrap(y1); d.x2 = dbl_wrap(x2); d.y2 = dbl_wrap(y2);
       }
-      out[pos[c]] = d;
+      *reinterpret_cast<yf_det*>(out + (uint32_t)pos[c] * (uint32_t)sizeof(yf_det)) = d;
     }
   }
-  if (lane == 0) counts[frame] = total;
+  if (lane == 0) counts[(uint32_t)frame] = total;
 }
 
 }  // namespace yfdec

@@ -519,6 +519,9 @@ struct DecodeArgs { void* dets; void* counts; int cap, mode; float w_scale, h_sc
 // batch takes 24 us instead of 34), larger batches the throughput shape.
 static const Variant* shape_for(const yf_engine* e, long n) { return (e->var_small && n <= SMALL_N) ? e->var_small : e->var; }
 
+// n <= INT32_MAX - 2 f grid: every group and frame number the fused kernel forms (yf_network.h states the limit) is an int
+static bool yf_frames_fit_int32(long n, int f, long grid) { return n <= (long)INT32_MAX - 2L * f * grid; }
+
 static int launch(yf_engine* e, const Variant* v, const void* d_in, void* d_out, void* d_dump, long n, hipStream_t s, int stop_stage = -1,
                   const DecodeArgs* dec = nullptr) {
   if (n <= 0) return YF_ENG_OK;
@@ -537,12 +540,14 @@ static int launch(yf_engine* e, const Variant* v, const void* d_in, void* d_out,
   if (e->grid_div > 1) grid = grid / e->grid_div > 0 ? grid / e->grid_div : 1;
 #endif
   if (grid > groups) grid = groups;
+  // the kernel counts groups and frames in 32 bits (yf_fused56.hip.h): its largest number is below n + 2 f grid (a workgroup's stride past the last group)
+  if (!yf_frames_fit_int32(n, v->f, grid)) { e->err = "too many frames for one launch (32-bit frame numbers inside the kernel)"; return YF_ENG_ERR_ARG; }
   prm.scratch = nullptr;
   yf_stream_scratch::Lease lease;    // marks its region on EVERY way out of this function (a failed launch must not keep a region acquired)
   if (v->park) {   // tail batching: a workgroup parks one group's T15 (f frames) in HBM, slot = blockIdx.x.  The region belongs to
                    // the launch STREAM: launches on one stream serialise, launches on different streams never share bytes.
     const size_t need = (size_t)grid * v->f * v->park;
-    if (need > e->park_region) { e->err = "tail scratch region too small for this kernel shape"; return YF_ENG_ERR_VARIANT; }
+    if (need > e->park_region || need > 0xffffffffu) { e->err = "tail scratch region too small for this kernel shape"; return YF_ENG_ERR_VARIANT; }   // (the kernel forms a slot's offset in 32 bits)
     HIPCHK(e, e->park.get(s, e->park_region, &lease));
     prm.scratch = lease.ptr;
   }

@@ -61,6 +61,16 @@ struct NetParams {
   char* scratch;          // tail batching: gridDim.x * F * TailBufs::T15_BYTES bytes (a workgroup parks one group's T15 there)
 };
 static_assert(sizeof(yf_table_index) <= YF_INDEX_RESERVED, "index does not fit its reserved slot");
+// Kernel arguments that a group needs once or twice (in, out, scratch, the decode's) are read from the kernarg segment WHERE THEY ARE USED, through a
+// pointer the compiler cannot see through: as plain prm.x they are loaded in the prologue and, live across the whole group loop, parked in VGPR lanes
+// (a v_readlane pair on the vector port per use).  A scalar load from the kernarg segment hits the scalar cache.
+typedef const __attribute__((address_space(4))) char* kargs_ptr;
+__device__ __forceinline__ kargs_ptr kargs_here() {
+  kargs_ptr p = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#define YF_ARG(FIELD) (*reinterpret_cast<const __attribute__((address_space(4))) decltype(NetParams::FIELD)*>(kargs_here() + offsetof(NetParams, FIELD)))
 
 // Issue priority per stage (s_setprio, 0..3), stage order: staging, conv2d_1, 3, 5, 6, pool_8 h, pool_8 v, conv2d_10, 12, 13, 15,
 // 17, 19, 23, then the thirteen tail stages.  See the kernel: a workgroup's priority FALLS as its group advances.
@@ -118,11 +128,14 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
   constexpr int FT = BATCH ? 2 * F : F;                  // frames per tail run
   typedef TailBufs<BATCH ? FRAME_STRIDE / 2 : FRAME_STRIDE> U;
   constexpr int OUT_ALL_BYTES = BATCH ? 0 : (F * OUT_FRAME_BYTES + 15) & ~15;      // BATCH stages the heads inside the tail sets
+  static_assert(std::is_same<decltype(&yoloface56_fused<F, NW, DUMP, CAM>), void (*)(const NetParams)>::value, "YF_ARG: NetParams is the kernel's only argument (kernarg offset 0)");
   uint8_t* luts = reinterpret_cast<uint8_t*>(smem);      // LUTs are addressed absolutely: the host checks that the kernel has no static LDS
   constexpr int PRE = v2::pre_bytes<F, tail_batch<DUMP>()>();   // LUTs | depthwise job tables | zeros | two constant ring slots | halo tables
   char* out_all = smem + PRE;
   char* frames = smem + PRE + OUT_ALL_BYTES;
-  long parked_first = -1;                                // first frame of the group whose T15 waits in the scratch
+  // Group and frame numbers are 32-bit inside the kernel (the scalar unit has no ordered 64-bit compare: as `long` their tests ran on the vector
+  // port); the host refuses a batch whose numbers would not fit (yf_engine.hip, launch).  Only the byte offset of a frame is widened, by scalar arithmetic.
+  const int n_frames = (int)prm.n;
   const int tid0 = threadIdx.x;
   const uint8_t* __restrict__ tab = prm.tab;
   int vz = 0;
@@ -133,11 +146,13 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
   // to conv2d_23, 1 for the first six tail stages, 0 for the rest.  The two workgroups of a CU are in different phases; the one
   // in the VALU-bound front stages then issues ahead of the one in the latency-bound tail, which only needs the slots left
   // over.  -6.8 % kernel time in-run (A/B 1.073 against no ladder); every placement of the three steps tried gave 6.0-7.3 %.
+  const __attribute__((address_space(1))) uint8_t* lut_src = (const __attribute__((address_space(1))) uint8_t*)(tab + PLAN.lut_off);
+  asm volatile("" : "+s"(lut_src));         // the LUTs' base as a scalar of its own: scalar base + 32-bit lane offset, no 64-bit lane arithmetic
   for (int i = tid0; i < v2::LUT_B / 16; i += NT)
-    reinterpret_cast<uint4*>(luts)[i] = reinterpret_cast<const uint4*>(tab + PLAN.lut_off)[i];
+    reinterpret_cast<v4u*>(luts)[i] = *(const __attribute__((address_space(1))) v4u*)(lut_src + (uint32_t)(16 * i));
   for (int i = tid0; i < v2::ZERO_B / 16; i += NT) reinterpret_cast<uint4*>(smem + v2::ZERO)[i] = uint4{0, 0, 0, 0};
   constexpr int DBG_LUT = PRE + OUT_ALL_BYTES + FRAME_BYTES + (F - 1) * FRAME_STRIDE;      // debug builds: LEAKY_RELU #43 alone, behind the frame arenas
-  if constexpr (DUMP) { if (tid0 < YF_DBG_LUT_BYTES / 16) reinterpret_cast<uint4*>(smem + DBG_LUT)[tid0] = reinterpret_cast<const uint4*>(tab + PLAN.lut_off + YF_N_LUT * 256 + YF_ADDLUT_BYTES)[tid0]; }
+  if constexpr (DUMP) { if (tid0 < YF_DBG_LUT_BYTES / 16) reinterpret_cast<v4u*>(smem + DBG_LUT)[tid0] = *(const __attribute__((address_space(1))) v4u*)(lut_src + (uint32_t)(YF_N_LUT * 256 + YF_ADDLUT_BYTES + 16 * tid0)); }
 #if !(defined(YF_LAB) && defined(YF_WHATIF_NO_PROLOGUE_TABLES))   // what-if (WRONG results): the ten table builds gone -- the bound for fetching host-built tables by LDS-DMA instead
   {   // job tables of the five depthwise geometries (offsets relative to the frame arenas)
     typedef v2::JobTabs<F, tail_batch<DUMP>()> JTS;
@@ -156,7 +171,15 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
   }
 #endif
 
-  const long n_groups = (prm.n + F - 1) / F;
+  // Wave-uniform values that the loop needs at one or two places are RECOMPUTED there by scalar arithmetic from a copy the compiler cannot see through
+  // (sfresh), not kept in an SGPR for the whole kernel: the kernel is short of SGPRs, and what does not fit is parked in VGPR lanes and comes back through
+  // the vector port.
+  auto sfresh = [](int v) { asm volatile("" : "+s"(v)); return v; };
+  auto n_groups = [&]() { return (int)((uint32_t)(sfresh(n_frames) + F - 1) / (uint32_t)F); };
+  int gstep = (int)gridDim.x;               // a plain scalar (as gridDim.x it is a pointer into the implicit arguments, re-read every group)
+  asm volatile("" : "+s"(gstep));
+  // the workgroup's slot of the tail scratch: one scalar base (the host bounds grid * F * T15_BYTES by the region's size, far below 4 GB)
+  auto park_slot = [&]() { return YF_ARG(scratch) + (uint32_t)(sfresh((int)blockIdx.x) * (F * TailBufs<FRAME_BYTES>::T15_BYTES)); };
   const AddK no_add = {};
   auto addctx = [&](int k) {
     const uint8_t* a = tab + offsetof(yf_table_index, add) + k * sizeof(yf_add);
@@ -179,15 +202,17 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
 #define YF_SYNC() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
 #endif
   // Stage calls: constants from an LDS ring slot, fetched one stage ahead by YF_FETCH
+  // (the thread index of a halo fill is laundered at the fill: its `tid < entries` mask is one compare, not an SGPR pair kept from the prologue's table build)
 #define YF_HALO(B, RING, FR, G, HOFF, WI, TID) \
-  v2::fill_halo_t<B, typename v2::HaloTabs<F, BATCH>::G, v2::HaloTabs<F, BATCH>::HOFF>(frames, load_halo_zp(tab, WI), TID)
-#define YF_FETCH(CS, WV, LN) v2::fetch_consts<CS>(tab, WV, LN)
+  do { int ht_ = TID; asm volatile("" : "+v"(ht_)); \
+       v2::fill_halo_t<B, typename v2::HaloTabs<F, BATCH>::G, v2::HaloTabs<F, BATCH>::HOFF>(frames, load_halo_zp(tab, WI), ht_); } while (0)
+#define YF_FETCH(CS, WV, LN) v2::fetch_consts_s<CS>(tab, WV, LN)
 #define YF_CONV1(WV, LN, CS) v2::conv1_2_stage<F, NW, CS>(frames, tab, WV, LN)
 #define YF_DENSE(FR, TPJ, KS, BW, IN, OUT, CH0, COUT, EPI, LUT, ADDB, DI, AD, WV, LN, CS) \
   v2::dense2_stage<FR, NW, TPJ, KS, BW, IN, OUT, CH0, COUT, EPI, LUT, ADDB, CS>(frames, out_all, tab, AD, WV, LN)
 #define YF_DW(FR, STRIDE, IN, OUT, C, LUT, WI, WV, LN, CS, JTOFF) v2::dw2_stage<FR, NW, STRIDE, IN, OUT, C, LUT, CS, v2::JobTabs<F, BATCH>::JTOFF>(frames, tab, WV, LN)
 #define YF_DUMP(BUF, C, OFF, ...) \
-  if constexpr (DUMP) { if (prm.dump) { dump_buf<BUF, C, F, NT>(frames, prm.dump, DS, DumpOffsets::OFF, first, prm.n, tid, ##__VA_ARGS__); YF_SYNC(); } }
+  if constexpr (DUMP) { if (prm.dump) { dump_buf<BUF, C, F, NT>(frames, prm.dump, DS, DumpOffsets::OFF, first, n_frames, tid, ##__VA_ARGS__); YF_SYNC(); } }
   int stage_no = 0;
 #define YF_STAGE_END() if constexpr (DUMP) { if (++stage_no == prm.stop_stage) continue; }
 #define YF_PRIO(K) stage_prio<K>()
@@ -195,20 +220,24 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
   // Fused box decode: the staged heads of group g stay in out_all until conv2d_53 of group g+1, so they are decoded by
   // the last F waves DURING conv2d_29 of the next group (a 4-job stage: those waves are idle there), off the critical
   // path; the workgroup's last group is decoded after the loop.
-  long prev_first = -1;
+  int prev_first = -1;
   auto decode_prev = [&](int w, int ln) {
-    if (prm.dets != nullptr && prev_first >= 0 && w >= NW - F && prev_first + (w - (NW - F)) < prm.n) {
+    if (prm.dets != nullptr && prev_first >= 0 && w >= NW - F && prev_first + (w - (NW - F)) < n_frames) {
       int dl = ln;
       asm volatile("" : "+v"(dl));              // keep the decode's per-lane index arithmetic out of the kernel-wide hoisted set
       yfdec::decode_frame(reinterpret_cast<const int8_t*>(out_all) + (w - (NW - F)) * OUT_FRAME_BYTES, prev_first + (w - (NW - F)), dl,
                           prm.mode, prm.w_scale, prm.h_scale, prm.dets, prm.counts, prm.cap);
     }
   };
-  for (long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
-    const long first = grp * F;
+  // The loop's state is ONE scalar: the group number, and in its sign bit whether the previous group's T15 waits in the scratch (tail batching; that
+  // group is grp - gstep, so its first frame need not be carried along).  The host's limit on n keeps grp + gstep below 2^31.
+  constexpr int PARKED = (int)0x80000000;
+  for (int st = blockIdx.x; (st & ~PARKED) < n_groups(); st += gstep) {
+    const int grp = st & ~PARKED;
+    const int first = grp * F;
 #ifdef YF_BARPROF
     bar_no = 0;
-    prof_on = !DUMP && prm.dump != nullptr && grp == (long)blockIdx.x + gridDim.x;
+    prof_on = !DUMP && prm.dump != nullptr && grp == (int)blockIdx.x + gstep;
 #endif
     // Loop-invariant code motion hoists the per-lane index arithmetic of every stage out of this loop and parks the
     // results in VGPRs for the whole kernel.  YF_LAUNDER selects stage groups (1 front 28x28, 2 middle 14x14, 4 tail
@@ -233,8 +262,8 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     YF_PRIO(0);
     int tid_s = tid0;
     asm volatile("" : "+v"(tid_s));         // the staging offsets are cheap: recomputed per group instead of parked in VGPRs for the whole kernel
-    if constexpr (CAM) stage_input_cam<F, NT>(frames, reinterpret_cast<const uint8_t*>(prm.in), first, prm.n, (int)uniform_u32(tab + offsetof(yf_table_index, in_zp)), tid_s);
-    else stage_input<F, NT>(frames, prm.in, first, prm.n, (int)uniform_u32(tab + offsetof(yf_table_index, in_zp)), tid_s);
+    if constexpr (CAM) stage_input_cam<F, NT>(frames, reinterpret_cast<const uint8_t*>(YF_ARG(in)), first, n_frames, (int)uniform_u32(tab + offsetof(yf_table_index, in_zp)), tid_s);
+    else stage_input<F, NT>(frames, YF_ARG(in), first, n_frames, (int)uniform_u32(tab + offsetof(yf_table_index, in_zp)), tid_s);
     YF_FETCH(0, W_f, L_f);                                                                            // conv2d_1's constants -> ring slot 0
     YF_HALO(B_T1, true, F, G1, H_T1, YF_W_DW3, tid_f);
     YF_SYNC();
@@ -333,13 +362,13 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     // alias analysis cannot tell the DMA's destination from the stage's buffers, so the transfer overlaps less than it could).
     // One wave-instruction moves 64 x 16 contiguous bytes.
     if constexpr (BATCH) {
-      if (parked_first >= 0) {
+      if (st < 0) {
         constexpr int PV = TailBufs<FRAME_BYTES>::T15_BYTES / 16, WI = (PV + 63) / 64;      // vectors / wave-instructions per frame
-        const char* park = prm.scratch + (long)blockIdx.x * (F * PV * 16);
+        const char* park = park_slot();                                               // one scalar base, 32-bit lane offsets
         for (int j = W_m; j < F * WI; j += NW) {
           const int f = j / WI, k0 = (j - f * WI) * 64;
           if (k0 + L_m < PV)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)(park + (f * PV + k0 + L_m) * 16),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)(park + (uint32_t)((f * PV + k0 + L_m) * 16)),
                                              (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(PRE + (2 * f + 1) * U::T15::FS + 16 * k0),
                                              16, 0, 0);
         }
@@ -356,32 +385,35 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     // first group of a pair parks its T15 (5.4 KB per frame) in a per-workgroup HBM scratch and skips the tail; the second
     // group fetches it back into the odd tail sets -- set f of the tail sits at f * FRAME_BYTES / 2, so the even sets ARE the
     // arenas' own T15 -- and runs the tail for both.  A workgroup's last group runs the tail alone when it has no partner.
-    long odd_first = -1;                          // first frame of the odd sets (the parked group), -1: none
+    int odd_first = -1;                           // first frame of the odd sets (the parked group), -1: none
     if constexpr (BATCH) {
       constexpr int V = U::T15_BYTES / 16;
-      uint4* park = reinterpret_cast<uint4*>(prm.scratch) + (long)blockIdx.x * (F * V);
-      if (parked_first < 0 && grp + gridDim.x < n_groups) {
+      static_assert(U::T15_BYTES == TailBufs<FRAME_BYTES>::T15_BYTES, "one slot size for the park stores and the DMA back");
+      if (st >= 0 && grp + gstep < n_groups()) {
+        char* park = park_slot();
+        __builtin_assume(tid_t >= 0 && tid_t < NT);       // (the first pass needs no `i < F * V` mask where F * V >= NT)
         for (int i = tid_t; i < F * V; i += NT) {
           const int f = i / V, k = i - f * V;
-          park[i] = *reinterpret_cast<const uint4*>(frames + f * FRAME_STRIDE + 16 * k);
+          *reinterpret_cast<uint4*>(park + (uint32_t)(16 * i)) = *reinterpret_cast<const uint4*>(frames + f * FRAME_STRIDE + 16 * k);
         }
-        parked_first = first;
+        st |= PARKED;
         continue;
       }
-      if (parked_first >= 0) {                  // its T15 is already in the odd sets (LDS-DMA issued before conv2d_23)
-        odd_first = parked_first;
-        parked_first = -1;
+      if (st < 0) {                             // its T15 is already in the odd sets (LDS-DMA issued before conv2d_23)
+        odd_first = (grp - gstep) * F;
+        st &= ~PARKED;
       }
     }
     // frame number of tail set f (BATCH: even sets = this group, odd sets = the parked one), -1 = nothing to write
-    auto frame_of = [&](int f) -> long {
-      long id = first + f;
-      if constexpr (BATCH) id = (f & 1) ? (odd_first >= 0 ? odd_first + (f >> 1) : -1) : first + (f >> 1);
-      return id < prm.n ? id : -1;
+    const int first_t = sfresh(grp) * F;            // `first` again, for the tail
+    auto frame_of = [&](int f) -> int {
+      int id = first_t + f;
+      if constexpr (BATCH) id = (f & 1) ? (odd_first >= 0 ? odd_first + (f >> 1) : -1) : first_t + (f >> 1);
+      return id < n_frames ? id : -1;
     };
 #define YF_DUMP_T(BUF, C, OFF, ...) \
   if constexpr (DUMP) { if (prm.dump) { if constexpr (BATCH) dump_sets<BUF, C, FT, NT>(frames, prm.dump, DS, DumpOffsets::OFF, frame_of, tid, ##__VA_ARGS__); \
-                                        else dump_buf<BUF, C, FT, NT>(frames, prm.dump, DS, DumpOffsets::OFF, first, prm.n, tid, ##__VA_ARGS__); \
+                                        else dump_buf<BUF, C, FT, NT>(frames, prm.dump, DS, DumpOffsets::OFF, first, n_frames, tid, ##__VA_ARGS__); \
                                         YF_SYNC(); } }
     YF_PRIO(14);
     YF_FETCH(12, W_t, L_t);
@@ -460,14 +492,15 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     YF_FETCH(23, W_t, L_t);
     // the decode's two look-up tables (2 KB) -> the first bytes of the frame arenas, dead since conv2d_47 (T15 / T30 of set 0), two stages ahead of
     // the decode: the barrier behind this stage waits for the transfer, the one behind conv2d_53 would do so on the critical path
-    if (BATCH && prm.dets != nullptr && W_t < 2) {
+    if (BATCH && YF_ARG(dets) != nullptr && W_t < 2) {
       int dl = L_t;
       asm volatile("" : "+v"(dl));
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(W_t == 0 ? yfdec::d_sig_bits : yfdec::d_exp_bits) + 16 * dl;
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(sfresh(W_t) == 0 ? yfdec::d_sig_bits : yfdec::d_exp_bits);   // scalar base, 32-bit lane offset
+      const uint32_t voff = 16u * (uint32_t)dl;
       const uint32_t dst = (uint32_t)(PRE + OUT_ALL_BYTES + 1024 * W_t);
       uint32_t keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(voff), "s"(src), "s"(dst) : "memory");
     }
     YF_DENSE(FT, 2, 3, 16, typename U::T20, typename U::T33, 0, 32, EPI_LUT, YF_L_LEAKY52, typename U::T33, YF_D_C51, no_add, W_t, L_t, 22);   // conv2d_51
     YF_SYNC(); YF_DUMP_T(typename U::T33, 32, T33)
@@ -477,11 +510,10 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
       YF_DENSE(FT, 1, 2, 16, typename U::T33, typename U::T33, 0, 18, EPI_HEAD, 0, typename U::T33, YF_D_C53, no_add, W_t, L_t, 23);   // conv2d_53
       YF_SYNC();
       // head: F*882 contiguous bytes -> HBM, 2-byte granules (882 is not a multiple of 4)
-      const long valid = min((long)F, prm.n - first);
-      const int n16 = (int)(valid * (OUT_FRAME_BYTES / 2));
-      uint16_t* dst = reinterpret_cast<uint16_t*>(prm.out + first * OUT_FRAME_BYTES);
+      const int n16 = min(F, n_frames - first) * (OUT_FRAME_BYTES / 2);
+      int8_t* dst = YF_ARG(out) + (size_t)(uint32_t)first * OUT_FRAME_BYTES;
       const uint16_t* srcp = reinterpret_cast<const uint16_t*>(out_all);
-      for (int i = tid; i < n16; i += NT) dst[i] = srcp[i];
+      for (int i = tid; i < n16; i += NT) *reinterpret_cast<uint16_t*>(dst + (uint32_t)(2 * i)) = srcp[i];
       prev_first = first;
     } else {
       YF_DENSE(FT, 1, 2, 16, typename U::T33, typename U::HEAD, 0, 18, EPI_HEAD_LDS, 0, typename U::T33, YF_D_C53, no_add, W_t, L_t, 23);   // conv2d_53
@@ -489,22 +521,32 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
       // heads: 882 bytes per frame from its set -> HBM, 2-byte granules; the boxes of set w are decoded by wave w meanwhile
       constexpr int H16 = OUT_FRAME_BYTES / 2;
       // with a decode the first FT waves decode (one frame each) while the other waves copy the heads; without one every wave copies
-      const bool split = prm.dets != nullptr && FT < NW;
+      yf_det* const dets = YF_ARG(dets);
+      int8_t* const heads = YF_ARG(out);
+      const bool split = dets != nullptr && FT < NW;
       const int c0 = split ? tid_t - FT * 64 : tid_t, cstep = split ? NT - FT * 64 : NT;
       if (!split || W_t >= FT) {
-        for (int i = c0; i < FT * H16; i += cstep) {
-          const int f = i / H16, k = i - f * H16;
-          const long id = frame_of(f);
-          if (id >= 0) reinterpret_cast<uint16_t*>(prm.out + id * OUT_FRAME_BYTES)[k] = *reinterpret_cast<const uint16_t*>(frames + f * U::HEAD::FS + U::HEAD::OFF + 2 * k);
+        // set by set: a set's frame number is wave-uniform, so its head's address is one scalar base plus the 32-bit lane offset 2 k
+#pragma unroll
+        for (int f = 0; f < FT; ++f) {
+          const int id = frame_of(f);
+          if (id >= 0) {
+            int8_t* dst = heads + (size_t)(uint32_t)id * OUT_FRAME_BYTES;
+            for (int k = c0; k < H16; k += cstep)
+              *reinterpret_cast<uint16_t*>(dst + (uint32_t)(2 * k)) = *reinterpret_cast<const uint16_t*>(frames + f * U::HEAD::FS + U::HEAD::OFF + 2 * k);
+          }
         }
       }
       for (int f = W_t; f < FT; f += NW) {
-        const long id = frame_of(f);
-        if (prm.dets != nullptr && id >= 0) {
+        const int id = frame_of(f);
+        if (dets != nullptr && id >= 0) {
           int dl = L_t;
           asm volatile("" : "+v"(dl));
-          yfdec::decode_frame_lds(reinterpret_cast<const int8_t*>(frames + f * U::HEAD::FS + U::HEAD::OFF), id, dl, prm.mode, prm.w_scale, prm.h_scale, prm.dets, prm.counts, prm.cap,
-                                  (uint32_t)(PRE + OUT_ALL_BYTES), prm.q_thr);
+          const kargs_ptr ka = kargs_here();          // one copy of the pointer for the decode's seven arguments
+#define YF_ARG_AT(FIELD) (*reinterpret_cast<const __attribute__((address_space(4))) decltype(NetParams::FIELD)*>(ka + offsetof(NetParams, FIELD)))
+          yfdec::decode_frame_lds(reinterpret_cast<const int8_t*>(frames + f * U::HEAD::FS + U::HEAD::OFF), id, dl, YF_ARG_AT(mode), YF_ARG_AT(w_scale), YF_ARG_AT(h_scale), dets,
+                                  YF_ARG_AT(counts), YF_ARG_AT(cap), (uint32_t)(PRE + OUT_ALL_BYTES), YF_ARG_AT(q_thr));
+#undef YF_ARG_AT
         }
       }
     }
@@ -514,6 +556,7 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     const int tid = tid0, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     decode_prev(wave, lane);
   }
+#undef YF_ARG
 #undef YF_HALO
 #undef YF_FETCH
 #undef YF_CONV1

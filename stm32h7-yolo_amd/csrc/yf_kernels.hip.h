@@ -474,7 +474,7 @@ YF_STAGE_FN void fill_halo(char* frames, int zp, int tid) {
 // masking is needed.
 __device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, int sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }  // ({hi,lo} >> sh)[31:0]
 template <int F, int NT>
-YF_STAGE_FN void stage_input(char* frames, const int8_t* __restrict__ in, long first_frame, long n_frames,
+YF_STAGE_FN void stage_input(char* frames, const int8_t* __restrict__ in, int first_frame, int n_frames,
                                             int zp, int tid) {
   const uint32_t hv = (uint32_t)(zp & 255) * 0x01010101u;
   constexpr int RSW = B_IN::RS, HH = B_IN::H, WQ = B_IN::W / 4;    // dwords per halo'd row, rows, 4-pixel items per row
@@ -486,9 +486,8 @@ YF_STAGE_FN void stage_input(char* frames, const int8_t* __restrict__ in, long f
     *reinterpret_cast<uint32_t*>(frames + f * B_IN::FS + B_IN::OFF + idx * 4) = hv;
   }
   // frames past the end of the batch re-read the last one; everything per item is 32-bit arithmetic off one scalar base
-  const long rest = n_frames - 1 - first_frame;
-  const int lastf = __builtin_amdgcn_readfirstlane((int)(rest < (long)(F - 1) ? rest : (long)(F - 1)));
-  const int8_t* base = in + first_frame * IN_FRAME_BYTES;
+  const int lastf = min(n_frames - 1 - first_frame, F - 1);                  // wave-uniform, scalar arithmetic (frame numbers are 32-bit inside the kernels)
+  const int8_t* base = in + (size_t)(uint32_t)first_frame * IN_FRAME_BYTES;   // only the byte offset of the group is 64-bit
   static_assert(RSW == B_IN::W + 4 && B_IN::S == 4, "dst = OFF + 16 * (r + y + RSW/4 + 1) relies on rows of W + 4 dwords");
   // ALL loads first (items past the end re-read the last one), then the shuffles and stores.  One loop with an early exit made every
   // iteration wait for its own load before the next one was issued -- three to four global-load latencies in a row per group (-1.1 %).
@@ -537,7 +536,7 @@ __device__ __forceinline__ uint32_t cam_pixel(uint32_t s0, uint32_t s1) {     //
   return (((rs & 0x7Cu) << 1) | ((gs & 0xFCu) << 8) | ((bs & 0x7Cu) << 17)) ^ 0x00808080u;
 }
 template <int F, int NT>
-YF_STAGE_FN void stage_input_cam(char* frames, const uint8_t* __restrict__ cam, long first_frame, long n_frames, int zp, int tid) {
+YF_STAGE_FN void stage_input_cam(char* frames, const uint8_t* __restrict__ cam, int first_frame, int n_frames, int zp, int tid) {
   const uint32_t hv = (uint32_t)(zp & 255) * 0x01010101u;
   constexpr int RSW = B_IN::RS, HH = B_IN::H, WQ = B_IN::W / 4;
   constexpr int PER_FRAME = HH * WQ, TOTAL = F * PER_FRAME;
@@ -546,9 +545,8 @@ YF_STAGE_FN void stage_input_cam(char* frames, const uint8_t* __restrict__ cam, 
     const int idx = k < RSW ? k : (k - RSW + 1) * RSW + 3;
     *reinterpret_cast<uint32_t*>(frames + f * B_IN::FS + B_IN::OFF + idx * 4) = hv;
   }
-  const long rest = n_frames - 1 - first_frame;
-  const int lastf = __builtin_amdgcn_readfirstlane((int)(rest < (long)(F - 1) ? rest : (long)(F - 1)));
-  const uint8_t* base = cam + first_frame * CAM_FRAME_BYTES;
+  const int lastf = min(n_frames - 1 - first_frame, F - 1);
+  const uint8_t* base = cam + (size_t)(uint32_t)first_frame * CAM_FRAME_BYTES;
   // items in PAIRS: the four 16-byte loads of two items are issued before the first is used (one loop iteration per item waited for its own
   // two loads before the next item's were issued: up to four global-load latencies in a row per group, as in stage_input before round 3)
   constexpr int ITERS = (TOTAL + NT - 1) / NT;
@@ -618,6 +616,7 @@ __device__ __forceinline__ void pool8_sweep(int o0, LOADC loadc, STORE store) {
 template <int F, int NT>
 YF_STAGE_FN void pool8_h(char* frames, int tid) {
   constexpr int NO = 5, OW = B_HB::W, IH = B_T4::H, NCH = (OW + NO - 1) / NO;   // output chunks, the last shifted left
+  __builtin_assume(tid >= 0 && tid < NT);        // every thread has a first item: no mask for it (it was an SGPR pair kept for the whole kernel)
   for (int i = tid; i < F * IH * NCH * 5; i += NT) {
     const int cg = i % 5; int t = i / 5;
     const int k = t % NCH; t /= NCH;
@@ -634,6 +633,7 @@ template <int F, int NT, bool STASH = false>      // STASH (debug builds): the r
 YF_STAGE_FN void pool8_v(char* frames, int tid) {
   constexpr int NO = 5, OW = B_HB::W, OH = B_T14::H, NCH = (OH + NO - 1) / NO;   // the last chunk shifted up
   static_assert(OH >= NO, "column shorter than one sweep");
+  __builtin_assume(tid >= 0 && tid < NT);
   for (int i = tid; i < F * OW * NCH * 5; i += NT) {
     const int cg = i % 5; int t = i / 5;
     const int k = t % NCH; t /= NCH;
@@ -701,6 +701,25 @@ __device__ __forceinline__ void fetch_consts(const uint8_t* __restrict__ tab, in
       uint32_t keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+    }
+  }
+}
+// The 56x56 kernel's form: the table blob's base stays ONE SGPR pair and the block's place is a 32-bit lane offset (saddr addressing) -- two VALU
+// instructions per fetch and no per-stage 64-bit pointer for loop-invariant code motion to hoist out of the group loop (24 of them were 48 SGPRs,
+// parked in VGPR lanes and read back in front of every fetch).
+template <int CS>
+__device__ __forceinline__ void fetch_consts_s(const uint8_t* __restrict__ tab, int wave, int lane) {
+  constexpr int BYTES = PLAN.vb_bytes[CS], NCHUNK = (BYTES + 1023) / 1024;
+  asm volatile("" : "+s"(wave));            // ... and neither is `wave < NCHUNK`, which as one condition shared by the stages is an SGPR pair for the whole loop
+  if (wave < NCHUNK) {
+    asm volatile("" : "+v"(lane));
+    const int off = wave * 1024 + lane * 16;
+    if (off < BYTES) {
+      const uint32_t voff = (uint32_t)(PLAN.vb_off[CS] + off);
+      const uint32_t dst = (uint32_t)(Lay56::slot(CS) + wave * 1024);
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(voff), "s"(tab), "s"(dst) : "memory");
     }
   }
 }

@@ -22,7 +22,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 FROZEN = os.path.join(ROOT, "profiles", "isa_hashes_frozen.txt")
 
 
-def hashes(lib):
+def disassemble(lib, resources=None):
+    """{kernel: [instruction, ...]} of every gfx950 kernel in `lib`; `resources` (a dict) also receives {kernel: {sgpr_count, vgpr_count,
+    private_segment_fixed_size, ...}} from the code objects' metadata notes."""
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
@@ -35,6 +37,11 @@ def hashes(lib):
             subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
                                   stderr=subprocess.DEVNULL)
             dis += subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], text=True)
+            if resources is not None:
+                notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+                for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+                    resources[name] = {k: int(v) for k, v in re.findall(r"\.(sgpr_count|vgpr_count|private_segment_fixed_size|sgpr_spill_count|vgpr_spill_count):\s+(\d+)", blk)}
     out, cur, getpc = {}, None, -9
     for ln in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(.+)>:", ln)
@@ -54,7 +61,11 @@ def hashes(lib):
         ends = [i for i, ins in enumerate(body) if ins.startswith("s_endpgm")]
         if ends:
             del body[ends[-1] + 1:]
-    return sorted((name, hashlib.sha256("\n".join(body).encode()).hexdigest()[:16], len(body)) for name, body in out.items() if name.startswith("_Z"))
+    return {name: body for name, body in out.items() if name.startswith("_Z")}
+
+
+def hashes(lib):
+    return sorted((name, hashlib.sha256("\n".join(body).encode()).hexdigest()[:16], len(body)) for name, body in disassemble(lib).items())
 
 
 def main():
