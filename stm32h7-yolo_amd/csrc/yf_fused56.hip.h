@@ -357,11 +357,15 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
     YF_STAGE_END()
     YF_PRIO(13);
     // BATCH: the parked group's T15 goes from the scratch straight into the odd tail sets by LDS-DMA (no registers), issued
-    // here -- their bytes (T9/T11's old slots) are dead once conv2d_19 is through.  The wait that guards it is the explicit
+    // here -- their bytes (the back of T9 and T11, [17088, 22496) of an arena) are dead once conv2d_19 is through.  The wait that guards it is the explicit
     // s_waitcnt vmcnt(0) in front of the barrier behind conv2d_23 (this toolchain also waits at conv2d_23's first LDS access: its
     // alias analysis cannot tell the DMA's destination from the stage's buffers, so the transfer overlaps less than it could).
     // One wave-instruction moves 64 x 16 contiguous bytes.
     if constexpr (BATCH) {
+#if !(defined(YF_LAB) && defined(YF_WHATIF_FS))
+      static_assert(U::T15::FS >= U::T15_BYTES && B_T9::OFF <= U::T15::FS && U::T15::FS + U::T15_BYTES <= B_T14::OFF,
+                    "the odd sets' T15 lands on T9 / T11 (dead), clear of conv2d_23's input (concat_22) and output (the even sets' T15)");
+#endif
       if (st < 0) {
         constexpr int PV = TailBufs<FRAME_BYTES>::T15_BYTES / 16, WI = (PV + 63) / 64;      // vectors / wave-instructions per frame
         const char* park = park_slot();                                               // one scalar base, 32-bit lane offsets

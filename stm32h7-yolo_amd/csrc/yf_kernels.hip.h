@@ -34,6 +34,7 @@
 #define YF_LAUNDER 0       /* laboratory builds may set it (profiles/r04_whatif.txt): stage groups whose thread index is recomputed per group instead of parked */
 #endif
 #define YF_ROW_SKEW 4      /* bytes of row skew in the depthwise inputs with 8- / 40-byte pixels (T1, T19: Buf::SK) */
+#define YF_T8_ROW_SKEW 32  /* bytes of row skew in T8 (36-byte pixels, conv2d_15's input): a row pitch of 608 B = 152 dwords, see Buf::SK */
 namespace YF_NS {
 
 // Stage functions are inlined (measured: real calls remove the scratch spills of the 128-VGPR builds but cost
@@ -74,6 +75,10 @@ constexpr int BUF_FS = 0;                      // one frame per workgroup
 // with 8- or 40-byte pixels a row's 16 lanes cover the 16 even LDS banks, and an even row pitch (in dwords) puts the next row on the
 // same banks -- a 2-way conflict on every tap read.  One dword of skew per row makes the pitch odd: rows alternate between the even
 // and the odd banks and the reads are conflict-free (T1: conv2d_3's input; T19: the input of conv2d_32 / 38 / 49).
+// T8 (36-byte pixels, conv2d_15's input): a row's 16 lanes are 9 dwords apart and cover the 16 banks {9c mod 32}; the two-frame kernel's row walk puts
+// the two lane groups of a half TWO rows apart, and two rows of 576 B are 288 dwords = 0 mod 32 -- the same 16 banks.  32 bytes of skew make two rows 304
+// dwords = 16 mod 32, and {9c + 16} is the complement of {9c}.  (The one-frame kernel's groups are ONE row apart: 152 dwords = 24 mod 32 instead of 16,
+// lanes c >= 8 of the upper row then meet lanes c - 8 of the lower one.  No pitch serves both walks: the complement needs an offset of exactly 16.)
 template <int OFF_, int W_, int H_, int S_, int RS_, int PT_, int PL_, int FS_ = BUF_FS, int SK_ = 0>
 struct Buf {
   static constexpr int OFF = OFF_, W = W_, H = H_, S = S_, RS = RS_, PT = PT_, PL = PL_, FS = FS_, SK = SK_;
@@ -84,6 +89,18 @@ struct Buf {
     else { const int y = p / W_; return at(y, p - y * W_); }
   }
 };
+// The LDS bank rule, evaluated at compile time on the byte addresses of the 32 lanes that one pass of a read serves: ds_read_b32 takes the two 32-lane
+// halves of a wave one after the other, bank = dword mod 32; ds_read_b64 likewise with bank PAIR = (dword / 2) mod 32 of an 8-byte aligned address.
+// Two lanes are free of each other on different banks or on the SAME address (a broadcast).  WIDTH = 4 or 8 bytes per lane.
+template <int WIDTH>
+constexpr bool lds_conflict_free(const int (&addr)[32]) {
+  for (int i = 0; i < 32; ++i) {
+    if (addr[i] % WIDTH != 0) return false;
+    for (int j = 0; j < i; ++j)
+      if (addr[i] != addr[j] && (addr[i] / WIDTH) % 32 == (addr[j] / WIDTH) % 32) return false;
+  }
+  return true;
+}
 
 #ifndef YF_H0
 #define YF_H0 56                               // input height = width; the network is fully convolutional
@@ -103,9 +120,9 @@ typedef Buf<16832, 14, 28, 20, 14, 0, 0> B_HB;    // pool_8 horizontal pass [28 
 typedef Buf<24672, 14, 14, 48, 14, 0, 0> B_T14;   // concat_22: pool [0,18) | conv [20,38)
 typedef Buf<16832, 14, 14, 32, 14, 0, 0> B_T6;    // conv2d_10 out
 typedef Buf<    0, 14, 14,  8, 14, 0, 0> B_T7;    // conv2d_12 out
-typedef Buf< 1568, 14, 14, 36, 16, 1, 1> B_T8;    // conv2d_13 out, halo ring
-typedef Buf<10784, 14, 14, 48, 14, 0, 0> B_T9;    // conv2d_15 out
-typedef Buf<20192, 14, 14,  8, 14, 0, 0> B_T11;   // eltwise_18 out
+typedef Buf< 1568, 14, 14, 36, 16, 1, 1, BUF_FS, YF_T8_ROW_SKEW> B_T8;    // conv2d_13 out, halo ring; 16 rows of 608 bytes
+typedef Buf<11296, 14, 14, 48, 14, 0, 0> B_T9;    // conv2d_15 out
+typedef Buf<20704, 14, 14,  8, 14, 0, 0> B_T11;   // eltwise_18 out
 typedef Buf<    0, 14, 14, 24, 15, 1, 1> B_T15;   // conv2d_23 out, top/left halo
 typedef Buf< 5408,  7,  7, 48,  7, 0, 0> B_T30;   // concat_46: pool [0,24) | conv [24,48)
 typedef Buf< 7760,  7,  7, 32,  7, 0, 0> B_T17;   // conv2d_27 out
@@ -925,6 +942,23 @@ YF_STAGE_FN void dense2_stage(char* frames, char* out_all, const uint8_t* __rest
 }
 
 // ---- conv2d_1 (see conv1_stage), constants from ring slot CS
+// The b64 reads of its tap pairs under the bank rule (lds_conflict_free): every run of 32 consecutive pixels that a half-wave takes -- runs that wrap into the
+// next row and run across the frame boundary included, the last run padded with its last pixel as the stage pads it -- on distinct bank pairs.  ARENA0 = where
+// the frame arenas start in LDS (it only has to keep the pairs 8-byte aligned).  A kernel row ky adds ky * RS dwords -- with an even RS whole bank pairs -- to
+// every lane alike, so kernel row 0 stands for all three.
+template <int F, class IN, class OUT>
+constexpr bool conv1_pairs_conflict_free(int arena0) {
+  if (IN::RS % 2 != 0) return false;
+  for (int q0 = 0; q0 < F * OUT::P; q0 += 32) {
+    int addr[32] = {};
+    for (int l = 0; l < 32; ++l) {
+      const int q = q0 + l < F * OUT::P ? q0 + l : F * OUT::P - 1, f = q / OUT::P, p = q - f * OUT::P, oy = p / OUT::W, ox = p - oy * OUT::W;
+      addr[l] = arena0 + f * IN::FS + IN::OFF + 4 * (2 * oy * IN::RS + 2 * ox + 4);
+    }
+    if (!lds_conflict_free<8>(addr)) return false;
+  }
+  return true;
+}
 template <int F, int NW, int CS, class IN = B_IN, class OUT = B_T1, class LAY = Lay56>
 YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, int wave, int lane) {
   constexpr int P = OUT::P, W1 = OUT::W, RSW = IN::RS, TOT = F * P;
@@ -934,12 +968,20 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
   const bool a_on = (c >> 2) == g;
   const uint32_t a_addr = a_on ? (uint32_t)(SLOT + (c & 3) * YF_CONV1_KROW) : (uint32_t)LAY::ZERO;
   const uint8_t* sc = tab + PLAN.sb_off[CS];
+  static_assert(RSW % 2 == 0 && IN::OFF % 8 == 0 && IN::FS % 8 == 0, "the tap pairs (kx = 1, 2) of a kernel row are 8-byte aligned");
   v4i a[2][3];
   PassV pv[2];
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
+    // The table's k order is tap t = 3 ky + kx in dword t of the row (yf_tables.h).  The MFMAs run on the order in which the taps are READ:
+    // {t00, t10, t01 t02} {t11 t12, t21 t22} {t20} -- the pairs (kx = 1, 2) of a kernel row in dwords [2,3] / [0,1] / [2,3] of a B operand (even-aligned
+    // register pairs).  Six register moves per pass, once per stage and wave; a lane outside its row block reads zeros either way.
+    v4i t[3];
 #pragma unroll
-    for (int ks = 0; ks < 3; ++ks) a[ps][ks] = lds_v4i(a_addr + (uint32_t)(ps * 4 * YF_CONV1_KROW + 16 * ks));
+    for (int ks = 0; ks < 3; ++ks) t[ks] = lds_v4i(a_addr + (uint32_t)(ps * 4 * YF_CONV1_KROW + 16 * ks));
+    a[ps][0] = v4i{t[0][0], t[0][3], t[0][1], t[0][2]};
+    a[ps][1] = v4i{t[1][0], t[1][1], t[1][3], t[2][0]};
+    a[ps][2] = v4i{t[1][2], t[2][1], t[2][2], t[2][3]};          // dwords 1..3 of the table's third step are zero
     pv[ps].m2 = lds_v4u((uint32_t)(PV + ps * 32));
     pv[ps].zr = lds_v4u((uint32_t)(PV + ps * 32 + 16));
   }
@@ -954,11 +996,14 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
     const int p = q - f * P;
     const int oy = DivW<W1>::div(p), ox = p - oy * W1;
     char* fbase = frames + f * IN::FS;
-    // tap (ky,kx) of output (oy,ox) = IN[2oy-1+ky][2ox-1+kx] = halo'd dword (2oy+ky)*RSW + 2ox+kx+3
+    // tap (ky,kx) of output (oy,ox) = IN[2oy-1+ky][2ox-1+kx] = halo'd dword (2oy+ky)*RSW + 2ox+kx+3.  Taps kx = 1, 2 of a kernel row start at the EVEN
+    // dword 2ox+4: one ds_read_b64, whose 32 lanes x 2 dwords cover one 64-bank row exactly (conv1_pairs_conflict_free above); tap kx = 0 stays a b32 read.
+    // Nine b32 reads were 2-way conflicts throughout (pixels ox and ox + 16 of a half-wave share a bank).  Plain C++ loads: the compiler sees the operands.
     const uint32_t* src = reinterpret_cast<const uint32_t*>(fbase + IN::OFF) + (2 * oy * RSW + 2 * ox + 3);
-    const v4i b0 = {(int)src[0], (int)src[1], (int)src[2], (int)src[RSW]};
-    const v4i b1 = {(int)src[RSW + 1], (int)src[RSW + 2], (int)src[2 * RSW], (int)src[2 * RSW + 1]};
-    const v4i b2 = {(int)src[2 * RSW + 2], any_value(), any_value(), any_value()};
+    const uint2 r0 = *reinterpret_cast<const uint2*>(src + 1), r1 = *reinterpret_cast<const uint2*>(src + RSW + 1), r2 = *reinterpret_cast<const uint2*>(src + 2 * RSW + 1);
+    const v4i b0 = {(int)src[0], (int)src[RSW], (int)r0.x, (int)r0.y};
+    const v4i b1 = {(int)r1.x, (int)r1.y, (int)r2.x, (int)r2.y};
+    const v4i b2 = {(int)src[2 * RSW], any_value(), any_value(), any_value()};
     char* dstpix = fbase + OUT::at(oy, ox);
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
@@ -983,7 +1028,7 @@ YF_STAGE_FN void conv1_2_stage(char* frames, const uint8_t* __restrict__ tab, in
 // last segment up (rows computed twice give the same bytes).  The stages of the 56x56 kernel with two frames per group:
 //   conv2d_3   28x28 stride 1   R = 7, FG = 1: one block of 4 x 7 rows; 8 jobs for 8 waves, as 56 jobs of one row before
 //   conv2d_15  14x14 stride 1   R = 2, FG = 1: blocks of 4 x 2 rows at rows 0 and 6 (16 rows computed, as before); 36 jobs, the busiest wave has 10 rows instead
-//                               of 9, and lanes g = 0, 1 are 288 dwords apart (2-way bank conflict) -- measured faster anyway: profiles/EXPERIMENTS.md, round 7
+//                               of 9 (profiles/EXPERIMENTS.md, round 7); lanes g = 0, 1 are two rows = 304 dwords apart, on complementary banks (Buf::SK, round 10)
 //   conv2d_10  14x14 stride 2   R = 7, FG = 2: a job is both frames x rows 0-6 / 7-13 of one channel group: 5 jobs for the 5 waves beside pool_8 h, 7 rows and
 //                               45 tap dwords per lane instead of 8 rows (16 computed for 14) and 72
 //   conv2d_27   7x7  stride 2   R = 4, FG = 2 (four frames per tail run, two more across a row's 16 lanes): a job is four frames x rows 0-3 / 3-6: 6 jobs
@@ -1013,7 +1058,22 @@ struct DwGeo {
   static_assert(IN::FS == OUT::FS, "one frame stride per stage");
   static_assert((H >= BR || (R > 1 && H >= R)) && (W >= 16 || W * FL <= 16) && F % (FL * FG) == 0 && RG * FG == 4, "tile shape");
   // first row (within the job's block) of row segment rs: a block taller than the frame (R > 1 only) moves its last segments up, as the last block of a frame is
+  static constexpr int seg_row_c(int rs) { return BR > H && rs * R > H - R ? H - R : rs * R; }
   __device__ static __forceinline__ int seg_row(int rs) { return BR > H ? min(rs * R, H - R) : rs * R; }
+  // The b32 tap reads of the stage under the bank rule (lds_conflict_free): lane (g, c) of dw2_stage reads at lane_in + a job's, a channel group's and a
+  // tap's offset, which every lane shares -- so the 32 lanes of each half must be free of each other on lane_in alone (frame, row segment, column).
+  static constexpr bool taps_conflict_free() {
+    for (int half = 0; half < 2; ++half) {
+      int addr[32] = {};
+      for (int l = 0; l < 32; ++l) {
+        const int g = 2 * half + l / 16, c = l % 16;
+        const int fl = FL == 2 ? c / 8 : 0, xc = FL == 2 ? c % 8 : c, xl = xc < W - 1 ? xc : W - 1;
+        addr[l] = (fl + FL * (g / RG)) * IN::FS + seg_row_c(g % RG) * STRIDE * IN::ROWB + xl * STRIDE * IN::S;
+      }
+      if (!lds_conflict_free<4>(addr)) return false;
+    }
+    return true;
+  }
   // offsets (relative to the workgroup's frame arenas) of job jj: the top-left tap of lane (0,0) and its output pixel
   __device__ static __forceinline__ uint2 job(int jj) {
     const int fp = jj / (NRB * NSEG); int rem = jj - fp * (NRB * NSEG);
@@ -1073,6 +1133,18 @@ struct HaloTabs {
 };
 constexpr int HT = SLOT0 + 2 * SLOT_B;                        // halo tables, then the frame arenas
 template <int F, bool BATCH> constexpr int pre_bytes() { return HT + HaloTabs<F, BATCH>::BYTES; }
+// Bank checks of the two-frame kernel's layouts: a layout edit that brings a 2-way conflict back into these reads fails the build.  Not asserted: the stride-2
+// stages conv2d_10 / conv2d_27 (their lane groups are an even number of rows apart times two -- no row skew separates them; profiles/r10_lds_conflicts_by_stage.txt
+// has their predicted figures) and the one-frame kernel's conv2d_15 (see Buf::SK).
+#if !(defined(YF_LAB) && defined(YF_WHATIF_FS))
+static_assert(DwGeo<2, 1, B_T1, B_T2>::taps_conflict_free(), "conv2d_3: the tap reads of a half-wave fall on distinct LDS banks");
+static_assert(DwGeo<2, 1, B_T8, B_T9>::taps_conflict_free(), "conv2d_15: the tap reads of a half-wave fall on distinct LDS banks");
+static_assert(conv1_pairs_conflict_free<2, B_IN, B_T1>(pre_bytes<2, true>()) && conv1_pairs_conflict_free<2, B_IN, B_T1>(pre_bytes<2, false>()) &&
+              conv1_pairs_conflict_free<1, B_IN, B_T1>(pre_bytes<1, true>()) && conv1_pairs_conflict_free<1, B_IN, B_T1>(pre_bytes<1, false>()),
+              "conv2d_1: the tap pairs of a half-wave fall on distinct LDS bank pairs");
+#endif
+static_assert(B_T7::OFF + B_T7::P * B_T7::S <= B_T8::OFF && B_T8::OFF + (B_T8::H + 2) * B_T8::ROWB <= B_T9::OFF && B_T9::OFF + B_T9::P * B_T9::S <= B_T11::OFF &&
+              B_T11::OFF + B_T11::P * B_T11::S <= B_T14::OFF, "T7 | T8 | T9 | T11 | concat_22 do not overlap");
 template <class G, int HOFF, int NT>
 __device__ __forceinline__ void build_halotab(char* smem, int tid) {
   for (int i = tid; i < G::N; i += NT) *reinterpret_cast<uint16_t*>(smem + HT + HOFF + 2 * i) = (uint16_t)(G::entry(i) >> 2);
