@@ -297,8 +297,10 @@ __global__ void __launch_bounds__(NW * 64, YF_WPE(NW)) yoloface56_fused(const Ne
       constexpr int PH = YF_POOL8H_WAVES, PV = YF_POOL8V_WAVES;
       YF_PRIO(5);
       YF_FETCH(5, W_m, L_m);
-      if (W_m < PH) pool8_h<F, PH * 64>(frames, tid_m);                                               // pool_8 (h): T4 -> HB ...
-      else v2::dw2_stage<F, NW - PH, 2, B_T4, B_T6M, 18, YF_L_LEAKY11, 4, v2::JobTabs<F, BATCH>::JT_DW10>(frames, tab, W_m - PH, L_m);   // ... beside conv2d_10: T4 -> T6
+      if (W_m < PH) {                                                                                 // pool_8 (h): T4 -> HB ...
+        if constexpr (F == 2) pool8_h_rows<F, PH>(frames, W_m, L_m);                                  // (two frames: rows across the lanes, a frame per half-wave)
+        else pool8_h<F, PH * 64>(frames, tid_m);
+      } else v2::dw2_stage<F, NW - PH, 2, B_T4, B_T6M, 18, YF_L_LEAKY11, 4, v2::JobTabs<F, BATCH>::JT_DW10>(frames, tab, W_m - PH, L_m);   // ... beside conv2d_10: T4 -> T6
       YF_SYNC(); YF_DUMP(B_T6M, 18, T6)
       YF_PRIO(8);
       YF_FETCH(6, W_m, L_m);

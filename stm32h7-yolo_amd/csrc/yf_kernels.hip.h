@@ -646,6 +646,57 @@ YF_STAGE_FN void pool8_h(char* frames, int tid) {
                                  [&](int ox, const SplitB& v) { *reinterpret_cast<uint32_t*>(dst + ox * 20) = v.merge(); });
   }
 }
+#if YF_H0 == 56
+// pool_8 h with the ROWS across the lanes (round 11; the two-frame kernels' form beside conv2d_10, on PH = 3 waves).  A wave-item is (channel dword cg, chunk k):
+// wave k sweeps chunk k, lanes 0-27 of a half take rows 0-27 -- lower half frame 0, upper half frame 1 -- and the wave loops over the five cg.  T4's row pitch is
+// 145 dwords, odd, so the 28 rows of a half fall on 28 different banks: every read of the sweep is conflict-free (pool8_rows_conflict_free below; the item order
+// of pool8_h put two or three of a half's lanes on every bank).  Every coordinate of the sweep is wave-uniform and, with one copy of the sweep per k, a
+// compile-time constant: sixteen loads at immediate offsets from one per-lane row base, no clamp, no division and no address arithmetic per load.  The four
+// surplus lanes of each half are masked for the whole pass: nothing outside HB's rows 0-27 is touched.  Same arithmetic (pool8_sweep), same HB.
+template <int F>
+constexpr bool pool8_rows_conflict_free(int arena0) {
+  constexpr int NO = 5, OW = B_HB::W, IH = B_T4::H;
+  if (F != 2 || IH > 32) return false;
+  for (int f = 0; f < F; ++f)                                  // half f of a wave holds frame f
+    for (int k = 0; k < (OW + NO - 1) / NO; ++k)
+      for (int cg = 0; cg < 5; ++cg)
+        for (int jj = 0; jj < 2 * (NO + 3); ++jj) {            // the loads of the sweep: coordinates 2j+1, 2j+2 of the odd pairs j = o0-2 .. o0+NO, clamped
+          const int o0 = k * NO < OW - NO ? k * NO : OW - NO, x0 = 2 * (o0 - 2 + jj / 2) + 1 + jj % 2, x = x0 < 0 ? 0 : x0 > B_T4::W - 1 ? B_T4::W - 1 : x0;
+          int addr[32] = {};
+          for (int l = 0; l < 32; ++l) {
+            const int y = l < IH ? l : IH - 1;                 // (masked lanes: stated as row 27 again, the same address)
+            addr[l] = arena0 + f * B_T4::FS + B_T4::OFF + (y + B_T4::PT) * B_T4::ROWB + (x + B_T4::PL) * B_T4::S + 4 * cg;
+          }
+          if (!lds_conflict_free<4>(addr)) return false;
+        }
+  return true;
+}
+template <int F, int PH>
+YF_STAGE_FN void pool8_h_rows(char* frames, int wave, int lane) {
+  constexpr int NO = 5, OW = B_HB::W, IH = B_T4::H;
+  static_assert(F == 2 && PH == 3 && PH * NO >= OW && IH <= 32, "one wave per chunk of five outputs, one frame per half-wave");
+  asm volatile("" : "+v"(lane));          // row base and row mask are cheap: recomputed per group, not parked (a VGPR pair and an SGPR pair) for the whole kernel
+  const int y = lane & 31;
+  if (y < IH) {
+    char* fbase = frames + (lane >> 5) * B_T4::FS;
+    const char* row = fbase + B_T4::at(y, 0);
+    char* dst = fbase + B_HB::OFF + y * (OW * 20);
+    auto pass = [&](auto o0) {
+#pragma nounroll
+      for (int cg = 0; cg < 5; ++cg)
+        pool8_sweep<NO, B_T4::W - 1>(decltype(o0)::value,
+                                     [&](int x) { return lds_u32(row + 4 * cg + x * B_T4::S); },
+                                     [&](int ox, const SplitB& v) { *reinterpret_cast<uint32_t*>(dst + 4 * cg + ox * 20) = v.merge(); });
+    };
+    if (wave == 0) pass(std::integral_constant<int, 0>());
+    else if (wave == 1) pass(std::integral_constant<int, NO>());
+    else pass(std::integral_constant<int, OW - NO>());
+  }
+}
+#endif
+// pool_8 v keeps its item order (cg, then the chunk k fastest).  The order q = 5 ox + cg fastest, then k, f -- consecutive banks across the lanes, 194 -> 76.5
+// conflict cycles per frame by the bank rule (tools/lds_bank_model.py) -- was measured in round 11 and stayed inside the run-to-run scatter, alone and on top of
+// pool8_h_rows (profiles/r11_pool_lanes_ab.txt): not taken.
 template <int F, int NT, bool STASH = false>      // STASH (debug builds): the raw pooled value goes to the still unwritten conv half of concat_22
 YF_STAGE_FN void pool8_v(char* frames, int tid) {
   constexpr int NO = 5, OW = B_HB::W, OH = B_T14::H, NCH = (OH + NO - 1) / NO;   // the last chunk shifted up
@@ -1142,6 +1193,8 @@ static_assert(DwGeo<2, 1, B_T8, B_T9>::taps_conflict_free(), "conv2d_15: the tap
 static_assert(conv1_pairs_conflict_free<2, B_IN, B_T1>(pre_bytes<2, true>()) && conv1_pairs_conflict_free<2, B_IN, B_T1>(pre_bytes<2, false>()) &&
               conv1_pairs_conflict_free<1, B_IN, B_T1>(pre_bytes<1, true>()) && conv1_pairs_conflict_free<1, B_IN, B_T1>(pre_bytes<1, false>()),
               "conv2d_1: the tap pairs of a half-wave fall on distinct LDS bank pairs");
+static_assert(pool8_rows_conflict_free<2>(pre_bytes<2, true>()) && pool8_rows_conflict_free<2>(pre_bytes<2, false>()),
+              "pool_8 h (rows across the lanes): every read of the sweep puts the rows of a half-wave on distinct LDS banks");
 #endif
 static_assert(B_T7::OFF + B_T7::P * B_T7::S <= B_T8::OFF && B_T8::OFF + (B_T8::H + 2) * B_T8::ROWB <= B_T9::OFF && B_T9::OFF + B_T9::P * B_T9::S <= B_T11::OFF &&
               B_T11::OFF + B_T11::P * B_T11::S <= B_T14::OFF, "T7 | T8 | T9 | T11 | concat_22 do not overlap");
