@@ -3,18 +3,21 @@
 
 
 // ------------------------------------------------------------------------------------------------ banded form
-// Second form for sizes that do not fit in LDS (160x160): FOUR kernels, each fusing a group of stages over a BAND of rows of
-// one frame.  A workgroup copies the band of its input tensor (with the halo rows the group needs) from the per-frame HBM
-// arena into LDS with coalesced loads, runs the SAME stage functions as the 56x56 kernel on band-local buffers, and writes
-// the band of its output tensor back.  Only five tensors cross HBM (T4, the pooled half of concat_22, T7, T8, T15):
-// ~0.78 MB per frame instead of 1.7 MB, all of it in full-row transfers.
-//   K1  input rows -> conv2d_1 -> conv2d_3 (dw) -> conv2d_5 -> conv2d_6 -> T4            band = 8 rows of the 80x80 grid
-//   K2  T4 -> pool_8 (+QUANTIZE) -> P8 ; conv2d_10 (dw) -> conv2d_12 -> T7 -> conv2d_13 -> T8     band = 4 rows of 40x40
-//   K3  T8 -> conv2d_15 (dw) -> conv2d_17 + add(T7) -> conv2d_19 | P8 -> conv2d_23 -> T15         band = 8 rows of 40x40
-//   K4  T15 -> pool_25, conv2d_27 (dw) ... conv2d_53 -> head                                       whole 20x20 grid
-// Halo rules: a band's input copy spans whole halo'd rows of the global tensor, so image borders bring their zero-point
-// halo with them and interior band edges bring real neighbour rows; the producer fills halo columns (and the first / last
-// band the top / bottom halo row) before the copy-out.
+// Second form for sizes that do not fit in LDS (160x160): THREE kernels, each fusing a group of stages over a BAND of rows of
+// one frame.  A workgroup copies the band of its input tensor (with the halo rows the group needs) into LDS with coalesced
+// loads -- band_k1 from the caller's frames, the others from the per-frame HBM arena --, runs the SAME stage functions as the
+// 56x56 kernel on band-local buffers, and writes the band of its output tensor back.  Only two tensors cross HBM through the
+// arena (T4 and T15; the pooled half of concat_22, T7 and T8 stay in LDS since K2 and K3 are one kernel): 0.49 MB per frame,
+// all of it in full-row transfers.  The arena keeps the offsets of P8, T7 and T8 (A_P8, A_T7, A_T8); no kernel touches them.
+//   band_k1   input rows -> conv2d_1 -> conv2d_3 (dw) -> conv2d_5 -> conv2d_6 -> T4                  band = 16 rows of the 80x80 grid, 5 jobs per frame
+//   band_k23  T4 -> pool_8 (+QUANTIZE) ; conv2d_10 (dw) -> conv2d_12 -> T7 -> conv2d_13 -> T8 ->
+//             conv2d_15 (dw) -> conv2d_17 + add(T7) -> conv2d_19 | pooled half -> conv2d_23 -> T15    band = 8 rows of 40x40, 5 jobs per frame
+//   band_k4   T15 -> pool_25, conv2d_27 (dw) ... conv2d_53 -> head                                    whole 20x20 grid, 1 job per frame
+// Each kernel is a persistent grid: workgroup b walks jobs b, b + gridDim.x, ... (split_job maps a job number to frame and band), keeps
+// its LDS buffers from one job to the next and fetches the next job's input into registers while it computes the current one.
+// Halo rules: a band's input copy spans whole halo'd rows of the global tensor, so interior band edges bring real neighbour
+// rows; the producer fills the left halo column of T4 / T15 (and the first band the top halo row) before the copy-out.  Inside
+// a kernel the halo columns of T1 / T8 are filled per job, their top / bottom halo rows by the first / last band only.
 namespace band {
 #define YF_BAND_PRIO(P) __builtin_amdgcn_s_setprio(P)      // priority ladder over a band job's stages (see the 56x56 kernel)
 constexpr int LB = LUT_BYTES;                                   // LUTs at LDS offset 0 (absolute addressing)
@@ -161,6 +164,7 @@ typedef Buf<LB + K1_R0,                          G1, K1_BH,      8, G1,     0, 0
 typedef Buf<L1_T2::OFF + K1_BH * G1 * 8,         G1, K1_BH,      4, G1,     0, 0> L1_T3;
 typedef Buf<LB,                                  G1, K1_BH,     20, T4_RS,  0, 1> L1_T4;    // left halo column; aliases IN and T1 (dead after conv2d_3)
 constexpr int K1_LDS = L1_T3::OFF + K1_BH * G1 * 4;
+static_assert(3 * K1_LDS > 160 * 1024, "at most two workgroups per CU: the tests' schedule restatement counts on a grid of at most 2 x CUs");
 
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, YF_K1_OCC) band_k1(const Params prm) {
@@ -291,6 +295,7 @@ typedef Buf<K23_RH,                              G2, K23_BP,  8, G2,     0, 0> L
 typedef Buf<K23_R14,                             G2, K23_BP, 48, G2,     0, 0> L23_T14;
 typedef Buf<K23_RH + K23_BP * G2 * 8,            G2, K23_BP, 24, T15_RS, 0, 1> L23_T15;      // behind T11, on T6's old bytes
 constexpr int K23_LDS = K23_R14 + K23_BP * G2 * 48;
+static_assert(3 * K23_LDS > 160 * 1024, "at most two workgroups per CU: the tests' schedule restatement counts on a grid of at most 2 x CUs");
 #if YF_K23_POOL_MERGE
 static_assert(YF_K23_T8_SKEW == 16 && K23_T8T9_BYTES == K23_NM * K23_T8_ROW + K23_BP * G2 * 48 && K23_T8T9_BYTES + K23_NM * G2 * 8 <= K23_RA_BYTES && K23_T8T9_BYTES % 16 == 0, "T8 | T9 | T7 fit region A");
 static_assert(K23_NM * G2 * 32 <= K23_BP * G2 * 48 && K23_BP * G2 * 8 + K23_BP * T15_ROW <= K23_RH_BYTES, "T6 fits concat_22's rows; T11 | T15 fit HB's bytes");
@@ -472,6 +477,7 @@ constexpr bool k4_ring_ok() {
 static_assert(k4_ring_ok(), "every tail block (without its add tables) fits its ring slot");
 constexpr int K4_LDS = K4_BUFS_END + v2::ZERO_B + LayK4::JT_BYTES;
 static_assert(K4_LDS <= 81920, "two workgroups per CU");
+static_assert(3 * K4_LDS > 160 * 1024, "at most two workgroups per CU: the tests' schedule restatement counts on a grid of at most 2 x CUs");
 
 // pool_25 for output rows [oy0, oy0 + K4_HALF) from a T15 half whose first halo'd row is h0
 template <int NT>

@@ -361,6 +361,91 @@ def band_edge_frames_160():
     return np.stack(frames)
 
 
+def reuse_frames_160(n=1024, seed=160):
+    """The frames of the workgroup-reuse tests at 160x160 (tests/test_band160_reuse_host.py, tests/test_band160_reuse_gpu.py): n frames whose heads are
+    pairwise distinct under every rounding, so that a frame in the wrong slot, a band taken from another frame or a row left over from the previous job of
+    a workgroup shows.  Frame k has kind k % 4 -- 0: band_edge_frames_160()[(k // 4) % 39] with an 8x8 patch of noise at a random place; 1: a constant frame
+    at a random level with noise in one of the five 32-row bands; 2: noise; 3: low-contrast noise (// 16).  All draws from one generator, in frame order."""
+    rng = np.random.default_rng(seed)
+    edges = band_edge_frames_160()
+    out = np.empty((n, 160, 160, 3), np.int8)
+    for k in range(n):
+        kind = k % 4
+        if kind == 0:
+            out[k] = edges[(k // 4) % edges.shape[0]]
+            y0, x0 = (int(v) for v in rng.integers(0, 152, 2))
+            out[k, y0:y0 + 8, x0:x0 + 8] = rng.integers(-128, 128, (8, 8, 3), dtype=np.int8)
+        elif kind == 1:
+            out[k] = rng.integers(-128, 128)
+            band = int(rng.integers(0, 5))
+            out[k, 32 * band:32 * band + 32] = rng.integers(-128, 128, (32, 160, 3), dtype=np.int8)
+        elif kind == 2:
+            out[k] = rng.integers(-128, 128, (160, 160, 3), dtype=np.int8)
+        else:
+            out[k] = (rng.integers(-128, 128, (160, 160, 3)) // 16).astype(np.int8)
+    return out
+
+
+# ---- the 160x160 band kernels' schedule, restated ---------------------------------------------------------------------------------------
+# csrc/yf_band160.hip.h: each band kernel is a persistent grid; workgroup b takes jobs b, b + grid, b + 2 grid, ... below n * (jobs per frame) and split_job
+# maps a job number to (frame, band) in the XCD-grouped order when grid % 8 == 0 and n % 8 == 0, in the plain order otherwise.  csrc/yf_engine.hip
+# (launch160_banded): grid = min(jobs, CUs x resident workgroups per CU); the static_asserts beside K1_LDS / K23_LDS / K4_LDS bound the residents by 2.
+BAND_KERNELS = ("band_k1", "band_k23", "band_k4")
+BAND_JOBS_PER_FRAME = (5, 5, 1)
+BAND_MAX_WGS_PER_CU = 2
+
+
+def band_grids(n, bands, cus):
+    """the grids launch160_banded can choose for n frames on a device of `cus` CUs: one or two resident workgroups per CU"""
+    return sorted({min(n * bands, cus * occ) for occ in range(1, BAND_MAX_WGS_PER_CU + 1)})
+
+
+def band_xcd_order(n, grid):
+    return grid % 8 == 0 and n % 8 == 0
+
+
+def band_split_job(v, xcd, bands):
+    """split_job: job number -> (frame, band)"""
+    if xcd:
+        l = v >> 3
+        q = l // bands
+        return (v & 7) + 8 * q, l - q * bands
+    return v // bands, v - (v // bands) * bands
+
+
+def band_walk(n, bands, grid, xcd=None):
+    """[workgroup][round] -> (frame, band): the jobs of every workgroup in the order it takes them (xcd None: the order the kernel takes)"""
+    xcd = band_xcd_order(n, grid) if xcd is None else xcd
+    return [[band_split_job(v, xcd, bands) for v in range(b, n * bands, grid)] for b in range(grid)]
+
+
+def band_locate(n, bands, grid, frame, band):
+    """(workgroup, round) that computes band `band` of frame `frame`: the inverse of band_split_job in the order the kernel takes"""
+    if band_xcd_order(n, grid):
+        v = (((frame >> 3) * bands + band) << 3) | (frame & 7)
+    else:
+        v = frame * bands + band
+    assert band_split_job(v, band_xcd_order(n, grid), bands) == (frame, band)
+    return v % grid, v // grid
+
+
+def run_160_after_complement(torch, network, d_x, n, canary=77, stream=None):
+    """Heads [n, 20, 20, 18] of the first n frames of the device tensor d_x through the 160x160 path.  The same count of the frames' bitwise complements
+    is launched first, on the same stream into a scratch output: the per-stream HBM arena outlives a launch, so a band row that a kernel fails to write
+    is then read back as ANOTHER frame's values, not as the right ones an earlier launch of the same frames left.  The output has a canary frame behind
+    the batch, asserted untouched."""
+    d_scratch = torch.empty((n, 20, 20, 18), dtype=torch.int8, device="cuda")
+    d_out = torch.full((n + 1, 20, 20, 18), canary, dtype=torch.int8, device="cuda")
+    d_not = torch.bitwise_not(d_x[:n])
+    torch.cuda.synchronize()
+    network.run_device_hw(160, 160, d_not.data_ptr(), d_scratch.data_ptr(), n, stream)
+    network.run_device_hw(160, 160, d_x.data_ptr(), d_out.data_ptr(), n, stream)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy()
+    assert (got[n] == canary).all(), f"n = {n}: wrote past the last frame"
+    return got[:n]
+
+
 # ---- the oracle's per-op dump ---------------------------------------------------------------------------------------------------------
 def dump_layout(h=56):
     """(sizes, offsets, shapes) of the oracle's per-op dump at 56x56: op i's output is dump[:, offs[i]:offs[i] + sizes[i]], shaped shapes[i] = (h, w, c)."""
