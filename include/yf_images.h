@@ -222,6 +222,46 @@ YF_API long yf_images_average_precision_device(const void* d_dets, const void* d
                                                yf_eval_result* d_result, double* d_curve, void* stream);
 YF_API int yf_images_eval_sort_tile(void);
 
+/* ---- tiled detection: a large image as overlapping tiles, each one a frame of the network, and the tiles' records one image's records
+ * again.  The reference has no tiling (its callers squeeze the whole photograph into one 56x56 frame, where a 60-pixel face of a
+ * 1920x1080 picture is less than 2 pixels): the grid, the order of the tiles and of the merged records and the saturation of a
+ * translated edge are this library's own definition, stated once in csrc/yf_images_tiles.h, which the kernels and a host build share.
+ * A C host's sequence: plan (host), upload descriptors, tiles and first, any ragged run above over the tile descriptors, gather,
+ * yf_images_nms_wide_device in place -- INTEGRATION.md.
+ *   grid:   per axis of length L, tile side T >= 1, stride 1 <= S <= T: L <= T gives one tile [0, L); otherwise
+ *           k = (L - T + S - 1) / S + 1 tiles of side T at i * S for i < k - 1 and at L - T for the last, flush with the edge.  An image's
+ *           tiles are in row-major order, y outer.  whole != 0: an image whose grid has more than one tile gets the whole image (origin
+ *           0, 0, H x W) as one more region, its FIRST tile; a one-tile grid already is the whole image and is not doubled. */
+typedef struct yf_tile { int32_t image, x0, y0, height, width; } yf_tile;           /* 20 bytes */
+/* Host-only, no GPU call.  images[n]: the parents (only offset, height, width, row_stride are read; no pixel).  Returns the number of
+ * tiles t; with tiles == NULL it only counts and writes nothing.  Otherwise tiles[t], tile_images[t] and first[n + 1] (all required) are
+ * written: tile_images[j] is a descriptor the ragged entry points take unchanged -- offset = parent.offset + y0 * parent.row_stride +
+ * x0 * C, the parent's row stride -- and first[i] .. first[i + 1] is the tile range of image i (first[0] = 0, first[n] = t).
+ * -1 with an error text: a bad argument (format, n < 0, a tile side < 1, a stride outside [1, tile side], a missing array), a parent
+ * with a side outside [1, 16384], t above tiles_cap, or t >= 2^31. */
+YF_API long yf_images_plan_tiles(const yf_image* images, long n, int format, int tile_h, int tile_w, int stride_y, int stride_x,
+                                 int whole, yf_tile* tiles, yf_image* tile_images, int32_t* first, long tiles_cap);
+/* The merge on the device.  d_dets yf_det[t][cap], d_counts int32[t]: what any decode above wrote for the t tiles; of tile j the first
+ * m_j = min(max(count, 0), cap) records are read, the suppression's clamp.  1 <= cap <= 1200, 1 <= out_cap <= YF_IMAGES_NMS_WIDE_MAX_CAP,
+ * t * cap < 2^31, n < 2^31.  d_tiles yf_tile[t] (only x0 and y0 are read: membership comes from d_first alone), d_first int32[n + 1].
+ *   output: d_out yf_det[n][out_cap] (no overlap with d_dets), d_out_counts int32[n].  For image i the tiles first[i] <= j < first[i + 1]
+ *           in ascending j, each tile's m_j records in their order: this concatenation goes to d_out[i][0..).  d_out_counts[i] = the
+ *           sum of the m_j, the true total, which may exceed out_cap; only the first out_cap records of the concatenation are written
+ *           (the cut may fall inside a tile), slots at and beyond min(total, out_cap) are not written.
+ *   record: the read one byte for byte, except frame = i, and x1, x2 + x0, y1, y2 + y0, the sum in int64 clamped to int32: an
+ *           INT32_MIN edge of YF_DECODE_PY moves by the origin, a saturated INT32_MAX edge of YF_DECODE_FW stays.
+ *   safety: for a non-decreasing d_first with first[0] = 0 and first[n] = t the result is as above.  For any other content the output
+ *           is unspecified, but no access leaves the buffers: every index that comes from device memory is range-checked before use.
+ * Two launches (a scan of the tile counts per image, one wave per tile to copy) whose cost follows the tiles and the records, never cap
+ * or out_cap; no allocation, no synchronisation, capturable.  d_work: 16-byte aligned, at least yf_images_gather_tiles_workspace(t)
+ * bytes (4 per tile, rounded up to 16; 0 for t <= 0); a smaller work_bytes is an error and nothing is launched.  Returns n; n = 0 or
+ * t = 0 launches nothing (t = 0 with n > 0 writes nothing either) -- after the checks: every pointer must be valid then too. */
+YF_API size_t yf_images_gather_tiles_workspace(long t);
+YF_API long   yf_images_gather_tiles_device(const void* d_dets, const void* d_counts, long t, int cap,
+                                            const yf_tile* d_tiles, const int32_t* d_first, long n,
+                                            void* d_out, void* d_out_counts, int out_cap,
+                                            void* d_work, size_t work_bytes, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

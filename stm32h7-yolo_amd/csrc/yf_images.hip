@@ -11,7 +11,8 @@
 // inside the image's extent: no load reaches past its last pixel.
 // The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame), decode_f32_kernel (the fp16 network's
 // float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h;
-// the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h.
+// the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
+// tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -29,6 +30,7 @@
 #include "yf_images_float.h"
 #include "yf_images_wide.hip.h"
 #include "yf_images_eval.hip.h"
+#include "yf_images_tiles.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -818,6 +820,44 @@ YF_API long yf_images_average_precision_device(const void* d_dets, const void* d
   hipLaunchKernelGGL(yfeval::curve_kernel, by_tile, wave, 0, s, w.val[0], w.head, w.tile_base, w.tile_sufmax, w.terms, d_curve);
   hipLaunchKernelGGL(yfeval::sum_kernel, one, wave, 0, s, w.head, w.terms, d_result);
   return launched("average precision kernel launches", n);
+}
+
+YF_API long yf_images_plan_tiles(const yf_image* images, long n, int format, int tile_h, int tile_w, int stride_y, int stride_x, int whole,
+                                 yf_tile* tiles, yf_image* tile_images, int32_t* first, long tiles_cap) {
+  const char* err = "";
+  const long t = yfi_plan_tiles(images, n, format, tile_h, tile_w, stride_y, stride_x, whole, tiles, tile_images, first, tiles_cap, &err);
+  if (t < 0) fail("%s", err);
+  return t;
+}
+
+YF_API size_t yf_images_gather_tiles_workspace(long t) {
+  if (t <= 0 || t >= (1l << 31)) return 0;
+  return ((size_t)t * sizeof(int32_t) + 15) & ~(size_t)15;
+}
+
+YF_API long yf_images_gather_tiles_device(const void* d_dets, const void* d_counts, long t, int cap, const yf_tile* d_tiles,
+                                          const int32_t* d_first, long n, void* d_out, void* d_out_counts, int out_cap, void* d_work,
+                                          size_t work_bytes, void* stream) {
+  if (n < 0 || n >= (1l << 31)) return fail("n must be in [0, 2^31)");
+  if (t < 0) return fail("t < 0");
+  if (cap <= 0 || cap > YF_IMAGES_CAND160) return fail("cap must be in [1, %d]", YF_IMAGES_CAND160);
+  if (out_cap <= 0 || out_cap > YF_IMAGES_NMS_WIDE_MAX_CAP) return fail("out_cap must be in [1, %d]", YF_IMAGES_NMS_WIDE_MAX_CAP);
+  if ((uint64_t)t * (uint64_t)cap >= (1ull << 31)) return fail("t * cap must be below 2^31");
+  if (!d_dets || !d_counts || !d_tiles || !d_first || !d_out || !d_out_counts)
+    return fail("d_dets, d_counts, d_tiles, d_first, d_out or d_out_counts is NULL");
+  if ((((uintptr_t)d_dets | (uintptr_t)d_counts | (uintptr_t)d_tiles | (uintptr_t)d_first | (uintptr_t)d_out | (uintptr_t)d_out_counts) & 3) != 0)
+    return fail("d_dets, d_counts, d_tiles, d_first, d_out and d_out_counts must be 4-byte aligned");
+  if (!d_work || ((uintptr_t)d_work & 15) != 0) return fail("d_work is NULL or not 16-byte aligned");
+  const size_t need = yf_images_gather_tiles_workspace(t);
+  if (work_bytes < need) return fail("work_bytes %zu is below yf_images_gather_tiles_workspace(t) = %zu", work_bytes, need);
+  if (n == 0 || t == 0) return n;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yftiles::prefix_kernel, grid_for(n, 8), dim3(yftiles::kThreads), 0, s, (const int*)d_counts, (int)t, cap, d_first, n,
+                     (int32_t*)d_work, (int32_t*)d_out_counts);
+  const long groups = (t + yftiles::kWaves - 1) / yftiles::kWaves;                  // one wave per tile, four per workgroup
+  hipLaunchKernelGGL(yftiles::copy_kernel, grid_for(groups, 8), dim3(yftiles::kThreads), 0, s, (const uint32_t*)d_dets, (const int*)d_counts,
+                     (int)t, cap, d_tiles, d_first, n, (const int32_t*)d_work, (uint32_t*)d_out, out_cap);
+  return launched("gather_tiles kernel launches", n);
 }
 
 }  // extern "C"

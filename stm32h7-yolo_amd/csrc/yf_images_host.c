@@ -1,6 +1,7 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), for the CPU tests only: libyf_images_host.so, no HIP. */
+ * functions the device kernels call), and the tile grid, planner and merge of yf_images_tiles.h, for the CPU tests only:
+ * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -10,6 +11,7 @@
 #include "yf_images_decode160.h"
 #include "yf_images_float.h"
 #include "yf_images_eval.h"
+#include "yf_images_tiles.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -206,4 +208,38 @@ EXPORT long yfi_eval_ap_host(const yf_det* dets, const int32_t* counts, const ui
   }
   free(key); free(flag); free(order); free(precision); free(recall);
   return rc;
+}
+
+/* ---- yf_images_tiles.h ----  yf_images_plan_tiles as libyf_images.so exports it (the error text is dropped) */
+EXPORT long yfi_plan_tiles_host(const yf_image* images, long n, int format, int tile_h, int tile_w, int stride_y, int stride_x, int whole,
+                                yf_tile* tiles, yf_image* tile_images, int32_t* first, long tiles_cap) {
+  const char* err;
+  return yfi_plan_tiles(images, n, format, tile_h, tile_w, stride_y, stride_x, whole, tiles, tile_images, first, tiles_cap, &err);
+}
+
+/* yf_images_gather_tiles_device as yf_images_tiles.h states it: per image its tiles in ascending order, each tile's clamped records in
+ * theirs, translated, the first out_cap of them written and the total counted.  As on the device, a range end is clamped to [0, t]
+ * first, so a malformed `first` reads and writes inside the buffers.  Returns n, or -1 for arguments the device entry refuses. */
+EXPORT long yfi_gather_tiles_host(const yf_det* dets, const int32_t* counts, long t, int cap, const yf_tile* tiles, const int32_t* first,
+                                  long n, yf_det* out, int32_t* out_counts, int out_cap) {
+  if (n < 0 || t < 0 || cap < 1 || cap > YF_IMAGES_CAND160 || out_cap < 1 || out_cap > YF_IMAGES_NMS_WIDE_MAX_CAP ||
+      (uint64_t)t * (uint64_t)cap >= (1ull << 31))
+    return -1;
+  if (t == 0) return n;
+  for (long i = 0; i < n; ++i) {
+    const long a = first[i] < 0 ? 0 : (first[i] > t ? t : first[i]), b = first[i + 1] < 0 ? 0 : (first[i + 1] > t ? t : first[i + 1]);
+    int64_t total = 0;
+    for (long j = a; j < b; ++j) {
+      const int m = yfi_tiles_clamp(counts[j], cap);
+      for (int r = 0; r < m && total + r < out_cap; ++r) {
+        uint32_t w[7];
+        memcpy(w, &dets[j * cap + r], sizeof w);
+        for (int q = 0; q < 7; ++q) w[q] = yfi_tiles_dword(w[q], q, (int32_t)i, tiles[j].x0, tiles[j].y0);
+        memcpy(&out[i * out_cap + total + r], w, sizeof w);
+      }
+      total += m;
+    }
+    out_counts[i] = (int32_t)total;
+  }
+  return n;
 }

@@ -12,6 +12,11 @@ the decode in float32 (`run_decode_f16_ragged_device`; the arithmetic: csrc/yf_i
 `evaluate(network, images, ground_truths)` scores those boxes against labelled ones as the reference's training script does
 (yoloface/tensorflow/yolov3_train_tf.py:657-759, calculate_iou / calculate_ap / calculate_map): `match_device` and
 `average_precision_device` on the same stream, without the records leaving the GPU (the arithmetic: csrc/yf_images_eval.h).
+
+`detect_tiled(network, images, tile)` runs a large picture as overlapping tiles, each one a frame of the network, and makes the tiles'
+records one picture's records again on the GPU: `plan_tiles` (the grid), the ragged run over the tile descriptors, `gather_tiles_device`
+(merge and translation), `nms_wide_device` across the tile borders.  The reference has no tiling; the definition is the library's own
+(csrc/yf_images_tiles.h).
 """
 import ctypes
 import os
@@ -38,6 +43,11 @@ class YfImage(ctypes.Structure):
 
 IMAGE_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("row_stride", "<i8")])
 assert IMAGE_DTYPE.itemsize == ctypes.sizeof(YfImage) == 24
+
+
+# a tile of an image (yf_tile): the image's index, the tile's origin in the image's pixels and its size
+TILE_DTYPE = np.dtype([("image", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("height", "<i4"), ("width", "<i4")])
+assert TILE_DTYPE.itemsize == 20
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -96,6 +106,8 @@ def _entries():
         "run_decode_f16_ragged_device": [vp] + ragged + [vp, vp, vp, vp, ci, vp, vp],
         "match_device": [vp, vp, cl, ci, vp, vp, ci, cd, vp, vp, vp],
         "average_precision_device": [vp, vp, vp, cl, ci, vp, ci, vp, cs, vp, vp, vp],
+        "plan_tiles": [vp, cl, ci, ci, ci, ci, ci, ci, vp, vp, vp, cl],
+        "gather_tiles_device": [vp, vp, cl, ci, vp, vp, cl, vp, vp, ci, vp, cs, vp],
     }
 
 
@@ -124,6 +136,8 @@ def load():
     lib.yf_images_set_decode_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     lib.yf_images_average_precision_workspace.restype = ctypes.c_size_t
     lib.yf_images_average_precision_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
+    lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
+    lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
     lib.yf_images_eval_sort_tile.restype = ctypes.c_int
     lib.yf_images_eval_sort_tile.argtypes = []
     if lib.yf_images_eval_sort_tile() != EVAL_SORT_TILE:
@@ -303,6 +317,63 @@ def average_precision_device(d_dets, d_counts, d_tp, n, cap, d_gt_counts, gt_cap
     _call("average_precision_device", n, d_dets, d_counts, d_tp, n, cap, d_gt_counts, gt_cap, d_work, work_bytes, d_result, d_curve, stream)
 
 
+def _pair(v, what):
+    """an int or (y, x) -> (y, x)"""
+    y, x = (v, v) if np.ndim(v) == 0 else v
+    if int(y) != y or int(x) != x:
+        raise ValueError(f"{what} {v!r}: an integer or (y, x) integers")
+    return int(y), int(x)
+
+
+def plan_tiles(shapes_or_descriptors, fmt, tile, stride=None, whole=True):
+    """The tile grid of a batch (yf_images_plan_tiles; host only): -> (tiles TILE_DTYPE[t], tile_desc IMAGE_DTYPE[t], first int32[n + 1]).
+    `shapes_or_descriptors`: an IMAGE_DTYPE array (as `pack_images` returns: the tile descriptors then point into the same pixel buffer,
+    parent row stride and all) or a list of (height, width), taken as packed images one after the other.  `tile`, `stride`: an int or
+    (y, x); stride=None means the tile side, so no overlap.  Per axis of length L: one tile [0, L) if L <= T, else
+    (L - T + S - 1) // S + 1 tiles of side T, the last one flush with the edge; row-major, y outer.  `whole`: an image of more than one
+    tile gets the whole image as its first tile.  Image i's tiles are first[i] .. first[i + 1]."""
+    code = format_code(fmt)
+    C = CHANNELS[code]
+    if isinstance(shapes_or_descriptors, np.ndarray) and shapes_or_descriptors.dtype == IMAGE_DTYPE:
+        desc = np.ascontiguousarray(shapes_or_descriptors).reshape(-1)
+    else:
+        desc, off = np.zeros(len(shapes_or_descriptors), IMAGE_DTYPE), 0
+        for i, (h, w) in enumerate(shapes_or_descriptors):
+            desc[i] = (off, h, w, int(w) * C)
+            off += int(h) * int(w) * C
+    th, tw = _pair(tile, "tile")
+    sy, sx = (th, tw) if stride is None else _pair(stride, "stride")
+    lib, n = load(), desc.shape[0]
+    args = (desc.ctypes.data, n, code, th, tw, sy, sx, int(bool(whole)))
+    t = lib.yf_images_plan_tiles(*args, None, None, None, 0)
+    if t < 0:
+        raise ImagesError(f"yf_images_plan_tiles: {(lib.yf_images_last_error_text() or b'').decode()}")
+    tiles, tile_desc, first = np.zeros(t, TILE_DTYPE), np.zeros(t, IMAGE_DTYPE), np.zeros(n + 1, np.int32)
+    if lib.yf_images_plan_tiles(*args, tiles.ctypes.data, tile_desc.ctypes.data, first.ctypes.data, t) != t:
+        raise ImagesError(f"yf_images_plan_tiles: {(lib.yf_images_last_error_text() or b'').decode()}")
+    return tiles, tile_desc, first
+
+
+def pack_tiles(images, fmt="bgr", tile=160, stride=None, whole=True):
+    """`pack_images`, then `plan_tiles` on its descriptors: -> (pixels uint8[bytes], tile_desc IMAGE_DTYPE[t], tiles TILE_DTYPE[t],
+    first int32[n + 1]).  The pixels are stored once; overlapping tiles share them."""
+    buf, desc = pack_images(images, fmt)
+    tiles, tile_desc, first = plan_tiles(desc, fmt, tile, stride, whole)
+    return buf, tile_desc, tiles, first
+
+
+def gather_tiles_workspace(t):
+    """Bytes of scratch gather_tiles_device needs for t tiles."""
+    return int(load().yf_images_gather_tiles_workspace(t))
+
+
+def gather_tiles_device(d_dets, d_counts, t, cap, d_tiles, d_first, n, d_out, d_out_counts, out_cap, d_work, work_bytes, stream=None):
+    """The records of t tiles merged per image (yf_images_gather_tiles_device): d_dets yf_det[t][cap], d_counts int32[t], d_tiles
+    TILE_DTYPE[t], d_first int32[n + 1] -> d_out yf_det[n][out_cap]: image i's tiles in order, their records in theirs, frame = i, the
+    edges moved by the tile's origin; d_out_counts int32[n] the true totals (only the first out_cap records are written)."""
+    _call("gather_tiles_device", n, d_dets, d_counts, t, cap, d_tiles, d_first, n, d_out, d_out_counts, out_cap, d_work, work_bytes, stream)
+
+
 def pack_ground_truths(ground_truths):
     """one [k, 4] array (x1, y1, x2, y2) per image -> (GT_DTYPE [n, gt_cap], int32 [n]), gt_cap the largest k (at least 1)"""
     gts = [np.asarray(g, np.float64).reshape(-1, 4) for g in ground_truths]
@@ -315,11 +386,12 @@ def pack_ground_truths(ground_truths):
     return packed, np.array([g.shape[0] for g in gts], np.int32)
 
 
-def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype):
+def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype, packed=None):
     """What `detect` launches, with the records left on the device: checks size and dtype as it does, packs the images, allocates the
     workspaces, runs images -> frames -> network -> records (and the suppression when iou_threshold is not None) on the device's current
     stream without synchronising.  -> (d_dets uint8 [n, cap, 28], d_counts int32 [n], d_status int32 [n], stream, keep), `keep` the
-    tensors that must outlive the launches.  `detect` keeps its own copy of these lines (it predates this helper and is left as it is);
+    tensors that must outlive the launches.  packed=(pixels, descriptors): the batch as it is (`pack_tiles`: one frame per tile) instead of
+    `pack_images(images)`.  `detect` keeps its own copy of these lines (it predates this helper and is left as it is);
     a change to one belongs in the other."""
     if size not in (56, 160):
         raise ValueError(f"size {size!r}: 56 or 160")
@@ -331,9 +403,9 @@ def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, d
     grid = size // 8
     if cap is None:
         cap = 3 * grid * grid
-    n = len(images)
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    buf, desc = pack_images(images, fmt)
+    buf, desc = pack_images(images, fmt) if packed is None else packed
+    n = desc.shape[0]
     d_px = torch.from_numpy(buf).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
     f16 = dtype == "fp16"
@@ -355,12 +427,15 @@ def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, d
     return d_dets, d_counts, d_status, stream, (d_px, d_desc, d_frames, d_heads)
 
 
-def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None):
+def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None,
+             tile=None, stride=None, whole=True):
     """Average precision of the network's boxes against labelled ones: what evaluate_model (yolov3_train_tf.py:809-869) reports, for the
     batch `detect` takes.  `ground_truths`: one [k, 4] array (x1, y1, x2, y2) per image, in that image's pixels.  The records are decoded as
     by `detect` (fmt, size, dtype as there; iou_threshold=None scores every record, a float suppresses first, as evaluate_model does),
     matched at IoU `conf_iou` (match_device) and scored (average_precision_device) on the same stream; only the 32-byte result and the
-    per-image status come back.  An image the library refused (status 1; `pack_images` produces none) raises ImagesError.
+    per-image status come back.  tile=None scores the untiled records; with a tile (and `stride`, `whole`: `detect_tiled`) the records are
+    those of the tiles merged per image (at most 1200 per image; more raises ImagesError).  An image (a tile) the library refused (status 1;
+    `pack_images` produces none) raises ImagesError.
     Returns {"ap", "detections", "ground_truths", "true_positives", "precision", "recall"}; the last two are the end of the curve:
     true_positives / (detections + 1e-16) and true_positives / max(1, ground_truths)."""
     n = len(images)
@@ -369,7 +444,12 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     gt, gt_counts = pack_ground_truths(ground_truths)
     if n == 0:
         return {"ap": 0.0, "detections": 0, "ground_truths": 0, "true_positives": 0, "precision": 0.0, "recall": 0.0}
-    d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, None, device, iou_threshold, size, dtype)
+    d_totals = None
+    if tile is None:
+        d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, None, device, iou_threshold, size, dtype)
+    else:
+        d_dets, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt, NMS_WIDE_MAX_CAP,
+                                                                                      device, iou_threshold, size, dtype)
     import torch
     dev, cap, gt_cap = d_dets.device, d_dets.shape[1], gt.shape[1]
     d_gt = torch.from_numpy(gt.view(np.float64).reshape(n, gt_cap, 4)).to(dev)
@@ -387,10 +467,76 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     bad = np.nonzero(d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"evaluate: the library refused image(s) {bad.tolist()} (status 1): their frames hold no picture")
+    if d_totals is not None:
+        _check_totals("evaluate", d_totals, cap)
     res = d_result.cpu().numpy().view(EVAL_RESULT_DTYPE)[0]
     m, num_gt, tp = int(res["detections"]), int(res["ground_truths"]), int(res["true_positives"])
     return {"ap": float(res["ap"]), "detections": m, "ground_truths": num_gt, "true_positives": tp,
             "precision": tp / (m + 1e-16), "recall": tp / max(1, num_gt)}
+
+
+def _tiled_records_on_device(network, images, tile, stride, whole, fmt, out_cap, device, iou_threshold, size, dtype):
+    """What `detect_tiled` launches, with the merged records left on the device: the tiles of `images` through the ragged run of `size`
+    and `dtype` (every candidate held: 147 / 1200 per tile), `gather_tiles_device`, and `nms_wide_device` on the merged records in place
+    when iou_threshold is not None -- one stream, no synchronisation.  -> (d_out uint8 [n, out_cap, 28], d_counts int32 [n] the counts
+    after the suppression, d_totals int32 [n] the merged totals before it, d_status int32 [t], stream, keep)."""
+    if not 1 <= out_cap <= NMS_WIDE_MAX_CAP:
+        raise ValueError(f"out_cap {out_cap!r}: 1 to {NMS_WIDE_MAX_CAP}")
+    import torch
+    buf, tile_desc, tiles, first = pack_tiles(images, fmt, tile, stride, whole)
+    n, t = len(images), tiles.shape[0]
+    d_dets, d_tile_counts, d_status, stream, keep = _records_on_device(network, None, fmt, None, device, None, size, dtype,
+                                                                       packed=(buf, tile_desc))
+    dev, cap = d_dets.device, d_dets.shape[1]
+    d_tiles = torch.from_numpy(tiles.view(np.uint8)).to(dev)
+    d_first = torch.from_numpy(first).to(dev)
+    d_out = torch.empty((n, out_cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_totals = torch.empty(n, dtype=torch.int32, device=dev)
+    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
+    work_bytes = gather_tiles_workspace(t)
+    d_work = torch.empty(max(work_bytes, 16), dtype=torch.uint8, device=dev)
+    gather_tiles_device(d_dets.data_ptr(), d_tile_counts.data_ptr(), t, cap, d_tiles.data_ptr(), d_first.data_ptr(), n, d_out.data_ptr(),
+                        d_totals.data_ptr(), out_cap, d_work.data_ptr(), work_bytes, stream=stream.cuda_stream)
+    if iou_threshold is not None:                       # the records in place, the kept counts beside the totals
+        nms_wide_device(d_out.data_ptr(), d_totals.data_ptr(), n, out_cap, iou_threshold, d_out.data_ptr(), d_counts.data_ptr(),
+                        stream=stream.cuda_stream)
+    else:
+        d_counts = d_totals
+    return d_out, d_counts, d_totals, d_status, stream, (keep, d_dets, d_tile_counts, d_tiles, d_first, d_work)
+
+
+def _check_totals(what, d_totals, out_cap):
+    totals = d_totals.cpu().numpy()
+    over = np.nonzero(totals > out_cap)[0]
+    if over.size:
+        i = int(over[0])
+        raise ImagesError(f"{what}: image {i} has {int(totals[i])} merged records, out_cap holds {out_cap}"
+                          + (f" (and {over.size - 1} more image(s) above it)" if over.size > 1 else ""))
+
+
+def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):
+    """`detect` for pictures larger than the faces in them: every image is cut into tiles (`plan_tiles`: `tile`, `stride` an int or (y, x),
+    stride=None no overlap; `whole` adds the whole image as a tile of its own), every tile is one frame of the network at `size` and `dtype`
+    (as in `detect`), and the tiles' records are merged per image on the GPU, translated to the image's own pixels (`gather_tiles_device`)
+    and suppressed across the tile borders, where overlapping tiles report one face twice (`nms_wide_device`, in place) -- all on one
+    stream.  Returns one int32 [k, 4] array (x1, y1, x2, y2) per image: with iou_threshold=None the merged records in tile order, each
+    tile's in decode order; with a float the kept ones in keep order.  out_cap: the merged records an image can hold (at most 1200); an
+    image with more raises ImagesError naming the image and its total."""
+    n = len(images)
+    if n == 0:
+        return []
+    d_out, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt, out_cap, device,
+                                                                                 iou_threshold, size, dtype)
+    stream.synchronize()
+    del keep
+    _check_totals("detect_tiled", d_totals, out_cap)
+    dets = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, out_cap)
+    counts = d_counts.cpu().numpy()
+    out = []
+    for i in range(n):
+        d = dets[i, :min(int(counts[i]), out_cap)]
+        out.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
+    return out
 
 
 def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8"):
