@@ -51,14 +51,14 @@ def frames(torch_cuda):
 
 @pytest.fixture(scope="module")
 def bind(network):
-    """bind(name, rounding): the session's network initialised from the variant's bytes with the rounding in force; the module leaves the network
-    as it found it (the shipped model under the reference rounding)."""
+    """bind(name, rounding): the session's network initialised from the variant's bytes (image: another model's, under a name of its own) with the
+    rounding in force; the module leaves the network as it found it (the shipped model under the reference rounding)."""
     state = {"name": None}
 
-    def go(name, rounding=REF):
+    def go(name, rounding=REF, image=None):
         if state["name"] != name:
             network.set_requant_rounding(REF)
-            network.init_model(rm.build(name))
+            network.init_model(rm.build(name) if image is None else image)
             state["name"] = name
         network.set_requant_rounding(rounding)
         assert network.requant_rounding == rounding
@@ -98,16 +98,29 @@ def test_shipped_bytes_through_init_model_give_the_golden_heads(network, bind, f
 def test_requantised_model_equals_its_oracle(yf, network, bind, oracles, frames, torch_cuda, name, rounding):
     """run_device at n = 1 (the one-frame kernel), 5 (odd: an unpaired last frame) and 67 (several workgroups); the dump build at n = 2 stage by
     stage; 160x160 at n = 2; the camera entry at n = 3 -- all against Oracle(variant.yfm) in the matching oracle variant."""
-    torch, what = torch_cuda, f"{name}, rounding {mv.rounding_name(rounding)}"
+    what = f"{name}, rounding {mv.rounding_name(rounding)}"
     bind(name, rounding)
-    orc, ov = oracles(name), ORACLE_VARIANT[rounding]
-    assert ("fp32 requantisation" in network.kernel_name) == (rounding == FP32)
+    assert_network_equals_oracle(torch_cuda, network, oracles(name), ORACLE_VARIANT[rounding], frames, what, oracles("S"), fp32=rounding == FP32)
+
+
+def assert_network_equals_oracle(torch, network, orc, ov, frames, what, shipped, fp32, stages_first=False):
+    """The bound network against `orc` in oracle variant `ov`, bit for bit, through every launch form (the docstring above); its heads must not be
+    the shipped model's.  stages_first: the dump build before the heads, so that a failure names the first wrong stage, pixel and channel rather
+    than what is left of it in a head.  Also used by tests/test_quant_designs_gpu.py."""
+    assert ("fp32 requantisation" in network.kernel_name) == fp32
     ref, dump_ref = orc.run(frames["x"], dump=True, threads=16, variant=ov)
-    assert not np.array_equal(ref, oracles("S").run(frames["x"], threads=16, variant=ov))
+    assert not np.array_equal(ref, shipped.run(frames["x"], threads=16, variant=ov))
+    if stages_first:
+        _assert_stages(torch, network, frames, ref, dump_ref, what)
     for n in (1, 5, 67):
         _assert_heads(_run(torch, network, frames["d_x"], n), ref[:n], f"{what}, n = {n}")
     _assert_heads(network.run(frames["x"][:5]), ref[:5], what + " (ai_network_run)")
+    if not stages_first:
+        _assert_stages(torch, network, frames, ref, dump_ref, what)
+    _assert_160_and_camera(torch, network, orc, ov, what)
 
+
+def _assert_stages(torch, network, frames, ref, dump_ref, what):
     sizes, offs, shapes = mv.dump_layout()
     d_out = torch.zeros((2, 7, 7, 18), dtype=torch.int8, device="cuda")
     d_dump = torch.zeros((2, network.dump_bytes()), dtype=torch.int8, device="cuda")
@@ -121,6 +134,8 @@ def test_requantised_model_equals_its_oracle(yf, network, bind, oracles, frames,
     assert off == network.dump_bytes()
     _assert_heads(d_out.cpu().numpy(), ref[:2], what + " (dump build)")
 
+
+def _assert_160_and_camera(torch, network, orc, ov, what):
     x160 = mv.band_edge_frames_160()[:2]
     ref160 = orc.run(x160, threads=16, variant=ov)
     d_in = torch.from_numpy(x160).cuda()

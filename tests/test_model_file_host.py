@@ -165,22 +165,43 @@ def _leaky_lut(T, t_in, t_out):
 
 @pytest.mark.parametrize("name", ["A", "W"])
 def test_variant_tables_equal_a_numpy_restatement_on_the_models_scales(hp, name):
+    assert_tables_equal_a_numpy_restatement(hp, rm.build(name))
+
+
+def assert_tables_equal_a_numpy_restatement(hp, image, fp32=True):
     """Every pass's constants, the LUTs and the add tables of a re-quantised model, against oracle/np_restatement.py's quantize_multiplier and
-    mbqm on the scales and zero points READ FROM THE FILE (reference rounding; under fp32 the channels' float32 scale)."""
-    image = rm.build(name)
+    mbqm on the scales and zero points READ FROM THE FILE: the reference rounding; the dense passes' constants under ties_up and single, in the
+    folded sign-free form and in the four-instruction one (YF_ROUND_GENERIC_KERNELS), everything else there as under the reference rounding;
+    under fp32 (where the model is admitted) the channels' float32 scale and bias'.  Also used by tests/test_quant_designs_host.py."""
     pack = model_file.load_yfm(image)
     T, ops = pack["tensors"], pack["ops"]
     rc, text, mf = parse(hp, image)
     assert rc == 0, text
     rc, tab, ix = prepare_model(hp, mf, REF)
     assert rc == 0
-    _, tab_f, ix_f = prepare_model(hp, mf, FP32)
+    rc_f, tab_f, ix_f = prepare_model(hp, mf, FP32)
+    assert (rc_f == 0) == bool(fp32)
+    others = {r: prepare_model(hp, mf, r) for r in (TIES_UP, 3, TIES_UP | GENERIC, 3 | GENERIC)}
+    assert all(v[0] == 0 and len(v[1]) == len(tab) for v in others.values())
+
+    def check_other_forms(c_off, j, mult, rs, bias2, z, dense):
+        for r, (_, tab_r, _) in others.items():
+            got = _chan(tab_r, c_off, j)
+            if not dense:                               # depthwise passes keep the reference rounding under ties_up and single
+                assert got == _chan(tab, c_off, j), (hex(r), c_off, j)
+                continue
+            rounding = (1 << 31) + ((1 << (rs - 1)) << 32) if r & 0xFF == TIES_UP else 1 << (31 + rs)
+            if r & GENERIC:
+                want, zr = (bias2 - ACC_OFFSET) * 2 * mult + rounding + (1 << 63), ((z << rs) - (1 << 31)) % (1 << 32)
+            else:
+                want, zr = (bias2 - ACC_OFFSET) * 2 * mult + rounding + ((z << rs) << 32), 0
+            assert got == (mult, rs, zr, want % (1 << 64)), (hex(r), c_off, j)
 
     def t_in_of(op):                                # a convolution's input parameters come from the tensor before an explicit PAD
         t = ops[op]["ins"][0]
         return ops[op - 1]["ins"][0] if ops[op - 1]["op"] == 34 and ops[op - 1]["out"] == t else t
 
-    def check_channel(c_off, c_off_f, j, op, ch, taps):
+    def check_channel(c_off, c_off_f, j, op, ch, taps, dense):
         o = ops[op]
         t_in, wt, bt, to = t_in_of(op), T[o["ins"][1]], T[o["ins"][2]], T[o["out"]]
         mult, rs, zr, c64 = _chan(tab, c_off, j)
@@ -189,6 +210,9 @@ def test_variant_tables_equal_a_numpy_restatement_on_the_models_scales(hp, name)
         bias2 = int(bt["data"][ch]) - T[t_in]["zp"] * int(taps.sum())
         assert c64 == ((bias2 - ACC_OFFSET) * 2 * mult + (1 << 31) + (((1 << (rs - 1)) - 1) << 32)) % (1 << 64), (op, ch)
         assert zr == (to["zp"] + 128) << rs, (op, ch)
+        check_other_forms(c_off, j, mult, rs, bias2, to["zp"] + 128, dense)
+        if not fp32:
+            return
         fs = np.float32(np.float32(np.float32(T[t_in]["scale"][0]) * np.float32(wt["scale"][ch])) / np.float32(to["scale"][0]))
         base = c_off_f + 80 * (j // 4)
         assert struct.unpack_from("<I", tab_f, base + 4 * (j % 4))[0] == int(fs.view(np.uint32)), (op, ch)
@@ -199,7 +223,7 @@ def test_variant_tables_equal_a_numpy_restatement_on_the_models_scales(hp, name)
         w = wt["data"].reshape(wt["shape"]).astype(np.int64)
         assert d.cout == wt["shape"][0]
         for ch in range(d.cout):
-            check_channel(d.c_off, ix_f.dense[s].c_off, ch, op, ch, w[ch].reshape(-1))
+            check_channel(d.c_off, ix_f.dense[s].c_off if fp32 else 0, ch, op, ch, w[ch].reshape(-1), True)
     for s, op in enumerate(DW_OPS):
         wt, d = T[ops[op]["ins"][1]], ix.dw[s]
         c = wt["shape"][3]
@@ -207,7 +231,7 @@ def test_variant_tables_equal_a_numpy_restatement_on_the_models_scales(hp, name)
         assert ix.halo_zp[s] == T[t_in_of(op)]["zp"]
         for ch in range(c):
             g, j = divmod(ch, 4)
-            check_channel(d.g_off + g * 224 + 144, ix_f.dw[s].g_off + g * 224 + 144, j, op, ch, w[:, ch])
+            check_channel(d.g_off + g * 224 + 144, ix_f.dw[s].g_off + g * 224 + 144 if fp32 else 0, j, op, ch, w[:, ch], False)
     assert ix.in_zp == T[0]["zp"] == -128
 
     lut = np.frombuffer(tab, np.int8, N_LUT * 256, ix.lut_off).reshape(N_LUT, 256)
@@ -231,6 +255,8 @@ def test_variant_tables_equal_a_numpy_restatement_on_the_models_scales(hp, name)
         assert np.array_equal(al[s, 1], mbqm((q - a.zp2) << 20, a.m2, a.s2) + ACC_OFFSET)
         assert a.c64o[0] | (a.c64o[1] << 32) == (-ACC_OFFSET * 2 * a.mo + (1 << 31) + (((1 << (a.rso - 1)) - 1) << 32)) % (1 << 64)
         assert a.zro == (a.zpo + 128) << a.rso
+    for r, (_, tab_r, ix_r) in others.items():          # LUTs and add tables: the reference rounding's under ties_up and single
+        assert tab_r[ix.lut_off:ix.lut_off + N_LUT * 256 + 3 * 2048] == tab[ix.lut_off:ix.lut_off + N_LUT * 256 + 3 * 2048] and bytes(ix_r.add) == bytes(ix.add), hex(r)
 
 
 # ---------------------------------------------------------------------------------------------------------------- decode tables
@@ -336,6 +362,20 @@ def test_a_scale_that_drives_a_channel_out_of_the_shift_range_is_refused_by_the_
     rc, text, mf = parse(hp, model_file.write_yfm(m))
     assert rc == 0, text
     assert prepare_model(hp, mf, rounding)[0] == SHIFT_RANGE
+    # and every rule of build_chan, build_chan_fp32 and the add block from both sides (tests/quant_designs.py, admission_edges): the model one step inside
+    # is admitted and its tables are the restatement's, the one a step outside is refused -- by the roundings the rule belongs to, the others admit both
+    import quant_designs as qd
+    for rule, inside, outside, refusing, admitting in qd.admission_edges():
+        (rc_i, text_i, mf_i), (rc_o, text_o, mf_o) = parse(hp, inside), parse(hp, outside)
+        assert (rc_i, rc_o) == (0, 0), (rule, text_i, text_o)
+        for r in (rounding, 3) if rounding == TIES_UP else (rounding,):          # the single-rounding form rides with ties_up: the same kernel set
+            if r in admitting:
+                assert prepare_model(hp, mf_i, r)[0] == 0, rule
+                assert prepare_model(hp, mf_o, r)[0] == (SHIFT_RANGE if r in refusing else 0), rule
+            else:
+                assert prepare_model(hp, mf_i, r)[0] == SHIFT_RANGE, rule
+        if rounding == REF:
+            assert_tables_equal_a_numpy_restatement(hp, inside, fp32=FP32 in admitting)
 
 
 def test_table_builder_refuses_a_model_description_of_another_size(hp):
