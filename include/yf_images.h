@@ -1,5 +1,6 @@
-/* C-ABI of libyf_images.so -- decoded images of any size to the network's int8 frames, resized as OpenCV's cv2.resize does
- * (INTER_LINEAR, 11-bit fixed-point weights), and on to detection records in each image's own pixels.
+/* C-ABI of libyf_images.so -- decoded images of any size (packed BGR / RGB / BGRA / RGBA, or NV12 / NV21 decoder surfaces converted as
+ * cv2.cvtColor does) to the network's int8 frames, resized as OpenCV's cv2.resize does (INTER_LINEAR, 11-bit fixed-point weights), and on
+ * to detection records in each image's own pixels.
  *
  * This is the front half of the reference's Python caller (yoloface/tflite/tflite_prediction.py:29-37,56-61): imread (BGR), BGR -> RGB,
  * cv2.resize(img, (56, 56)), minus 128, int8; after the network, boxes scaled by W/56. and H/56.  The resize is bit-exact against
@@ -33,6 +34,10 @@ typedef struct yf_image {
 
 /* Pixel formats (bytes per pixel 3, 3, 4, 4); the alpha byte is never read.  Frames come out in RGB order whatever the format. */
 enum { YF_PIX_BGR8 = 0 /* cv2.imread */, YF_PIX_RGB8 = 1, YF_PIX_BGRA8 = 2, YF_PIX_RGBA8 = 3 };
+/* 4:2:0 semi-planar surfaces, what hardware video and JPEG decoders write: a plane of Y bytes and, at half resolution both ways, a plane
+ * of chroma byte pairs (NV12: U, V; NV21: V, U).  Only the yf_images_prepare_yuv_* entries below take them; every other entry refuses
+ * them and says so.  Out of scope: packed 4:2:2 (YUYV, UYVY), three-plane I420, BT.709, full-range variants, odd-sided surfaces. */
+enum { YF_PIX_NV12 = 4, YF_PIX_NV21 = 5 };
 
 #define YF_IMAGES_MAX_SIDE 16384   /* 1 <= height, width <= this */
 
@@ -49,6 +54,41 @@ YF_API long yf_images_prepare_device(const void* d_pixels, size_t pixels_bytes, 
  * which is never read and whose frame is written as all -128.  No load touches a byte outside an image's own extent. */
 YF_API long yf_images_prepare_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
                                             int out_hw, void* d_frames, int32_t* d_status, void* stream);
+/* ---- NV12 / NV21 surfaces -> the same frames.  frame = the frame of cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12 / _NV21) under the BGR
+ * path above, bit for bit: each of the four source pixels an output pixel samples is converted first (integer BT.601 limited range, the
+ * constants and the clamp of OpenCV 4's color_yuv.simd.hpp, stated once in csrc/yf_images_yuv.h and restated as ptq.yuv420sp_to_rgb_u8;
+ * like the resize, not pinned against a real cv2), then the bytes are interpolated.  Pixel (y, x) takes the chroma pair of UV row y >> 1
+ * at byte columns 2 * (x >> 1), + 1; chroma is not interpolated.  The surface is read where it lies: no BGR copy is made.
+ *   One surface of a ragged batch (40 bytes): height x width luma bytes, rows stride_y apart, first at offset_y; height / 2 rows of
+ *   width chroma bytes, stride_uv apart, first at offset_uv.  Valid: height and width even and in [2, 16384] (cv2 refuses odd sides),
+ *   stride_y >= width, stride_uv >= width, offset_y + (height - 1) * stride_y + width <= pixels_bytes and
+ *   offset_uv + (height / 2 - 1) * stride_uv + width <= pixels_bytes.  No alignment is asked of offsets or strides; the planes may lie
+ *   anywhere in the buffer, UV before Y included.  No load touches a byte outside a plane's extent as the descriptor states it. */
+typedef struct yf_image_yuv {
+  uint64_t offset_y, offset_uv;
+  int32_t  height, width;
+  int64_t  stride_y, stride_uv;
+} yf_image_yuv;
+/* format: YF_PIX_NV12 or YF_PIX_NV21.  Uniform: picture i's Y plane at d_pixels + i * frame_stride, its UV plane uv_offset bytes after
+ * that (uv_offset >= 0, frame_stride >= 0); every argument is checked on the host before any launch.  Ragged: the kernel checks each
+ * descriptor; an invalid one gives d_status 1 and a frame of all -128 (fp16: all 0) and is never read.  The _f16 forms write the fp16
+ * network's frames (56x56 only; see the fp16 section below).  One launch each, asynchronous on `stream`, no allocation, no host
+ * synchronisation; n = 0 launches nothing and returns 0.
+ * There are no run_decode forms: the frames are the interface.  After a YUV prepare the caller runs yf_network_run_device (56),
+ * yf_network_run_device_hw (160) or yf_network_fp16_run_device, then yf_images_decode_ragged_device, yf_images_decode160_ragged_device
+ * or yf_images_decode_f32_ragged_device with yf_image descriptors of the pictures' sizes: those three decodes read only `height` and
+ * `width` of a descriptor (offset and row_stride may be anything), so boxes come out in the Y plane's pixels.  INTEGRATION.md has the
+ * sequence. */
+YF_API long yf_images_prepare_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long stride_y,
+                                         long uv_offset, long stride_uv, long frame_stride, long n, int out_hw, void* d_frames,
+                                         void* stream);
+YF_API long yf_images_prepare_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images, long n,
+                                                int out_hw, void* d_frames, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_yuv_f16_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long stride_y,
+                                             long uv_offset, long stride_uv, long frame_stride, long n, void* d_frames_f16, void* stream);
+YF_API long yf_images_prepare_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                    long n, void* d_frames_f16, int32_t* d_status, void* stream);
+
 /* Images -> frames (the caller's workspace d_frames int8[n][56][56][3]) -> heads d_heads int8[n][7][7][18] -> yf_det records
  * d_dets[n][cap], d_counts int32[n], boxes in each image's own pixels: w_scale = (float)((double)W / 56.0), h_scale likewise (the
  * script's `W/56.` applied to a float32 array).  mode: YF_DECODE_PY (the script's), YF_DECODE_FW, YF_DECODE_FW_HOST.

@@ -9,6 +9,8 @@
 // wave take consecutive output columns, so the reads of a sampled source row coalesce.
 // The frame (or a band of 20 rows at 160x160) is staged in LDS and written with 16-byte stores.  Loads are single bytes at addresses
 // inside the image's extent: no load reaches past its last pixel.
+// prepare_yuv_kernel / prepare_yuv_f16_kernel: the same plan for NV12 / NV21 surfaces, each source pixel converted as cv2.cvtColor does
+// before the interpolation (yf_images_yuv.h).
 // The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame), decode_f32_kernel (the fp16 network's
 // float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h;
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
@@ -23,6 +25,7 @@
 #include <stdio.h>
 #include "../../include/yf_images.h"
 #include "yf_images_taps.h"
+#include "yf_images_yuv.h"
 #include "yf_images_nms.h"
 #include "yf_decode.hip.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -135,6 +138,89 @@ __global__ void __launch_bounds__(kThreads) prepare_kernel(PrepArgs a) { prepare
 // fp16 frames [n][56][56][3] for yf_network_fp16_run_device: the fp16 network has no other size
 template <int C, bool BGR, bool RAGGED>
 __global__ void __launch_bounds__(kThreads) prepare_f16_kernel(PrepArgs a) { prepare_frames<56, C, BGR, RAGGED, uint16_t>(a); }
+
+// ---- NV12 / NV21 surfaces (yf_images_yuv.h): the plan of prepare_frames with another source.  The tap tables carry the chroma offsets
+// beside the luma ones; an output pixel reads four luma bytes and the chroma pairs of its four samples (a pair shared by two columns or
+// two rows is read and converted once), converts the four source pixels and interpolates their bytes: yfi_yuv_sample, which the host
+// build calls too.  Lanes of a wave on consecutive output columns: the luma bytes and the chroma pairs of a sampled row coalesce as the
+// packed formats' pixels do, at 1 and 2 bytes per source pixel instead of 3 or 4.
+struct YuvArgs {
+  const uint8_t* px;
+  uint64_t bytes;
+  const yf_image_yuv* imgs;    // ragged
+  int32_t* status;             // ragged
+  int h, w;                    // uniform
+  int64_t sy, suv, uv_off, fs; // uniform
+  long n;
+  void* frames;
+};
+
+template <int OUT, bool VFIRST, bool RAGGED, typename T>
+__device__ __forceinline__ void prepare_yuv_frames(const YuvArgs& a) {
+  constexpr int ROWS = Band<OUT>::ROWS;
+  constexpr bool F16 = sizeof(T) == 2;
+  constexpr int FRAME_BYTES = OUT * OUT * 3 * (int)sizeof(T);
+  constexpr int BAND_VECS = ROWS * OUT * 3 * (int)sizeof(T) / 16;
+  __shared__ yfi_yuv_xtap s_xt[OUT];
+  __shared__ yfi_yuv_ytap s_yt[OUT];
+  __shared__ int4 s_stage[BAND_VECS];
+  __shared__ uint16_t s_half[F16 ? 256 : 1];
+  const int tid = threadIdx.x;
+  if constexpr (F16) s_half[tid] = yfi_f16_of_u8(tid);
+  for (long f = blockIdx.x; f < a.n; f += gridDim.x) {
+    uint64_t off_y, off_uv;
+    int h, w;
+    int64_t sy, suv;
+    if (RAGGED) {
+      const yf_image_yuv im = a.imgs[f];
+      off_y = im.offset_y; off_uv = im.offset_uv; h = im.height; w = im.width; sy = im.stride_y; suv = im.stride_uv;
+    } else {
+      off_y = (uint64_t)f * (uint64_t)a.fs; off_uv = off_y + (uint64_t)a.uv_off; h = a.h; w = a.w; sy = a.sy; suv = a.suv;
+    }
+    int4* out = (int4*)((char*)a.frames + f * FRAME_BYTES);
+    __syncthreads();                               // the previous frame's readers of the tap tables and the stage are done
+    if (RAGGED) {
+      const bool ok = yfi_yuv_image_ok(off_y, off_uv, h, w, sy, suv, a.bytes);
+      if (tid == 0) a.status[f] = ok ? 0 : 1;
+      if (!ok) {                                   // never read: the frame is all -128 (fp16: all 0)
+        const int v = F16 ? 0 : (int)0x80808080;
+        const int4 fill = make_int4(v, v, v, v);
+        for (int q = tid; q < FRAME_BYTES / 16; q += kThreads) out[q] = fill;
+        continue;
+      }
+    }
+    for (int t = tid; t < 2 * OUT; t += kThreads) {
+      if (t < OUT) s_xt[t] = yfi_yuv_xtap_of(yfi_axis_tap(t, OUT, w));
+      else s_yt[t - OUT] = yfi_yuv_ytap_of(yfi_axis_tap(t - OUT, OUT, h), sy, suv);
+    }
+    __syncthreads();
+    const uint8_t* yp = a.px + off_y;
+    const uint8_t* uvp = a.px + off_uv;
+    T* stage = (T*)s_stage;
+    for (int r0 = 0; r0 < OUT; r0 += ROWS) {
+      for (int p = tid; p < ROWS * OUT; p += kThreads) {
+        const int yy = p / OUT, xx = p - yy * OUT;
+        int32_t rgb[3];
+        yfi_yuv_sample(yp, uvp, s_xt[xx], s_yt[r0 + yy], VFIRST, rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (F16) stage[p * 3 + c] = s_half[rgb[c]];
+          else stage[p * 3 + c] = (int8_t)(rgb[c] - 128);
+        }
+      }
+      __syncthreads();
+      int4* dst = out + r0 / ROWS * BAND_VECS;
+      for (int q = tid; q < BAND_VECS; q += kThreads) dst[q] = s_stage[q];
+      __syncthreads();
+    }
+  }
+}
+
+template <int OUT, bool VFIRST, bool RAGGED>
+__global__ void __launch_bounds__(kThreads) prepare_yuv_kernel(YuvArgs a) { prepare_yuv_frames<OUT, VFIRST, RAGGED, int8_t>(a); }
+
+template <bool VFIRST, bool RAGGED>
+__global__ void __launch_bounds__(kThreads) prepare_yuv_f16_kernel(YuvArgs a) { prepare_yuv_frames<56, VFIRST, RAGGED, uint16_t>(a); }
 
 // Per-image-scale decode: one wave per frame, decode_frame of csrc/yf_decode.hip.h unchanged, the scales the script's W/56. and H/56. become
 // on a float32 array.  An image whose descriptor was flagged (status 1) or whose sides are out of range gets count 0.
@@ -353,6 +439,9 @@ int channels_of(int format) {
 
 // ---- argument checks ----  what a uniform and a ragged batch share:
 bool check_batch(int format, long n, int out_hw, const void* d_frames) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_prepare_yuv_device, yf_images_prepare_yuv_ragged_device, "
+                "yf_images_prepare_yuv_f16_device or yf_images_prepare_yuv_f16_ragged_device");
   if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
   if (out_hw != 56 && out_hw != 160) return fail("out_hw must be 56 or 160");
   if (n < 0) return fail("n < 0");
@@ -388,6 +477,50 @@ bool check_ragged(const void* d_pixels, size_t pixels_bytes, int format, const y
   if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0))
     return fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
   *a = PrepArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, n, d_frames};
+  return true;
+}
+
+// ---- NV12 / NV21 ----  what a uniform and a ragged batch of surfaces share ...
+bool check_yuv_batch(int format, long n, int out_hw, const void* d_frames) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  if (out_hw != 56 && out_hw != 160) return fail("out_hw must be 56 or 160");
+  if (n < 0) return fail("n < 0");
+  if (!d_frames || ((uintptr_t)d_frames & 15) != 0) return fail("d_frames is NULL or not 16-byte aligned");
+  return true;
+}
+
+// ... every argument of a uniform one (a->imgs == nullptr says "uniform") ...
+bool check_yuv_uniform(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long stride_y, long uv_offset,
+                       long stride_uv, long frame_stride, long n, int out_hw, void* d_frames, YuvArgs* a) {
+  if (!check_yuv_batch(format, n, out_hw, d_frames)) return false;
+  if (height < 2 || width < 2 || height > YF_IMAGES_MAX_SIDE || width > YF_IMAGES_MAX_SIDE) return fail("height and width must be in [2, 16384]");
+  if ((height & 1) != 0 || (width & 1) != 0) return fail("height and width must be even");
+  if (stride_y < (long)width) return fail("stride_y < width");
+  if (stride_uv < (long)width) return fail("stride_uv < width");
+  if (uv_offset < 0) return fail("uv_offset < 0");
+  if (frame_stride < 0) return fail("frame_stride < 0");
+  if (n > 0) {
+    if (!d_pixels) return fail("d_pixels is NULL");
+    if (!yfi_yuv_image_ok(0, (uint64_t)uv_offset, height, width, stride_y, stride_uv, pixels_bytes))
+      return fail("the first surface reaches outside [0, pixels_bytes)");
+    const uint64_t end_y = (uint64_t)(height - 1) * (uint64_t)stride_y + (uint64_t)width;
+    const uint64_t end_uv = (uint64_t)uv_offset + (uint64_t)(height / 2 - 1) * (uint64_t)stride_uv + (uint64_t)width;
+    const uint64_t extent = end_y > end_uv ? end_y : end_uv;
+    if (n > 1 && frame_stride > 0 && (uint64_t)(n - 1) > (pixels_bytes - extent) / (uint64_t)frame_stride)
+      return fail("the last surface reaches outside [0, pixels_bytes)");
+  }
+  *a = YuvArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, nullptr, nullptr, height, width, (int64_t)stride_y, (int64_t)stride_uv,
+               (int64_t)uv_offset, (int64_t)frame_stride, n, d_frames};
+  return true;
+}
+
+// ... and what the host can see of a ragged one
+bool check_yuv_ragged(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images, long n, int out_hw, void* d_frames,
+                      int32_t* d_status, YuvArgs* a) {
+  if (!check_yuv_batch(format, n, out_hw, d_frames)) return false;
+  if (n > 0 && (!d_pixels || !d_images || ((uintptr_t)d_images & 7) != 0 || !d_status || ((uintptr_t)d_status & 3) != 0))
+    return fail("d_pixels, d_images (8-byte aligned) or d_status (4-byte aligned) is NULL or misaligned");
+  *a = YuvArgs{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, 0, 0, 0, 0, 0, 0, n, d_frames};
   return true;
 }
 
@@ -477,6 +610,22 @@ long prepare_f16(int format, const PrepArgs& a, hipStream_t s) {
   const PrepKernel* k = a.imgs ? kPrepareF16<true> : kPrepareF16<false>;
   hipLaunchKernelGGL(k[format], grid_for(a.n, 6), dim3(kThreads), 0, s, a);      // LDS per workgroup: 23.5 KB
   return launched("prepare_f16 kernel launch", a.n);
+}
+
+using YuvKernel = void (*)(YuvArgs);
+template <int OUT, bool RAGGED>                                    // indexed by chroma order: NV12, NV21
+constexpr YuvKernel kPrepareYuv[2] = {prepare_yuv_kernel<OUT, false, RAGGED>, prepare_yuv_kernel<OUT, true, RAGGED>};
+template <bool RAGGED>
+constexpr YuvKernel kPrepareYuvF16[2] = {prepare_yuv_f16_kernel<false, RAGGED>, prepare_yuv_f16_kernel<true, RAGGED>};
+
+// out_hw: 56 or 160; f16: fp16 frames (56 only)
+long prepare_yuv(int out_hw, bool f16, int format, const YuvArgs& a, hipStream_t s) {
+  if (a.n == 0) return 0;
+  const YuvKernel* k = f16 ? (a.imgs ? kPrepareYuvF16<true> : kPrepareYuvF16<false>)
+                           : out_hw == 56 ? (a.imgs ? kPrepareYuv<56, true> : kPrepareYuv<56, false>)
+                                          : (a.imgs ? kPrepareYuv<160, true> : kPrepareYuv<160, false>);
+  hipLaunchKernelGGL(k[format == YF_PIX_NV21], grid_for(a.n, f16 ? 6 : 8), dim3(kThreads), 0, s, a);
+  return launched("prepare_yuv kernel launch", a.n);
 }
 
 // d_images == nullptr: the scalar scales; else per-image scales (and d_status, which may be nullptr)
@@ -631,6 +780,37 @@ YF_API long yf_images_prepare_ragged_device(const void* d_pixels, size_t pixels_
   PrepArgs a;
   if (!check_ragged(d_pixels, pixels_bytes, format, d_images, n, out_hw, d_frames, d_status, &a)) return 0;
   return prepare(out_hw, format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long stride_y,
+                                         long uv_offset, long stride_uv, long frame_stride, long n, int out_hw, void* d_frames,
+                                         void* stream) {
+  YuvArgs a;
+  if (!check_yuv_uniform(d_pixels, pixels_bytes, format, height, width, stride_y, uv_offset, stride_uv, frame_stride, n, out_hw, d_frames, &a))
+    return 0;
+  return prepare_yuv(out_hw, false, format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images, long n,
+                                                int out_hw, void* d_frames, int32_t* d_status, void* stream) {
+  YuvArgs a;
+  if (!check_yuv_ragged(d_pixels, pixels_bytes, format, d_images, n, out_hw, d_frames, d_status, &a)) return 0;
+  return prepare_yuv(out_hw, false, format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_yuv_f16_device(const void* d_pixels, size_t pixels_bytes, int format, int height, int width, long stride_y,
+                                             long uv_offset, long stride_uv, long frame_stride, long n, void* d_frames_f16, void* stream) {
+  YuvArgs a;
+  if (!check_yuv_uniform(d_pixels, pixels_bytes, format, height, width, stride_y, uv_offset, stride_uv, frame_stride, n, 56, d_frames_f16, &a))
+    return 0;
+  return prepare_yuv(56, true, format, a, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                    long n, void* d_frames_f16, int32_t* d_status, void* stream) {
+  YuvArgs a;
+  if (!check_yuv_ragged(d_pixels, pixels_bytes, format, d_images, n, 56, d_frames_f16, d_status, &a)) return 0;
+  return prepare_yuv(56, true, format, a, (hipStream_t)stream);
 }
 
 YF_API long yf_images_run_decode_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format, int height, int width,

@@ -1,4 +1,4 @@
-/* Host build of the resize arithmetic in yf_images_taps.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
+/* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
  * functions the device kernels call), and the tile grid, planner and merge of yf_images_tiles.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "yf_images_taps.h"
+#include "yf_images_yuv.h"
 #include "yf_images_nms.h"
 #include "yf_images_decode160.h"
 #include "yf_images_float.h"
@@ -77,6 +78,50 @@ EXPORT int yfi_decode160_q_threshold_host(void) { return yfi_d160_monotonic(yf_s
 
 EXPORT int yfi_image_ok_host(uint64_t offset, int64_t h, int64_t w, int64_t rs, int C, uint64_t bytes) {
   return yfi_image_ok(offset, h, w, rs, C, bytes);
+}
+
+/* ---- yf_images_yuv.h ----  (R, G, B) of n (Y, U, V) triples: yuv uint8[n][3] -> rgb uint8[n][3] */
+EXPORT void yfi_yuv_rgb_host(const uint8_t* yuv, long n, uint8_t* rgb) {
+  for (long k = 0; k < n; ++k) {
+    const int32_t yy = yfi_yuv_luma(yuv[3 * k]);
+    const yfi_chroma c = yfi_yuv_chroma(yuv[3 * k + 1], yuv[3 * k + 2]);
+    rgb[3 * k] = (uint8_t)yfi_yuv_channel(yy, c.r);
+    rgb[3 * k + 1] = (uint8_t)yfi_yuv_channel(yy, c.g);
+    rgb[3 * k + 2] = (uint8_t)yfi_yuv_channel(yy, c.b);
+  }
+}
+
+EXPORT int yfi_yuv_image_ok_host(uint64_t offset_y, uint64_t offset_uv, int64_t h, int64_t w, int64_t stride_y, int64_t stride_uv, uint64_t bytes) {
+  return yfi_yuv_image_ok(offset_y, offset_uv, h, w, stride_y, stride_uv, bytes);
+}
+
+/* One surface as prepare_yuv_kernel / prepare_yuv_f16_kernel take it: `base` + the descriptor's offsets, checked against `bytes` ->
+ * frame int8[out_hw][out_hw][3] (f16 == 0) or the fp16 bits uint16[56][56][3] (f16 != 0), through the header's tap and address
+ * functions.  Returns the status the kernel writes: 0, or 1 for an invalid descriptor, whose frame is all -128 (fp16: all 0) and which
+ * is never read.  -1: out_hw is not 56 or 160 (fp16: not 56). */
+EXPORT int yfi_prepare_yuv_host(const uint8_t* base, uint64_t bytes, const yf_image_yuv* im, int v_first, int out_hw, int f16, void* frame) {
+  if (out_hw != 56 && (f16 || out_hw != 160)) return -1;
+  const size_t count = (size_t)out_hw * (size_t)out_hw * 3;
+  if (!yfi_yuv_image_ok(im->offset_y, im->offset_uv, im->height, im->width, im->stride_y, im->stride_uv, bytes)) {
+    if (f16) memset(frame, 0, count * 2); else memset(frame, 0x80, count);
+    return 1;
+  }
+  const uint8_t* yp = base + im->offset_y;
+  const uint8_t* uvp = base + im->offset_uv;
+  for (int y = 0; y < out_hw; ++y) {
+    const yfi_yuv_ytap ty = yfi_yuv_ytap_of(yfi_axis_tap(y, out_hw, im->height), im->stride_y, im->stride_uv);
+    for (int x = 0; x < out_hw; ++x) {
+      const yfi_yuv_xtap tx = yfi_yuv_xtap_of(yfi_axis_tap(x, out_hw, im->width));
+      int32_t rgb[3];
+      yfi_yuv_sample(yp, uvp, tx, ty, v_first, rgb);
+      for (int c = 0; c < 3; ++c) {
+        const size_t at = ((size_t)y * out_hw + x) * 3 + c;
+        if (f16) ((uint16_t*)frame)[at] = yfi_f16_of_u8(rgb[c]);
+        else ((int8_t*)frame)[at] = (int8_t)(rgb[c] - 128);
+      }
+    }
+  }
+  return 0;
 }
 
 /* ---- yf_images_float.h ----  the 256 halves of v / 255. */

@@ -17,6 +17,13 @@ the decode in float32 (`run_decode_f16_ragged_device`; the arithmetic: csrc/yf_i
 records one picture's records again on the GPU: `plan_tiles` (the grid), the ragged run over the tile descriptors, `gather_tiles_device`
 (merge and translation), `nms_wide_device` across the tile borders.  The reference has no tiling; the definition is the library's own
 (csrc/yf_images_tiles.h).
+
+NV12 / NV21 surfaces -- 4:2:0 semi-planar, what hardware video and JPEG decoders write and what `detect_video` of the reference's
+yoloface/tensorflow/yoloface_test.py:318-385 has behind cv2.VideoCapture -- are read where they lie: `pack_yuv_images`, the four
+`prepare_yuv_*` bindings, and `detect` / `evaluate` with fmt="nv12" or "nv21".  The frame of a surface is the frame of
+`cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12)` under the BGR path, bit-exact against `ptq.yuv420sp_to_rgb_u8` (a restatement of OpenCV 4's
+color_yuv.simd.hpp, BT.601 limited range, not pinned against a real cv2; the arithmetic: csrc/yf_images_yuv.h).  Out of scope: YUYV / UYVY,
+I420, BT.709, full-range variants, odd-sided surfaces, and tiling (`detect_tiled`, `evaluate(tile=...)`: a tile's origin would have to be even).
 """
 import ctypes
 import os
@@ -26,7 +33,9 @@ import numpy as np
 from . import binding, libs
 
 YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8 = 0, 1, 2, 3
-FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba": YF_PIX_RGBA8}
+YF_PIX_NV12, YF_PIX_NV21 = 4, 5        # 4:2:0 semi-planar, BT.601 limited range; not YUYV / UYVY, I420, BT.709, full range or odd sides
+FORMATS = {"bgr": YF_PIX_BGR8, "rgb": YF_PIX_RGB8, "bgra": YF_PIX_BGRA8, "rgba": YF_PIX_RGBA8, "nv12": YF_PIX_NV12, "nv21": YF_PIX_NV21}
+YUV_FORMATS = (YF_PIX_NV12, YF_PIX_NV21)
 CHANNELS = {YF_PIX_BGR8: 3, YF_PIX_RGB8: 3, YF_PIX_BGRA8: 4, YF_PIX_RGBA8: 4}
 MAX_SIDE = 16384
 NMS_MAX_CAP = 256
@@ -43,6 +52,12 @@ class YfImage(ctypes.Structure):
 
 IMAGE_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("row_stride", "<i8")])
 assert IMAGE_DTYPE.itemsize == ctypes.sizeof(YfImage) == 24
+
+
+# an NV12 / NV21 surface of a ragged batch (yf_image_yuv)
+YUV_IMAGE_DTYPE = np.dtype([("offset_y", "<u8"), ("offset_uv", "<u8"), ("height", "<i4"), ("width", "<i4"), ("stride_y", "<i8"),
+                            ("stride_uv", "<i8")])
+assert YUV_IMAGE_DTYPE.itemsize == 40
 
 
 # a tile of an image (yf_tile): the image's index, the tile's origin in the image's pixels and its size
@@ -89,6 +104,11 @@ def _entries():
     return {
         "prepare_device": uniform + [ci, vp, vp],
         "prepare_ragged_device": ragged + [ci, vp, vp, vp],
+        # d_pixels, pixels_bytes, format, height, width, stride_y, uv_offset, stride_uv, frame_stride, n
+        "prepare_yuv_device": [vp, cs, ci, ci, ci, cl, cl, cl, cl, cl] + [ci, vp, vp],
+        "prepare_yuv_ragged_device": ragged + [ci, vp, vp, vp],
+        "prepare_yuv_f16_device": [vp, cs, ci, ci, ci, cl, cl, cl, cl, cl] + [vp, vp],
+        "prepare_yuv_f16_ragged_device": ragged + [vp, vp, vp],
         "run_decode_device": [vp] + uniform + [vp, vp, ci, vp, vp, ci, vp],
         "run_decode_ragged_device": [vp] + ragged + [vp, vp, ci, vp, vp, ci, vp, vp],
         "decode_ragged_device": [vp, vp, cl, ci, vp, vp, ci, vp],
@@ -151,9 +171,22 @@ def format_code(fmt):
         if fmt.lower() not in FORMATS:
             raise ValueError(f"format {fmt!r}: one of {sorted(FORMATS)}")
         return FORMATS[fmt.lower()]
-    if int(fmt) not in CHANNELS:
-        raise ValueError(f"format {fmt!r}: one of YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8")
+    if int(fmt) not in CHANNELS and int(fmt) not in YUV_FORMATS:
+        raise ValueError(f"format {fmt!r}: one of YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8, YF_PIX_RGBA8, YF_PIX_NV12, YF_PIX_NV21")
     return int(fmt)
+
+
+def is_yuv(fmt):
+    return format_code(fmt) in YUV_FORMATS
+
+
+def _packed_code(fmt, what):
+    """the code of a packed format; NV12 / NV21 have no pixels of C bytes"""
+    code = format_code(fmt)
+    if code in YUV_FORMATS:
+        raise ValueError(f"{what}: format {fmt!r} is a two-plane surface; {what} takes {sorted(k for k, v in FORMATS.items() if v in CHANNELS)}"
+                         " (NV12 / NV21: pack_yuv_images, prepare_yuv_*; tiles of such surfaces are not supported)")
+    return code
 
 
 def pack_images(images, fmt="bgr", align=16):
@@ -161,7 +194,7 @@ def pack_images(images, fmt="bgr", align=16):
     An image whose pixels lie packed along its rows (channel stride 1, pixel stride C) keeps its row stride, so a crop of a larger picture is
     copied as the span from its first to its last pixel, parent row stride and all; any other layout is made contiguous first.  Every image
     starts on an `align`-byte boundary.  Negative strides are refused."""
-    code = format_code(fmt)
+    code = _packed_code(fmt, "pack_images")
     C = CHANNELS[code]
     spans, desc, off = [], np.zeros(len(images), IMAGE_DTYPE), 0
     for i, img in enumerate(images):
@@ -188,6 +221,71 @@ def pack_images(images, fmt="bgr", align=16):
     return buf, desc
 
 
+def _plane_span(a, i, what):
+    """a plane uint8 [rows, W] whose bytes lie along its rows -> (the bytes from its first to its last as one view, its row pitch); any
+    other layout is made contiguous first"""
+    rows, w = a.shape
+    if any(s < 0 for s in a.strides):
+        raise ValueError(f"image {i}: negative strides {a.strides} of the {what} plane (flip with np.ascontiguousarray first)")
+    if not (a.strides[1] == 1 and (rows == 1 or a.strides[0] >= w)):
+        a = np.ascontiguousarray(a)
+    pitch = a.strides[0] if rows > 1 else w
+    return np.lib.stride_tricks.as_strided(a, shape=((rows - 1) * pitch + w,), strides=(1,)), pitch
+
+
+def pack_yuv_images(images, fmt, align=16):
+    """NV12 / NV21 surfaces -> (pixels uint8[bytes], descriptors YUV_IMAGE_DTYPE[n]).  An image is cv2's layout, one uint8 [H * 3 / 2, W]
+    array (H rows of Y, then H / 2 rows of chroma byte pairs), or a pair (y [H, W], uv [H / 2, W]) of arrays or views, which may carry
+    their own row pitches: a plane whose bytes lie along its rows keeps its pitch, as `pack_images` keeps a crop's.  Every plane starts on
+    an `align`-byte boundary, a surface's Y plane before its UV plane.  Odd sides (cv2 refuses them too), sides outside 2..16384, other
+    dtypes or shapes and negative strides are refused."""
+    code = format_code(fmt)
+    if code not in YUV_FORMATS:
+        raise ValueError(f"pack_yuv_images: format {fmt!r}: 'nv12' or 'nv21'")
+    spans, desc, off = [], np.zeros(len(images), YUV_IMAGE_DTYPE), 0
+    for i, img in enumerate(images):
+        if isinstance(img, (tuple, list)):
+            if len(img) != 2:
+                raise ValueError(f"image {i}: a pair (y, uv) or one [H * 3 / 2, W] array, got {len(img)} planes")
+            y, uv = np.asarray(img[0]), np.asarray(img[1])
+        else:
+            a = np.asarray(img)
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError(f"image {i}: expected uint8 [H * 3 / 2, W] or a pair (y, uv), got {a.dtype} {a.shape}")
+            if a.shape[0] % 3 != 0:
+                raise ValueError(f"image {i}: {a.shape[0]} rows are not H * 3 / 2 of an even H (odd sides are refused)")
+            h = a.shape[0] // 3 * 2
+            y, uv = a[:h], a[h:]
+        if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or uv.ndim != 2:
+            raise ValueError(f"image {i}: expected uint8 planes y [H, W] and uv [H / 2, W], got {y.dtype} {y.shape} and {uv.dtype} {uv.shape}")
+        h, w = y.shape
+        if h % 2 or w % 2:
+            raise ValueError(f"image {i}: {h}x{w} has an odd side (NV12 / NV21 surfaces have even sides)")
+        if not (2 <= h <= MAX_SIDE and 2 <= w <= MAX_SIDE):
+            raise ValueError(f"image {i}: {h}x{w} is outside 2..{MAX_SIDE} per side")
+        if uv.shape != (h // 2, w):
+            raise ValueError(f"image {i}: the uv plane is {uv.shape}, a {h}x{w} surface has {(h // 2, w)}")
+        y_span, sy = _plane_span(y, i, "y")
+        uv_span, suv = _plane_span(uv, i, "uv")
+        off = -(-off // align) * align
+        off_y = off
+        off = -(-(off + y_span.shape[0]) // align) * align
+        desc[i] = (off_y, off, h, w, sy, suv)
+        spans += [(off_y, y_span), (off, uv_span)]
+        off += uv_span.shape[0]
+    buf = np.zeros(max(off, 1), np.uint8)
+    for o, span in spans:
+        buf[o:o + span.shape[0]] = span
+    return buf, desc
+
+
+def yuv_sizes(desc):
+    """YUV_IMAGE_DTYPE[n] -> IMAGE_DTYPE[n] for the ragged decodes, which read only height and width: boxes in the Y plane's pixels"""
+    out = np.zeros(desc.shape[0], IMAGE_DTYPE)
+    out["height"], out["width"], out["row_stride"] = desc["height"], desc["width"], desc["width"]
+    return out
+
+
 def _call(name, n, *args):
     """yf_images_<name>(*args), which returns n or fails with a text"""
     lib = load()
@@ -210,6 +308,51 @@ def prepare_device(d_pixels, pixels_bytes, fmt, height, width, row_stride, frame
 
 def prepare_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, stream=None):
     _call("prepare_ragged_device", n, d_pixels, pixels_bytes, format_code(fmt), d_images, n, out_hw, d_frames, d_status, stream)
+
+
+def _yuv_code(fmt):
+    code = format_code(fmt)
+    if code not in YUV_FORMATS:
+        raise ValueError(f"format {fmt!r}: 'nv12' or 'nv21'")
+    return code
+
+
+def prepare_yuv_device(d_pixels, pixels_bytes, fmt, height, width, stride_y, uv_offset, stride_uv, frame_stride, n, out_hw, d_frames, stream=None):
+    """n NV12 / NV21 surfaces of height x width -> int8 frames (yf_images_prepare_yuv_device): surface i's Y plane at i * frame_stride, its
+    UV plane uv_offset bytes after that."""
+    _call("prepare_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), height, width, stride_y, uv_offset, stride_uv, frame_stride, n, out_hw,
+          d_frames, stream)
+
+
+def prepare_yuv_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, stream=None):
+    """d_images: YUV_IMAGE_DTYPE[n] on the device (yf_images_prepare_yuv_ragged_device)"""
+    _call("prepare_yuv_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, out_hw, d_frames, d_status, stream)
+
+
+def prepare_yuv_f16_device(d_pixels, pixels_bytes, fmt, height, width, stride_y, uv_offset, stride_uv, frame_stride, n, d_frames_f16, stream=None):
+    _call("prepare_yuv_f16_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), height, width, stride_y, uv_offset, stride_uv, frame_stride, n,
+          d_frames_f16, stream)
+
+
+def prepare_yuv_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, stream=None):
+    _call("prepare_yuv_f16_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, d_frames_f16, d_status, stream)
+
+
+def _run_yuv_ragged(network, d_px, nbytes, fmt, d_yuv_desc, d_desc, n, d_frames, d_heads, d_dets, d_counts, cap, d_status, size, f16, s):
+    """What the run_decode_*_ragged_device entries do for packed pixels, for NV12 / NV21 surfaces, on stream `s`: the YUV prepare, the
+    network's device run, the ragged decode of that size and dtype with the descriptors of the pictures' sizes (d_desc, IMAGE_DTYPE)."""
+    if f16:
+        prepare_yuv_f16_ragged_device(d_px, nbytes, fmt, d_yuv_desc, n, d_frames, d_status, stream=s)
+        network.fp16_run_device(d_frames, d_heads, n, stream=s)
+        decode_f32_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, d_status=d_status, stream=s)
+        return
+    prepare_yuv_ragged_device(d_px, nbytes, fmt, d_yuv_desc, n, size, d_frames, d_status, stream=s)
+    if size == 56:
+        network.run_device(d_frames, d_heads, n, stream=s)
+        decode_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, stream=s)
+    else:
+        network.run_device_hw(size, size, d_frames, d_heads, n, stream=s)
+        decode160_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, d_status=d_status, stream=s)
 
 
 def run_decode_device(network, d_pixels, pixels_bytes, fmt, height, width, row_stride, frame_stride, n, d_frames, d_heads, d_dets, d_counts,
@@ -332,7 +475,7 @@ def plan_tiles(shapes_or_descriptors, fmt, tile, stride=None, whole=True):
     (y, x); stride=None means the tile side, so no overlap.  Per axis of length L: one tile [0, L) if L <= T, else
     (L - T + S - 1) // S + 1 tiles of side T, the last one flush with the edge; row-major, y outer.  `whole`: an image of more than one
     tile gets the whole image as its first tile.  Image i's tiles are first[i] .. first[i + 1]."""
-    code = format_code(fmt)
+    code = _packed_code(fmt, "plan_tiles")
     C = CHANNELS[code]
     if isinstance(shapes_or_descriptors, np.ndarray) and shapes_or_descriptors.dtype == IMAGE_DTYPE:
         desc = np.ascontiguousarray(shapes_or_descriptors).reshape(-1)
@@ -404,10 +547,16 @@ def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, d
     if cap is None:
         cap = 3 * grid * grid
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    buf, desc = pack_images(images, fmt) if packed is None else packed
+    yuv_desc = None
+    if packed is None and is_yuv(fmt):
+        buf, yuv_desc = pack_yuv_images(images, fmt)
+        desc = yuv_sizes(yuv_desc)
+    else:
+        buf, desc = pack_images(images, fmt) if packed is None else packed
     n = desc.shape[0]
     d_px = torch.from_numpy(buf).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    d_yuv_desc = None if yuv_desc is None else torch.from_numpy(yuv_desc.view(np.uint8)).to(dev)
     f16 = dtype == "fp16"
     d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
     d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
@@ -420,11 +569,15 @@ def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, d
         run = run_decode_f16_ragged_device
     else:
         set_decode_tables(*network.decode_tables())
-    run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
-        d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    if d_yuv_desc is not None:
+        _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_yuv_desc.data_ptr(), d_desc.data_ptr(), n, d_frames.data_ptr(),
+                        d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, stream.cuda_stream)
+    else:
+        run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
+            d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
     if iou_threshold is not None:
         nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
-    return d_dets, d_counts, d_status, stream, (d_px, d_desc, d_frames, d_heads)
+    return d_dets, d_counts, d_status, stream, (d_px, d_desc, d_yuv_desc, d_frames, d_heads)
 
 
 def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None,
@@ -438,6 +591,8 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     `pack_images` produces none) raises ImagesError.
     Returns {"ap", "detections", "ground_truths", "true_positives", "precision", "recall"}; the last two are the end of the curve:
     true_positives / (detections + 1e-16) and true_positives / max(1, ground_truths)."""
+    if tile is not None:
+        _packed_code(fmt, "evaluate(tile=...)")
     n = len(images)
     if len(ground_truths) != n:
         raise ValueError(f"{n} images, {len(ground_truths)} lists of ground truths")
@@ -522,6 +677,7 @@ def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_
     stream.  Returns one int32 [k, 4] array (x1, y1, x2, y2) per image: with iou_threshold=None the merged records in tile order, each
     tile's in decode order; with a float the kept ones in keep order.  out_cap: the merged records an image can hold (at most 1200); an
     image with more raises ImagesError naming the image and its total."""
+    _packed_code(fmt, "detect_tiled")
     n = len(images)
     if n == 0:
         return []
@@ -548,7 +704,10 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     heads, which find smaller faces; suppression through nms_wide_device); cap=None holds every candidate: 147 / 1200.
     dtype: "int8" (the quantised network) or "fp16" -- the fp16 network, which makes this h5_predition.py:29-73 for the batch: fp16 frames
     of pixel / 255., float32 logits, the float32 decode (`run_decode_f16_ragged_device`).  Call `network.fp16_init()` first, as for
-    `fp16_run_device`: detect does not do it.  The fp16 network exists at 56 only."""
+    `fp16_run_device`: detect does not do it.  The fp16 network exists at 56 only.
+    fmt="nv12" / "nv21": `images` are surfaces as `pack_yuv_images` takes them; the sequence is the YUV prepare, the network's device run
+    and the ragged decode of that size and dtype, on one stream, and the boxes are in the Y plane's pixels -- those of
+    cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12) under fmt="bgr"."""
     if size not in (56, 160):
         raise ValueError(f"size {size!r}: 56 or 160")
     if dtype not in ("int8", "fp16"):
@@ -563,9 +722,15 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     if n == 0:
         return []
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    buf, desc = pack_images(images, fmt)
+    yuv_desc = None
+    if is_yuv(fmt):
+        buf, yuv_desc = pack_yuv_images(images, fmt)
+        desc = yuv_sizes(yuv_desc)
+    else:
+        buf, desc = pack_images(images, fmt)
     d_px = torch.from_numpy(buf).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    d_yuv_desc = None if yuv_desc is None else torch.from_numpy(yuv_desc.view(np.uint8)).to(dev)
     f16 = dtype == "fp16"
     d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
     d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
@@ -578,8 +743,12 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
         run = run_decode_f16_ragged_device
     else:
         set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
-    run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
-        d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
+    if d_yuv_desc is not None:
+        _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_yuv_desc.data_ptr(), d_desc.data_ptr(), n, d_frames.data_ptr(),
+                        d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, stream.cuda_stream)
+    else:
+        run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
+            d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
     if iou_threshold is not None:
         nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
     stream.synchronize()

@@ -331,3 +331,30 @@ def resize_linear_u8(img, out_w, out_h):
     r0, r1 = rows[yi], rows[yi1]
     out = (((yb0[:, None, None] * (r0 >> 4)) >> 16) + ((yb1[:, None, None] * (r1 >> 4)) >> 16) + 2) >> 2
     return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def yuv420sp_to_rgb_u8(y, uv, v_first=False):
+    """OpenCV's `cv2.cvtColor(yuv, cv2.COLOR_YUV2RGB_NV12)` (v_first: `_NV21`) for a 4:2:0 semi-planar surface, restated from the published
+    algorithm (imgproc/src/color_yuv.simd.hpp, YUV420sp -> RGB: BT.601 limited range in 20-bit fixed point) and, like `resize_linear_u8`,
+    not pinned against a real cv2.  `y` uint8 [H, W], `uv` uint8 [H / 2, W] of byte pairs (U, V; v_first: V, U), H and W even -> uint8
+    [H, W, 3] in RGB order (`[..., ::-1]` is COLOR_YUV2BGR_*).  Pixel (r, c) takes the pair of UV row r >> 1 at columns 2 * (c >> 1), + 1;
+    chroma is not interpolated.  int32 suffices (the largest magnitude is about 5.6e8); `>>` of a negative is arithmetic.
+        yy = max(0, Y - 16) * 1220542;  uu = U - 128;  vv = V - 128
+        R = clamp8((yy + (1 << 19) + 1673527 * vv) >> 20)
+        G = clamp8((yy + (1 << 19) - 852492 * vv - 409993 * uu) >> 20)
+        B = clamp8((yy + (1 << 19) + 2116026 * uu) >> 20)"""
+    y, uv = np.asarray(y), np.asarray(uv)
+    if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or uv.ndim != 2:
+        raise ValueError(f"expected uint8 planes [H, W] and [H / 2, W], got {y.dtype} {y.shape} and {uv.dtype} {uv.shape}")
+    h, w = y.shape
+    if h % 2 or w % 2 or uv.shape != (h // 2, w):
+        raise ValueError(f"Y plane {y.shape}, UV plane {uv.shape}: even sides and a UV plane of [H / 2, W]")
+    first = np.repeat(np.repeat(uv[:, 0::2], 2, axis=0), 2, axis=1).astype(np.int32)
+    second = np.repeat(np.repeat(uv[:, 1::2], 2, axis=0), 2, axis=1).astype(np.int32)
+    uu, vv = ((second, first) if v_first else (first, second))
+    uu, vv = uu - 128, vv - 128
+    yy = np.maximum(0, y.astype(np.int32) - 16) * np.int32(1220542) + np.int32(1 << 19)
+    r = (yy + 1673527 * vv) >> 20
+    g = (yy - 852492 * vv - 409993 * uu) >> 20
+    b = (yy + 2116026 * uu) >> 20
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
