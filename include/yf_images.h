@@ -302,6 +302,49 @@ YF_API long   yf_images_gather_tiles_device(const void* d_dets, const void* d_co
                                             void* d_out, void* d_out_counts, int out_cap,
                                             void* d_work, size_t work_bytes, void* stream);
 
+/* ---- face chips: every record's region cut from its picture and resized to one fixed size, what a recogniser, a landmark model or a
+ * blur filter takes next -- from the source where it lies, packed pixels or an NV12 / NV21 surface, without the records leaving the
+ * device.  The reference stops at the boxes (cv2.rectangle, yoloface/tflite/tflite_prediction.py:64): the region rule, the order of the
+ * chips and the status codes are this library's own definition, stated once in csrc/yf_images_crop.h, which the kernels and a host build
+ * share.  A C host's sequence: any run above, a suppression, the crop -- INTEGRATION.md.
+ *   input:  d_dets yf_det[n][cap], d_counts int32[n], as any decode, suppression or tile merge above writes them; of frame i the first
+ *           m_i = min(max(count, 0), cap) records are read, the suppression's clamp.  1 <= cap <= YF_IMAGES_NMS_WIDE_MAX_CAP,
+ *           n * cap < 2^31.  The picture of frame i is descriptor i of d_images (yf_image for the four packed formats, yf_image_yuv for
+ *           NV12 / NV21); the kernel checks each descriptor exactly as the ragged prepares do.  After a tile merge the pictures are the
+ *           parents.
+ *   order:  chip k = first[i] + s is slot s of frame i; d_first int32[n + 1] (written) is the exclusive prefix of the m_i, first[n] the
+ *           true total, which may exceed chips_cap.  Only chips k < chips_cap are written; chip slots and info rows at and beyond
+ *           min(total, chips_cap) are not touched.
+ *   region: int64 arithmetic on the int32 edges, which are inclusive.  bw = x2 - x1 + 1, bh = y2 - y1 + 1, either < 1: status 1.
+ *           Margin: mx = bw * margin_permille / 1000, my likewise (floor); x1 -= mx, x2 += mx, y1 -= my, y2 += my.  With
+ *           YF_CROP_SQUARE: side = max(x2 - x1 + 1, y2 - y1 + 1), x1 -= (side - (x2 - x1 + 1)) / 2, x2 = x1 + side - 1, y likewise.
+ *           Clamp to [0, W - 1] x [0, H - 1]; x1 > x2 or y1 > y2: status 1.  The region is not squared again after the clamp.
+ *   chip:   cv2.resize(P[y1 : y2 + 1, x1 : x2 + 1], (out_w, out_h)), INTER_LINEAR as everywhere in this library; P the picture's three
+ *           colour bytes, or the converted surface (each sampled pixel converted first, its chroma pair taken by its absolute row and
+ *           column in the surface, so odd origins and odd sides are right).  out_format, YF_PIX_RGB8 or YF_PIX_BGR8, is the byte order of
+ *           the chip.  d_chips uint8 [chips_cap][out_h][out_w][3], 16-byte aligned; out_h and out_w multiples of 16 in [16, 256].
+ *   info:   d_info yf_chip[chips_cap]: the frame, the slot, the region actually sampled (x0, y0, width, height: chip pixel (cx, cy) lies
+ *           near picture pixel (x0 + cx * width / out_w, y0 + cy * height / out_h)) and the status: 0 a chip, 1 an empty region, 2 the
+ *           picture's descriptor is invalid (checked first: every record of such a picture has status 2).  A chip of status 1 or 2 is
+ *           all zero bytes, its picture is never read, and x0 = y0 = width = height = 0.
+ *   safety: counts and records are device memory that may hold anything; every index derived from them is range-checked before use, and
+ *           no load leaves a picture's extent as its descriptor states it.
+ * Two launches (a scan of the clamped counts into d_first, one workgroup per chip that exists) whose cost follows the records, never cap
+ * or chips_cap; asynchronous on `stream`, no allocation, no host synchronisation, capturable; every argument is checked before the first
+ * launch, and each entry refuses the other family's formats with a text.  Every pointer must be valid (d_dets, d_counts, d_first and
+ * d_info 4-byte aligned, d_images 8-byte aligned) for an empty batch too.  Returns n; n = 0 launches nothing and returns 0, after the
+ * checks. */
+typedef struct yf_chip { int32_t frame, slot, x0, y0, width, height, status; } yf_chip;     /* 28 bytes */
+#define YF_CROP_SQUARE 1
+YF_API long yf_images_crop_records_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images,
+                                          const void* d_dets, const void* d_counts, long n, int cap, int out_h, int out_w,
+                                          int out_format, int margin_permille, int flags, void* d_chips, long chips_cap,
+                                          int32_t* d_first, yf_chip* d_info, void* stream);
+YF_API long yf_images_crop_records_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int out_h, int out_w,
+                                              int out_format, int margin_permille, int flags, void* d_chips, long chips_cap,
+                                              int32_t* d_first, yf_chip* d_info, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

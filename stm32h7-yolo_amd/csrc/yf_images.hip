@@ -14,7 +14,8 @@
 // The other kernels: decode_ragged_kernel (7x7 heads, each image's own scales, one wave per frame), decode_f32_kernel (the fp16 network's
 // float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h;
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
-// tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h.
+// tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h; the face chips (every record's region of its picture,
+// resized) in yf_images_crop.h and yf_images_crop.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@
 #include "yf_images_wide.hip.h"
 #include "yf_images_eval.hip.h"
 #include "yf_images_tiles.hip.h"
+#include "yf_images_crop.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -761,6 +763,59 @@ long run_decode_f16(ai_handle net, int format, const PrepArgs& a, void* d_logits
   return decode_f32(d_logits, a.imgs, a.status, a.n, w_scale, h_scale, d_dets, d_counts, cap, (hipStream_t)stream);
 }
 
+// ---- face chips (yf_images_crop.h) ----  the chip kernels by source format (the four packed formats in the order of their codes,
+// then NV12, NV21) and by the chip's byte order (RGB, BGR): a packed kernel knows only whether the two orders differ
+using CropKernel = void (*)(yfcrop::Args);
+constexpr CropKernel kChips[6][2] = {{yfcrop::chips_kernel<3, true>, yfcrop::chips_kernel<3, false>},       // BGR8
+                                     {yfcrop::chips_kernel<3, false>, yfcrop::chips_kernel<3, true>},       // RGB8
+                                     {yfcrop::chips_kernel<4, true>, yfcrop::chips_kernel<4, false>},       // BGRA8
+                                     {yfcrop::chips_kernel<4, false>, yfcrop::chips_kernel<4, true>},       // RGBA8
+                                     {yfcrop::chips_yuv_kernel<false, false>, yfcrop::chips_yuv_kernel<false, true>},
+                                     {yfcrop::chips_yuv_kernel<true, false>, yfcrop::chips_yuv_kernel<true, true>}};
+static_assert(YF_PIX_NV12 == 4 && YF_PIX_NV21 == 5, "the order of kChips");
+
+// workgroups of chip kernel `which` that fit on a CU at once, from the runtime's occupancy query (asked once per kernel; 4 if it fails)
+int chips_per_cu(int format, int bgr) {
+  static std::mutex mu;
+  static int cached[6][2];
+  std::lock_guard<std::mutex> lk(mu);
+  int& c = cached[format][bgr];
+  if (c == 0) {
+    int blocks = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kChips[format][bgr], yfcrop::kThreads, 0) != hipSuccess || blocks <= 0) {
+      (void)hipGetLastError();
+      blocks = 4;
+    }
+    c = blocks > 8 ? 8 : blocks;
+  }
+  return c;
+}
+
+// both entries behind their format check: every other argument, then the scan and the chips
+long crop_records(const void* d_pixels, size_t pixels_bytes, int format, const void* d_images, const void* d_dets, const void* d_counts, long n,
+                  int cap, int out_h, int out_w, int out_format, int margin_permille, int flags, void* d_chips, long chips_cap, int32_t* d_first,
+                  yf_chip* d_info, void* stream) {
+  const char* err = yfi_crop_check(n, cap, out_h, out_w, out_format, margin_permille, flags, chips_cap);
+  if (err) return fail("%s", err);
+  if (!d_dets || !d_counts || !d_first || !d_info) return fail("d_dets, d_counts, d_first or d_info is NULL");
+  if ((((uintptr_t)d_dets | (uintptr_t)d_counts | (uintptr_t)d_first | (uintptr_t)d_info) & 3) != 0)
+    return fail("d_dets, d_counts, d_first and d_info must be 4-byte aligned");
+  if (!d_chips || ((uintptr_t)d_chips & 15) != 0) return fail("d_chips is NULL or not 16-byte aligned");
+  if (!d_pixels) return fail("d_pixels is NULL");
+  if (!d_images || ((uintptr_t)d_images & 7) != 0) return fail("d_images is NULL or not 8-byte aligned");
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yfcrop::first_kernel, dim3(1), dim3(yfcrop::kThreads), 0, s, (const int*)d_counts, n, cap, d_first);
+  const long most = n * (long)cap < chips_cap ? n * (long)cap : chips_cap;            // no more chips than that can exist
+  if (most > 0) {
+    const yfcrop::Args a{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, (const yf_det*)d_dets, (const int*)d_counts, n, cap, out_h,
+                         out_w, margin_permille, flags, (uint8_t*)d_chips, chips_cap, d_first, d_info};
+    const int bgr = out_format == YF_PIX_BGR8;
+    hipLaunchKernelGGL(kChips[format][bgr], grid_for(most, chips_per_cu(format, bgr)), dim3(yfcrop::kThreads), 0, s, a);
+  }
+  return launched("crop_records kernel launches", n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1038,6 +1093,26 @@ YF_API long yf_images_gather_tiles_device(const void* d_dets, const void* d_coun
   hipLaunchKernelGGL(yftiles::copy_kernel, grid_for(groups, 8), dim3(yftiles::kThreads), 0, s, (const uint32_t*)d_dets, (const int*)d_counts,
                      (int)t, cap, d_tiles, d_first, n, (const int32_t*)d_work, (uint32_t*)d_out, out_cap);
   return launched("gather_tiles kernel launches", n);
+}
+
+YF_API long yf_images_crop_records_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                          const void* d_counts, long n, int cap, int out_h, int out_w, int out_format, int margin_permille,
+                                          int flags, void* d_chips, long chips_cap, int32_t* d_first, yf_chip* d_info, void* stream) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_crop_records_yuv_device");
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  return crop_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, out_h, out_w, out_format, margin_permille, flags,
+                      d_chips, chips_cap, d_first, d_info, stream);
+}
+
+YF_API long yf_images_crop_records_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int out_h, int out_w, int out_format,
+                                              int margin_permille, int flags, void* d_chips, long chips_cap, int32_t* d_first,
+                                              yf_chip* d_info, void* stream) {
+  if (channels_of(format)) return fail("format YF_PIX_BGR8 / RGB8 / BGRA8 / RGBA8: packed pixels go through yf_images_crop_records_device");
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  return crop_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, out_h, out_w, out_format, margin_permille, flags,
+                      d_chips, chips_cap, d_first, d_info, stream);
 }
 
 }  // extern "C"

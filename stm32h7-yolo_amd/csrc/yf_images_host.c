@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), and the tile grid, planner and merge of yf_images_tiles.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h and the face chips of yf_images_crop.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -13,6 +13,7 @@
 #include "yf_images_float.h"
 #include "yf_images_eval.h"
 #include "yf_images_tiles.h"
+#include "yf_images_crop.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -287,4 +288,100 @@ EXPORT long yfi_gather_tiles_host(const yf_det* dets, const int32_t* counts, lon
     out_counts[i] = (int32_t)total;
   }
   return n;
+}
+
+/* ---- yf_images_crop.h ----  yf_images_crop_records_device / _yuv_device as the header states them: the exclusive prefix of the clamped
+ * counts into first[n + 1], then chip by chip the record's region and its resize through the header's tap function, for the chips below
+ * chips_cap; chip slots and info rows at and beyond min(total, chips_cap) are not touched.  `images`: yf_image[n] (packed formats) or
+ * yf_image_yuv[n] (NV12 / NV21), offsets from `base`, checked against `bytes`.  Returns n, or -1 for arguments the device entries refuse. */
+static void crop_packed(const uint8_t* base, const yf_image* im, int C, int src_bgr, int out_bgr, const yf_chip* r, int out_h, int out_w,
+                        uint8_t* chip) {
+  const int swap = src_bgr != out_bgr;
+  for (int y = 0; y < out_h; ++y) {
+    const yfi_tap ty = yfi_crop_tap(y, out_h, r->y0, r->height);
+    const uint8_t* r0 = base + im->offset + (uint64_t)ty.s0 * (uint64_t)im->row_stride;
+    const uint8_t* r1 = base + im->offset + (uint64_t)ty.s1 * (uint64_t)im->row_stride;
+    for (int x = 0; x < out_w; ++x) {
+      const yfi_tap tx = yfi_crop_tap(x, out_w, r->x0, r->width);
+      for (int c = 0; c < 3; ++c) {
+        const int sc = swap ? 2 - c : c;
+        const int32_t h0 = yfi_hpass(r0[tx.s0 * C + sc], r0[tx.s1 * C + sc], tx.w0, tx.w1);
+        const int32_t h1 = yfi_hpass(r1[tx.s0 * C + sc], r1[tx.s1 * C + sc], tx.w0, tx.w1);
+        chip[((size_t)y * out_w + x) * 3 + c] = (uint8_t)yfi_vpass(h0, h1, ty.w0, ty.w1);
+      }
+    }
+  }
+}
+
+static void crop_yuv(const uint8_t* base, const yf_image_yuv* im, int v_first, int out_bgr, const yf_chip* r, int out_h, int out_w,
+                     uint8_t* chip) {
+  for (int y = 0; y < out_h; ++y) {
+    const yfi_yuv_ytap ty = yfi_yuv_ytap_of(yfi_crop_tap(y, out_h, r->y0, r->height), im->stride_y, im->stride_uv);
+    for (int x = 0; x < out_w; ++x) {
+      const yfi_yuv_xtap tx = yfi_yuv_xtap_of(yfi_crop_tap(x, out_w, r->x0, r->width));
+      int32_t rgb[3];
+      yfi_yuv_sample(base + im->offset_y, base + im->offset_uv, tx, ty, v_first, rgb);
+      for (int c = 0; c < 3; ++c) chip[((size_t)y * out_w + x) * 3 + c] = (uint8_t)rgb[out_bgr ? 2 - c : c];
+    }
+  }
+}
+
+static long crop_records(const uint8_t* base, uint64_t bytes, int format, const void* images, const yf_det* dets, const int32_t* counts, long n,
+                         int cap, int out_h, int out_w, int out_format, int margin_permille, int flags, uint8_t* chips, long chips_cap,
+                         int32_t* first, yf_chip* info) {
+  if (yfi_crop_check(n, cap, out_h, out_w, out_format, margin_permille, flags, chips_cap) != NULL) return -1;
+  if (!dets || !counts || !first || !info || !chips || !base || !images) return -1;
+  if (n == 0) return 0;
+  const int yuv = format == YF_PIX_NV12 || format == YF_PIX_NV21;
+  const int C = yfi_tiles_channels(format), out_bgr = out_format == YF_PIX_BGR8;
+  const size_t chip_bytes = (size_t)out_h * (size_t)out_w * 3;
+  int64_t k = 0;
+  for (long i = 0; i < n; ++i) {
+    const int m = yfi_crop_clamp(counts[i], cap);
+    first[i] = (int32_t)k;
+    for (int s = 0; s < m; ++s, ++k) {
+      if (k >= (int64_t)chips_cap) continue;
+      const yf_det* d = &dets[i * cap + s];
+      uint8_t* chip = chips + (size_t)k * chip_bytes;
+      yf_chip r = {(int32_t)i, s, 0, 0, 0, 0, 2};
+      if (yuv) {
+        const yf_image_yuv* im = (const yf_image_yuv*)images + i;
+        if (yfi_yuv_image_ok(im->offset_y, im->offset_uv, im->height, im->width, im->stride_y, im->stride_uv, bytes))
+          r.status = yfi_crop_region(d->x1, d->y1, d->x2, d->y2, im->width, im->height, margin_permille, flags, &r);
+        if (r.status == 0) crop_yuv(base, im, format == YF_PIX_NV21, out_bgr, &r, out_h, out_w, chip);
+      } else {
+        const yf_image* im = (const yf_image*)images + i;
+        if (yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes))
+          r.status = yfi_crop_region(d->x1, d->y1, d->x2, d->y2, im->width, im->height, margin_permille, flags, &r);
+        if (r.status == 0) crop_packed(base, im, C, format == YF_PIX_BGR8 || format == YF_PIX_BGRA8, out_bgr, &r, out_h, out_w, chip);
+      }
+      if (r.status != 0) memset(chip, 0, chip_bytes);
+      info[k] = r;
+    }
+  }
+  first[n] = (int32_t)k;
+  return n;
+}
+
+EXPORT long yfi_crop_records_host(const uint8_t* base, uint64_t bytes, int format, const yf_image* images, const yf_det* dets,
+                                  const int32_t* counts, long n, int cap, int out_h, int out_w, int out_format, int margin_permille, int flags,
+                                  uint8_t* chips, long chips_cap, int32_t* first, yf_chip* info) {
+  if (!yfi_tiles_channels(format)) return -1;
+  return crop_records(base, bytes, format, images, dets, counts, n, cap, out_h, out_w, out_format, margin_permille, flags, chips, chips_cap,
+                      first, info);
+}
+
+EXPORT long yfi_crop_records_yuv_host(const uint8_t* base, uint64_t bytes, int format, const yf_image_yuv* images, const yf_det* dets,
+                                      const int32_t* counts, long n, int cap, int out_h, int out_w, int out_format, int margin_permille,
+                                      int flags, uint8_t* chips, long chips_cap, int32_t* first, yf_chip* info) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return -1;
+  return crop_records(base, bytes, format, images, dets, counts, n, cap, out_h, out_w, out_format, margin_permille, flags, chips, chips_cap,
+                      first, info);
+}
+
+/* the region rule alone: out[5] = {x0, y0, width, height, status} */
+EXPORT void yfi_crop_region_host(int32_t x1, int32_t y1, int32_t x2, int32_t y2, int32_t W, int32_t H, int margin_permille, int flags, int32_t* out) {
+  yf_chip r;
+  const int st = yfi_crop_region(x1, y1, x2, y2, W, H, margin_permille, flags, &r);
+  out[0] = r.x0; out[1] = r.y0; out[2] = r.width; out[3] = r.height; out[4] = st;
 }

@@ -18,6 +18,10 @@ records one picture's records again on the GPU: `plan_tiles` (the grid), the rag
 (merge and translation), `nms_wide_device` across the tile borders.  The reference has no tiling; the definition is the library's own
 (csrc/yf_images_tiles.h).
 
+`detect_chips(network, images)` goes one step past the boxes, where the reference stops at cv2.rectangle: every kept box is cut out of its
+picture and resized to one fixed size on the GPU, from the pixels (or the NV12 / NV21 surface) that are already there --
+`crop_records_device`, `crop_records_yuv_device`; the region rule is the library's own (csrc/yf_images_crop.h, `ptq.crop_region`).
+
 NV12 / NV21 surfaces -- 4:2:0 semi-planar, what hardware video and JPEG decoders write and what `detect_video` of the reference's
 yoloface/tensorflow/yoloface_test.py:318-385 has behind cv2.VideoCapture -- are read where they lie: `pack_yuv_images`, the four
 `prepare_yuv_*` bindings, and `detect` / `evaluate` with fmt="nv12" or "nv21".  The frame of a surface is the frame of
@@ -63,6 +67,14 @@ assert YUV_IMAGE_DTYPE.itemsize == 40
 # a tile of an image (yf_tile): the image's index, the tile's origin in the image's pixels and its size
 TILE_DTYPE = np.dtype([("image", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("height", "<i4"), ("width", "<i4")])
 assert TILE_DTYPE.itemsize == 20
+
+
+# the info row of a face chip (yf_chip): its frame and slot, the region actually sampled, and the status (0 a chip, 1 an empty region,
+# 2 the picture's descriptor is invalid)
+CHIP_DTYPE = np.dtype([("frame", "<i4"), ("slot", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4"), ("status", "<i4")])
+assert CHIP_DTYPE.itemsize == 28
+YF_CROP_SQUARE = 1
+ORDERS = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -128,6 +140,10 @@ def _entries():
         "average_precision_device": [vp, vp, vp, cl, ci, vp, ci, vp, cs, vp, vp, vp],
         "plan_tiles": [vp, cl, ci, ci, ci, ci, ci, ci, vp, vp, vp, cl],
         "gather_tiles_device": [vp, vp, cl, ci, vp, vp, cl, vp, vp, ci, vp, cs, vp],
+        # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, out_h, out_w, out_format, margin_permille, flags, d_chips,
+        # chips_cap, d_first, d_info, stream
+        "crop_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp, vp, vp],
+        "crop_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp, vp, vp],
     }
 
 
@@ -667,6 +683,98 @@ def _check_totals(what, d_totals, out_cap):
         i = int(over[0])
         raise ImagesError(f"{what}: image {i} has {int(totals[i])} merged records, out_cap holds {out_cap}"
                           + (f" (and {over.size - 1} more image(s) above it)" if over.size > 1 else ""))
+
+
+def _order_code(order):
+    if isinstance(order, str) and order.lower() in ORDERS:
+        return ORDERS[order.lower()]
+    if order in (YF_PIX_RGB8, YF_PIX_BGR8) and not isinstance(order, str):
+        return int(order)
+    raise ValueError(f"order {order!r}: 'rgb' or 'bgr'")
+
+
+def crop_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, out_h, out_w, d_chips, chips_cap, d_first, d_info,
+                        order="rgb", margin_permille=0, square=False, stream=None):
+    """Face chips of the records of a batch of packed pictures (yf_images_crop_records_device): d_images IMAGE_DTYPE[n], d_dets
+    yf_det[n][cap], d_counts int32[n] -> d_chips uint8 [chips_cap, out_h, out_w, 3] in `order`, d_first int32[n + 1] (chip first[i] + s is
+    slot s of frame i; first[n] the true total), d_info CHIP_DTYPE[chips_cap].  The region rule: csrc/yf_images_crop.h, ptq.crop_region."""
+    _call("crop_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "crop_records_device"), d_images, d_dets, d_counts, n, cap,
+          out_h, out_w, _order_code(order), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info, stream)
+
+
+def crop_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, out_h, out_w, d_chips, chips_cap, d_first, d_info,
+                            order="rgb", margin_permille=0, square=False, stream=None):
+    """`crop_records_device` for NV12 / NV21 surfaces, read where they lie (yf_images_crop_records_yuv_device): d_images
+    YUV_IMAGE_DTYPE[n]; a chip is the chip of the converted picture."""
+    _call("crop_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, out_h, out_w,
+          _order_code(order), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info, stream)
+
+
+def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, order="rgb", fmt="bgr", cap=None, iou_threshold=0.4, size=56,
+                 dtype="int8", device=None, tile=None, stride=None, whole=True, chips_cap=None):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile`, `stride`, `whole` these are), and every kept box cut out of its picture and
+    resized to `out` = (out_h, out_w) (an int: square chips; multiples of 16 in 16..256) on the GPU, on the same stream, from the pixels
+    that are already there: what a recogniser, a landmark model or a blur filter takes next.  `margin`: the box grows by this share of
+    its width and height on every side (0..1, rounded to permille); `square`: the grown box is made square about its centre before it is
+    clamped to the picture (it is not squared again afterwards: csrc/yf_images_crop.h, `ptq.crop_region`); `order`: the chips' byte
+    order, "rgb" or "bgr".  fmt, cap, iou_threshold, size, dtype, device as in `detect` (NV12 / NV21 surfaces are cut where they lie;
+    with `tile`, cap is `detect_tiled`'s out_cap and the chips are cut from the parent pictures).
+    The chips are sized from a read-back of the counts; with chips_cap= nothing is read back before the crop, and a batch with more
+    boxes raises ImagesError.
+    Returns (boxes, chips, info): per image the int32 [k, 4] array `detect` returns, a uint8 [k, out_h, out_w, 3] array of its chips in
+    the same order, and the CHIP_DTYPE [k] rows (the region actually sampled; status 1: the box has no pixel in the picture, the chip is
+    zeros)."""
+    out_h, out_w = _pair(out, "out")
+    permille = int(round(float(margin) * 1000))
+    if not 0 <= permille <= 1000:
+        raise ValueError(f"margin {margin!r}: 0 to 1")
+    order_code = _order_code(order)
+    n = len(images)
+    if n == 0:
+        return [], [], []
+    import torch
+    if tile is None:
+        d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype)
+        d_px, d_desc = keep[0], keep[2] if is_yuv(fmt) else keep[1]
+        d_totals = None
+    else:
+        _packed_code(fmt, "detect_chips(tile=...)")
+        d_dets, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt,
+                                                                                      NMS_WIDE_MAX_CAP if cap is None else cap, device,
+                                                                                      iou_threshold, size, dtype)
+        d_px = keep[0][0]                                # the parents' pixels, as pack_tiles laid them out: pack_images' layout
+        d_desc = torch.from_numpy(pack_images(images, fmt)[1].view(np.uint8)).to(d_px.device)
+    dev, cap = d_dets.device, d_dets.shape[1]
+    if chips_cap is None:
+        stream.synchronize()
+        room = int(np.clip(d_counts.cpu().numpy(), 0, cap).sum())
+    else:
+        room = int(chips_cap)
+    d_chips = torch.empty((max(room, 1), out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    d_info = torch.empty((max(room, 1), CHIP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    crop = crop_records_yuv_device if is_yuv(fmt) else crop_records_device
+    crop(d_px.data_ptr(), d_px.numel(), fmt, d_desc.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, cap, out_h, out_w,
+         d_chips.data_ptr(), room, d_first.data_ptr(), d_info.data_ptr(), order=order_code, margin_permille=permille, square=square,
+         stream=stream.cuda_stream)
+    stream.synchronize()
+    del keep
+    if d_totals is not None:
+        _check_totals("detect_chips", d_totals, cap)
+    first = d_first.cpu().numpy()
+    if int(first[n]) > room:
+        raise ImagesError(f"detect_chips: {int(first[n])} boxes in the batch, chips_cap holds {room}")
+    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
+    chips = d_chips.cpu().numpy()
+    info = d_info.cpu().numpy().view(CHIP_DTYPE).reshape(-1)
+    boxes, per_chips, per_info = [], [], []
+    for i in range(n):
+        a, b = int(first[i]), int(first[i + 1])
+        d = dets[i, :b - a]
+        boxes.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
+        per_chips.append(chips[a:b])
+        per_info.append(info[a:b])
+    return boxes, per_chips, per_info
 
 
 def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):

@@ -358,3 +358,39 @@ def yuv420sp_to_rgb_u8(y, uv, v_first=False):
     g = (yy - 852492 * vv - 409993 * uu) >> 20
     b = (yy + 2116026 * uu) >> 20
     return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
+def crop_region(box, width, height, margin_permille=0, square=False):
+    """The region of a detection's box in a picture of `height` x `width` pixels, as csrc/yf_images_crop.h states it, in Python integers:
+    `box` = (x1, y1, x2, y2), inclusive edges.  bw = x2 - x1 + 1, bh likewise, either < 1: no region.  Margin: mx = bw * margin_permille
+    // 1000, my likewise; x1 -= mx, x2 += mx, y1 -= my, y2 += my.  `square`: side = max(width, height) of that, x1 -= (side - width) // 2,
+    x2 = x1 + side - 1, y likewise.  Clamp to the picture; x1 > x2 or y1 > y2: no region.  The region is not squared again after the
+    clamp.  -> (x0, y0, width, height), or None."""
+    x1, y1, x2, y2 = (int(v) for v in box)
+    bw, bh = x2 - x1 + 1, y2 - y1 + 1
+    if bw < 1 or bh < 1:
+        return None
+    mx, my = bw * int(margin_permille) // 1000, bh * int(margin_permille) // 1000
+    x1, x2, y1, y2 = x1 - mx, x2 + mx, y1 - my, y2 + my
+    if square:
+        w, h = x2 - x1 + 1, y2 - y1 + 1
+        side = max(w, h)
+        x1 -= (side - w) // 2
+        x2 = x1 + side - 1
+        y1 -= (side - h) // 2
+        y2 = y1 + side - 1
+    x1, y1, x2, y2 = max(x1, 0), max(y1, 0), min(x2, int(width) - 1), min(y2, int(height) - 1)
+    if x1 > x2 or y1 > y2:
+        return None
+    return x1, y1, x2 - x1 + 1, y2 - y1 + 1
+
+
+def crop_resize_u8(img, box, out_w, out_h, margin_permille=0, square=False):
+    """The face chip of `box` in `img` (uint8 [H, W, C]): `cv2.resize(img[y0 : y0 + h, x0 : x0 + w], (out_w, out_h))` of the region
+    `crop_region` gives, through `resize_linear_u8` -- what yf_images_crop_records_device computes.  A box without a region gives zeros."""
+    img = np.asarray(img, np.uint8)
+    region = crop_region(box, img.shape[1], img.shape[0], margin_permille, square)
+    if region is None:
+        return np.zeros((out_h, out_w) + img.shape[2:], np.uint8)
+    x0, y0, w, h = region
+    return resize_linear_u8(img[y0:y0 + h, x0:x0 + w], out_w, out_h).reshape((out_h, out_w) + img.shape[2:])
