@@ -345,6 +345,48 @@ YF_API long yf_images_crop_records_yuv_device(const void* d_pixels, size_t pixel
                                               int out_format, int margin_permille, int flags, void* d_chips, long chips_cap,
                                               int32_t* d_first, yf_chip* d_info, void* stream);
 
+/* ---- redaction: the write side of the boxes.  Every record's region of its picture is pixelated (a block mosaic) or filled with one
+ * colour, in place, in the picture where it lies -- packed pixels or an NV12 / NV21 surface -- without the records leaving the device:
+ * video anonymisation, dataset scrubbing, a privacy filter in front of a recorder or encoder.  The reference has no such step; the
+ * definition is this library's own, stated once in csrc/yf_images_redact.h, which the kernels and a host build share.  A C host's
+ * sequence: any run above, a suppression, the redaction -- INTEGRATION.md.
+ *   input:  d_dets, d_counts, n, cap, d_images, margin_permille, flags as the crop above takes them: of frame i the first
+ *           m_i = min(max(count, 0), cap) records count, the region of a record is the crop's region (margin, YF_CROP_SQUARE, clamp; a
+ *           record without a region is skipped), the picture of frame i is descriptor i.  d_pixels is read and WRITTEN.
+ *   mosaic: mode YF_REDACT_MOSAIC, block = k in {4, 8, 16, 32, 64}; colour is ignored.  The block grid is anchored at picture pixel
+ *           (0, 0); blocks at the right and bottom edge are clipped.  A region touches the blocks bx in [x0 / k, (x0 + width - 1) / k],
+ *           by likewise; the redacted set of a picture is the union of the blocks its records touch.  Every pixel of a block of the set
+ *           gets, per colour byte channel, v = (sum + cnt / 2) / cnt over the block's cnt pixels as they were before the call.  The
+ *           fourth byte of BGRA / RGBA is neither read nor written.  NV12 / NV21: the blocks of the Y plane, and for each the chroma
+ *           block of the same (bx, by) -- k / 2 pairs by k / 2 rows, clipped to W / 2 and H / 2 -- whose first bytes are averaged
+ *           together and whose second bytes together.  The result does not depend on the order of a frame's records, and a second call
+ *           changes nothing.
+ *   fill:   mode YF_REDACT_FILL, block = 0, colour = 0x00RRGGBB (NV12 / NV21: 0x00YYUUVV); a non-zero top byte is refused.  Every pixel
+ *           of every region, the exact region, gets R, G, B in the bytes where the format keeps them; alpha is untouched.  NV12 / NV21:
+ *           the region's Y bytes and the chroma pairs cx in [x0 >> 1, (x0 + width - 1) >> 1], cy in [y0 >> 1, (y0 + height - 1) >> 1],
+ *           (U, V) for NV12 and (V, U) for NV21.
+ *   output: nothing outside the redacted set is written, row padding and the bytes between pictures included.  d_first int32[n + 1]
+ *           (written): the exclusive prefix of the m_i, first[n] the total, as for chips; it is also the kernels' schedule.  d_status
+ *           int32[n] (written): 0, or 1 for a picture whose descriptor is invalid (checked as the ragged prepares check it), which is
+ *           neither read nor written.
+ *   alias:  for the mosaic the pictures of different frames must not share bytes.  The call cannot check this: a caller who breaks it
+ *           gets unspecified picture contents, but never an access outside a picture's extent.  The fill tolerates shared pictures,
+ *           because all writers write the same bytes.
+ *   safety: counts, records and d_first (read back) are device memory that may hold anything; every index derived from them is
+ *           range-checked before use, and no load or store leaves a picture's or plane's extent as its descriptor states it.
+ * Two launches (the crop's scan of the clamped counts into d_first, one workgroup per record that exists); asynchronous on `stream`, no
+ * allocation, no host synchronisation, capturable; every argument is checked before the first launch, and each entry refuses the other
+ * family's formats with a text.  Every pointer must be valid (d_dets, d_counts, d_first and d_status 4-byte aligned, d_images 8-byte
+ * aligned) for an empty batch too.  Returns n; n = 0 launches nothing and returns 0, after the checks. */
+enum { YF_REDACT_MOSAIC = 0, YF_REDACT_FILL = 1 };
+YF_API long yf_images_redact_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                            const void* d_counts, long n, int cap, int mode, int block, uint32_t colour,
+                                            int margin_permille, int flags, int32_t* d_first, int32_t* d_status, void* stream);
+YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                const void* d_dets, const void* d_counts, long n, int cap, int mode, int block,
+                                                uint32_t colour, int margin_permille, int flags, int32_t* d_first, int32_t* d_status,
+                                                void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

@@ -15,7 +15,8 @@
 // float32 logits, the arithmetic of yf_images_float.h, one wave per frame) and nms_kernel (up to 256 records, one wave per frame) below; the decode of 20x20 heads and the suppression of up to 1200 records per frame in yf_images_wide.hip.h;
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
 // tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h; the face chips (every record's region of its picture,
-// resized) in yf_images_crop.h and yf_images_crop.hip.h.
+// resized) in yf_images_crop.h and yf_images_crop.hip.h; the redaction (every record's region pixelated or filled in place) in
+// yf_images_redact.h and yf_images_redact.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -36,6 +37,7 @@
 #include "yf_images_eval.hip.h"
 #include "yf_images_tiles.hip.h"
 #include "yf_images_crop.hip.h"
+#include "yf_images_redact.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -816,6 +818,40 @@ long crop_records(const void* d_pixels, size_t pixels_bytes, int format, const v
   return launched("crop_records kernel launches", n);
 }
 
+// ---- redaction (yf_images_redact.h) ----  the kernels by format (the four packed formats in the order of their codes, then NV12, NV21)
+// and mode (mosaic, fill)
+using RedactKernel = void (*)(yfredact::Args);
+constexpr RedactKernel kRedact[6][2] = {{yfredact::mosaic_kernel<3>, yfredact::fill_kernel<3>},
+                                        {yfredact::mosaic_kernel<3>, yfredact::fill_kernel<3>},
+                                        {yfredact::mosaic_kernel<4>, yfredact::fill_kernel<4>},
+                                        {yfredact::mosaic_kernel<4>, yfredact::fill_kernel<4>},
+                                        {yfredact::mosaic_yuv_kernel, yfredact::fill_yuv_kernel<false>},
+                                        {yfredact::mosaic_yuv_kernel, yfredact::fill_yuv_kernel<true>}};
+static_assert(YF_REDACT_MOSAIC == 0 && YF_REDACT_FILL == 1, "the order of kRedact");
+
+// both entries behind their format check: every other argument, then the crop's scan and the records
+long redact_records(void* d_pixels, size_t pixels_bytes, int format, const void* d_images, const void* d_dets, const void* d_counts, long n,
+                    int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, int32_t* d_first, int32_t* d_status,
+                    void* stream) {
+  const char* err = yfi_redact_check(n, cap, mode, block, colour, margin_permille, flags);
+  if (err) return fail("%s", err);
+  if (!d_dets || !d_counts || !d_first || !d_status) return fail("d_dets, d_counts, d_first or d_status is NULL");
+  if ((((uintptr_t)d_dets | (uintptr_t)d_counts | (uintptr_t)d_first | (uintptr_t)d_status) & 3) != 0)
+    return fail("d_dets, d_counts, d_first and d_status must be 4-byte aligned");
+  if (!d_pixels) return fail("d_pixels is NULL");
+  if (!d_images || ((uintptr_t)d_images & 7) != 0) return fail("d_images is NULL or not 8-byte aligned");
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yfcrop::first_kernel, dim3(1), dim3(yfcrop::kThreads), 0, s, (const int*)d_counts, n, cap, d_first);
+  yfredact::Args a{};
+  a.c.bytes = (uint64_t)pixels_bytes; a.c.imgs = d_images; a.c.dets = (const yf_det*)d_dets; a.c.counts = (const int*)d_counts;
+  a.c.n = n; a.c.cap = cap; a.c.margin = margin_permille; a.c.flags = flags; a.c.first = d_first;
+  a.px = (uint8_t*)d_pixels; a.format = format; a.block = block; a.colour = colour; a.status = d_status;
+  // no more workgroups than records can exist; 9.6 KB of LDS per mosaic workgroup, eight waves per SIMD
+  hipLaunchKernelGGL(kRedact[format][mode], grid_for(n * (long)cap, 8), dim3(yfredact::kThreads), 0, s, a);
+  return launched("redact_records kernel launches", n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1113,6 +1149,25 @@ YF_API long yf_images_crop_records_yuv_device(const void* d_pixels, size_t pixel
   if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
   return crop_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, out_h, out_w, out_format, margin_permille, flags,
                       d_chips, chips_cap, d_first, d_info, stream);
+}
+
+YF_API long yf_images_redact_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                            const void* d_counts, long n, int cap, int mode, int block, uint32_t colour, int margin_permille,
+                                            int flags, int32_t* d_first, int32_t* d_status, void* stream) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_redact_records_yuv_device");
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  return redact_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first,
+                        d_status, stream);
+}
+
+YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                const void* d_dets, const void* d_counts, long n, int cap, int mode, int block, uint32_t colour,
+                                                int margin_permille, int flags, int32_t* d_first, int32_t* d_status, void* stream) {
+  if (channels_of(format)) return fail("format YF_PIX_BGR8 / RGB8 / BGRA8 / RGBA8: packed pixels go through yf_images_redact_records_device");
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  return redact_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first,
+                        d_status, stream);
 }
 
 }  // extern "C"

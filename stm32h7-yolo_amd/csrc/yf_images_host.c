@@ -1,9 +1,10 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h and the face chips of yf_images_crop.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h and the redaction of yf_images_redact.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "yf_images_taps.h"
@@ -14,6 +15,7 @@
 #include "yf_images_eval.h"
 #include "yf_images_tiles.h"
 #include "yf_images_crop.h"
+#include "yf_images_redact.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -384,4 +386,116 @@ EXPORT void yfi_crop_region_host(int32_t x1, int32_t y1, int32_t x2, int32_t y2,
   yf_chip r;
   const int st = yfi_crop_region(x1, y1, x2, y2, W, H, margin_permille, flags, &r);
   out[0] = r.x0; out[1] = r.y0; out[2] = r.width; out[3] = r.height; out[4] = st;
+}
+
+/* ---- yf_images_redact.h ----  yf_images_redact_records_device / _yuv_device as the header states them, in place on the caller's buffer:
+ * the exclusive prefix of the clamped counts into first[n + 1], status[n], and picture by picture the mosaic or the fill.  The mosaic
+ * states the union literally: a map of the picture's blocks, one byte each, marks the blocks the frame's records touch; then every marked
+ * block is read, averaged and written once (blocks do not overlap, so no copy of the source is needed).  `images`: yf_image[n] or
+ * yf_image_yuv[n], offsets from `base`, checked against `bytes`.  Returns n, or -1 for arguments the device entries refuse (or no memory
+ * for the map). */
+static void redact_mean(uint8_t* p, int64_t stride, int rows, int cols, int C, int NC) {
+  for (int c = 0; c < NC; ++c) {
+    uint32_t sum = 0;
+    for (int y = 0; y < rows; ++y)
+      for (int x = 0; x < cols; ++x) sum += p[(int64_t)y * stride + (int64_t)x * C + c];
+    const uint8_t v = (uint8_t)yfi_redact_mean(sum, (uint32_t)rows * (uint32_t)cols);
+    for (int y = 0; y < rows; ++y)
+      for (int x = 0; x < cols; ++x) p[(int64_t)y * stride + (int64_t)x * C + c] = v;
+  }
+}
+
+static void redact_fill(uint8_t* p, int64_t stride, int rows, int cols, int C, int NC, const uint8_t* f) {
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < cols; ++x)
+      for (int c = 0; c < NC; ++c) p[(int64_t)y * stride + (int64_t)x * C + c] = f[c];
+}
+
+static long redact_records(uint8_t* base, uint64_t bytes, int format, const void* images, const yf_det* dets, const int32_t* counts, long n,
+                           int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, int32_t* first, int32_t* status) {
+  if (yfi_redact_check(n, cap, mode, block, colour, margin_permille, flags) != NULL) return -1;
+  if (!dets || !counts || !first || !status || !base || !images) return -1;
+  if (n == 0) return 0;
+  const int yuv = format == YF_PIX_NV12 || format == YF_PIX_NV21;
+  const int C = yuv ? 1 : yfi_tiles_channels(format);
+  uint8_t f[3];
+  yfi_redact_fill_bytes(colour, format, f);
+  int64_t total = 0;
+  for (long i = 0; i < n; ++i) {
+    first[i] = (int32_t)total;
+    total += yfi_crop_clamp(counts[i], cap);
+  }
+  first[n] = (int32_t)total;
+  for (long i = 0; i < n; ++i) {
+    const int m = yfi_crop_clamp(counts[i], cap);
+    const yf_image* im = yuv ? NULL : (const yf_image*)images + i;
+    const yf_image_yuv* iy = yuv ? (const yf_image_yuv*)images + i : NULL;
+    const int ok = yuv ? yfi_yuv_image_ok(iy->offset_y, iy->offset_uv, iy->height, iy->width, iy->stride_y, iy->stride_uv, bytes)
+                       : yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes);
+    status[i] = ok ? 0 : 1;
+    if (!ok) continue;
+    const int32_t W = yuv ? iy->width : im->width, H = yuv ? iy->height : im->height;
+    uint8_t* px = base + (yuv ? iy->offset_y : im->offset);
+    uint8_t* uv = yuv ? base + iy->offset_uv : NULL;
+    const int64_t rs = yuv ? iy->stride_y : im->row_stride;
+    const int nbx = mode == YF_REDACT_MOSAIC ? (W + block - 1) / block : 0, nby = mode == YF_REDACT_MOSAIC ? (H + block - 1) / block : 0;
+    uint8_t* set = NULL;
+    if (mode == YF_REDACT_MOSAIC && m > 0) {
+      set = (uint8_t*)calloc((size_t)nbx * (size_t)nby, 1);
+      if (!set) return -1;
+    }
+    for (int s = 0; s < m; ++s) {
+      const yf_det* d = &dets[i * cap + s];
+      yf_chip r;
+      if (yfi_crop_region(d->x1, d->y1, d->x2, d->y2, W, H, margin_permille, flags, &r) != 0) continue;
+      if (mode == YF_REDACT_MOSAIC) {
+        const yfi_blocks b = yfi_redact_blocks(&r, block);
+        for (int by = b.by0; by <= b.by1; ++by) memset(set + (size_t)by * nbx + b.bx0, 1, (size_t)(b.bx1 - b.bx0 + 1));
+      } else if (!yuv) {
+        redact_fill(px + (int64_t)r.y0 * rs + (int64_t)r.x0 * C, rs, r.height, r.width, C, 3, f);
+      } else {
+        const int cx0 = r.x0 >> 1, cx1 = (r.x0 + r.width - 1) >> 1, cy0 = r.y0 >> 1, cy1 = (r.y0 + r.height - 1) >> 1;
+        redact_fill(px + (int64_t)r.y0 * rs + r.x0, rs, r.height, r.width, 1, 1, f);
+        redact_fill(uv + (int64_t)cy0 * iy->stride_uv + 2 * cx0, iy->stride_uv, cy1 - cy0 + 1, cx1 - cx0 + 1, 2, 2, f + 1);
+      }
+    }
+    if (set) {
+      for (int by = 0; by < nby; ++by)
+        for (int bx = 0; bx < nbx; ++bx) {
+          if (!set[(size_t)by * nbx + bx]) continue;
+          int32_t x, w, y, h;
+          yfi_redact_span(bx, block, W, &x, &w);
+          yfi_redact_span(by, block, H, &y, &h);
+          redact_mean(px + (int64_t)y * rs + (int64_t)x * C, rs, h, w, C, yuv ? 1 : 3);
+          if (yuv) {
+            yfi_redact_chroma_span(bx, block, W, &x, &w);
+            yfi_redact_chroma_span(by, block, H, &y, &h);
+            redact_mean(uv + (int64_t)y * iy->stride_uv + 2 * x, iy->stride_uv, h, w, 2, 2);
+          }
+        }
+      free(set);
+    }
+  }
+  return n;
+}
+
+EXPORT long yfi_redact_records_host(uint8_t* base, uint64_t bytes, int format, const yf_image* images, const yf_det* dets, const int32_t* counts,
+                                    long n, int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, int32_t* first,
+                                    int32_t* status) {
+  if (!yfi_tiles_channels(format)) return -1;
+  return redact_records(base, bytes, format, images, dets, counts, n, cap, mode, block, colour, margin_permille, flags, first, status);
+}
+
+EXPORT long yfi_redact_records_yuv_host(uint8_t* base, uint64_t bytes, int format, const yf_image_yuv* images, const yf_det* dets,
+                                        const int32_t* counts, long n, int cap, int mode, int block, uint32_t colour, int margin_permille,
+                                        int flags, int32_t* first, int32_t* status) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return -1;
+  return redact_records(base, bytes, format, images, dets, counts, n, cap, mode, block, colour, margin_permille, flags, first, status);
+}
+
+/* the argument check alone: the text of the first fault into out (at most out_bytes, 0-terminated), or an empty text; returns 1 for a fault */
+EXPORT int yfi_redact_check_host(long n, int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, char* out, int out_bytes) {
+  const char* t = yfi_redact_check(n, cap, mode, block, colour, margin_permille, flags);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
 }

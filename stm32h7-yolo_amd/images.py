@@ -22,6 +22,11 @@ records one picture's records again on the GPU: `plan_tiles` (the grid), the rag
 picture and resized to one fixed size on the GPU, from the pixels (or the NV12 / NV21 surface) that are already there --
 `crop_records_device`, `crop_records_yuv_device`; the region rule is the library's own (csrc/yf_images_crop.h, `ptq.crop_region`).
 
+`detect_redacted(network, images)` is the write side of the boxes: every kept box is pixelated (a block mosaic) or filled with one colour
+in its picture on the GPU, packed pixels or an NV12 / NV21 surface, and the redacted pictures come back in the caller's shapes --
+`redact_records_device`, `redact_records_yuv_device`; the definition is the library's own (csrc/yf_images_redact.h, `ptq.redact_u8`,
+`ptq.redact_yuv420sp`).
+
 NV12 / NV21 surfaces -- 4:2:0 semi-planar, what hardware video and JPEG decoders write and what `detect_video` of the reference's
 yoloface/tensorflow/yoloface_test.py:318-385 has behind cv2.VideoCapture -- are read where they lie: `pack_yuv_images`, the four
 `prepare_yuv_*` bindings, and `detect` / `evaluate` with fmt="nv12" or "nv21".  The frame of a surface is the frame of
@@ -75,6 +80,8 @@ CHIP_DTYPE = np.dtype([("frame", "<i4"), ("slot", "<i4"), ("x0", "<i4"), ("y0", 
 assert CHIP_DTYPE.itemsize == 28
 YF_CROP_SQUARE = 1
 ORDERS = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}
+YF_REDACT_MOSAIC, YF_REDACT_FILL = 0, 1
+REDACT_MODES = {"mosaic": YF_REDACT_MOSAIC, "fill": YF_REDACT_FILL}
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -144,6 +151,10 @@ def _entries():
         # chips_cap, d_first, d_info, stream
         "crop_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp, vp, vp],
         "crop_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp, vp, vp],
+        # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first, d_status,
+        # stream
+        "redact_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
+        "redact_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
     }
 
 
@@ -775,6 +786,117 @@ def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, orde
         per_chips.append(chips[a:b])
         per_info.append(info[a:b])
     return boxes, per_chips, per_info
+
+
+def _mode_code(mode):
+    if isinstance(mode, str) and mode.lower() in REDACT_MODES:
+        return REDACT_MODES[mode.lower()]
+    if mode in (YF_REDACT_MOSAIC, YF_REDACT_FILL) and not isinstance(mode, (str, bool)):
+        return int(mode)
+    raise ValueError(f"mode {mode!r}: 'mosaic' or 'fill'")
+
+
+def _colour_code(colour):
+    """(R, G, B) -- for NV12 / NV21 surfaces (Y, U, V) -- or the integer 0x00RRGGBB -> that integer"""
+    if isinstance(colour, (tuple, list, np.ndarray)):
+        c = [int(v) for v in colour]
+        if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+            raise ValueError(f"colour {colour!r}: three bytes")
+        return c[0] << 16 | c[1] << 8 | c[2]
+    if not 0 <= int(colour) <= 0xFFFFFF:
+        raise ValueError(f"colour {colour!r}: 0x00RRGGBB")
+    return int(colour)
+
+
+def redact_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_first, d_status, mode="mosaic", block=8, colour=0,
+                          margin_permille=0, square=False, stream=None):
+    """The regions of the records of a batch of packed pictures pixelated or filled IN PLACE (yf_images_redact_records_device): d_images
+    IMAGE_DTYPE[n], d_dets yf_det[n][cap], d_counts int32[n]; d_pixels is written.  mode "mosaic": block 4, 8, 16, 32 or 64, a grid
+    anchored at each picture's pixel (0, 0); mode "fill": block 0, colour 0x00RRGGBB or (R, G, B).  d_first int32[n + 1] and d_status
+    int32[n] (1: the picture's descriptor is invalid, the picture untouched) are written.  For the mosaic the pictures of different frames
+    must not share bytes.  The definition: csrc/yf_images_redact.h, ptq.redact_u8."""
+    _call("redact_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "redact_records_device"), d_images, d_dets, d_counts, n, cap,
+          _mode_code(mode), block, _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status, stream)
+
+
+def redact_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_first, d_status, mode="mosaic", block=8,
+                              colour=0, margin_permille=0, square=False, stream=None):
+    """`redact_records_device` for NV12 / NV21 surfaces, redacted where they lie (yf_images_redact_records_yuv_device): d_images
+    YUV_IMAGE_DTYPE[n]; colour 0x00YYUUVV or (Y, U, V).  ptq.redact_yuv420sp."""
+    _call("redact_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, _mode_code(mode), block,
+          _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status, stream)
+
+
+def _strided(buf, offset, rows, row_bytes, pitch):
+    return np.lib.stride_tricks.as_strided(buf[offset:], shape=(rows, row_bytes), strides=(pitch, 1))
+
+
+def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None,
+                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and every kept box hidden in its picture on the GPU,
+    on the same stream, in the pixels that are already there: mode "mosaic" pixelates the blocks of `block` x `block` pixels (4, 8, 16,
+    32 or 64; the grid starts at the picture's pixel (0, 0)) that the box touches, each block to its mean; mode "fill" writes `colour`,
+    (R, G, B) whatever the byte order of `fmt` -- for NV12 / NV21 surfaces (Y, U, V) -- into the box, and `block` is not used.  `margin`
+    and `square` grow the box as in `detect_chips` (csrc/yf_images_crop.h, `ptq.crop_region`).  fmt, cap, iou_threshold, size, dtype,
+    device as in `detect`; with `tile`, cap is `detect_tiled`'s out_cap and the parent pictures are redacted.
+    Returns (pictures, boxes): the redacted pictures in the caller's shapes, new arrays (NV12 / NV21: (y, uv) pairs) -- the caller's
+    arrays are not changed --, and per image the int32 [k, 4] array `detect` returns.  The definition is the library's own:
+    csrc/yf_images_redact.h, restated as `ptq.redact_u8` and `ptq.redact_yuv420sp`."""
+    mode_code = _mode_code(mode)
+    block = 0 if mode_code == YF_REDACT_FILL else int(block)
+    if mode_code == YF_REDACT_MOSAIC and block not in (4, 8, 16, 32, 64):
+        raise ValueError(f"block {block!r}: 4, 8, 16, 32 or 64")
+    colour_code = _colour_code(colour)
+    permille = int(round(float(margin) * 1000))
+    if not 0 <= permille <= 1000:
+        raise ValueError(f"margin {margin!r}: 0 to 1")
+    n = len(images)
+    if n == 0:
+        return [], []
+    import torch
+    yuv = is_yuv(fmt)
+    if tile is None:
+        d_dets, d_counts, _, stream, keep = _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype)
+        d_px, d_desc = keep[0], keep[2] if yuv else keep[1]
+        d_totals = None
+    else:
+        _packed_code(fmt, "detect_redacted(tile=...)")
+        d_dets, d_counts, d_totals, _, stream, keep = _tiled_records_on_device(network, images, tile, stride, True, fmt,
+                                                                               NMS_WIDE_MAX_CAP if cap is None else cap, device,
+                                                                               iou_threshold, size, dtype)
+        d_px = keep[0][0]                                # the parents' pixels, as pack_tiles laid them out: pack_images' layout
+        d_desc = torch.from_numpy(pack_images(images, fmt)[1].view(np.uint8)).to(d_px.device)
+    dev, cap = d_dets.device, d_dets.shape[1]
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    redact = redact_records_yuv_device if yuv else redact_records_device
+    redact(d_px.data_ptr(), d_px.numel(), fmt, d_desc.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, cap, d_first.data_ptr(),
+           d_status.data_ptr(), mode=mode_code, block=block, colour=colour_code, margin_permille=permille, square=square,
+           stream=stream.cuda_stream)
+    stream.synchronize()
+    if d_totals is not None:
+        _check_totals("detect_redacted", d_totals, cap)
+    bad = np.nonzero(d_status.cpu().numpy())[0]
+    if bad.size:
+        raise ImagesError(f"detect_redacted: the descriptor of image {int(bad[0])} is invalid")
+    first = d_first.cpu().numpy()
+    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
+    buf = d_px.cpu().numpy()
+    desc = d_desc.cpu().numpy().view(YUV_IMAGE_DTYPE if yuv else IMAGE_DTYPE).reshape(-1)
+    del keep
+    pictures, boxes = [], []
+    for i in range(n):
+        d = dets[i, :int(first[i + 1]) - int(first[i])]
+        boxes.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
+        e = desc[i]
+        h, w = int(e["height"]), int(e["width"])
+        if yuv:
+            pictures.append((_strided(buf, int(e["offset_y"]), h, w, int(e["stride_y"])).copy(),
+                             _strided(buf, int(e["offset_uv"]), h // 2, w, int(e["stride_uv"])).copy()))
+        else:
+            C = CHANNELS[format_code(fmt)]
+            pictures.append(_strided(buf, int(e["offset"]), h, w * C, int(e["row_stride"])).copy().reshape(h, w, C))
+    return pictures, boxes
 
 
 def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):

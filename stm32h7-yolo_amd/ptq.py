@@ -394,3 +394,69 @@ def crop_resize_u8(img, box, out_w, out_h, margin_permille=0, square=False):
         return np.zeros((out_h, out_w) + img.shape[2:], np.uint8)
     x0, y0, w, h = region
     return resize_linear_u8(img[y0:y0 + h, x0:x0 + w], out_w, out_h).reshape((out_h, out_w) + img.shape[2:])
+
+
+def _mosaic_plane(src, out, blocks, kx, ky):
+    """every block of `blocks` (a set of (bx, by)) of the plane `out` [rows, cols, channels] gets, per channel, the rounded integer mean
+    (sum + cnt // 2) // cnt of the same block of `src`; a block holds kx columns and ky rows, clipped at the plane's right and bottom edge"""
+    for bx, by in blocks:
+        blk = src[by * ky:by * ky + ky, bx * kx:bx * kx + kx].astype(np.int64)
+        cnt = blk.shape[0] * blk.shape[1]
+        out[by * ky:by * ky + ky, bx * kx:bx * kx + kx] = (blk.sum(axis=(0, 1)) + cnt // 2) // cnt
+
+
+def _touched_blocks(regions, block):
+    """the union of the blocks of a grid anchored at pixel (0, 0) that the regions (x0, y0, width, height) touch; None: a record without a region"""
+    return {(bx, by) for x0, y0, w, h in (r for r in regions if r is not None)
+            for bx in range(x0 // block, (x0 + w - 1) // block + 1) for by in range(y0 // block, (y0 + h - 1) // block + 1)}
+
+
+def _redact_mode(mode, block):
+    if mode in ("mosaic", 0) and not isinstance(mode, bool):
+        if block not in (4, 8, 16, 32, 64):
+            raise ValueError(f"block {block!r}: 4, 8, 16, 32 or 64")
+        return True
+    if mode in ("fill", 1) and not isinstance(mode, bool):
+        if block not in (0, None):
+            raise ValueError(f"block {block!r}: the fill has no block (0)")
+        return False
+    raise ValueError(f"mode {mode!r}: 'mosaic' or 'fill'")
+
+
+def redact_u8(picture_hwc, regions, mode, block, colour):
+    """The redacted copy of a packed picture (uint8 [H, W, 3 or 4]), as csrc/yf_images_redact.h states it.  `regions`: (x0, y0, width,
+    height) per record, as `crop_region` gives them (None entries are skipped).
+    mode "mosaic", block k in {4, 8, 16, 32, 64}: the block grid is anchored at pixel (0, 0) and clipped at the right and bottom edge; the
+    union of the blocks the regions touch is redacted, each block to its rounded integer mean per colour channel, (sum + cnt // 2) // cnt
+    over the pixels of the picture as it came in.  mode "fill", block 0: every pixel of every region gets `colour`, three bytes for the
+    picture's channels 0, 1, 2 in the picture's own order.  A fourth channel is never touched."""
+    src = np.asarray(picture_hwc, np.uint8)
+    out = src.copy()
+    if _redact_mode(mode, block):
+        _mosaic_plane(src[..., :3], out[..., :3], _touched_blocks(regions, block), block, block)
+    else:
+        for x0, y0, w, h in (r for r in regions if r is not None):
+            out[y0:y0 + h, x0:x0 + w, :3] = np.asarray(colour, np.uint8).reshape(3)
+    return out
+
+
+def redact_yuv420sp(y, uv, regions, mode, block, colour, v_first=False):
+    """`redact_u8` for an NV12 / NV21 surface (y uint8 [H, W], uv uint8 [H / 2, W]) -> (y, uv) redacted copies.  Mosaic: the luma blocks on
+    the Y plane, and for each block of the set the chroma block of the same (bx, by) -- block // 2 pairs by block // 2 rows, clipped to
+    W / 2 and H / 2 -- whose first bytes are averaged together and whose second bytes together (v_first does not matter).  Fill: `colour`
+    = (Y, U, V); the regions' Y bytes, and the chroma pairs cx in [x0 >> 1, (x0 + width - 1) >> 1], cy in [y0 >> 1, (y0 + height - 1)
+    >> 1] get (U, V), or (V, U) with v_first."""
+    y_src, uv_src = np.asarray(y, np.uint8), np.asarray(uv, np.uint8)
+    y_out, uv_out = y_src.copy(), uv_src.copy()
+    h2, w = uv_src.shape
+    pairs_src, pairs_out = uv_src.reshape(h2, w // 2, 2), uv_out.reshape(h2, w // 2, 2)
+    if _redact_mode(mode, block):
+        blocks = _touched_blocks(regions, block)
+        _mosaic_plane(y_src[..., None], y_out[..., None], blocks, block, block)
+        _mosaic_plane(pairs_src, pairs_out, blocks, block // 2, block // 2)
+    else:
+        yy, u, v = (int(c) for c in colour)
+        for x0, y0, rw, rh in (r for r in regions if r is not None):
+            y_out[y0:y0 + rh, x0:x0 + rw] = yy
+            pairs_out[y0 >> 1:((y0 + rh - 1) >> 1) + 1, x0 >> 1:((x0 + rw - 1) >> 1) + 1] = (v, u) if v_first else (u, v)
+    return y_out, uv_out

@@ -41,7 +41,7 @@ def disassemble(lib, resources=None):
                 notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
                 for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
                     name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    resources[name] = {k: int(v) for k, v in re.findall(r"\.(sgpr_count|vgpr_count|private_segment_fixed_size|sgpr_spill_count|vgpr_spill_count):\s+(\d+)", blk)}
+                    resources[name] = {k: int(v) for k, v in re.findall(r"\.(sgpr_count|vgpr_count|private_segment_fixed_size|group_segment_fixed_size|sgpr_spill_count|vgpr_spill_count):\s+(\d+)", blk)}
     out, cur, getpc = {}, None, -9
     for ln in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(.+)>:", ln)
