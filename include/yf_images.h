@@ -387,6 +387,45 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
                                                 uint32_t colour, int margin_permille, int flags, int32_t* d_first, int32_t* d_status,
                                                 void* stream);
 
+/* ---- tracking: the step between "the boxes of this frame" and "what to do with this frame" of a video.  Each frame's records (after a
+ * suppression) are associated with per-stream track state: every face gets an identity that lasts over the frames, and a face the
+ * detector misses for a few frames is held over with its last box -- so a redaction (above) does not show it on exactly those frames,
+ * and a recogniser behind the chips knows which chip is which.  The output is records again, which the crop and the redaction take as
+ * they are.  The reference has no tracker; the definition is this library's own, stated once in csrc/yf_images_track.h (the match, the
+ * update, the order of the output, what is out of scope), which the kernel and a host build share.  The video loop: INTEGRATION.md.
+ *   state:  d_state yf_track_state[streams] (8-byte aligned), yf_images_track_state_bytes(streams) bytes (0 for streams <= 0).  An
+ *           all-zero state is the empty state: a hipMemsetAsync resets a stream (or all).  The bytes are untrusted: whatever they hold,
+ *           the step reads and writes only inside them.
+ *   input:  the batch holds n = streams * steps frames, d_dets yf_det[n][cap], d_counts int32[n], 1 <= cap <= YF_IMAGES_NMS_WIDE_MAX_CAP.
+ *           layout YF_TRACK_TIME_MAJOR: frame f = t * streams + s, one frame of every camera per step; YF_TRACK_STREAM_MAJOR:
+ *           f = s * steps + t, a clip per stream.  Of a frame the first min(max(count, 0), cap, 64) records count, in the order they
+ *           lie; a larger count sets bit 0 of the frame's status.  The steps of a stream are taken in order t = 0 .. steps - 1; the
+ *           state at d_state[s] is read before the first and written after the last.
+ *   params: a host pointer, copied.  A slot's box and a detection match if they share a pixel and their IoU (the suppression's
+ *           arithmetic, float64) is >= match_iou (any value but NaN); the match is greedy by descending IoU.  A track is reported once
+ *           it has min_hits >= 1 matches, and kept over max_misses >= 0 frames without one.  The library's suggestion for faces at a
+ *           video rate is {0.3, 1, 5}; that is a choice, not something measured.
+ *   output: d_out yf_det[n][out_cap], d_info yf_track_info[n][out_cap], d_out_counts int32[n], out_cap >= 1 (64 holds every track).
+ *           Per frame the reported tracks in ascending id: the track's last record with `frame` set to f, beside {id, hits, misses,
+ *           age}; misses > 0 marks a held-over track.  d_out_counts[f] is the true number; only the first out_cap are written and
+ *           nothing beyond min(count, out_cap).  d_status int32[n] or NULL: bit 0 as above, bit 1: a detection found all 64 slots
+ *           taken and was dropped.
+ * One launch (one wave per stream, the state in registers over the stream's steps); asynchronous on `stream`, no allocation, no host
+ * synchronisation, capturable.  Every argument is checked before the launch: NULL pointers (d_status excepted), 4-byte alignment of the
+ * records, counts and outputs, 8-byte alignment of the state, cap, out_cap, match_iou, min_hits, max_misses, layout, streams and
+ * steps >= 0 with streams * steps <= 2^31 - 2.  Returns n; n = 0 launches nothing and returns 0, after the checks; a failure returns -1
+ * (unlike the entries above: here 0 is a valid n) with a text in yf_images_last_error_text. */
+#define YF_TRACK_SLOTS 64
+typedef struct yf_track        { uint32_t id; int32_t hits, misses, age; yf_det det; } yf_track;           /* 44 bytes; id 0 = free slot */
+typedef struct yf_track_state  { uint32_t issued, reserved; yf_track slot[YF_TRACK_SLOTS]; } yf_track_state; /* 2824 bytes per stream */
+typedef struct yf_track_info   { uint32_t id; int32_t hits, misses, age; } yf_track_info;                  /* 16 bytes, parallel to an output record */
+typedef struct yf_track_params { double match_iou; int32_t min_hits, max_misses; } yf_track_params;
+enum { YF_TRACK_TIME_MAJOR = 0, YF_TRACK_STREAM_MAJOR = 1 };
+YF_API size_t yf_images_track_state_bytes(long streams);
+YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                                     const yf_track_params* params, void* d_state, void* d_out, void* d_info, void* d_out_counts,
+                                     int out_cap, int32_t* d_status, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

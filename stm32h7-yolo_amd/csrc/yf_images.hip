@@ -16,7 +16,8 @@
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
 // tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h; the face chips (every record's region of its picture,
 // resized) in yf_images_crop.h and yf_images_crop.hip.h; the redaction (every record's region pixelated or filled in place) in
-// yf_images_redact.h and yf_images_redact.hip.h.
+// yf_images_redact.h and yf_images_redact.hip.h; the tracker (each frame's records associated with per-stream track state) in
+// yf_images_track.h and yf_images_track.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -38,6 +39,7 @@
 #include "yf_images_tiles.hip.h"
 #include "yf_images_crop.hip.h"
 #include "yf_images_redact.hip.h"
+#include "yf_images_track.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -852,6 +854,22 @@ long redact_records(void* d_pixels, size_t pixels_bytes, int format, const void*
   return launched("redact_records kernel launches", n);
 }
 
+// ---- tracking (yf_images_track.h) ----  -1 and the text: here 0 is a valid number of frames
+long track(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap, const yf_track_params* params,
+           void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
+  const char* err = yfi_track_check(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status);
+  if (err) return fail("%s", err) - 1;
+  const long n = streams * steps;
+  if (n == 0) return 0;
+  yftrack::Args a{};
+  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
+  a.match_iou = params->match_iou; a.min_hits = params->min_hits; a.max_misses = params->max_misses;
+  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
+  a.out_cap = out_cap; a.status = d_status;
+  hipLaunchKernelGGL(yftrack::step_kernel, grid_for(streams, 16), dim3(64), 0, (hipStream_t)stream, a);       // one-wave workgroups, no LDS
+  return launched("track kernel launch", n) == n ? n : -1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1168,6 +1186,14 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
   if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
   return redact_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first,
                         d_status, stream);
+}
+
+YF_API size_t yf_images_track_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
+
+YF_API long yf_images_track_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                                   const yf_track_params* params, void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap,
+                                   int32_t* d_status, void* stream) {
+  return track(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h and the redaction of yf_images_redact.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h and the tracker of yf_images_track.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -16,6 +16,7 @@
 #include "yf_images_tiles.h"
 #include "yf_images_crop.h"
 #include "yf_images_redact.h"
+#include "yf_images_track.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -499,3 +500,110 @@ EXPORT int yfi_redact_check_host(long n, int cap, int mode, int block, uint32_t 
   if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
   return t != NULL;
 }
+
+/* ---- yf_images_track.h ----  yf_images_track_device as the header states it, on host memory (`stream` is not used): stream by stream,
+ * step by step, literally -- the table of the eligible pairs' IoUs, then round after round the largest entry among the slots and
+ * detections still unmatched (a scan in ascending detection, then ascending slot, with a strict comparison: the tie rule), the update,
+ * the births, and the output by a selection of the smallest (id, slot) not yet emitted.  Returns n, or -1 for arguments the device entry
+ * refuses. */
+static void track_step_host(yf_track_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_params* p, int32_t frame,
+                            yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
+  const int m = yfi_track_clamp(count, cap);
+  int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
+  static _Thread_local double iou[YF_TRACK_SLOTS][YF_TRACK_MAX_DETS];
+  int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
+  for (int j = 0; j < m; ++j) det_slot[j] = -1;
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    const yf_track* k = &st->slot[s];
+    slot_det[s] = -1;
+    occupied[s] = k->id != 0;
+    if (!occupied[s]) continue;
+    const double area_a = yfi_nms_area(k->det.x1, k->det.y1, k->det.x2, k->det.y2);
+    for (int j = 0; j < m; ++j) {
+      const yf_det* d = &dets[j];
+      yfi_track_iou(k->det.x1, k->det.y1, k->det.x2, k->det.y2, area_a, d->x1, d->y1, d->x2, d->y2,
+                    yfi_nms_area(d->x1, d->y1, d->x2, d->y2), p->match_iou, &iou[s][j]);          /* 0.0: not eligible */
+    }
+  }
+  for (;;) {
+    double best = 0.0;
+    int bj = -1, bs = -1;
+    for (int j = 0; j < m; ++j) {
+      if (det_slot[j] >= 0) continue;
+      for (int s = 0; s < YF_TRACK_SLOTS; ++s)
+        if (occupied[s] && slot_det[s] < 0 && iou[s][j] > best) { best = iou[s][j]; bj = j; bs = s; }
+    }
+    if (bj < 0) break;
+    det_slot[bj] = bs;
+    slot_det[bs] = bj;
+  }
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    yf_track* k = &st->slot[s];
+    if (!occupied[s]) continue;
+    k->age = yfi_track_inc(k->age);
+    if (slot_det[s] >= 0) {
+      k->det = dets[slot_det[s]];
+      k->hits = yfi_track_inc(k->hits);
+      k->misses = 0;
+    } else {
+      k->misses = yfi_track_inc(k->misses);
+      if (k->misses > p->max_misses) memset(k, 0, sizeof *k);
+    }
+  }
+  int s = 0;
+  for (int j = 0; j < m; ++j) {
+    if (det_slot[j] >= 0) continue;
+    while (s < YF_TRACK_SLOTS && st->slot[s].id != 0) ++s;
+    if (s == YF_TRACK_SLOTS) { bits |= YFI_TRACK_ST_DROPPED; break; }
+    yf_track* k = &st->slot[s];
+    st->issued = yfi_track_next_id(st->issued, 0);
+    k->id = st->issued; k->hits = 1; k->misses = 0; k->age = 1; k->det = dets[j];
+  }
+  int emitted[YF_TRACK_SLOTS] = {0}, total = 0;
+  for (;;) {
+    int pick = -1;
+    for (int q = 0; q < YF_TRACK_SLOTS; ++q) {
+      const yf_track* k = &st->slot[q];
+      if (emitted[q] || k->id == 0 || k->hits < p->min_hits) continue;
+      if (pick < 0 || k->id < st->slot[pick].id) pick = q;
+    }
+    if (pick < 0) break;
+    emitted[pick] = 1;
+    if (total < out_cap) {
+      const yf_track* k = &st->slot[pick];
+      out[total] = k->det;
+      out[total].frame = frame;
+      info[total].id = k->id; info[total].hits = k->hits; info[total].misses = k->misses; info[total].age = k->age;
+    }
+    ++total;
+  }
+  *out_count = total;
+  if (status) *status = bits;
+}
+
+EXPORT long yf_images_track_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                 const yf_track_params* params, void* state, void* out, void* info, void* out_counts, int out_cap,
+                                 int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status) != NULL) return -1;
+  const yf_track_params p = *params;
+  for (long s = 0; s < streams; ++s)
+    for (long t = 0; t < steps; ++t) {
+      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
+      track_step_host((yf_track_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
+                      (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
+                      (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
+    }
+  return streams * steps;
+}
+
+/* the argument check alone: the text of the first fault into text (at most text_bytes, 0-terminated), or an empty text; returns 1 for a fault */
+EXPORT int yfi_track_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                const yf_track_params* params, const void* state, const void* out, const void* info, const void* out_counts,
+                                int out_cap, const void* status, char* text, int text_bytes) {
+  const char* t = yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }

@@ -27,6 +27,12 @@ in its picture on the GPU, packed pixels or an NV12 / NV21 surface, and the reda
 `redact_records_device`, `redact_records_yuv_device`; the definition is the library's own (csrc/yf_images_redact.h, `ptq.redact_u8`,
 `ptq.redact_yuv420sp`).
 
+`detect_tracked(network, images, tracker, steps)` is the step a video needs between the boxes of a frame and what is done with the frame:
+a `Tracker` keeps per-stream track state on the device and associates each frame's kept boxes with it, so that every face has an identity
+over the frames and a face the detector misses for a few frames is held over with its last box -- `track_device`; its output is records
+again, which `crop_records_device` and `redact_records_device` take as they are.  The reference has no tracker; the definition is the
+library's own (csrc/yf_images_track.h, `ptq.track_step`).
+
 NV12 / NV21 surfaces -- 4:2:0 semi-planar, what hardware video and JPEG decoders write and what `detect_video` of the reference's
 yoloface/tensorflow/yoloface_test.py:318-385 has behind cv2.VideoCapture -- are read where they lie: `pack_yuv_images`, the four
 `prepare_yuv_*` bindings, and `detect` / `evaluate` with fmt="nv12" or "nv21".  The frame of a surface is the frame of
@@ -82,6 +88,19 @@ YF_CROP_SQUARE = 1
 ORDERS = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}
 YF_REDACT_MOSAIC, YF_REDACT_FILL = 0, 1
 REDACT_MODES = {"mosaic": YF_REDACT_MOSAIC, "fill": YF_REDACT_FILL}
+
+
+# the tracker (yf_track_params, yf_track_info, yf_track_state): 64 slots per stream, at most 64 detections of a frame count
+class YfTrackParams(ctypes.Structure):
+    _fields_ = [("match_iou", ctypes.c_double), ("min_hits", ctypes.c_int32), ("max_misses", ctypes.c_int32)]
+
+
+TRACK_INFO_DTYPE = np.dtype([("id", "<u4"), ("hits", "<i4"), ("misses", "<i4"), ("age", "<i4")])
+TRACK_SLOTS, TRACK_STATE_BYTES = 64, 2824
+assert TRACK_INFO_DTYPE.itemsize == 16 and ctypes.sizeof(YfTrackParams) == 16
+YF_TRACK_TIME_MAJOR, YF_TRACK_STREAM_MAJOR = 0, 1
+TRACK_LAYOUTS = {"time": YF_TRACK_TIME_MAJOR, "stream": YF_TRACK_STREAM_MAJOR}
+YF_TRACK_CLIPPED, YF_TRACK_DROPPED = 1, 2      # the bits of a frame's status
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -155,6 +174,8 @@ def _entries():
         # stream
         "redact_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
         "redact_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
+        # d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream
+        "track_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
     }
 
 
@@ -183,6 +204,8 @@ def load():
     lib.yf_images_set_decode_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     lib.yf_images_average_precision_workspace.restype = ctypes.c_size_t
     lib.yf_images_average_precision_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
+    lib.yf_images_track_state_bytes.restype = ctypes.c_size_t
+    lib.yf_images_track_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
     lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
     lib.yf_images_eval_sort_tile.restype = ctypes.c_int
@@ -897,6 +920,104 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
             C = CHANNELS[format_code(fmt)]
             pictures.append(_strided(buf, int(e["offset"]), h, w * C, int(e["row_stride"])).copy().reshape(h, w, C))
     return pictures, boxes
+
+
+def _layout_code(layout):
+    if isinstance(layout, str) and layout.lower() in TRACK_LAYOUTS:
+        return TRACK_LAYOUTS[layout.lower()]
+    if layout in (YF_TRACK_TIME_MAJOR, YF_TRACK_STREAM_MAJOR) and not isinstance(layout, (str, bool)):
+        return int(layout)
+    raise ValueError(f"layout {layout!r}: 'time' (frame t * streams + s) or 'stream' (frame s * steps + t)")
+
+
+def track_state_bytes(streams):
+    """The bytes of the track state of `streams` streams (yf_images_track_state_bytes): 2824 each.  All zero is the empty state."""
+    return int(load().yf_images_track_state_bytes(streams))
+
+
+def track_device(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status=None,
+                 stream=None):
+    """The records of streams * steps frames associated with the track state of their streams (yf_images_track_device): d_dets
+    yf_det[n][cap], d_counts int32[n], frame t * streams + s (layout "time") or s * steps + t ("stream"); params = (match_iou, min_hits,
+    max_misses); d_state the streams' state (`track_state_bytes`, read and written); d_out yf_det[n][out_cap], d_info
+    TRACK_INFO_DTYPE[n][out_cap], d_out_counts int32[n], d_status int32[n] or None are written.  The definition: csrc/yf_images_track.h,
+    ptq.track_step.  Returns n."""
+    lib = load()
+    p = YfTrackParams(float(params[0]), int(params[1]), int(params[2]))
+    rc = lib.yf_images_track_device(d_dets, d_counts, streams, steps, _layout_code(layout), cap, ctypes.byref(p), d_state, d_out, d_info,
+                                    d_out_counts, out_cap, d_status, stream)
+    if rc != streams * steps or rc < 0:
+        raise ImagesError(f"yf_images_track_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
+    return rc
+
+
+class Tracker:
+    """The track state of `streams` video streams on the device, and the parameters of their association.  match_iou=0.3, min_hits=1,
+    max_misses=5 are the library's choice for faces at a video rate -- a box that moved by less than about half its side still matches,
+    every detection is reported at once, a face is held over for five frames -- not something the reference states or a measurement.
+    `update` takes the records of the next steps; `reset` empties every stream (an all-zero state is the empty state)."""
+
+    def __init__(self, streams, match_iou=0.3, min_hits=1, max_misses=5, device=None):
+        import torch
+        if int(streams) < 1:
+            raise ValueError(f"streams {streams!r}: at least 1")
+        self.params = (float(match_iou), int(min_hits), int(max_misses))
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.reset(streams)
+
+    def reset(self, streams=None):
+        """every stream empty again; with `streams`, a new number of them"""
+        import torch
+        if streams is not None:
+            self.streams = int(streams)
+            self.d_state = torch.zeros((self.streams, TRACK_STATE_BYTES), dtype=torch.uint8, device=self.device)
+        else:
+            self.d_state.zero_()
+
+    def update(self, d_dets, d_counts, steps, layout="time", cap=None, out_cap=TRACK_SLOTS, stream=None):
+        """The next `steps` frames of every stream: d_dets uint8 [streams * steps, cap, 28] and d_counts int32 [streams * steps], tensors on
+        the tracker's device (the output of a suppression).  -> (d_out uint8 [n, out_cap, 28], d_info uint8 [n, out_cap, 16], d_out_counts
+        int32 [n], d_status int32 [n]) on the stream given (default: the device's current one), not synchronised."""
+        import torch
+        n = self.streams * int(steps)
+        cap = d_dets.shape[1] if cap is None else cap
+        d_out = torch.empty((n, out_cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        d_info = torch.empty((n, out_cap, TRACK_INFO_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        d_out_counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        d_status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        track_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap, self.params, self.d_state.data_ptr(),
+                     d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap, d_status.data_ptr(), stream)
+        return d_out, d_info, d_out_counts, d_status
+
+
+def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8"):
+    """`detect` with the suppression for the next `steps` frames of the `tracker`'s streams, and the kept boxes associated with its track
+    state on the same stream: `images` holds tracker.streams * steps pictures, frame t of stream s at index t * streams + s (layout
+    "time": one frame of every camera per step) or s * steps + t ("stream": a clip per stream).  fmt, iou_threshold (not None: the tracker
+    takes a frame's records in descending confidence), size, dtype as in `detect`; the tracker's device is used.
+    Returns per frame a list of (id, x1, y1, x2, y2, conf, hits, misses) in ascending id: the tracks reported for that frame, a held-over
+    one (misses > 0) with the box it was last seen at.  The tracker carries on from there at the next call.  The definition is the
+    library's own: csrc/yf_images_track.h, restated as `ptq.track_step`."""
+    steps = int(steps)
+    if steps < 0 or len(images) != tracker.streams * steps:
+        raise ValueError(f"{len(images)} images: {tracker.streams} streams x {steps} steps")
+    if iou_threshold is None:
+        raise ValueError("iou_threshold None: the tracker takes suppressed records")
+    _layout_code(layout)
+    n = len(images)
+    if n == 0:
+        return []
+    d_dets, d_counts, _, stream, keep = _records_on_device(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype)
+    d_out, d_info, d_out_counts, d_status = tracker.update(d_dets, d_counts, steps, layout, stream=stream.cuda_stream)
+    stream.synchronize()
+    del keep
+    out = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, -1)
+    info = d_info.cpu().numpy().view(TRACK_INFO_DTYPE).reshape(n, -1)
+    counts = d_out_counts.cpu().numpy()
+    return [[(int(i["id"]), int(d["x1"]), int(d["y1"]), int(d["x2"]), int(d["y2"]), float(d["conf"]), int(i["hits"]), int(i["misses"]))
+             for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
 
 
 def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):

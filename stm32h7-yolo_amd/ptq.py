@@ -460,3 +460,121 @@ def redact_yuv420sp(y, uv, regions, mode, block, colour, v_first=False):
             y_out[y0:y0 + rh, x0:x0 + rw] = yy
             pairs_out[y0 >> 1:((y0 + rh - 1) >> 1) + 1, x0 >> 1:((x0 + rw - 1) >> 1) + 1] = (v, u) if v_first else (u, v)
     return y_out, uv_out
+
+
+# ---- the tracker (csrc/yf_images_track.h), in plain Python ----
+TRACK_SLOTS, TRACK_MAX_DETS = 64, 64
+TRACK_CLIPPED, TRACK_DROPPED = 1, 2
+_INT32_MAX = 2 ** 31 - 1
+_ZERO_DET = (0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0)
+
+
+def track_empty_state():
+    """The empty state of one stream: what 2824 zero bytes are.  {"issued", "reserved", "slots": 64 x [id, hits, misses, age, det]}, det a
+    record as below."""
+    return {"issued": 0, "reserved": 0, "slots": [[0, 0, 0, 0, _ZERO_DET] for _ in range(TRACK_SLOTS)]}
+
+
+def _track_inc(v):
+    return v if v == _INT32_MAX else v + 1
+
+
+def _track_area(d):
+    return (float(d[8]) - float(d[6]) + 1.0) * (float(d[9]) - float(d[7]) + 1.0)
+
+
+def track_iou(a, b):
+    """(inter, iou) of two records' boxes: the suppression's arithmetic (csrc/yf_images_nms.h, the + 1 pixel convention of
+    yoloface_test.py:165-190), one float64 operation per step; iou is None when inter is not above 0"""
+    xx1, yy1 = float(max(a[6], b[6])), float(max(a[7], b[7]))
+    xx2, yy2 = float(min(a[8], b[8])), float(min(a[9], b[9]))
+    wv, hv = xx2 - xx1 + 1.0, yy2 - yy1 + 1.0
+    w, h = wv if wv > 0.0 else 0.0, hv if hv > 0.0 else 0.0
+    inter = w * h
+    if not inter > 0.0:
+        return inter, None
+    uni = (_track_area(a) + _track_area(b)) - inter
+    return inter, inter / uni
+
+
+def track_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
+    """One step of the tracker -- one stream, one frame -- as csrc/yf_images_track.h states it, in Python integers and floats (float64).
+    `state`: as `track_empty_state` gives it (not changed; the new state is returned).  `dets`: the frame's records, tuples (frame, anchor,
+    row, col, q_conf, conf, x1, y1, x2, y2) -- only the four edges are read, a record travels as it is.  `params`: (match_iou, min_hits,
+    max_misses).  `count`, `cap`: the frame's count and the capacity of its row (default: len(dets) both); the first
+    m = min(max(count, 0), cap, 64) records count.  `stats`: a dict whose counters "matches", "births", "removals", "held", "ties",
+    "dropped" are added to.
+    -> (state, emitted, status): emitted = [(record with its frame field set to `frame`, (id, hits, misses, age)), ...] in ascending id,
+    all of them (the device writes the first out_cap); status bit 0: count above min(cap, 64), bit 1: a detection found no free slot.
+
+    The match is the global greedy one: repeatedly the eligible pair (inter > 0.0 and iou >= match_iou) of the largest IoU among the slots
+    and detections still unmatched, ties to the lower detection, then the lower slot.  Taking the pairs in that order once, sorted, and
+    skipping those with a matched member picks the same pairs: the order of two pairs does not depend on which others are left."""
+    match_iou, min_hits, max_misses = float(params[0]), int(params[1]), int(params[2])
+    count = len(dets) if count is None else int(count)
+    cap = len(dets) if cap is None else int(cap)
+    lim = min(cap, TRACK_MAX_DETS)
+    m = min(max(count, 0), lim)
+    status = TRACK_CLIPPED if count > lim else 0
+    dets = [tuple(d) for d in dets[:m]]
+    slots = [list(s) for s in state["slots"]]
+    issued = int(state["issued"])
+    occupied = [s[0] != 0 for s in slots]
+    pairs = []
+    for k, s in enumerate(slots):
+        if occupied[k]:
+            for j, d in enumerate(dets):
+                iou = track_iou(s[4], d)[1]
+                if iou is not None and iou >= match_iou:
+                    pairs.append((-iou, j, k))
+    pairs.sort()
+    slot_det, det_slot = {}, {}
+    ties = 0
+    for at, (neg, j, k) in enumerate(pairs):
+        if j in det_slot or k in slot_det:
+            continue
+        # a tie: another pair of the same IoU was still to be had when this one was taken, and shares a member with it
+        nxt = at + 1
+        while nxt < len(pairs) and pairs[nxt][0] == neg:
+            j2, k2 = pairs[nxt][1:]
+            if j2 not in det_slot and k2 not in slot_det and (j2 == j or k2 == k):
+                ties += 1
+                break
+            nxt += 1
+        det_slot[j], slot_det[k] = k, j
+    removals = held = 0
+    for k, s in enumerate(slots):
+        if not occupied[k]:
+            continue
+        s[3] = _track_inc(s[3])
+        if k in slot_det:
+            s[4], s[1], s[2] = dets[slot_det[k]], _track_inc(s[1]), 0
+        else:
+            s[2] = _track_inc(s[2])
+            if s[2] > max_misses:
+                slots[k] = [0, 0, 0, 0, _ZERO_DET]
+                removals += 1
+    births = dropped = 0
+    for j, d in enumerate(dets):
+        if j in det_slot:
+            continue
+        free = [k for k, s in enumerate(slots) if s[0] == 0]
+        if not free:
+            status |= TRACK_DROPPED
+            dropped += 1
+            continue
+        issued = (issued + 1) & 0xFFFFFFFF
+        if issued == 0:
+            issued = 1
+        slots[free[0]] = [issued, 1, 0, 1, d]
+        births += 1
+    emitted = []
+    for k in sorted((k for k, s in enumerate(slots) if s[0] != 0 and s[1] >= min_hits), key=lambda k: (slots[k][0], k)):
+        i, hits, misses, age, d = slots[k]
+        emitted.append(((int(frame),) + tuple(d[1:]), (i, hits, misses, age)))
+        held += misses > 0
+    if stats is not None:
+        for name, v in (("matches", len(slot_det)), ("births", births), ("removals", removals), ("held", held), ("ties", ties),
+                        ("dropped", dropped)):
+            stats[name] = stats.get(name, 0) + v
+    return {"issued": issued, "reserved": state["reserved"], "slots": slots}, emitted, status

@@ -1,0 +1,31 @@
+"""Static resources of the tracker's kernel, read off the built libyf_images.so (tools/isa_hashes.py): the kernel of namespace yftrack
+exists, uses no scratch and spills no register.  Its VGPR count is recorded in profiles/track_bench.txt, not bounded here: what the float64
+IoU costs has not been weighed against occupancy."""
+import os
+import sys
+
+import pytest
+
+from conftest import ROOT
+from images_support import images          # noqa: F401 (fixture)
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+pytestmark = pytest.mark.skipif(not all(os.path.exists(os.path.join(LLVM, t)) for t in ("llvm-objcopy", "llvm-objdump", "llvm-readelf", "clang-offload-bundler")),
+                                reason="needs the ROCm LLVM tools")
+
+
+def test_the_track_kernel_uses_no_scratch(images):
+    images.load()                                 # builds the library if it is stale
+    sys.path.insert(0, ROOT)
+    from tools import isa_hashes
+    res = {}
+    isa_hashes.disassemble(images.lib_path(), res)
+    ours = [k for k in res if "yftrack" in k]
+    assert len(ours) == 1 and "step_kernel" in ours[0], sorted(res)
+    # tests/test_crops_resources.py and tests/test_redact_resources.py count their kernels by these names
+    assert not any("yfcrop" in k or "yfredact" in k for k in ours)
+    for k in ours:
+        assert res[k]["private_segment_fixed_size"] == 0, (k, res[k])
+        assert res[k]["sgpr_spill_count"] == 0 and res[k]["vgpr_spill_count"] == 0, (k, res[k])
+        assert res[k]["group_segment_fixed_size"] == 0, (k, res[k])          # one wave, registers and cross-lane reads only
