@@ -33,6 +33,9 @@ over the frames and a face the detector misses for a few frames is held over wit
 again, which `crop_records_device` and `redact_records_device` take as they are.  The reference has no tracker; the definition is the
 library's own (csrc/yf_images_track.h, `ptq.track_step`).
 
+All of these start alike: `_stage` packs the batch and launches images -> records on the device's current stream, and what it returns
+(`_Batch`: the records, the pixels, the pictures' descriptors, the stream) is what a call's own stage is launched on.
+
 NV12 / NV21 surfaces -- 4:2:0 semi-planar, what hardware video and JPEG decoders write and what `detect_video` of the reference's
 yoloface/tensorflow/yoloface_test.py:318-385 has behind cv2.VideoCapture -- are read where they lie: `pack_yuv_images`, the four
 `prepare_yuv_*` bindings, and `detect` / `evaluate` with fmt="nv12" or "nv21".  The frame of a surface is the frame of
@@ -41,6 +44,7 @@ color_yuv.simd.hpp, BT.601 limited range, not pinned against a real cv2; the ari
 I420, BT.709, full-range variants, odd-sided surfaces, and tiling (`detect_tiled`, `evaluate(tile=...)`: a tile's origin would have to be even).
 """
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -85,9 +89,9 @@ assert TILE_DTYPE.itemsize == 20
 CHIP_DTYPE = np.dtype([("frame", "<i4"), ("slot", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4"), ("status", "<i4")])
 assert CHIP_DTYPE.itemsize == 28
 YF_CROP_SQUARE = 1
-ORDERS = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}
+ORDERS, ORDER_WHAT = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}, "order {!r}: 'rgb' or 'bgr'"
 YF_REDACT_MOSAIC, YF_REDACT_FILL = 0, 1
-REDACT_MODES = {"mosaic": YF_REDACT_MOSAIC, "fill": YF_REDACT_FILL}
+REDACT_MODES, MODE_WHAT = {"mosaic": YF_REDACT_MOSAIC, "fill": YF_REDACT_FILL}, "mode {!r}: 'mosaic' or 'fill'"
 
 
 # the tracker (yf_track_params, yf_track_info, yf_track_state): 64 slots per stream, at most 64 detections of a frame count
@@ -100,6 +104,7 @@ TRACK_SLOTS, TRACK_STATE_BYTES = 64, 2824
 assert TRACK_INFO_DTYPE.itemsize == 16 and ctypes.sizeof(YfTrackParams) == 16
 YF_TRACK_TIME_MAJOR, YF_TRACK_STREAM_MAJOR = 0, 1
 TRACK_LAYOUTS = {"time": YF_TRACK_TIME_MAJOR, "stream": YF_TRACK_STREAM_MAJOR}
+LAYOUT_WHAT = "layout {!r}: 'time' (frame t * streams + s) or 'stream' (frame s * steps + t)"
 YF_TRACK_CLIPPED, YF_TRACK_DROPPED = 1, 2      # the bits of a frame's status
 
 
@@ -579,55 +584,116 @@ def pack_ground_truths(ground_truths):
     return packed, np.array([g.shape[0] for g in gts], np.int32)
 
 
-def _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype, packed=None):
-    """What `detect` launches, with the records left on the device: checks size and dtype as it does, packs the images, allocates the
-    workspaces, runs images -> frames -> network -> records (and the suppression when iou_threshold is not None) on the device's current
-    stream without synchronising.  -> (d_dets uint8 [n, cap, 28], d_counts int32 [n], d_status int32 [n], stream, keep), `keep` the
-    tensors that must outlive the launches.  packed=(pixels, descriptors): the batch as it is (`pack_tiles`: one frame per tile) instead of
-    `pack_images(images)`.  `detect` keeps its own copy of these lines (it predates this helper and is left as it is);
-    a change to one belongs in the other."""
+def _check_frames(size, dtype):
     if size not in (56, 160):
         raise ValueError(f"size {size!r}: 56 or 160")
     if dtype not in ("int8", "fp16"):
         raise ValueError(f"dtype {dtype!r}: 'int8' or 'fp16'")
     if dtype == "fp16" and size != 56:
         raise ValueError("dtype 'fp16': the fp16 network has 56x56 frames only")
+
+
+@dataclasses.dataclass
+class _Batch:
+    """A batch as `_stage` left it on the device.  The tensors live as long as the object: hold it until the stream is synchronised."""
+    n: int                  # pictures
+    cap: int                # records a picture can hold: d_dets uint8 [n, cap, 28]
+    device: object
+    stream: object          # the device's current stream at staging: everything was launched on it, nothing waited for
+    d_dets: object          # the records a caller works on: after the suppression if there was one; with tiles, those of a picture's tiles merged
+    d_counts: object        # int32 [n], how many of them each picture has
+    d_status: object       # int32 per frame of the network (a picture, or with tiles a tile): 1 the library refused its descriptor
+    d_totals: object        # with tiles int32 [n], the merged records per picture before the suppression and the cut at cap; else None
+    d_px: object            # the pictures' bytes, as pack_images / pack_yuv_images laid them out
+    nbytes: int
+    d_pictures: object      # the pictures' descriptors as the crop and redact entries take them: YUV_IMAGE_DTYPE [n] for NV12 / NV21
+                            # surfaces, IMAGE_DTYPE [n] for packed pictures (with tiles: of the parent pictures, not of the tiles)
+    held: tuple             # everything else the launches read or write
+
+    def boxes(self, counts):
+        """the first counts[i] records of every picture i -> a list of int32 [k, 4] arrays (x1, y1, x2, y2); after a synchronise"""
+        dets = self.d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(self.n, self.cap)
+        out = []
+        for i in range(self.n):
+            d = dets[i, :int(counts[i])]
+            out.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
+        return out
+
+    def check_totals(self, what):
+        """with tiles: a picture whose merged records did not fit into cap raises; after a synchronise"""
+        if self.d_totals is None:
+            return
+        totals = self.d_totals.cpu().numpy()
+        over = np.nonzero(totals > self.cap)[0]
+        if over.size:
+            i = int(over[0])
+            raise ImagesError(f"{what}: image {i} has {int(totals[i])} merged records, out_cap holds {self.cap}"
+                              + (f" (and {over.size - 1} more image(s) above it)" if over.size > 1 else ""))
+
+
+def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=None, stride=None, whole=True, out_cap=None):
+    """What every `detect_*` call and `evaluate` launch first, with the records left on the device -- the place to hang a new stage
+    behind: packs the pictures, allocates the workspaces and runs images -> frames -> network -> records (and the suppression when
+    iou_threshold is not None) at `size` and `dtype` on the device's current stream, without synchronising.  cap=None holds every candidate
+    (147 / 1200).  With `tile` (and `stride`, `whole`: `plan_tiles`) the frames are the pictures' tiles, every candidate of a tile is
+    held, and the tiles' records are merged per picture (`gather_tiles_device`) into out_cap slots (None: 1200) and suppressed there
+    (`nms_wide_device`); the pixels are packed once, the tiles share them."""
+    if tile is not None:
+        out_cap = NMS_WIDE_MAX_CAP if out_cap is None else out_cap
+        if not 1 <= out_cap <= NMS_WIDE_MAX_CAP:
+            raise ValueError(f"out_cap {out_cap!r}: 1 to {NMS_WIDE_MAX_CAP}")
+    _check_frames(size, dtype)
     import torch
-    grid = size // 8
+    yuv, n = is_yuv(fmt), len(images)
+    buf, pictures = pack_yuv_images(images, fmt) if yuv else pack_images(images, fmt)
+    desc = yuv_sizes(pictures) if yuv else pictures     # a frame's descriptor for the run and the decode: IMAGE_DTYPE
+    if tile is not None:
+        tiles, desc, first = plan_tiles(pictures, fmt, tile, stride, whole)
+        cap = None
+    grid, t = size // 8, desc.shape[0]
     if cap is None:
         cap = 3 * grid * grid
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    yuv_desc = None
-    if packed is None and is_yuv(fmt):
-        buf, yuv_desc = pack_yuv_images(images, fmt)
-        desc = yuv_sizes(yuv_desc)
-    else:
-        buf, desc = pack_images(images, fmt) if packed is None else packed
-    n = desc.shape[0]
-    d_px = torch.from_numpy(buf).to(dev)
-    d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
-    d_yuv_desc = None if yuv_desc is None else torch.from_numpy(yuv_desc.view(np.uint8)).to(dev)
+    upload = lambda a: torch.from_numpy(a.view(np.uint8)).to(dev)
+    d_px, d_desc = torch.from_numpy(buf).to(dev), upload(desc)
+    d_pictures = d_desc if desc is pictures else upload(pictures)
     f16 = dtype == "fp16"
-    d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
-    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
-    d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
-    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    d_frames = torch.empty((t, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
+    d_heads = torch.empty((t, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
+    d_dets = torch.empty((t, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_counts = torch.empty(t, dtype=torch.int32, device=dev)
+    d_status = torch.empty(t, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
+    s = stream.cuda_stream
     run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
     if f16:
         run = run_decode_f16_ragged_device
     else:
-        set_decode_tables(*network.decode_tables())
-    if d_yuv_desc is not None:
-        _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_yuv_desc.data_ptr(), d_desc.data_ptr(), n, d_frames.data_ptr(),
-                        d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, stream.cuda_stream)
+        set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
+    if yuv:
+        _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_pictures.data_ptr(), d_desc.data_ptr(), t, d_frames.data_ptr(),
+                        d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, s)
     else:
-        run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
-            d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
-    if iou_threshold is not None:
-        nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
-    return d_dets, d_counts, d_status, stream, (d_px, d_desc, d_yuv_desc, d_frames, d_heads)
+        run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), t, d_frames.data_ptr(), d_heads.data_ptr(),
+            d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=s)
+    held = (d_desc, d_frames, d_heads)
+    if tile is None:
+        if iou_threshold is not None:
+            nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=s)
+        return _Batch(n, cap, dev, stream, d_dets, d_counts, d_status, None, d_px, buf.nbytes, d_pictures, held)
+    d_tiles, d_first = upload(tiles), torch.from_numpy(first).to(dev)
+    d_out = torch.empty((n, out_cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_totals = torch.empty(n, dtype=torch.int32, device=dev)
+    work_bytes = gather_tiles_workspace(t)
+    d_work = torch.empty(max(work_bytes, 16), dtype=torch.uint8, device=dev)
+    gather_tiles_device(d_dets.data_ptr(), d_counts.data_ptr(), t, cap, d_tiles.data_ptr(), d_first.data_ptr(), n, d_out.data_ptr(),
+                        d_totals.data_ptr(), out_cap, d_work.data_ptr(), work_bytes, stream=s)
+    d_kept = d_totals
+    if iou_threshold is not None:                       # the records in place, the kept counts beside the totals
+        d_kept = torch.empty(n, dtype=torch.int32, device=dev)
+        nms_wide_device(d_out.data_ptr(), d_totals.data_ptr(), n, out_cap, iou_threshold, d_out.data_ptr(), d_kept.data_ptr(), stream=s)
+    return _Batch(n, out_cap, dev, stream, d_out, d_kept, d_status, d_totals, d_px, buf.nbytes, d_pictures,
+                  held + (d_dets, d_counts, d_tiles, d_first, d_work))
 
 
 def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None,
@@ -649,82 +715,47 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     gt, gt_counts = pack_ground_truths(ground_truths)
     if n == 0:
         return {"ap": 0.0, "detections": 0, "ground_truths": 0, "true_positives": 0, "precision": 0.0, "recall": 0.0}
-    d_totals = None
-    if tile is None:
-        d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, None, device, iou_threshold, size, dtype)
-    else:
-        d_dets, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt, NMS_WIDE_MAX_CAP,
-                                                                                      device, iou_threshold, size, dtype)
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole)
     import torch
-    dev, cap, gt_cap = d_dets.device, d_dets.shape[1], gt.shape[1]
+    dev, cap, gt_cap, s = b.device, b.cap, gt.shape[1], b.stream.cuda_stream
     d_gt = torch.from_numpy(gt.view(np.float64).reshape(n, gt_cap, 4)).to(dev)
     d_gt_counts = torch.from_numpy(gt_counts).to(dev)
     d_tp = torch.empty((n, cap), dtype=torch.uint8, device=dev)
     work_bytes = average_precision_workspace(n, cap)
     d_work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
     d_result = torch.empty(4, dtype=torch.float64, device=dev)
-    match_device(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, d_gt.data_ptr(), d_gt_counts.data_ptr(), gt_cap, conf_iou,
-                 d_tp.data_ptr(), stream=stream.cuda_stream)
-    average_precision_device(d_dets.data_ptr(), d_counts.data_ptr(), d_tp.data_ptr(), n, cap, d_gt_counts.data_ptr(), gt_cap,
-                             d_work.data_ptr(), work_bytes, d_result.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    del keep
-    bad = np.nonzero(d_status.cpu().numpy())[0]
+    match_device(b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, cap, d_gt.data_ptr(), d_gt_counts.data_ptr(), gt_cap, conf_iou,
+                 d_tp.data_ptr(), stream=s)
+    average_precision_device(b.d_dets.data_ptr(), b.d_counts.data_ptr(), d_tp.data_ptr(), n, cap, d_gt_counts.data_ptr(), gt_cap,
+                             d_work.data_ptr(), work_bytes, d_result.data_ptr(), stream=s)
+    b.stream.synchronize()
+    bad = np.nonzero(b.d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"evaluate: the library refused image(s) {bad.tolist()} (status 1): their frames hold no picture")
-    if d_totals is not None:
-        _check_totals("evaluate", d_totals, cap)
+    b.check_totals("evaluate")
     res = d_result.cpu().numpy().view(EVAL_RESULT_DTYPE)[0]
     m, num_gt, tp = int(res["detections"]), int(res["ground_truths"]), int(res["true_positives"])
     return {"ap": float(res["ap"]), "detections": m, "ground_truths": num_gt, "true_positives": tp,
             "precision": tp / (m + 1e-16), "recall": tp / max(1, num_gt)}
 
 
-def _tiled_records_on_device(network, images, tile, stride, whole, fmt, out_cap, device, iou_threshold, size, dtype):
-    """What `detect_tiled` launches, with the merged records left on the device: the tiles of `images` through the ragged run of `size`
-    and `dtype` (every candidate held: 147 / 1200 per tile), `gather_tiles_device`, and `nms_wide_device` on the merged records in place
-    when iou_threshold is not None -- one stream, no synchronisation.  -> (d_out uint8 [n, out_cap, 28], d_counts int32 [n] the counts
-    after the suppression, d_totals int32 [n] the merged totals before it, d_status int32 [t], stream, keep)."""
-    if not 1 <= out_cap <= NMS_WIDE_MAX_CAP:
-        raise ValueError(f"out_cap {out_cap!r}: 1 to {NMS_WIDE_MAX_CAP}")
-    import torch
-    buf, tile_desc, tiles, first = pack_tiles(images, fmt, tile, stride, whole)
-    n, t = len(images), tiles.shape[0]
-    d_dets, d_tile_counts, d_status, stream, keep = _records_on_device(network, None, fmt, None, device, None, size, dtype,
-                                                                       packed=(buf, tile_desc))
-    dev, cap = d_dets.device, d_dets.shape[1]
-    d_tiles = torch.from_numpy(tiles.view(np.uint8)).to(dev)
-    d_first = torch.from_numpy(first).to(dev)
-    d_out = torch.empty((n, out_cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_totals = torch.empty(n, dtype=torch.int32, device=dev)
-    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
-    work_bytes = gather_tiles_workspace(t)
-    d_work = torch.empty(max(work_bytes, 16), dtype=torch.uint8, device=dev)
-    gather_tiles_device(d_dets.data_ptr(), d_tile_counts.data_ptr(), t, cap, d_tiles.data_ptr(), d_first.data_ptr(), n, d_out.data_ptr(),
-                        d_totals.data_ptr(), out_cap, d_work.data_ptr(), work_bytes, stream=stream.cuda_stream)
-    if iou_threshold is not None:                       # the records in place, the kept counts beside the totals
-        nms_wide_device(d_out.data_ptr(), d_totals.data_ptr(), n, out_cap, iou_threshold, d_out.data_ptr(), d_counts.data_ptr(),
-                        stream=stream.cuda_stream)
-    else:
-        d_counts = d_totals
-    return d_out, d_counts, d_totals, d_status, stream, (keep, d_dets, d_tile_counts, d_tiles, d_first, d_work)
+def _code(table, value, what):
+    """`value` as a code of `table` (name -> code): one of its names in any letter case, or one of its codes as a number (not a bool);
+    anything else is refused with `what`, a text with one place for the value"""
+    if isinstance(value, str):
+        if value.lower() in table:
+            return table[value.lower()]
+    elif not isinstance(value, bool) and value in table.values():
+        return int(value)
+    raise ValueError(what.format(value))
 
 
-def _check_totals(what, d_totals, out_cap):
-    totals = d_totals.cpu().numpy()
-    over = np.nonzero(totals > out_cap)[0]
-    if over.size:
-        i = int(over[0])
-        raise ImagesError(f"{what}: image {i} has {int(totals[i])} merged records, out_cap holds {out_cap}"
-                          + (f" (and {over.size - 1} more image(s) above it)" if over.size > 1 else ""))
-
-
-def _order_code(order):
-    if isinstance(order, str) and order.lower() in ORDERS:
-        return ORDERS[order.lower()]
-    if order in (YF_PIX_RGB8, YF_PIX_BGR8) and not isinstance(order, str):
-        return int(order)
-    raise ValueError(f"order {order!r}: 'rgb' or 'bgr'")
+def _permille(margin):
+    """a share of a box's side, 0 to 1 -> permille, as the crop and redact entries take it"""
+    permille = int(round(float(margin) * 1000))
+    if not 0 <= permille <= 1000:
+        raise ValueError(f"margin {margin!r}: 0 to 1")
+    return permille
 
 
 def crop_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, out_h, out_w, d_chips, chips_cap, d_first, d_info,
@@ -733,7 +764,8 @@ def crop_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts,
     yf_det[n][cap], d_counts int32[n] -> d_chips uint8 [chips_cap, out_h, out_w, 3] in `order`, d_first int32[n + 1] (chip first[i] + s is
     slot s of frame i; first[n] the true total), d_info CHIP_DTYPE[chips_cap].  The region rule: csrc/yf_images_crop.h, ptq.crop_region."""
     _call("crop_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "crop_records_device"), d_images, d_dets, d_counts, n, cap,
-          out_h, out_w, _order_code(order), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info, stream)
+          out_h, out_w, _code(ORDERS, order, ORDER_WHAT), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info,
+          stream)
 
 
 def crop_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, out_h, out_w, d_chips, chips_cap, d_first, d_info,
@@ -741,7 +773,7 @@ def crop_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
     """`crop_records_device` for NV12 / NV21 surfaces, read where they lie (yf_images_crop_records_yuv_device): d_images
     YUV_IMAGE_DTYPE[n]; a chip is the chip of the converted picture."""
     _call("crop_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, out_h, out_w,
-          _order_code(order), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info, stream)
+          _code(ORDERS, order, ORDER_WHAT), margin_permille, YF_CROP_SQUARE if square else 0, d_chips, chips_cap, d_first, d_info, stream)
 
 
 def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, order="rgb", fmt="bgr", cap=None, iou_threshold=0.4, size=56,
@@ -759,64 +791,35 @@ def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, orde
     the same order, and the CHIP_DTYPE [k] rows (the region actually sampled; status 1: the box has no pixel in the picture, the chip is
     zeros)."""
     out_h, out_w = _pair(out, "out")
-    permille = int(round(float(margin) * 1000))
-    if not 0 <= permille <= 1000:
-        raise ValueError(f"margin {margin!r}: 0 to 1")
-    order_code = _order_code(order)
+    permille = _permille(margin)
+    order_code = _code(ORDERS, order, ORDER_WHAT)
     n = len(images)
     if n == 0:
         return [], [], []
     import torch
-    if tile is None:
-        d_dets, d_counts, d_status, stream, keep = _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype)
-        d_px, d_desc = keep[0], keep[2] if is_yuv(fmt) else keep[1]
-        d_totals = None
-    else:
+    if tile is not None:
         _packed_code(fmt, "detect_chips(tile=...)")
-        d_dets, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt,
-                                                                                      NMS_WIDE_MAX_CAP if cap is None else cap, device,
-                                                                                      iou_threshold, size, dtype)
-        d_px = keep[0][0]                                # the parents' pixels, as pack_tiles laid them out: pack_images' layout
-        d_desc = torch.from_numpy(pack_images(images, fmt)[1].view(np.uint8)).to(d_px.device)
-    dev, cap = d_dets.device, d_dets.shape[1]
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, whole, out_cap=cap)
     if chips_cap is None:
-        stream.synchronize()
-        room = int(np.clip(d_counts.cpu().numpy(), 0, cap).sum())
+        b.stream.synchronize()
+        room = int(np.clip(b.d_counts.cpu().numpy(), 0, b.cap).sum())
     else:
         room = int(chips_cap)
-    d_chips = torch.empty((max(room, 1), out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    d_info = torch.empty((max(room, 1), CHIP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    d_chips = torch.empty((max(room, 1), out_h, out_w, 3), dtype=torch.uint8, device=b.device)
+    d_info = torch.empty((max(room, 1), CHIP_DTYPE.itemsize), dtype=torch.uint8, device=b.device)
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     crop = crop_records_yuv_device if is_yuv(fmt) else crop_records_device
-    crop(d_px.data_ptr(), d_px.numel(), fmt, d_desc.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, cap, out_h, out_w,
+    crop(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap, out_h, out_w,
          d_chips.data_ptr(), room, d_first.data_ptr(), d_info.data_ptr(), order=order_code, margin_permille=permille, square=square,
-         stream=stream.cuda_stream)
-    stream.synchronize()
-    del keep
-    if d_totals is not None:
-        _check_totals("detect_chips", d_totals, cap)
+         stream=b.stream.cuda_stream)
+    b.stream.synchronize()
+    b.check_totals("detect_chips")
     first = d_first.cpu().numpy()
     if int(first[n]) > room:
         raise ImagesError(f"detect_chips: {int(first[n])} boxes in the batch, chips_cap holds {room}")
-    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
     chips = d_chips.cpu().numpy()
     info = d_info.cpu().numpy().view(CHIP_DTYPE).reshape(-1)
-    boxes, per_chips, per_info = [], [], []
-    for i in range(n):
-        a, b = int(first[i]), int(first[i + 1])
-        d = dets[i, :b - a]
-        boxes.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
-        per_chips.append(chips[a:b])
-        per_info.append(info[a:b])
-    return boxes, per_chips, per_info
-
-
-def _mode_code(mode):
-    if isinstance(mode, str) and mode.lower() in REDACT_MODES:
-        return REDACT_MODES[mode.lower()]
-    if mode in (YF_REDACT_MOSAIC, YF_REDACT_FILL) and not isinstance(mode, (str, bool)):
-        return int(mode)
-    raise ValueError(f"mode {mode!r}: 'mosaic' or 'fill'")
+    return b.boxes(np.diff(first)), [chips[a:z] for a, z in zip(first, first[1:])], [info[a:z] for a, z in zip(first, first[1:])]
 
 
 def _colour_code(colour):
@@ -839,15 +842,17 @@ def redact_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_count
     int32[n] (1: the picture's descriptor is invalid, the picture untouched) are written.  For the mosaic the pictures of different frames
     must not share bytes.  The definition: csrc/yf_images_redact.h, ptq.redact_u8."""
     _call("redact_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "redact_records_device"), d_images, d_dets, d_counts, n, cap,
-          _mode_code(mode), block, _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status, stream)
+          _code(REDACT_MODES, mode, MODE_WHAT), block, _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status,
+          stream)
 
 
 def redact_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_first, d_status, mode="mosaic", block=8,
                               colour=0, margin_permille=0, square=False, stream=None):
     """`redact_records_device` for NV12 / NV21 surfaces, redacted where they lie (yf_images_redact_records_yuv_device): d_images
     YUV_IMAGE_DTYPE[n]; colour 0x00YYUUVV or (Y, U, V).  ptq.redact_yuv420sp."""
-    _call("redact_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, _mode_code(mode), block,
-          _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status, stream)
+    _call("redact_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap,
+          _code(REDACT_MODES, mode, MODE_WHAT), block, _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_first, d_status,
+          stream)
 
 
 def _strided(buf, offset, rows, row_bytes, pitch):
@@ -865,53 +870,36 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     Returns (pictures, boxes): the redacted pictures in the caller's shapes, new arrays (NV12 / NV21: (y, uv) pairs) -- the caller's
     arrays are not changed --, and per image the int32 [k, 4] array `detect` returns.  The definition is the library's own:
     csrc/yf_images_redact.h, restated as `ptq.redact_u8` and `ptq.redact_yuv420sp`."""
-    mode_code = _mode_code(mode)
+    mode_code = _code(REDACT_MODES, mode, MODE_WHAT)
     block = 0 if mode_code == YF_REDACT_FILL else int(block)
     if mode_code == YF_REDACT_MOSAIC and block not in (4, 8, 16, 32, 64):
         raise ValueError(f"block {block!r}: 4, 8, 16, 32 or 64")
     colour_code = _colour_code(colour)
-    permille = int(round(float(margin) * 1000))
-    if not 0 <= permille <= 1000:
-        raise ValueError(f"margin {margin!r}: 0 to 1")
+    permille = _permille(margin)
     n = len(images)
     if n == 0:
         return [], []
     import torch
     yuv = is_yuv(fmt)
-    if tile is None:
-        d_dets, d_counts, _, stream, keep = _records_on_device(network, images, fmt, cap, device, iou_threshold, size, dtype)
-        d_px, d_desc = keep[0], keep[2] if yuv else keep[1]
-        d_totals = None
-    else:
+    if tile is not None:
         _packed_code(fmt, "detect_redacted(tile=...)")
-        d_dets, d_counts, d_totals, _, stream, keep = _tiled_records_on_device(network, images, tile, stride, True, fmt,
-                                                                               NMS_WIDE_MAX_CAP if cap is None else cap, device,
-                                                                               iou_threshold, size, dtype)
-        d_px = keep[0][0]                                # the parents' pixels, as pack_tiles laid them out: pack_images' layout
-        d_desc = torch.from_numpy(pack_images(images, fmt)[1].view(np.uint8)).to(d_px.device)
-    dev, cap = d_dets.device, d_dets.shape[1]
-    d_first = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
+    d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the redaction's own: the staging's status does not raise here
     redact = redact_records_yuv_device if yuv else redact_records_device
-    redact(d_px.data_ptr(), d_px.numel(), fmt, d_desc.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, cap, d_first.data_ptr(),
-           d_status.data_ptr(), mode=mode_code, block=block, colour=colour_code, margin_permille=permille, square=square,
-           stream=stream.cuda_stream)
-    stream.synchronize()
-    if d_totals is not None:
-        _check_totals("detect_redacted", d_totals, cap)
+    redact(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap,
+           d_first.data_ptr(), d_status.data_ptr(), mode=mode_code, block=block, colour=colour_code, margin_permille=permille, square=square,
+           stream=b.stream.cuda_stream)
+    b.stream.synchronize()
+    b.check_totals("detect_redacted")
     bad = np.nonzero(d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"detect_redacted: the descriptor of image {int(bad[0])} is invalid")
-    first = d_first.cpu().numpy()
-    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
-    buf = d_px.cpu().numpy()
-    desc = d_desc.cpu().numpy().view(YUV_IMAGE_DTYPE if yuv else IMAGE_DTYPE).reshape(-1)
-    del keep
-    pictures, boxes = [], []
-    for i in range(n):
-        d = dets[i, :int(first[i + 1]) - int(first[i])]
-        boxes.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
-        e = desc[i]
+    boxes = b.boxes(np.diff(d_first.cpu().numpy()))
+    buf = b.d_px.cpu().numpy()
+    desc = b.d_pictures.cpu().numpy().view(YUV_IMAGE_DTYPE if yuv else IMAGE_DTYPE).reshape(-1)
+    pictures = []
+    for e in desc:
         h, w = int(e["height"]), int(e["width"])
         if yuv:
             pictures.append((_strided(buf, int(e["offset_y"]), h, w, int(e["stride_y"])).copy(),
@@ -920,14 +908,6 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
             C = CHANNELS[format_code(fmt)]
             pictures.append(_strided(buf, int(e["offset"]), h, w * C, int(e["row_stride"])).copy().reshape(h, w, C))
     return pictures, boxes
-
-
-def _layout_code(layout):
-    if isinstance(layout, str) and layout.lower() in TRACK_LAYOUTS:
-        return TRACK_LAYOUTS[layout.lower()]
-    if layout in (YF_TRACK_TIME_MAJOR, YF_TRACK_STREAM_MAJOR) and not isinstance(layout, (str, bool)):
-        return int(layout)
-    raise ValueError(f"layout {layout!r}: 'time' (frame t * streams + s) or 'stream' (frame s * steps + t)")
 
 
 def track_state_bytes(streams):
@@ -944,8 +924,8 @@ def track_device(d_dets, d_counts, streams, steps, layout, cap, params, d_state,
     ptq.track_step.  Returns n."""
     lib = load()
     p = YfTrackParams(float(params[0]), int(params[1]), int(params[2]))
-    rc = lib.yf_images_track_device(d_dets, d_counts, streams, steps, _layout_code(layout), cap, ctypes.byref(p), d_state, d_out, d_info,
-                                    d_out_counts, out_cap, d_status, stream)
+    rc = lib.yf_images_track_device(d_dets, d_counts, streams, steps, _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT), cap, ctypes.byref(p), d_state,
+                                    d_out, d_info, d_out_counts, out_cap, d_status, stream)
     if rc != streams * steps or rc < 0:
         raise ImagesError(f"yf_images_track_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
     return rc
@@ -1005,14 +985,13 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
         raise ValueError(f"{len(images)} images: {tracker.streams} streams x {steps} steps")
     if iou_threshold is None:
         raise ValueError("iou_threshold None: the tracker takes suppressed records")
-    _layout_code(layout)
+    _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
     n = len(images)
     if n == 0:
         return []
-    d_dets, d_counts, _, stream, keep = _records_on_device(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype)
-    d_out, d_info, d_out_counts, d_status = tracker.update(d_dets, d_counts, steps, layout, stream=stream.cuda_stream)
-    stream.synchronize()
-    del keep
+    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype)
+    d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
+    b.stream.synchronize()
     out = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, -1)
     info = d_info.cpu().numpy().view(TRACK_INFO_DTYPE).reshape(n, -1)
     counts = d_out_counts.cpu().numpy()
@@ -1032,18 +1011,10 @@ def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_
     n = len(images)
     if n == 0:
         return []
-    d_out, d_counts, d_totals, d_status, stream, keep = _tiled_records_on_device(network, images, tile, stride, whole, fmt, out_cap, device,
-                                                                                 iou_threshold, size, dtype)
-    stream.synchronize()
-    del keep
-    _check_totals("detect_tiled", d_totals, out_cap)
-    dets = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, out_cap)
-    counts = d_counts.cpu().numpy()
-    out = []
-    for i in range(n):
-        d = dets[i, :min(int(counts[i]), out_cap)]
-        out.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
-    return out
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, out_cap)
+    b.stream.synchronize()
+    b.check_totals("detect_tiled")
+    return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))
 
 
 def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8"):
@@ -1059,54 +1030,9 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     fmt="nv12" / "nv21": `images` are surfaces as `pack_yuv_images` takes them; the sequence is the YUV prepare, the network's device run
     and the ragged decode of that size and dtype, on one stream, and the boxes are in the Y plane's pixels -- those of
     cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12) under fmt="bgr"."""
-    if size not in (56, 160):
-        raise ValueError(f"size {size!r}: 56 or 160")
-    if dtype not in ("int8", "fp16"):
-        raise ValueError(f"dtype {dtype!r}: 'int8' or 'fp16'")
-    if dtype == "fp16" and size != 56:
-        raise ValueError("dtype 'fp16': the fp16 network has 56x56 frames only")
-    grid = size // 8
-    if cap is None:
-        cap = 3 * grid * grid
-    import torch
-    n = len(images)
-    if n == 0:
+    _check_frames(size, dtype)                          # before the empty batch is returned, and before torch, the network or the library
+    if len(images) == 0:
         return []
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    yuv_desc = None
-    if is_yuv(fmt):
-        buf, yuv_desc = pack_yuv_images(images, fmt)
-        desc = yuv_sizes(yuv_desc)
-    else:
-        buf, desc = pack_images(images, fmt)
-    d_px = torch.from_numpy(buf).to(dev)
-    d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
-    d_yuv_desc = None if yuv_desc is None else torch.from_numpy(yuv_desc.view(np.uint8)).to(dev)
-    f16 = dtype == "fp16"
-    d_frames = torch.empty((n, size, size, 3), dtype=torch.float16 if f16 else torch.int8, device=dev)
-    d_heads = torch.empty((n, grid, grid, 18), dtype=torch.float32 if f16 else torch.int8, device=dev)
-    d_dets = torch.empty((n, cap, binding.DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_counts = torch.empty(n, dtype=torch.int32, device=dev)
-    d_status = torch.empty(n, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    run, nms = (run_decode_ragged_device, nms_device) if size == 56 else (run_decode160_ragged_device, nms_wide_device)
-    if f16:
-        run = run_decode_f16_ragged_device
-    else:
-        set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
-    if d_yuv_desc is not None:
-        _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_yuv_desc.data_ptr(), d_desc.data_ptr(), n, d_frames.data_ptr(),
-                        d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, stream.cuda_stream)
-    else:
-        run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), n, d_frames.data_ptr(), d_heads.data_ptr(),
-            d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=stream.cuda_stream)
-    if iou_threshold is not None:
-        nms(d_dets.data_ptr(), d_counts.data_ptr(), n, cap, iou_threshold, stream=stream.cuda_stream)
-    stream.synchronize()
-    dets = d_dets.cpu().numpy().view(binding.DET_DTYPE).reshape(n, cap)
-    counts = d_counts.cpu().numpy()
-    out = []
-    for i in range(n):
-        d = dets[i, :min(int(counts[i]), cap)]
-        out.append(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], axis=1).astype(np.int32).reshape(-1, 4))
-    return out
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype)
+    b.stream.synchronize()
+    return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))
