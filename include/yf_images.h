@@ -387,6 +387,45 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
                                                 uint32_t colour, int margin_permille, int flags, int32_t* d_first, int32_t* d_status,
                                                 void* stream);
 
+/* ---- drawing: where every script of the reference ends.  The outline of every record is drawn in place into the picture where it lies
+ * -- packed pixels or an NV12 / NV21 surface -- without the records leaving the device: cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255),
+ * 2) of yoloface/tflite/tflite_prediction.py:59-64 (and LCD_DrawRectangle of the firmware) for a whole batch, in one colour or, with keys,
+ * in a colour per record -- the track id of the tracker below keeps a face's colour over the frames.  The definition is stated once in
+ * csrc/yf_images_draw.h, which the kernels and a host build share.  The video loop with drawing: INTEGRATION.md.
+ *   input:  d_dets, d_counts, n, cap, d_images as the redaction above takes them; d_pixels is WRITTEN (never read).
+ *   set:    the record's four int32 edges as they are (no margin, no square, no clamp), xa = min(x1, x2), xb = max(x1, x2), y likewise,
+ *           int64 arithmetic.  half = h in [0, 3].  For a pixel (x, y): ex = max(xa - x, x - xb, 0), ix = min(x - xa, xb - x), ey and iy
+ *           likewise.  Drawn iff ex <= h and ey <= h; and ex == 0 or ey == 0 or ex * ex + ey * ey <= h * h (round outer corners); and
+ *           ex > 0 or ey > 0 or min(ix, iy) <= h (the interior stays); and the pixel lies in the picture.  h = 0: the one-pixel outline of
+ *           LCD_DrawRectangle and cv2.rectangle(..., 1).  h = 1: what OpenCV's drawing.cpp is read to draw for thickness 2 (a band of three
+ *           pixels per edge, a disc of radius 1 at each corner) -- read from memory of the source, NOT pinned against a real cv2.
+ *   colour: d_keys NULL: colour = 0x00RRGGBB (NV12 / NV21: 0x00YYUUVV) for every record, a non-zero top byte is refused; key_stride,
+ *           d_palette, palette_n must be 0, NULL, 0.  d_keys given: the record in slot s of frame f gets
+ *           d_palette[key % palette_n] & 0xFFFFFF, key the uint32 at d_keys + (f * cap + s) * key_stride; key_stride a multiple of 4 in
+ *           [4, 64] (the id fields of a yf_track_info array: the array, stride 16), 1 <= palette_n <= 256, both 4-byte aligned device
+ *           memory.  R, G, B go where the format keeps them; alpha is never written.
+ *   overlap: a pixel drawn by several records of its frame gets the colour of the highest slot that draws it.
+ *   yuv:    the Y byte of every drawn pixel; a chroma pair is written iff at least one of its four luma pixels is drawn, with the chroma
+ *           of the highest slot that draws any of them; (U, V) for NV12, (V, U) for NV21.
+ *   output: nothing but the drawn set is written, row padding and the bytes between pictures included.  d_first int32[n + 1] and d_status
+ *           int32[n] as the redaction writes them (status 1: the picture's descriptor is invalid, the picture is not touched).
+ *   alias:  with keys the pictures of different frames must not share bytes (otherwise unspecified contents, never an access outside a
+ *           picture's extent); without keys pictures may be shared.
+ *   safety: counts, records, d_first (read back), keys and palette are device memory that may hold anything; every index derived from
+ *           them is range-checked before use, and no store leaves a picture's or plane's extent as its descriptor states it.  What a
+ *           record costs follows the pixels it writes, never its edges.
+ * Two launches (the crop's scan, one workgroup per record that exists); asynchronous on `stream`, no allocation, no host synchronisation,
+ * capturable; every argument is checked before the first launch, and each entry refuses the other family's formats with a text.  Pointer
+ * rules as for the redaction.  Returns n; n = 0 launches nothing and returns 0, after the checks. */
+YF_API long yf_images_draw_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                          const void* d_counts, long n, int cap, int half, uint32_t colour, const void* d_keys,
+                                          int key_stride, const uint32_t* d_palette, int palette_n, int32_t* d_first, int32_t* d_status,
+                                          void* stream);
+YF_API long yf_images_draw_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int half, uint32_t colour,
+                                              const void* d_keys, int key_stride, const uint32_t* d_palette, int palette_n,
+                                              int32_t* d_first, int32_t* d_status, void* stream);
+
 /* ---- tracking: the step between "the boxes of this frame" and "what to do with this frame" of a video.  Each frame's records (after a
  * suppression) are associated with per-stream track state: every face gets an identity that lasts over the frames, and a face the
  * detector misses for a few frames is held over with its last box -- so a redaction (above) does not show it on exactly those frames,

@@ -16,7 +16,8 @@
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
 // tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h; the face chips (every record's region of its picture,
 // resized) in yf_images_crop.h and yf_images_crop.hip.h; the redaction (every record's region pixelated or filled in place) in
-// yf_images_redact.h and yf_images_redact.hip.h; the tracker (each frame's records associated with per-stream track state) in
+// yf_images_redact.h and yf_images_redact.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
+// yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
 // yf_images_track.h and yf_images_track.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
@@ -39,6 +40,7 @@
 #include "yf_images_tiles.hip.h"
 #include "yf_images_crop.hip.h"
 #include "yf_images_redact.hip.h"
+#include "yf_images_draw.hip.h"
 #include "yf_images_track.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
@@ -854,6 +856,35 @@ long redact_records(void* d_pixels, size_t pixels_bytes, int format, const void*
   return launched("redact_records kernel launches", n);
 }
 
+// ---- drawing (yf_images_draw.h) ----  the kernels by format (the four packed formats in the order of their codes, then NV12, NV21)
+using DrawKernel = void (*)(yfdraw::Args);
+constexpr DrawKernel kDraw[6] = {yfdraw::outline_kernel<3>, yfdraw::outline_kernel<3>, yfdraw::outline_kernel<4>, yfdraw::outline_kernel<4>,
+                                 yfdraw::outline_yuv_kernel<false>, yfdraw::outline_yuv_kernel<true>};
+
+// both entries behind their format check: every other argument, then the crop's scan and the records
+long draw_records(void* d_pixels, size_t pixels_bytes, int format, const void* d_images, const void* d_dets, const void* d_counts, long n,
+                  int cap, int half, uint32_t colour, const void* d_keys, int key_stride, const uint32_t* d_palette, int palette_n,
+                  int32_t* d_first, int32_t* d_status, void* stream) {
+  const char* err = yfi_draw_check(n, cap, half, colour, d_keys, key_stride, d_palette, palette_n);
+  if (err) return fail("%s", err);
+  if (!d_dets || !d_counts || !d_first || !d_status) return fail("d_dets, d_counts, d_first or d_status is NULL");
+  if ((((uintptr_t)d_dets | (uintptr_t)d_counts | (uintptr_t)d_first | (uintptr_t)d_status) & 3) != 0)
+    return fail("d_dets, d_counts, d_first and d_status must be 4-byte aligned");
+  if (!d_pixels) return fail("d_pixels is NULL");
+  if (!d_images || ((uintptr_t)d_images & 7) != 0) return fail("d_images is NULL or not 8-byte aligned");
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yfcrop::first_kernel, dim3(1), dim3(yfcrop::kThreads), 0, s, (const int*)d_counts, n, cap, d_first);
+  yfdraw::Args a{};
+  a.r.c.bytes = (uint64_t)pixels_bytes; a.r.c.imgs = d_images; a.r.c.dets = (const yf_det*)d_dets; a.r.c.counts = (const int*)d_counts;
+  a.r.c.n = n; a.r.c.cap = cap; a.r.c.first = d_first;
+  a.r.px = (uint8_t*)d_pixels; a.r.format = format; a.r.colour = colour; a.r.status = d_status;
+  a.half = half; a.keys = (const uint8_t*)d_keys; a.key_stride = key_stride; a.palette = d_palette; a.palette_n = palette_n;
+  // no more workgroups than records can exist; 9.6 KB of LDS per workgroup, eight waves per SIMD
+  hipLaunchKernelGGL(kDraw[format], grid_for(n * (long)cap, 8), dim3(yfdraw::kThreads), 0, s, a);
+  return launched("draw_records kernel launches", n);
+}
+
 // ---- tracking (yf_images_track.h) ----  -1 and the text: here 0 is a valid number of frames
 long track(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap, const yf_track_params* params,
            void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
@@ -1186,6 +1217,26 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
   if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
   return redact_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first,
                         d_status, stream);
+}
+
+YF_API long yf_images_draw_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                          const void* d_counts, long n, int cap, int half, uint32_t colour, const void* d_keys, int key_stride,
+                                          const uint32_t* d_palette, int palette_n, int32_t* d_first, int32_t* d_status, void* stream) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_draw_records_yuv_device");
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  return draw_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, half, colour, d_keys, key_stride, d_palette, palette_n,
+                      d_first, d_status, stream);
+}
+
+YF_API long yf_images_draw_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int half, uint32_t colour,
+                                              const void* d_keys, int key_stride, const uint32_t* d_palette, int palette_n, int32_t* d_first,
+                                              int32_t* d_status, void* stream) {
+  if (channels_of(format)) return fail("format YF_PIX_BGR8 / RGB8 / BGRA8 / RGBA8: packed pixels go through yf_images_draw_records_device");
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  return draw_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, half, colour, d_keys, key_stride, d_palette, palette_n,
+                      d_first, d_status, stream);
 }
 
 YF_API size_t yf_images_track_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h and the tracker of yf_images_track.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the drawing of yf_images_draw.h and the tracker of yf_images_track.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -16,6 +16,7 @@
 #include "yf_images_tiles.h"
 #include "yf_images_crop.h"
 #include "yf_images_redact.h"
+#include "yf_images_draw.h"
 #include "yf_images_track.h"
 #include "gen/yf_decode_tables_gen.h"
 
@@ -497,6 +498,112 @@ EXPORT long yfi_redact_records_yuv_host(uint8_t* base, uint64_t bytes, int forma
 /* the argument check alone: the text of the first fault into out (at most out_bytes, 0-terminated), or an empty text; returns 1 for a fault */
 EXPORT int yfi_redact_check_host(long n, int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, char* out, int out_bytes) {
   const char* t = yfi_redact_check(n, cap, mode, block, colour, margin_permille, flags);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+/* ---- yf_images_draw.h ----  yf_images_draw_records_device / _yuv_device as the header states them, in place on the caller's buffer,
+ * literally: frame by frame, record after record in slot order (that IS the overlap rule), every pixel of the record's outer box inside
+ * the picture asked of yfi_draw_covers -- no bands, no ownership.  A surface's drawn pixel writes its Y byte and its chroma pair, so a
+ * pair ends with the chroma of the highest slot that draws one of its pixels.  `keys`, `palette`: host memory here.  Returns n, or -1
+ * for arguments the device entries refuse. */
+static long draw_records(uint8_t* base, uint64_t bytes, int format, const void* images, const yf_det* dets, const int32_t* counts, long n,
+                         int cap, int half, uint32_t colour, const uint8_t* keys, int key_stride, const uint32_t* palette, int palette_n,
+                         int32_t* first, int32_t* status) {
+  if (yfi_draw_check(n, cap, half, colour, keys, key_stride, palette, palette_n) != NULL) return -1;
+  if (!dets || !counts || !first || !status || !base || !images) return -1;
+  if (n == 0) return 0;
+  const int yuv = format == YF_PIX_NV12 || format == YF_PIX_NV21;
+  const int C = yuv ? 1 : yfi_tiles_channels(format);
+  int64_t total = 0;
+  for (long i = 0; i < n; ++i) {
+    first[i] = (int32_t)total;
+    total += yfi_crop_clamp(counts[i], cap);
+  }
+  first[n] = (int32_t)total;
+  for (long i = 0; i < n; ++i) {
+    const int m = yfi_crop_clamp(counts[i], cap);
+    const yf_image* im = yuv ? NULL : (const yf_image*)images + i;
+    const yf_image_yuv* iy = yuv ? (const yf_image_yuv*)images + i : NULL;
+    const int ok = yuv ? yfi_yuv_image_ok(iy->offset_y, iy->offset_uv, iy->height, iy->width, iy->stride_y, iy->stride_uv, bytes)
+                       : yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes);
+    status[i] = ok ? 0 : 1;
+    if (!ok) continue;
+    const int32_t W = yuv ? iy->width : im->width, H = yuv ? iy->height : im->height;
+    uint8_t* px = base + (yuv ? iy->offset_y : im->offset);
+    uint8_t* uv = yuv ? base + iy->offset_uv : NULL;
+    const int64_t rs = yuv ? iy->stride_y : im->row_stride;
+    for (int s = 0; s < m; ++s) {
+      const yf_det* d = &dets[i * cap + s];
+      uint32_t col = colour;
+      if (keys) {
+        uint32_t key;
+        memcpy(&key, keys + (i * (int64_t)cap + s) * (int64_t)key_stride, 4);
+        col = yfi_draw_key_colour(key, palette, palette_n);
+      }
+      uint8_t f[3];
+      yfi_redact_fill_bytes(col, format, f);
+      const yfi_draw_edges e = yfi_draw_clip(d->x1, d->y1, d->x2, d->y2, half, W, H);
+      const yfi_draw_span rows = yfi_draw_span_of(e.ya - half, e.yb + half, H), cols = yfi_draw_span_of(e.xa - half, e.xb + half, W);
+      for (int32_t y = rows.at; y < rows.at + rows.n; ++y)
+        for (int32_t x = cols.at; x < cols.at + cols.n; ++x) {
+          if (!yfi_draw_covers(&e, half, x, y)) continue;
+          if (!yuv) {
+            for (int c = 0; c < 3; ++c) px[(int64_t)y * rs + (int64_t)x * C + c] = f[c];
+          } else {
+            px[(int64_t)y * rs + x] = f[0];
+            uint8_t* pair = uv + (int64_t)(y >> 1) * iy->stride_uv + 2 * (x >> 1);
+            pair[0] = f[1]; pair[1] = f[2];
+          }
+        }
+    }
+  }
+  return n;
+}
+
+EXPORT long yfi_draw_records_host(uint8_t* base, uint64_t bytes, int format, const yf_image* images, const yf_det* dets, const int32_t* counts,
+                                  long n, int cap, int half, uint32_t colour, const void* keys, int key_stride, const uint32_t* palette,
+                                  int palette_n, int32_t* first, int32_t* status) {
+  if (!yfi_tiles_channels(format)) return -1;
+  return draw_records(base, bytes, format, images, dets, counts, n, cap, half, colour, (const uint8_t*)keys, key_stride, palette, palette_n, first,
+                      status);
+}
+
+EXPORT long yfi_draw_records_yuv_host(uint8_t* base, uint64_t bytes, int format, const yf_image_yuv* images, const yf_det* dets,
+                                      const int32_t* counts, long n, int cap, int half, uint32_t colour, const void* keys, int key_stride,
+                                      const uint32_t* palette, int palette_n, int32_t* first, int32_t* status) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return -1;
+  return draw_records(base, bytes, format, images, dets, counts, n, cap, half, colour, (const uint8_t*)keys, key_stride, palette, palette_n, first,
+                      status);
+}
+
+/* THE rule alone: the drawn sets of n records (boxes int32[n][4]: x1, y1, x2, y2) in a picture of W x H, out uint8[n][H][W] of 0 / 1 --
+ * yfi_draw_clip and yfi_draw_covers, asked for every pixel of the picture */
+EXPORT void yfi_draw_masks_host(const int32_t* boxes, long n, int half, int32_t W, int32_t H, uint8_t* out) {
+  for (long k = 0; k < n; ++k) {
+    const yfi_draw_edges e = yfi_draw_clip(boxes[4 * k], boxes[4 * k + 1], boxes[4 * k + 2], boxes[4 * k + 3], half, W, H);
+    for (int32_t y = 0; y < H; ++y)
+      for (int32_t x = 0; x < W; ++x) out[((size_t)k * (size_t)H + (size_t)y) * (size_t)W + (size_t)x] = (uint8_t)yfi_draw_covers(&e, half, x, y);
+  }
+}
+
+/* ... and what the kernels walk instead: per record out[14] = {at, n} of the spans top, bottom, between, across, left, right
+ * (yfi_draw_bands_of), then yfi_draw_visible and a 0 */
+EXPORT void yfi_draw_bands_host(const int32_t* boxes, long n, int half, int32_t W, int32_t H, int32_t* out) {
+  for (long k = 0; k < n; ++k) {
+    const yfi_draw_edges e = yfi_draw_clip(boxes[4 * k], boxes[4 * k + 1], boxes[4 * k + 2], boxes[4 * k + 3], half, W, H);
+    const yfi_draw_bands b = yfi_draw_bands_of(&e, half, W, H);
+    const yfi_draw_span s[6] = {b.top, b.bottom, b.between, b.across, b.left, b.right};
+    for (int q = 0; q < 6; ++q) { out[14 * k + 2 * q] = s[q].at; out[14 * k + 2 * q + 1] = s[q].n; }
+    out[14 * k + 12] = yfi_draw_visible(&e, half, W, H);
+    out[14 * k + 13] = 0;
+  }
+}
+
+/* the argument check alone: the text of the first fault into out (at most out_bytes, 0-terminated), or an empty text; returns 1 for a fault */
+EXPORT int yfi_draw_check_host(long n, int cap, int half, uint32_t colour, const void* keys, int key_stride, const void* palette, int palette_n,
+                               char* out, int out_bytes) {
+  const char* t = yfi_draw_check(n, cap, half, colour, keys, key_stride, palette, palette_n);
   if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
   return t != NULL;
 }

@@ -27,6 +27,11 @@ in its picture on the GPU, packed pixels or an NV12 / NV21 surface, and the reda
 `redact_records_device`, `redact_records_yuv_device`; the definition is the library's own (csrc/yf_images_redact.h, `ptq.redact_u8`,
 `ptq.redact_yuv420sp`).
 
+`detect_drawn(network, images)` is the line every script of the reference ends with, cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2)
+(tflite_prediction.py:59-64), for the whole batch on the GPU: the outline of every kept box drawn in place, in one colour or -- with a
+`Tracker` -- in a colour per track that a face keeps over the frames; `draw_records_device`, `draw_records_yuv_device`; the definition:
+csrc/yf_images_draw.h, `ptq.draw_rectangles_u8`, `ptq.draw_rectangles_yuv420sp`.
+
 `detect_tracked(network, images, tracker, steps)` is the step a video needs between the boxes of a frame and what is done with the frame:
 a `Tracker` keeps per-stream track state on the device and associates each frame's kept boxes with it, so that every face has an identity
 over the frames and a face the detector misses for a few frames is held over with its last box -- `track_device`; its output is records
@@ -179,6 +184,10 @@ def _entries():
         # stream
         "redact_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
         "redact_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
+        # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, half, colour, d_keys, key_stride, d_palette, palette_n, d_first,
+        # d_status, stream
+        "draw_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, vp, ci, vp, ci, vp, vp, vp],
+        "draw_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, vp, ci, vp, ci, vp, vp, vp],
         # d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream
         "track_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
     }
@@ -859,6 +868,24 @@ def _strided(buf, offset, rows, row_bytes, pitch):
     return np.lib.stride_tricks.as_strided(buf[offset:], shape=(rows, row_bytes), strides=(pitch, 1))
 
 
+def _pictures_back(b, fmt):
+    """the pictures of a staged batch as they lie on the device now, in the caller's shapes: new arrays (NV12 / NV21: (y, uv) pairs);
+    after a synchronise"""
+    yuv = is_yuv(fmt)
+    buf = b.d_px.cpu().numpy()
+    desc = b.d_pictures.cpu().numpy().view(YUV_IMAGE_DTYPE if yuv else IMAGE_DTYPE).reshape(-1)
+    pictures = []
+    for e in desc:
+        h, w = int(e["height"]), int(e["width"])
+        if yuv:
+            pictures.append((_strided(buf, int(e["offset_y"]), h, w, int(e["stride_y"])).copy(),
+                             _strided(buf, int(e["offset_uv"]), h // 2, w, int(e["stride_uv"])).copy()))
+        else:
+            C = CHANNELS[format_code(fmt)]
+            pictures.append(_strided(buf, int(e["offset"]), h, w * C, int(e["row_stride"])).copy().reshape(h, w, C))
+    return pictures
+
+
 def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None,
                     iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and every kept box hidden in its picture on the GPU,
@@ -895,19 +922,7 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     bad = np.nonzero(d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"detect_redacted: the descriptor of image {int(bad[0])} is invalid")
-    boxes = b.boxes(np.diff(d_first.cpu().numpy()))
-    buf = b.d_px.cpu().numpy()
-    desc = b.d_pictures.cpu().numpy().view(YUV_IMAGE_DTYPE if yuv else IMAGE_DTYPE).reshape(-1)
-    pictures = []
-    for e in desc:
-        h, w = int(e["height"]), int(e["width"])
-        if yuv:
-            pictures.append((_strided(buf, int(e["offset_y"]), h, w, int(e["stride_y"])).copy(),
-                             _strided(buf, int(e["offset_uv"]), h // 2, w, int(e["stride_uv"])).copy()))
-        else:
-            C = CHANNELS[format_code(fmt)]
-            pictures.append(_strided(buf, int(e["offset"]), h, w * C, int(e["row_stride"])).copy().reshape(h, w, C))
-    return pictures, boxes
+    return _pictures_back(b, fmt), b.boxes(np.diff(d_first.cpu().numpy()))
 
 
 def track_state_bytes(streams):
@@ -972,6 +987,15 @@ class Tracker:
         return d_out, d_info, d_out_counts, d_status
 
 
+def _track_tuples(d_out, d_info, d_out_counts, n):
+    """a tracker's output of n frames -> per frame the list of (id, x1, y1, x2, y2, conf, hits, misses); after a synchronise"""
+    out = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, -1)
+    info = d_info.cpu().numpy().view(TRACK_INFO_DTYPE).reshape(n, -1)
+    counts = d_out_counts.cpu().numpy()
+    return [[(int(i["id"]), int(d["x1"]), int(d["y1"]), int(d["x2"]), int(d["y2"]), float(d["conf"]), int(i["hits"]), int(i["misses"]))
+             for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
+
+
 def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8"):
     """`detect` with the suppression for the next `steps` frames of the `tracker`'s streams, and the kept boxes associated with its track
     state on the same stream: `images` holds tracker.streams * steps pictures, frame t of stream s at index t * streams + s (layout
@@ -992,11 +1016,108 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
     b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype)
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
     b.stream.synchronize()
-    out = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, -1)
-    info = d_info.cpu().numpy().view(TRACK_INFO_DTYPE).reshape(n, -1)
-    counts = d_out_counts.cpu().numpy()
-    return [[(int(i["id"]), int(d["x1"]), int(d["y1"]), int(d["x2"]), int(d["y2"]), float(d["conf"]), int(i["hits"]), int(i["misses"]))
-             for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
+    return _track_tuples(d_out, d_info, d_out_counts, n)
+
+
+# the colours of `detect_drawn`'s tracks, (R, G, B): sixteen that are easy to tell apart; a track has colour id % 16
+TRACK_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+                 (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255), (170, 110, 40), (255, 250, 200), (128, 0, 0), (170, 255, 195))
+DRAW_MAX_HALF, DRAW_MAX_PALETTE = 3, 256
+
+
+def _draw(name, fmt_code, d_pixels, pixels_bytes, d_images, d_dets, d_counts, n, cap, d_first, d_status, half, colour, d_keys, key_stride,
+          d_palette, palette_n, stream):
+    if d_keys is None:
+        colour, key_stride, d_palette, palette_n = _colour_code(colour), 0, None, 0
+    else:
+        colour = 0
+    _call(name, n, d_pixels, pixels_bytes, fmt_code, d_images, d_dets, d_counts, n, cap, int(half), colour, d_keys, key_stride, d_palette,
+          palette_n, d_first, d_status, stream)
+
+
+def draw_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_first, d_status, half=1, colour=0xFF0000, d_keys=None,
+                        key_stride=4, d_palette=None, palette_n=0, stream=None):
+    """The outlines of the records of a batch of packed pictures drawn IN PLACE (yf_images_draw_records_device): d_images IMAGE_DTYPE[n],
+    d_dets yf_det[n][cap], d_counts int32[n]; d_pixels is written.  half 0..3: 0 the one-pixel outline, 1 the script's thickness 2.
+    d_keys None: every record in `colour`, 0x00RRGGBB or (R, G, B).  d_keys given: the record in slot s of frame f in
+    d_palette[key % palette_n], key the uint32 at d_keys + (f * cap + s) * key_stride (the d_info of a tracker: stride 16), d_palette
+    uint32 0x00RRGGBB [palette_n] on the device, and `colour` is not used.  Where records overlap the highest slot shows.  d_first
+    int32[n + 1] and d_status int32[n] (1: the picture's descriptor is invalid, the picture untouched) are written.  With keys the
+    pictures of different frames must not share bytes.  The definition: csrc/yf_images_draw.h, ptq.draw_rectangles_u8."""
+    _draw("draw_records_device", _packed_code(fmt, "draw_records_device"), d_pixels, pixels_bytes, d_images, d_dets, d_counts, n, cap, d_first,
+          d_status, half, colour, d_keys, key_stride, d_palette, palette_n, stream)
+
+
+def draw_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_first, d_status, half=1, colour=0x515AF0,
+                            d_keys=None, key_stride=4, d_palette=None, palette_n=0, stream=None):
+    """`draw_records_device` for NV12 / NV21 surfaces, drawn where they lie (yf_images_draw_records_yuv_device): d_images
+    YUV_IMAGE_DTYPE[n]; colours 0x00YYUUVV or (Y, U, V).  A chroma pair is written when one of its four luma pixels is drawn.
+    ptq.draw_rectangles_yuv420sp."""
+    _draw("draw_records_yuv_device", _yuv_code(fmt), d_pixels, pixels_bytes, d_images, d_dets, d_counts, n, cap, d_first, d_status, half,
+          colour, d_keys, key_stride, d_palette, palette_n, stream)
+
+
+def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=None, iou_threshold=0.4, size=56, dtype="int8", tile=None,
+                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and the outline of every kept box drawn into its picture
+    on the GPU, on the same stream, in the pixels that are already there -- the last line of the reference's scripts,
+    cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2), which the defaults reproduce: `colour` (R, G, B) whatever the byte order of
+    `fmt` (for NV12 / NV21 surfaces (Y, U, V)), red; `half` = 1, the band of three pixels that thickness 2 is read to draw (half 0..3:
+    csrc/yf_images_draw.h; the reading of OpenCV's thickness 2 is not pinned against a real cv2).  fmt, cap, iou_threshold, size, dtype,
+    device as in `detect`.
+    With `tracker` (a `Tracker`; then `images` are its next `steps` frames in `layout`, as `detect_tracked` takes them; steps=None: as
+    many as the images make; iou_threshold must not be None and the tracker's device is used) the tracker is updated with the kept boxes
+    and the REPORTED TRACKS are drawn, held-over ones included, each in palette[id % len(palette)]: a face keeps its colour over the
+    frames.  `palette`: up to 256 (R, G, B) -- (Y, U, V) -- triples; None: `TRACK_PALETTE`.  Where outlines overlap, the later record
+    (the higher track id) shows.
+    Returns (pictures, boxes) as `detect_redacted` does: the pictures in the caller's shapes, new arrays, and `detect`'s boxes; with a
+    tracker (pictures, tracks), `detect_tracked`'s tuples."""
+    half = int(half)
+    if not 0 <= half <= DRAW_MAX_HALF:
+        raise ValueError(f"half {half!r}: 0 to {DRAW_MAX_HALF}")
+    colour_code = _colour_code(colour)
+    n = len(images)
+    if tracker is not None:
+        steps = n // tracker.streams if steps is None else int(steps)
+        if steps < 0 or n != tracker.streams * steps:
+            raise ValueError(f"{n} images: {tracker.streams} streams x {steps} steps")
+        if iou_threshold is None:
+            raise ValueError("iou_threshold None: the tracker takes suppressed records")
+        _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+        table = [_colour_code(c) for c in (TRACK_PALETTE if palette is None else palette)]
+        if not 1 <= len(table) <= DRAW_MAX_PALETTE:
+            raise ValueError(f"palette: 1 to {DRAW_MAX_PALETTE} colours")
+        device = tracker.device.index
+    if n == 0:
+        return [], []
+    import torch
+    yuv = is_yuv(fmt)
+    if tile is not None:
+        _packed_code(fmt, "detect_drawn(tile=...)")
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
+    d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the drawing's own: the staging's status does not raise here
+    draw = draw_records_yuv_device if yuv else draw_records_device
+    s = b.stream.cuda_stream
+    if tracker is None:
+        draw(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap,
+             d_first.data_ptr(), d_status.data_ptr(), half=half, colour=colour_code, stream=s)
+    else:
+        d_out, d_info, d_out_counts, _ = tracker.update(b.d_dets, b.d_counts, steps, layout, cap=b.cap, stream=s)
+        d_palette = torch.tensor(table, dtype=torch.int32).to(b.device)
+        # the keys are the id fields of the info rows, as they lie: TRACK_INFO_DTYPE's first field, one row per output slot
+        draw(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), d_out.data_ptr(), d_out_counts.data_ptr(), n, d_out.shape[1],
+             d_first.data_ptr(), d_status.data_ptr(), half=half, d_keys=d_info.data_ptr(), key_stride=TRACK_INFO_DTYPE.itemsize,
+             d_palette=d_palette.data_ptr(), palette_n=len(table), stream=s)
+    b.stream.synchronize()
+    b.check_totals("detect_drawn")
+    bad = np.nonzero(d_status.cpu().numpy())[0]
+    if bad.size:
+        raise ImagesError(f"detect_drawn: the descriptor of image {int(bad[0])} is invalid")
+    pictures = _pictures_back(b, fmt)
+    if tracker is None:
+        return pictures, b.boxes(np.diff(d_first.cpu().numpy()))
+    return pictures, _track_tuples(d_out, d_info, d_out_counts, n)
 
 
 def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):

@@ -462,6 +462,71 @@ def redact_yuv420sp(y, uv, regions, mode, block, colour, v_first=False):
     return y_out, uv_out
 
 
+# ---- the drawing (csrc/yf_images_draw.h), in plain numpy ----
+def outline_mask(box, half, width, height):
+    """the drawn set of one record in a picture of height x width, bool [height, width]"""
+    x1, y1, x2, y2 = (int(v) for v in box)
+    xa, xb, ya, yb = min(x1, x2), max(x1, x2), min(y1, y2), max(y1, y2)
+    h = int(half)
+    xs, ys = np.arange(width, dtype=np.int64)[None, :], np.arange(height, dtype=np.int64)[:, None]
+    # the distances outside the box, cut at h + 1 (more than h is all the rule asks), and inside it
+    ex = np.minimum(np.maximum(np.maximum(xa - xs, xs - xb), 0), h + 1)
+    ey = np.minimum(np.maximum(np.maximum(ya - ys, ys - yb), 0), h + 1)
+    ix, iy = np.minimum(xs - xa, xb - xs), np.minimum(ys - ya, yb - ys)
+    near = (ex <= h) & (ey <= h)
+    round_corner = (ex == 0) | (ey == 0) | (ex * ex + ey * ey <= h * h)
+    not_interior = (ex > 0) | (ey > 0) | (np.minimum(ix, iy) <= h)
+    return near & round_corner & not_interior
+
+
+def _draw_colours(colours, count):
+    c = np.asarray(colours, np.int64)
+    if c.ndim == 1:
+        c = np.broadcast_to(c, (count, 3))
+    if c.shape != (count, 3) or c.min(initial=0) < 0 or c.max(initial=0) > 255:
+        raise ValueError(f"colours: three bytes, or three bytes per box ({count} boxes)")
+    return c.astype(np.uint8)
+
+
+def _draw_half(half):
+    if isinstance(half, bool) or half not in (0, 1, 2, 3):
+        raise ValueError(f"half {half!r}: 0, 1, 2 or 3")
+    return int(half)
+
+
+def draw_rectangles_u8(picture_hwc, boxes, half, colours):
+    """The copy of a packed picture (uint8 [H, W, 3 or 4]) with the outline of every box (x1, y1, x2, y2) drawn, as
+    csrc/yf_images_draw.h states it, box after box in the order given -- a pixel that several boxes draw ends with the colour of the last,
+    which is the overlap rule.  The edges are used as they are (no clamp; x1 > x2 is the same box as x2 > x1).  `half` = h in 0..3: a
+    pixel at distances (ex, ey) outside the box and (ix, iy) inside it is drawn iff ex <= h and ey <= h, and ex == 0 or ey == 0 or
+    ex * ex + ey * ey <= h * h, and ex > 0 or ey > 0 or min(ix, iy) <= h.  h = 0 is cv2.rectangle(..., 1); h = 1 is what OpenCV's
+    drawing.cpp is read to draw for thickness 2 (three pixels per edge, a disc of radius 1 at each corner) -- read from memory of the
+    source and, like `resize_linear_u8`, not pinned against a real cv2.  `colours`: three bytes for the picture's channels 0, 1, 2 in the
+    picture's own order, or one such triple per box.  A fourth channel is never touched."""
+    out = np.asarray(picture_hwc, np.uint8).copy()
+    h = _draw_half(half)
+    cols = _draw_colours(colours, len(boxes))
+    for box, colour in zip(boxes, cols):
+        out[..., :3][outline_mask(box, h, out.shape[1], out.shape[0])] = colour
+    return out
+
+
+def draw_rectangles_yuv420sp(y, uv, boxes, half, colours, v_first=False):
+    """`draw_rectangles_u8` for an NV12 / NV21 surface (y uint8 [H, W], uv uint8 [H / 2, W]) -> (y, uv) copies.  `colours`: (Y, U, V), or
+    one triple per box.  Box after box: the Y byte of every drawn pixel, and every chroma pair of which at least one of the four luma
+    pixels is drawn gets (U, V), or (V, U) with v_first."""
+    y_out, uv_out = np.asarray(y, np.uint8).copy(), np.asarray(uv, np.uint8).copy()
+    hh, w = y_out.shape
+    pairs = uv_out.reshape(hh // 2, w // 2, 2)
+    h = _draw_half(half)
+    cols = _draw_colours(colours, len(boxes))
+    for box, (yy, u, v) in zip(boxes, cols):
+        mask = outline_mask(box, h, w, hh)
+        y_out[mask] = yy
+        pairs[mask.reshape(hh // 2, 2, w // 2, 2).any(axis=(1, 3))] = (v, u) if v_first else (u, v)
+    return y_out, uv_out
+
+
 # ---- the tracker (csrc/yf_images_track.h), in plain Python ----
 TRACK_SLOTS, TRACK_MAX_DETS = 64, 64
 TRACK_CLIPPED, TRACK_DROPPED = 1, 2
