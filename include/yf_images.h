@@ -387,6 +387,59 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
                                                 uint32_t colour, int margin_permille, int flags, int32_t* d_first, int32_t* d_status,
                                                 void* stream);
 
+/* ---- redaction by blur: the third way to hide a face, the one video anonymisers use by default.  Every record's region is replaced by
+ * a coarse grid of its own means resized back to the region, in place, in the picture where it lies.  The grid is per face -- every face
+ * gets the same number of cells, so a large face is hidden as well as a small one, which a mosaic of a fixed block is not.  The
+ * reference has no such step; the definition is this library's own, stated once in csrc/yf_images_blur.h, which the kernels and a host
+ * build share.  A C host's sequence and the video loop with the tracker in front: INTEGRATION.md.
+ *   input:  d_dets, d_counts, n, cap, d_images, margin_permille, flags as the redaction above takes them (records, regions, pictures
+ *           are exactly its own).  d_pixels is read and WRITTEN.
+ *   grid:   grid = g in [1, YF_BLUR_MAX_GRID].  A region of width x height pixels has gx = max(1, min(g, width / m)) by gy (likewise
+ *           from height) cells, m = YF_BLUR_MIN_CELL for packed pixels and the Y plane, 2 for the chroma plane: no cell is narrower than
+ *           m, so that a small region does not come back as it was (only a 1 x 1 region keeps its bytes).  Cell cx holds the region's
+ *           columns [cx * width / gx, (cx + 1) * width / gx), rows likewise (integer division).
+ *   means:  per cell and colour byte channel v = (sum + cnt / 2) / cnt over the cell's pixels as they were before the call, exact
+ *           integers in 64 bits.  The fourth byte of BGRA / RGBA is neither read nor written.
+ *   result: the region's pixels become cv2.resize(G, (width, height)), INTER_LINEAR, of the [gy, gx, channels] grid of means G, as
+ *           csrc/yf_images_taps.h restates it.  A constant region stays constant.
+ *   yuv:    the Y plane is a one-channel picture over the region; the chroma plane a two-channel picture of pairs over the fill's chroma
+ *           region (cx in [x0 >> 1, (x0 + width - 1) >> 1], cy likewise) with its own gx, gy, means and resample.  First bytes are
+ *           averaged together and second bytes together: U / V order does not matter to the blur.
+ *   overlap: a pixel in several regions of its frame belongs to the lowest slot whose region contains it and gets that record's value;
+ *           a chroma pair to the lowest slot whose chroma region contains it.  Every record's grid is computed from the pixels as they
+ *           were before the call, whoever owns them: the order of a frame's records matters only for who owns an overlap.  A second
+ *           call blurs the blur: unlike the mosaic, the call is NOT idempotent.
+ *   work:   record k = first[f] + s keeps its grid in slot k of d_work; yf_images_blur_workspace(records_cap, grid) = records_cap * grid
+ *           * grid * 4 bytes rounded up to 16 (0 for arguments the call refuses).  Its contents are the library's own.  A record with
+ *           k >= records_cap has no slot and is FILLED with colour (0x00RRGGBB; NV12 / NV21: 0x00YYUUVV) by the fill's rule under the same
+ *           ownership rule: a face never stays visible because a buffer was small.  records_cap = 0 is legal and turns the call into a
+ *           fill; records_cap = n * cap fills nothing.
+ *   output: nothing but the owned pixels of the regions is written, row padding and the bytes between pictures included.  d_first
+ *           int32[n + 1] (written): the exclusive prefix of the m_i; first[n] is the records_cap that would have sufficed.  d_status
+ *           int32[n] (written), two bits: bit 0 the picture's descriptor is invalid, the picture is neither read nor written; bit 1
+ *           (value 2) the frame has a record without a slot (first[f + 1] > first[f] and first[f + 1] > records_cap).
+ *   alias:  the pictures of different frames must not share bytes (otherwise unspecified contents, never an access outside a picture's
+ *           extent).
+ *   safety: counts, records and d_first (read back) are device memory that may hold anything; every index derived from them is
+ *           range-checked before use, and no load or store leaves a picture's or plane's extent as its descriptor states it.
+ * Three launches on one stream (the crop's scan; the means, one workgroup per record with a slot, which reads the pictures only; the
+ * paint, one workgroup per record, which reads the slots only): no kernel reads a byte that another workgroup of its launch writes.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, capturable; every argument is checked before the first launch
+ * (n, cap, grid, colour's top byte, margin_permille, flags, records_cap in [0, n * cap], work_bytes, d_work non-NULL and 16-byte aligned
+ * when the workspace is not 0), and each entry refuses the other family's formats with a text.  Pointer rules as for the redaction.
+ * Returns n; n = 0 launches nothing and returns 0, after the checks. */
+#define YF_BLUR_MAX_GRID 16
+#define YF_BLUR_MIN_CELL 4
+YF_API size_t yf_images_blur_workspace(long records_cap, int grid);
+YF_API long yf_images_blur_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                          const void* d_counts, long n, int cap, int grid, uint32_t colour, int margin_permille, int flags,
+                                          void* d_work, size_t work_bytes, long records_cap, int32_t* d_first, int32_t* d_status,
+                                          void* stream);
+YF_API long yf_images_blur_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int grid, uint32_t colour,
+                                              int margin_permille, int flags, void* d_work, size_t work_bytes, long records_cap,
+                                              int32_t* d_first, int32_t* d_status, void* stream);
+
 /* ---- drawing: where every script of the reference ends.  The outline of every record is drawn in place into the picture where it lies
  * -- packed pixels or an NV12 / NV21 surface -- without the records leaving the device: cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255),
  * 2) of yoloface/tflite/tflite_prediction.py:59-64 (and LCD_DrawRectangle of the firmware) for a whole batch, in one colour or, with keys,

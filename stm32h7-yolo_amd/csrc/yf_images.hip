@@ -16,7 +16,8 @@
 // the scoring of records against ground truth (match, average precision) in yf_images_eval.hip.h; the merge of the records of an image's
 // tiles (tile grid, prefix, copy) in yf_images_tiles.h and yf_images_tiles.hip.h; the face chips (every record's region of its picture,
 // resized) in yf_images_crop.h and yf_images_crop.hip.h; the redaction (every record's region pixelated or filled in place) in
-// yf_images_redact.h and yf_images_redact.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
+// yf_images_redact.h and yf_images_redact.hip.h; the blur (every record's region replaced by a grid of its means resized back) in
+// yf_images_blur.h and yf_images_blur.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
 // yf_images_track.h and yf_images_track.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
@@ -40,6 +41,7 @@
 #include "yf_images_tiles.hip.h"
 #include "yf_images_crop.hip.h"
 #include "yf_images_redact.hip.h"
+#include "yf_images_blur.hip.h"
 #include "yf_images_draw.hip.h"
 #include "yf_images_track.hip.h"
 
@@ -856,6 +858,38 @@ long redact_records(void* d_pixels, size_t pixels_bytes, int format, const void*
   return launched("redact_records kernel launches", n);
 }
 
+// ---- blur (yf_images_blur.h) ----  the kernels by format (the four packed formats in the order of their codes, then NV12, NV21)
+using BlurKernel = void (*)(yfblur::Args);
+constexpr BlurKernel kBlurMeans[6] = {yfblur::means_kernel<3>, yfblur::means_kernel<3>, yfblur::means_kernel<4>, yfblur::means_kernel<4>,
+                                      yfblur::means_kernel<0>, yfblur::means_kernel<0>};
+constexpr BlurKernel kBlurPaint[6] = {yfblur::paint_kernel<3>, yfblur::paint_kernel<3>, yfblur::paint_kernel<4>, yfblur::paint_kernel<4>,
+                                      yfblur::paint_kernel<0>, yfblur::paint_kernel<0>};
+
+// both entries behind their format check: every other argument, then the crop's scan, the means and the paint
+long blur_records(void* d_pixels, size_t pixels_bytes, int format, const void* d_images, const void* d_dets, const void* d_counts, long n,
+                  int cap, int grid, uint32_t colour, int margin_permille, int flags, void* d_work, size_t work_bytes, long records_cap,
+                  int32_t* d_first, int32_t* d_status, void* stream) {
+  const char* err = yfi_blur_check(n, cap, grid, colour, margin_permille, flags, d_work, work_bytes, records_cap);
+  if (err) return fail("%s", err);
+  if (!d_dets || !d_counts || !d_first || !d_status) return fail("d_dets, d_counts, d_first or d_status is NULL");
+  if ((((uintptr_t)d_dets | (uintptr_t)d_counts | (uintptr_t)d_first | (uintptr_t)d_status) & 3) != 0)
+    return fail("d_dets, d_counts, d_first and d_status must be 4-byte aligned");
+  if (!d_pixels) return fail("d_pixels is NULL");
+  if (!d_images || ((uintptr_t)d_images & 7) != 0) return fail("d_images is NULL or not 8-byte aligned");
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yfcrop::first_kernel, dim3(1), dim3(yfcrop::kThreads), 0, s, (const int*)d_counts, n, cap, d_first);
+  yfblur::Args a{};
+  a.c.bytes = (uint64_t)pixels_bytes; a.c.imgs = d_images; a.c.dets = (const yf_det*)d_dets; a.c.counts = (const int*)d_counts;
+  a.c.n = n; a.c.cap = cap; a.c.margin = margin_permille; a.c.flags = flags; a.c.first = d_first;
+  a.px = (uint8_t*)d_pixels; a.format = format; a.grid = grid; a.colour = colour; a.work = (uint32_t*)d_work; a.records_cap = records_cap;
+  a.status = d_status;
+  // the means: no more workgroups than slots, and one at least, for d_status (6 KB of LDS each); the paint: than records (14.7 KB)
+  hipLaunchKernelGGL(kBlurMeans[format], grid_for(records_cap > 0 ? records_cap : 1, 8), dim3(yfblur::kThreads), 0, s, a);
+  hipLaunchKernelGGL(kBlurPaint[format], grid_for(n * (long)cap, 8), dim3(yfblur::kThreads), 0, s, a);
+  return launched("blur_records kernel launches", n);
+}
+
 // ---- drawing (yf_images_draw.h) ----  the kernels by format (the four packed formats in the order of their codes, then NV12, NV21)
 using DrawKernel = void (*)(yfdraw::Args);
 constexpr DrawKernel kDraw[6] = {yfdraw::outline_kernel<3>, yfdraw::outline_kernel<3>, yfdraw::outline_kernel<4>, yfdraw::outline_kernel<4>,
@@ -1217,6 +1251,29 @@ YF_API long yf_images_redact_records_yuv_device(void* d_pixels, size_t pixels_by
   if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
   return redact_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, mode, block, colour, margin_permille, flags, d_first,
                         d_status, stream);
+}
+
+YF_API size_t yf_images_blur_workspace(long records_cap, int grid) { return yfi_blur_workspace(records_cap, grid); }
+
+YF_API long yf_images_blur_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,
+                                          const void* d_counts, long n, int cap, int grid, uint32_t colour, int margin_permille, int flags,
+                                          void* d_work, size_t work_bytes, long records_cap, int32_t* d_first, int32_t* d_status,
+                                          void* stream) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_blur_records_yuv_device");
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  return blur_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, grid, colour, margin_permille, flags, d_work,
+                      work_bytes, records_cap, d_first, d_status, stream);
+}
+
+YF_API long yf_images_blur_records_yuv_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int grid, uint32_t colour,
+                                              int margin_permille, int flags, void* d_work, size_t work_bytes, long records_cap,
+                                              int32_t* d_first, int32_t* d_status, void* stream) {
+  if (channels_of(format)) return fail("format YF_PIX_BGR8 / RGB8 / BGRA8 / RGBA8: packed pixels go through yf_images_blur_records_device");
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  return blur_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, grid, colour, margin_permille, flags, d_work,
+                      work_bytes, records_cap, d_first, d_status, stream);
 }
 
 YF_API long yf_images_draw_records_device(void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, const void* d_dets,

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the drawing of yf_images_draw.h and the tracker of yf_images_track.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h and the tracker of yf_images_track.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -16,6 +16,7 @@
 #include "yf_images_tiles.h"
 #include "yf_images_crop.h"
 #include "yf_images_redact.h"
+#include "yf_images_blur.h"
 #include "yf_images_draw.h"
 #include "yf_images_track.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -498,6 +499,118 @@ EXPORT long yfi_redact_records_yuv_host(uint8_t* base, uint64_t bytes, int forma
 /* the argument check alone: the text of the first fault into out (at most out_bytes, 0-terminated), or an empty text; returns 1 for a fault */
 EXPORT int yfi_redact_check_host(long n, int cap, int mode, int block, uint32_t colour, int margin_permille, int flags, char* out, int out_bytes) {
   const char* t = yfi_redact_check(n, cap, mode, block, colour, margin_permille, flags);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+/* ---- yf_images_blur.h ----  yf_images_blur_records_device / _yuv_device as the header states them, in place on the caller's buffer,
+ * literally: frame by frame, first the grid of every record with a slot from the picture as it came in (into its slot of `work`), then
+ * the records painted from the LAST slot to the first, so that a pixel ends with the value of the lowest slot whose region holds it --
+ * that IS the ownership rule; no list of owners.  A record without a slot is painted with the fill's bytes in the same order.  Returns
+ * n, or -1 for arguments the device entries refuse (or no memory for a row of taps). */
+static void blur_means(const uint8_t* p, int64_t stride, const yf_chip* r, int C, int NC, int gx, int gy, uint8_t* cells, int at) {
+  for (int cy = 0; cy < gy; ++cy)
+    for (int cx = 0; cx < gx; ++cx) {
+      const int32_t xa = yfi_blur_cell_at(cx, r->width, gx), xb = yfi_blur_cell_at(cx + 1, r->width, gx);
+      const int32_t ya = yfi_blur_cell_at(cy, r->height, gy), yb = yfi_blur_cell_at(cy + 1, r->height, gy);
+      for (int c = 0; c < NC; ++c) {
+        uint64_t sum = 0;
+        for (int32_t y = ya; y < yb; ++y)
+          for (int32_t x = xa; x < xb; ++x) sum += p[(int64_t)(r->y0 + y) * stride + (int64_t)(r->x0 + x) * C + c];
+        cells[(cy * gx + cx) * 4 + at + c] = (uint8_t)yfi_blur_mean(sum, (uint64_t)(xb - xa) * (uint64_t)(yb - ya));
+      }
+    }
+}
+
+/* cells == NULL: the fill with f[0 .. NC - 1].  The horizontal taps are worked out once per region (xt: room for r->width taps) */
+static void blur_paint(uint8_t* p, int64_t stride, const yf_chip* r, int C, int NC, int gx, int gy, const uint32_t* cells, int at,
+                       const uint8_t* f, yfi_tap* xt) {
+  for (int32_t x = 0; x < r->width; ++x) xt[x] = yfi_axis_tap(x, r->width, gx);
+  for (int32_t y = 0; y < r->height; ++y) {
+    const yfi_tap ty = yfi_axis_tap(y, r->height, gy);
+    for (int32_t x = 0; x < r->width; ++x) {
+      uint8_t* q = p + (int64_t)(r->y0 + y) * stride + (int64_t)(r->x0 + x) * C;
+      for (int c = 0; c < NC; ++c) q[c] = cells ? yfi_blur_sample(cells, gx, at + c, xt[x], ty) : f[c];
+    }
+  }
+}
+
+static long blur_records(uint8_t* base, uint64_t bytes, int format, const void* images, const yf_det* dets, const int32_t* counts, long n,
+                         int cap, int grid, uint32_t colour, int margin_permille, int flags, void* work, size_t work_bytes, long records_cap,
+                         int32_t* first, int32_t* status) {
+  if (yfi_blur_check(n, cap, grid, colour, margin_permille, flags, work, work_bytes, records_cap) != NULL) return -1;
+  if (!dets || !counts || !first || !status || !base || !images) return -1;
+  if (n == 0) return 0;
+  const int yuv = format == YF_PIX_NV12 || format == YF_PIX_NV21;
+  const int C = yuv ? 1 : yfi_tiles_channels(format);
+  uint8_t f[3];
+  yfi_redact_fill_bytes(colour, format, f);
+  int64_t total = 0;
+  for (long i = 0; i < n; ++i) {
+    first[i] = (int32_t)total;
+    total += yfi_crop_clamp(counts[i], cap);
+  }
+  first[n] = (int32_t)total;
+  for (long i = 0; i < n; ++i) {
+    const int m = yfi_crop_clamp(counts[i], cap);
+    const yf_image* im = yuv ? NULL : (const yf_image*)images + i;
+    const yf_image_yuv* iy = yuv ? (const yf_image_yuv*)images + i : NULL;
+    const int ok = yuv ? yfi_yuv_image_ok(iy->offset_y, iy->offset_uv, iy->height, iy->width, iy->stride_y, iy->stride_uv, bytes)
+                       : yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes);
+    status[i] = (ok ? 0 : YFI_BLUR_INVALID) | (first[i + 1] > first[i] && (long)first[i + 1] > records_cap ? YFI_BLUR_FILLED : 0);
+    if (!ok) continue;
+    const int32_t W = yuv ? iy->width : im->width, H = yuv ? iy->height : im->height;
+    uint8_t* px = base + (yuv ? iy->offset_y : im->offset);
+    uint8_t* uv = yuv ? base + iy->offset_uv : NULL;
+    const int64_t rs = yuv ? iy->stride_y : im->row_stride;
+    yfi_tap* xt = m > 0 ? (yfi_tap*)malloc((size_t)W * sizeof(yfi_tap)) : NULL;
+    if (m > 0 && !xt) return -1;
+    for (int pass = 0; pass < 2; ++pass)                      /* every grid from the picture as it came in, then the paint, last slot first */
+      for (int s = pass ? m - 1 : 0; pass ? s >= 0 : s < m; s += pass ? -1 : 1) {
+        const yf_det* d = &dets[i * cap + s];
+        const long k = (long)first[i] + s;
+        yf_chip r;
+        if (yfi_crop_region(d->x1, d->y1, d->x2, d->y2, W, H, margin_permille, flags, &r) != 0) continue;
+        const yf_chip c = yfi_blur_chroma(&r);
+        const int gx = yfi_blur_cells(r.width, grid, YF_BLUR_MIN_CELL), gy = yfi_blur_cells(r.height, grid, YF_BLUR_MIN_CELL);
+        const int hx = yfi_blur_cells(c.width, grid, YFI_BLUR_MIN_CELL_CHROMA), hy = yfi_blur_cells(c.height, grid, YFI_BLUR_MIN_CELL_CHROMA);
+        uint8_t* slot = k < records_cap ? (uint8_t*)work + (size_t)k * (size_t)(grid * grid) * 4u : NULL;
+        if (pass == 0 && slot) {
+          memset(slot, 0, (size_t)(grid * grid) * 4u);
+          blur_means(px, rs, &r, C, yuv ? 1 : 3, gx, gy, slot, 0);
+          if (yuv) blur_means(uv, iy->stride_uv, &c, 2, 2, hx, hy, slot, 1);
+        } else if (pass == 1) {
+          blur_paint(px, rs, &r, C, yuv ? 1 : 3, gx, gy, (const uint32_t*)slot, 0, f, xt);
+          if (yuv) blur_paint(uv, iy->stride_uv, &c, 2, 2, hx, hy, (const uint32_t*)slot, 1, f + 1, xt);
+        }
+      }
+    free(xt);
+  }
+  return n;
+}
+
+EXPORT long yfi_blur_records_host(uint8_t* base, uint64_t bytes, int format, const yf_image* images, const yf_det* dets, const int32_t* counts,
+                                  long n, int cap, int grid, uint32_t colour, int margin_permille, int flags, void* work, size_t work_bytes,
+                                  long records_cap, int32_t* first, int32_t* status) {
+  if (!yfi_tiles_channels(format)) return -1;
+  return blur_records(base, bytes, format, images, dets, counts, n, cap, grid, colour, margin_permille, flags, work, work_bytes, records_cap,
+                      first, status);
+}
+
+EXPORT long yfi_blur_records_yuv_host(uint8_t* base, uint64_t bytes, int format, const yf_image_yuv* images, const yf_det* dets,
+                                      const int32_t* counts, long n, int cap, int grid, uint32_t colour, int margin_permille, int flags,
+                                      void* work, size_t work_bytes, long records_cap, int32_t* first, int32_t* status) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return -1;
+  return blur_records(base, bytes, format, images, dets, counts, n, cap, grid, colour, margin_permille, flags, work, work_bytes, records_cap,
+                      first, status);
+}
+
+EXPORT size_t yfi_blur_workspace_host(long records_cap, int grid) { return yfi_blur_workspace(records_cap, grid); }
+
+/* the argument check alone, as yfi_redact_check_host */
+EXPORT int yfi_blur_check_host(long n, int cap, int grid, uint32_t colour, int margin_permille, int flags, const void* work, size_t work_bytes,
+                               long records_cap, char* out, int out_bytes) {
+  const char* t = yfi_blur_check(n, cap, grid, colour, margin_permille, flags, work, work_bytes, records_cap);
   if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
   return t != NULL;
 }

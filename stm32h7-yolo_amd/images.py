@@ -27,6 +27,11 @@ in its picture on the GPU, packed pixels or an NV12 / NV21 surface, and the reda
 `redact_records_device`, `redact_records_yuv_device`; the definition is the library's own (csrc/yf_images_redact.h, `ptq.redact_u8`,
 `ptq.redact_yuv420sp`).
 
+`detect_blurred(network, images)` hides the boxes the soft way, the one video anonymisers use by default: every kept box becomes a coarse
+grid of its own means resized back to the box, so that every face gets the same number of cells whatever its size --
+`blur_records_device`, `blur_records_yuv_device`, `blur_workspace`; the definition is the library's own (csrc/yf_images_blur.h,
+`ptq.blur_u8`, `ptq.blur_yuv420sp`).
+
 `detect_drawn(network, images)` is the line every script of the reference ends with, cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2)
 (tflite_prediction.py:59-64), for the whole batch on the GPU: the outline of every kept box drawn in place, in one colour or -- with a
 `Tracker` -- in a colour per track that a face keeps over the frames; `draw_records_device`, `draw_records_yuv_device`; the definition:
@@ -97,6 +102,7 @@ YF_CROP_SQUARE = 1
 ORDERS, ORDER_WHAT = {"rgb": YF_PIX_RGB8, "bgr": YF_PIX_BGR8}, "order {!r}: 'rgb' or 'bgr'"
 YF_REDACT_MOSAIC, YF_REDACT_FILL = 0, 1
 REDACT_MODES, MODE_WHAT = {"mosaic": YF_REDACT_MOSAIC, "fill": YF_REDACT_FILL}, "mode {!r}: 'mosaic' or 'fill'"
+BLUR_MAX_GRID, BLUR_MIN_CELL = 16, 4   # YF_BLUR_MAX_GRID, YF_BLUR_MIN_CELL
 
 
 # the tracker (yf_track_params, yf_track_info, yf_track_state): 64 slots per stream, at most 64 detections of a frame count
@@ -184,6 +190,10 @@ def _entries():
         # stream
         "redact_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
         "redact_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp],
+        # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, grid, colour, margin_permille, flags, d_work, work_bytes,
+        # records_cap, d_first, d_status, stream
+        "blur_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, ci, ci, vp, cs, cl, vp, vp, vp],
+        "blur_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, ci, ci, vp, cs, cl, vp, vp, vp],
         # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, half, colour, d_keys, key_stride, d_palette, palette_n, d_first,
         # d_status, stream
         "draw_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, vp, ci, vp, ci, vp, vp, vp],
@@ -218,6 +228,8 @@ def load():
     lib.yf_images_set_decode_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     lib.yf_images_average_precision_workspace.restype = ctypes.c_size_t
     lib.yf_images_average_precision_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
+    lib.yf_images_blur_workspace.restype = ctypes.c_size_t
+    lib.yf_images_blur_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
     lib.yf_images_track_state_bytes.restype = ctypes.c_size_t
     lib.yf_images_track_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
@@ -922,6 +934,75 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     bad = np.nonzero(d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"detect_redacted: the descriptor of image {int(bad[0])} is invalid")
+    return _pictures_back(b, fmt), b.boxes(np.diff(d_first.cpu().numpy()))
+
+
+def blur_workspace(records_cap, grid):
+    """The bytes of the workspace of a blur of at most `records_cap` records at `grid` (yf_images_blur_workspace): records_cap * grid *
+    grid * 4 rounded up to 16; 0 for arguments the call refuses."""
+    return int(load().yf_images_blur_workspace(records_cap, grid))
+
+
+def blur_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_work, work_bytes, records_cap, d_first, d_status,
+                        grid=8, colour=0, margin_permille=0, square=False, stream=None):
+    """The regions of the records of a batch of packed pictures blurred IN PLACE (yf_images_blur_records_device): every region becomes a
+    grid of at most grid x grid means of its own pixels (no cell narrower than 4 pixels), resized back to the region as cv2.resize does.
+    d_images IMAGE_DTYPE[n], d_dets yf_det[n][cap], d_counts int32[n]; d_pixels is read and written.  d_work: `blur_workspace(records_cap,
+    grid)` bytes, 16-byte aligned; record k = first[f] + s keeps its grid in slot k, and a record with k >= records_cap is filled with
+    colour (0x00RRGGBB or (R, G, B)) instead.  d_first int32[n + 1] and d_status int32[n] are written: bit 0 the picture's descriptor is
+    invalid (the picture untouched), bit 1 a record of the frame was filled for lack of a slot.  A pixel in several regions gets the value of
+    the lowest slot; a second call blurs the blur.  The pictures of different frames must not share bytes.  The definition:
+    csrc/yf_images_blur.h, ptq.blur_u8."""
+    _call("blur_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "blur_records_device"), d_images, d_dets, d_counts, n, cap,
+          grid, _colour_code(colour), margin_permille, YF_CROP_SQUARE if square else 0, d_work, work_bytes, records_cap, d_first, d_status, stream)
+
+
+def blur_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_work, work_bytes, records_cap, d_first,
+                            d_status, grid=8, colour=0, margin_permille=0, square=False, stream=None):
+    """`blur_records_device` for NV12 / NV21 surfaces, blurred where they lie (yf_images_blur_records_yuv_device): d_images
+    YUV_IMAGE_DTYPE[n]; the Y plane and the chroma plane each get a grid of their own; colour 0x00YYUUVV or (Y, U, V).
+    ptq.blur_yuv420sp."""
+    _call("blur_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, grid, _colour_code(colour),
+          margin_permille, YF_CROP_SQUARE if square else 0, d_work, work_bytes, records_cap, d_first, d_status, stream)
+
+
+def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None, iou_threshold=0.4, size=56,
+                   dtype="int8", tile=None, stride=None, device=None):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and every kept box blurred in its picture on the GPU, on
+    the same stream, in the pixels that are already there: the box becomes a grid of at most `grid` x `grid` (1 to 16) means of its own
+    pixels, resized back to the box -- every face gets the same number of cells, so a large face is hidden as well as a small one.
+    `margin` and `square` grow the box as in `detect_chips`.  The workspace is sized for every record the batch can hold, so no box is
+    ever filled with `colour` for lack of room.  fmt, cap, iou_threshold, size, dtype, device as in `detect`; with `tile`, cap is
+    `detect_tiled`'s out_cap and the parent pictures are blurred.
+    Returns (pictures, boxes) as `detect_redacted` does.  The definition is the library's own: csrc/yf_images_blur.h, restated as
+    `ptq.blur_u8` and `ptq.blur_yuv420sp`."""
+    grid = int(grid)
+    if not 1 <= grid <= BLUR_MAX_GRID:
+        raise ValueError(f"grid {grid!r}: 1 to {BLUR_MAX_GRID}")
+    colour_code = _colour_code(colour)
+    permille = _permille(margin)
+    n = len(images)
+    if n == 0:
+        return [], []
+    import torch
+    yuv = is_yuv(fmt)
+    if tile is not None:
+        _packed_code(fmt, "detect_blurred(tile=...)")
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    records_cap = n * b.cap
+    room = blur_workspace(records_cap, grid)
+    d_work = torch.empty(room, dtype=torch.uint8, device=b.device)
+    d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
+    d_status = torch.empty(n, dtype=torch.int32, device=b.device)
+    blur = blur_records_yuv_device if yuv else blur_records_device
+    blur(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap, d_work.data_ptr(),
+         room, records_cap, d_first.data_ptr(), d_status.data_ptr(), grid=grid, colour=colour_code, margin_permille=permille, square=square,
+         stream=b.stream.cuda_stream)
+    b.stream.synchronize()
+    b.check_totals("detect_blurred")
+    bad = np.nonzero(d_status.cpu().numpy() & 1)[0]
+    if bad.size:
+        raise ImagesError(f"detect_blurred: the descriptor of image {int(bad[0])} is invalid")
     return _pictures_back(b, fmt), b.boxes(np.diff(d_first.cpu().numpy()))
 
 

@@ -25,6 +25,8 @@ or calib.host_histogram: csrc/yf_calib_hist.h), by percentile or by least modell
 `quantize_model` applies the rules to a whole float model: .yfw bytes and calibrated ranges in, a .yfm image out that yf_network_init_model
 admits.  The ranges come from the calibration library (calib.py: the float32 evaluation on the GPU, or its host build).
 """
+import functools
+
 import numpy as np
 
 from . import model_file
@@ -295,6 +297,28 @@ class Calibrator:
         return activation_qparams(*self.ranges[name])
 
 
+@functools.lru_cache(maxsize=4096)
+def _resize_axis(n_out, n_in):
+    """the source index and the two 11-bit weights of every output index of one axis of `resize_linear_u8` (read-only arrays)"""
+    scale = np.float64(n_in) / n_out
+    idx, c0, c1 = np.zeros(n_out, np.int64), np.zeros(n_out, np.int64), np.zeros(n_out, np.int64)
+    for d in range(n_out):
+        f = np.float32((d + 0.5) * scale - 0.5)                        # OpenCV computes this in float
+        s = int(np.floor(f))
+        f = np.float32(f - s)
+        if s < 0:
+            s, f = 0, np.float32(0)
+        if s >= n_in - 1:
+            s, f = n_in - 1, np.float32(0)
+        # saturate_cast<short>(float) = cvRound: round half to even
+        c0[d] = int(np.rint(np.float32((np.float32(1) - f) * np.float32(2048))))
+        c1[d] = int(np.rint(np.float32(f * np.float32(2048))))
+        idx[d] = s
+    for a in (idx, c0, c1):
+        a.setflags(write=False)
+    return idx, c0, c1
+
+
 def resize_linear_u8(img, out_w, out_h):
     """OpenCV's `cv2.resize(img, (out_w, out_h))` (INTER_LINEAR, the default) for uint8 images [H, W, C], restated from the
     published algorithm (imgproc/resize.cpp: pixel centres aligned -- src = (dst + 0.5) * scale - 0.5 --, NO antialiasing,
@@ -306,25 +330,8 @@ def resize_linear_u8(img, out_w, out_h):
     h, w = src.shape[:2]
     src = src.reshape(h, w, -1).astype(np.int64)
 
-    def axis(n_out, n_in):
-        scale = np.float64(n_in) / n_out
-        idx, c0, c1 = np.zeros(n_out, np.int64), np.zeros(n_out, np.int64), np.zeros(n_out, np.int64)
-        for d in range(n_out):
-            f = np.float32((d + 0.5) * scale - 0.5)                        # OpenCV computes this in float
-            s = int(np.floor(f))
-            f = np.float32(f - s)
-            if s < 0:
-                s, f = 0, np.float32(0)
-            if s >= n_in - 1:
-                s, f = n_in - 1, np.float32(0)
-            # saturate_cast<short>(float) = cvRound: round half to even
-            c0[d] = int(np.rint(np.float32((np.float32(1) - f) * np.float32(2048))))
-            c1[d] = int(np.rint(np.float32(f * np.float32(2048))))
-            idx[d] = s
-        return idx, c0, c1
-
-    xi, xa0, xa1 = axis(out_w, w)
-    yi, yb0, yb1 = axis(out_h, h)
+    xi, xa0, xa1 = _resize_axis(int(out_w), int(w))
+    yi, yb0, yb1 = _resize_axis(int(out_h), int(h))
     xi1 = np.minimum(xi + 1, w - 1)
     rows = src[:, xi, :] * xa0[None, :, None] + src[:, xi1, :] * xa1[None, :, None]          # [H, out_w, C], int32 range
     yi1 = np.minimum(yi + 1, h - 1)
@@ -459,6 +466,90 @@ def redact_yuv420sp(y, uv, regions, mode, block, colour, v_first=False):
         for x0, y0, rw, rh in (r for r in regions if r is not None):
             y_out[y0:y0 + rh, x0:x0 + rw] = yy
             pairs_out[y0 >> 1:((y0 + rh - 1) >> 1) + 1, x0 >> 1:((x0 + rw - 1) >> 1) + 1] = (v, u) if v_first else (u, v)
+    return y_out, uv_out
+
+
+# ---- the blur (csrc/yf_images_blur.h), in plain numpy ----
+BLUR_MAX_GRID = 16
+BLUR_MIN_CELL = 4
+
+
+def blur_cells(side, grid, min_cell=BLUR_MIN_CELL):
+    """the cells along a side of `side` pixels: max(1, min(grid, side // min_cell))"""
+    return max(1, min(int(grid), int(side) // min_cell))
+
+
+def blur_grid_u8(plane_hwc, grid, min_cell=BLUR_MIN_CELL):
+    """The grid of means of a region (uint8 [height, width, channels]) -> uint8 [gy, gx, channels]: cell cx holds the columns
+    [cx * width // gx, (cx + 1) * width // gx), rows likewise; per cell and channel (sum + cnt // 2) // cnt in exact integers."""
+    src = np.asarray(plane_hwc, np.uint8)
+    h, w = src.shape[:2]
+    gx, gy = blur_cells(w, grid, min_cell), blur_cells(h, grid, min_cell)
+    # the prefix sums of the region, int64: a cell's sum is four reads
+    acc = np.zeros((h + 1, w + 1, src.shape[2]), np.int64)
+    acc[1:, 1:] = src.astype(np.int64).cumsum(axis=0).cumsum(axis=1)
+    xs = np.array([c * w // gx for c in range(gx + 1)])
+    ys = np.array([c * h // gy for c in range(gy + 1)])
+    sums = acc[ys[1:, None], xs[None, 1:]] - acc[ys[:-1, None], xs[None, 1:]] - acc[ys[1:, None], xs[None, :-1]] + acc[ys[:-1, None], xs[None, :-1]]
+    cnt = ((ys[1:] - ys[:-1])[:, None] * (xs[1:] - xs[:-1])[None, :])[..., None]
+    return ((sums + cnt // 2) // cnt).astype(np.uint8)
+
+
+def _blur_grid(grid):
+    if isinstance(grid, bool) or int(grid) != grid or not 1 <= int(grid) <= BLUR_MAX_GRID:
+        raise ValueError(f"grid {grid!r}: 1 to {BLUR_MAX_GRID}")
+    return int(grid)
+
+
+def _blur_plane(src, out, rects, grid, min_cell, colours):
+    """every rectangle (x0, y0, width, height) of `rects` (None: no region) of the plane `out` [rows, cols, channels] becomes the grid of
+    means of the same rectangle of `src` resized back to it -- or, with colours[k] not None, that colour; a pixel in several rectangles
+    gets the value of the first that holds it: they are painted from the last to the first."""
+    for k in range(len(rects) - 1, -1, -1):
+        if rects[k] is None:
+            continue
+        x0, y0, w, h = rects[k]
+        if colours[k] is not None:
+            out[y0:y0 + h, x0:x0 + w] = colours[k]
+        else:
+            out[y0:y0 + h, x0:x0 + w] = resize_linear_u8(blur_grid_u8(src[y0:y0 + h, x0:x0 + w], grid, min_cell), w, h)
+
+
+def blur_u8(picture_hwc, regions, grid, colour=None, filled=()):
+    """The blurred copy of a packed picture (uint8 [H, W, 3 or 4]), as csrc/yf_images_blur.h states it.  `regions`: (x0, y0, width,
+    height) per record, as `crop_region` gives them (None entries are skipped).  Every region becomes `resize_linear_u8` of its own grid
+    of means (`blur_grid_u8`: at most grid x grid cells, none narrower than 4 pixels), the means taken from the picture as it came in;
+    a pixel in several regions gets the value of the first region that holds it.  `filled`: the indices of the records that get `colour`
+    instead (three bytes for the picture's channels 0, 1, 2 in the picture's own order) -- the records without a slot in the workspace.
+    A fourth channel is never touched."""
+    grid = _blur_grid(grid)
+    src = np.asarray(picture_hwc, np.uint8)
+    out = src.copy()
+    filled = set(filled)
+    colours = [np.asarray(colour, np.uint8).reshape(3) if k in filled else None for k in range(len(regions))]
+    _blur_plane(src[..., :3], out[..., :3], list(regions), grid, BLUR_MIN_CELL, colours)
+    return out
+
+
+def blur_yuv420sp(y, uv, regions, grid, colour=None, filled=(), v_first=False):
+    """`blur_u8` for an NV12 / NV21 surface (y uint8 [H, W], uv uint8 [H / 2, W]) -> (y, uv) blurred copies.  The Y plane is a one-channel
+    picture over the region; the chroma plane a two-channel picture of pairs over the chroma region cx in [x0 >> 1, (x0 + width - 1) >>
+    1], cy likewise, with a grid of its own whose cells are at least 2 pairs wide; a pair in several chroma regions gets the value of the
+    first.  First bytes are averaged together and second bytes together (v_first matters to the fill only).  `colour` = (Y, U, V)."""
+    grid = _blur_grid(grid)
+    y_src, uv_src = np.asarray(y, np.uint8), np.asarray(uv, np.uint8)
+    y_out, uv_out = y_src.copy(), uv_src.copy()
+    h2, w = uv_src.shape
+    pairs_src, pairs_out = uv_src.reshape(h2, w // 2, 2), uv_out.reshape(h2, w // 2, 2)
+    regions, filled = list(regions), set(filled)
+    chroma = [None if r is None else (r[0] >> 1, r[1] >> 1, ((r[0] + r[2] - 1) >> 1) - (r[0] >> 1) + 1, ((r[1] + r[3] - 1) >> 1) - (r[1] >> 1) + 1)
+              for r in regions]
+    if filled:
+        yy, u, v = (int(c) for c in colour)
+    luma = [np.uint8(yy) if k in filled else None for k in range(len(regions))]
+    pair = [np.array((v, u) if v_first else (u, v), np.uint8) if k in filled else None for k in range(len(regions))]
+    _blur_plane(y_src[..., None], y_out[..., None], regions, grid, BLUR_MIN_CELL, luma)
+    _blur_plane(pairs_src, pairs_out, chroma, grid, 2, pair)
     return y_out, uv_out
 
 
