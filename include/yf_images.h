@@ -518,6 +518,60 @@ YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, l
                                      const yf_track_params* params, void* d_state, void* d_out, void* d_info, void* d_out_counts,
                                      int out_cap, int32_t* d_status, void* stream);
 
+/* ---- letterboxed frames: the picture resized with its aspect kept, centred in the square frame, the rest padded with one grey, and the
+ * boxes mapped back through the same rectangle.  Every entry above stretches the picture onto the frame, as the reference's scripts do
+ * (cv2.resize(img, (56, 56))); that stays the default.  Every mainstream YOLO trainer letterboxes instead, so a retrained model (.yfm, or
+ * a float model quantised through yf_calib) wants such frames for inference AND for its calibration.  THE SHIPPED MODEL WAS TRAINED ON
+ * STRETCHED PICTURES, and no effect of letterboxing on its accuracy has been measured: yf_images_match_device /
+ * yf_images_average_precision_device score either preprocessing on labelled pictures.  The definition is this library's own, stated once
+ * in csrc/yf_images_fit.h, which the kernels, a host build and a sanitizer program share.
+ *   fit:    for a picture of H x W and a frame side S (56 or 160), in int64: W >= H: width = S, height = max(1, (2 H S + W) / (2 W)) --
+ *           the exact ratio rounded half up --, W < H symmetric; x0 = (S - width) / 2, y0 = (S - height) / 2 (floor: the odd pixel of
+ *           padding goes right and bottom, as ultralytics' LetterBox centres it).  A square picture: {0, 0, S, S}.  yf_images_fit
+ *           computes it on the host: 0, or -1 with a text for sides outside [1, 16384], an out_hw that is not 56 or 160, or fit NULL.
+ *   frame:  inside the rectangle frame[y0 + y][x0 + x][c] = (int8)(R[y][x][rgb(c)] - 128), R = cv2.resize(picture, (width, height))
+ *           INTER_LINEAR (the arithmetic of the plain prepare at a run-time output size); outside (int8)(pad - 128), pad a byte 0..255,
+ *           one grey for the three channels (the trainers use 114).  fp16 frames: fp16(v / 255.) of the same bytes.  NV12 / NV21: each
+ *           sampled pixel converted first, as in the plain YUV prepare.  A padded pixel loads nothing from the picture.  For a square
+ *           picture the frame equals the plain prepare's byte for byte.
+ *   boxes:  the YF_DECODE_PY decode (at both grids, and of the fp16 network's float32 logits), with another tail: after the four edges in
+ *           frame pixels, x = (x - (float)x0) * x_scale, y = (y - (float)y0) * y_scale in float32, one IEEE operation per step, with
+ *           x_scale = (float)((double)W / (double)width), y_scale = (float)((double)H / (double)height) -- per axis, the scales the
+ *           resize used --, then float32 -> int32 as every decode (truncation; out of range and NaN -> INT32_MIN).  Boxes are not
+ *           clipped: an edge can land in the padding, outside the picture.  There is no firmware mode.  For a square picture the records
+ *           equal the plain ragged decode's byte for byte.
+ * The batches are ragged only (one descriptor per picture; a uniform batch is descriptors of one size).  d_status[i] = 1 for an invalid
+ * descriptor: its frame is all -128 (fp16: zeros), its picture is never read and its count is 0.  The decodes recompute the fit from the
+ * descriptor's height and width alone (a yf_image_yuv batch: a yf_image per surface with its sides); d_status may be NULL there.  True
+ * counts go to d_counts, only the first cap records are written, nothing beyond min(count, cap): cap in [1, 147] at 56 and for the float
+ * logits, [1, 1200] at 160.  The run_* entries are prepare, the network and the decode on `stream`; as for the plain path there is none
+ * for NV12 / NV21: the frames are the interface (yf_images_prepare_fit_yuv_ragged_device, yf_network_run_device,
+ * yf_images_decode_fit_ragged_device).  Calibration frames for yf_calib are these frames: INTEGRATION.md.
+ * All asynchronous on `stream`, no allocation, no host synchronisation, capturable (the int8 decodes under the decode-table rule of
+ * yf_images_set_decode_tables above: a first call outside capture).  Every argument is checked before the first launch -- each entry
+ * refuses the other family's formats, pad outside [0, 255], out_hw other than 56 or 160, a cap out of range, NULL or misaligned
+ * pointers as the plain entries do -- and n = 0 launches nothing after the checks.  Return n, or 0 and a text. */
+typedef struct yf_fit { int32_t x0, y0, width, height; } yf_fit;                   /* where the picture lies in its frame */
+YF_API int  yf_images_fit(int height, int width, int out_hw, yf_fit* fit);
+YF_API long yf_images_prepare_fit_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                int out_hw, int pad, void* d_frames, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_fit_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                    long n, int out_hw, int pad, void* d_frames, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_fit_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                    int pad, void* d_frames_f16, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_fit_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                        long n, int pad, void* d_frames_f16, int32_t* d_status, void* stream);
+YF_API long yf_images_decode_fit_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int out_hw,
+                                               void* d_dets, void* d_counts, int cap, void* stream);
+YF_API long yf_images_decode_f32_fit_ragged_device(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n,
+                                                   void* d_dets, void* d_counts, int cap, void* stream);
+YF_API long yf_images_run_decode_fit_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                   const yf_image* d_images, long n, int out_hw, int pad, void* d_frames, void* d_heads,
+                                                   void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+YF_API long yf_images_run_decode_fit_f16_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                       const yf_image* d_images, long n, int pad, void* d_frames_f16, void* d_logits,
+                                                       void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

@@ -19,7 +19,8 @@
 // yf_images_redact.h and yf_images_redact.hip.h; the blur (every record's region replaced by a grid of its means resized back) in
 // yf_images_blur.h and yf_images_blur.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
-// yf_images_track.h and yf_images_track.hip.h.
+// yf_images_track.h and yf_images_track.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
+// boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -44,6 +45,7 @@
 #include "yf_images_blur.hip.h"
 #include "yf_images_draw.hip.h"
 #include "yf_images_track.hip.h"
+#include "yf_images_fit.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -935,6 +937,51 @@ long track(const void* d_dets, const void* d_counts, long streams, long steps, i
   return launched("track kernel launch", n) == n ? n : -1;
 }
 
+// ---- letterboxed frames (yf_images_fit.h) ----  the prepare kernels by format (the four packed formats in the order of their codes,
+// then NV12, NV21), for a frame side and an element type
+using FitKernel = void (*)(yffit::Args);
+template <int OUT, typename T>
+constexpr FitKernel kFit[6] = {yffit::frames_kernel<OUT, 3, true, T>, yffit::frames_kernel<OUT, 3, false, T>,
+                               yffit::frames_kernel<OUT, 4, true, T>, yffit::frames_kernel<OUT, 4, false, T>,
+                               yffit::frames_yuv_kernel<OUT, false, T>, yffit::frames_yuv_kernel<OUT, true, T>};
+
+// the four prepare entries: every argument (yfi_fit_check_prepare), then the launch.  yuv: the entry's family; f16: fp16 frames
+long fit_prepare(bool yuv, bool f16, const void* d_pixels, size_t pixels_bytes, int format, const void* d_images, long n, int out_hw, int pad,
+                 void* d_frames, int32_t* d_status, hipStream_t s) {
+  const char* err = yfi_fit_check_prepare(yuv, f16, d_pixels, format, d_images, n, out_hw, pad, d_frames, d_status);
+  if (err) return fail("%s", err);
+  if (n == 0) return 0;
+  const FitKernel* k = f16 ? kFit<56, uint16_t> : (out_hw == 56 ? kFit<56, int8_t> : kFit<160, int8_t>);
+  const yffit::Args a{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, n, d_frames, pad};
+  hipLaunchKernelGGL(k[format], grid_for(n, f16 ? 6 : 8), dim3(yffit::kThreads), 0, s, a);          // the plain prepare's LDS and grids
+  return launched("prepare_fit kernel launch", n);
+}
+
+// of checked arguments; net: the network whose tables decode (nullptr: the pair of yf_images_set_decode_tables)
+long fit_decode(ai_handle net, const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int out_hw, void* d_dets,
+                void* d_counts, int cap, hipStream_t s) {
+  if (n == 0) return 0;
+  int q_thr = 128;
+  if (!tables_ready(net, s, &q_thr)) return 0;
+  if (out_hw == 56) {
+    const long groups = (n + yffit::kWaves - 1) / yffit::kWaves;
+    hipLaunchKernelGGL(yffit::decode56_kernel, dim3((unsigned)(groups < 65536 ? groups : 65536)), dim3(yffit::kThreads), 0, s,
+                       (const int8_t*)d_heads, d_images, d_status, n, (yf_det*)d_dets, (int*)d_counts, cap);
+  } else {
+    hipLaunchKernelGGL(yffit::decode160_kernel, grid_for(n, 8), dim3(yffit::kThreads), 0, s, (const int8_t*)d_heads, d_images, d_status, n,
+                       q_thr, (yf_det*)d_dets, (int*)d_counts, cap);                                // 9.2 KB of LDS per workgroup
+  }
+  return launched("decode_fit kernel launch", n);
+}
+
+long fit_decode_f32(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n, void* d_dets, void* d_counts, int cap,
+                    hipStream_t s) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(yffit::decode_f32_kernel, grid_for((n + yffit::kWaves - 1) / yffit::kWaves, 8), dim3(yffit::kThreads), 0, s,
+                     (const float*)d_logits, d_images, d_status, n, (yf_det*)d_dets, (int*)d_counts, cap);       // 13.8 KB of LDS per workgroup
+  return launched("decode_f32_fit kernel launch", n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1302,6 +1349,84 @@ YF_API long yf_images_track_device(const void* d_dets, const void* d_counts, lon
                                    const yf_track_params* params, void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap,
                                    int32_t* d_status, void* stream) {
   return track(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
+}
+
+YF_API int yf_images_fit(int height, int width, int out_hw, yf_fit* fit) {
+  if (!fit) { fail("fit is NULL"); return -1; }
+  if (out_hw != 56 && out_hw != 160) { fail("out_hw must be 56 or 160"); return -1; }
+  if (!yfi_fit_sides_ok(height, width)) { fail("height and width must be in [1, 16384]"); return -1; }
+  *fit = yfi_fit_of(height, width, out_hw);
+  return 0;
+}
+
+YF_API long yf_images_prepare_fit_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                int out_hw, int pad, void* d_frames, int32_t* d_status, void* stream) {
+  return fit_prepare(false, false, d_pixels, pixels_bytes, format, d_images, n, out_hw, pad, d_frames, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_fit_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                    long n, int out_hw, int pad, void* d_frames, int32_t* d_status, void* stream) {
+  return fit_prepare(true, false, d_pixels, pixels_bytes, format, d_images, n, out_hw, pad, d_frames, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_fit_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                    int pad, void* d_frames_f16, int32_t* d_status, void* stream) {
+  return fit_prepare(false, true, d_pixels, pixels_bytes, format, d_images, n, 56, pad, d_frames_f16, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_fit_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                        long n, int pad, void* d_frames_f16, int32_t* d_status, void* stream) {
+  return fit_prepare(true, true, d_pixels, pixels_bytes, format, d_images, n, 56, pad, d_frames_f16, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode_fit_ragged_device(const void* d_heads, const yf_image* d_images, const int32_t* d_status, long n, int out_hw,
+                                               void* d_dets, void* d_counts, int cap, void* stream) {
+  const char* err = yfi_fit_check_decode(0, d_heads, d_images, d_status, n, out_hw, d_dets, d_counts, cap);
+  if (err) return fail("%s", err);
+  return fit_decode(nullptr, d_heads, d_images, d_status, n, out_hw, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+YF_API long yf_images_decode_f32_fit_ragged_device(const void* d_logits, const yf_image* d_images, const int32_t* d_status, long n,
+                                                   void* d_dets, void* d_counts, int cap, void* stream) {
+  const char* err = yfi_fit_check_decode(1, d_logits, d_images, d_status, n, 56, d_dets, d_counts, cap);
+  if (err) return fail("%s", err);
+  return fit_decode_f32(d_logits, d_images, d_status, n, d_dets, d_counts, cap, (hipStream_t)stream);
+}
+
+// images -> letterboxed frames -> heads -> records on the stream: every argument first, then tables, prepare, network, decode
+YF_API long yf_images_run_decode_fit_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                   const yf_image* d_images, long n, int out_hw, int pad, void* d_frames, void* d_heads,
+                                                   void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream) {
+  if (!net) return fail("network handle is NULL");
+  const char* err = yfi_fit_check_prepare(0, 0, d_pixels, format, d_images, n, out_hw, pad, d_frames, d_status);
+  if (!err) err = yfi_fit_check_decode(0, d_heads, d_images, d_status, n, out_hw, d_dets, d_counts, cap);
+  if (err) return fail("%s", err);
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!tables_ready(net, s)) return 0;
+  if (fit_prepare(false, false, d_pixels, pixels_bytes, format, d_images, n, out_hw, pad, d_frames, d_status, s) != n) return 0;
+  if (out_hw == 56) {
+    if (yf_network_run_device(net, d_frames, d_heads, n, stream) != n) return network_failed(net, "yf_network_run_device");
+  } else if (yf_network_run_device_hw(net, 160, 160, d_frames, d_heads, n, stream) != n) {
+    return network_failed(net, "yf_network_run_device_hw");
+  }
+  return fit_decode(net, d_heads, d_images, d_status, n, out_hw, d_dets, d_counts, cap, s);
+}
+
+// ... on the fp16 network; nothing is launched on a network without yf_network_fp16_init
+YF_API long yf_images_run_decode_fit_f16_ragged_device(ai_handle net, const void* d_pixels, size_t pixels_bytes, int format,
+                                                       const yf_image* d_images, long n, int pad, void* d_frames_f16, void* d_logits,
+                                                       void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream) {
+  if (!net) return fail("network handle is NULL");
+  const char* err = yfi_fit_check_prepare(0, 1, d_pixels, format, d_images, n, 56, pad, d_frames_f16, d_status);
+  if (!err) err = yfi_fit_check_decode(1, d_logits, d_images, d_status, n, 56, d_dets, d_counts, cap);
+  if (err) return fail("%s", err);
+  if (!yf_network_fp16_ready(net)) return network_failed(net, "yf_network_fp16_ready");
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  if (fit_prepare(false, true, d_pixels, pixels_bytes, format, d_images, n, 56, pad, d_frames_f16, d_status, s) != n) return 0;
+  if (yf_network_fp16_run_device(net, d_frames_f16, d_logits, n, stream) != n) return network_failed(net, "yf_network_fp16_run_device");
+  return fit_decode_f32(d_logits, d_images, d_status, n, d_dets, d_counts, cap, s);
 }
 
 }  // extern "C"

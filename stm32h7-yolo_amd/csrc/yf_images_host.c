@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h and the tracker of yf_images_track.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h and the letterboxed frames and decodes of yf_images_fit.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -19,6 +19,7 @@
 #include "yf_images_blur.h"
 #include "yf_images_draw.h"
 #include "yf_images_track.h"
+#include "yf_images_fit.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -827,3 +828,119 @@ EXPORT int yfi_track_check_host(const void* dets, const void* counts, long strea
 }
 
 EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
+
+/* ---- yf_images_fit.h ----  out[4] = {x0, y0, width, height} of a picture of h x w in a frame of side S (no range check: the tests
+ * ask for what the definition gives) */
+EXPORT void yfi_fit_host(int64_t h, int64_t w, int64_t S, int32_t* out) {
+  const yf_fit f = yfi_fit_of(h, w, S);
+  out[0] = f.x0; out[1] = f.y0; out[2] = f.width; out[3] = f.height;
+}
+
+static void fit_store(void* frame, size_t at, int f16, int32_t v) {
+  if (f16) ((uint16_t*)frame)[at] = yfi_f16_of_u8(v);
+  else ((int8_t*)frame)[at] = (int8_t)(v - 128);
+}
+
+/* One packed picture as yffit::frames_kernel takes it: `base` + the descriptor's offset, checked against `bytes` -> frame
+ * int8[out_hw][out_hw][3] (f16 == 0) or the fp16 bits uint16[56][56][3], through yfi_fit_of and yfi_fit_tap; a padded pixel reads nothing.
+ * Returns the status the kernel writes: 0, or 1 for an invalid descriptor, whose frame is all -128 (fp16: all 0) and which is never
+ * read.  -1: the format is not a packed one, out_hw is not 56 or 160 (fp16: not 56), or pad is outside [0, 255]. */
+EXPORT int yfi_prepare_fit_host(const uint8_t* base, uint64_t bytes, int format, const yf_image* im, int out_hw, int pad, int f16, void* frame) {
+  const int C = yfi_tiles_channels(format), bgr = format == YF_PIX_BGR8 || format == YF_PIX_BGRA8;
+  if (!C || (out_hw != 56 && (f16 || out_hw != 160)) || pad < 0 || pad > 255) return -1;
+  const size_t count = (size_t)out_hw * (size_t)out_hw * 3;
+  if (!yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes)) {
+    if (f16) memset(frame, 0, count * 2); else memset(frame, 0x80, count);
+    return 1;
+  }
+  const yf_fit fit = yfi_fit_of(im->height, im->width, out_hw);
+  const uint8_t* px = base + im->offset;
+  for (int y = 0; y < out_hw; ++y) {
+    const yfi_tap ty = yfi_fit_tap(y, fit.y0, fit.height, im->height);
+    for (int x = 0; x < out_hw; ++x) {
+      const yfi_tap tx = yfi_fit_tap(x, fit.x0, fit.width, im->width);
+      for (int c = 0; c < 3; ++c) {
+        const size_t at = ((size_t)y * out_hw + x) * 3 + c;
+        if ((tx.w0 | ty.w0) < 0) { fit_store(frame, at, f16, pad); continue; }
+        const uint8_t* r0 = px + (uint64_t)ty.s0 * (uint64_t)im->row_stride;
+        const uint8_t* r1 = px + (uint64_t)ty.s1 * (uint64_t)im->row_stride;
+        const int sc = bgr ? 2 - c : c;
+        const int32_t h0 = yfi_hpass(r0[tx.s0 * C + sc], r0[tx.s1 * C + sc], tx.w0, tx.w1);
+        const int32_t h1 = yfi_hpass(r1[tx.s0 * C + sc], r1[tx.s1 * C + sc], tx.w0, tx.w1);
+        fit_store(frame, at, f16, yfi_vpass(h0, h1, ty.w0, ty.w1));
+      }
+    }
+  }
+  return 0;
+}
+
+/* ... and one NV12 / NV21 surface as yffit::frames_yuv_kernel takes it (yfi_prepare_yuv_host with the fit) */
+EXPORT int yfi_prepare_fit_yuv_host(const uint8_t* base, uint64_t bytes, const yf_image_yuv* im, int v_first, int out_hw, int pad, int f16,
+                                    void* frame) {
+  if ((out_hw != 56 && (f16 || out_hw != 160)) || pad < 0 || pad > 255) return -1;
+  const size_t count = (size_t)out_hw * (size_t)out_hw * 3;
+  if (!yfi_yuv_image_ok(im->offset_y, im->offset_uv, im->height, im->width, im->stride_y, im->stride_uv, bytes)) {
+    if (f16) memset(frame, 0, count * 2); else memset(frame, 0x80, count);
+    return 1;
+  }
+  const yf_fit fit = yfi_fit_of(im->height, im->width, out_hw);
+  const uint8_t* yp = base + im->offset_y;
+  const uint8_t* uvp = base + im->offset_uv;
+  for (int y = 0; y < out_hw; ++y) {
+    const yfi_tap fy = yfi_fit_tap(y, fit.y0, fit.height, im->height);
+    const yfi_yuv_ytap ty = yfi_yuv_ytap_of(fy, im->stride_y, im->stride_uv);
+    for (int x = 0; x < out_hw; ++x) {
+      const yfi_tap fx = yfi_fit_tap(x, fit.x0, fit.width, im->width);
+      int32_t rgb[3] = {pad, pad, pad};
+      if ((fx.w0 | fy.w0) >= 0) yfi_yuv_sample(yp, uvp, yfi_yuv_xtap_of(fx), ty, v_first, rgb);
+      for (int c = 0; c < 3; ++c) fit_store(frame, ((size_t)y * out_hw + x) * 3 + c, f16, rgb[c]);
+    }
+  }
+  return 0;
+}
+
+/* The decode of one int8 head (7x7 at out_hw 56, 20x20 at 160) of a picture of height x width as yffit::decode56_kernel /
+ * decode160_kernel compute it, with the compiled-in tables: candidates in the order (anchor, row, col), conf > 0.7f (at 160 the byte test
+ * against yfi_d160_q_threshold, which says the same for a monotonic table), the record of yfi_fit_candidate for those that fire, the first
+ * `cap` written.  status != 0 or a side outside [1, 16384]: 0 records.  Returns the true count, or -1 for another out_hw. */
+EXPORT int yfi_decode_fit_host(const int8_t* head, int32_t frame, int32_t height, int32_t width, int32_t status, int out_hw, yf_det* dets,
+                               int cap) {
+  if (out_hw != 56 && out_hw != 160) return -1;
+  if (!yfi_fit_sides_ok(height, width) || status != 0) return 0;
+  const int G = out_hw / 8, q_thr = yfi_d160_q_threshold(yf_sigmoid_bits);
+  const yfi_fit_map m = yfi_fit_map_of(height, width, out_hw);
+  int n = 0;
+  for (int i = 0; i < 3 * G * G; ++i) {
+    const int8_t* p = head + yfi_fit_offset(i, G);
+    if (out_hw == 56 ? !(yfi_d160_bits(yf_sigmoid_bits[p[4] + 128]) > 0.7f) : p[4] < q_thr) continue;
+    if (n < cap) dets[n] = yfi_fit_candidate(p, i, G, frame, yf_sigmoid_bits, yf_exp_bits, m);
+    ++n;
+  }
+  return n;
+}
+
+/* ... and of one frame's float32 logits [7][7][18] as yffit::decode_f32_kernel computes it */
+EXPORT int yfi_decode_f32_fit_host(const float* logits, int32_t frame, int32_t height, int32_t width, int32_t status, yf_det* dets, int cap) {
+  if (!yfi_fit_sides_ok(height, width) || status != 0) return 0;
+  const yfi_fit_map m = yfi_fit_map_of(height, width, 56);
+  int n = 0;
+  for (int i = 0; i < YFI_F32_CAND; ++i) {
+    const float* p = logits + yfi_fit_offset(i, 7);
+    const float conf = yfi_sigmoid_f32(p[4]);
+    if (!(conf > 0.7f)) continue;
+    if (n < cap) dets[n] = yfi_fit_candidate_f32(p, i, frame, conf, m);
+    ++n;
+  }
+  return n;
+}
+
+/* the argument checks alone, as the entry points make them: what 0 a prepare (yuv: the entry's family, f16: fp16 frames), what 1 a
+ * decode (f16: float32 logits; a: the heads, pad and format are not used).  The text of the first fault into out (at most out_bytes,
+ * 0-terminated), or an empty text; returns 1 for a fault */
+EXPORT int yfi_fit_check_host(int what, int yuv, int f16, const void* a, int format, const void* images, long n, int out_hw, int pad,
+                              const void* frames_or_dets, const void* status, const void* counts, int cap, char* out, int out_bytes) {
+  const char* t = what == 0 ? yfi_fit_check_prepare(yuv, f16, a, format, images, n, out_hw, pad, frames_or_dets, status)
+                            : yfi_fit_check_decode(f16, a, images, status, n, out_hw, frames_or_dets, counts, cap);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
+}

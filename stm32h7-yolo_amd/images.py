@@ -43,6 +43,13 @@ over the frames and a face the detector misses for a few frames is held over wit
 again, which `crop_records_device` and `redact_records_device` take as they are.  The reference has no tracker; the definition is the
 library's own (csrc/yf_images_track.h, `ptq.track_step`).
 
+`fit="letterbox"` on `detect`, every `detect_*` call and `evaluate` replaces the stretch onto the square frame by what every mainstream
+YOLO trainer does: the picture resized with its aspect kept into a centred rectangle of the frame (`fit_of`), the rest padded with the
+grey `pad`, and the boxes mapped back through the same rectangle -- `prepare_fit_*`, `decode_fit_ragged_device`,
+`decode_f32_fit_ragged_device`, `run_decode_fit_*`; the definition is the library's own (csrc/yf_images_fit.h, `ptq.letterbox_fit`,
+`ptq.letterbox_u8`).  It is for retrained models and their calibration frames: the shipped model was trained on stretched pictures, and
+what letterboxing does to its accuracy has not been measured.  fit="stretch", the default, is every call as it was.
+
 All of these start alike: `_stage` packs the batch and launches images -> records on the device's current stream, and what it returns
 (`_Batch`: the records, the pixels, the pictures' descriptors, the stream) is what a call's own stage is launched on.
 
@@ -120,6 +127,9 @@ YF_TRACK_CLIPPED, YF_TRACK_DROPPED = 1, 2      # the bits of a frame's status
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
+# where a picture lies in its letterboxed frame (yf_fit), and the two ways a picture becomes a frame
+FIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4")])
+FITS, FIT_WHAT = ("stretch", "letterbox"), "fit {!r}: 'stretch' (cv2.resize onto the frame) or 'letterbox' (the aspect kept, the rest padded)"
 GT_DTYPE = np.dtype([("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8")])
 EVAL_RESULT_DTYPE = np.dtype([("ap", "<f8"), ("detections", "<i8"), ("ground_truths", "<i8"), ("true_positives", "<i8")])
 assert GT_DTYPE.itemsize == 32 and EVAL_RESULT_DTYPE.itemsize == 32
@@ -200,6 +210,15 @@ def _entries():
         "draw_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, vp, ci, vp, ci, vp, vp, vp],
         # d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream
         "track_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
+        # letterboxed frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] pad, d_frames, d_status, stream
+        "prepare_fit_ragged_device": ragged + [ci, ci, vp, vp, vp],
+        "prepare_fit_yuv_ragged_device": ragged + [ci, ci, vp, vp, vp],
+        "prepare_fit_f16_ragged_device": ragged + [ci, vp, vp, vp],
+        "prepare_fit_yuv_f16_ragged_device": ragged + [ci, vp, vp, vp],
+        "decode_fit_ragged_device": [vp, vp, vp, cl, ci, vp, vp, ci, vp],
+        "decode_f32_fit_ragged_device": [vp, vp, vp, cl, vp, vp, ci, vp],
+        "run_decode_fit_ragged_device": [vp] + ragged + [ci, ci, vp, vp, vp, vp, ci, vp, vp],
+        "run_decode_fit_f16_ragged_device": [vp] + ragged + [ci, vp, vp, vp, vp, ci, vp, vp],
     }
 
 
@@ -234,6 +253,8 @@ def load():
     lib.yf_images_track_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
     lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
+    lib.yf_images_fit.restype = ctypes.c_int
+    lib.yf_images_fit.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.yf_images_eval_sort_tile.restype = ctypes.c_int
     lib.yf_images_eval_sort_tile.argtypes = []
     if lib.yf_images_eval_sort_tile() != EVAL_SORT_TILE:
@@ -517,6 +538,76 @@ def run_decode_f16_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images,
           d_dets, d_counts, cap, d_status, stream)
 
 
+def fit_of(h, w, size):
+    """Where a picture of h x w lies in a letterboxed frame of side `size` (yf_images_fit; host only): -> (x0, y0, width, height).  The
+    definition: csrc/yf_images_fit.h, ptq.letterbox_fit."""
+    lib, out = load(), np.zeros(1, FIT_DTYPE)
+    if lib.yf_images_fit(int(h), int(w), int(size), out.ctypes.data) != 0:
+        raise ImagesError(f"yf_images_fit: {(lib.yf_images_last_error_text() or b'').decode()}")
+    return tuple(int(out[0][k]) for k in ("x0", "y0", "width", "height"))
+
+
+def prepare_fit_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, pad=114, stream=None):
+    """Packed pictures -> letterboxed int8 frames (yf_images_prepare_fit_ragged_device): each picture resized with its aspect kept into
+    the rectangle of `fit_of`, the rest of its frame (int8)(pad - 128).  ptq.letterbox_u8."""
+    _call("prepare_fit_ragged_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "prepare_fit_ragged_device"), d_images, n, out_hw, pad,
+          d_frames, d_status, stream)
+
+
+def prepare_fit_yuv_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, pad=114, stream=None):
+    """... for NV12 / NV21 surfaces (yf_images_prepare_fit_yuv_ragged_device): d_images YUV_IMAGE_DTYPE[n]"""
+    _call("prepare_fit_yuv_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, out_hw, pad, d_frames, d_status, stream)
+
+
+def prepare_fit_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, pad=114, stream=None):
+    """... to the fp16 network's frames, fp16 [n][56][56][3] of byte / 255. (yf_images_prepare_fit_f16_ragged_device)"""
+    _call("prepare_fit_f16_ragged_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "prepare_fit_f16_ragged_device"), d_images, n, pad,
+          d_frames_f16, d_status, stream)
+
+
+def prepare_fit_yuv_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, pad=114, stream=None):
+    _call("prepare_fit_yuv_f16_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, pad, d_frames_f16, d_status, stream)
+
+
+def decode_fit_ragged_device(d_heads, d_images, n, out_hw, d_dets, d_counts, cap, d_status=None, stream=None):
+    """The decode of the heads of letterboxed frames (yf_images_decode_fit_ragged_device): d_heads int8 [n][7][7][18] (out_hw 56) or
+    [n][20][20][18] (160), d_images IMAGE_DTYPE[n] (only the sides are read) -> boxes in each picture's own pixels, mapped back through
+    its fit."""
+    _call("decode_fit_ragged_device", n, d_heads, d_images, d_status, n, out_hw, d_dets, d_counts, cap, stream)
+
+
+def decode_f32_fit_ragged_device(d_logits, d_images, n, d_dets, d_counts, cap, d_status=None, stream=None):
+    _call("decode_f32_fit_ragged_device", n, d_logits, d_images, d_status, n, d_dets, d_counts, cap, stream)
+
+
+def run_decode_fit_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_heads, d_dets, d_counts, cap, d_status,
+                                 pad=114, stream=None):
+    """Packed pictures -> letterboxed frames -> the network -> records in the pictures' pixels (yf_images_run_decode_fit_ragged_device)"""
+    _call("run_decode_fit_ragged_device", n, network.handle, d_pixels, pixels_bytes, _packed_code(fmt, "run_decode_fit_ragged_device"), d_images,
+          n, out_hw, pad, d_frames, d_heads, d_dets, d_counts, cap, d_status, stream)
+
+
+def run_decode_fit_f16_ragged_device(network, d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_logits, d_dets, d_counts, cap, d_status,
+                                     pad=114, stream=None):
+    _call("run_decode_fit_f16_ragged_device", n, network.handle, d_pixels, pixels_bytes, _packed_code(fmt, "run_decode_fit_f16_ragged_device"),
+          d_images, n, pad, d_frames_f16, d_logits, d_dets, d_counts, cap, d_status, stream)
+
+
+def _run_fit_yuv_ragged(network, d_px, nbytes, fmt, d_yuv_desc, d_desc, n, d_frames, d_heads, d_dets, d_counts, cap, d_status, size, f16, pad, s):
+    """`_run_yuv_ragged` with letterboxed frames: the YUV fit prepare, the network's device run, the fit decode of that size and dtype"""
+    if f16:
+        prepare_fit_yuv_f16_ragged_device(d_px, nbytes, fmt, d_yuv_desc, n, d_frames, d_status, pad=pad, stream=s)
+        network.fp16_run_device(d_frames, d_heads, n, stream=s)
+        decode_f32_fit_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, d_status=d_status, stream=s)
+        return
+    prepare_fit_yuv_ragged_device(d_px, nbytes, fmt, d_yuv_desc, n, size, d_frames, d_status, pad=pad, stream=s)
+    if size == 56:
+        network.run_device(d_frames, d_heads, n, stream=s)
+    else:
+        network.run_device_hw(size, size, d_frames, d_heads, n, stream=s)
+    decode_fit_ragged_device(d_heads, d_desc, n, size, d_dets, d_counts, cap, d_status=d_status, stream=s)
+
+
 def match_device(d_dets, d_counts, n, cap, d_gt, d_gt_counts, gt_cap, iou_threshold, d_tp, d_best=None, stream=None):
     """Records against their frame's ground truths (yf_images_match_device): d_dets yf_det[n][cap], d_counts int32[n], d_gt GT_DTYPE[n][gt_cap],
     d_gt_counts int32[n] -> d_tp uint8[n][cap] (1 true positive, 0 false positive) and, if given, d_best int32[n][cap] (the best ground
@@ -652,13 +743,22 @@ class _Batch:
                               + (f" (and {over.size - 1} more image(s) above it)" if over.size > 1 else ""))
 
 
-def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=None, stride=None, whole=True, out_cap=None):
+def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=None, stride=None, whole=True, out_cap=None, fit="stretch",
+           pad=114):
     """What every `detect_*` call and `evaluate` launch first, with the records left on the device -- the place to hang a new stage
     behind: packs the pictures, allocates the workspaces and runs images -> frames -> network -> records (and the suppression when
     iou_threshold is not None) at `size` and `dtype` on the device's current stream, without synchronising.  cap=None holds every candidate
     (147 / 1200).  With `tile` (and `stride`, `whole`: `plan_tiles`) the frames are the pictures' tiles, every candidate of a tile is
     held, and the tiles' records are merged per picture (`gather_tiles_device`) into out_cap slots (None: 1200) and suppressed there
-    (`nms_wide_device`); the pixels are packed once, the tiles share them."""
+    (`nms_wide_device`); the pixels are packed once, the tiles share them.  fit="stretch" resizes every frame's picture (or tile) onto the
+    whole frame, as the reference does; fit="letterbox" keeps its aspect, pads the rest of the frame with the grey `pad` and maps the boxes
+    back through the same rectangle (`prepare_fit_*`, `run_decode_fit_*`, `decode_fit_*`; with tiles, every tile and the whole-picture
+    tile is letterboxed, and a square tile is the same either way)."""
+    if fit not in FITS:
+        raise ValueError(FIT_WHAT.format(fit))
+    if not 0 <= int(pad) <= 255:
+        raise ValueError(f"pad {pad!r}: 0 to 255")
+    letterbox, pad = fit == "letterbox", int(pad)
     if tile is not None:
         out_cap = NMS_WIDE_MAX_CAP if out_cap is None else out_cap
         if not 1 <= out_cap <= NMS_WIDE_MAX_CAP:
@@ -691,9 +791,18 @@ def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=N
         run = run_decode_f16_ragged_device
     else:
         set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
-    if yuv:
+    if yuv and letterbox:
+        _run_fit_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_pictures.data_ptr(), d_desc.data_ptr(), t, d_frames.data_ptr(),
+                            d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, pad, s)
+    elif yuv:
         _run_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_pictures.data_ptr(), d_desc.data_ptr(), t, d_frames.data_ptr(),
                         d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, s)
+    elif letterbox and f16:
+        run_decode_fit_f16_ragged_device(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), t, d_frames.data_ptr(),
+                                         d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), pad=pad, stream=s)
+    elif letterbox:
+        run_decode_fit_ragged_device(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), t, size, d_frames.data_ptr(),
+                                     d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), pad=pad, stream=s)
     else:
         run(network, d_px.data_ptr(), buf.nbytes, fmt, d_desc.data_ptr(), t, d_frames.data_ptr(), d_heads.data_ptr(),
             d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), stream=s)
@@ -718,14 +827,14 @@ def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=N
 
 
 def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None,
-             tile=None, stride=None, whole=True):
+             tile=None, stride=None, whole=True, fit="stretch", pad=114):
     """Average precision of the network's boxes against labelled ones: what evaluate_model (yolov3_train_tf.py:809-869) reports, for the
     batch `detect` takes.  `ground_truths`: one [k, 4] array (x1, y1, x2, y2) per image, in that image's pixels.  The records are decoded as
     by `detect` (fmt, size, dtype as there; iou_threshold=None scores every record, a float suppresses first, as evaluate_model does),
     matched at IoU `conf_iou` (match_device) and scored (average_precision_device) on the same stream; only the 32-byte result and the
     per-image status come back.  tile=None scores the untiled records; with a tile (and `stride`, `whole`: `detect_tiled`) the records are
     those of the tiles merged per image (at most 1200 per image; more raises ImagesError).  An image (a tile) the library refused (status 1;
-    `pack_images` produces none) raises ImagesError.
+    `pack_images` produces none) raises ImagesError.  fit, pad: as in `detect` -- the tool to score both preprocessings on labelled pictures.
     Returns {"ap", "detections", "ground_truths", "true_positives", "precision", "recall"}; the last two are the end of the curve:
     true_positives / (detections + 1e-16) and true_positives / max(1, ground_truths)."""
     if tile is not None:
@@ -736,7 +845,7 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     gt, gt_counts = pack_ground_truths(ground_truths)
     if n == 0:
         return {"ap": 0.0, "detections": 0, "ground_truths": 0, "true_positives": 0, "precision": 0.0, "recall": 0.0}
-    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole)
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, fit=fit, pad=pad)
     import torch
     dev, cap, gt_cap, s = b.device, b.cap, gt.shape[1], b.stream.cuda_stream
     d_gt = torch.from_numpy(gt.view(np.float64).reshape(n, gt_cap, 4)).to(dev)
@@ -798,14 +907,14 @@ def crop_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, order="rgb", fmt="bgr", cap=None, iou_threshold=0.4, size=56,
-                 dtype="int8", device=None, tile=None, stride=None, whole=True, chips_cap=None):
+                 dtype="int8", device=None, tile=None, stride=None, whole=True, chips_cap=None, fit="stretch", pad=114):
     """`detect` (with `tile`: `detect_tiled`, whose `tile`, `stride`, `whole` these are), and every kept box cut out of its picture and
     resized to `out` = (out_h, out_w) (an int: square chips; multiples of 16 in 16..256) on the GPU, on the same stream, from the pixels
     that are already there: what a recogniser, a landmark model or a blur filter takes next.  `margin`: the box grows by this share of
     its width and height on every side (0..1, rounded to permille); `square`: the grown box is made square about its centre before it is
     clamped to the picture (it is not squared again afterwards: csrc/yf_images_crop.h, `ptq.crop_region`); `order`: the chips' byte
     order, "rgb" or "bgr".  fmt, cap, iou_threshold, size, dtype, device as in `detect` (NV12 / NV21 surfaces are cut where they lie;
-    with `tile`, cap is `detect_tiled`'s out_cap and the chips are cut from the parent pictures).
+    with `tile`, cap is `detect_tiled`'s out_cap and the chips are cut from the parent pictures; fit, pad as in `detect`).
     The chips are sized from a read-back of the counts; with chips_cap= nothing is read back before the crop, and a batch with more
     boxes raises ImagesError.
     Returns (boxes, chips, info): per image the int32 [k, 4] array `detect` returns, a uint8 [k, out_h, out_w, 3] array of its chips in
@@ -820,7 +929,7 @@ def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, orde
     import torch
     if tile is not None:
         _packed_code(fmt, "detect_chips(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, whole, out_cap=cap)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, whole, out_cap=cap, fit=fit, pad=pad)
     if chips_cap is None:
         b.stream.synchronize()
         room = int(np.clip(b.d_counts.cpu().numpy(), 0, b.cap).sum())
@@ -899,8 +1008,8 @@ def _pictures_back(b, fmt):
 
 
 def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None,
-                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None):
-    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and every kept box hidden in its picture on the GPU,
+                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box hidden in its picture on the GPU,
     on the same stream, in the pixels that are already there: mode "mosaic" pixelates the blocks of `block` x `block` pixels (4, 8, 16,
     32 or 64; the grid starts at the picture's pixel (0, 0)) that the box touches, each block to its mean; mode "fill" writes `colour`,
     (R, G, B) whatever the byte order of `fmt` -- for NV12 / NV21 surfaces (Y, U, V) -- into the box, and `block` is not used.  `margin`
@@ -922,7 +1031,7 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_redacted(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the redaction's own: the staging's status does not raise here
     redact = redact_records_yuv_device if yuv else redact_records_device
@@ -967,8 +1076,8 @@ def blur_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None, iou_threshold=0.4, size=56,
-                   dtype="int8", tile=None, stride=None, device=None):
-    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and every kept box blurred in its picture on the GPU, on
+                   dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114):
+    """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box blurred in its picture on the GPU, on
     the same stream, in the pixels that are already there: the box becomes a grid of at most `grid` x `grid` (1 to 16) means of its own
     pixels, resized back to the box -- every face gets the same number of cells, so a large face is hidden as well as a small one.
     `margin` and `square` grow the box as in `detect_chips`.  The workspace is sized for every record the batch can hold, so no box is
@@ -988,7 +1097,7 @@ def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_blurred(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
     records_cap = n * b.cap
     room = blur_workspace(records_cap, grid)
     d_work = torch.empty(room, dtype=torch.uint8, device=b.device)
@@ -1077,11 +1186,11 @@ def _track_tuples(d_out, d_info, d_out_counts, n):
              for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
 
 
-def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8"):
+def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8", fit="stretch", pad=114):
     """`detect` with the suppression for the next `steps` frames of the `tracker`'s streams, and the kept boxes associated with its track
     state on the same stream: `images` holds tracker.streams * steps pictures, frame t of stream s at index t * streams + s (layout
     "time": one frame of every camera per step) or s * steps + t ("stream": a clip per stream).  fmt, iou_threshold (not None: the tracker
-    takes a frame's records in descending confidence), size, dtype as in `detect`; the tracker's device is used.
+    takes a frame's records in descending confidence), size, dtype, fit, pad as in `detect`; the tracker's device is used.
     Returns per frame a list of (id, x1, y1, x2, y2, conf, hits, misses) in ascending id: the tracks reported for that frame, a held-over
     one (misses > 0) with the box it was last seen at.  The tracker carries on from there at the next call.  The definition is the
     library's own: csrc/yf_images_track.h, restated as `ptq.track_step`."""
@@ -1094,7 +1203,7 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
     n = len(images)
     if n == 0:
         return []
-    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype)
+    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype, fit=fit, pad=pad)
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
     b.stream.synchronize()
     return _track_tuples(d_out, d_info, d_out_counts, n)
@@ -1139,13 +1248,13 @@ def draw_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=None, iou_threshold=0.4, size=56, dtype="int8", tile=None,
-                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None):
+                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None, fit="stretch", pad=114):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and the outline of every kept box drawn into its picture
     on the GPU, on the same stream, in the pixels that are already there -- the last line of the reference's scripts,
     cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2), which the defaults reproduce: `colour` (R, G, B) whatever the byte order of
     `fmt` (for NV12 / NV21 surfaces (Y, U, V)), red; `half` = 1, the band of three pixels that thickness 2 is read to draw (half 0..3:
     csrc/yf_images_draw.h; the reading of OpenCV's thickness 2 is not pinned against a real cv2).  fmt, cap, iou_threshold, size, dtype,
-    device as in `detect`.
+    device, fit, pad as in `detect`.
     With `tracker` (a `Tracker`; then `images` are its next `steps` frames in `layout`, as `detect_tracked` takes them; steps=None: as
     many as the images make; iou_threshold must not be None and the tracker's device is used) the tracker is updated with the kept boxes
     and the REPORTED TRACKS are drawn, held-over ones included, each in palette[id % len(palette)]: a face keeps its colour over the
@@ -1175,7 +1284,7 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_drawn(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the drawing's own: the staging's status does not raise here
     draw = draw_records_yuv_device if yuv else draw_records_device
@@ -1201,25 +1310,27 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
     return pictures, _track_tuples(d_out, d_info, d_out_counts, n)
 
 
-def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8"):
+def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8",
+                 fit="stretch", pad=114):
     """`detect` for pictures larger than the faces in them: every image is cut into tiles (`plan_tiles`: `tile`, `stride` an int or (y, x),
     stride=None no overlap; `whole` adds the whole image as a tile of its own), every tile is one frame of the network at `size` and `dtype`
     (as in `detect`), and the tiles' records are merged per image on the GPU, translated to the image's own pixels (`gather_tiles_device`)
     and suppressed across the tile borders, where overlapping tiles report one face twice (`nms_wide_device`, in place) -- all on one
     stream.  Returns one int32 [k, 4] array (x1, y1, x2, y2) per image: with iou_threshold=None the merged records in tile order, each
     tile's in decode order; with a float the kept ones in keep order.  out_cap: the merged records an image can hold (at most 1200); an
-    image with more raises ImagesError naming the image and its total."""
+    image with more raises ImagesError naming the image and its total.  fit="letterbox" (and pad): every tile, and the whole-image tile, keeps
+    its aspect in its frame, as in `detect`; a square tile is the same frame either way."""
     _packed_code(fmt, "detect_tiled")
     n = len(images)
     if n == 0:
         return []
-    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, out_cap)
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, out_cap, fit=fit, pad=pad)
     b.stream.synchronize()
     b.check_totals("detect_tiled")
     return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))
 
 
-def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8"):
+def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8", fit="stretch", pad=114):
     """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
     tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
     of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network.  iou_threshold=None returns every record above the
@@ -1231,10 +1342,17 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     `fp16_run_device`: detect does not do it.  The fp16 network exists at 56 only.
     fmt="nv12" / "nv21": `images` are surfaces as `pack_yuv_images` takes them; the sequence is the YUV prepare, the network's device run
     and the ragged decode of that size and dtype, on one stream, and the boxes are in the Y plane's pixels -- those of
-    cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12) under fmt="bgr"."""
+    cv2.cvtColor(yuv, cv2.COLOR_YUV2BGR_NV12) under fmt="bgr".
+    fit="stretch": every picture is resized onto the whole frame, as the reference does.  fit="letterbox": its aspect is kept, the rest
+    of the frame is the grey `pad` (0..255; the trainers' 114), and the boxes are mapped back through the same rectangle
+    (`run_decode_fit_ragged_device`; the definition: csrc/yf_images_fit.h, `ptq.letterbox_u8`) -- what a model trained by a letterboxing
+    trainer expects.  The shipped model was trained on stretched pictures; what letterboxing does to its accuracy has not been measured
+    (`evaluate` scores either on labelled pictures).  Any other `fit` raises ValueError."""
     _check_frames(size, dtype)                          # before the empty batch is returned, and before torch, the network or the library
+    if fit not in FITS:
+        raise ValueError(FIT_WHAT.format(fit))
     if len(images) == 0:
         return []
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, fit=fit, pad=pad)
     b.stream.synchronize()
     return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))

@@ -340,6 +340,35 @@ def resize_linear_u8(img, out_w, out_h):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+def letterbox_fit(h, w, size):
+    """Where a picture of `h` x `w` lies in a letterboxed frame of side `size`, as csrc/yf_images_fit.h states it, in Python integers:
+    -> (x0, y0, width, height).  The longer side becomes `size`, the other one the exact ratio rounded HALF UP (at least 1):
+    (2 * h * size + w) // (2 * w) for w >= h; the rectangle is centred with the odd pixel of padding right and bottom (floor), as
+    ultralytics' LetterBox centres it.  The rounding is the library's choice: Python's `round` differs from it at exact halves only,
+    where it rounds to even."""
+    h, w, size = int(h), int(w), int(size)
+    fw = fh = size
+    if w > h:
+        fh = max(1, (2 * h * size + w) // (2 * w))
+    elif h > w:
+        fw = max(1, (2 * w * size + h) // (2 * h))
+    return (size - fw) // 2, (size - fh) // 2, fw, fh
+
+
+def letterbox_u8(img_hwc, size, pad=114):
+    """The letterboxed frame of a uint8 picture [H, W, C]: `resize_linear_u8` to the rectangle of `letterbox_fit`, the rest of the
+    [size, size, C] frame filled with `pad` (0..255; the trainers' grey is 114) in every channel -> uint8 [size, size, C]."""
+    src = np.asarray(img_hwc, np.uint8)
+    if src.ndim != 3:
+        raise ValueError(f"expected uint8 [H, W, C], got {src.shape}")
+    if not 0 <= int(pad) <= 255:
+        raise ValueError(f"pad {pad!r}: 0 to 255")
+    x0, y0, fw, fh = letterbox_fit(src.shape[0], src.shape[1], size)
+    out = np.full((int(size), int(size), src.shape[2]), int(pad), np.uint8)
+    out[y0:y0 + fh, x0:x0 + fw] = resize_linear_u8(src, fw, fh)
+    return out
+
+
 def yuv420sp_to_rgb_u8(y, uv, v_first=False):
     """OpenCV's `cv2.cvtColor(yuv, cv2.COLOR_YUV2RGB_NV12)` (v_first: `_NV21`) for a 4:2:0 semi-planar surface, restated from the published
     algorithm (imgproc/src/color_yuv.simd.hpp, YUV420sp -> RGB: BT.601 limited range in 20-bit fixed point) and, like `resize_linear_u8`,
