@@ -572,6 +572,47 @@ YF_API long yf_images_run_decode_fit_f16_ragged_device(ai_handle net, const void
                                                        const yf_image* d_images, long n, int pad, void* d_frames_f16, void* d_logits,
                                                        void* d_dets, void* d_counts, int cap, int32_t* d_status, void* stream);
 
+/* ---- area-averaged frames: every source pixel counted.  The resize of every entry above is cv2.resize's INTER_LINEAR, which reads four
+ * source pixels per output pixel whatever the reduction; a 1920 x 1080 picture reduced to 56 x 56 then shows the network 12 544 of its
+ * 2 073 600 pixels, and fine texture aliases into the frame.  These entries write the same frames with the exact area average instead.
+ * LINEAR STAYS THE DEFAULT: THE SHIPPED MODEL WAS TRAINED ON LINEARLY RESIZED PICTURES and no effect of the filter on its accuracy has
+ * been measured; a model calibrated (yf_calib) or trained on area-averaged frames wants them at inference too -- the same filter in
+ * both places.  The definition is this library's own, integers only, stated once in csrc/yf_images_area.h, which the
+ * kernels, a host build and a sanitizer program share:
+ *   axis:   n_in source and n_out output positions on the grid of n_in n_out sub-positions; a(d, s) = the length of the overlap of
+ *           [d n_in, (d + 1) n_in) and [s n_out, (s + 1) n_out), an integer; the a(d, .) sum to n_in.  Any ratio: reduction, enlargement,
+ *           identity.
+ *   pixel:  S = sum of ay(y, sy) ax(x, sx) p[sy][sx], v = (2 S + H W) / (2 H W) in 64-bit integer division: the exact average, rounded
+ *           half up.  No floats, no rounded weight tables: the result does not depend on the order of addition.
+ *   frame:  (int8)(v - 128), or fp16(v / 255.); RGB order, the alpha byte never read.  NV12 / NV21: every source pixel converted first (the
+ *           arithmetic of the plain YUV prepare), then averaged.
+ *   fit:    YF_FIT_STRETCH: the picture onto the whole frame.  YF_FIT_LETTERBOX: onto the rectangle of yf_images_fit, the rest of the frame
+ *           (int8)(pad - 128) (fp16 of pad / 255.); a square picture has the same bytes either way.  pad is checked always and read only
+ *           when letterboxed.  The decodes do not change: boxes map back through the fit, not through the filter -- the plain ragged
+ *           decodes for YF_FIT_STRETCH, yf_images_decode_fit_ragged_device / yf_images_decode_f32_fit_ragged_device for YF_FIT_LETTERBOX.
+ *   cv2:    for integer ratios v is the rounded block mean, INTER_AREA's integer path (at exactly 2x (a + b + c + d + 2) >> 2, the linear
+ *           prepare's bytes); for other ratios OpenCV accumulates float weights and this is the exact value they approximate.  Not
+ *           pinned against a real cv2.
+ * The batches are ragged only (a uniform batch is descriptors of one size) and there are no run_* forms: the frames are the interface, as
+ * for NV12 / NV21.  The work grows with the source pictures, not with the frames: a frame is split into bands of whole output rows, one
+ * job per (frame, band), yf_images_area_bands(n, out_hw) bands per frame -- from n and out_hw alone, the sizes live in device memory --
+ * and the frames do not depend on the split.  d_status[i] = 1 for an invalid descriptor: its frame is all -128 (fp16: zeros) and its
+ * picture is never read.  No load touches a byte outside a picture's own extent: 16-byte loads lie wholly inside a row's width * C bytes,
+ * unaligned heads and tails are read byte by byte, and no alignment is asked of offsets or strides.  Asynchronous on `stream`, no
+ * allocation, no host synchronisation, capturable.  Every argument is checked before the first launch -- each entry refuses the other
+ * family's formats, an out_hw other than 56 or 160, a fit other than the two, pad outside [0, 255], NULL or misaligned pointers as the
+ * letterbox entries do -- and n = 0 launches nothing after the checks.  Return n, or 0 and a text. */
+enum { YF_FIT_STRETCH = 0, YF_FIT_LETTERBOX = 1 };
+YF_API int  yf_images_area_bands(long n, int out_hw);          /* bands per frame of a batch of n; 0 for n < 0 or another out_hw */
+YF_API long yf_images_prepare_area_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                 int out_hw, int fit, int pad, void* d_frames, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_area_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                     long n, int out_hw, int fit, int pad, void* d_frames, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_area_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                     int fit, int pad, void* d_frames_f16, int32_t* d_status, void* stream);
+YF_API long yf_images_prepare_area_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                         long n, int fit, int pad, void* d_frames_f16, int32_t* d_status, void* stream);
+
 YF_API const char* yf_images_last_error_text(void);
 /* sha256 prefix over the library's sources and flags (csrc/Makefile IMAGES_SRCS), checked by images.py before it loads an existing file */
 YF_API const char* yf_images_build_id(void);

@@ -20,7 +20,8 @@
 // yf_images_blur.h and yf_images_blur.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
 // yf_images_track.h and yf_images_track.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
-// boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h.
+// boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h; the area-averaged frames (every source pixel counted, a job per band
+// of a frame) in yf_images_area.h and yf_images_area.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
 // launches, one body behind each uniform / ragged pair of run_decode entries, and the C entry points.
 #include <hip/hip_runtime.h>
@@ -46,6 +47,7 @@
 #include "yf_images_draw.hip.h"
 #include "yf_images_track.hip.h"
 #include "yf_images_fit.hip.h"
+#include "yf_images_area.hip.h"
 
 #ifndef YF_IMAGES_BUILD_ID
 #define YF_IMAGES_BUILD_ID "unknown"
@@ -982,6 +984,25 @@ long fit_decode_f32(const void* d_logits, const yf_image* d_images, const int32_
   return launched("decode_f32_fit kernel launch", n);
 }
 
+// ---- area-averaged frames (yf_images_area.h) ----  the kernels by format code, for a frame side and an element type
+using AreaKernel = void (*)(yfarea::Args);
+template <int OUT, typename T>
+constexpr AreaKernel kArea[6] = {yfarea::area_kernel<OUT, 0, T>, yfarea::area_kernel<OUT, 1, T>, yfarea::area_kernel<OUT, 2, T>,
+                                 yfarea::area_kernel<OUT, 3, T>, yfarea::area_kernel<OUT, 4, T>, yfarea::area_kernel<OUT, 5, T>};
+
+// the four entries: every argument (yfi_area_check_prepare), then one launch of n * bands jobs.  yuv: the entry's family; f16: fp16 frames
+long area_prepare(bool yuv, bool f16, const void* d_pixels, size_t pixels_bytes, int format, const void* d_images, long n, int out_hw, int fit,
+                  int pad, void* d_frames, int32_t* d_status, hipStream_t s) {
+  const char* err = yfi_area_check_prepare(yuv, f16, d_pixels, format, d_images, n, out_hw, fit, pad, d_frames, d_status);
+  if (err) return fail("%s", err);
+  if (n == 0) return 0;
+  const AreaKernel* k = f16 ? kArea<56, uint16_t> : (out_hw == 56 ? kArea<56, int8_t> : kArea<160, int8_t>);
+  const int bands = yfi_area_bands(n, out_hw);
+  const yfarea::Args a{(const uint8_t*)d_pixels, (uint64_t)pixels_bytes, d_images, d_status, n, d_frames, pad, fit, bands};
+  hipLaunchKernelGGL(k[format], grid_for(n * bands, yfarea::per_cu_of(out_hw)), dim3(yfarea::threads_of(out_hw)), 0, s, a);     // 32 waves per CU
+  return launched("prepare_area kernel launch", n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1427,6 +1448,32 @@ YF_API long yf_images_run_decode_fit_f16_ragged_device(ai_handle net, const void
   if (fit_prepare(false, true, d_pixels, pixels_bytes, format, d_images, n, 56, pad, d_frames_f16, d_status, s) != n) return 0;
   if (yf_network_fp16_run_device(net, d_frames_f16, d_logits, n, stream) != n) return network_failed(net, "yf_network_fp16_run_device");
   return fit_decode_f32(d_logits, d_images, d_status, n, d_dets, d_counts, cap, s);
+}
+
+// ---- area-averaged frames ----
+YF_API int yf_images_area_bands(long n, int out_hw) {
+  if (n < 0 || (out_hw != 56 && out_hw != 160)) return 0;
+  return yfi_area_bands(n, out_hw);
+}
+
+YF_API long yf_images_prepare_area_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                 int out_hw, int fit, int pad, void* d_frames, int32_t* d_status, void* stream) {
+  return area_prepare(false, false, d_pixels, pixels_bytes, format, d_images, n, out_hw, fit, pad, d_frames, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_area_yuv_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                     long n, int out_hw, int fit, int pad, void* d_frames, int32_t* d_status, void* stream) {
+  return area_prepare(true, false, d_pixels, pixels_bytes, format, d_images, n, out_hw, fit, pad, d_frames, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_area_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images, long n,
+                                                     int fit, int pad, void* d_frames_f16, int32_t* d_status, void* stream) {
+  return area_prepare(false, true, d_pixels, pixels_bytes, format, d_images, n, 56, fit, pad, d_frames_f16, d_status, (hipStream_t)stream);
+}
+
+YF_API long yf_images_prepare_area_yuv_f16_ragged_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                         long n, int fit, int pad, void* d_frames_f16, int32_t* d_status, void* stream) {
+  return area_prepare(true, true, d_pixels, pixels_bytes, format, d_images, n, 56, fit, pad, d_frames_f16, d_status, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h and the letterboxed frames and decodes of yf_images_fit.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -20,6 +20,7 @@
 #include "yf_images_draw.h"
 #include "yf_images_track.h"
 #include "yf_images_fit.h"
+#include "yf_images_area.h"
 #include "gen/yf_decode_tables_gen.h"
 
 #define EXPORT __attribute__((visibility("default")))
@@ -941,6 +942,128 @@ EXPORT int yfi_fit_check_host(int what, int yuv, int f16, const void* a, int for
                               const void* frames_or_dets, const void* status, const void* counts, int cap, char* out, int out_bytes) {
   const char* t = what == 0 ? yfi_fit_check_prepare(yuv, f16, a, format, images, n, out_hw, pad, frames_or_dets, status)
                             : yfi_fit_check_decode(f16, a, images, status, n, out_hw, frames_or_dets, counts, cap);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+/* ---- yf_images_area.h ----  out[0] = a(d, s) on an axis of n_in sources and n_out outputs, out[1], out[2] = the first and the last
+ * source of d (no range check: the tests ask for what the definition gives) */
+EXPORT void yfi_area_weight_host(int32_t d, int32_t s, int32_t n_in, int32_t n_out, int32_t* out) {
+  out[0] = yfi_area_weight(d, s, n_in, n_out);
+  out[1] = yfi_area_first(d, n_in, n_out);
+  out[2] = yfi_area_last(d, n_in, n_out);
+}
+
+/* a whole axis: for every d in [0, n_out) its first and last source and the sum of a(d, s) over them, through yfi_area_span_of and
+ * yfi_area_span_weight as the kernels take them; returns the number of d whose neighbours outside the span (first - 1, last + 1) do
+ * not weigh 0, or whose span disagrees with yfi_area_weight */
+EXPORT int yfi_area_axis_host(int32_t n_in, int32_t n_out, int32_t* firsts, int32_t* lasts, int64_t* sums) {
+  int bad = 0;
+  for (int32_t d = 0; d < n_out; ++d) {
+    const yfi_area_span a = yfi_area_span_of(d, n_in, n_out);
+    int64_t sum = 0;
+    for (int32_t s = a.first; s <= a.last; ++s) {
+      sum += yfi_area_span_weight(a, s);
+      bad += yfi_area_span_weight(a, s) != yfi_area_weight(d, s, n_in, n_out);
+    }
+    bad += a.first > 0 && yfi_area_weight(d, a.first - 1, n_in, n_out) != 0;
+    bad += a.last + 1 < n_in && yfi_area_weight(d, a.last + 1, n_in, n_out) != 0;
+    firsts[d] = a.first; lasts[d] = a.last; sums[d] = sum;
+  }
+  return bad;
+}
+
+EXPORT int yfi_area_bands_host(long n, int out_hw) { return yfi_area_bands(n, out_hw); }
+EXPORT int yfi_area_band_row_host(int b, int bands, int out_hw) { return yfi_area_band_row(b, bands, out_hw); }
+
+/* The frame of one picture whose pixel (sy, sx) has the RGB bytes `pixel` gives: output pixel by output pixel, source row by source
+ * row, the definition as it is written -- nothing of the kernel's staging. */
+typedef void (*area_pixel_fn)(const void* ctx, int sy, int sx, int32_t rgb[3]);
+
+static void area_frame(const void* ctx, area_pixel_fn pixel, int h, int w, int out_hw, int fit, int pad, int f16, void* frame) {
+  const yf_fit r = yfi_area_rect(h, w, out_hw, fit);
+  const uint64_t D = (uint64_t)h * (uint64_t)w;
+  for (int y = 0; y < out_hw; ++y) {
+    for (int x = 0; x < out_hw; ++x) {
+      const size_t at = ((size_t)y * out_hw + x) * 3;
+      if (y < r.y0 || y >= r.y0 + r.height || x < r.x0 || x >= r.x0 + r.width) {
+        for (int c = 0; c < 3; ++c) fit_store(frame, at + c, f16, pad);
+        continue;
+      }
+      const int dy = y - r.y0, dx = x - r.x0;
+      uint64_t S[3] = {0, 0, 0};
+      for (int sy = yfi_area_first(dy, h, r.height); sy <= yfi_area_last(dy, h, r.height); ++sy) {
+        uint32_t row[3] = {0, 0, 0};
+        for (int sx = yfi_area_first(dx, w, r.width); sx <= yfi_area_last(dx, w, r.width); ++sx) {
+          int32_t rgb[3];
+          pixel(ctx, sy, sx, rgb);
+          const uint32_t ax = (uint32_t)yfi_area_weight(dx, sx, w, r.width);
+          for (int c = 0; c < 3; ++c) row[c] += ax * (uint32_t)rgb[c];
+        }
+        const uint64_t ay = (uint64_t)yfi_area_weight(dy, sy, h, r.height);
+        for (int c = 0; c < 3; ++c) S[c] += ay * row[c];
+      }
+      for (int c = 0; c < 3; ++c) fit_store(frame, at + c, f16, yfi_area_round(S[c], D));
+    }
+  }
+}
+
+typedef struct area_packed { const uint8_t* px; int64_t rs; int C, bgr; } area_packed;
+static void area_packed_pixel(const void* ctx, int sy, int sx, int32_t rgb[3]) {
+  const area_packed* p = (const area_packed*)ctx;
+  const uint8_t* s = p->px + (uint64_t)sy * (uint64_t)p->rs + (size_t)sx * p->C;
+  for (int c = 0; c < 3; ++c) rgb[c] = s[p->bgr ? 2 - c : c];
+}
+
+typedef struct area_planes { const uint8_t* y; const uint8_t* uv; int64_t sy, suv; int v_first; } area_planes;
+static void area_planes_pixel(const void* ctx, int sy, int sx, int32_t rgb[3]) {
+  const area_planes* p = (const area_planes*)ctx;
+  const int32_t yy = yfi_yuv_luma(p->y[(uint64_t)sy * (uint64_t)p->sy + sx]);
+  const yfi_chroma k = yfi_yuv_pair(p->uv + (uint64_t)(sy >> 1) * (uint64_t)p->suv + (sx >> 1) * 2, p->v_first);
+  rgb[0] = yfi_yuv_channel(yy, k.r); rgb[1] = yfi_yuv_channel(yy, k.g); rgb[2] = yfi_yuv_channel(yy, k.b);
+}
+
+static int area_args_ok(int out_hw, int fit, int pad, int f16) {
+  return (out_hw == 56 || (!f16 && out_hw == 160)) && (fit == YF_FIT_STRETCH || fit == YF_FIT_LETTERBOX) && pad >= 0 && pad <= 255;
+}
+
+/* One packed picture as yfarea::area_kernel takes it: `base` + the descriptor's offset, checked against `bytes` -> frame
+ * int8[out_hw][out_hw][3] (f16 == 0) or the fp16 bits uint16[56][56][3].  Returns the status the kernel writes: 0, or 1 for an invalid
+ * descriptor, whose frame is all -128 (fp16: all 0) and which is never read.  -1: the format is not a packed one, out_hw is not 56 or 160
+ * (fp16: not 56), fit is not one of the two, or pad is outside [0, 255]. */
+EXPORT int yfi_prepare_area_host(const uint8_t* base, uint64_t bytes, int format, const yf_image* im, int out_hw, int fit, int pad, int f16,
+                                 void* frame) {
+  const int C = yfi_tiles_channels(format);
+  if (!C || !area_args_ok(out_hw, fit, pad, f16)) return -1;
+  const size_t count = (size_t)out_hw * (size_t)out_hw * 3;
+  if (!yfi_image_ok(im->offset, im->height, im->width, im->row_stride, C, bytes)) {
+    if (f16) memset(frame, 0, count * 2); else memset(frame, 0x80, count);
+    return 1;
+  }
+  const area_packed p = {base + im->offset, im->row_stride, C, format == YF_PIX_BGR8 || format == YF_PIX_BGRA8};
+  area_frame(&p, area_packed_pixel, im->height, im->width, out_hw, fit, pad, f16, frame);
+  return 0;
+}
+
+/* ... and one NV12 / NV21 surface: every source pixel converted, then averaged */
+EXPORT int yfi_prepare_area_yuv_host(const uint8_t* base, uint64_t bytes, const yf_image_yuv* im, int v_first, int out_hw, int fit, int pad,
+                                     int f16, void* frame) {
+  if (!area_args_ok(out_hw, fit, pad, f16)) return -1;
+  const size_t count = (size_t)out_hw * (size_t)out_hw * 3;
+  if (!yfi_yuv_image_ok(im->offset_y, im->offset_uv, im->height, im->width, im->stride_y, im->stride_uv, bytes)) {
+    if (f16) memset(frame, 0, count * 2); else memset(frame, 0x80, count);
+    return 1;
+  }
+  const area_planes p = {base + im->offset_y, base + im->offset_uv, im->stride_y, im->stride_uv, v_first};
+  area_frame(&p, area_planes_pixel, im->height, im->width, out_hw, fit, pad, f16, frame);
+  return 0;
+}
+
+/* the argument checks alone, as the entry points make them: the text of the first fault into out (at most out_bytes, 0-terminated), or
+ * an empty text; returns 1 for a fault */
+EXPORT int yfi_area_check_host(int yuv, int f16, const void* pixels, int format, const void* images, long n, int out_hw, int fit, int pad,
+                               const void* frames, const void* status, char* out, int out_bytes) {
+  const char* t = yfi_area_check_prepare(yuv, f16, pixels, format, images, n, out_hw, fit, pad, frames, status);
   if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
   return t != NULL;
 }

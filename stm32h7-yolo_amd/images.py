@@ -50,6 +50,14 @@ grey `pad`, and the boxes mapped back through the same rectangle -- `prepare_fit
 `ptq.letterbox_u8`).  It is for retrained models and their calibration frames: the shipped model was trained on stretched pictures, and
 what letterboxing does to its accuracy has not been measured.  fit="stretch", the default, is every call as it was.
 
+`interp="area"` on the same calls replaces the filter of that resize: cv2.resize's INTER_LINEAR reads four source pixels per output pixel
+whatever the reduction (12 544 of the 2 073 600 pixels of a 1920 x 1080 picture reach a 56 x 56 frame, and fine texture aliases), the area
+average counts every source pixel with the share of it an output pixel covers, exactly, in integers -- `prepare_area_*`, `area_bands`; the
+definition is the library's own (csrc/yf_images_area.h, `ptq.resize_area_u8`).  It combines with either fit, both sizes, both dtypes,
+packed pictures, NV12 / NV21 surfaces and tiles.  The shipped model was trained on linearly resized pictures and what the filter does to
+its accuracy has not been measured; calibration frames must be made with the filter the deployed pipeline uses.  interp="linear", the
+default, is every call as it was.
+
 All of these start alike: `_stage` packs the batch and launches images -> records on the device's current stream, and what it returns
 (`_Batch`: the records, the pixels, the pictures' descriptors, the stream) is what a call's own stage is launched on.
 
@@ -130,6 +138,9 @@ YF_TRACK_CLIPPED, YF_TRACK_DROPPED = 1, 2      # the bits of a frame's status
 # where a picture lies in its letterboxed frame (yf_fit), and the two ways a picture becomes a frame
 FIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4")])
 FITS, FIT_WHAT = ("stretch", "letterbox"), "fit {!r}: 'stretch' (cv2.resize onto the frame) or 'letterbox' (the aspect kept, the rest padded)"
+# the filter of the resize: cv2.resize's INTER_LINEAR (four source pixels per output pixel), or the exact area average of every source pixel
+INTERPS, INTERP_WHAT = ("linear", "area"), "interp {!r}: 'linear' (cv2.resize's INTER_LINEAR) or 'area' (every source pixel averaged)"
+YF_FIT_STRETCH, YF_FIT_LETTERBOX = 0, 1
 GT_DTYPE = np.dtype([("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8")])
 EVAL_RESULT_DTYPE = np.dtype([("ap", "<f8"), ("detections", "<i8"), ("ground_truths", "<i8"), ("true_positives", "<i8")])
 assert GT_DTYPE.itemsize == 32 and EVAL_RESULT_DTYPE.itemsize == 32
@@ -219,6 +230,11 @@ def _entries():
         "decode_f32_fit_ragged_device": [vp, vp, vp, cl, vp, vp, ci, vp],
         "run_decode_fit_ragged_device": [vp] + ragged + [ci, ci, vp, vp, vp, vp, ci, vp, vp],
         "run_decode_fit_f16_ragged_device": [vp] + ragged + [ci, vp, vp, vp, vp, ci, vp, vp],
+        # area-averaged frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] fit, pad, d_frames, d_status, stream
+        "prepare_area_ragged_device": ragged + [ci, ci, ci, vp, vp, vp],
+        "prepare_area_yuv_ragged_device": ragged + [ci, ci, ci, vp, vp, vp],
+        "prepare_area_f16_ragged_device": ragged + [ci, ci, vp, vp, vp],
+        "prepare_area_yuv_f16_ragged_device": ragged + [ci, ci, vp, vp, vp],
     }
 
 
@@ -255,6 +271,8 @@ def load():
     lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
     lib.yf_images_fit.restype = ctypes.c_int
     lib.yf_images_fit.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.yf_images_area_bands.restype = ctypes.c_int
+    lib.yf_images_area_bands.argtypes = [ctypes.c_long, ctypes.c_int]
     lib.yf_images_eval_sort_tile.restype = ctypes.c_int
     lib.yf_images_eval_sort_tile.argtypes = []
     if lib.yf_images_eval_sort_tile() != EVAL_SORT_TILE:
@@ -608,6 +626,72 @@ def _run_fit_yuv_ragged(network, d_px, nbytes, fmt, d_yuv_desc, d_desc, n, d_fra
     decode_fit_ragged_device(d_heads, d_desc, n, size, d_dets, d_counts, cap, d_status=d_status, stream=s)
 
 
+def _fit_code(fit):
+    if fit not in FITS:
+        raise ValueError(FIT_WHAT.format(fit))
+    return FITS.index(fit)
+
+
+def area_bands(n, out_hw):
+    """How many bands of output rows the area prepare splits each frame of a batch of n into (yf_images_area_bands; host only): one job
+    per (frame, band), from n and out_hw alone.  The frames do not depend on it."""
+    bands = int(load().yf_images_area_bands(int(n), int(out_hw)))
+    if bands < 1:
+        raise ImagesError(f"yf_images_area_bands({n}, {out_hw}): n >= 0 and out_hw 56 or 160")
+    return bands
+
+
+def prepare_area_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, fit="stretch", pad=114, stream=None):
+    """Packed pictures -> area-averaged int8 frames (yf_images_prepare_area_ragged_device): every source pixel counted with the share of it
+    an output pixel covers, rounded half up -- `ptq.resize_area_u8`; fit="letterbox": resized so to the rectangle of `fit_of`, the rest of
+    the frame (int8)(pad - 128) -- `ptq.letterbox_u8(..., interp="area")`.  The definition: csrc/yf_images_area.h."""
+    _call("prepare_area_ragged_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "prepare_area_ragged_device"), d_images, n, out_hw,
+          _fit_code(fit), pad, d_frames, d_status, stream)
+
+
+def prepare_area_yuv_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, out_hw, d_frames, d_status, fit="stretch", pad=114, stream=None):
+    """... for NV12 / NV21 surfaces (yf_images_prepare_area_yuv_ragged_device): d_images YUV_IMAGE_DTYPE[n]; every pixel converted, then averaged"""
+    _call("prepare_area_yuv_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, out_hw, _fit_code(fit), pad, d_frames,
+          d_status, stream)
+
+
+def prepare_area_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, fit="stretch", pad=114, stream=None):
+    """... to the fp16 network's frames, fp16 [n][56][56][3] of byte / 255. (yf_images_prepare_area_f16_ragged_device)"""
+    _call("prepare_area_f16_ragged_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "prepare_area_f16_ragged_device"), d_images, n,
+          _fit_code(fit), pad, d_frames_f16, d_status, stream)
+
+
+def prepare_area_yuv_f16_ragged_device(d_pixels, pixels_bytes, fmt, d_images, n, d_frames_f16, d_status, fit="stretch", pad=114, stream=None):
+    _call("prepare_area_yuv_f16_ragged_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, n, _fit_code(fit), pad, d_frames_f16,
+          d_status, stream)
+
+
+def _run_area_ragged(network, d_px, nbytes, fmt, d_pictures, d_desc, n, d_frames, d_heads, d_dets, d_counts, cap, d_status, size, f16, fit, pad, s):
+    """interp="area" of `_stage`, composed on stream `s` as `_run_yuv_ragged` and `_run_fit_yuv_ragged` compose theirs: the area prepare of
+    the family and dtype (d_pictures: the descriptors it takes), the network's device run, and the decode that exists for the fit -- the
+    plain ragged one for "stretch", the fit one for "letterbox" -- with the descriptors of the frames' sizes (d_desc, IMAGE_DTYPE)."""
+    letterbox = fit == "letterbox"
+    if f16:
+        prepare = prepare_area_yuv_f16_ragged_device if is_yuv(fmt) else prepare_area_f16_ragged_device
+        prepare(d_px, nbytes, fmt, d_pictures, n, d_frames, d_status, fit=fit, pad=pad, stream=s)
+        network.fp16_run_device(d_frames, d_heads, n, stream=s)
+        decode = decode_f32_fit_ragged_device if letterbox else decode_f32_ragged_device
+        decode(d_heads, d_desc, n, d_dets, d_counts, cap, d_status=d_status, stream=s)
+        return
+    prepare = prepare_area_yuv_ragged_device if is_yuv(fmt) else prepare_area_ragged_device
+    prepare(d_px, nbytes, fmt, d_pictures, n, size, d_frames, d_status, fit=fit, pad=pad, stream=s)
+    if size == 56:
+        network.run_device(d_frames, d_heads, n, stream=s)
+    else:
+        network.run_device_hw(size, size, d_frames, d_heads, n, stream=s)
+    if letterbox:
+        decode_fit_ragged_device(d_heads, d_desc, n, size, d_dets, d_counts, cap, d_status=d_status, stream=s)
+    elif size == 56:
+        decode_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, stream=s)
+    else:
+        decode160_ragged_device(d_heads, d_desc, n, d_dets, d_counts, cap, d_status=d_status, stream=s)
+
+
 def match_device(d_dets, d_counts, n, cap, d_gt, d_gt_counts, gt_cap, iou_threshold, d_tp, d_best=None, stream=None):
     """Records against their frame's ground truths (yf_images_match_device): d_dets yf_det[n][cap], d_counts int32[n], d_gt GT_DTYPE[n][gt_cap],
     d_gt_counts int32[n] -> d_tp uint8[n][cap] (1 true positive, 0 false positive) and, if given, d_best int32[n][cap] (the best ground
@@ -744,7 +828,7 @@ class _Batch:
 
 
 def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=None, stride=None, whole=True, out_cap=None, fit="stretch",
-           pad=114):
+           pad=114, interp="linear"):
     """What every `detect_*` call and `evaluate` launch first, with the records left on the device -- the place to hang a new stage
     behind: packs the pictures, allocates the workspaces and runs images -> frames -> network -> records (and the suppression when
     iou_threshold is not None) at `size` and `dtype` on the device's current stream, without synchronising.  cap=None holds every candidate
@@ -753,9 +837,13 @@ def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=N
     (`nms_wide_device`); the pixels are packed once, the tiles share them.  fit="stretch" resizes every frame's picture (or tile) onto the
     whole frame, as the reference does; fit="letterbox" keeps its aspect, pads the rest of the frame with the grey `pad` and maps the boxes
     back through the same rectangle (`prepare_fit_*`, `run_decode_fit_*`, `decode_fit_*`; with tiles, every tile and the whole-picture
-    tile is letterboxed, and a square tile is the same either way)."""
+    tile is letterboxed, and a square tile is the same either way).  interp="linear" resizes as cv2.resize's INTER_LINEAR does, every
+    launch as it was; interp="area" averages every source pixel of the picture (or tile) instead (`prepare_area_*`, then the network
+    and the decode of the fit, `_run_area_ragged`; a tile is a descriptor into its parent's pixels, so tiles need nothing of their own)."""
     if fit not in FITS:
         raise ValueError(FIT_WHAT.format(fit))
+    if interp not in INTERPS:
+        raise ValueError(INTERP_WHAT.format(interp))
     if not 0 <= int(pad) <= 255:
         raise ValueError(f"pad {pad!r}: 0 to 255")
     letterbox, pad = fit == "letterbox", int(pad)
@@ -791,7 +879,11 @@ def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=N
         run = run_decode_f16_ragged_device
     else:
         set_decode_tables(*network.decode_tables())     # a model file may bring its own; a later decode of these heads without the network finds them
-    if yuv and letterbox:
+    if interp == "area":
+        _run_area_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, (d_pictures if yuv else d_desc).data_ptr(), d_desc.data_ptr(), t,
+                         d_frames.data_ptr(), d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16,
+                         fit, pad, s)
+    elif yuv and letterbox:
         _run_fit_yuv_ragged(network, d_px.data_ptr(), buf.nbytes, fmt, d_pictures.data_ptr(), d_desc.data_ptr(), t, d_frames.data_ptr(),
                             d_heads.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), cap, d_status.data_ptr(), size, f16, pad, s)
     elif yuv:
@@ -827,7 +919,7 @@ def _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile=N
 
 
 def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_threshold=None, size=56, dtype="int8", device=None,
-             tile=None, stride=None, whole=True, fit="stretch", pad=114):
+             tile=None, stride=None, whole=True, fit="stretch", pad=114, interp="linear"):
     """Average precision of the network's boxes against labelled ones: what evaluate_model (yolov3_train_tf.py:809-869) reports, for the
     batch `detect` takes.  `ground_truths`: one [k, 4] array (x1, y1, x2, y2) per image, in that image's pixels.  The records are decoded as
     by `detect` (fmt, size, dtype as there; iou_threshold=None scores every record, a float suppresses first, as evaluate_model does),
@@ -845,7 +937,7 @@ def evaluate(network, images, ground_truths, fmt="bgr", conf_iou=0.5, iou_thresh
     gt, gt_counts = pack_ground_truths(ground_truths)
     if n == 0:
         return {"ap": 0.0, "detections": 0, "ground_truths": 0, "true_positives": 0, "precision": 0.0, "recall": 0.0}
-    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, fit=fit, pad=pad, interp=interp)
     import torch
     dev, cap, gt_cap, s = b.device, b.cap, gt.shape[1], b.stream.cuda_stream
     d_gt = torch.from_numpy(gt.view(np.float64).reshape(n, gt_cap, 4)).to(dev)
@@ -907,7 +999,7 @@ def crop_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, order="rgb", fmt="bgr", cap=None, iou_threshold=0.4, size=56,
-                 dtype="int8", device=None, tile=None, stride=None, whole=True, chips_cap=None, fit="stretch", pad=114):
+                 dtype="int8", device=None, tile=None, stride=None, whole=True, chips_cap=None, fit="stretch", pad=114, interp="linear"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile`, `stride`, `whole` these are), and every kept box cut out of its picture and
     resized to `out` = (out_h, out_w) (an int: square chips; multiples of 16 in 16..256) on the GPU, on the same stream, from the pixels
     that are already there: what a recogniser, a landmark model or a blur filter takes next.  `margin`: the box grows by this share of
@@ -929,7 +1021,7 @@ def detect_chips(network, images, out=(112, 112), margin=0.0, square=False, orde
     import torch
     if tile is not None:
         _packed_code(fmt, "detect_chips(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, whole, out_cap=cap, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, whole, out_cap=cap, fit=fit, pad=pad, interp=interp)
     if chips_cap is None:
         b.stream.synchronize()
         room = int(np.clip(b.d_counts.cpu().numpy(), 0, b.cap).sum())
@@ -1008,7 +1100,7 @@ def _pictures_back(b, fmt):
 
 
 def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None,
-                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114):
+                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box hidden in its picture on the GPU,
     on the same stream, in the pixels that are already there: mode "mosaic" pixelates the blocks of `block` x `block` pixels (4, 8, 16,
     32 or 64; the grid starts at the picture's pixel (0, 0)) that the box touches, each block to its mean; mode "fill" writes `colour`,
@@ -1031,7 +1123,7 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_redacted(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad, interp=interp)
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the redaction's own: the staging's status does not raise here
     redact = redact_records_yuv_device if yuv else redact_records_device
@@ -1076,7 +1168,7 @@ def blur_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None, iou_threshold=0.4, size=56,
-                   dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114):
+                   dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box blurred in its picture on the GPU, on
     the same stream, in the pixels that are already there: the box becomes a grid of at most `grid` x `grid` (1 to 16) means of its own
     pixels, resized back to the box -- every face gets the same number of cells, so a large face is hidden as well as a small one.
@@ -1097,7 +1189,7 @@ def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_blurred(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad, interp=interp)
     records_cap = n * b.cap
     room = blur_workspace(records_cap, grid)
     d_work = torch.empty(room, dtype=torch.uint8, device=b.device)
@@ -1186,7 +1278,7 @@ def _track_tuples(d_out, d_info, d_out_counts, n):
              for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
 
 
-def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8", fit="stretch", pad=114):
+def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8", fit="stretch", pad=114, interp="linear"):
     """`detect` with the suppression for the next `steps` frames of the `tracker`'s streams, and the kept boxes associated with its track
     state on the same stream: `images` holds tracker.streams * steps pictures, frame t of stream s at index t * streams + s (layout
     "time": one frame of every camera per step) or s * steps + t ("stream": a clip per stream).  fmt, iou_threshold (not None: the tracker
@@ -1203,7 +1295,7 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
     n = len(images)
     if n == 0:
         return []
-    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype, fit=fit, pad=pad, interp=interp)
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
     b.stream.synchronize()
     return _track_tuples(d_out, d_info, d_out_counts, n)
@@ -1248,7 +1340,7 @@ def draw_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=None, iou_threshold=0.4, size=56, dtype="int8", tile=None,
-                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None, fit="stretch", pad=114):
+                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None, fit="stretch", pad=114, interp="linear"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and the outline of every kept box drawn into its picture
     on the GPU, on the same stream, in the pixels that are already there -- the last line of the reference's scripts,
     cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2), which the defaults reproduce: `colour` (R, G, B) whatever the byte order of
@@ -1284,7 +1376,7 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
     yuv = is_yuv(fmt)
     if tile is not None:
         _packed_code(fmt, "detect_drawn(tile=...)")
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad, interp=interp)
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the drawing's own: the staging's status does not raise here
     draw = draw_records_yuv_device if yuv else draw_records_device
@@ -1311,7 +1403,7 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
 
 
 def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_cap=1200, device=None, iou_threshold=0.4, size=56, dtype="int8",
-                 fit="stretch", pad=114):
+                 fit="stretch", pad=114, interp="linear"):
     """`detect` for pictures larger than the faces in them: every image is cut into tiles (`plan_tiles`: `tile`, `stride` an int or (y, x),
     stride=None no overlap; `whole` adds the whole image as a tile of its own), every tile is one frame of the network at `size` and `dtype`
     (as in `detect`), and the tiles' records are merged per image on the GPU, translated to the image's own pixels (`gather_tiles_device`)
@@ -1324,13 +1416,13 @@ def detect_tiled(network, images, tile, stride=None, whole=True, fmt="bgr", out_
     n = len(images)
     if n == 0:
         return []
-    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, out_cap, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, None, device, iou_threshold, size, dtype, tile, stride, whole, out_cap, fit=fit, pad=pad, interp=interp)
     b.stream.synchronize()
     b.check_totals("detect_tiled")
     return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))
 
 
-def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8", fit="stretch", pad=114):
+def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None, size=56, dtype="int8", fit="stretch", pad=114, interp="linear"):
     """Boxes per image, in that image's own pixels: a list of int32 [k, 4] arrays (x1, y1, x2, y2), one per image -- what
     tflite_prediction.py:29-61 computes for each photo, for the whole batch in one ragged launch sequence.  `images`: uint8 [H, W, C] arrays
     of any sizes (cv2.imread gives BGR: fmt="bgr"); `network`: an initialised Network.  iou_threshold=None returns every record above the
@@ -1347,12 +1439,18 @@ def detect(network, images, fmt="bgr", cap=None, device=None, iou_threshold=None
     of the frame is the grey `pad` (0..255; the trainers' 114), and the boxes are mapped back through the same rectangle
     (`run_decode_fit_ragged_device`; the definition: csrc/yf_images_fit.h, `ptq.letterbox_u8`) -- what a model trained by a letterboxing
     trainer expects.  The shipped model was trained on stretched pictures; what letterboxing does to its accuracy has not been measured
-    (`evaluate` scores either on labelled pictures).  Any other `fit` raises ValueError."""
+    (`evaluate` scores either on labelled pictures).  Any other `fit` raises ValueError.
+    interp="linear": the resize is cv2.resize's INTER_LINEAR, as the reference's.  interp="area": every source pixel of the picture is
+    averaged into its frame (`prepare_area_*`, then the network and the decode of the fit; the definition: csrc/yf_images_area.h,
+    `ptq.resize_area_u8`), with either fit, any fmt, size and dtype.  The shipped model was trained on linearly resized pictures; what
+    the filter does to its accuracy has not been measured.  Any other `interp` raises ValueError."""
     _check_frames(size, dtype)                          # before the empty batch is returned, and before torch, the network or the library
     if fit not in FITS:
         raise ValueError(FIT_WHAT.format(fit))
+    if interp not in INTERPS:
+        raise ValueError(INTERP_WHAT.format(interp))
     if len(images) == 0:
         return []
-    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, fit=fit, pad=pad)
+    b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, fit=fit, pad=pad, interp=interp)
     b.stream.synchronize()
     return b.boxes(np.minimum(b.d_counts.cpu().numpy(), b.cap))

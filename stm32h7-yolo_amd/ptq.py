@@ -355,18 +355,50 @@ def letterbox_fit(h, w, size):
     return (size - fw) // 2, (size - fh) // 2, fw, fh
 
 
-def letterbox_u8(img_hwc, size, pad=114):
-    """The letterboxed frame of a uint8 picture [H, W, C]: `resize_linear_u8` to the rectangle of `letterbox_fit`, the rest of the
-    [size, size, C] frame filled with `pad` (0..255; the trainers' grey is 114) in every channel -> uint8 [size, size, C]."""
+def letterbox_u8(img_hwc, size, pad=114, interp="linear"):
+    """The letterboxed frame of a uint8 picture [H, W, C]: `resize_linear_u8` (interp="area": `resize_area_u8`) to the rectangle of
+    `letterbox_fit`, the rest of the [size, size, C] frame filled with `pad` (0..255; the trainers' grey is 114) in every channel ->
+    uint8 [size, size, C]."""
     src = np.asarray(img_hwc, np.uint8)
     if src.ndim != 3:
         raise ValueError(f"expected uint8 [H, W, C], got {src.shape}")
     if not 0 <= int(pad) <= 255:
         raise ValueError(f"pad {pad!r}: 0 to 255")
+    if interp not in ("linear", "area"):
+        raise ValueError(f"interp {interp!r}: 'linear' or 'area'")
     x0, y0, fw, fh = letterbox_fit(src.shape[0], src.shape[1], size)
     out = np.full((int(size), int(size), src.shape[2]), int(pad), np.uint8)
-    out[y0:y0 + fh, x0:x0 + fw] = resize_linear_u8(src, fw, fh)
+    out[y0:y0 + fh, x0:x0 + fw] = resize_linear_u8(src, fw, fh) if interp == "linear" else resize_area_u8(src, fh, fw)
     return out
+
+
+@functools.lru_cache(maxsize=256)
+def _area_axis(n_out, n_in):
+    """int64 [n_out, n_in]: a(d, s), the overlap of output d's [d n_in, (d + 1) n_in) with source s's [s n_out, (s + 1) n_out) on the
+    grid of n_in * n_out sub-positions (read-only)"""
+    d = np.arange(n_out, dtype=np.int64)[:, None]
+    s = np.arange(n_in, dtype=np.int64)[None, :]
+    a = np.maximum(0, np.minimum((d + 1) * n_in, (s + 1) * n_out) - np.maximum(d * n_in, s * n_out))
+    a.setflags(write=False)
+    return a
+
+
+def resize_area_u8(img, out_h, out_w):
+    """The exact area average of a uint8 picture [H, W, C] at [out_h, out_w, C], as csrc/yf_images_area.h states it, in integers: every
+    source pixel counted with the share of it an output pixel covers.  Per axis a(d, s) = the overlap of [d n_in, (d + 1) n_in) and
+    [s n_out, (s + 1) n_out) (an integer; the a(d, .) sum to n_in); per output pixel and channel
+        S = sum ay(y, sy) ax(x, sx) p[sy][sx],   v = (2 S + H W) // (2 H W)          rounded half up
+    for any ratio -- reduction, enlargement, identity.  For integer ratios this is the rounded block mean, the result of the integer path
+    of cv2.resize(..., interpolation=cv2.INTER_AREA); elsewhere OpenCV accumulates float weights and this is the value they approximate.
+    Not pinned against a real cv2.  (Note the order (out_h, out_w); `resize_linear_u8` keeps cv2's (out_w, out_h).)"""
+    src = np.asarray(img, np.uint8)
+    h, w = src.shape[:2]
+    src = src.reshape(h, w, -1).astype(np.int64)
+    ay, ax = _area_axis(int(out_h), int(h)), _area_axis(int(out_w), int(w))
+    rows = np.einsum("xs,hsc->hxc", ax, src)                     # [H, out_w, C]: at most 255 * W
+    total = np.einsum("yh,hxc->yxc", ay, rows)                   # at most 255 * H * W, about 6.8e10
+    d = np.int64(h) * np.int64(w)
+    return ((2 * total + d) // (2 * d)).astype(np.uint8)
 
 
 def yuv420sp_to_rgb_u8(y, uv, v_first=False):
