@@ -518,6 +518,33 @@ YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, l
                                      const yf_track_params* params, void* d_state, void* d_out, void* d_info, void* d_out_counts,
                                      int out_cap, int32_t* d_status, void* stream);
 
+/* ---- tracking with a motion model: the tracker above with a constant-velocity g-h (alpha-beta) filter on every edge of a track's box.
+ * The box of a held-over track moves on with the velocity the track had, so a redaction still covers a moving face on the frames the
+ * detector misses it, and the face keeps its id when it is detected again -- the match is taken against the PREDICTED box.  A second
+ * entry beside the one above, which does not change; the definition is stated once in csrc/yf_images_motion.h (the filter, its integer
+ * arithmetic, what is still out of scope), which the kernel, a host build and a sanitizer program share.
+ *   state:  d_state yf_track_motion_state[streams] (8-byte aligned), yf_images_track_motion_state_bytes(streams) bytes: 7176 per stream,
+ *           a slot the base tracker's 44 bytes, 4 of padding and pos[4], vel[4] (int64, 1/256 pixel and 1/256 pixel per step, of x1, y1,
+ *           x2, y2).  All zero is the empty state; the bytes are untrusted (every pos and vel read is clamped to +-2^40 first).  THE TWO
+ *           ENTRIES' STATES ARE DIFFERENT FORMATS OF DIFFERENT SIZES: a yf_track_state must never be passed here, nor this state above.
+ *   params: a host pointer, copied: base as above; alpha, beta, damp in [0, 256] (units of 1/256), smooth 0 or 1.  Per step and edge,
+ *           P' = pos + vel; matched to a detection z: r = 256 z - P', pos = P' + alpha r / 256, vel += beta r / 256; unmatched: pos = P',
+ *           vel = damp vel / 256.  (256, 0) is the tracker above, byte for byte, from the empty state; (256, 256) predicts with the last
+ *           frame-to-frame difference.  The library's suggestion is {192, 128, 256, 0}: a choice, not something measured -- there is no
+ *           accuracy or identity-switch figure for real video.
+ *   output: as above.  A held-over track (misses > 0) is reported with its last record's edges replaced by the filter's position
+ *           rounded to pixels; with smooth 1 a matched track too (the filtered box), with smooth 0 it reports its detection verbatim.
+ *           A predicted box is not clamped to the picture; the crop, the redaction, the blur and the drawing clip themselves.
+ * The input, the layouts, the checks (and alpha, beta, damp, smooth), n = 0, the return value and the error text are the entry's above;
+ * one launch, one wave per stream, the state in registers over the stream's steps; asynchronous, no allocation, capturable. */
+typedef struct yf_track_motion        { yf_track base; int32_t pad; int64_t pos[4]; int64_t vel[4]; } yf_track_motion;    /* 112 bytes */
+typedef struct yf_track_motion_state  { uint32_t issued, reserved; yf_track_motion slot[YF_TRACK_SLOTS]; } yf_track_motion_state; /* 7176 bytes per stream */
+typedef struct yf_track_motion_params { yf_track_params base; int32_t alpha, beta, damp, smooth; } yf_track_motion_params;         /* 32 bytes */
+YF_API size_t yf_images_track_motion_state_bytes(long streams);
+YF_API long   yf_images_track_motion_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                                            const yf_track_motion_params* params, void* d_state, void* d_out, void* d_info,
+                                            void* d_out_counts, int out_cap, int32_t* d_status, void* stream);
+
 /* ---- letterboxed frames: the picture resized with its aspect kept, centred in the square frame, the rest padded with one grey, and the
  * boxes mapped back through the same rectangle.  Every entry above stretches the picture onto the frame, as the reference's scripts do
  * (cv2.resize(img, (56, 56))); that stays the default.  Every mainstream YOLO trainer letterboxes instead, so a retrained model (.yfm, or

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h, the tracker with a motion model of yf_images_motion.h, the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -19,6 +19,7 @@
 #include "yf_images_blur.h"
 #include "yf_images_draw.h"
 #include "yf_images_track.h"
+#include "yf_images_motion.h"
 #include "yf_images_fit.h"
 #include "yf_images_area.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -723,28 +724,19 @@ EXPORT int yfi_draw_check_host(long n, int cap, int half, uint32_t colour, const
   return t != NULL;
 }
 
-/* ---- yf_images_track.h ----  yf_images_track_device as the header states it, on host memory (`stream` is not used): stream by stream,
- * step by step, literally -- the table of the eligible pairs' IoUs, then round after round the largest entry among the slots and
- * detections still unmatched (a scan in ascending detection, then ascending slot, with a strict comparison: the tie rule), the update,
- * the births, and the output by a selection of the smallest (id, slot) not yet emitted.  Returns n, or -1 for arguments the device entry
- * refuses. */
-static void track_step_host(yf_track_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_params* p, int32_t frame,
-                            yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
-  const int m = yfi_track_clamp(count, cap);
-  int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
+/* ---- yf_images_track.h, yf_images_motion.h ----  the match of one step, shared by both trackers: box[s] the box an occupied slot s is matched by -> slot_det[s], det_slot[j < m]; -1: none */
+static void track_match_host(int32_t (*box)[4], const int* occupied, const yf_det* dets, int m, double match_iou, int* slot_det,
+                             int* det_slot) {
   static _Thread_local double iou[YF_TRACK_SLOTS][YF_TRACK_MAX_DETS];
-  int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
   for (int j = 0; j < m; ++j) det_slot[j] = -1;
   for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
-    const yf_track* k = &st->slot[s];
     slot_det[s] = -1;
-    occupied[s] = k->id != 0;
     if (!occupied[s]) continue;
-    const double area_a = yfi_nms_area(k->det.x1, k->det.y1, k->det.x2, k->det.y2);
+    const double area_a = yfi_nms_area(box[s][0], box[s][1], box[s][2], box[s][3]);
     for (int j = 0; j < m; ++j) {
       const yf_det* d = &dets[j];
-      yfi_track_iou(k->det.x1, k->det.y1, k->det.x2, k->det.y2, area_a, d->x1, d->y1, d->x2, d->y2,
-                    yfi_nms_area(d->x1, d->y1, d->x2, d->y2), p->match_iou, &iou[s][j]);          /* 0.0: not eligible */
+      yfi_track_iou(box[s][0], box[s][1], box[s][2], box[s][3], area_a, d->x1, d->y1, d->x2, d->y2,
+                    yfi_nms_area(d->x1, d->y1, d->x2, d->y2), match_iou, &iou[s][j]);              /* 0.0: not eligible */
     }
   }
   for (;;) {
@@ -759,6 +751,25 @@ static void track_step_host(yf_track_state* st, const yf_det* dets, int32_t coun
     det_slot[bj] = bs;
     slot_det[bs] = bj;
   }
+}
+
+/* ---- yf_images_track.h ----  yf_images_track_device as the header states it, on host memory (`stream` is not used): stream by stream,
+ * step by step, literally -- the table of the eligible pairs' IoUs, then round after round the largest entry among the slots and
+ * detections still unmatched (a scan in ascending detection, then ascending slot, with a strict comparison: the tie rule), the update,
+ * the births, and the output by a selection of the smallest (id, slot) not yet emitted.  Returns n, or -1 for arguments the device entry
+ * refuses. */
+static void track_step_host(yf_track_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_params* p, int32_t frame,
+                            yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
+  const int m = yfi_track_clamp(count, cap);
+  int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
+  int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
+  int32_t box[YF_TRACK_SLOTS][4];
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    const yf_track* k = &st->slot[s];
+    occupied[s] = k->id != 0;
+    box[s][0] = k->det.x1; box[s][1] = k->det.y1; box[s][2] = k->det.x2; box[s][3] = k->det.y2;
+  }
+  track_match_host(box, occupied, dets, m, p->match_iou, slot_det, det_slot);
   for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
     yf_track* k = &st->slot[s];
     if (!occupied[s]) continue;
@@ -829,6 +840,118 @@ EXPORT int yfi_track_check_host(const void* dets, const void* counts, long strea
 }
 
 EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
+
+/* ---- yf_images_motion.h ----  yf_images_track_motion_device as the header states it, on host memory: the step above with the
+ * prediction in front of the match and the filter in the update.  A free slot's bytes are neither read (but its id) nor written. */
+static void motion_step_host(yf_track_motion_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_motion_params* p,
+                             int32_t frame, yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
+  const int m = yfi_track_clamp(count, cap);
+  int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
+  int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
+  int32_t box[YF_TRACK_SLOTS][4];
+  int64_t pp[YF_TRACK_SLOTS][4];
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    const yf_track_motion* k = &st->slot[s];
+    occupied[s] = k->base.id != 0;
+    for (int e = 0; e < 4; ++e) {
+      pp[s][e] = occupied[s] ? yfi_motion_sat(k->pos[e]) + yfi_motion_sat(k->vel[e]) : 0;
+      box[s][e] = yfi_motion_box(pp[s][e]);
+    }
+  }
+  track_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot);
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    yf_track_motion* k = &st->slot[s];
+    if (!occupied[s]) continue;
+    k->base.age = yfi_track_inc(k->base.age);
+    if (slot_det[s] >= 0) {
+      const yf_det* d = &dets[slot_det[s]];
+      const int32_t z[4] = {d->x1, d->y1, d->x2, d->y2};
+      k->base.det = *d;
+      k->base.hits = yfi_track_inc(k->base.hits);
+      k->base.misses = 0;
+      for (int e = 0; e < 4; ++e) {
+        const int64_t r = 256ll * (int64_t)z[e] - pp[s][e];
+        k->pos[e] = yfi_motion_sat(pp[s][e] + yfi_motion_mul(p->alpha, r));
+        k->vel[e] = yfi_motion_sat(yfi_motion_sat(k->vel[e]) + yfi_motion_mul(p->beta, r));
+      }
+    } else {
+      k->base.misses = yfi_track_inc(k->base.misses);
+      if (k->base.misses > p->base.max_misses) memset(k, 0, sizeof *k);
+      else
+        for (int e = 0; e < 4; ++e) {
+          k->pos[e] = yfi_motion_sat(pp[s][e]);
+          k->vel[e] = yfi_motion_mul(p->damp, yfi_motion_sat(k->vel[e]));
+        }
+    }
+  }
+  int s = 0;
+  for (int j = 0; j < m; ++j) {
+    if (det_slot[j] >= 0) continue;
+    while (s < YF_TRACK_SLOTS && st->slot[s].base.id != 0) ++s;
+    if (s == YF_TRACK_SLOTS) { bits |= YFI_TRACK_ST_DROPPED; break; }
+    yf_track_motion* k = &st->slot[s];
+    const int32_t z[4] = {dets[j].x1, dets[j].y1, dets[j].x2, dets[j].y2};
+    st->issued = yfi_track_next_id(st->issued, 0);
+    k->base.id = st->issued; k->base.hits = 1; k->base.misses = 0; k->base.age = 1; k->base.det = dets[j];
+    k->pad = 0;
+    for (int e = 0; e < 4; ++e) { k->pos[e] = 256ll * (int64_t)z[e]; k->vel[e] = 0; }
+  }
+  int emitted[YF_TRACK_SLOTS] = {0}, total = 0;
+  for (;;) {
+    int pick = -1;
+    for (int q = 0; q < YF_TRACK_SLOTS; ++q) {
+      const yf_track* k = &st->slot[q].base;
+      if (emitted[q] || k->id == 0 || k->hits < p->base.min_hits) continue;
+      if (pick < 0 || k->id < st->slot[pick].base.id) pick = q;
+    }
+    if (pick < 0) break;
+    emitted[pick] = 1;
+    if (total < out_cap) {
+      const yf_track_motion* k = &st->slot[pick];
+      out[total] = k->base.det;
+      out[total].frame = frame;
+      if (k->base.misses > 0 || p->smooth != 0) {                    /* pos was written in this step or at an earlier one: within the clamp */
+        out[total].x1 = yfi_motion_box(k->pos[0]); out[total].y1 = yfi_motion_box(k->pos[1]);
+        out[total].x2 = yfi_motion_box(k->pos[2]); out[total].y2 = yfi_motion_box(k->pos[3]);
+      }
+      info[total].id = k->base.id; info[total].hits = k->base.hits; info[total].misses = k->base.misses; info[total].age = k->base.age;
+    }
+    ++total;
+  }
+  *out_count = total;
+  if (status) *status = bits;
+}
+
+EXPORT long yf_images_track_motion_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                        const yf_track_motion_params* params, void* state, void* out, void* info, void* out_counts,
+                                        int out_cap, int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_motion_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status) != NULL) return -1;
+  const yf_track_motion_params p = *params;
+  for (long s = 0; s < streams; ++s)
+    for (long t = 0; t < steps; ++t) {
+      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
+      motion_step_host((yf_track_motion_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
+                       (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
+                       (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
+    }
+  return streams * steps;
+}
+
+EXPORT int yfi_motion_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                 const yf_track_motion_params* params, const void* state, const void* out, const void* info,
+                                 const void* out_counts, int out_cap, const void* status, char* text, int text_bytes) {
+  const char* t = yfi_motion_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+EXPORT size_t yf_images_track_motion_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_motion_state) : 0; }
+
+/* the filter's helpers as they are (no range check: the tests ask for what the definition gives) */
+EXPORT int64_t yfi_motion_mul_host(int32_t g, int64_t v) { return yfi_motion_mul(g, v); }
+EXPORT int32_t yfi_motion_box_host(int64_t p) { return yfi_motion_box(p); }
+EXPORT int64_t yfi_motion_sat_host(int64_t v) { return yfi_motion_sat(v); }
 
 /* ---- yf_images_fit.h ----  out[4] = {x0, y0, width, height} of a picture of h x w in a frame of side S (no range check: the tests
  * ask for what the definition gives) */

@@ -38,7 +38,8 @@
  * A CALL: n = streams * steps frames; YF_TRACK_TIME_MAJOR: f = t * streams + s; YF_TRACK_STREAM_MAJOR: f = s * steps + t.  The steps of
  * stream s are taken in order t = 0 .. steps - 1 on state[s], which is read before the first and written after the last.
  *
- * OUT OF SCOPE.  No motion model: a held-over box stays where it was last seen.  No appearance features.  No re-identification after a
+ * OUT OF SCOPE.  No motion model HERE: a held-over box stays where it was last seen; the entry beside this one, yf_images_motion.h
+ * (yf_images_track_motion_device), adds a constant-velocity filter per edge.  No appearance features.  No re-identification after a
  * track is removed: the face gets a new id.  No optimal (Hungarian) assignment: the match is the greedy one above. */
 #ifndef YF_IMAGES_TRACK_H
 #define YF_IMAGES_TRACK_H

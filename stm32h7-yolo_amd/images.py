@@ -43,6 +43,17 @@ over the frames and a face the detector misses for a few frames is held over wit
 again, which `crop_records_device` and `redact_records_device` take as they are.  The reference has no tracker; the definition is the
 library's own (csrc/yf_images_track.h, `ptq.track_step`).
 
+`Tracker(..., motion=True)` adds a motion model to that step: a constant-velocity g-h (alpha-beta) filter on every edge of a track's box,
+in integers, so that the box of a held-over track moves on with the velocity the track had and the match is taken against the PREDICTED
+box -- a moving face stays hidden on the frames the detector misses it, and keeps its id when it is seen again -- `track_motion_device`,
+`track_motion_state_bytes`, `YfTrackMotionParams`; a second entry with a larger state (7176 bytes per stream against 2824) beside the
+first, which does not change; the definition is the library's own (csrc/yf_images_motion.h, `ptq.track_motion_step`).  The gains
+(alpha, beta, damp) are in 1/256; `MOTION_GAINS` = (192, 128, 256) is the library's suggestion, a choice and not a measurement: there is
+no accuracy or identity-switch figure for real video.  (256, 0, any) is the tracker without the model, byte for byte.  Still out of scope:
+a covariance (a Kalman filter), appearance features, re-identification, optimal assignment, clamping a predicted box to the picture (the
+crop, the redaction, the blur and the drawing clip themselves).  `detect_tracked`, `detect_drawn`, `detect_redacted` and `detect_blurred`
+take such a tracker as they take the plain one; with a tracker the last two hide the REPORTED TRACKS, held-over ones included.
+
 `fit="letterbox"` on `detect`, every `detect_*` call and `evaluate` replaces the stretch onto the square frame by what every mainstream
 YOLO trainer does: the picture resized with its aspect kept into a centred rectangle of the frame (`fit_of`), the rest padded with the
 grey `pad`, and the boxes mapped back through the same rectangle -- `prepare_fit_*`, `decode_fit_ragged_device`,
@@ -134,6 +145,17 @@ LAYOUT_WHAT = "layout {!r}: 'time' (frame t * streams + s) or 'stream' (frame s 
 YF_TRACK_CLIPPED, YF_TRACK_DROPPED = 1, 2      # the bits of a frame's status
 
 
+# the tracker with a motion model (yf_track_motion_params, yf_track_motion_state): a slot is the tracker's 44 bytes, 4 of padding and
+# pos[4], vel[4] (int64, 1/256 pixel); gains in 1/256
+class YfTrackMotionParams(ctypes.Structure):
+    _fields_ = [("base", YfTrackParams), ("alpha", ctypes.c_int32), ("beta", ctypes.c_int32), ("damp", ctypes.c_int32), ("smooth", ctypes.c_int32)]
+
+
+TRACK_MOTION_STATE_BYTES = 7176
+MOTION_GAINS = (192, 128, 256)                 # (alpha, beta, damp): the library's suggestion -- a choice, not a measurement
+assert ctypes.sizeof(YfTrackMotionParams) == 32
+
+
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
 # where a picture lies in its letterboxed frame (yf_fit), and the two ways a picture becomes a frame
 FIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4")])
@@ -221,6 +243,7 @@ def _entries():
         "draw_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ctypes.c_uint32, vp, ci, vp, ci, vp, vp, vp],
         # d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream
         "track_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
+        "track_motion_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
         # letterboxed frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] pad, d_frames, d_status, stream
         "prepare_fit_ragged_device": ragged + [ci, ci, vp, vp, vp],
         "prepare_fit_yuv_ragged_device": ragged + [ci, ci, vp, vp, vp],
@@ -267,6 +290,8 @@ def load():
     lib.yf_images_blur_workspace.argtypes = [ctypes.c_long, ctypes.c_int]
     lib.yf_images_track_state_bytes.restype = ctypes.c_size_t
     lib.yf_images_track_state_bytes.argtypes = [ctypes.c_long]
+    lib.yf_images_track_motion_state_bytes.restype = ctypes.c_size_t
+    lib.yf_images_track_motion_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
     lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
     lib.yf_images_fit.restype = ctypes.c_int
@@ -1099,17 +1124,33 @@ def _pictures_back(b, fmt):
     return pictures
 
 
+def _tracker_steps(tracker, n, steps, layout, iou_threshold):
+    """the checks of a `detect_*` call's tracker arguments -> steps (None: as many as the n images make)"""
+    steps = n // tracker.streams if steps is None else int(steps)
+    if steps < 0 or n != tracker.streams * steps:
+        raise ValueError(f"{n} images: {tracker.streams} streams x {steps} steps")
+    if iou_threshold is None:
+        raise ValueError("iou_threshold None: the tracker takes suppressed records")
+    _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+    return steps
+
+
 def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None,
-                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear"):
+                    iou_threshold=0.4, size=56, dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear",
+                    tracker=None, steps=None, layout="time"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box hidden in its picture on the GPU,
     on the same stream, in the pixels that are already there: mode "mosaic" pixelates the blocks of `block` x `block` pixels (4, 8, 16,
     32 or 64; the grid starts at the picture's pixel (0, 0)) that the box touches, each block to its mean; mode "fill" writes `colour`,
     (R, G, B) whatever the byte order of `fmt` -- for NV12 / NV21 surfaces (Y, U, V) -- into the box, and `block` is not used.  `margin`
     and `square` grow the box as in `detect_chips` (csrc/yf_images_crop.h, `ptq.crop_region`).  fmt, cap, iou_threshold, size, dtype,
     device as in `detect`; with `tile`, cap is `detect_tiled`'s out_cap and the parent pictures are redacted.
+    With `tracker` (a `Tracker`; `images` are its next `steps` frames in `layout`, as in `detect_drawn`) the tracker is updated with the
+    kept boxes on the same stream and the REPORTED TRACKS are hidden, held-over ones included: a face the detector misses for a few
+    frames stays hidden -- with `Tracker(motion=...)` where its filter says it has moved to.
     Returns (pictures, boxes): the redacted pictures in the caller's shapes, new arrays (NV12 / NV21: (y, uv) pairs) -- the caller's
-    arrays are not changed --, and per image the int32 [k, 4] array `detect` returns.  The definition is the library's own:
-    csrc/yf_images_redact.h, restated as `ptq.redact_u8` and `ptq.redact_yuv420sp`."""
+    arrays are not changed --, and per image the int32 [k, 4] array `detect` returns; with a tracker (pictures, tracks),
+    `detect_tracked`'s tuples.  The definition is the library's own: csrc/yf_images_redact.h, restated as `ptq.redact_u8` and
+    `ptq.redact_yuv420sp`."""
     mode_code = _code(REDACT_MODES, mode, MODE_WHAT)
     block = 0 if mode_code == YF_REDACT_FILL else int(block)
     if mode_code == YF_REDACT_MOSAIC and block not in (4, 8, 16, 32, 64):
@@ -1117,6 +1158,9 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     colour_code = _colour_code(colour)
     permille = _permille(margin)
     n = len(images)
+    if tracker is not None:
+        steps = _tracker_steps(tracker, n, steps, layout, iou_threshold)
+        device = tracker.device.index
     if n == 0:
         return [], []
     import torch
@@ -1127,7 +1171,11 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)      # the redaction's own: the staging's status does not raise here
     redact = redact_records_yuv_device if yuv else redact_records_device
-    redact(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap,
+    d_dets, d_counts, rec_cap = b.d_dets, b.d_counts, b.cap
+    if tracker is not None:
+        d_dets, d_info, d_counts, _ = tracker.update(b.d_dets, b.d_counts, steps, layout, cap=b.cap, stream=b.stream.cuda_stream)
+        rec_cap = d_dets.shape[1]
+    redact(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, rec_cap,
            d_first.data_ptr(), d_status.data_ptr(), mode=mode_code, block=block, colour=colour_code, margin_permille=permille, square=square,
            stream=b.stream.cuda_stream)
     b.stream.synchronize()
@@ -1135,6 +1183,8 @@ def detect_redacted(network, images, mode="mosaic", block=8, colour=(0, 0, 0), m
     bad = np.nonzero(d_status.cpu().numpy())[0]
     if bad.size:
         raise ImagesError(f"detect_redacted: the descriptor of image {int(bad[0])} is invalid")
+    if tracker is not None:
+        return _pictures_back(b, fmt), _track_tuples(d_dets, d_info, d_counts, n)
     return _pictures_back(b, fmt), b.boxes(np.diff(d_first.cpu().numpy()))
 
 
@@ -1168,14 +1218,16 @@ def blur_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square=False, fmt="bgr", cap=None, iou_threshold=0.4, size=56,
-                   dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear"):
+                   dtype="int8", tile=None, stride=None, device=None, fit="stretch", pad=114, interp="linear", tracker=None, steps=None,
+                   layout="time"):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are; fit, pad as in `detect`), and every kept box blurred in its picture on the GPU, on
     the same stream, in the pixels that are already there: the box becomes a grid of at most `grid` x `grid` (1 to 16) means of its own
     pixels, resized back to the box -- every face gets the same number of cells, so a large face is hidden as well as a small one.
     `margin` and `square` grow the box as in `detect_chips`.  The workspace is sized for every record the batch can hold, so no box is
     ever filled with `colour` for lack of room.  fmt, cap, iou_threshold, size, dtype, device as in `detect`; with `tile`, cap is
-    `detect_tiled`'s out_cap and the parent pictures are blurred.
-    Returns (pictures, boxes) as `detect_redacted` does.  The definition is the library's own: csrc/yf_images_blur.h, restated as
+    `detect_tiled`'s out_cap and the parent pictures are blurred.  `tracker`, `steps`, `layout` as in `detect_redacted`: the reported
+    tracks are blurred, held-over ones included.
+    Returns (pictures, boxes) as `detect_redacted` does; with a tracker (pictures, tracks).  The definition is the library's own: csrc/yf_images_blur.h, restated as
     `ptq.blur_u8` and `ptq.blur_yuv420sp`."""
     grid = int(grid)
     if not 1 <= grid <= BLUR_MAX_GRID:
@@ -1183,6 +1235,9 @@ def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square
     colour_code = _colour_code(colour)
     permille = _permille(margin)
     n = len(images)
+    if tracker is not None:
+        steps = _tracker_steps(tracker, n, steps, layout, iou_threshold)
+        device = tracker.device.index
     if n == 0:
         return [], []
     import torch
@@ -1190,13 +1245,17 @@ def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square
     if tile is not None:
         _packed_code(fmt, "detect_blurred(tile=...)")
     b = _stage(network, images, fmt, cap, device, iou_threshold, size, dtype, tile, stride, True, out_cap=cap, fit=fit, pad=pad, interp=interp)
-    records_cap = n * b.cap
+    d_dets, d_counts, rec_cap = b.d_dets, b.d_counts, b.cap
+    if tracker is not None:
+        d_dets, d_info, d_counts, _ = tracker.update(b.d_dets, b.d_counts, steps, layout, cap=b.cap, stream=b.stream.cuda_stream)
+        rec_cap = d_dets.shape[1]
+    records_cap = n * rec_cap
     room = blur_workspace(records_cap, grid)
     d_work = torch.empty(room, dtype=torch.uint8, device=b.device)
     d_first = torch.empty(n + 1, dtype=torch.int32, device=b.device)
     d_status = torch.empty(n, dtype=torch.int32, device=b.device)
     blur = blur_records_yuv_device if yuv else blur_records_device
-    blur(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), b.d_dets.data_ptr(), b.d_counts.data_ptr(), n, b.cap, d_work.data_ptr(),
+    blur(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), d_dets.data_ptr(), d_counts.data_ptr(), n, rec_cap, d_work.data_ptr(),
          room, records_cap, d_first.data_ptr(), d_status.data_ptr(), grid=grid, colour=colour_code, margin_permille=permille, square=square,
          stream=b.stream.cuda_stream)
     b.stream.synchronize()
@@ -1204,6 +1263,8 @@ def detect_blurred(network, images, grid=8, colour=(0, 0, 0), margin=0.0, square
     bad = np.nonzero(d_status.cpu().numpy() & 1)[0]
     if bad.size:
         raise ImagesError(f"detect_blurred: the descriptor of image {int(bad[0])} is invalid")
+    if tracker is not None:
+        return _pictures_back(b, fmt), _track_tuples(d_dets, d_info, d_counts, n)
     return _pictures_back(b, fmt), b.boxes(np.diff(d_first.cpu().numpy()))
 
 
@@ -1228,17 +1289,51 @@ def track_device(d_dets, d_counts, streams, steps, layout, cap, params, d_state,
     return rc
 
 
+def track_motion_state_bytes(streams):
+    """The bytes of the state of `streams` streams of the tracker with a motion model (yf_images_track_motion_state_bytes): 7176 each.
+    All zero is the empty state.  Not the format of `track_state_bytes`: neither state may be passed to the other entry."""
+    return int(load().yf_images_track_motion_state_bytes(streams))
+
+
+def track_motion_device(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status=None,
+                        stream=None):
+    """`track_device` with a motion model (yf_images_track_motion_device): params = (match_iou, min_hits, max_misses, alpha, beta, damp,
+    smooth), the gains of the constant-velocity filter in [0, 256] (1/256), smooth 0 or 1; d_state the streams' state of
+    `track_motion_state_bytes` (read and written).  A held-over track is written with the box the filter moved on; with smooth 1 a matched
+    track with its filtered box.  The definition: csrc/yf_images_motion.h, ptq.track_motion_step.  Returns n."""
+    lib = load()
+    p = YfTrackMotionParams(YfTrackParams(float(params[0]), int(params[1]), int(params[2])), *(int(v) for v in params[3:7]))
+    rc = lib.yf_images_track_motion_device(d_dets, d_counts, streams, steps, _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT), cap, ctypes.byref(p),
+                                           d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream)
+    if rc != streams * steps or rc < 0:
+        raise ImagesError(f"yf_images_track_motion_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
+    return rc
+
+
 class Tracker:
     """The track state of `streams` video streams on the device, and the parameters of their association.  match_iou=0.3, min_hits=1,
     max_misses=5 are the library's choice for faces at a video rate -- a box that moved by less than about half its side still matches,
     every detection is reported at once, a face is held over for five frames -- not something the reference states or a measurement.
-    `update` takes the records of the next steps; `reset` empties every stream (an all-zero state is the empty state)."""
+    `update` takes the records of the next steps; `reset` empties every stream (an all-zero state is the empty state).
+    `motion`: None, the tracker as it is -- a held-over box stays where it was last seen (`track_device`, 2824 bytes per stream); True, a
+    constant-velocity filter per edge at the suggested gains `MOTION_GAINS` (a choice, not a measurement), or a triple (alpha, beta,
+    damp) in 1/256 -- a held-over box moves on and the match is taken against the predicted box (`track_motion_device`, 7176 bytes per
+    stream).  `smooth` (with motion): a matched track reports its filtered box, not its detection."""
 
-    def __init__(self, streams, match_iou=0.3, min_hits=1, max_misses=5, device=None):
+    def __init__(self, streams, match_iou=0.3, min_hits=1, max_misses=5, device=None, motion=None, smooth=False):
         import torch
         if int(streams) < 1:
             raise ValueError(f"streams {streams!r}: at least 1")
         self.params = (float(match_iou), int(min_hits), int(max_misses))
+        if motion is None or motion is False:
+            if smooth:
+                raise ValueError("smooth: only with motion")
+            self.motion = None
+        else:
+            gains = MOTION_GAINS if motion is True else tuple(int(v) for v in motion)
+            if len(gains) != 3 or not all(0 <= g <= 256 for g in gains):
+                raise ValueError(f"motion {motion!r}: True or (alpha, beta, damp), each 0..256")
+            self.motion = gains + (1 if smooth else 0,)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.reset(streams)
 
@@ -1247,7 +1342,8 @@ class Tracker:
         import torch
         if streams is not None:
             self.streams = int(streams)
-            self.d_state = torch.zeros((self.streams, TRACK_STATE_BYTES), dtype=torch.uint8, device=self.device)
+            state_bytes = TRACK_STATE_BYTES if self.motion is None else TRACK_MOTION_STATE_BYTES
+            self.d_state = torch.zeros((self.streams, state_bytes), dtype=torch.uint8, device=self.device)
         else:
             self.d_state.zero_()
 
@@ -1264,8 +1360,13 @@ class Tracker:
         d_status = torch.empty(n, dtype=torch.int32, device=self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        track_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap, self.params, self.d_state.data_ptr(),
-                     d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap, d_status.data_ptr(), stream)
+        if self.motion is None:
+            track_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap, self.params, self.d_state.data_ptr(),
+                         d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap, d_status.data_ptr(), stream)
+        else:
+            track_motion_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap, self.params + self.motion,
+                                self.d_state.data_ptr(), d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap,
+                                d_status.data_ptr(), stream)
         return d_out, d_info, d_out_counts, d_status
 
 
@@ -1284,7 +1385,7 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
     "time": one frame of every camera per step) or s * steps + t ("stream": a clip per stream).  fmt, iou_threshold (not None: the tracker
     takes a frame's records in descending confidence), size, dtype, fit, pad as in `detect`; the tracker's device is used.
     Returns per frame a list of (id, x1, y1, x2, y2, conf, hits, misses) in ascending id: the tracks reported for that frame, a held-over
-    one (misses > 0) with the box it was last seen at.  The tracker carries on from there at the next call.  The definition is the
+    one (misses > 0) with the box it was last seen at -- with a `Tracker(motion=...)`, the box its filter moved on.  The tracker carries on from there at the next call.  The definition is the
     library's own: csrc/yf_images_track.h, restated as `ptq.track_step`."""
     steps = int(steps)
     if steps < 0 or len(images) != tracker.streams * steps:
@@ -1360,12 +1461,7 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
     colour_code = _colour_code(colour)
     n = len(images)
     if tracker is not None:
-        steps = n // tracker.streams if steps is None else int(steps)
-        if steps < 0 or n != tracker.streams * steps:
-            raise ValueError(f"{n} images: {tracker.streams} streams x {steps} steps")
-        if iou_threshold is None:
-            raise ValueError("iou_threshold None: the tracker takes suppressed records")
-        _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+        steps = _tracker_steps(tracker, n, steps, layout, iou_threshold)
         table = [_colour_code(c) for c in (TRACK_PALETTE if palette is None else palette)]
         if not 1 <= len(table) <= DRAW_MAX_PALETTE:
             raise ValueError(f"palette: 1 to {DRAW_MAX_PALETTE} colours")

@@ -714,6 +714,34 @@ def track_iou(a, b):
     return inter, inter / uni
 
 
+def _track_match(boxes, dets, match_iou):
+    """the global greedy match of one step: `boxes` {slot: record} of the occupied slots (only the four edges are read), `dets` the
+    detections that count -> (slot_det, det_slot, ties).  The eligible pairs taken once in sorted order (-iou, detection, slot), those
+    with a matched member skipped: the same pairs as round after round of the largest IoU left."""
+    pairs = []
+    for k, box in sorted(boxes.items()):
+        for j, d in enumerate(dets):
+            iou = track_iou(box, d)[1]
+            if iou is not None and iou >= match_iou:
+                pairs.append((-iou, j, k))
+    pairs.sort()
+    slot_det, det_slot = {}, {}
+    ties = 0
+    for at, (neg, j, k) in enumerate(pairs):
+        if j in det_slot or k in slot_det:
+            continue
+        # a tie: another pair of the same IoU was still to be had when this one was taken, and shares a member with it
+        nxt = at + 1
+        while nxt < len(pairs) and pairs[nxt][0] == neg:
+            j2, k2 = pairs[nxt][1:]
+            if j2 not in det_slot and k2 not in slot_det and (j2 == j or k2 == k):
+                ties += 1
+                break
+            nxt += 1
+        det_slot[j], slot_det[k] = k, j
+    return slot_det, det_slot, ties
+
+
 def track_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
     """One step of the tracker -- one stream, one frame -- as csrc/yf_images_track.h states it, in Python integers and floats (float64).
     `state`: as `track_empty_state` gives it (not changed; the new state is returned).  `dets`: the frame's records, tuples (frame, anchor,
@@ -737,28 +765,7 @@ def track_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
     slots = [list(s) for s in state["slots"]]
     issued = int(state["issued"])
     occupied = [s[0] != 0 for s in slots]
-    pairs = []
-    for k, s in enumerate(slots):
-        if occupied[k]:
-            for j, d in enumerate(dets):
-                iou = track_iou(s[4], d)[1]
-                if iou is not None and iou >= match_iou:
-                    pairs.append((-iou, j, k))
-    pairs.sort()
-    slot_det, det_slot = {}, {}
-    ties = 0
-    for at, (neg, j, k) in enumerate(pairs):
-        if j in det_slot or k in slot_det:
-            continue
-        # a tie: another pair of the same IoU was still to be had when this one was taken, and shares a member with it
-        nxt = at + 1
-        while nxt < len(pairs) and pairs[nxt][0] == neg:
-            j2, k2 = pairs[nxt][1:]
-            if j2 not in det_slot and k2 not in slot_det and (j2 == j or k2 == k):
-                ties += 1
-                break
-            nxt += 1
-        det_slot[j], slot_det[k] = k, j
+    slot_det, det_slot, ties = _track_match({k: s[4] for k, s in enumerate(slots) if occupied[k]}, dets, match_iou)
     removals = held = 0
     for k, s in enumerate(slots):
         if not occupied[k]:
@@ -789,6 +796,103 @@ def track_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
     for k in sorted((k for k, s in enumerate(slots) if s[0] != 0 and s[1] >= min_hits), key=lambda k: (slots[k][0], k)):
         i, hits, misses, age, d = slots[k]
         emitted.append(((int(frame),) + tuple(d[1:]), (i, hits, misses, age)))
+        held += misses > 0
+    if stats is not None:
+        for name, v in (("matches", len(slot_det)), ("births", births), ("removals", removals), ("held", held), ("ties", ties),
+                        ("dropped", dropped)):
+            stats[name] = stats.get(name, 0) + v
+    return {"issued": issued, "reserved": state["reserved"], "slots": slots}, emitted, status
+
+
+# ---- the tracker with a motion model (csrc/yf_images_motion.h), in plain Python integers ----
+MOTION_ONE, MOTION_LIMIT = 256, 2 ** 40
+MOTION_DEFAULT = (192, 128, 256, 0)          # (alpha, beta, damp, smooth): the library's suggestion -- a choice, not a measurement
+_INT32_MIN = -2 ** 31
+
+
+def track_motion_empty_state():
+    """The empty state of one stream: what 7176 zero bytes are.  {"issued", "reserved", "slots": 64 x [id, hits, misses, age, det, pad,
+    pos, vel]}, det a record as in `track_step`, pos and vel lists of four integers (x1, y1, x2, y2; 1/256 pixel, 1/256 pixel per step)."""
+    return {"issued": 0, "reserved": 0, "slots": [[0, 0, 0, 0, _ZERO_DET, 0, [0] * 4, [0] * 4] for _ in range(TRACK_SLOTS)]}
+
+
+def motion_sat(v):
+    """yfi_motion_sat: the clamp of a position or velocity to [-2^40, 2^40]"""
+    return max(-MOTION_LIMIT, min(MOTION_LIMIT, int(v)))
+
+
+def motion_mul(g, v):
+    """yfi_motion_mul: the gain g (1/256) applied to v, toward zero"""
+    return (g * v) >> 8 if v >= 0 else -((g * -v) >> 8)
+
+
+def motion_box(p):
+    """yfi_motion_box: the pixel of a position, floor((p + 128) / 256) clamped to int32"""
+    return max(_INT32_MIN, min(_INT32_MAX, (int(p) + 128) // 256))
+
+
+def track_motion_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
+    """One step of the tracker with a motion model -- one stream, one frame -- as csrc/yf_images_motion.h states it: `track_step` with a
+    constant-velocity g-h filter on every edge, in Python integers (the IoU of the match stays float64).  `state`: as
+    `track_motion_empty_state` gives it (not changed; the new state is returned).  `dets`, `count`, `cap`, `frame`, `stats`: as in
+    `track_step`.  `params`: (match_iou, min_hits, max_misses, alpha, beta, damp, smooth), the gains in [0, 256] (1/256), smooth 0 or 1;
+    `MOTION_DEFAULT` holds the library's suggestion for the last four, a choice and not a measurement.
+    -> (state, emitted, status) as `track_step` gives them: a held-over track (misses > 0), and with smooth every track, is emitted with
+    its edges replaced by the filter's position in pixels."""
+    match_iou, min_hits, max_misses = float(params[0]), int(params[1]), int(params[2])
+    alpha, beta, damp, smooth = (int(v) for v in params[3:7])
+    count = len(dets) if count is None else int(count)
+    cap = len(dets) if cap is None else int(cap)
+    lim = min(cap, TRACK_MAX_DETS)
+    m = min(max(count, 0), lim)
+    status = TRACK_CLIPPED if count > lim else 0
+    dets = [tuple(d) for d in dets[:m]]
+    slots = [[s[0], s[1], s[2], s[3], s[4], s[5], list(s[6]), list(s[7])] for s in state["slots"]]
+    issued = int(state["issued"])
+    occupied = [s[0] != 0 for s in slots]
+    # predict: P' = pos + vel, both through the clamp first; the box of the match is P' in pixels
+    pred = {k: [motion_sat(p) + motion_sat(v) for p, v in zip(s[6], s[7])] for k, s in enumerate(slots) if occupied[k]}
+    boxes = {k: (0,) * 6 + tuple(motion_box(p) for p in pp) for k, pp in pred.items()}
+    slot_det, det_slot, ties = _track_match(boxes, dets, match_iou)
+    removals = held = 0
+    for k, s in enumerate(slots):
+        if not occupied[k]:
+            continue
+        s[3] = _track_inc(s[3])
+        vel = [motion_sat(v) for v in s[7]]
+        if k in slot_det:
+            d = dets[slot_det[k]]
+            s[4], s[1], s[2] = d, _track_inc(s[1]), 0
+            res = [256 * int(z) - pp for z, pp in zip(d[6:10], pred[k])]
+            s[6] = [motion_sat(pp + motion_mul(alpha, r)) for pp, r in zip(pred[k], res)]
+            s[7] = [motion_sat(v + motion_mul(beta, r)) for v, r in zip(vel, res)]
+        else:
+            s[2] = _track_inc(s[2])
+            if s[2] > max_misses:
+                slots[k] = [0, 0, 0, 0, _ZERO_DET, 0, [0] * 4, [0] * 4]
+                removals += 1
+            else:
+                s[6] = [motion_sat(pp) for pp in pred[k]]
+                s[7] = [motion_mul(damp, v) for v in vel]
+    births = dropped = 0
+    for j, d in enumerate(dets):
+        if j in det_slot:
+            continue
+        free = [k for k, s in enumerate(slots) if s[0] == 0]
+        if not free:
+            status |= TRACK_DROPPED
+            dropped += 1
+            continue
+        issued = (issued + 1) & 0xFFFFFFFF
+        if issued == 0:
+            issued = 1
+        slots[free[0]] = [issued, 1, 0, 1, d, 0, [256 * int(z) for z in d[6:10]], [0] * 4]
+        births += 1
+    emitted = []
+    for k in sorted((k for k, s in enumerate(slots) if s[0] != 0 and s[1] >= min_hits), key=lambda k: (slots[k][0], k)):
+        i, hits, misses, age, d, _, pos, _ = slots[k]
+        edges = tuple(motion_box(p) for p in pos) if misses > 0 or smooth else tuple(d[6:10])
+        emitted.append(((int(frame),) + tuple(d[1:6]) + edges, (i, hits, misses, age)))
         held += misses > 0
     if stats is not None:
         for name, v in (("matches", len(slot_det)), ("births", births), ("removals", removals), ("held", held), ("ties", ties),
