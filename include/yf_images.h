@@ -494,7 +494,8 @@ YF_API long yf_images_draw_records_yuv_device(void* d_pixels, size_t pixels_byte
  *           lie; a larger count sets bit 0 of the frame's status.  The steps of a stream are taken in order t = 0 .. steps - 1; the
  *           state at d_state[s] is read before the first and written after the last.
  *   params: a host pointer, copied.  A slot's box and a detection match if they share a pixel and their IoU (the suppression's
- *           arithmetic, float64) is >= match_iou (any value but NaN); the match is greedy by descending IoU.  A track is reported once
+ *           arithmetic, float64) is >= match_iou (any value but NaN); the match is greedy by descending IoU (an optimal assignment in
+ *           its place: yf_images_track_motion_assign_device, below).  A track is reported once
  *           it has min_hits >= 1 matches, and kept over max_misses >= 0 frames without one.  The library's suggestion for faces at a
  *           video rate is {0.3, 1, 5}; that is a choice, not something measured.
  *   output: d_out yf_det[n][out_cap], d_info yf_track_info[n][out_cap], d_out_counts int32[n], out_cap >= 1 (64 holds every track).
@@ -536,7 +537,8 @@ YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, l
  *           rounded to pixels; with smooth 1 a matched track too (the filtered box), with smooth 0 it reports its detection verbatim.
  *           A predicted box is not clamped to the picture; the crop, the redaction, the blur and the drawing clip themselves.
  * The input, the layouts, the checks (and alpha, beta, damp, smooth), n = 0, the return value and the error text are the entry's above;
- * one launch, one wave per stream, the state in registers over the stream's steps; asynchronous, no allocation, capturable. */
+ * one launch, one wave per stream, the state in registers over the stream's steps; asynchronous, no allocation, capturable.  Still out
+ * of scope: a covariance, appearance features, re-identification, clamping a predicted box; the optimal assignment is the entry below. */
 typedef struct yf_track_motion        { yf_track base; int32_t pad; int64_t pos[4]; int64_t vel[4]; } yf_track_motion;    /* 112 bytes */
 typedef struct yf_track_motion_state  { uint32_t issued, reserved; yf_track_motion slot[YF_TRACK_SLOTS]; } yf_track_motion_state; /* 7176 bytes per stream */
 typedef struct yf_track_motion_params { yf_track_params base; int32_t alpha, beta, damp, smooth; } yf_track_motion_params;         /* 32 bytes */
@@ -544,6 +546,25 @@ YF_API size_t yf_images_track_motion_state_bytes(long streams);
 YF_API long   yf_images_track_motion_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
                                             const yf_track_motion_params* params, void* d_state, void* d_out, void* d_info,
                                             void* d_out_counts, int out_cap, int32_t* d_status, void* stream);
+
+/* ---- tracking with a motion model and optimal assignment: the entry above with a choice of the match.  Both entries above associate
+ * detections with tracks by the global greedy rule -- repeatedly the eligible pair of the largest IoU --, which costs identities where
+ * two faces pass each other: one detection overlaps both tracks, greedy gives it to the one it overlaps most, the other detection is
+ * stranded: one new id, one track held over.  YF_ASSIGN_OPTIMAL replaces that match by a maximum-weight assignment over the eligible
+ * pairs -- the weight of a pair is its IoU at 2^-30 resolution; maximum total IoU, not cardinality first --, with its ties settled by one
+ * prescribed shortest-augmenting-path procedure in integers, so that the kernel, a host build and Python agree bit for bit.  The
+ * definition is stated once in csrc/yf_images_assign.h (the weights, the procedure, the bound on its potentials).
+ *   assign: YF_ASSIGN_GREEDY: the entry above under another name (its kernel is launched); YF_ASSIGN_OPTIMAL: the above.
+ *   state, input, params, output: the entry's above (7176 bytes per stream); only the match differs.  Gains (256, 0) with
+ *           YF_ASSIGN_OPTIMAL is "the base tracker with optimal assignment": NO ENTRY ON THE 2824-BYTE STATE IS ADDED.
+ * The checks (the entry's above in its order, then assign), n = 0, the return value and the error text are the entry's above; one launch,
+ * one wave per stream, 16 KB of LDS per wave; asynchronous, no allocation, no host synchronisation, capturable.  A frame with m
+ * detections costs at most m (m + 1) / 2 rounds of the search, 2080 at m = 64; a frame without an eligible pair skips it.
+ * Still missing: a covariance, appearance features, re-identification, clamping a predicted box. */
+enum { YF_ASSIGN_GREEDY = 0, YF_ASSIGN_OPTIMAL = 1 };
+YF_API long   yf_images_track_motion_assign_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                                                   const yf_track_motion_params* params, int assign, void* d_state, void* d_out,
+                                                   void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream);
 
 /* ---- letterboxed frames: the picture resized with its aspect kept, centred in the square frame, the rest padded with one grey, and the
  * boxes mapped back through the same rectangle.  Every entry above stretches the picture onto the frame, as the reference's scripts do

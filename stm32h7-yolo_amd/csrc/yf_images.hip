@@ -20,7 +20,8 @@
 // yf_images_blur.h and yf_images_blur.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
 // yf_images_track.h and yf_images_track.hip.h, and with a motion model (a constant-velocity filter per edge, held-over boxes move on) in
-// yf_images_motion.h and yf_images_motion.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
+// yf_images_motion.h and yf_images_motion.hip.h, and with the optimal assignment in the place of the greedy match in yf_images_assign.h and
+// yf_images_assign.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
 // boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h; the area-averaged frames (every source pixel counted, a job per band
 // of a frame) in yf_images_area.h and yf_images_area.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
@@ -48,6 +49,7 @@
 #include "yf_images_draw.hip.h"
 #include "yf_images_track.hip.h"
 #include "yf_images_motion.hip.h"
+#include "yf_images_assign.hip.h"
 #include "yf_images_fit.hip.h"
 #include "yf_images_area.hip.h"
 
@@ -958,6 +960,27 @@ long track_motion(const void* d_dets, const void* d_counts, long streams, long s
   return launched("track_motion kernel launch", n) == n ? n : -1;
 }
 
+// ---- tracking with a motion model and a choice of the match (yf_images_assign.h) ----  the contract of `track`; YF_ASSIGN_GREEDY is
+// `track_motion` and its kernel, YF_ASSIGN_OPTIMAL the kernel of yf_images_assign.hip.h
+long track_motion_assign(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                         const yf_track_motion_params* params, int assign, void* d_state, void* d_out, void* d_info, void* d_out_counts,
+                         int out_cap, int32_t* d_status, void* stream) {
+  const char* err = yfi_assign_check(d_dets, d_counts, streams, steps, layout, cap, params, assign, d_state, d_out, d_info, d_out_counts, out_cap, d_status);
+  if (err) return fail("%s", err) - 1;
+  if (assign == YF_ASSIGN_GREEDY)
+    return track_motion(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
+  const long n = streams * steps;
+  if (n == 0) return 0;
+  yfassign::AssignArgs a{};
+  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
+  a.match_iou = params->base.match_iou; a.min_hits = params->base.min_hits; a.max_misses = params->base.max_misses;
+  a.alpha = params->alpha; a.beta = params->beta; a.damp = params->damp; a.smooth = params->smooth;
+  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
+  a.out_cap = out_cap; a.status = d_status;
+  hipLaunchKernelGGL(yfassign::step_kernel, grid_for(streams, 8), dim3(64), 0, (hipStream_t)stream, a);       // one-wave workgroups, 16 KB of LDS each
+  return launched("track_motion_assign kernel launch", n) == n ? n : -1;
+}
+
 // ---- letterboxed frames (yf_images_fit.h) ----  the prepare kernels by format (the four packed formats in the order of their codes,
 // then NV12, NV21), for a frame side and an element type
 using FitKernel = void (*)(yffit::Args);
@@ -1389,6 +1412,13 @@ YF_API long yf_images_track_motion_device(const void* d_dets, const void* d_coun
                                           const yf_track_motion_params* params, void* d_state, void* d_out, void* d_info,
                                           void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
   return track_motion(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
+}
+
+YF_API long yf_images_track_motion_assign_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
+                                                 const yf_track_motion_params* params, int assign, void* d_state, void* d_out, void* d_info,
+                                                 void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
+  return track_motion_assign(d_dets, d_counts, streams, steps, layout, cap, params, assign, d_state, d_out, d_info, d_out_counts, out_cap, d_status,
+                             stream);
 }
 
 YF_API size_t yf_images_track_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }

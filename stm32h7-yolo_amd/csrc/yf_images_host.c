@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h, the tracker with a motion model of yf_images_motion.h, the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h, the tracker with a motion model of yf_images_motion.h and its optimal assignment of yf_images_assign.h, the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -20,6 +20,7 @@
 #include "yf_images_draw.h"
 #include "yf_images_track.h"
 #include "yf_images_motion.h"
+#include "yf_images_assign.h"
 #include "yf_images_fit.h"
 #include "yf_images_area.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -841,10 +842,29 @@ EXPORT int yfi_track_check_host(const void* dets, const void* counts, long strea
 
 EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
 
+/* ---- yf_images_assign.h ----  the optimal match of one step, with `track_match_host`'s arguments: the table of weights, then the
+ * header's sequential procedure; returns the matching's total weight; `table` (int32[m][64], or NULL) receives the weights */
+static int64_t assign_match_host(int32_t (*box)[4], const int* occupied, const yf_det* dets, int m, double match_iou, int* slot_det,
+                                 int* det_slot, int32_t* table) {
+  static _Thread_local int32_t w[YF_TRACK_MAX_DETS * YF_TRACK_SLOTS];
+  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
+    const double area_a = yfi_nms_area(box[s][0], box[s][1], box[s][2], box[s][3]);
+    for (int j = 0; j < m; ++j) {
+      const yf_det* d = &dets[j];
+      double iou;
+      const int ok = yfi_track_iou(box[s][0], box[s][1], box[s][2], box[s][3], area_a, d->x1, d->y1, d->x2, d->y2,
+                                   yfi_nms_area(d->x1, d->y1, d->x2, d->y2), match_iou, &iou);
+      w[j * YF_TRACK_SLOTS + s] = yfi_assign_weight(ok && occupied[s], iou);
+    }
+  }
+  if (table) memcpy(table, w, sizeof(int32_t) * (size_t)m * YF_TRACK_SLOTS);
+  return yfi_assign_solve(w, m, slot_det, det_slot);
+}
+
 /* ---- yf_images_motion.h ----  yf_images_track_motion_device as the header states it, on host memory: the step above with the
  * prediction in front of the match and the filter in the update.  A free slot's bytes are neither read (but its id) nor written. */
 static void motion_step_host(yf_track_motion_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_motion_params* p,
-                             int32_t frame, yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
+                             int assign, int32_t frame, yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
   const int m = yfi_track_clamp(count, cap);
   int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
   int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
@@ -858,7 +878,8 @@ static void motion_step_host(yf_track_motion_state* st, const yf_det* dets, int3
       box[s][e] = yfi_motion_box(pp[s][e]);
     }
   }
-  track_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot);
+  if (assign == YF_ASSIGN_OPTIMAL) assign_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot, NULL);
+  else track_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot);
   for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
     yf_track_motion* k = &st->slot[s];
     if (!occupied[s]) continue;
@@ -932,7 +953,7 @@ EXPORT long yf_images_track_motion_host(const void* dets, const void* counts, lo
     for (long t = 0; t < steps; ++t) {
       const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
       motion_step_host((yf_track_motion_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
-                       (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
+                       YF_ASSIGN_GREEDY, (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
                        (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
     }
   return streams * steps;
@@ -947,6 +968,44 @@ EXPORT int yfi_motion_check_host(const void* dets, const void* counts, long stre
 }
 
 EXPORT size_t yf_images_track_motion_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_motion_state) : 0; }
+
+/* ---- yf_images_assign.h ----  yf_images_track_motion_assign_device as the header states it, on host memory: the entry above with
+ * the match chosen by `assign` */
+EXPORT long yf_images_track_motion_assign_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                               const yf_track_motion_params* params, int assign, void* state, void* out, void* info,
+                                               void* out_counts, int out_cap, int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_assign_check(dets, counts, streams, steps, layout, cap, params, assign, state, out, info, out_counts, out_cap, status) != NULL) return -1;
+  const yf_track_motion_params p = *params;
+  for (long s = 0; s < streams; ++s)
+    for (long t = 0; t < steps; ++t) {
+      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
+      motion_step_host((yf_track_motion_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
+                       assign, (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
+                       (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
+    }
+  return streams * steps;
+}
+
+EXPORT int yfi_assign_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                 const yf_track_motion_params* params, int assign, const void* state, const void* out, const void* info,
+                                 const void* out_counts, int out_cap, const void* status, char* text, int text_bytes) {
+  const char* t = yfi_assign_check(dets, counts, streams, steps, layout, cap, params, assign, state, out, info, out_counts, out_cap, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+/* the match alone: boxes int32[64][4] of the slots, occupied int[64], dets yf_det[m], m <= 64 -> slot_det int[64], det_slot int[m] (-1:
+ * none); returns the total weight.  With weights (int32[m][64], or NULL) the table is written too. */
+EXPORT int64_t yfi_assign_match_host(const int32_t* boxes, const int* occupied, const void* dets, int m, double match_iou, int* slot_det,
+                                     int* det_slot, int32_t* weights) {
+  int32_t box[YF_TRACK_SLOTS][4];
+  memcpy(box, boxes, sizeof box);
+  return assign_match_host(box, occupied, (const yf_det*)dets, m, match_iou, slot_det, det_slot, weights);
+}
+
+/* the procedure alone on a table of weights int32[m][64] */
+EXPORT int64_t yfi_assign_solve_host(const int32_t* weights, int m, int* slot_det, int* det_slot) { return yfi_assign_solve(weights, m, slot_det, det_slot); }
 
 /* the filter's helpers as they are (no range check: the tests ask for what the definition gives) */
 EXPORT int64_t yfi_motion_mul_host(int32_t g, int64_t v) { return yfi_motion_mul(g, v); }

@@ -42,8 +42,9 @@
  * measurement -- no accuracy or identity-switch figure on real video stands behind it.
  *
  * STILL OUT OF SCOPE.  No covariance (this is not a Kalman filter: the gains are fixed).  No appearance features.  No re-identification
- * after a track is removed.  No optimal (Hungarian) assignment.  A predicted box is not clamped to the picture: it may leave it; the
- * crop, the redaction, the blur and the drawing clip to the picture themselves. */
+ * after a track is removed.  No optimal assignment HERE: the match is the greedy one; the entry beside this one, yf_images_assign.h
+ * (yf_images_track_motion_assign_device), puts a maximum-weight assignment in its place.  A predicted box is not clamped to the
+ * picture: it may leave it; the crop, the redaction, the blur and the drawing clip to the picture themselves. */
 #ifndef YF_IMAGES_MOTION_H
 #define YF_IMAGES_MOTION_H
 #include "yf_images_track.h"

@@ -40,7 +40,8 @@
  *
  * OUT OF SCOPE.  No motion model HERE: a held-over box stays where it was last seen; the entry beside this one, yf_images_motion.h
  * (yf_images_track_motion_device), adds a constant-velocity filter per edge.  No appearance features.  No re-identification after a
- * track is removed: the face gets a new id.  No optimal (Hungarian) assignment: the match is the greedy one above. */
+ * track is removed: the face gets a new id.  No optimal assignment HERE: the match is the greedy one above; yf_images_assign.h
+ * (yf_images_track_motion_assign_device) puts a maximum-weight assignment in its place, on the motion entry's state. */
 #ifndef YF_IMAGES_TRACK_H
 #define YF_IMAGES_TRACK_H
 #include <stddef.h>

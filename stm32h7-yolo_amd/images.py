@@ -50,8 +50,11 @@ box -- a moving face stays hidden on the frames the detector misses it, and keep
 first, which does not change; the definition is the library's own (csrc/yf_images_motion.h, `ptq.track_motion_step`).  The gains
 (alpha, beta, damp) are in 1/256; `MOTION_GAINS` = (192, 128, 256) is the library's suggestion, a choice and not a measurement: there is
 no accuracy or identity-switch figure for real video.  (256, 0, any) is the tracker without the model, byte for byte.  Still out of scope:
-a covariance (a Kalman filter), appearance features, re-identification, optimal assignment, clamping a predicted box to the picture (the
-crop, the redaction, the blur and the drawing clip themselves).  `detect_tracked`, `detect_drawn`, `detect_redacted` and `detect_blurred`
+a covariance (a Kalman filter), appearance features, re-identification, clamping a predicted box to the picture (the crop, the
+redaction, the blur and the drawing clip themselves).  `Tracker(..., assign="optimal")` replaces the greedy match -- repeatedly the pair
+of the largest IoU, which strands a detection where two faces pass each other -- by the maximum-weight assignment over the eligible
+pairs, `track_motion_assign_device` (csrc/yf_images_assign.h, `ptq.track_assign_match`); it runs on the 7176-byte state with or
+without `motion`.  `detect_tracked`, `detect_drawn`, `detect_redacted` and `detect_blurred`
 take such a tracker as they take the plain one; with a tracker the last two hide the REPORTED TRACKS, held-over ones included.
 
 `fit="letterbox"` on `detect`, every `detect_*` call and `evaluate` replaces the stretch onto the square frame by what every mainstream
@@ -154,6 +157,11 @@ class YfTrackMotionParams(ctypes.Structure):
 TRACK_MOTION_STATE_BYTES = 7176
 MOTION_GAINS = (192, 128, 256)                 # (alpha, beta, damp): the library's suggestion -- a choice, not a measurement
 assert ctypes.sizeof(YfTrackMotionParams) == 32
+# the match of the tracker with a motion model (yf_images_track_motion_assign_device): the global greedy one, or the optimal assignment
+YF_ASSIGN_GREEDY, YF_ASSIGN_OPTIMAL = 0, 1
+ASSIGNS = {"greedy": YF_ASSIGN_GREEDY, "optimal": YF_ASSIGN_OPTIMAL}
+ASSIGN_NAMES = {code: name for name, code in ASSIGNS.items()}
+ASSIGN_WHAT = "assign {!r}: 'greedy' (repeatedly the pair of the largest IoU) or 'optimal' (the maximum total IoU)"
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -244,6 +252,8 @@ def _entries():
         # d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream
         "track_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
         "track_motion_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
+        # ... with assign after params
+        "track_motion_assign_device": [vp, vp, cl, cl, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp],
         # letterboxed frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] pad, d_frames, d_status, stream
         "prepare_fit_ragged_device": ragged + [ci, ci, vp, vp, vp],
         "prepare_fit_yuv_ragged_device": ragged + [ci, ci, vp, vp, vp],
@@ -1310,6 +1320,23 @@ def track_motion_device(d_dets, d_counts, streams, steps, layout, cap, params, d
     return rc
 
 
+def track_motion_assign_device(d_dets, d_counts, streams, steps, layout, cap, params, assign, d_state, d_out, d_info, d_out_counts, out_cap,
+                               d_status=None, stream=None):
+    """`track_motion_device` with a choice of the match (yf_images_track_motion_assign_device): assign "greedy", that entry under another
+    name; "optimal", the maximum-weight assignment over the eligible pairs -- maximum total IoU at 2^-30 resolution, its ties settled
+    by one prescribed procedure -- in the place of the greedy match, so that two faces passing each other keep their ids where greedy
+    strands one detection.  The state is `track_motion_state_bytes`' (7176 bytes per stream).  The definition:
+    csrc/yf_images_assign.h, ptq.track_assign_match, ptq.track_motion_step(assign="optimal").  Returns n."""
+    lib = load()
+    p = YfTrackMotionParams(YfTrackParams(float(params[0]), int(params[1]), int(params[2])), *(int(v) for v in params[3:7]))
+    code = _code(ASSIGNS, assign, ASSIGN_WHAT)
+    rc = lib.yf_images_track_motion_assign_device(d_dets, d_counts, streams, steps, _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT), cap, ctypes.byref(p),
+                                                  code, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream)
+    if rc != streams * steps or rc < 0:
+        raise ImagesError(f"yf_images_track_motion_assign_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
+    return rc
+
+
 class Tracker:
     """The track state of `streams` video streams on the device, and the parameters of their association.  match_iou=0.3, min_hits=1,
     max_misses=5 are the library's choice for faces at a video rate -- a box that moved by less than about half its side still matches,
@@ -1318,13 +1345,18 @@ class Tracker:
     `motion`: None, the tracker as it is -- a held-over box stays where it was last seen (`track_device`, 2824 bytes per stream); True, a
     constant-velocity filter per edge at the suggested gains `MOTION_GAINS` (a choice, not a measurement), or a triple (alpha, beta,
     damp) in 1/256 -- a held-over box moves on and the match is taken against the predicted box (`track_motion_device`, 7176 bytes per
-    stream).  `smooth` (with motion): a matched track reports its filtered box, not its detection."""
+    stream).  `smooth` (with motion): a matched track reports its filtered box, not its detection.
+    `assign`: "greedy", the match as it is; "optimal", the maximum-weight assignment of csrc/yf_images_assign.h in its place
+    (`track_motion_assign_device`): two faces that pass each other keep their ids where greedy strands a detection.  With motion=None
+    it runs on the motion state at gains (256, 0, 256, 0) -- the plain tracker's results with the other match -- SO THE STATE IS THEN 7176
+    BYTES PER STREAM, not 2824 (`self.motion` stays None)."""
 
-    def __init__(self, streams, match_iou=0.3, min_hits=1, max_misses=5, device=None, motion=None, smooth=False):
+    def __init__(self, streams, match_iou=0.3, min_hits=1, max_misses=5, device=None, motion=None, smooth=False, assign="greedy"):
         import torch
         if int(streams) < 1:
             raise ValueError(f"streams {streams!r}: at least 1")
         self.params = (float(match_iou), int(min_hits), int(max_misses))
+        self.assign = ASSIGN_NAMES[_code(ASSIGNS, assign, ASSIGN_WHAT)]
         if motion is None or motion is False:
             if smooth:
                 raise ValueError("smooth: only with motion")
@@ -1342,7 +1374,7 @@ class Tracker:
         import torch
         if streams is not None:
             self.streams = int(streams)
-            state_bytes = TRACK_STATE_BYTES if self.motion is None else TRACK_MOTION_STATE_BYTES
+            state_bytes = TRACK_STATE_BYTES if self.motion is None and self.assign == "greedy" else TRACK_MOTION_STATE_BYTES
             self.d_state = torch.zeros((self.streams, state_bytes), dtype=torch.uint8, device=self.device)
         else:
             self.d_state.zero_()
@@ -1360,7 +1392,12 @@ class Tracker:
         d_status = torch.empty(n, dtype=torch.int32, device=self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.motion is None:
+        if self.assign == "optimal":
+            track_motion_assign_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap,
+                                       self.params + ((256, 0, 256, 0) if self.motion is None else self.motion), "optimal",
+                                       self.d_state.data_ptr(), d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap,
+                                       d_status.data_ptr(), stream)
+        elif self.motion is None:
             track_device(d_dets.data_ptr(), d_counts.data_ptr(), self.streams, int(steps), layout, cap, self.params, self.d_state.data_ptr(),
                          d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap, d_status.data_ptr(), stream)
         else:

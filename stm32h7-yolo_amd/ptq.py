@@ -831,14 +831,96 @@ def motion_box(p):
     return max(_INT32_MIN, min(_INT32_MAX, (int(p) + 128) // 256))
 
 
-def track_motion_step(state, dets, params, count=None, cap=None, frame=0, stats=None):
+# ---- the optimal assignment (csrc/yf_images_assign.h), in plain Python integers ----
+ASSIGN_TOP = 2 ** 30 + 1                     # the largest weight; cost = ASSIGN_TOP - weight
+ASSIGNS = ("greedy", "optimal")
+
+
+def track_assign_weights(boxes, dets, match_iou):
+    """the table of weights of one step: w[i][j] of detection i and slot j < 64 -- 1 + int(iou * 2^30) (the product exact, the conversion
+    truncating) for an eligible pair (inter > 0.0 and iou >= match_iou), 0 otherwise and for every slot not in `boxes`"""
+    w = [[0] * TRACK_SLOTS for _ in dets]
+    for k, box in boxes.items():
+        for i, d in enumerate(dets):
+            iou = track_iou(box, d)[1]
+            if iou is not None and iou >= match_iou:
+                w[i][k] = 1 + int(iou * 1073741824.0)
+    return w
+
+
+def track_assign_solve(w, stats=None):
+    """yfi_assign_solve: the maximum-weight assignment of the rows of w (detections, at most 64) to its 64 columns (slots) by the
+    shortest-augmenting-path procedure csrc/yf_images_assign.h prescribes -- rows in ascending order, cost ASSIGN_TOP - w, potentials
+    from 0, a strict comparison in the relaxation, the LOWEST column attaining the minimum -- -> (slot_det, det_slot, total_weight); a
+    row assigned to a column of weight 0 is unmatched.  The procedure is the definition: it settles which of several optima is taken.
+    `stats`: a dict whose counter "rounds" (the repetitions of the search, at most m (m + 1) / 2) is added to and whose "potential" is
+    raised to the largest |u|, |v| met, "path" to the columns of the longest augmenting path."""
+    m, inf = len(w), 1 << 62
+    rounds = bound = longest = 0
+    u, v, p = [0] * m, [0] * TRACK_SLOTS, [-1] * TRACK_SLOTS
+    for i in range(m):
+        minv, used, way = [inf] * TRACK_SLOTS, [False] * TRACK_SLOTS, [-1] * TRACK_SLOTS
+        visited = [r == i for r in range(m)]
+        i0, j0 = i, -1
+        while True:
+            for j in range(TRACK_SLOTS):
+                if not used[j]:
+                    cur = (ASSIGN_TOP - w[i0][j]) - u[i0] - v[j]
+                    if cur < minv[j]:
+                        minv[j], way[j] = cur, j0
+            delta, j1 = inf, -1
+            for j in range(TRACK_SLOTS):
+                if not used[j] and minv[j] < delta:
+                    delta, j1 = minv[j], j
+            for r in range(m):
+                if visited[r]:
+                    u[r] += delta
+            for j in range(TRACK_SLOTS):
+                if used[j]:
+                    v[j] -= delta
+                else:
+                    minv[j] -= delta
+            rounds += 1
+            bound = max(bound, max(u, default=0), -min(v))
+            j0 = j1
+            if p[j0] < 0:
+                break
+            used[j0], i0 = True, p[j0]
+            visited[i0] = True
+        length = 0
+        while j0 >= 0:
+            j1 = way[j0]
+            p[j0] = p[j1] if j1 >= 0 else i
+            j0 = j1
+            length += 1
+        longest = max(longest, length)
+    if stats is not None:
+        stats["rounds"] = stats.get("rounds", 0) + rounds
+        stats["potential"] = max(stats.get("potential", 0), bound)
+        stats["path"] = max(stats.get("path", 0), longest)
+    slot_det = {j: p[j] for j in range(TRACK_SLOTS) if p[j] >= 0 and w[p[j]][j] > 0}
+    det_slot = {i: j for j, i in slot_det.items()}
+    return slot_det, det_slot, sum(w[i][j] for j, i in slot_det.items())
+
+
+def track_assign_match(boxes, dets, match_iou):
+    """the optimal match of one step, with `_track_match`'s arguments: the maximum total weight over the eligible pairs -- maximum total
+    IoU at 2^-30 resolution, not cardinality first -- -> (slot_det, det_slot, total_weight) in plain Python integers"""
+    return track_assign_solve(track_assign_weights(boxes, dets, match_iou))
+
+
+def track_motion_step(state, dets, params, count=None, cap=None, frame=0, stats=None, assign="greedy"):
     """One step of the tracker with a motion model -- one stream, one frame -- as csrc/yf_images_motion.h states it: `track_step` with a
     constant-velocity g-h filter on every edge, in Python integers (the IoU of the match stays float64).  `state`: as
     `track_motion_empty_state` gives it (not changed; the new state is returned).  `dets`, `count`, `cap`, `frame`, `stats`: as in
     `track_step`.  `params`: (match_iou, min_hits, max_misses, alpha, beta, damp, smooth), the gains in [0, 256] (1/256), smooth 0 or 1;
     `MOTION_DEFAULT` holds the library's suggestion for the last four, a choice and not a measurement.
     -> (state, emitted, status) as `track_step` gives them: a held-over track (misses > 0), and with smooth every track, is emitted with
-    its edges replaced by the filter's position in pixels."""
+    its edges replaced by the filter's position in pixels.
+    `assign`: "greedy", the match of `track_step`; "optimal", `track_assign_match` in its place (csrc/yf_images_assign.h; the counter
+    "ties" is then not added to)."""
+    if assign not in ASSIGNS:
+        raise ValueError(f"assign {assign!r}: 'greedy' or 'optimal'")
     match_iou, min_hits, max_misses = float(params[0]), int(params[1]), int(params[2])
     alpha, beta, damp, smooth = (int(v) for v in params[3:7])
     count = len(dets) if count is None else int(count)
@@ -853,7 +935,10 @@ def track_motion_step(state, dets, params, count=None, cap=None, frame=0, stats=
     # predict: P' = pos + vel, both through the clamp first; the box of the match is P' in pixels
     pred = {k: [motion_sat(p) + motion_sat(v) for p, v in zip(s[6], s[7])] for k, s in enumerate(slots) if occupied[k]}
     boxes = {k: (0,) * 6 + tuple(motion_box(p) for p in pp) for k, pp in pred.items()}
-    slot_det, det_slot, ties = _track_match(boxes, dets, match_iou)
+    if assign == "optimal":
+        slot_det, det_slot, ties = track_assign_match(boxes, dets, match_iou)[:2] + (0,)
+    else:
+        slot_det, det_slot, ties = _track_match(boxes, dets, match_iou)
     removals = held = 0
     for k, s in enumerate(slots):
         if not occupied[k]:
