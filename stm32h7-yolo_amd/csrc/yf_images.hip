@@ -19,9 +19,9 @@
 // yf_images_redact.h and yf_images_redact.hip.h; the blur (every record's region replaced by a grid of its means resized back) in
 // yf_images_blur.h and yf_images_blur.hip.h; the drawing (every record's outline in place, in one colour or a colour per record) in
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
-// yf_images_track.h and yf_images_track.hip.h, and with a motion model (a constant-velocity filter per edge, held-over boxes move on) in
-// yf_images_motion.h and yf_images_motion.hip.h, and with the optimal assignment in the place of the greedy match in yf_images_assign.h and
-// yf_images_assign.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
+// yf_images_track.h, with a motion model (a constant-velocity filter per edge, held-over boxes move on) in yf_images_motion.h, and with
+// the optimal assignment in the place of the greedy match in yf_images_assign.h, the three kernels one step body in
+// yf_images_step.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
 // boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h; the area-averaged frames (every source pixel counted, a job per band
 // of a frame) in yf_images_area.h and yf_images_area.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
@@ -47,9 +47,7 @@
 #include "yf_images_redact.hip.h"
 #include "yf_images_blur.hip.h"
 #include "yf_images_draw.hip.h"
-#include "yf_images_track.hip.h"
-#include "yf_images_motion.hip.h"
-#include "yf_images_assign.hip.h"
+#include "yf_images_step.hip.h"
 #include "yf_images_fit.hip.h"
 #include "yf_images_area.hip.h"
 
@@ -927,41 +925,47 @@ long draw_records(void* d_pixels, size_t pixels_bytes, int format, const void* d
   return launched("draw_records kernel launches", n);
 }
 
-// ---- tracking (yf_images_track.h) ----  -1 and the text: here 0 is a valid number of frames
+// ---- tracking (yf_images_track.h, yf_images_motion.h, yf_images_assign.h) ----  what the three entries do behind their checks: `a` comes
+// with what its kernel alone takes (the gains), gets what every step kernel takes, and is launched on one-wave workgroups of which
+// `per_cu` fit on a CU.  -1 and the text: here 0 is a valid number of frames
+template <class A>
+long track_launch(void (*kernel)(A), A a, int per_cu, const char* what, const void* d_dets, const void* d_counts, long streams, long steps,
+                  int layout, int cap, const yf_track_params& p, void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap,
+                  int32_t* d_status, void* stream) {
+  const long n = streams * steps;
+  if (n == 0) return 0;
+  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
+  a.match_iou = p.match_iou; a.min_hits = p.min_hits; a.max_misses = p.max_misses;
+  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
+  a.out_cap = out_cap; a.status = d_status;
+  hipLaunchKernelGGL(kernel, grid_for(streams, per_cu), dim3(64), 0, (hipStream_t)stream, a);
+  return launched(what, n) == n ? n : -1;
+}
+
+yfstep::MotionArgs gains_of(const yf_track_motion_params* p) {
+  yfstep::MotionArgs a{};
+  a.alpha = p->alpha; a.beta = p->beta; a.damp = p->damp; a.smooth = p->smooth;
+  return a;
+}
+
 long track(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap, const yf_track_params* params,
            void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
   const char* err = yfi_track_check(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status);
   if (err) return fail("%s", err) - 1;
-  const long n = streams * steps;
-  if (n == 0) return 0;
-  yftrack::Args a{};
-  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
-  a.match_iou = params->match_iou; a.min_hits = params->min_hits; a.max_misses = params->max_misses;
-  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
-  a.out_cap = out_cap; a.status = d_status;
-  hipLaunchKernelGGL(yftrack::step_kernel, grid_for(streams, 16), dim3(64), 0, (hipStream_t)stream, a);       // one-wave workgroups, no LDS
-  return launched("track kernel launch", n) == n ? n : -1;
+  return track_launch(yftrack::step_kernel, yfstep::Args{}, yfstep::kPerCuTrack, "track kernel launch", d_dets, d_counts, streams, steps, layout,
+                      cap, *params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
 }
 
-// ---- tracking with a motion model (yf_images_motion.h) ----  the contract of `track`
+// with a motion model: the contract of `track`
 long track_motion(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap, const yf_track_motion_params* params,
                   void* d_state, void* d_out, void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
   const char* err = yfi_motion_check(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status);
   if (err) return fail("%s", err) - 1;
-  const long n = streams * steps;
-  if (n == 0) return 0;
-  yfmotion::Args a{};
-  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
-  a.match_iou = params->base.match_iou; a.min_hits = params->base.min_hits; a.max_misses = params->base.max_misses;
-  a.alpha = params->alpha; a.beta = params->beta; a.damp = params->damp; a.smooth = params->smooth;
-  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
-  a.out_cap = out_cap; a.status = d_status;
-  hipLaunchKernelGGL(yfmotion::step_kernel, grid_for(streams, 16), dim3(64), 0, (hipStream_t)stream, a);      // one-wave workgroups, no LDS
-  return launched("track_motion kernel launch", n) == n ? n : -1;
+  return track_launch(yfmotion::step_kernel, gains_of(params), yfstep::kPerCuMotion, "track_motion kernel launch", d_dets, d_counts, streams,
+                      steps, layout, cap, params->base, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
 }
 
-// ---- tracking with a motion model and a choice of the match (yf_images_assign.h) ----  the contract of `track`; YF_ASSIGN_GREEDY is
-// `track_motion` and its kernel, YF_ASSIGN_OPTIMAL the kernel of yf_images_assign.hip.h
+// with a motion model and a choice of the match: the contract of `track`; YF_ASSIGN_GREEDY is `track_motion` and its kernel
 long track_motion_assign(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
                          const yf_track_motion_params* params, int assign, void* d_state, void* d_out, void* d_info, void* d_out_counts,
                          int out_cap, int32_t* d_status, void* stream) {
@@ -969,16 +973,8 @@ long track_motion_assign(const void* d_dets, const void* d_counts, long streams,
   if (err) return fail("%s", err) - 1;
   if (assign == YF_ASSIGN_GREEDY)
     return track_motion(d_dets, d_counts, streams, steps, layout, cap, params, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
-  const long n = streams * steps;
-  if (n == 0) return 0;
-  yfassign::AssignArgs a{};
-  a.dets = (const yf_det*)d_dets; a.counts = (const int*)d_counts; a.streams = streams; a.steps = steps; a.layout = layout; a.cap = cap;
-  a.match_iou = params->base.match_iou; a.min_hits = params->base.min_hits; a.max_misses = params->base.max_misses;
-  a.alpha = params->alpha; a.beta = params->beta; a.damp = params->damp; a.smooth = params->smooth;
-  a.state = (uint32_t*)d_state; a.out = (yf_det*)d_out; a.info = (yf_track_info*)d_info; a.out_counts = (int*)d_out_counts;
-  a.out_cap = out_cap; a.status = d_status;
-  hipLaunchKernelGGL(yfassign::step_kernel, grid_for(streams, 8), dim3(64), 0, (hipStream_t)stream, a);       // one-wave workgroups, 16 KB of LDS each
-  return launched("track_motion_assign kernel launch", n) == n ? n : -1;
+  return track_launch(yfassign::step_kernel, gains_of(params), yfstep::kPerCuAssign, "track_motion_assign kernel launch", d_dets, d_counts,
+                      streams, steps, layout, cap, params->base, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
 }
 
 // ---- letterboxed frames (yf_images_fit.h) ----  the prepare kernels by format (the four packed formats in the order of their codes,

@@ -1,6 +1,6 @@
 /* Optimal assignment of detections to tracks: the tracker with a motion model of yf_images_motion.h with the match of its step 3 replaced
  * by a maximum-weight assignment over the eligible pairs (yf_images_track_motion_assign_device), shared by the device kernel
- * (yf_images_assign.hip.h), the host entry in yf_images.hip, a host build (yf_images_host.c, which tests/test_track_assign_host.py checks
+ * (yf_images_step.hip.h), the host entry in yf_images.hip, a host build (yf_images_host.c, which tests/test_track_assign_host.py checks
  * against ptq.track_assign_match and ptq.track_motion_step(assign="optimal")) and a sanitizer program
  * (tests/csrc/track_assign_sanitize_main.c).  Plain C.
  *

@@ -754,94 +754,6 @@ static void track_match_host(int32_t (*box)[4], const int* occupied, const yf_de
   }
 }
 
-/* ---- yf_images_track.h ----  yf_images_track_device as the header states it, on host memory (`stream` is not used): stream by stream,
- * step by step, literally -- the table of the eligible pairs' IoUs, then round after round the largest entry among the slots and
- * detections still unmatched (a scan in ascending detection, then ascending slot, with a strict comparison: the tie rule), the update,
- * the births, and the output by a selection of the smallest (id, slot) not yet emitted.  Returns n, or -1 for arguments the device entry
- * refuses. */
-static void track_step_host(yf_track_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_params* p, int32_t frame,
-                            yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
-  const int m = yfi_track_clamp(count, cap);
-  int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
-  int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
-  int32_t box[YF_TRACK_SLOTS][4];
-  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
-    const yf_track* k = &st->slot[s];
-    occupied[s] = k->id != 0;
-    box[s][0] = k->det.x1; box[s][1] = k->det.y1; box[s][2] = k->det.x2; box[s][3] = k->det.y2;
-  }
-  track_match_host(box, occupied, dets, m, p->match_iou, slot_det, det_slot);
-  for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
-    yf_track* k = &st->slot[s];
-    if (!occupied[s]) continue;
-    k->age = yfi_track_inc(k->age);
-    if (slot_det[s] >= 0) {
-      k->det = dets[slot_det[s]];
-      k->hits = yfi_track_inc(k->hits);
-      k->misses = 0;
-    } else {
-      k->misses = yfi_track_inc(k->misses);
-      if (k->misses > p->max_misses) memset(k, 0, sizeof *k);
-    }
-  }
-  int s = 0;
-  for (int j = 0; j < m; ++j) {
-    if (det_slot[j] >= 0) continue;
-    while (s < YF_TRACK_SLOTS && st->slot[s].id != 0) ++s;
-    if (s == YF_TRACK_SLOTS) { bits |= YFI_TRACK_ST_DROPPED; break; }
-    yf_track* k = &st->slot[s];
-    st->issued = yfi_track_next_id(st->issued, 0);
-    k->id = st->issued; k->hits = 1; k->misses = 0; k->age = 1; k->det = dets[j];
-  }
-  int emitted[YF_TRACK_SLOTS] = {0}, total = 0;
-  for (;;) {
-    int pick = -1;
-    for (int q = 0; q < YF_TRACK_SLOTS; ++q) {
-      const yf_track* k = &st->slot[q];
-      if (emitted[q] || k->id == 0 || k->hits < p->min_hits) continue;
-      if (pick < 0 || k->id < st->slot[pick].id) pick = q;
-    }
-    if (pick < 0) break;
-    emitted[pick] = 1;
-    if (total < out_cap) {
-      const yf_track* k = &st->slot[pick];
-      out[total] = k->det;
-      out[total].frame = frame;
-      info[total].id = k->id; info[total].hits = k->hits; info[total].misses = k->misses; info[total].age = k->age;
-    }
-    ++total;
-  }
-  *out_count = total;
-  if (status) *status = bits;
-}
-
-EXPORT long yf_images_track_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
-                                 const yf_track_params* params, void* state, void* out, void* info, void* out_counts, int out_cap,
-                                 int32_t* status, void* stream) {
-  (void)stream;
-  if (yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status) != NULL) return -1;
-  const yf_track_params p = *params;
-  for (long s = 0; s < streams; ++s)
-    for (long t = 0; t < steps; ++t) {
-      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
-      track_step_host((yf_track_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
-                      (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
-                      (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
-    }
-  return streams * steps;
-}
-
-/* the argument check alone: the text of the first fault into text (at most text_bytes, 0-terminated), or an empty text; returns 1 for a fault */
-EXPORT int yfi_track_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
-                                const yf_track_params* params, const void* state, const void* out, const void* info, const void* out_counts,
-                                int out_cap, const void* status, char* text, int text_bytes) {
-  const char* t = yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status);
-  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
-  return t != NULL;
-}
-
-EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
-
 /* ---- yf_images_assign.h ----  the optimal match of one step, with `track_match_host`'s arguments: the table of weights, then the
  * header's sequential procedure; returns the matching's total weight; `table` (int32[m][64], or NULL) receives the weights */
 static int64_t assign_match_host(int32_t (*box)[4], const int* occupied, const yf_det* dets, int m, double match_iou, int* slot_det,
@@ -861,81 +773,98 @@ static int64_t assign_match_host(int32_t (*box)[4], const int* occupied, const y
   return yfi_assign_solve(w, m, slot_det, det_slot);
 }
 
-/* ---- yf_images_motion.h ----  yf_images_track_motion_device as the header states it, on host memory: the step above with the
- * prediction in front of the match and the filter in the update.  A free slot's bytes are neither read (but its id) nor written. */
-static void motion_step_host(yf_track_motion_state* st, const yf_det* dets, int32_t count, int cap, const yf_track_motion_params* p,
-                             int assign, int32_t frame, yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap, int32_t* status) {
+/* ---- yf_images_track.h, yf_images_motion.h, yf_images_assign.h ----  one step of a stream as the headers state it, literally, on
+ * either state: mp NULL is the base tracker (yf_track_state, the greedy match on the slot's last record), mp given the tracker with a
+ * motion model (yf_track_motion_state, whose slot begins with the base slot: the prediction in front of the match chosen by `assign`,
+ * the filter in the update).  The match -- for the greedy one the table of the eligible pairs' IoUs, then round after round the largest
+ * entry among the slots and detections still unmatched (a scan in ascending detection, then ascending slot, with a strict comparison: the
+ * tie rule) --, the update, the births, and the output by a selection of the smallest (id, slot) not yet emitted.  A free slot's bytes
+ * are neither read (but its id) nor written. */
+static void track_step_host(void* state, const yf_track_params* p, const yf_track_motion_params* mp, int assign, const yf_det* dets,
+                            int32_t count, int cap, int32_t frame, yf_det* out, yf_track_info* info, int32_t* out_count, int out_cap,
+                            int32_t* status) {
   const int m = yfi_track_clamp(count, cap);
   int bits = yfi_track_clipped(count, cap) ? YFI_TRACK_ST_CLIPPED : 0;
   int slot_det[YF_TRACK_SLOTS], det_slot[YF_TRACK_MAX_DETS], occupied[YF_TRACK_SLOTS];
   int32_t box[YF_TRACK_SLOTS][4];
   int64_t pp[YF_TRACK_SLOTS][4];
+  yf_track* slot[YF_TRACK_SLOTS];                                    /* the base slot, and where there is one its motion model */
+  yf_track_motion* mo[YF_TRACK_SLOTS];
+  uint32_t* issued = mp ? &((yf_track_motion_state*)state)->issued : &((yf_track_state*)state)->issued;
   for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
-    const yf_track_motion* k = &st->slot[s];
-    occupied[s] = k->base.id != 0;
+    mo[s] = mp ? &((yf_track_motion_state*)state)->slot[s] : NULL;
+    slot[s] = mp ? &mo[s]->base : &((yf_track_state*)state)->slot[s];
+    const yf_track* k = slot[s];
+    const int32_t last[4] = {k->det.x1, k->det.y1, k->det.x2, k->det.y2};
+    occupied[s] = k->id != 0;
     for (int e = 0; e < 4; ++e) {
-      pp[s][e] = occupied[s] ? yfi_motion_sat(k->pos[e]) + yfi_motion_sat(k->vel[e]) : 0;
-      box[s][e] = yfi_motion_box(pp[s][e]);
+      pp[s][e] = mp && occupied[s] ? yfi_motion_sat(mo[s]->pos[e]) + yfi_motion_sat(mo[s]->vel[e]) : 0;
+      box[s][e] = mp ? yfi_motion_box(pp[s][e]) : last[e];
     }
   }
-  if (assign == YF_ASSIGN_OPTIMAL) assign_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot, NULL);
-  else track_match_host(box, occupied, dets, m, p->base.match_iou, slot_det, det_slot);
+  if (assign == YF_ASSIGN_OPTIMAL) assign_match_host(box, occupied, dets, m, p->match_iou, slot_det, det_slot, NULL);
+  else track_match_host(box, occupied, dets, m, p->match_iou, slot_det, det_slot);
   for (int s = 0; s < YF_TRACK_SLOTS; ++s) {
-    yf_track_motion* k = &st->slot[s];
+    yf_track* k = slot[s];
     if (!occupied[s]) continue;
-    k->base.age = yfi_track_inc(k->base.age);
+    k->age = yfi_track_inc(k->age);
     if (slot_det[s] >= 0) {
       const yf_det* d = &dets[slot_det[s]];
       const int32_t z[4] = {d->x1, d->y1, d->x2, d->y2};
-      k->base.det = *d;
-      k->base.hits = yfi_track_inc(k->base.hits);
-      k->base.misses = 0;
-      for (int e = 0; e < 4; ++e) {
+      k->det = *d;
+      k->hits = yfi_track_inc(k->hits);
+      k->misses = 0;
+      for (int e = 0; mp && e < 4; ++e) {
         const int64_t r = 256ll * (int64_t)z[e] - pp[s][e];
-        k->pos[e] = yfi_motion_sat(pp[s][e] + yfi_motion_mul(p->alpha, r));
-        k->vel[e] = yfi_motion_sat(yfi_motion_sat(k->vel[e]) + yfi_motion_mul(p->beta, r));
+        mo[s]->pos[e] = yfi_motion_sat(pp[s][e] + yfi_motion_mul(mp->alpha, r));
+        mo[s]->vel[e] = yfi_motion_sat(yfi_motion_sat(mo[s]->vel[e]) + yfi_motion_mul(mp->beta, r));
       }
     } else {
-      k->base.misses = yfi_track_inc(k->base.misses);
-      if (k->base.misses > p->base.max_misses) memset(k, 0, sizeof *k);
-      else
-        for (int e = 0; e < 4; ++e) {
-          k->pos[e] = yfi_motion_sat(pp[s][e]);
-          k->vel[e] = yfi_motion_mul(p->damp, yfi_motion_sat(k->vel[e]));
+      k->misses = yfi_track_inc(k->misses);
+      if (k->misses > p->max_misses) {
+        if (mp) memset(mo[s], 0, sizeof *mo[s]);
+        else memset(k, 0, sizeof *k);
+      } else
+        for (int e = 0; mp && e < 4; ++e) {
+          mo[s]->pos[e] = yfi_motion_sat(pp[s][e]);
+          mo[s]->vel[e] = yfi_motion_mul(mp->damp, yfi_motion_sat(mo[s]->vel[e]));
         }
     }
   }
   int s = 0;
   for (int j = 0; j < m; ++j) {
     if (det_slot[j] >= 0) continue;
-    while (s < YF_TRACK_SLOTS && st->slot[s].base.id != 0) ++s;
+    while (s < YF_TRACK_SLOTS && slot[s]->id != 0) ++s;
     if (s == YF_TRACK_SLOTS) { bits |= YFI_TRACK_ST_DROPPED; break; }
-    yf_track_motion* k = &st->slot[s];
+    yf_track* k = slot[s];
     const int32_t z[4] = {dets[j].x1, dets[j].y1, dets[j].x2, dets[j].y2};
-    st->issued = yfi_track_next_id(st->issued, 0);
-    k->base.id = st->issued; k->base.hits = 1; k->base.misses = 0; k->base.age = 1; k->base.det = dets[j];
-    k->pad = 0;
-    for (int e = 0; e < 4; ++e) { k->pos[e] = 256ll * (int64_t)z[e]; k->vel[e] = 0; }
+    *issued = yfi_track_next_id(*issued, 0);
+    k->id = *issued; k->hits = 1; k->misses = 0; k->age = 1; k->det = dets[j];
+    if (mp) {
+      mo[s]->pad = 0;
+      for (int e = 0; e < 4; ++e) { mo[s]->pos[e] = 256ll * (int64_t)z[e]; mo[s]->vel[e] = 0; }
+    }
   }
   int emitted[YF_TRACK_SLOTS] = {0}, total = 0;
   for (;;) {
     int pick = -1;
     for (int q = 0; q < YF_TRACK_SLOTS; ++q) {
-      const yf_track* k = &st->slot[q].base;
-      if (emitted[q] || k->id == 0 || k->hits < p->base.min_hits) continue;
-      if (pick < 0 || k->id < st->slot[pick].base.id) pick = q;
+      const yf_track* k = slot[q];
+      if (emitted[q] || k->id == 0 || k->hits < p->min_hits) continue;
+      if (pick < 0 || k->id < slot[pick]->id) pick = q;
     }
     if (pick < 0) break;
     emitted[pick] = 1;
     if (total < out_cap) {
-      const yf_track_motion* k = &st->slot[pick];
-      out[total] = k->base.det;
+      const yf_track* k = slot[pick];
+      out[total] = k->det;
       out[total].frame = frame;
-      if (k->base.misses > 0 || p->smooth != 0) {                    /* pos was written in this step or at an earlier one: within the clamp */
-        out[total].x1 = yfi_motion_box(k->pos[0]); out[total].y1 = yfi_motion_box(k->pos[1]);
-        out[total].x2 = yfi_motion_box(k->pos[2]); out[total].y2 = yfi_motion_box(k->pos[3]);
+      if (mp && (k->misses > 0 || mp->smooth != 0)) {                /* pos was written in this step or at an earlier one: within the clamp */
+        const int64_t* pos = mo[pick]->pos;
+        out[total].x1 = yfi_motion_box(pos[0]); out[total].y1 = yfi_motion_box(pos[1]);
+        out[total].x2 = yfi_motion_box(pos[2]); out[total].y2 = yfi_motion_box(pos[3]);
       }
-      info[total].id = k->base.id; info[total].hits = k->base.hits; info[total].misses = k->base.misses; info[total].age = k->base.age;
+      info[total].id = k->id; info[total].hits = k->hits; info[total].misses = k->misses; info[total].age = k->age;
     }
     ++total;
   }
@@ -943,20 +872,51 @@ static void motion_step_host(yf_track_motion_state* st, const yf_det* dets, int3
   if (status) *status = bits;
 }
 
+/* a call behind its check, on host memory: stream by stream, step by step; `params` is the entry's own copy.  Returns n */
+static long track_run_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap, const yf_track_params* p,
+                           const yf_track_motion_params* mp, int assign, void* state, void* out, void* info, void* out_counts, int out_cap,
+                           int32_t* status) {
+  const size_t state_bytes = mp ? sizeof(yf_track_motion_state) : sizeof(yf_track_state);
+  for (long s = 0; s < streams; ++s)
+    for (long t = 0; t < steps; ++t) {
+      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
+      track_step_host((char*)state + (size_t)s * state_bytes, p, mp, assign, (const yf_det*)dets + (size_t)f * (size_t)cap,
+                      ((const int32_t*)counts)[f], cap, (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap,
+                      (yf_track_info*)info + (size_t)f * (size_t)out_cap, (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
+    }
+  return streams * steps;
+}
+
+/* ---- yf_images_track.h ----  yf_images_track_device on host memory (`stream` is not used).  Returns n, or -1 for arguments the device
+ * entry refuses. */
+EXPORT long yf_images_track_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                 const yf_track_params* params, void* state, void* out, void* info, void* out_counts, int out_cap,
+                                 int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status) != NULL) return -1;
+  const yf_track_params p = *params;
+  return track_run_host(dets, counts, streams, steps, layout, cap, &p, NULL, YF_ASSIGN_GREEDY, state, out, info, out_counts, out_cap, status);
+}
+
+/* the argument check alone: the text of the first fault into text (at most text_bytes, 0-terminated), or an empty text; returns 1 for a fault */
+EXPORT int yfi_track_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
+                                const yf_track_params* params, const void* state, const void* out, const void* info, const void* out_counts,
+                                int out_cap, const void* status, char* text, int text_bytes) {
+  const char* t = yfi_track_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+EXPORT size_t yf_images_track_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }
+
+/* ---- yf_images_motion.h ----  yf_images_track_motion_device on host memory: the contract of the entry above */
 EXPORT long yf_images_track_motion_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
                                         const yf_track_motion_params* params, void* state, void* out, void* info, void* out_counts,
                                         int out_cap, int32_t* status, void* stream) {
   (void)stream;
   if (yfi_motion_check(dets, counts, streams, steps, layout, cap, params, state, out, info, out_counts, out_cap, status) != NULL) return -1;
   const yf_track_motion_params p = *params;
-  for (long s = 0; s < streams; ++s)
-    for (long t = 0; t < steps; ++t) {
-      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
-      motion_step_host((yf_track_motion_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
-                       YF_ASSIGN_GREEDY, (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
-                       (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
-    }
-  return streams * steps;
+  return track_run_host(dets, counts, streams, steps, layout, cap, &p.base, &p, YF_ASSIGN_GREEDY, state, out, info, out_counts, out_cap, status);
 }
 
 EXPORT int yfi_motion_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,
@@ -977,14 +937,7 @@ EXPORT long yf_images_track_motion_assign_host(const void* dets, const void* cou
   (void)stream;
   if (yfi_assign_check(dets, counts, streams, steps, layout, cap, params, assign, state, out, info, out_counts, out_cap, status) != NULL) return -1;
   const yf_track_motion_params p = *params;
-  for (long s = 0; s < streams; ++s)
-    for (long t = 0; t < steps; ++t) {
-      const long f = layout == YF_TRACK_TIME_MAJOR ? t * streams + s : s * steps + t;
-      motion_step_host((yf_track_motion_state*)state + s, (const yf_det*)dets + (size_t)f * (size_t)cap, ((const int32_t*)counts)[f], cap, &p,
-                       assign, (int32_t)f, (yf_det*)out + (size_t)f * (size_t)out_cap, (yf_track_info*)info + (size_t)f * (size_t)out_cap,
-                       (int32_t*)out_counts + f, out_cap, status ? status + f : NULL);
-    }
-  return streams * steps;
+  return track_run_host(dets, counts, streams, steps, layout, cap, &p.base, &p, assign, state, out, info, out_counts, out_cap, status);
 }
 
 EXPORT int yfi_assign_check_host(const void* dets, const void* counts, long streams, long steps, int layout, int cap,

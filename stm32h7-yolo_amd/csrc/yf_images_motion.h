@@ -1,6 +1,6 @@
 /* Tracking with a motion model: the tracker of yf_images_track.h with a constant-velocity g-h (alpha-beta) filter on every edge of a
  * track's box, so that a held-over box moves on with its face (yf_images_track_motion_device), shared by the device kernel
- * (yf_images_motion.hip.h), the host entry in yf_images.hip, a host build (yf_images_host.c, which tests/test_track_motion_host.py checks
+ * (yf_images_step.hip.h), the host entry in yf_images.hip, a host build (yf_images_host.c, which tests/test_track_motion_host.py checks
  * against ptq.track_motion_step) and a sanitizer program (tests/csrc/track_motion_sanitize_main.c).  Plain C.
  *
  * The reference has no tracker; the definition is the library's own.  The filter is in integers -- no float takes part in it --, so the

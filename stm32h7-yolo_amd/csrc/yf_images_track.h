@@ -1,5 +1,5 @@
 /* Tracking: the detection records of the frames of a video stream associated with per-stream track state -- identities and a hold-over
- * (yf_images_track_device), shared by the device kernel (yf_images_track.hip.h), the host entry in yf_images.hip and a host build
+ * (yf_images_track_device), shared by the device kernel (yf_images_step.hip.h), the host entry in yf_images.hip and a host build
  * (yf_images_host.c, libyf_images_host.so, which tests/test_track_host.py checks against ptq.track_step).  Plain C.
  *
  * The reference has no tracker: its detect_video (yoloface/tensorflow/yoloface_test.py:318-385) treats every frame alone.  The

@@ -166,6 +166,17 @@ def test_streams_by_steps_in_both_layouts(torch_cuda, images, streams):
     assert (results[ts.TIME].out_counts > 0).any() and results[ts.TIME].state["issued"].all()       # at 7 steps every stream has had tracks
 
 
+def test_a_workgroup_that_takes_a_second_stream(torch_cuda, images):
+    """more streams than the launch has workgroups (the device's CUs times the launcher's own number per CU; the table of weights in LDS
+    is reused for the second stream without a barrier): the device against the host build in every byte, from the empty state and from
+    the state that call left"""
+    grid = torch_cuda.cuda.get_device_properties(0).multi_processor_count * ts.per_cu("Assign")
+    host = lambda d, c, streams, steps, layout, cap, p, state0, out_cap: asg.host_run(d, c, streams, steps, layout, cap, p, asg.OPTIMAL, state0, out_cap)
+    device = lambda d, c, streams, steps, layout, cap, p, state0, out_cap: device_run(torch_cuda, images, d, c, streams, steps, layout, cap, p,
+                                                                                     asg.OPTIMAL, state0, out_cap)
+    ts.beyond_the_grid(device, host, grid, (0.3, 2, 1) + asg.SUGGESTED, ms.empty_state)
+
+
 def test_one_call_of_many_steps_equals_many_calls_of_one(torch_cuda, images):
     params = ms.R_BASE + asg.SUGGESTED
     dets, counts = ts.lay_out(ms.random_frames(), ms.R_CAP, ts.TIME)

@@ -68,6 +68,13 @@ def test_streams_by_steps_in_both_layouts(torch_cuda, images, streams):
     assert (results[ts.TIME].out_counts > 0).any() and results[ts.TIME].state["issued"].all()       # at 7 steps every stream has had tracks
 
 
+def test_a_workgroup_that_takes_a_second_stream(torch_cuda, images):
+    """more streams than the launch has workgroups (the device's CUs times the launcher's own number per CU): the device against the
+    host build in every byte, from the empty state and from the state that call left"""
+    grid = torch_cuda.cuda.get_device_properties(0).multi_processor_count * ts.per_cu("Track")
+    ts.beyond_the_grid(lambda *a: device_run(torch_cuda, images, *a), ts.host_run, grid, (0.3, 2, 1), ts.empty_state)
+
+
 def test_one_call_of_many_steps_equals_many_calls_of_one(torch_cuda, images):
     dets, counts, want = ts.random_call(ts.TIME)
     run = lambda *a: device_run(torch_cuda, images, *a)

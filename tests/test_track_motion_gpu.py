@@ -112,6 +112,13 @@ def test_streams_by_steps_in_both_layouts(torch_cuda, images, streams):
     assert results[ts.TIME].state["slot"]["vel"].any()
 
 
+def test_a_workgroup_that_takes_a_second_stream(torch_cuda, images):
+    """more streams than the launch has workgroups (the device's CUs times the launcher's own number per CU): the device against the
+    host build in every byte, from the empty state and from the state that call left"""
+    grid = torch_cuda.cuda.get_device_properties(0).multi_processor_count * ts.per_cu("Motion")
+    ts.beyond_the_grid(lambda *a: device_run(torch_cuda, images, *a), ms.host_run, grid, (0.3, 2, 1) + ms.SUGGESTED + (1,), ms.empty_state)
+
+
 def full_table():
     """one stream, 64 occupied slots with a velocity each, 64 detections: 40 slots are seen again where they moved to, 24 are not -- 10
     of those at max_misses, which go --, and 24 new boxes find 10 free slots: 14 are dropped"""

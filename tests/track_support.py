@@ -9,10 +9,13 @@ are 0xA5 bytes (and count, if the count says so).  The conf of a record is kept 
 import ctypes
 import functools
 import importlib
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
 
+from conftest import ROOT
 from images_support import host_lib
 
 
@@ -363,6 +366,30 @@ def drift_frames(streams, steps, seed=5900):
             clip.append(([(o[0], o[1], o[0] + o[2] - 1, o[1] + o[3] - 1) for o in objects if rng.random() > 0.25], None))
         frames.append(clip)
     return frames
+
+
+def per_cu(kernel):
+    """the workgroups of the 'Track', 'Motion' or 'Assign' kernel that a CU holds at once, the measure of the launcher's grid: the constant
+    the launcher itself takes, read from csrc/yf_images_step.hip.h"""
+    text = open(os.path.join(ROOT, "stm32h7-yolo_amd", "csrc", "yf_images_step.hip.h")).read()
+    return int(re.search(r"\bkPerCu%s = (\d+)" % kernel, text).group(1))
+
+
+def beyond_the_grid(device, host, workgroups, params, state0):
+    """three streams more than the launch has workgroups, so that some workgroups take a second stream (state reloaded into the registers,
+    the assign kernel's table reused), two steps at cap 4 with 0 to 4 records a frame; then the same again in the other layout on the
+    state the first call left, part occupied and part empty: `device` against `host`, both `host_run`'s signature, in every byte"""
+    streams, steps, cap, out_cap = workgroups + 3, 2, 4, 4
+    frames = [[(boxes[:cap], None) for boxes, _ in clip] for clip in drift_frames(streams, steps)]
+    state = state0(streams)
+    for layout in LAYOUTS:
+        dets, counts = lay_out(frames, cap, layout)
+        want = host(dets, counts, streams, steps, layout, cap, params, state, out_cap)
+        got = device(dets, counts, streams, steps, layout, cap, params, state, out_cap)
+        assert want.rc == streams * steps and same(got, want), layout
+        assert (want.state["issued"] > 0).mean() > 0.9 and (want.out_counts > 0).any()             # tracks nearly everywhere
+        state = got.state
+    return got
 
 
 @functools.lru_cache(maxsize=None)
