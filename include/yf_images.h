@@ -532,7 +532,9 @@ YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, l
  *           P' = pos + vel; matched to a detection z: r = 256 z - P', pos = P' + alpha r / 256, vel += beta r / 256; unmatched: pos = P',
  *           vel = damp vel / 256.  (256, 0) is the tracker above, byte for byte, from the empty state; (256, 256) predicts with the last
  *           frame-to-frame difference.  The library's suggestion is {192, 128, 256, 0}: a choice, not something measured -- there is no
- *           accuracy or identity-switch figure for real video.
+ *           accuracy or identity-switch figure for real video.  What exists since: yf_images_score_tracks_device below scores the
+ *           reported tracks against labelled identities, and profiles/track_score_bench.txt holds its figures for the settings on
+ *           SYNTHETIC clips; a figure on labelled video still does not exist.
  *   output: as above.  A held-over track (misses > 0) is reported with its last record's edges replaced by the filter's position
  *           rounded to pixels; with smooth 1 a matched track too (the filtered box), with smooth 0 it reports its detection verbatim.
  *           A predicted box is not clamped to the picture; the crop, the redaction, the blur and the drawing clip themselves.
@@ -560,11 +562,62 @@ YF_API long   yf_images_track_motion_device(const void* d_dets, const void* d_co
  * The checks (the entry's above in its order, then assign), n = 0, the return value and the error text are the entry's above; one launch,
  * one wave per stream, 16 KB of LDS per wave; asynchronous, no allocation, no host synchronisation, capturable.  A frame with m
  * detections costs at most m (m + 1) / 2 rounds of the search, 2080 at m = 64; a frame without an eligible pair skips it.
- * Still missing: a covariance, appearance features, re-identification, clamping a predicted box. */
+ * Still missing: a covariance, appearance features, re-identification, clamping a predicted box.  Which match keeps identities better is
+ * measured by yf_images_score_tracks_device below -- on synthetic clips so far (profiles/track_score_bench.txt: without the motion model
+ * the optimal assignment exchanges two faces that pass each other where the greedy match does not), not on labelled video. */
 enum { YF_ASSIGN_GREEDY = 0, YF_ASSIGN_OPTIMAL = 1 };
 YF_API long   yf_images_track_motion_assign_device(const void* d_dets, const void* d_counts, long streams, long steps, int layout, int cap,
                                                    const yf_track_motion_params* params, int assign, void* d_state, void* d_out,
                                                    void* d_info, void* d_out_counts, int out_cap, int32_t* d_status, void* stream);
+
+/* ---- scoring tracks against labelled identities: the CLEAR-MOT score (Bernardin and Stiefelhagen, 2008) of what a tracker above
+ * reported against ground-truth tracks -- misses, false positives, IDENTITY SWITCHES, MOTA and MOTP --, per stream over the steps of a
+ * clip, on the device: the records do not leave it.  It is what measures the tracker's settings against each other (greedy or optimal,
+ * with or without the motion model, the gains); the first figures, on synthetic clips and not on video, are in
+ * profiles/track_score_bench.txt.  A new entry beside the tracker's, which do not change.  The reference has no tracker; the definition
+ * is this library's own, stated once in csrc/yf_images_score.h (the rows and columns that count, the continuity rule, the switches, the
+ * counters, what is out of scope), which the kernel, a host build and a sanitizer program share.  Everything after the IoU is integers.
+ *   truth:  d_gt yf_gt_track[n][gt_cap], d_gt_counts int32[n], 1 <= gt_cap <= 64: per frame the labelled objects {id, x1, y1, x2, y2},
+ *           edges inclusive pixels as in a record; valid ids are 1 .. YF_SCORE_MAX_IDS and an id names one object of its stream.  Of a
+ *           frame the first min(max(count, 0), gt_cap, 64) rows count (a larger count: status bit 0); a row of id 0, of an id above 256
+ *           or of an id an earlier row of the frame has is void (status bit 2): it counts for nothing.
+ *   tracks: a tracker's output as it lies: d_out yf_det[n][out_cap], d_info yf_track_info[n][out_cap] (only `id` is read),
+ *           d_out_counts int32[n], out_cap >= 1; the first min(max(count, 0), out_cap, 64) records count (a larger count: status bit 1);
+ *           a record of id 0 is void (status bit 3; the trackers emit none).  n = streams * steps frames in `layout`, as above.
+ *   state:  d_state yf_score_state[streams] (8-byte aligned), yf_images_score_state_bytes(streams) bytes: 3136 per stream -- eight
+ *           uint64 counters, then per ground-truth id the hypothesis id it was last matched to and the frames it was present and
+ *           tracked.  All zero is the empty state; the bytes are untrusted: whatever they hold, a step reads and writes only inside
+ *           them (only a range-checked ground-truth id indexes them).  The counters add modulo 2^64, present and tracked saturate.
+ *   step:   a pair is eligible as in the tracker (the boxes share a pixel, IoU >= score_iou, any value but NaN); an object keeps the
+ *           hypothesis id it was last matched to while that pair stays eligible, the remaining rows and columns are assigned by
+ *           yfi_assign_solve (maximum total IoU at 2^-30 resolution); a new match to another id than the last one is one switch.
+ *   output: the state; d_match int32[n][gt_cap] or NULL: for each of a frame's rows that count the column of its hypothesis, or -1
+ *           (places beyond them are not written); d_status int32[n] or NULL: the bits above.
+ * One launch (one wave per stream, the counters and the per-object tables in registers over the stream's steps, 16 KB of LDS);
+ * asynchronous on `stream`, no allocation, no host synchronisation, capturable.  Every argument is checked before the launch
+ * (yfi_score_check): NULL pointers (d_match and d_status excepted), 4-byte alignment of the arrays and 8-byte alignment of the state,
+ * out_cap, gt_cap, score_iou, layout, streams and steps >= 0 with streams * steps <= 2^31 - 2.  Returns n; n = 0 launches nothing and
+ * returns 0, after the checks; a failure returns -1 with a text in yf_images_last_error_text.
+ * yf_images_score_summary is host only, no GPU call, like yf_images_plan_tiles: host_states are `streams` downloaded states (any
+ * alignment); *out receives the sums of the counters over the streams, objects (entries with present > 0, counted per stream),
+ * mostly_tracked (5 tracked >= 4 present), mostly_lost (5 tracked <= present), and
+ *   mota = gt ? 1.0 - (double)(misses + false_positives + switches) / (double)gt : 0.0,
+ *   motp = matches ? ((double)overlap / (double)matches) / 1073741824.0 : 0.0 -- the mean IoU of the matched pairs at 2^-30 resolution;
+ * each weight carries the + 1 of the assignment's weights, so motp lies 2^-30 above the truncated mean.  Returns 0, or -1 (out NULL,
+ * streams < 0, host_states NULL with streams > 0).
+ * Out of scope: IDF1 and HOTA (one assignment over the whole clip, hypothesis ids without a bound), fragmentations, more than 256
+ * labelled objects per stream or 64 per frame, and any figure for real labelled video. */
+#define YF_SCORE_MAX_IDS 256
+typedef struct yf_gt_track      { uint32_t id; int32_t x1, y1, x2, y2; } yf_gt_track;                          /* 20 bytes */
+typedef struct yf_score_state   { uint64_t frames, gt, hyp, matches, misses, false_positives, switches, overlap;
+                                  uint32_t last[YF_SCORE_MAX_IDS]; int32_t present[YF_SCORE_MAX_IDS], tracked[YF_SCORE_MAX_IDS]; } yf_score_state; /* 3136 bytes per stream */
+typedef struct yf_score_summary { uint64_t frames, gt, hyp, matches, misses, false_positives, switches, overlap;
+                                  int64_t objects, mostly_tracked, mostly_lost; double mota, motp; } yf_score_summary;  /* 104 bytes */
+YF_API size_t yf_images_score_state_bytes(long streams);
+YF_API long   yf_images_score_tracks_device(const void* d_out, const void* d_info, const void* d_out_counts, int out_cap, const void* d_gt,
+                                            const void* d_gt_counts, int gt_cap, long streams, long steps, int layout, double score_iou,
+                                            void* d_state, int32_t* d_match, int32_t* d_status, void* stream);
+YF_API int    yf_images_score_summary(const void* host_states, long streams, yf_score_summary* out);
 
 /* ---- letterboxed frames: the picture resized with its aspect kept, centred in the square frame, the rest padded with one grey, and the
  * boxes mapped back through the same rectangle.  Every entry above stretches the picture onto the frame, as the reference's scripts do

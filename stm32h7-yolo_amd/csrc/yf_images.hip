@@ -21,7 +21,8 @@
 // yf_images_draw.h and yf_images_draw.hip.h; the tracker (each frame's records associated with per-stream track state) in
 // yf_images_track.h, with a motion model (a constant-velocity filter per edge, held-over boxes move on) in yf_images_motion.h, and with
 // the optimal assignment in the place of the greedy match in yf_images_assign.h, the three kernels one step body in
-// yf_images_step.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
+// yf_images_step.hip.h; the CLEAR-MOT score of a tracker's records against labelled identities in yf_images_score.h and
+// yf_images_score.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
 // boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h; the area-averaged frames (every source pixel counted, a job per band
 // of a frame) in yf_images_area.h and yf_images_area.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
@@ -48,6 +49,7 @@
 #include "yf_images_blur.hip.h"
 #include "yf_images_draw.hip.h"
 #include "yf_images_step.hip.h"
+#include "yf_images_score.hip.h"
 #include "yf_images_fit.hip.h"
 #include "yf_images_area.hip.h"
 
@@ -977,6 +979,24 @@ long track_motion_assign(const void* d_dets, const void* d_counts, long streams,
                       streams, steps, layout, cap, params->base, d_state, d_out, d_info, d_out_counts, out_cap, d_status, stream);
 }
 
+// ---- scoring tracks (yf_images_score.h) ----  every argument, then one launch of one-wave workgroups; -1 and the text: 0 is a valid n
+long score_tracks(const void* d_out, const void* d_info, const void* d_out_counts, int out_cap, const void* d_gt, const void* d_gt_counts,
+                  int gt_cap, long streams, long steps, int layout, double score_iou, void* d_state, int32_t* d_match, int32_t* d_status,
+                  void* stream) {
+  const char* err = yfi_score_check(d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps, layout, score_iou, d_state,
+                                    d_match, d_status);
+  if (err) return fail("%s", err) - 1;
+  const long n = streams * steps;
+  if (n == 0) return 0;
+  yfscore::Args a{};
+  a.out = (const yf_det*)d_out; a.info = (const yf_track_info*)d_info; a.out_counts = (const int*)d_out_counts; a.out_cap = out_cap;
+  a.gt = (const yf_gt_track*)d_gt; a.gt_counts = (const int*)d_gt_counts; a.gt_cap = gt_cap;
+  a.streams = streams; a.steps = steps; a.layout = layout; a.score_iou = score_iou;
+  a.state = (yf_score_state*)d_state; a.match = d_match; a.status = d_status;
+  hipLaunchKernelGGL(yfscore::clip_kernel, grid_for(streams, yfscore::kPerCuScore), dim3(64), 0, (hipStream_t)stream, a);
+  return launched("score_tracks kernel launch", n) == n ? n : -1;
+}
+
 // ---- letterboxed frames (yf_images_fit.h) ----  the prepare kernels by format (the four packed formats in the order of their codes,
 // then NV12, NV21), for a frame side and an element type
 using FitKernel = void (*)(yffit::Args);
@@ -1415,6 +1435,20 @@ YF_API long yf_images_track_motion_assign_device(const void* d_dets, const void*
                                                  void* d_out_counts, int out_cap, int32_t* d_status, void* stream) {
   return track_motion_assign(d_dets, d_counts, streams, steps, layout, cap, params, assign, d_state, d_out, d_info, d_out_counts, out_cap, d_status,
                              stream);
+}
+
+YF_API size_t yf_images_score_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_score_state) : 0; }
+
+YF_API long yf_images_score_tracks_device(const void* d_out, const void* d_info, const void* d_out_counts, int out_cap, const void* d_gt,
+                                          const void* d_gt_counts, int gt_cap, long streams, long steps, int layout, double score_iou,
+                                          void* d_state, int32_t* d_match, int32_t* d_status, void* stream) {
+  return score_tracks(d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps, layout, score_iou, d_state, d_match,
+                      d_status, stream);
+}
+
+YF_API int yf_images_score_summary(const void* host_states, long streams, yf_score_summary* out) {
+  if (yfi_score_summary(host_states, streams, out) != 0) { fail("out is NULL, streams < 0, or host_states is NULL with streams > 0"); return -1; }
+  return 0;
 }
 
 YF_API size_t yf_images_track_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }

@@ -53,7 +53,11 @@
  * is added.  Where every detection and every slot has at most one eligible partner the two matches are the same pairs.
  *
  * STILL OUT OF SCOPE.  No covariance.  No appearance features.  No re-identification after a track is removed.  A predicted box is not
- * clamped to the picture.  No identity-switch figure on labelled video stands behind either match. */
+ * clamped to the picture.  No identity-switch figure on labelled video stands behind either match.  What exists since: a score of tracks against labelled identities (yf_images_score.h,
+ * yf_images_score_tracks_device: misses, false positives, identity switches, MOTA) and its figures on SYNTHETIC clips
+ * (profiles/track_score_bench.txt); what still does not: any figure on labelled video.
+ * On those clips the optimal assignment WITHOUT the motion model exchanges two faces that pass each other where the greedy match does
+ * not; with the motion model neither does. */
 #ifndef YF_IMAGES_ASSIGN_H
 #define YF_IMAGES_ASSIGN_H
 #include "yf_images_motion.h"

@@ -1,6 +1,6 @@
 /* Host build of the resize arithmetic in yf_images_taps.h, the NV12 / NV21 conversion and addressing in yf_images_yuv.h, the suppression arithmetic in yf_images_nms.h, the 20x20 decode arithmetic in
  * yf_images_decode160.h, the fp16 frames and float32 decode of yf_images_float.h and the scoring arithmetic of yf_images_eval.h (the
- * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h, the tracker with a motion model of yf_images_motion.h and its optimal assignment of yf_images_assign.h, the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
+ * functions the device kernels call), the tile grid, planner and merge of yf_images_tiles.h the face chips of yf_images_crop.h, the redaction of yf_images_redact.h, the blur of yf_images_blur.h, the drawing of yf_images_draw.h, the tracker of yf_images_track.h, the tracker with a motion model of yf_images_motion.h and its optimal assignment of yf_images_assign.h, the score of tracks against labelled identities of yf_images_score.h, the letterboxed frames and decodes of yf_images_fit.h and the area-averaged frames of yf_images_area.h, for the CPU tests only:
  * libyf_images_host.so, no HIP. */
 #include <stddef.h>
 #include <stdint.h>
@@ -21,6 +21,7 @@
 #include "yf_images_track.h"
 #include "yf_images_motion.h"
 #include "yf_images_assign.h"
+#include "yf_images_score.h"
 #include "yf_images_fit.h"
 #include "yf_images_area.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -959,6 +960,29 @@ EXPORT int64_t yfi_assign_match_host(const int32_t* boxes, const int* occupied, 
 
 /* the procedure alone on a table of weights int32[m][64] */
 EXPORT int64_t yfi_assign_solve_host(const int32_t* weights, int m, int* slot_det, int* det_slot) { return yfi_assign_solve(weights, m, slot_det, det_slot); }
+
+/* ---- yf_images_score.h ----  yf_images_score_tracks_device as the header states it, on host memory (`stream` is not used): the
+ * header's sequential step, stream by stream.  Returns n, or -1 for arguments the device entry refuses. */
+EXPORT long yf_images_score_tracks_host(const void* out, const void* info, const void* out_counts, int out_cap, const void* gt,
+                                        const void* gt_counts, int gt_cap, long streams, long steps, int layout, double score_iou, void* state,
+                                        int32_t* match, int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_score_check(out, info, out_counts, out_cap, gt, gt_counts, gt_cap, streams, steps, layout, score_iou, state, match, status) != NULL) return -1;
+  return yfi_score_run(out, info, out_counts, out_cap, gt, gt_counts, gt_cap, streams, steps, layout, score_iou, state, match, status);
+}
+
+EXPORT int yfi_score_check_host(const void* out, const void* info, const void* out_counts, int out_cap, const void* gt, const void* gt_counts,
+                                int gt_cap, long streams, long steps, int layout, double score_iou, const void* state, const void* match,
+                                const void* status, char* text, int text_bytes) {
+  const char* t = yfi_score_check(out, info, out_counts, out_cap, gt, gt_counts, gt_cap, streams, steps, layout, score_iou, state, match, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+EXPORT size_t yf_images_score_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_score_state) : 0; }
+
+/* yf_images_score_summary as libyf_images.so exports it (the error text is dropped): the header's body */
+EXPORT int yf_images_score_summary_host(const void* host_states, long streams, yf_score_summary* out) { return yfi_score_summary(host_states, streams, out); }
 
 /* the filter's helpers as they are (no range check: the tests ask for what the definition gives) */
 EXPORT int64_t yfi_motion_mul_host(int32_t g, int64_t v) { return yfi_motion_mul(g, v); }

@@ -39,7 +39,9 @@
  * every output byte equals yf_images_track_device's for any damp and either smooth (and every slot's `base` equals the base tracker's
  * slot).  (256, 256) predicts with the last frame-to-frame difference: pos = 256 z, vel = 256 * (z - the previous z) while matched.
  * The library's suggestion is YFI_MOTION_ALPHA, YFI_MOTION_BETA, YFI_MOTION_DAMP, smooth 0 = (192, 128, 256, 0): a choice, not a
- * measurement -- no accuracy or identity-switch figure on real video stands behind it.
+ * measurement -- no accuracy or identity-switch figure on real video stands behind it.  What exists since: a score of tracks against labelled identities (yf_images_score.h,
+ * yf_images_score_tracks_device: misses, false positives, identity switches, MOTA) and its figures on SYNTHETIC clips
+ * (profiles/track_score_bench.txt); what still does not: any figure on labelled video.
  *
  * STILL OUT OF SCOPE.  No covariance (this is not a Kalman filter: the gains are fixed).  No appearance features.  No re-identification
  * after a track is removed.  No optimal assignment HERE: the match is the greedy one; the entry beside this one, yf_images_assign.h

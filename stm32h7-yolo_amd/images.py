@@ -49,13 +49,22 @@ box -- a moving face stays hidden on the frames the detector misses it, and keep
 `track_motion_state_bytes`, `YfTrackMotionParams`; a second entry with a larger state (7176 bytes per stream against 2824) beside the
 first, which does not change; the definition is the library's own (csrc/yf_images_motion.h, `ptq.track_motion_step`).  The gains
 (alpha, beta, damp) are in 1/256; `MOTION_GAINS` = (192, 128, 256) is the library's suggestion, a choice and not a measurement: there is
-no accuracy or identity-switch figure for real video.  (256, 0, any) is the tracker without the model, byte for byte.  Still out of scope:
+no accuracy or identity-switch figure for real video -- what exists since is `evaluate_tracking` / `TrackScore` (below) and their figures
+on synthetic clips, profiles/track_score_bench.txt.  (256, 0, any) is the tracker without the model, byte for byte.  Still out of scope:
 a covariance (a Kalman filter), appearance features, re-identification, clamping a predicted box to the picture (the crop, the
 redaction, the blur and the drawing clip themselves).  `Tracker(..., assign="optimal")` replaces the greedy match -- repeatedly the pair
 of the largest IoU, which strands a detection where two faces pass each other -- by the maximum-weight assignment over the eligible
 pairs, `track_motion_assign_device` (csrc/yf_images_assign.h, `ptq.track_assign_match`); it runs on the 7176-byte state with or
 without `motion`.  `detect_tracked`, `detect_drawn`, `detect_redacted` and `detect_blurred`
 take such a tracker as they take the plain one; with a tracker the last two hide the REPORTED TRACKS, held-over ones included.
+
+`evaluate_tracking(network, images, ground_truths, tracker, steps)` scores what a tracker reports against labelled identities -- the
+CLEAR-MOT score (Bernardin and Stiefelhagen, 2008): misses, false positives, identity switches, MOTA, MOTP -- on the device, per stream
+over the steps of a clip, without the records leaving it: `TrackScore`, `score_tracks_device`, `score_state_bytes`, `score_summary`,
+`pack_track_truth`; the definition is the library's own (csrc/yf_images_score.h, `ptq.track_score_step`, `ptq.track_score_summary`).  It
+is what measures the tracker's settings against each other; the figures that exist are those of synthetic clips
+(profiles/track_score_bench.txt), none of labelled video.  Out of scope: IDF1, HOTA, fragmentations, more than 256 labelled objects per
+stream or 64 per frame.
 
 `fit="letterbox"` on `detect`, every `detect_*` call and `evaluate` replaces the stretch onto the square frame by what every mainstream
 YOLO trainer does: the picture resized with its aspect kept into a centred rectangle of the frame (`fit_of`), the rest padded with the
@@ -162,6 +171,17 @@ YF_ASSIGN_GREEDY, YF_ASSIGN_OPTIMAL = 0, 1
 ASSIGNS = {"greedy": YF_ASSIGN_GREEDY, "optimal": YF_ASSIGN_OPTIMAL}
 ASSIGN_NAMES = {code: name for name, code in ASSIGNS.items()}
 ASSIGN_WHAT = "assign {!r}: 'greedy' (repeatedly the pair of the largest IoU) or 'optimal' (the maximum total IoU)"
+# the score of tracks against labelled identities (yf_gt_track, yf_score_state, yf_score_summary): at most 64 labelled objects of a frame
+# count, their ids 1 .. 256
+SCORE_MAX_IDS, SCORE_MAX_GT, SCORE_STATE_BYTES = 256, 64, 3136
+SCORE_COUNTERS = ("frames", "gt", "hyp", "matches", "misses", "false_positives", "switches", "overlap")
+GT_TRACK_DTYPE = np.dtype([("id", "<u4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
+SCORE_STATE_DTYPE = np.dtype([(name, "<u8") for name in SCORE_COUNTERS]
+                             + [("last", "<u4", (SCORE_MAX_IDS,)), ("present", "<i4", (SCORE_MAX_IDS,)), ("tracked", "<i4", (SCORE_MAX_IDS,))])
+SCORE_SUMMARY_DTYPE = np.dtype([(name, "<u8") for name in SCORE_COUNTERS]
+                               + [("objects", "<i8"), ("mostly_tracked", "<i8"), ("mostly_lost", "<i8"), ("mota", "<f8"), ("motp", "<f8")])
+assert GT_TRACK_DTYPE.itemsize == 20 and SCORE_STATE_DTYPE.itemsize == SCORE_STATE_BYTES and SCORE_SUMMARY_DTYPE.itemsize == 104
+YF_SCORE_GT_CLIPPED, YF_SCORE_HYP_CLIPPED, YF_SCORE_GT_VOID, YF_SCORE_HYP_VOID = 1, 2, 4, 8      # the bits of a frame's status
 
 
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
@@ -254,6 +274,8 @@ def _entries():
         "track_motion_device": [vp, vp, cl, cl, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp],
         # ... with assign after params
         "track_motion_assign_device": [vp, vp, cl, cl, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp],
+        # d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps, layout, score_iou, d_state, d_match, d_status, stream
+        "score_tracks_device": [vp, vp, vp, ci, vp, vp, ci, cl, cl, ci, cd, vp, vp, vp, vp],
         # letterboxed frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] pad, d_frames, d_status, stream
         "prepare_fit_ragged_device": ragged + [ci, ci, vp, vp, vp],
         "prepare_fit_yuv_ragged_device": ragged + [ci, ci, vp, vp, vp],
@@ -302,6 +324,10 @@ def load():
     lib.yf_images_track_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_track_motion_state_bytes.restype = ctypes.c_size_t
     lib.yf_images_track_motion_state_bytes.argtypes = [ctypes.c_long]
+    lib.yf_images_score_state_bytes.restype = ctypes.c_size_t
+    lib.yf_images_score_state_bytes.argtypes = [ctypes.c_long]
+    lib.yf_images_score_summary.restype = ctypes.c_int
+    lib.yf_images_score_summary.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
     lib.yf_images_gather_tiles_workspace.argtypes = [ctypes.c_long]
     lib.yf_images_fit.restype = ctypes.c_int
@@ -1437,6 +1463,139 @@ def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", io
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
     b.stream.synchronize()
     return _track_tuples(d_out, d_info, d_out_counts, n)
+
+
+def score_state_bytes(streams):
+    """The bytes of the score state of `streams` streams (yf_images_score_state_bytes): 3136 each.  All zero is the empty state."""
+    return int(load().yf_images_score_state_bytes(streams))
+
+
+def score_tracks_device(d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps, layout, score_iou, d_state,
+                        d_match=None, d_status=None, stream=None):
+    """The CLEAR-MOT score of a tracker's output against labelled identities (yf_images_score_tracks_device): d_out yf_det[n][out_cap],
+    d_info TRACK_INFO_DTYPE[n][out_cap], d_out_counts int32[n] as `track_device` and its siblings wrote them; d_gt
+    GT_TRACK_DTYPE[n][gt_cap], d_gt_counts int32[n] (`pack_track_truth`); frame t * streams + s (layout "time") or s * steps + t
+    ("stream"); d_state the streams' state (`score_state_bytes`, read and written: the counters and the per-object tables go on from call
+    to call); d_match int32[n][gt_cap] or None: per labelled row the column of its hypothesis or -1; d_status int32[n] or None.  The
+    definition: csrc/yf_images_score.h, ptq.track_score_step.  Returns n."""
+    lib = load()
+    rc = lib.yf_images_score_tracks_device(d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps,
+                                           _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT), float(score_iou), d_state, d_match, d_status, stream)
+    if rc != streams * steps or rc < 0:
+        raise ImagesError(f"yf_images_score_tracks_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
+    return rc
+
+
+def score_summary(states):
+    """yf_images_score_summary of downloaded states (bytes, or an array of SCORE_STATE_BYTES per stream; host memory, no GPU call) -> a
+    dict of yf_score_summary's fields: the eight counters summed over the streams, objects, mostly_tracked, mostly_lost, mota, motp."""
+    lib = load()
+    raw = np.ascontiguousarray(np.frombuffer(states, np.uint8) if isinstance(states, (bytes, bytearray)) else np.asarray(states)).view(np.uint8).reshape(-1)
+    if raw.size % SCORE_STATE_BYTES:
+        raise ValueError(f"{raw.size} bytes of state: {SCORE_STATE_BYTES} per stream")
+    out = np.zeros(1, SCORE_SUMMARY_DTYPE)
+    if lib.yf_images_score_summary(raw.ctypes.data if raw.size else None, raw.size // SCORE_STATE_BYTES, out.ctypes.data) != 0:
+        raise ImagesError(f"yf_images_score_summary: {(lib.yf_images_last_error_text() or b'').decode()}")
+    return {name: (float if name in ("mota", "motp") else int)(out[0][name]) for name in SCORE_SUMMARY_DTYPE.names}
+
+
+def pack_track_truth(ground_truths, gt_cap=None):
+    """per frame a list of (id, x1, y1, x2, y2) -- a labelled object's id (1 .. 256, one object per stream) and its box, edges inclusive
+    pixels -- -> (GT_TRACK_DTYPE [n, gt_cap], int32 [n]); gt_cap None: the largest number of a frame (at least 1)"""
+    rows = [[tuple(int(v) for v in t) for t in g] for g in ground_truths]
+    gt_cap = max([1] + [len(r) for r in rows]) if gt_cap is None else int(gt_cap)
+    if not 1 <= gt_cap <= SCORE_MAX_GT or any(len(r) > gt_cap for r in rows):
+        raise ValueError(f"gt_cap {gt_cap}, {max([0] + [len(r) for r in rows])} labelled objects in one frame: at most {SCORE_MAX_GT}, and gt_cap holds every frame's")
+    packed = np.zeros((len(rows), gt_cap), GT_TRACK_DTYPE)
+    for f, r in enumerate(rows):
+        if any(len(t) != 5 for t in r):
+            raise ValueError(f"frame {f}: every labelled object is (id, x1, y1, x2, y2)")
+        packed[f, :len(r)] = r
+    return packed, np.array([len(r) for r in rows], np.int32)
+
+
+class TrackScore:
+    """The CLEAR-MOT score of `streams` video streams on the device (csrc/yf_images_score.h): misses, false positives, identity switches,
+    MOTA and MOTP of what a `Tracker` reported against labelled identities, at IoU `score_iou`.  `update` scores the next steps, the
+    records staying on the device; `summary` synchronises and downloads the states; `reset` empties every stream."""
+
+    def __init__(self, streams, score_iou=0.5, device=None):
+        import torch
+        if int(streams) < 1:
+            raise ValueError(f"streams {streams!r}: at least 1")
+        if score_iou != score_iou:
+            raise ValueError("score_iou is NaN")
+        self.streams, self.score_iou = int(streams), float(score_iou)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.d_state = torch.zeros((self.streams, SCORE_STATE_BYTES), dtype=torch.uint8, device=self.device)
+
+    def reset(self):
+        """every stream's counters and per-object tables empty again"""
+        self.d_state.zero_()
+
+    def update(self, d_out, d_info, d_out_counts, d_gt, d_gt_counts, steps, layout="time", out_cap=None, gt_cap=None, with_match=False,
+               stream=None):
+        """The next `steps` frames of every stream: d_out, d_info, d_out_counts as `Tracker.update` returned them, d_gt uint8
+        [n, gt_cap, 20] and d_gt_counts int32 [n] the uploaded arrays of `pack_track_truth`, tensors on this device.  -> (d_match int32
+        [n, gt_cap] or None without `with_match`, d_status int32 [n]) on the stream given (default: the device's current one), not
+        synchronised."""
+        import torch
+        n = self.streams * int(steps)
+        out_cap = d_out.shape[1] if out_cap is None else out_cap
+        gt_cap = d_gt.shape[1] if gt_cap is None else gt_cap
+        d_match = torch.full((n, gt_cap), -1, dtype=torch.int32, device=self.device) if with_match else None
+        d_status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        score_tracks_device(d_out.data_ptr(), d_info.data_ptr(), d_out_counts.data_ptr(), out_cap, d_gt.data_ptr(), d_gt_counts.data_ptr(), gt_cap,
+                            self.streams, int(steps), layout, self.score_iou, self.d_state.data_ptr(),
+                            None if d_match is None else d_match.data_ptr(), d_status.data_ptr(), stream)
+        return d_match, d_status
+
+    def states(self):
+        """the states as they are on the device, SCORE_STATE_DTYPE [streams]; synchronises"""
+        return self.d_state.cpu().numpy().view(SCORE_STATE_DTYPE).reshape(self.streams)
+
+    def summary(self):
+        """-> `score_summary` of the states, after a synchronise (the download)"""
+        return score_summary(self.states())
+
+
+def evaluate_tracking(network, images, ground_truths, tracker, steps, layout="time", score_iou=0.5, score=None, fmt="bgr", iou_threshold=0.4,
+                      size=56, dtype="int8", fit="stretch", pad=114, interp="linear"):
+    """`detect_tracked` scored against labelled identities: the next `steps` frames of the `tracker`'s streams are detected, suppressed
+    and associated as there (`images`, `layout`, fmt, iou_threshold, size, dtype, fit, pad, interp: as there), and what the tracker
+    reports is scored on the same stream against `ground_truths` -- per frame, indexed as `images`, a list of (id, x1, y1, x2, y2) in that
+    picture's pixels (`pack_track_truth`) -- without the records leaving the device; one synchronise at the end.  `score`: a `TrackScore`
+    of the tracker's streams and device that carries the score across calls (its score_iou is used); None scores this call alone at
+    `score_iou`.  Returns the summary (`TrackScore.summary`): the counters, objects, mostly_tracked, mostly_lost, mota, motp.  The
+    definition: csrc/yf_images_score.h, restated as `ptq.track_score_step`."""
+    steps = int(steps)
+    if steps < 0 or len(images) != tracker.streams * steps:
+        raise ValueError(f"{len(images)} images: {tracker.streams} streams x {steps} steps")
+    if len(ground_truths) != len(images):
+        raise ValueError(f"{len(images)} images, {len(ground_truths)} lists of labelled objects")
+    if iou_threshold is None:
+        raise ValueError("iou_threshold None: the tracker takes suppressed records")
+    _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+    if score is None:
+        score = TrackScore(tracker.streams, score_iou, tracker.device.index)
+    elif score.streams != tracker.streams or score.device != tracker.device:
+        raise ValueError(f"score: {score.streams} streams on {score.device}, the tracker has {tracker.streams} on {tracker.device}")
+    gt, gt_counts = pack_track_truth(ground_truths)
+    n = len(images)
+    if n == 0:
+        return score.summary()
+    import torch
+    b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype, fit=fit, pad=pad, interp=interp)
+    s = b.stream.cuda_stream
+    with torch.cuda.stream(b.stream):
+        d_gt = torch.from_numpy(gt.view(np.uint8).reshape(n, gt.shape[1], GT_TRACK_DTYPE.itemsize)).to(b.device)
+        d_gt_counts = torch.from_numpy(gt_counts).to(b.device)
+    d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=s)
+    score.update(d_out, d_info, d_out_counts, d_gt, d_gt_counts, steps, layout, stream=s)
+    b.stream.synchronize()
+    return score.summary()
 
 
 # the colours of `detect_drawn`'s tracks, (R, G, B): sixteen that are easy to tell apart; a track has colour id % 16

@@ -984,3 +984,115 @@ def track_motion_step(state, dets, params, count=None, cap=None, frame=0, stats=
                         ("dropped", dropped)):
             stats[name] = stats.get(name, 0) + v
     return {"issued": issued, "reserved": state["reserved"], "slots": slots}, emitted, status
+
+
+# ---- the score of tracks against labelled identities (csrc/yf_images_score.h), in plain Python integers ----
+SCORE_MAX_IDS, SCORE_MAX_ROWS = 256, 64
+SCORE_GT_CLIPPED, SCORE_HYP_CLIPPED, SCORE_GT_VOID, SCORE_HYP_VOID = 1, 2, 4, 8
+SCORE_COUNTERS = ("frames", "gt", "hyp", "matches", "misses", "false_positives", "switches", "overlap")
+_U64 = 2 ** 64 - 1
+
+
+def track_score_empty_state():
+    """The empty state of one stream: what 3136 zero bytes are.  {"counters": the eight of SCORE_COUNTERS, "last": 256 hypothesis ids,
+    "present": 256, "tracked": 256}, the three tables indexed by a ground-truth id - 1."""
+    return {"counters": [0] * 8, "last": [0] * SCORE_MAX_IDS, "present": [0] * SCORE_MAX_IDS, "tracked": [0] * SCORE_MAX_IDS}
+
+
+def track_score_step(state, truths, hyps, score_iou, gt_count=None, gt_cap=None, out_count=None, out_cap=None, stats=None):
+    """One step of the CLEAR-MOT score -- one stream, one frame -- as csrc/yf_images_score.h states it, in Python integers (the IoU stays
+    float64).  `state`: as `track_score_empty_state` gives it (not changed; the new state is returned).  `truths`: the frame's labelled
+    objects (id, x1, y1, x2, y2), valid ids 1 .. 256.  `hyps`: the tracks a tracker reported for the frame, (id, x1, y1, x2, y2) -- of
+    `track_step`'s emitted pairs (record, info): (info[0], *record[6:10]).  `gt_count`, `gt_cap`, `out_count`, `out_cap`: the counts and
+    the capacities of the two rows (default: the lengths); the first min(max(count, 0), cap, 64) of each count.  `stats`: a dict whose
+    counters "kept", "new", "switches", "void_rows", "void_columns" are added to.
+    -> (state, match, status): match[i] for every row that counts, the column of its hypothesis or -1; status bit 0 / 1: a count above
+    min(cap, 64) of the truth / the hypotheses, bit 2: a void row (id 0, above 256, or an earlier row's), bit 3: a record of id 0.
+
+    An object keeps the hypothesis id it was last matched to while that pair stays eligible (inter > 0.0 and iou >= score_iou); the
+    other rows and columns go to `track_assign_solve`; a new match to another id than the last one is one switch."""
+    score_iou = float(score_iou)
+    gt_count = len(truths) if gt_count is None else int(gt_count)
+    gt_cap = len(truths) if gt_cap is None else int(gt_cap)
+    out_count = len(hyps) if out_count is None else int(out_count)
+    out_cap = len(hyps) if out_cap is None else int(out_cap)
+    glim, hlim = min(gt_cap, SCORE_MAX_ROWS), min(out_cap, TRACK_SLOTS)
+    g, h = min(max(gt_count, 0), glim), min(max(out_count, 0), hlim)
+    status = (SCORE_GT_CLIPPED if gt_count > glim else 0) | (SCORE_HYP_CLIPPED if out_count > hlim else 0)
+    truths = [tuple(int(v) for v in t) for t in truths[:g]]
+    hyps = [tuple(int(v) for v in t) for t in hyps[:h]]
+    row_ok = [1 <= t[0] <= SCORE_MAX_IDS and all(e[0] != t[0] for e in truths[:i]) for i, t in enumerate(truths)]
+    col_ok = [t[0] != 0 for t in hyps]
+    if not all(row_ok):
+        status |= SCORE_GT_VOID
+    if not all(col_ok):
+        status |= SCORE_HYP_VOID
+    as_record = lambda t: (0,) * 6 + tuple(t[1:5])
+    w = track_assign_weights({j: as_record(t) for j, t in enumerate(hyps) if col_ok[j]}, [as_record(t) for t in truths], score_iou)
+    for i in range(g):
+        if not row_ok[i]:
+            w[i] = [0] * TRACK_SLOTS
+    last, present, tracked = list(state["last"]), list(state["present"]), list(state["tracked"])
+    # continuity: a valid correspondence is kept
+    row_col, row_w, kept_cols = [-1] * g, [0] * g, set()
+    for i in range(g):
+        if not row_ok[i]:
+            continue
+        k = last[truths[i][0] - 1]
+        if k == 0:
+            continue
+        j = next((j for j, t in enumerate(hyps) if t[0] == k), None)
+        if j is None or j in kept_cols or w[i][j] <= 0:
+            continue
+        kept_cols.add(j)
+        row_col[i], row_w[i] = j, w[i][j]
+    kept = len(kept_cols)
+    # the rest: the kept rows and columns leave the table, the procedure of csrc/yf_images_assign.h takes all g rows
+    for i in range(g):
+        for j in range(TRACK_SLOTS):
+            if row_col[i] >= 0 or j in kept_cols:
+                w[i][j] = 0
+    switches = new = 0
+    det_slot = track_assign_solve(w)[1] if any(v > 0 for row in w for v in row) else {}
+    for i, j in sorted(det_slot.items()):
+        k = last[truths[i][0] - 1]
+        switches += k != 0 and k != hyps[j][0]
+        row_col[i], row_w[i] = j, w[i][j]
+        new += 1
+    rows, cols, matches = sum(row_ok), sum(col_ok), kept + new
+    for i in range(g):
+        if not row_ok[i]:
+            continue
+        o = truths[i][0] - 1
+        present[o] = _track_inc(present[o])
+        if row_col[i] >= 0:
+            tracked[o] = _track_inc(tracked[o])
+            last[o] = hyps[row_col[i]][0]
+    adds = (1, rows, cols, matches, rows - matches, cols - matches, switches, sum(row_w))
+    counters = [(c + a) & _U64 for c, a in zip(state["counters"], adds)]
+    if stats is not None:
+        for name, v in (("kept", kept), ("new", new), ("switches", switches), ("void_rows", g - rows), ("void_columns", h - cols)):
+            stats[name] = stats.get(name, 0) + v
+    return {"counters": counters, "last": last, "present": present, "tracked": tracked}, row_col, status
+
+
+def track_score_summary(states):
+    """yf_images_score_summary over the states of the streams: the sums of the eight counters (modulo 2^64), "objects" (entries with
+    present > 0, counted per stream), "mostly_tracked" (5 tracked >= 4 present), "mostly_lost" (5 tracked <= present), and
+    mota = 1.0 - float(misses + false_positives + switches) / float(gt) (0.0 without ground truth), motp = (float(overlap) /
+    float(matches)) / 2^30 (0.0 without a match), each a chain of single float64 operations: the mean IoU of the matched pairs at 2^-30
+    resolution, every weight with the + 1 of the assignment's weights."""
+    out = {name: 0 for name in SCORE_COUNTERS}
+    out.update(objects=0, mostly_tracked=0, mostly_lost=0)
+    for st in states:
+        for name, c in zip(SCORE_COUNTERS, st["counters"]):
+            out[name] = (out[name] + c) & _U64
+        for p, t in zip(st["present"], st["tracked"]):
+            if p > 0:
+                out["objects"] += 1
+                out["mostly_tracked"] += 5 * t >= 4 * p
+                out["mostly_lost"] += 5 * t <= p
+    errors = (out["misses"] + out["false_positives"] + out["switches"]) & _U64
+    out["mota"] = 1.0 - float(errors) / float(out["gt"]) if out["gt"] else 0.0
+    out["motp"] = (float(out["overlap"]) / float(out["matches"])) / 1073741824.0 if out["matches"] else 0.0
+    return out
