@@ -540,7 +540,8 @@ YF_API long   yf_images_track_device(const void* d_dets, const void* d_counts, l
  *           A predicted box is not clamped to the picture; the crop, the redaction, the blur and the drawing clip themselves.
  * The input, the layouts, the checks (and alpha, beta, damp, smooth), n = 0, the return value and the error text are the entry's above;
  * one launch, one wave per stream, the state in registers over the stream's steps; asynchronous, no allocation, capturable.  Still out
- * of scope: a covariance, appearance features, re-identification, clamping a predicted box; the optimal assignment is the entry below. */
+ * of scope: a covariance, clamping a predicted box; the optimal assignment is the entry below, appearance and re-identification the
+ * stage further below (yf_images_reid_device). */
 typedef struct yf_track_motion        { yf_track base; int32_t pad; int64_t pos[4]; int64_t vel[4]; } yf_track_motion;    /* 112 bytes */
 typedef struct yf_track_motion_state  { uint32_t issued, reserved; yf_track_motion slot[YF_TRACK_SLOTS]; } yf_track_motion_state; /* 7176 bytes per stream */
 typedef struct yf_track_motion_params { yf_track_params base; int32_t alpha, beta, damp, smooth; } yf_track_motion_params;         /* 32 bytes */
@@ -562,7 +563,7 @@ YF_API long   yf_images_track_motion_device(const void* d_dets, const void* d_co
  * The checks (the entry's above in its order, then assign), n = 0, the return value and the error text are the entry's above; one launch,
  * one wave per stream, 16 KB of LDS per wave; asynchronous, no allocation, no host synchronisation, capturable.  A frame with m
  * detections costs at most m (m + 1) / 2 rounds of the search, 2080 at m = 64; a frame without an eligible pair skips it.
- * Still missing: a covariance, appearance features, re-identification, clamping a predicted box.  Which match keeps identities better is
+ * Still missing: a covariance, clamping a predicted box (appearance and re-identification: yf_images_reid_device below).  Which match keeps identities better is
  * measured by yf_images_score_tracks_device below -- on synthetic clips so far (profiles/track_score_bench.txt: without the motion model
  * the optimal assignment exchanges two faces that pass each other where the greedy match does not), not on labelled video. */
 enum { YF_ASSIGN_GREEDY = 0, YF_ASSIGN_OPTIMAL = 1 };
@@ -618,6 +619,90 @@ YF_API long   yf_images_score_tracks_device(const void* d_out, const void* d_inf
                                             const void* d_gt_counts, int gt_cap, long streams, long steps, int layout, double score_iou,
                                             void* d_state, int32_t* d_match, int32_t* d_status, void* stream);
 YF_API int    yf_images_score_summary(const void* host_states, long streams, yf_score_summary* out);
+
+/* ---- appearance: a descriptor per record, and re-identification of lost tracks.  The three trackers above associate by box overlap
+ * alone: a face that is hidden for longer than max_misses steps loses its track and returns under a new id, which the score above counts
+ * as an identity switch.  These two entries are the second look at the picture: a small appearance descriptor per reported record, and
+ * a stage behind a tracker that gives a newly born track the identity of a recently lost one that looks the same.  New entries beside the
+ * existing ones, which do not change.  The reference has neither; the definitions are this library's own, stated once in
+ * csrc/yf_images_describe.h and csrc/yf_images_reid.h, which the kernels, a host build and a sanitizer program share.  Integers
+ * throughout.  The video loop with both: INTEGRATION.md.
+ *
+ * yf_images_describe_records_device, yf_images_describe_records_yuv_device: a yf_face_desc per record.
+ *   input:  d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, margin_permille, flags as the blur above takes them:
+ *           records, counts, regions and the picture checks are exactly its own.  d_pixels is only READ.
+ *   output: d_desc yf_face_desc[n][cap] (4-byte aligned): the record in slot s of frame f goes to d_desc[f][s]; only the slots of the
+ *           first m_f = min(max(count, 0), cap) records of a frame are written, the slots beyond them are not touched.
+ *   valid:  a record's descriptor is INVALID, all 68 bytes zero, when the record has no region, when the region is narrower or lower
+ *           than YF_DESC_GRID = 8 pixels, or when the picture's descriptor is invalid.  Otherwise flags = YF_DESC_VALID (bit 0) and the
+ *           region is cut into 8 x 8 cells with the blur's cell bounds (cell c of a side: [c * side / 8, (c + 1) * side / 8), never
+ *           empty); v[cy * 8 + cx] is the cell's mean luma in exact 64-bit integers -- packed formats: S the sum over the cell's pixels
+ *           of 77 R + 150 G + 29 B, v = (S + 128 cnt) / (256 cnt), alpha never read; NV12 / NV21: v = (sum of Y + cnt / 2) / cnt, only
+ *           the Y plane is read.
+ *   d_first int32[n + 1] and d_status int32[n] are written as the redaction writes them; status 1: the picture's descriptor is invalid.
+ * The descriptor is a tiny template, NOT a learned embedding.  The re-identification below takes any 64 bytes: a caller with a
+ * recogniser behind the chips can hand over its own embedding quantised to uint8 in the place of this one.
+ * Two launches on one stream (the crop's scan; one workgroup per record that exists, rows summed across the lanes, 64-bit accumulation
+ * only per cell).  Asynchronous on `stream`, no allocation, no host synchronisation, capturable; every argument is checked before the
+ * first launch (yfi_describe_check: n, cap, n * cap, margin_permille, flags, NULL pointers, 4-byte alignment of d_dets, d_counts, d_desc,
+ * d_first, d_status, 8-byte alignment of d_images), and each entry refuses the other family's formats with a text.  Counts, records and
+ * d_first (read back) are untrusted device memory, range-checked before use; no load leaves a picture's or plane's extent.  Returns n;
+ * n = 0 launches nothing and returns 0, after the checks.
+ *
+ * yf_images_reid_device: the ids of a tracker's output rewritten.  It sits behind any of the three tracker entries and reads their output
+ * as it lies -- d_info yf_track_info[n][out_cap], d_out_counts int32[n] -- with d_desc yf_face_desc[n][out_cap], the descriptors of
+ * d_out (the entry above with cap = out_cap).  It writes d_info_out yf_track_info[n][out_cap]: the id replaced, hits, misses and age
+ * copied; d_info_out may be d_info itself.  Draw keys, chips, redaction and yf_images_score_tracks_device take the result unchanged.  THE
+ * RECORDS KEEP THE TRACKER'S ORDER: the ids of a frame are then no longer ascending.
+ *   state:  d_state yf_reid_state[streams] (8-byte aligned), yf_images_reid_state_bytes(streams) bytes: 5128 per stream -- a clock and
+ *           64 entries {id, the identity reported; alias, the tracker id currently mapped to it; seen, the clock when it was last bound;
+ *           flags, bit 0 "has a descriptor"; v[64]}.  All zero is the empty state; the bytes are untrusted: whatever they hold, a step
+ *           reads and writes only inside them.
+ *   params: yf_reid_params {max_distance >= 0, max_age >= 0, blend in [0, 256]}, a host pointer that is copied.
+ *   distance of two descriptors a, b with byte sums A, B: d = sum_i |(64 a_i - A) - (64 b_i - B)|, the mean-removed sum of absolute
+ *           differences: exact in int32, at most 64 * 64 * 255, unchanged by a common brightness offset up to rounding.
+ *   step:   of a frame the first m = min(max(count, 0), out_cap, 64) records count (a larger count: status bit 0); a record of tracker id
+ *           0 is void, its id stays 0 (status bit 1).  The clock advances (modulo 2^32).  (bind) A record whose tracker id is the alias of
+ *           an entry -- the lowest such entry -- reports that entry's id, and if it was detected in this frame (misses == 0) and its
+ *           descriptor is valid the entry's descriptor moves towards it, per byte (old * (256 - blend) + new * blend + 128) >> 8.
+ *           (expire) An entry that no record bound and whose age now - seen exceeds max_age is freed.  (re-identify) Among the unbound
+ *           records that were detected with a valid descriptor and the unbound entries with a descriptor, the pair of the smallest
+ *           distance <= max_distance is taken -- ties: the lowest record, then the lowest entry --, the entry's alias becomes the record's
+ *           tracker id and the record reports the entry's id, again and again until no pair is left.  (births) Every record still
+ *           unbound takes the lowest free entry, or evicts the unbound entry of the largest age (ties: the lowest), with id = alias =
+ *           its tracker id.
+ *   output: d_info_out; d_what int32[n][out_cap] or NULL: 0 void, 1 known, 2 re-identified, 3 born; d_status int32[n] or NULL.  The
+ *           places at and beyond min(count, out_cap) are not written; records at and beyond 64 are copied as they are (what 0).
+ * n = streams * steps frames in the tracker's layouts; the steps of stream s are taken in order on d_state[s].  One launch (one wave
+ * per stream, a lane per entry, the entry's 20 words in registers over the stream's steps, the 64 x 64 distances in 16 KB of LDS; a frame
+ * without an unbound record computes no distance); asynchronous on `stream`, no allocation, no host synchronisation, capturable.  Every
+ * argument is checked before the launch (yfi_reid_check): NULL pointers (d_what and d_status excepted), 4-byte alignment of the arrays
+ * and 8-byte alignment of the state, out_cap >= 1, the parameters, layout, streams and steps >= 0 with streams * steps <= 2^31 - 2.
+ * Returns n; n = 0 launches nothing and returns 0, after the checks; a failure returns -1 with a text in yf_images_last_error_text.
+ * Out of scope: an id the tracker itself exchanged between two faces cannot be corrected; an entry whose track the tracker still holds
+ * over cannot be claimed by another track; colour descriptors and learned embeddings are not included.  The suggested max_distance is
+ * a choice made on synthetic textures (profiles/reid_bench.txt); nothing is measured on labelled video. */
+#define YF_DESC_GRID 8
+#define YF_DESC_BYTES 64
+#define YF_DESC_VALID 1u
+#define YF_REID_ENTRIES 64
+#define YF_REID_KNOWN 1
+#define YF_REID_REIDENTIFIED 2
+#define YF_REID_BORN 3
+typedef struct yf_face_desc   { uint32_t flags; uint8_t v[YF_DESC_BYTES]; } yf_face_desc;                             /* 68 bytes */
+typedef struct yf_reid_entry  { uint32_t id, alias, seen, flags; uint8_t v[YF_DESC_BYTES]; } yf_reid_entry;           /* 80 bytes */
+typedef struct yf_reid_state  { uint32_t clock, reserved; yf_reid_entry entry[YF_REID_ENTRIES]; } yf_reid_state;     /* 5128 bytes per stream */
+typedef struct yf_reid_params { int32_t max_distance, max_age, blend; } yf_reid_params;
+YF_API long   yf_images_describe_records_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images,
+                                                const void* d_dets, const void* d_counts, long n, int cap, int margin_permille, int flags,
+                                                void* d_desc, int32_t* d_first, int32_t* d_status, void* stream);
+YF_API long   yf_images_describe_records_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                    const void* d_dets, const void* d_counts, long n, int cap, int margin_permille,
+                                                    int flags, void* d_desc, int32_t* d_first, int32_t* d_status, void* stream);
+YF_API size_t yf_images_reid_state_bytes(long streams);
+YF_API long   yf_images_reid_device(const void* d_info, const void* d_out_counts, const void* d_desc, int out_cap, long streams, long steps,
+                                    int layout, const yf_reid_params* params, void* d_state, void* d_info_out, int32_t* d_what,
+                                    int32_t* d_status, void* stream);
 
 /* ---- letterboxed frames: the picture resized with its aspect kept, centred in the square frame, the rest padded with one grey, and the
  * boxes mapped back through the same rectangle.  Every entry above stretches the picture onto the frame, as the reference's scripts do

@@ -22,7 +22,8 @@
 // yf_images_track.h, with a motion model (a constant-velocity filter per edge, held-over boxes move on) in yf_images_motion.h, and with
 // the optimal assignment in the place of the greedy match in yf_images_assign.h, the three kernels one step body in
 // yf_images_step.hip.h; the CLEAR-MOT score of a tracker's records against labelled identities in yf_images_score.h and
-// yf_images_score.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
+// yf_images_score.hip.h; the appearance descriptors of the records and the re-identification of lost tracks behind a tracker in
+// yf_images_describe.h, yf_images_describe.hip.h, yf_images_reid.h and yf_images_reid.hip.h; the letterboxed frames and their decodes (the picture's aspect kept, the rest padded, the
 // boxes mapped back) in yf_images_fit.h and yf_images_fit.hip.h; the area-averaged frames (every source pixel counted, a job per band
 // of a frame) in yf_images_area.h and yf_images_area.hip.h.
 // After the kernels, the host layer: the error text, the argument checks (each stated once, whichever entry points share it), the
@@ -50,6 +51,8 @@
 #include "yf_images_draw.hip.h"
 #include "yf_images_step.hip.h"
 #include "yf_images_score.hip.h"
+#include "yf_images_describe.hip.h"
+#include "yf_images_reid.hip.h"
 #include "yf_images_fit.hip.h"
 #include "yf_images_area.hip.h"
 
@@ -997,6 +1000,46 @@ long score_tracks(const void* d_out, const void* d_info, const void* d_out_count
   return launched("score_tracks kernel launch", n) == n ? n : -1;
 }
 
+// ---- appearance descriptors (yf_images_describe.h) ----  the kernels by format (the four packed formats in the order of their codes,
+// then NV12, NV21, which differ in the chroma plane only: one kernel)
+using DescribeKernel = void (*)(yfdescribe::Args);
+constexpr DescribeKernel kDescribe[6] = {yfdescribe::records_kernel<3, true>, yfdescribe::records_kernel<3, false>,
+                                         yfdescribe::records_kernel<4, true>, yfdescribe::records_kernel<4, false>,
+                                         yfdescribe::records_kernel<0, false>, yfdescribe::records_kernel<0, false>};
+
+// both entries behind their format check: every other argument, then the crop's scan and the records
+long describe_records(const void* d_pixels, size_t pixels_bytes, int format, const void* d_images, const void* d_dets, const void* d_counts,
+                      long n, int cap, int margin_permille, int flags, void* d_desc, int32_t* d_first, int32_t* d_status, void* stream) {
+  const char* err = yfi_describe_check(d_pixels, d_images, d_dets, d_counts, n, cap, margin_permille, flags, d_desc, d_first, d_status);
+  if (err) return fail("%s", err);
+  if (n == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(yfcrop::first_kernel, dim3(1), dim3(yfcrop::kThreads), 0, s, (const int*)d_counts, n, cap, d_first);
+  yfdescribe::Args a{};
+  a.c.bytes = (uint64_t)pixels_bytes; a.c.imgs = d_images; a.c.dets = (const yf_det*)d_dets; a.c.counts = (const int*)d_counts;
+  a.c.n = n; a.c.cap = cap; a.c.margin = margin_permille; a.c.flags = flags; a.c.first = d_first;
+  a.px = (const uint8_t*)d_pixels; a.desc = (uint32_t*)d_desc; a.status = d_status;
+  // no more workgroups than records can exist, and one at least, for d_status; 0.6 KB of LDS per workgroup, eight waves per SIMD
+  hipLaunchKernelGGL(kDescribe[format], grid_for(n * (long)cap, 8), dim3(yfdescribe::kThreads), 0, s, a);
+  return launched("describe_records kernel launches", n);
+}
+
+// ---- re-identification (yf_images_reid.h) ----  every argument, then one launch of one-wave workgroups; -1 and the text: 0 is a valid n
+long reid(const void* d_info, const void* d_out_counts, const void* d_desc, int out_cap, long streams, long steps, int layout,
+          const yf_reid_params* params, void* d_state, void* d_info_out, int32_t* d_what, int32_t* d_status, void* stream) {
+  const char* err = yfi_reid_check(d_info, d_out_counts, d_desc, out_cap, streams, steps, layout, params, d_state, d_info_out, d_what, d_status);
+  if (err) return fail("%s", err) - 1;
+  const long n = streams * steps;
+  if (n == 0) return 0;
+  yfreid::Args a{};
+  a.info = (const yf_track_info*)d_info; a.out_counts = (const int*)d_out_counts; a.desc = (const yf_face_desc*)d_desc; a.out_cap = out_cap;
+  a.streams = streams; a.steps = steps; a.layout = layout;
+  a.max_distance = params->max_distance; a.max_age = params->max_age; a.blend = params->blend;
+  a.state = (yf_reid_state*)d_state; a.info_out = (yf_track_info*)d_info_out; a.what = d_what; a.status = d_status;
+  hipLaunchKernelGGL(yfreid::stream_kernel, grid_for(streams, yfreid::kPerCuReid), dim3(64), 0, (hipStream_t)stream, a);
+  return launched("reid kernel launch", n) == n ? n : -1;
+}
+
 // ---- letterboxed frames (yf_images_fit.h) ----  the prepare kernels by format (the four packed formats in the order of their codes,
 // then NV12, NV21), for a frame side and an element type
 using FitKernel = void (*)(yffit::Args);
@@ -1449,6 +1492,33 @@ YF_API long yf_images_score_tracks_device(const void* d_out, const void* d_info,
 YF_API int yf_images_score_summary(const void* host_states, long streams, yf_score_summary* out) {
   if (yfi_score_summary(host_states, streams, out) != 0) { fail("out is NULL, streams < 0, or host_states is NULL with streams > 0"); return -1; }
   return 0;
+}
+
+YF_API long yf_images_describe_records_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image* d_images,
+                                              const void* d_dets, const void* d_counts, long n, int cap, int margin_permille, int flags,
+                                              void* d_desc, int32_t* d_first, int32_t* d_status, void* stream) {
+  if (format == YF_PIX_NV12 || format == YF_PIX_NV21)
+    return fail("format YF_PIX_NV12 / YF_PIX_NV21: such surfaces go through yf_images_describe_records_yuv_device");
+  if (!channels_of(format)) return fail("format must be YF_PIX_BGR8, YF_PIX_RGB8, YF_PIX_BGRA8 or YF_PIX_RGBA8");
+  return describe_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, margin_permille, flags, d_desc, d_first, d_status,
+                          stream);
+}
+
+YF_API long yf_images_describe_records_yuv_device(const void* d_pixels, size_t pixels_bytes, int format, const yf_image_yuv* d_images,
+                                                  const void* d_dets, const void* d_counts, long n, int cap, int margin_permille, int flags,
+                                                  void* d_desc, int32_t* d_first, int32_t* d_status, void* stream) {
+  if (channels_of(format)) return fail("format YF_PIX_BGR8 / RGB8 / BGRA8 / RGBA8: packed pixels go through yf_images_describe_records_device");
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return fail("format must be YF_PIX_NV12 or YF_PIX_NV21");
+  return describe_records(d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, margin_permille, flags, d_desc, d_first, d_status,
+                          stream);
+}
+
+YF_API size_t yf_images_reid_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_reid_state) : 0; }
+
+YF_API long yf_images_reid_device(const void* d_info, const void* d_out_counts, const void* d_desc, int out_cap, long streams, long steps,
+                                  int layout, const yf_reid_params* params, void* d_state, void* d_info_out, int32_t* d_what,
+                                  int32_t* d_status, void* stream) {
+  return reid(d_info, d_out_counts, d_desc, out_cap, streams, steps, layout, params, d_state, d_info_out, d_what, d_status, stream);
 }
 
 YF_API size_t yf_images_track_state_bytes(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_track_state) : 0; }

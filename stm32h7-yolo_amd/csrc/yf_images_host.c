@@ -22,6 +22,8 @@
 #include "yf_images_motion.h"
 #include "yf_images_assign.h"
 #include "yf_images_score.h"
+#include "yf_images_describe.h"
+#include "yf_images_reid.h"
 #include "yf_images_fit.h"
 #include "yf_images_area.h"
 #include "gen/yf_decode_tables_gen.h"
@@ -983,6 +985,54 @@ EXPORT size_t yf_images_score_state_bytes_host(long streams) { return streams > 
 
 /* yf_images_score_summary as libyf_images.so exports it (the error text is dropped): the header's body */
 EXPORT int yf_images_score_summary_host(const void* host_states, long streams, yf_score_summary* out) { return yfi_score_summary(host_states, streams, out); }
+
+/* ---- yf_images_describe.h ----  yf_images_describe_records_device / _yuv_device as the header states them, on host memory: the
+ * header's check and the header's run.  Returns n, or -1 for arguments the device entries refuse. */
+EXPORT long yfi_describe_records_host(const uint8_t* base, uint64_t bytes, int format, const yf_image* images, const yf_det* dets,
+                                      const int32_t* counts, long n, int cap, int margin_permille, int flags, yf_face_desc* desc, int32_t* first,
+                                      int32_t* status) {
+  if (!yfi_tiles_channels(format)) return -1;
+  if (yfi_describe_check(base, images, dets, counts, n, cap, margin_permille, flags, desc, first, status) != NULL) return -1;
+  return yfi_describe_run(base, bytes, format, images, dets, counts, n, cap, margin_permille, flags, desc, first, status);
+}
+
+EXPORT long yfi_describe_records_yuv_host(const uint8_t* base, uint64_t bytes, int format, const yf_image_yuv* images, const yf_det* dets,
+                                          const int32_t* counts, long n, int cap, int margin_permille, int flags, yf_face_desc* desc,
+                                          int32_t* first, int32_t* status) {
+  if (format != YF_PIX_NV12 && format != YF_PIX_NV21) return -1;
+  if (yfi_describe_check(base, images, dets, counts, n, cap, margin_permille, flags, desc, first, status) != NULL) return -1;
+  return yfi_describe_run(base, bytes, format, images, dets, counts, n, cap, margin_permille, flags, desc, first, status);
+}
+
+/* the argument check alone, as yfi_redact_check_host */
+EXPORT int yfi_describe_check_host(const void* pixels, const void* images, const void* dets, const void* counts, long n, int cap,
+                                   int margin_permille, int flags, const void* desc, const void* first, const void* status, char* out,
+                                   int out_bytes) {
+  const char* t = yfi_describe_check(pixels, images, dets, counts, n, cap, margin_permille, flags, desc, first, status);
+  if (out && out_bytes > 0) snprintf(out, (size_t)out_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+/* ---- yf_images_reid.h ----  yf_images_reid_device as the header states it, on host memory (`stream` is not used): the header's check
+ * and the header's step, stream by stream.  Returns n, or -1 for arguments the device entry refuses. */
+EXPORT long yf_images_reid_host(const void* info, const void* out_counts, const void* desc, int out_cap, long streams, long steps, int layout,
+                                const yf_reid_params* params, void* state, void* info_out, int32_t* what, int32_t* status, void* stream) {
+  (void)stream;
+  if (yfi_reid_check(info, out_counts, desc, out_cap, streams, steps, layout, params, state, info_out, what, status) != NULL) return -1;
+  return yfi_reid_run(info, out_counts, desc, out_cap, streams, steps, layout, params, state, info_out, what, status);
+}
+
+EXPORT int yfi_reid_check_host(const void* info, const void* out_counts, const void* desc, int out_cap, long streams, long steps, int layout,
+                               const yf_reid_params* params, const void* state, const void* info_out, const void* what, const void* status,
+                               char* text, int text_bytes) {
+  const char* t = yfi_reid_check(info, out_counts, desc, out_cap, streams, steps, layout, params, state, info_out, what, status);
+  if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t ? t : "");
+  return t != NULL;
+}
+
+EXPORT size_t yf_images_reid_state_bytes_host(long streams) { return streams > 0 ? (size_t)streams * sizeof(yf_reid_state) : 0; }
+
+EXPORT int32_t yfi_reid_distance_host(const uint8_t* a, const uint8_t* b) { return yfi_reid_distance(a, b); }
 
 /* the filter's helpers as they are (no range check: the tests ask for what the definition gives) */
 EXPORT int64_t yfi_motion_mul_host(int32_t g, int64_t v) { return yfi_motion_mul(g, v); }

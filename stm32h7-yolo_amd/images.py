@@ -51,8 +51,8 @@ first, which does not change; the definition is the library's own (csrc/yf_image
 (alpha, beta, damp) are in 1/256; `MOTION_GAINS` = (192, 128, 256) is the library's suggestion, a choice and not a measurement: there is
 no accuracy or identity-switch figure for real video -- what exists since is `evaluate_tracking` / `TrackScore` (below) and their figures
 on synthetic clips, profiles/track_score_bench.txt.  (256, 0, any) is the tracker without the model, byte for byte.  Still out of scope:
-a covariance (a Kalman filter), appearance features, re-identification, clamping a predicted box to the picture (the crop, the
-redaction, the blur and the drawing clip themselves).  `Tracker(..., assign="optimal")` replaces the greedy match -- repeatedly the pair
+a covariance (a Kalman filter) and clamping a predicted box to the picture (the crop, the redaction, the blur and the drawing clip
+themselves); appearance and re-identification are `ReId`'s (below).  `Tracker(..., assign="optimal")` replaces the greedy match -- repeatedly the pair
 of the largest IoU, which strands a detection where two faces pass each other -- by the maximum-weight assignment over the eligible
 pairs, `track_motion_assign_device` (csrc/yf_images_assign.h, `ptq.track_assign_match`); it runs on the 7176-byte state with or
 without `motion`.  `detect_tracked`, `detect_drawn`, `detect_redacted` and `detect_blurred`
@@ -65,6 +65,15 @@ over the steps of a clip, without the records leaving it: `TrackScore`, `score_t
 is what measures the tracker's settings against each other; the figures that exist are those of synthetic clips
 (profiles/track_score_bench.txt), none of labelled video.  Out of scope: IDF1, HOTA, fragmentations, more than 256 labelled objects per
 stream or 64 per frame.
+
+`ReId(streams)` is the second look at the picture behind a tracker: `describe_records_device` gives every reported box an appearance
+descriptor -- its region as an 8 x 8 grid of mean luma, a tiny template and not a learned embedding (csrc/yf_images_describe.h,
+`ptq.describe_u8`) -- and `reid_device` rewrites the tracker's ids, so that a track born while a lost one that looks the same is still
+remembered reports the lost one's id (csrc/yf_images_reid.h, `ptq.reid_step`): a face hidden for longer than max_misses steps keeps its
+identity, which no setting of the tracker alone achieves.  `detect_tracked`, `detect_drawn` and `evaluate_tracking` take `reid=`.  The
+stage takes any 64 bytes per record, so a recogniser's embedding quantised to uint8 can stand in for the template.  `REID_MAX_DISTANCE`
+is a choice made on synthetic textures (profiles/reid_bench.txt); nothing is measured on labelled video.  Out of scope: an id the
+tracker itself exchanged between two faces, an entry whose track the tracker still holds over, colour descriptors, learned embeddings.
 
 `fit="letterbox"` on `detect`, every `detect_*` call and `evaluate` replaces the stretch onto the square frame by what every mainstream
 YOLO trainer does: the picture resized with its aspect kept into a centred rectangle of the frame (`fit_of`), the rest padded with the
@@ -184,6 +193,27 @@ assert GT_TRACK_DTYPE.itemsize == 20 and SCORE_STATE_DTYPE.itemsize == SCORE_STA
 YF_SCORE_GT_CLIPPED, YF_SCORE_HYP_CLIPPED, YF_SCORE_GT_VOID, YF_SCORE_HYP_VOID = 1, 2, 4, 8      # the bits of a frame's status
 
 
+# appearance descriptors and re-identification (yf_face_desc, yf_reid_entry, yf_reid_state, yf_reid_params): an 8 x 8 grid of mean luma
+# per record, a table of 64 identities per stream
+class YfReidParams(ctypes.Structure):
+    _fields_ = [("max_distance", ctypes.c_int32), ("max_age", ctypes.c_int32), ("blend", ctypes.c_int32)]
+
+
+DESC_BYTES, REID_ENTRIES, REID_STATE_BYTES = 64, 64, 5128
+FACE_DESC_DTYPE = np.dtype([("flags", "<u4"), ("v", "u1", (DESC_BYTES,))])
+REID_ENTRY_DTYPE = np.dtype([("id", "<u4"), ("alias", "<u4"), ("seen", "<u4"), ("flags", "<u4"), ("v", "u1", (DESC_BYTES,))])
+REID_STATE_DTYPE = np.dtype([("clock", "<u4"), ("reserved", "<u4"), ("entry", REID_ENTRY_DTYPE, (REID_ENTRIES,))])
+assert FACE_DESC_DTYPE.itemsize == 68 and REID_ENTRY_DTYPE.itemsize == 80 and REID_STATE_DTYPE.itemsize == REID_STATE_BYTES
+assert ctypes.sizeof(YfReidParams) == 12
+YF_REID_CLIPPED, YF_REID_VOID = 1, 2           # the bits of a frame's status
+YF_REID_KNOWN, YF_REID_REIDENTIFIED, YF_REID_BORN = 1, 2, 3
+# the library's suggestion for ReId: A CHOICE MADE ON SYNTHETIC TEXTURES, between the largest same-face distance (62528) and the
+# smallest different-face distance (79244) that tools/reid_bench.py saw on its clips (profiles/reid_bench.txt) -- not a figure from
+# labelled video
+REID_MAX_DISTANCE = 70000
+REID_MAX_AGE, REID_BLEND = 300, 64              # ten seconds at 30 frames a second; a quarter of the new descriptor per frame: choices
+
+
 # a ground-truth box (yf_gt_box) and the result of average_precision_device (yf_eval_result)
 # where a picture lies in its letterboxed frame (yf_fit), and the two ways a picture becomes a frame
 FIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("width", "<i4"), ("height", "<i4")])
@@ -276,6 +306,11 @@ def _entries():
         "track_motion_assign_device": [vp, vp, cl, cl, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp],
         # d_out, d_info, d_out_counts, out_cap, d_gt, d_gt_counts, gt_cap, streams, steps, layout, score_iou, d_state, d_match, d_status, stream
         "score_tracks_device": [vp, vp, vp, ci, vp, vp, ci, cl, cl, ci, cd, vp, vp, vp, vp],
+        # d_pixels, pixels_bytes, format, d_images, d_dets, d_counts, n, cap, margin_permille, flags, d_desc, d_first, d_status, stream
+        "describe_records_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, vp, vp, vp, vp],
+        "describe_records_yuv_device": [vp, cs, ci, vp, vp, vp, cl, ci, ci, ci, vp, vp, vp, vp],
+        # d_info, d_out_counts, d_desc, out_cap, streams, steps, layout, params, d_state, d_info_out, d_what, d_status, stream
+        "reid_device": [vp, vp, vp, ci, cl, cl, ci, vp, vp, vp, vp, vp, vp],
         # letterboxed frames: d_pixels, pixels_bytes, format, d_images, n, [out_hw,] pad, d_frames, d_status, stream
         "prepare_fit_ragged_device": ragged + [ci, ci, vp, vp, vp],
         "prepare_fit_yuv_ragged_device": ragged + [ci, ci, vp, vp, vp],
@@ -326,6 +361,8 @@ def load():
     lib.yf_images_track_motion_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_score_state_bytes.restype = ctypes.c_size_t
     lib.yf_images_score_state_bytes.argtypes = [ctypes.c_long]
+    lib.yf_images_reid_state_bytes.restype = ctypes.c_size_t
+    lib.yf_images_reid_state_bytes.argtypes = [ctypes.c_long]
     lib.yf_images_score_summary.restype = ctypes.c_int
     lib.yf_images_score_summary.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
     lib.yf_images_gather_tiles_workspace.restype = ctypes.c_size_t
@@ -1433,6 +1470,114 @@ class Tracker:
         return d_out, d_info, d_out_counts, d_status
 
 
+def describe_records_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_desc, d_first, d_status, margin_permille=0,
+                            square=False, stream=None):
+    """An appearance descriptor per record of a batch of packed pictures (yf_images_describe_records_device): d_images IMAGE_DTYPE[n],
+    d_dets yf_det[n][cap], d_counts int32[n]; d_pixels is only read.  d_desc FACE_DESC_DTYPE[n][cap] is written in the slots of the first
+    min(max(count, 0), cap) records of each frame: flags 1 and the 8 x 8 grid of the region's mean luma, or 68 zero bytes for a record
+    without a region, with a region narrower or lower than 8 pixels, or in an invalid picture.  d_first int32[n + 1] and d_status
+    int32[n] (1: the picture's descriptor is invalid) are written.  A tiny template, not a learned embedding.  The definition:
+    csrc/yf_images_describe.h, ptq.describe_u8."""
+    _call("describe_records_device", n, d_pixels, pixels_bytes, _packed_code(fmt, "describe_records_device"), d_images, d_dets, d_counts, n,
+          cap, margin_permille, YF_CROP_SQUARE if square else 0, d_desc, d_first, d_status, stream)
+
+
+def describe_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_counts, n, cap, d_desc, d_first, d_status, margin_permille=0,
+                                square=False, stream=None):
+    """`describe_records_device` for NV12 / NV21 surfaces (yf_images_describe_records_yuv_device): d_images YUV_IMAGE_DTYPE[n]; only the
+    Y plane is read.  ptq.describe_yuv420sp."""
+    _call("describe_records_yuv_device", n, d_pixels, pixels_bytes, _yuv_code(fmt), d_images, d_dets, d_counts, n, cap, margin_permille,
+          YF_CROP_SQUARE if square else 0, d_desc, d_first, d_status, stream)
+
+
+def reid_state_bytes(streams):
+    """The bytes of the re-identification state of `streams` streams (yf_images_reid_state_bytes): 5128 each.  All zero is the empty
+    state."""
+    return int(load().yf_images_reid_state_bytes(streams))
+
+
+def reid_device(d_info, d_out_counts, d_desc, out_cap, streams, steps, layout, params, d_state, d_info_out, d_what=None, d_status=None,
+                stream=None):
+    """The ids of a tracker's output rewritten by appearance (yf_images_reid_device): d_info TRACK_INFO_DTYPE[n][out_cap] and d_out_counts
+    int32[n] as a tracker wrote them, d_desc FACE_DESC_DTYPE[n][out_cap] the descriptors of its boxes, n = streams * steps frames in
+    `layout`; params = (max_distance, max_age, blend); d_state the streams' state (`reid_state_bytes`, read and written).  d_info_out
+    (may be d_info) gets every record with its id replaced: a track born while a lost one that looks the same (distance <=
+    max_distance, lost for at most max_age steps) is in the table reports the lost one's id.  The records keep the tracker's order.
+    d_what int32[n][out_cap] or None: 0 void, 1 known, 2 re-identified, 3 born; d_status int32[n] or None.  The definition:
+    csrc/yf_images_reid.h, ptq.reid_step.  Returns n."""
+    lib = load()
+    p = YfReidParams(int(params[0]), int(params[1]), int(params[2]))
+    rc = lib.yf_images_reid_device(d_info, d_out_counts, d_desc, out_cap, streams, steps, _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT),
+                                   ctypes.byref(p), d_state, d_info_out, d_what, d_status, stream)
+    if rc != streams * steps or rc < 0:
+        raise ImagesError(f"yf_images_reid_device: {(lib.yf_images_last_error_text() or b'').decode()} (returned {rc})")
+    return rc
+
+
+class ReId:
+    """The re-identification state of `streams` video streams on the device (csrc/yf_images_reid.h): the stage behind a `Tracker` that
+    lets a lost track keep its id.  `update` describes the tracker's reported boxes from the pictures where they lie and rewrites the
+    ids on the same stream; `reset` empties every stream (an all-zero state is the empty state); `states` downloads them.
+    max_distance: the largest distance (mean-removed sum of absolute differences of two 8 x 8 luma grids, times 64) at which a new
+    track takes over a lost identity -- the default `REID_MAX_DISTANCE` is a choice made on synthetic textures
+    (profiles/reid_bench.txt), not a figure from labelled video.  max_age: the steps a lost identity is remembered.  blend: how much of
+    a new descriptor enters the stored one per frame, in 1/256.  margin, square: the region of a box, as in `detect_chips`."""
+
+    def __init__(self, streams, max_distance=None, max_age=REID_MAX_AGE, blend=REID_BLEND, margin=0.0, square=False, device=None):
+        import torch
+        if int(streams) < 1:
+            raise ValueError(f"streams {streams!r}: at least 1")
+        max_distance = REID_MAX_DISTANCE if max_distance is None else int(max_distance)
+        if max_distance < 0 or int(max_age) < 0 or not 0 <= int(blend) <= 256:
+            raise ValueError(f"max_distance {max_distance!r}, max_age {max_age!r}: at least 0; blend {blend!r}: 0 to 256")
+        self.streams, self.params = int(streams), (max_distance, int(max_age), int(blend))
+        self.permille, self.square = _permille(margin), bool(square)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.d_state = torch.zeros((self.streams, REID_STATE_BYTES), dtype=torch.uint8, device=self.device)
+
+    def reset(self):
+        """every stream empty again"""
+        self.d_state.zero_()
+
+    def update(self, d_px, nbytes, fmt, d_pictures, d_out, d_info, d_out_counts, steps, layout="time", with_what=False, stream=None):
+        """The next `steps` frames of every stream: d_px / nbytes / d_pictures the pictures and their descriptors on the device as the
+        crop entries take them, d_out, d_info, d_out_counts a `Tracker.update`'s output for them.  d_info is REWRITTEN in place.  ->
+        (d_desc uint8 [n, out_cap, 68], d_what int32 [n, out_cap] or None, d_status int32 [n]: the describe's) on the stream given
+        (default: the device's current one), not synchronised."""
+        import torch
+        n, out_cap = self.streams * int(steps), d_out.shape[1]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        d_desc = torch.empty((n, out_cap, FACE_DESC_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        d_first = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+        d_status = torch.empty(n, dtype=torch.int32, device=self.device)
+        d_what = torch.empty((n, out_cap), dtype=torch.int32, device=self.device) if with_what else None
+        describe = describe_records_yuv_device if is_yuv(fmt) else describe_records_device
+        describe(d_px.data_ptr(), nbytes, fmt, d_pictures.data_ptr(), d_out.data_ptr(), d_out_counts.data_ptr(), n, out_cap, d_desc.data_ptr(),
+                 d_first.data_ptr(), d_status.data_ptr(), margin_permille=self.permille, square=self.square, stream=stream)
+        reid_device(d_info.data_ptr(), d_out_counts.data_ptr(), d_desc.data_ptr(), out_cap, self.streams, int(steps), layout, self.params,
+                    self.d_state.data_ptr(), d_info.data_ptr(), None if d_what is None else d_what.data_ptr(), None, stream)
+        return d_desc, d_what, d_status
+
+    def states(self):
+        """-> REID_STATE_DTYPE [streams], after a synchronise (the download)"""
+        return self.d_state.cpu().numpy().view(REID_STATE_DTYPE).reshape(self.streams)
+
+
+def _reid_after(reid, tracker, b, fmt, d_out, d_info, d_out_counts, steps, layout):
+    """`reid` (a `ReId` or None) behind `tracker` on the staged batch b: the tracker's output described from the pictures where they lie
+    and its ids rewritten in d_info, on b's stream"""
+    if reid is None:
+        return
+    _check_reid(reid, tracker)
+    reid.update(b.d_px, b.nbytes, fmt, b.d_pictures, d_out, d_info, d_out_counts, steps, layout, stream=b.stream.cuda_stream)
+
+
+def _check_reid(reid, tracker):
+    if reid is not None and (reid.streams != tracker.streams or reid.device != tracker.device):
+        raise ValueError(f"reid: {reid.streams} streams on {reid.device}, the tracker has {tracker.streams} on {tracker.device}")
+
+
 def _track_tuples(d_out, d_info, d_out_counts, n):
     """a tracker's output of n frames -> per frame the list of (id, x1, y1, x2, y2, conf, hits, misses); after a synchronise"""
     out = d_out.cpu().numpy().view(binding.DET_DTYPE).reshape(n, -1)
@@ -1442,25 +1587,31 @@ def _track_tuples(d_out, d_info, d_out_counts, n):
              for d, i in zip(out[f, :counts[f]], info[f, :counts[f]])] for f in range(n)]
 
 
-def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8", fit="stretch", pad=114, interp="linear"):
+def detect_tracked(network, images, tracker, steps, layout="time", fmt="bgr", iou_threshold=0.4, size=56, dtype="int8", fit="stretch", pad=114, interp="linear",
+                   reid=None):
     """`detect` with the suppression for the next `steps` frames of the `tracker`'s streams, and the kept boxes associated with its track
     state on the same stream: `images` holds tracker.streams * steps pictures, frame t of stream s at index t * streams + s (layout
     "time": one frame of every camera per step) or s * steps + t ("stream": a clip per stream).  fmt, iou_threshold (not None: the tracker
     takes a frame's records in descending confidence), size, dtype, fit, pad as in `detect`; the tracker's device is used.
     Returns per frame a list of (id, x1, y1, x2, y2, conf, hits, misses) in ascending id: the tracks reported for that frame, a held-over
     one (misses > 0) with the box it was last seen at -- with a `Tracker(motion=...)`, the box its filter moved on.  The tracker carries on from there at the next call.  The definition is the
-    library's own: csrc/yf_images_track.h, restated as `ptq.track_step`."""
+    library's own: csrc/yf_images_track.h, restated as `ptq.track_step`.
+    `reid`: a `ReId` of the tracker's streams and device; the reported boxes are then described from the pictures where they lie and the
+    ids rewritten on the same stream (csrc/yf_images_reid.h): a face that returns after its track died reports its old id.  The tuples
+    carry the rewritten ids and keep the tracker's order, so they are then no longer in ascending id."""
     steps = int(steps)
     if steps < 0 or len(images) != tracker.streams * steps:
         raise ValueError(f"{len(images)} images: {tracker.streams} streams x {steps} steps")
     if iou_threshold is None:
         raise ValueError("iou_threshold None: the tracker takes suppressed records")
     _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+    _check_reid(reid, tracker)
     n = len(images)
     if n == 0:
         return []
     b = _stage(network, images, fmt, None, tracker.device.index, iou_threshold, size, dtype, fit=fit, pad=pad, interp=interp)
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=b.stream.cuda_stream)
+    _reid_after(reid, tracker, b, fmt, d_out, d_info, d_out_counts, steps, layout)
     b.stream.synchronize()
     return _track_tuples(d_out, d_info, d_out_counts, n)
 
@@ -1562,14 +1713,15 @@ class TrackScore:
 
 
 def evaluate_tracking(network, images, ground_truths, tracker, steps, layout="time", score_iou=0.5, score=None, fmt="bgr", iou_threshold=0.4,
-                      size=56, dtype="int8", fit="stretch", pad=114, interp="linear"):
+                      size=56, dtype="int8", fit="stretch", pad=114, interp="linear", reid=None):
     """`detect_tracked` scored against labelled identities: the next `steps` frames of the `tracker`'s streams are detected, suppressed
     and associated as there (`images`, `layout`, fmt, iou_threshold, size, dtype, fit, pad, interp: as there), and what the tracker
     reports is scored on the same stream against `ground_truths` -- per frame, indexed as `images`, a list of (id, x1, y1, x2, y2) in that
     picture's pixels (`pack_track_truth`) -- without the records leaving the device; one synchronise at the end.  `score`: a `TrackScore`
     of the tracker's streams and device that carries the score across calls (its score_iou is used); None scores this call alone at
     `score_iou`.  Returns the summary (`TrackScore.summary`): the counters, objects, mostly_tracked, mostly_lost, mota, motp.  The
-    definition: csrc/yf_images_score.h, restated as `ptq.track_score_step`."""
+    definition: csrc/yf_images_score.h, restated as `ptq.track_score_step`.  `reid`: as in `detect_tracked`; the rewritten ids are
+    scored."""
     steps = int(steps)
     if steps < 0 or len(images) != tracker.streams * steps:
         raise ValueError(f"{len(images)} images: {tracker.streams} streams x {steps} steps")
@@ -1578,6 +1730,7 @@ def evaluate_tracking(network, images, ground_truths, tracker, steps, layout="ti
     if iou_threshold is None:
         raise ValueError("iou_threshold None: the tracker takes suppressed records")
     _code(TRACK_LAYOUTS, layout, LAYOUT_WHAT)
+    _check_reid(reid, tracker)
     if score is None:
         score = TrackScore(tracker.streams, score_iou, tracker.device.index)
     elif score.streams != tracker.streams or score.device != tracker.device:
@@ -1593,6 +1746,7 @@ def evaluate_tracking(network, images, ground_truths, tracker, steps, layout="ti
         d_gt = torch.from_numpy(gt.view(np.uint8).reshape(n, gt.shape[1], GT_TRACK_DTYPE.itemsize)).to(b.device)
         d_gt_counts = torch.from_numpy(gt_counts).to(b.device)
     d_out, d_info, d_out_counts, d_status = tracker.update(b.d_dets, b.d_counts, steps, layout, stream=s)
+    _reid_after(reid, tracker, b, fmt, d_out, d_info, d_out_counts, steps, layout)
     score.update(d_out, d_info, d_out_counts, d_gt, d_gt_counts, steps, layout, stream=s)
     b.stream.synchronize()
     return score.summary()
@@ -1637,7 +1791,8 @@ def draw_records_yuv_device(d_pixels, pixels_bytes, fmt, d_images, d_dets, d_cou
 
 
 def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=None, iou_threshold=0.4, size=56, dtype="int8", tile=None,
-                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None, fit="stretch", pad=114, interp="linear"):
+                 stride=None, device=None, tracker=None, steps=None, layout="time", palette=None, fit="stretch", pad=114, interp="linear",
+                 reid=None):
     """`detect` (with `tile`: `detect_tiled`, whose `tile` and `stride` these are), and the outline of every kept box drawn into its picture
     on the GPU, on the same stream, in the pixels that are already there -- the last line of the reference's scripts,
     cv2.rectangle(img, (x1, y1), (x2, y2), (0, 0, 255), 2), which the defaults reproduce: `colour` (R, G, B) whatever the byte order of
@@ -1648,7 +1803,8 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
     many as the images make; iou_threshold must not be None and the tracker's device is used) the tracker is updated with the kept boxes
     and the REPORTED TRACKS are drawn, held-over ones included, each in palette[id % len(palette)]: a face keeps its colour over the
     frames.  `palette`: up to 256 (R, G, B) -- (Y, U, V) -- triples; None: `TRACK_PALETTE`.  Where outlines overlap, the later record
-    (the higher track id) shows.
+    (the higher track id) shows.  `reid` (with a tracker): as in `detect_tracked`; the descriptors are taken from the pictures before
+    anything is drawn into them, and the colours follow the rewritten ids.
     Returns (pictures, boxes) as `detect_redacted` does: the pictures in the caller's shapes, new arrays, and `detect`'s boxes; with a
     tracker (pictures, tracks), `detect_tracked`'s tuples."""
     half = int(half)
@@ -1662,6 +1818,9 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
         if not 1 <= len(table) <= DRAW_MAX_PALETTE:
             raise ValueError(f"palette: 1 to {DRAW_MAX_PALETTE} colours")
         device = tracker.device.index
+        _check_reid(reid, tracker)
+    elif reid is not None:
+        raise ValueError("reid: only with a tracker")
     if n == 0:
         return [], []
     import torch
@@ -1678,6 +1837,7 @@ def detect_drawn(network, images, half=1, colour=(255, 0, 0), fmt="bgr", cap=Non
              d_first.data_ptr(), d_status.data_ptr(), half=half, colour=colour_code, stream=s)
     else:
         d_out, d_info, d_out_counts, _ = tracker.update(b.d_dets, b.d_counts, steps, layout, cap=b.cap, stream=s)
+        _reid_after(reid, tracker, b, fmt, d_out, d_info, d_out_counts, steps, layout)
         d_palette = torch.tensor(table, dtype=torch.int32).to(b.device)
         # the keys are the id fields of the info rows, as they lie: TRACK_INFO_DTYPE's first field, one row per output slot
         draw(b.d_px.data_ptr(), b.nbytes, fmt, b.d_pictures.data_ptr(), d_out.data_ptr(), d_out_counts.data_ptr(), n, d_out.shape[1],

@@ -1096,3 +1096,135 @@ def track_score_summary(states):
     out["mota"] = 1.0 - float(errors) / float(out["gt"]) if out["gt"] else 0.0
     out["motp"] = (float(out["overlap"]) / float(out["matches"])) / 1073741824.0 if out["matches"] else 0.0
     return out
+
+
+# ---- appearance descriptors and re-identification (csrc/yf_images_describe.h, csrc/yf_images_reid.h), in plain Python integers ----
+DESC_GRID, DESC_BYTES = 8, 64
+REID_ENTRIES = 64
+REID_CLIPPED, REID_VOID = 1, 2
+REID_KNOWN, REID_REIDENTIFIED, REID_BORN = 1, 2, 3
+_LUMA = {"bgr": (29, 150, 77), "bgra": (29, 150, 77), "rgb": (77, 150, 29), "rgba": (77, 150, 29)}
+
+
+def _describe_cells(region, cell_value):
+    """the 64 bytes of a region (x0, y0, width, height), or None for none or one narrower or lower than 8: cell c of a side holds
+    [c * side // 8, (c + 1) * side // 8); cell_value(x range, y range, cnt) is the cell's byte"""
+    if region is None or region[2] < DESC_GRID or region[3] < DESC_GRID:
+        return None
+    x0, y0, w, h = region
+    out = []
+    for cy in range(DESC_GRID):
+        ya, yb = cy * h // DESC_GRID, (cy + 1) * h // DESC_GRID
+        for cx in range(DESC_GRID):
+            xa, xb = cx * w // DESC_GRID, (cx + 1) * w // DESC_GRID
+            out.append(cell_value(range(x0 + xa, x0 + xb), range(y0 + ya, y0 + yb), (xb - xa) * (yb - ya)))
+    return out
+
+
+def describe_u8(picture_hwc, box, fmt, margin_permille=0, square=False):
+    """The appearance descriptor of `box` = (x1, y1, x2, y2) in a packed picture (uint8 [H, W, 3 or 4], fmt "bgr", "rgb", "bgra" or
+    "rgba"), as csrc/yf_images_describe.h states it: the 64 bytes v[cy * 8 + cx], or None for an invalid descriptor (no region, or a
+    region narrower or lower than 8 pixels).  The region is `crop_region`'s, cut into 8 x 8 cells; a cell's byte is its mean luma,
+    (S + 128 cnt) // (256 cnt) with S the sum over its pixels of 77 R + 150 G + 29 B; a fourth channel is never read.  A tiny template,
+    not a learned embedding."""
+    wts = _LUMA[fmt.lower()]
+    img = [[tuple(int(c) for c in px[:3]) for px in row] for row in np.asarray(picture_hwc, np.uint8).tolist()]
+    region = crop_region(box, len(img[0]), len(img), margin_permille, square)
+
+    def luma(xs, ys, cnt):
+        s = sum(wts[0] * img[y][x][0] + wts[1] * img[y][x][1] + wts[2] * img[y][x][2] for y in ys for x in xs)
+        return (s + 128 * cnt) // (256 * cnt)
+    return _describe_cells(region, luma)
+
+
+def describe_yuv420sp(y, box, margin_permille=0, square=False):
+    """`describe_u8` for an NV12 / NV21 surface: only the Y plane (uint8 [H, W]) is read; a cell's byte is (sum of Y + cnt // 2) //
+    cnt."""
+    plane = np.asarray(y, np.uint8).tolist()
+    region = crop_region(box, len(plane[0]), len(plane), margin_permille, square)
+    return _describe_cells(region, lambda xs, ys, cnt: (sum(plane[yy][x] for yy in ys for x in xs) + cnt // 2) // cnt)
+
+
+def reid_distance(a, b):
+    """The distance of two descriptors of 64 bytes: sum_i |(64 a_i - A) - (64 b_i - B)| with A, B the byte sums -- the mean-removed sum
+    of absolute differences, at most 64 * 64 * 255."""
+    a, b = [int(v) for v in a], [int(v) for v in b]
+    assert len(a) == DESC_BYTES and len(b) == DESC_BYTES
+    sa, sb = sum(a), sum(b)
+    return sum(abs((64 * x - sa) - (64 * y - sb)) for x, y in zip(a, b))
+
+
+def reid_empty_state():
+    """The empty state of one stream: what 5128 zero bytes are.  {"clock", "reserved", "entries": 64 of {"id", "alias", "seen", "flags",
+    "v": 64 bytes}}."""
+    return {"clock": 0, "reserved": 0, "entries": [{"id": 0, "alias": 0, "seen": 0, "flags": 0, "v": [0] * DESC_BYTES} for _ in range(REID_ENTRIES)]}
+
+
+def _reid_meet(entry, new, blend):
+    if entry["flags"] & 1:
+        entry["v"] = [(o * (256 - blend) + n * blend + 128) >> 8 for o, n in zip(entry["v"], new)]
+    else:
+        entry["v"] = list(new)
+        entry["flags"] |= 1
+
+
+def reid_step(state, records, descs, params, count=None, out_cap=None):
+    """One step of the re-identification -- one stream, one frame -- as csrc/yf_images_reid.h states it.  `state`: as `reid_empty_state`
+    gives it (not changed; the new state is returned).  `records`: the tracker's info rows (id, hits, misses, age) of the frame in the
+    order they lie.  `descs`: per record its 64 descriptor bytes, or None for an invalid one.  `params` = (max_distance, max_age, blend).
+    `count`, `out_cap`: the frame's count and the rows' capacity (default: the length); the first m = min(max(count, 0), out_cap, 64)
+    records count.
+    -> (state, ids, what, status): per record that counts its new id and 0 void / 1 known / 2 re-identified / 3 born; status bit 0: a
+    count above min(out_cap, 64), bit 1: a record of tracker id 0."""
+    max_distance, max_age, blend = (int(v) for v in params)
+    count = len(records) if count is None else int(count)
+    out_cap = len(records) if out_cap is None else int(out_cap)
+    lim = min(out_cap, REID_ENTRIES)
+    m = min(max(count, 0), lim)
+    status = REID_CLIPPED if count > lim else 0
+    recs = [tuple(int(v) for v in r) for r in records[:m]]
+    descs = [None if d is None else [int(v) for v in d] for d in descs[:m]]
+    if any(r[0] == 0 for r in recs):
+        status |= REID_VOID
+    entries = [dict(e, v=list(e["v"])) for e in state["entries"]]
+    now = (state["clock"] + 1) & 0xFFFFFFFF
+    ids, what, bound = [0] * m, [0] * m, [False] * REID_ENTRIES
+    # bind
+    for r, (tid, _, misses, _) in enumerate(recs):
+        if tid == 0:
+            continue
+        e = next((k for k, en in enumerate(entries) if en["id"] != 0 and en["alias"] == tid), None)
+        if e is None:
+            continue
+        bound[e], what[r], ids[r] = True, REID_KNOWN, entries[e]["id"]
+        entries[e]["seen"] = now
+        if misses == 0 and descs[r] is not None:
+            _reid_meet(entries[e], descs[r], blend)
+    # expire
+    for k, en in enumerate(entries):
+        if en["id"] != 0 and not bound[k] and ((now - en["seen"]) & 0xFFFFFFFF) > max_age:
+            entries[k] = {"id": 0, "alias": 0, "seen": 0, "flags": 0, "v": [0] * DESC_BYTES}
+    # re-identify
+    rcand = [r for r in range(m) if what[r] == 0 and recs[r][0] != 0 and recs[r][2] == 0 and descs[r] is not None]
+    ecand = [k for k, en in enumerate(entries) if not bound[k] and en["id"] != 0 and en["flags"] & 1] if rcand else []
+    pairs = sorted((reid_distance(descs[r], entries[k]["v"]), r, k) for r in rcand for k in ecand)
+    for d, r, k in pairs:                                           # only a taken entry's descriptor changes: the distances hold
+        if d > max_distance:
+            break
+        if what[r] != 0 or bound[k]:
+            continue
+        entries[k]["alias"], entries[k]["seen"] = recs[r][0], now
+        _reid_meet(entries[k], descs[r], blend)
+        bound[k], what[r], ids[r] = True, REID_REIDENTIFIED, entries[k]["id"]
+    # births
+    for r in range(m):
+        if what[r] != 0 or recs[r][0] == 0:
+            continue
+        e = next((k for k, en in enumerate(entries) if en["id"] == 0), None)
+        if e is None:
+            ages = [((now - en["seen"]) & 0xFFFFFFFF, -k) for k, en in enumerate(entries) if not bound[k]]
+            e = -max(ages)[1]
+        entries[e] = {"id": recs[r][0], "alias": recs[r][0], "seen": now, "flags": 0 if descs[r] is None else 1,
+                      "v": [0] * DESC_BYTES if descs[r] is None else list(descs[r])}
+        bound[e], what[r], ids[r] = True, REID_BORN, recs[r][0]
+    return {"clock": now, "reserved": state.get("reserved", 0), "entries": entries}, ids, what, status
